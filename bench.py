@@ -56,7 +56,7 @@ def available_cpus():
 
 
 def _getenv_c(name):
-    """The C environment (what HIP and cvo_process_hint_hw_queues see; os.environ is Python's start-up snapshot)."""
+    """The C environment (what HIP and cvo_ctx_create see; os.environ is Python's start-up snapshot)."""
     import ctypes
     g = ctypes.CDLL(None).getenv
     g.restype = ctypes.c_char_p
@@ -66,6 +66,25 @@ def _getenv_c(name):
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(out_dir, res, poses, stat):
+    """What one step hands its caller, as .npy files (float32 / float64, a few KB): the all-gathered pose table and status
+    of every pair, and this rank's AlignResult fields (its shard: every pair when the run has one rank).  Timings are left
+    out; everything else depends only on the inputs, which the seeded cases make identical from run to run."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "poses": poses.cpu().numpy().astype(np.float32),                           # (pairs, 16): column-major 4 x 4
+        "status": stat.cpu().numpy().astype(np.float64),                           # (pairs,): cvo_align_batch return code
+        "transform": np.stack([r.transform for r in res]).astype(np.float32),     # (shard, 4, 4)
+        "iterations": np.array([r.iterations for r in res], np.float64),
+        "final_ell": np.array([r.final_ell for r in res], np.float64),
+        "final_num_neighbors": np.array([r.final_num_neighbors for r in res], np.float64),
+        "ret": np.array([r.ret for r in res], np.float64),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"[bench] outputs of the last timed step written to {out_dir}: " + ", ".join(f"{k} {v.shape}" for k, v in arrays.items()))
 
 
 def main():
@@ -90,16 +109,19 @@ def main():
     ap.add_argument("--no-pipeline", action="store_true", help="skip the PCIe-inclusive pipeline leg")
     ap.add_argument("--no-extra-legs", action="store_true",
                     help="skip the early-phase, 20k, colour / semantic batch and batch-queue legs (they run after the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (poses and per-pair results) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
     import cases
     from unified_cvo_amd import CvoGPU, sharding, _capi
-    # The hardware-queue contract lives in the library (include/cvo_hip.h, cvo_ctx_advice): _capi.lib() calls
-    # cvo_process_hint_hw_queues(), which puts GPU_MAX_HW_QUEUES=8 into the environment unless the caller chose a value.  HIP reads the variable at the process's
-    # first HIP call, so the library is loaded HERE - after `import torch` (the process must end up with ONE HIP runtime:
-    # torch's), before torch touches the GPU; the bench line reports what the context found (config.hardware_queues).
+    # The library is loaded HERE - after `import torch` (the process must end up with ONE HIP runtime: torch's), before
+    # torch touches the GPU.  It leaves the process's hardware-queue setting as it finds it; the bench line reports what
+    # the context found (config.hardware_queues, include/cvo_hip.h).
     _capi.lib()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -190,6 +212,8 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     elapsed = sharding.max_over_ranks(elapsed, coll_dev)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, poses, stat)
     if CLOCK_EXTRA_STEP:  # outside the timed region: the instrumented kernels (device clock per launch)
         step(clocked=True)
         step(clocked=True)

@@ -153,11 +153,9 @@ const char* cvo_last_error(const cvo_ctx* ctx);
 /* Hardware queues.  A batch (cvo_align_batch, CvoGPUSharded) runs on four sub-batch HIP streams that must sit on four
  * different hardware queues; HIP deals streams onto GPU_MAX_HW_QUEUES queues (default 4, read once at the process's
  * first HIP call) and the upload stream, RCCL and the host application bring streams of their own.
- * cvo_process_hint_hw_queues() puts GPU_MAX_HW_QUEUES=8 into the environment unless the variable is already set
- * (CVO_NO_HW_QUEUE_HINT=1 disables it) and returns the value in force: a PROCESS-WIDE side effect, which is why it is
- * an explicit call - make it before the process's first HIP call and before other threads read the environment
- * (setenv is not thread-safe).  The Python wrapper and cvo::CvoGPU's constructor call it; CVO_HW_QUEUE_HINT_AT_LOAD=1
- * makes the library do it when it is loaded.  If HIP was initialised earlier, or the variable says less than 8,
+ * cvo_process_hint_hw_queues() returns the number of hardware queues in force (4 when the variable is unset); the
+ * library never changes it: that is the host's (or the machine's) choice, made before the process's first HIP call.
+ * If the variable says less than 8,
  * cvo_ctx_create leaves an advisory text in cvo_ctx_advice() ("" = nothing to report) and prints it once per process
  * on stderr (CVO_QUIET=1 silences the print).  Nothing but speed depends on it. */
 int cvo_process_hint_hw_queues(void);

@@ -57,11 +57,12 @@ ORDER = ["valu_f32", "valu_f64", "valu_int", "valu_move", "valu_trans", "salu", 
 
 def device_asm(extra_flags):
     flags = [f for f in B.HIPCC_FLAGS if f not in ("-shared", "-fPIC")]
-    out = os.path.join(tempfile.gettempdir(), "_cvo_isa.s")
-    cmd = [B._hipcc()] + flags + extra_flags + ["-I", os.path.join(ROOT, "include"), "--cuda-device-only", "-S", "-o", out,
-                                                B.sources()[0]]
-    subprocess.run(cmd, check=True, capture_output=True)
-    return open(out).read().splitlines()
+    with tempfile.TemporaryDirectory() as d:  # (private: a fixed name in the shared temp dir can belong to another user)
+        out = os.path.join(d, "_cvo_isa.s")
+        cmd = [B._hipcc()] + flags + extra_flags + ["-I", os.path.join(ROOT, "include"), "--cuda-device-only", "-S", "-o", out,
+                                                    B.sources()[0]]
+        subprocess.run(cmd, check=True, capture_output=True)
+        return open(out).read().splitlines()
 
 
 def kernels(lines):

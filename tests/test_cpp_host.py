@@ -39,8 +39,8 @@ def test_cpp_defaults_match_python_defaults():
 
 
 def test_cpp_reader_matches_python_reader_on_config_files():
-    files = sorted(glob.glob(os.path.join(cases.CONFIGS, "*.yaml"))) + sorted(glob.glob("/root/reference/cvo_params/*.yaml"))
-    assert len(files) >= 4
+    files = sorted(glob.glob(os.path.join(cases.CONFIGS, "*.yaml"))) + sorted(glob.glob(os.path.join(cases.GOLDEN, "cvo_params", "*.yaml")))
+    assert len(files) == 20
     for path in files:
         kv, warns = _dump(path)
         with warnings.catch_warnings():
@@ -361,37 +361,49 @@ def test_shard_plan_partition_and_gather_arithmetic():
         assert line.endswith("counts=" + ",".join(map(str, counts)))
 
 
-def test_library_load_sets_the_hardware_queue_hint():
-    """The hardware-queue contract (include/cvo_hip.h, cvo_ctx_advice): loading the library puts GPU_MAX_HW_QUEUES=8 into
-    the process environment - HIP reads it at the process's first HIP call - unless the variable is already set or
-    CVO_NO_HW_QUEUE_HINT is.  No GPU needed: nothing here calls HIP."""
-    code = ("import ctypes, os, sys; sys.path.insert(0, %r); from unified_cvo_amd import _capi; _capi.lib(); "
-            "g = ctypes.CDLL(None).getenv; g.restype = ctypes.c_char_p; print(g(b'GPU_MAX_HW_QUEUES'))" % cases.ROOT)
-    env = {k: v for k, v in os.environ.items() if k not in ("GPU_MAX_HW_QUEUES", "CVO_NO_HW_QUEUE_HINT")}
-    run = lambda e: subprocess.check_output([sys.executable, "-c", code], env=e, text=True).strip()  # noqa: E731
-    assert run(env) == "b'8'"
-    assert run(dict(env, GPU_MAX_HW_QUEUES="3")) == "b'3'"          # an explicit choice is left alone
-    assert run(dict(env, CVO_NO_HW_QUEUE_HINT="1")) == "None"
+def test_library_load_leaves_the_environment_alone():
+    """The hardware-queue contract (include/cvo_hip.h, cvo_ctx_advice): loading the library and asking it for the hardware
+    queues in force (cvo_process_hint_hw_queues) change nothing in the process environment - the queue count HIP reads at
+    the process's first HIP call is the host's choice.  No GPU needed: nothing here calls HIP."""
+    code = ("import ctypes, sys; sys.path.insert(0, %r)\n"
+            "from unified_cvo_amd import _capi\n"
+            "def env():\n"
+            "    e, out = ctypes.POINTER(ctypes.c_char_p).in_dll(ctypes.CDLL(None), 'environ'), []\n"
+            "    while e[len(out)]: out.append(e[len(out)])\n"
+            "    return sorted(out)\n"
+            "before = env()\n"
+            "n = _capi.lib().cvo_process_hint_hw_queues()\n"
+            "print(env() == before, n)" % cases.ROOT)
+    same, n = subprocess.check_output([sys.executable, "-c", code], text=True).split()
+    assert same == "True" and int(n) >= 1
 
 
 @pytest.mark.gpu
 def test_hardware_queue_advice_channel():
-    """cvo_ctx_advice: silent when the process has 8 hardware queues, a text (and one stderr line) below that."""
-    code = ("import sys; sys.path.insert(0, %r); from unified_cvo_amd import CvoGPU; print('ADVICE[' + CvoGPU().advice() + ']')"
-            % cases.ROOT)
-    env = {k: v for k, v in os.environ.items() if k not in ("GPU_MAX_HW_QUEUES", "CVO_NO_HW_QUEUE_HINT", "CVO_QUIET")}
-    ok = subprocess.run([sys.executable, "-c", code], env=env, text=True, capture_output=True)
-    assert "ADVICE[]" in ok.stdout and "[cvo] advice" not in ok.stderr          # the load-time hint did its job
-    low = subprocess.run([sys.executable, "-c", code], env=dict(env, GPU_MAX_HW_QUEUES="2"), text=True, capture_output=True)
-    assert "ADVICE[GPU_MAX_HW_QUEUES is 2" in low.stdout and "[cvo] advice: GPU_MAX_HW_QUEUES is 2" in low.stderr
+    """cvo_ctx_advice: silent when the process has 8 hardware queues, a text (and one stderr line unless CVO_QUIET is set)
+    below that.  The child processes inherit this process's hardware-queue setting; cvo_process_hint_hw_queues reports it."""
+    code = ("import sys; sys.path.insert(0, %r); from unified_cvo_amd import CvoGPU, _capi; "
+            "n = _capi.lib().cvo_process_hint_hw_queues(); print('N[%%d]ADVICE[%%s]' %% (n, CvoGPU().advice()))" % cases.ROOT)
+    env = {k: v for k, v in os.environ.items() if k != "CVO_QUIET"}
+    r = subprocess.run([sys.executable, "-c", code], env=env, text=True, capture_output=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    n = int(r.stdout.split("N[")[1].split("]")[0])
+    text = r.stdout.split("ADVICE[")[1].rsplit("]", 1)[0]
+    if n >= 8:
+        assert text == "" and "[cvo] advice" not in r.stderr
+    else:
+        assert (f" is {n}: batches run on four sub-batch streams" in text or "is unset (HIP's default: 4)" in text), text
+        assert r.stderr.count("[cvo] advice: ") == 1 and "[cvo] advice: " + text in r.stderr
+        quiet = subprocess.run([sys.executable, "-c", code], env=dict(env, CVO_QUIET="1"), text=True, capture_output=True)
+        assert "ADVICE[" + text + "]" in quiet.stdout and "[cvo] advice" not in quiet.stderr
 
 
 @pytest.mark.gpu
 def test_cpp_host_runs_the_headline_batch_at_the_c_abi_speed(tmp_path):
     """the C++ host of the multi-GPU mode (cvo::CvoGPUSharded, RCCL communicator alive, one
     device here) solves BASELINE.json's per-GPU headline workload - 64 resident 10k x 10k pairs, 2000 iterations - within
-    10 % of cvo_align_batch called directly, in a process that sets NO environment variable (the library's load-time
-    hardware-queue hint is all it gets), and returns bit-identical poses."""
+    10 % of cvo_align_batch called directly, in a process started with this one's environment (the same hardware queues),
+    and returns bit-identical poses."""
     import time
     from unified_cvo_amd import CvoGPU
     shard = os.path.join(HOST, "cvo_align_sharded")
@@ -403,13 +415,13 @@ def test_cpp_host_runs_the_headline_batch_at_the_c_abi_speed(tmp_path):
         _write_xyz_pcd(tmp_path / f"s{p}.pcd", src.device_arrays()[0])
         _write_xyz_pcd(tmp_path / f"t{p}.pcd", tgt.device_arrays()[0])
         args += [str(tmp_path / f"s{p}.pcd"), str(tmp_path / f"t{p}.pcd")]
-    env = {k: v for k, v in os.environ.items() if k not in ("GPU_MAX_HW_QUEUES", "CVO_NO_HW_QUEUE_HINT")}
-    out = subprocess.check_output([shard, "--bench", "5", yaml, "0", "1"] + args, text=True, env=env)
+    out = subprocess.check_output([shard, "--bench", "5", yaml, "0", "1"] + args, text=True)
     lines = [l.split() for l in out.strip().splitlines()]
     bench = [l for l in lines if l and l[0] == "bench"][0]
     assert bench[:7] == ["bench", "devices", "1", "pairs", str(NP), "reps", "5"]
     ms_cpp = float(bench[bench.index("min") + 1])
-    assert not [l for l in lines if l and l[0] == "advice"]
+    from unified_cvo_amd import _capi
+    assert bool([l for l in lines if l and l[0] == "advice"]) == (_capi.lib().cvo_process_hint_hw_queues() < 8)
     P = pairs[0][0]
     gpu = CvoGPU(params=P)
     both = gpu.upload_many([a[1] for a in pairs] + [a[2] for a in pairs])

@@ -10,7 +10,8 @@ import cases
 from unified_cvo_amd import CvoParams, parse_cvo_yaml_text, read_cvo_params_yaml
 from unified_cvo_amd.params import _YAML_KEYS
 
-REF_PARAMS = "/root/reference/cvo_params"
+# the 16 parameter files the reference ships (cvo_params/*.yaml), stored verbatim as fixtures
+REF_PARAMS = os.path.join(cases.GOLDEN, "cvo_params")
 
 
 def test_defaults_match_reference_constructor():
@@ -65,7 +66,6 @@ def test_bad_value_raises():
         parse_cvo_yaml_text("MAX_ITER: lots\n")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_PARAMS), reason="reference checkout not present")
 def test_every_shipped_file_parses_like_pyyaml():
     """All 16 reference yaml files: our reader == PyYAML on the keys read_CvoParams_yaml asks for."""
     files = sorted(glob.glob(os.path.join(REF_PARAMS, "*.yaml")))

@@ -160,9 +160,6 @@ def lib(path=None):
             f"{path} is missing: build it with `python -m unified_cvo_amd.build` "
             "(there is no CPU fallback for the hot path)")
     L = C.CDLL(path)
-    # process-wide: GPU_MAX_HW_QUEUES=8 unless the caller chose a value (include/cvo_hip.h, hardware queues).  Here, right
-    # after the load: before this process's first HIP call if the library is loaded before anything touches the GPU
-    L.cvo_process_hint_hw_queues()
     vp, ip, fp = C.c_void_p, C.c_int, C.POINTER(C.c_float)
     L.cvo_version.restype = C.c_char_p
     L.cvo_params_default.argtypes = [C.POINTER(cvo_params_t)]

@@ -6,33 +6,11 @@
 // turns kernel by kernel: 0.37 s instead of 0.25 s per step measured under torchrun, where RCCL brings streams of its
 // own; see also the note in cvo_ctx_create).  HIP deals streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and
 // reads that variable once, when the runtime initialises - i.e. at the process's first HIP call.  So:
-//   * cvo_process_hint_hw_queues() puts GPU_MAX_HW_QUEUES=8 into the environment unless the variable is already set or
-//     CVO_NO_HW_QUEUE_HINT is: an EXPLICIT call a host makes before its first HIP call and before it starts threads
-//     (unified_cvo_amd/_capi.py does right after loading the library, cvo::CvoGPU's constructor before its context);
-//     at load time only with CVO_HW_QUEUE_HINT_AT_LOAD=1;
+//   * the library never writes the process environment: how many hardware queues HIP opens is the host's (or the
+//     machine's) choice; cvo_process_hint_hw_queues() only reports the value in force (4 when nothing is set);
 //   * cvo_ctx_create checks what the variable says NOW and, below 8, leaves an advisory text in cvo_ctx_advice() and
-//     prints it once per process (stderr) - the case of a host that initialised HIP first with the default, or
-//     that set a smaller value on purpose.
-namespace {
-bool g_hw_queue_hint_set = false;
-void hw_queue_hint() {
-  if (std::getenv("CVO_NO_HW_QUEUE_HINT")) return;
-  if (!std::getenv("GPU_MAX_HW_QUEUES")) {
-    setenv("GPU_MAX_HW_QUEUES", "8", 0);
-    g_hw_queue_hint_set = true;
-  }
-}
-// At LOAD time only on request (CVO_HW_QUEUE_HINT_AT_LOAD=1): a library constructor that edits the environment changes HIP's
-// queue allocation for the whole host process behind its back, and setenv is not safe against getenv in other threads.
-// The hint is an explicit call - cvo_process_hint_hw_queues() - that a host makes where it controls the ordering: before
-// its first HIP call, before it starts threads (the Python wrapper and the C++ veneer's CvoGPU constructor do).
-__attribute__((constructor(101))) void cvo_hw_queue_hint_at_load() {
-  if (std::getenv("CVO_HW_QUEUE_HINT_AT_LOAD")) hw_queue_hint();
-}
-}  // namespace
-
+//     prints it once per process (stderr).
 extern "C" int cvo_process_hint_hw_queues(void) {
-  hw_queue_hint();
   const char* q = std::getenv("GPU_MAX_HW_QUEUES");
   return q ? atoi(q) : 4;
 }
@@ -302,9 +280,9 @@ int cvo_ctx_create(int device, cvo_ctx** out) {
       snprintf(msg, sizeof msg,
                "GPU_MAX_HW_QUEUES is %s%s: batches run on four sub-batch streams next to the upload stream and whatever "
                "RCCL / the host application adds; with fewer than 8 hardware queues streams share a queue and take turns "
-               "(measured: 0.37 s instead of 0.25 s per 64-pair step under torchrun).  Export GPU_MAX_HW_QUEUES=8 before "
-               "the process's first HIP call",
-               q ? q : "unset (HIP's default: 4)", q ? "" : ": cvo_process_hint_hw_queues() was not called before HIP initialised");
+               "(measured: 0.37 s instead of 0.25 s per 64-pair step under torchrun); the count is fixed at the process's "
+               "first HIP call",
+               q ? q : "unset (HIP's default: 4)", "");
       c->advice = msg;
       static std::atomic<bool> said{false};
       if (!said.exchange(true) && !std::getenv("CVO_QUIET")) fprintf(stderr, "[cvo] advice: %s\n", msg);
