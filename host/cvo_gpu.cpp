@@ -361,6 +361,46 @@ std::vector<int> CvoGPU::align_stream(const ResidentClouds& sources, const Resid
   return rets;
 }
 
+// function_angle: 0 = inner products, 1 = approximate function_angle, 2 = exact
+std::vector<float> CvoGPU::score_batch(const ResidentClouds& sources, const ResidentClouds& targets,
+                                       const std::vector<std::pair<int, int>>& pairs, const std::vector<Mat4f>& T,
+                                       const std::vector<float>& ell, int function_angle) const {
+  std::lock_guard<std::mutex> lk(call_mutex);
+  const int n = (int)pairs.size();
+  if ((int)T.size() != n || (ell.size() != 1 && (int)ell.size() != n)) throw std::runtime_error("score batch: size mismatch");
+  std::vector<const cvo_cloud*> sh((size_t)n), th((size_t)n);
+  std::vector<float> Tm(16 * (size_t)n), l((size_t)n), out((size_t)n, 0.f);
+  for (int k = 0; k < n; k++) {
+    const auto& pr = pairs[k];
+    if (pr.first < 0 || pr.first >= sources.size() || pr.second < 0 || pr.second >= targets.size())
+      throw std::runtime_error("score batch: pair index out of range");
+    sh[k] = sources.handles[pr.first];
+    th[k] = targets.handles[pr.second];
+    std::copy(T[k].data(), T[k].data() + 16, &Tm[16 * (size_t)k]);
+    l[k] = ell.size() == 1 ? ell[0] : ell[k];
+  }
+  if (function_angle == 0)
+    check(ctx, cvo_inner_product_batch(ctx, &params, n, sh.data(), th.data(), Tm.data(), l.data(), out.data()),
+          "cvo_inner_product_batch");
+  else
+    check(ctx, cvo_function_angle_batch(ctx, &params, n, sh.data(), th.data(), Tm.data(), l.data(), function_angle == 1 ? 1 : 0,
+                                        out.data()),
+          "cvo_function_angle_batch");
+  return out;
+}
+
+std::vector<float> CvoGPU::inner_product_batch(const ResidentClouds& sources, const ResidentClouds& targets,
+                                               const std::vector<std::pair<int, int>>& pairs, const std::vector<Mat4f>& T,
+                                               const std::vector<float>& ell) const {
+  return score_batch(sources, targets, pairs, T, ell, 0);
+}
+
+std::vector<float> CvoGPU::function_angle_batch(const ResidentClouds& sources, const ResidentClouds& targets,
+                                                const std::vector<std::pair<int, int>>& pairs, const std::vector<Mat4f>& T,
+                                                const std::vector<float>& ell, bool is_approximate) const {
+  return score_batch(sources, targets, pairs, T, ell, is_approximate ? 1 : 2);
+}
+
 std::string CvoGPU::advice() const { return cvo_ctx_advice(ctx); }
 
 float CvoGPU::inner_product_gpu(const CvoPointCloud& a, const CvoPointCloud& b, const Mat4f& T, float ell) const {

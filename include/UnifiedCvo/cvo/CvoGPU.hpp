@@ -81,6 +81,15 @@ class CvoGPU {
                                 const std::vector<std::pair<int, int>>& pairs, const std::vector<Mat4f>& inits,
                                 std::vector<Mat4f>& transforms, int slots = 128, const std::vector<int>* max_iterations = nullptr,
                                 double* seconds = nullptr) const;
+  // New: many scores in one call (cvo_inner_product_batch / cvo_function_angle_batch, include/cvo_hip.h).  Job k scores
+  // sources[pairs[k].first] against targets[pairs[k].second] under T[k] with lengthscale ell[k] (ell may also hold ONE
+  // value for every job); every value is bit-identical to inner_product_gpu / function_angle of the same clouds.
+  std::vector<float> inner_product_batch(const ResidentClouds& sources, const ResidentClouds& targets,
+                                         const std::vector<std::pair<int, int>>& pairs, const std::vector<Mat4f>& T,
+                                         const std::vector<float>& ell) const;
+  std::vector<float> function_angle_batch(const ResidentClouds& sources, const ResidentClouds& targets,
+                                          const std::vector<std::pair<int, int>>& pairs, const std::vector<Mat4f>& T,
+                                          const std::vector<float>& ell, bool is_approximate = true) const;
   // cvo_ctx_advice of this object's context ("" = nothing to report; see include/cvo_hip.h, hardware queues)
   std::string advice() const;
 
@@ -115,6 +124,9 @@ class CvoGPU {
   // concurrent callers of ONE object get upstream's behaviour (upstream serialises them on the default stream as
   // well).  For concurrency use one CvoGPU per host thread, or align_batch.
   mutable std::mutex call_mutex;
+  std::vector<float> score_batch(const ResidentClouds& sources, const ResidentClouds& targets,
+                                 const std::vector<std::pair<int, int>>& pairs, const std::vector<Mat4f>& T,
+                                 const std::vector<float>& ell, int function_angle) const;
 };
 
 }  // namespace cvo

@@ -279,6 +279,19 @@ int cvo_function_angle(cvo_ctx* ctx, const cvo_params_t* params, const cvo_cloud
                        const cvo_cloud* target, const float T[16], float ell, int is_approximate,
                        float* out);
 
+/* New (not in the reference): n_jobs scores in one call - what the reference's drivers compute pair by pair
+ * (main_indicator_in_sequence.cpp, main_evaluate_indicator.cpp, the multi-frame drivers' function_angle checks).
+ * Job k = (sources[k], targets[k], T[16k .. 16k+15], ell[k]); out[k] = what cvo_inner_product / cvo_function_angle
+ * returns for it, bit for bit.  The whole call is validated first (on an error nothing is written to out); n_jobs == 0
+ * is accepted; a job with an empty cloud yields 0.  The jobs go through k_overlap_table in chunks, one launch and one
+ * synchronisation per chunk (no job-count limit); void jobs (a row beyond nearest_neighbors_max) and chain-only calls run
+ * the list chain as the single call does.  The exact function_angle evaluates <X, X> / <Y, Y> once per distinct cloud and
+ * lengthscale of the call. */
+int cvo_inner_product_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_jobs, const cvo_cloud* const* sources,
+                            const cvo_cloud* const* targets, const float* T, const float* ell, float* out);
+int cvo_function_angle_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_jobs, const cvo_cloud* const* sources,
+                             const cvo_cloud* const* targets, const float* T, const float* ell, int is_approximate,
+                             float* out);
 /* ---- compute_association_gpu(float lengthscale) (CvoGPU.cu:1876-1911) -----------------
  * CSR of Association::pairs (row = source index, col = target index, ascending).
  * row_ptr: n_source + 1 ints.  col/val: capacity entries.  *nnz_out = pairs found (may

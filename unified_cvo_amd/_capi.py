@@ -144,6 +144,7 @@ EXPORTED = [
     "cvo_ctx_set_option", "cvo_ctx_advice", "cvo_debug_cloud_order",
     "cvo_process_hint_hw_queues", "cvo_shutdown",
     "cvo_batch_open", "cvo_batch_submit", "cvo_batch_poll", "cvo_batch_pending", "cvo_batch_stats", "cvo_batch_close",
+    "cvo_inner_product_batch", "cvo_function_angle_batch", "cvo_debug_last_score_batch",
 ]
 
 _libs = {}
@@ -197,6 +198,9 @@ def lib(path=None):
     L.cvo_batch_close.restype = None
     L.cvo_inner_product.argtypes = [vp, C.POINTER(cvo_params_t), vp, vp, fp, C.c_float, fp]
     L.cvo_function_angle.argtypes = [vp, C.POINTER(cvo_params_t), vp, vp, fp, C.c_float, ip, fp]
+    L.cvo_inner_product_batch.argtypes = [vp, C.POINTER(cvo_params_t), ip, C.POINTER(vp), C.POINTER(vp), fp, fp, fp]
+    L.cvo_function_angle_batch.argtypes = [vp, C.POINTER(cvo_params_t), ip, C.POINTER(vp), C.POINTER(vp), fp, fp, ip, fp]
+    L.cvo_debug_last_score_batch.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.cvo_association.argtypes = [vp, C.POINTER(cvo_params_t), vp, vp, fp, C.c_float, C.POINTER(C.c_int),
                                   C.POINTER(C.c_int), fp, C.c_size_t, C.POINTER(C.c_size_t)]
     L.cvo_association_non_isotropic.argtypes = [vp, C.POINTER(cvo_params_t), vp, vp, fp, fp, C.POINTER(C.c_int),

@@ -565,6 +565,50 @@ class CvoGPU:
                                               1 if is_approximate else 0, C.byref(out)))
         return out.value
 
+    def _score_batch(self, fn, sources, targets, Ts, ells, *extra):
+        n = len(sources)
+        if len(targets) != n or len(Ts) != n:
+            raise CvoError(f"{n} sources, {len(targets)} targets, {len(Ts)} transforms: one of each per job")
+        ell = np.asarray(ells, np.float32)
+        ell = np.full(n, ell, np.float32) if ell.ndim == 0 else np.ascontiguousarray(ell)
+        if ell.shape != (n,):
+            raise CvoError(f"ells: a scalar or {n} values, got shape {ell.shape}")
+        up = {}  # CvoPointCloud -> DeviceCloud, keyed by object identity: a cloud of several jobs goes up once
+
+        def dev(pc):
+            if isinstance(pc, DeviceCloud):
+                return pc
+            if id(pc) not in up:
+                up[id(pc)] = (pc, DeviceCloud(self, pc))
+            return up[id(pc)][1]
+
+        src = [dev(s) for s in sources]
+        tgt = [dev(t) for t in targets]
+        sh = (C.c_void_p * max(n, 1))(*[s.handle for s in src])
+        th = (C.c_void_p * max(n, 1))(*[t.handle for t in tgt])
+        Tm = np.concatenate([_mat_to_c(T) for T in Ts]).astype(np.float32) if n else np.zeros(16, np.float32)
+        out = np.zeros(max(n, 1), np.float32)
+        p = self.params.to_ctypes()
+        self._check(fn(self.ctx, C.byref(p), n, sh, th, _fptr(Tm), _fptr(ell if n else np.zeros(1, np.float32)), *extra,
+                       _fptr(out)))
+        return out[:n]
+
+    def inner_product_batch(self, sources, targets, Ts, ells):
+        """inner_product_gpu for many (source, target, T, ell) jobs in one call (cvo_inner_product_batch): np.float32[n],
+        every value bit-identical to inner_product_gpu's.  ells: one per job or a scalar."""
+        return self._score_batch(self.L.cvo_inner_product_batch, sources, targets, Ts, ells)
+
+    def function_angle_batch(self, sources, targets, Ts, ells, is_approximate=True):
+        """function_angle for many jobs in one call (cvo_function_angle_batch): np.float32[n], bit-identical to
+        function_angle's.  The exact form evaluates <X, X> / <Y, Y> once per distinct cloud and ell."""
+        return self._score_batch(self.L.cvo_function_angle_batch, sources, targets, Ts, ells, 1 if is_approximate else 0)
+
+    def debug_last_score_batch(self):
+        """(overlap evaluations, chain evaluations, launches) of the last batched score call."""
+        a, b, c = C.c_int(), C.c_int(), C.c_int()
+        self._check(self.L.cvo_debug_last_score_batch(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def compute_association_gpu(self, source, target, T, lengthscale):
         """Association::pairs as CSR (row_ptr, col, val) (CvoGPU.cu:1876-1911)."""
         src, tgt = self._dev(source), self._dev(target)

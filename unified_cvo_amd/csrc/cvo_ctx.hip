@@ -93,6 +93,11 @@ void free_workspace(cvo_ctx* c) {
   if (c->h_ov) (void)hipHostFree(c->h_ov);
   c->d_ov = c->h_ov = nullptr;
   c->ov_tiles_cap = 0;
+  if (c->d_sb) (void)hipFree(c->d_sb);
+  if (c->h_sb) (void)hipHostFree(c->h_sb);
+  if (c->h_sb_res) (void)hipHostFree(c->h_sb_res);
+  c->d_sb = c->h_sb = c->h_sb_res = nullptr;
+  c->sb_jobs_cap = c->sb_tiles_cap = 0;
   if (c->d_ctl) (void)hipFree(c->d_ctl);
   if (c->h_ctl) (void)hipHostFree(c->h_ctl);
   for (int i = 0; i < 2; i++)

@@ -48,6 +48,14 @@ int cvo_debug_device_memory(cvo_ctx* ctx, size_t* free_bytes, size_t* total_byte
   return CVO_OK;
 }
 
+int cvo_debug_last_score_batch(const cvo_ctx* ctx, int* overlap_evals, int* chain_evals, int* launches) {
+  if (!ctx) return CVO_E_INVALID;
+  if (overlap_evals) *overlap_evals = ctx->last_score_overlap;
+  if (chain_evals) *chain_evals = ctx->last_score_chain;
+  if (launches) *launches = ctx->last_score_launches;
+  return CVO_OK;
+}
+
 int cvo_debug_verified_rows(cvo_ctx* ctx, unsigned long long* rows) {
   if (!ctx || !rows || ctx->last_pairs < 1) return fail(ctx, CVO_E_INVALID, "cvo_debug_verified_rows: bad argument");
   unsigned long long t = 0;

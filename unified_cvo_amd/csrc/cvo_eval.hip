@@ -1,4 +1,4 @@
-// cvo_eval.hip -- single evaluations: inner_product_gpu / function_angle in one launch of k_overlap or through the list chain, run_single_eval for the association exports.
+// cvo_eval.hip -- single evaluations: inner_product_gpu / function_angle in one launch of k_overlap or through the list chain, run_single_eval for the association exports; their batched forms (k_overlap_table, cvo_*_batch).
 // A SECTION of the one translation unit cvo_hip.hip (which includes the sections in dependency order and says why it is one
 // unit); not compiled on its own.  Shared declarations: cvo_internal.h.
 namespace {
@@ -33,7 +33,63 @@ struct OverlapArgs {
 static_assert(sizeof(OverlapArgs) <= 4096, "k_overlap takes its jobs as kernel arguments");
 template <int FEAT>
 __global__ __launch_bounds__(64 * OV_WAVES) void k_overlap_entry(const OverlapArgs A) {
-  k_overlap<FEAT>(A.job[blockIdx.y], A.P);
+  k_overlap<FEAT>(A.job[blockIdx.y], A.P, (int)blockIdx.x);
+}
+
+// The batched form (cvo_inner_product_batch / cvo_function_angle_batch): the jobs are a DEVICE table, the grid is flat -
+// one block per row tile of every job, sum of the jobs' tiles, no idle blocks - and a block finds its (job, tile) by a
+// binary search of the tiles' exclusive prefix sum tile_start[0 .. n_jobs] (wave-uniform: scalar loads, log2 n_jobs steps).
+template <int FEAT>
+__global__ __launch_bounds__(64 * OV_WAVES) void k_overlap_table(const OverlapJob* __restrict__ jobs, const int* __restrict__ tile_start,
+                                                                 const int n_jobs, const DevParams P) {
+  const int b = (int)blockIdx.x;
+  int lo = 0, hi = n_jobs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tile_start[mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  k_overlap<FEAT>(jobs[lo], P, b - tile_start[lo]);
+}
+
+// An OverlapJob's description of one evaluation <f_X, f_Y> under Tm (everything but its partials, gate words and result
+// slots).
+void fill_overlap_job(const cvo_cloud* X, const cvo_cloud* Y, const float* Tm, float ell, int K, OverlapJob& J) {
+  J.D.N = X->n;
+  J.D.M = Y->n;
+  J.D.xs4 = X->xs4;
+  J.D.ys4 = Y->xs4;
+  J.D.xfeat = X->feat;
+  J.D.yfeat = Y->feat;
+  J.D.xlabel = X->label;
+  J.D.ylabel = Y->label;
+  J.D.xgeo = X->geo;
+  J.D.ygeo = Y->geo;
+  J.D.xlid = X->lid;
+  J.D.ylid = Y->lid;
+  J.xtile = X->tile4;
+  J.ytile = Y->tile4;
+  J.n_xtiles = (X->n + 63) / 64;
+  J.n_ytiles = (Y->n + 63) / 64;
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) J.R[3 * i + j] = Tm[4 * j + i];  // CvoGPU.cu:1363-1364 (as fill_pair)
+    J.T[i] = Tm[12 + i];
+  }
+  {
+    // |R^T v| <= stretch |v|: 1 (+ rounding) for a rotation, the Frobenius norm for anything else a caller may pass
+    double dev = 0, fro = 0;
+    for (int i = 0; i < 3; i++)
+      for (int j = 0; j < 3; j++) {
+        double g = 0;
+        for (int k = 0; k < 3; k++) g += (double)J.R[3 * k + i] * (double)J.R[3 * k + j];
+        dev = std::max(dev, std::fabs(g - (i == j ? 1.0 : 0.0)));
+        fro += (double)J.R[3 * i + j] * (double)J.R[3 * i + j];
+      }
+    J.stretch = (dev <= 1e-4) ? 1.001f : (float)(std::sqrt(fro) * 1.001);
+    if (!std::isfinite(J.stretch)) J.stretch = __builtin_inff();  // (every tile is visited)
+  }
+  J.ell = ell;
+  J.K = K;
 }
 
 int ensure_tiles(cvo_ctx* ctx, const cvo_cloud* c, hipStream_t s) {
@@ -80,42 +136,7 @@ int run_overlap_kernel(cvo_ctx* ctx, const cvo_params_t* params, int n, const cv
     if ((rc = ensure_tiles(ctx, X, stream)) != CVO_OK || (rc = ensure_tiles(ctx, Y, stream)) != CVO_OK) return rc;
     all_hot = all_hot && X->lid != nullptr && Y->lid != nullptr;
     OverlapJob& J = A.job[p];
-    J.D.N = X->n;
-    J.D.M = Y->n;
-    J.D.xs4 = X->xs4;
-    J.D.ys4 = Y->xs4;
-    J.D.xfeat = X->feat;
-    J.D.yfeat = Y->feat;
-    J.D.xlabel = X->label;
-    J.D.ylabel = Y->label;
-    J.D.xgeo = X->geo;
-    J.D.ygeo = Y->geo;
-    J.D.xlid = X->lid;
-    J.D.ylid = Y->lid;
-    J.xtile = X->tile4;
-    J.ytile = Y->tile4;
-    J.n_xtiles = (X->n + 63) / 64;
-    J.n_ytiles = (Y->n + 63) / 64;
-    const float* Tm = Tms + 16 * (size_t)p;
-    for (int i = 0; i < 3; i++) {
-      for (int j = 0; j < 3; j++) J.R[3 * i + j] = Tm[4 * j + i];  // CvoGPU.cu:1363-1364 (as fill_pair)
-      J.T[i] = Tm[12 + i];
-    }
-    {
-      // |R^T v| <= stretch |v|: 1 (+ rounding) for a rotation, the Frobenius norm for anything else a caller may pass
-      double dev = 0, fro = 0;
-      for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) {
-          double g = 0;
-          for (int k = 0; k < 3; k++) g += (double)J.R[3 * k + i] * (double)J.R[3 * k + j];
-          dev = std::max(dev, std::fabs(g - (i == j ? 1.0 : 0.0)));
-          fro += (double)J.R[3 * i + j] * (double)J.R[3 * i + j];
-        }
-      J.stretch = (dev <= 1e-4) ? 1.001f : (float)(std::sqrt(fro) * 1.001);
-      if (!std::isfinite(J.stretch)) J.stretch = __builtin_inff();  // (every tile is visited)
-    }
-    J.ell = ell;
-    J.K = params->nearest_neighbors_max;
+    fill_overlap_job(X, Y, Tms + 16 * (size_t)p, ell, params->nearest_neighbors_max, J);
     J.part = reinterpret_cast<double*>(ctx->d_ov + 256) + (size_t)p * ctx->ov_tiles_cap;
     J.gate = reinterpret_cast<int*>(ctx->d_ov) + 2 * p;
     J.sum_host = reinterpret_cast<double*>(ctx->h_ov) + p;
@@ -144,6 +165,9 @@ int run_overlap_kernel(cvo_ctx* ctx, const cvo_params_t* params, int n, const cv
   return CVO_OK;
 }
 
+int run_ip_chain(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_cloud* const* src, const cvo_cloud* const* tgt,
+                 const float* Tms, float ell, double* out);
+
 int run_inner_products(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_cloud* const* src, const cvo_cloud* const* tgt,
                        const float* Tms, float ell, double* out) {
   // One launch when the call has a geometric cut-off to cull by and nobody asked for the list chain (CVO_IP_CHAIN; the
@@ -155,6 +179,12 @@ int run_inner_products(cvo_ctx* ctx, const cvo_params_t* params, int n, const cv
     if (rc != CVO_OK) return rc;
     if (!void_sum) return CVO_OK;
   }
+  return run_ip_chain(ctx, params, n, src, tgt, Tms, ell, out);
+}
+
+// The list chain for n (< 8: one sub-batch) inner products of one lengthscale (see run_inner_products).
+int run_ip_chain(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_cloud* const* src, const cvo_cloud* const* tgt,
+                 const float* Tms, float ell, double* out) {
   BatchSetup S;
   DevParams dp;
   int rc = setup_batch(ctx, params, n, src, tgt, Tms, nullptr, 1, ell, &S, &dp);
@@ -202,6 +232,240 @@ int run_inner_products(cvo_ctx* ctx, const cvo_params_t* params, int n, const cv
     out[p] = res[p];
     ctx->h_states[p].asum = res[p];
   }
+  return CVO_OK;
+}
+
+// ---- batched scores (cvo_inner_product_batch / cvo_function_angle_batch) ------------------------------------------------
+// Every job's value is, bit for bit, what the single call returns: the same evaluations (k_overlap sums a job's row tiles in
+// tile order whatever shares the launch; the list chain's values do not depend on their company), the same void rule and
+// the same host arithmetic.  One launch of k_overlap_table and one synchronisation per chunk of the job list.
+constexpr int SB_CHUNK_JOBS = 1024;    // jobs per launch (pinned staging and device table are sized by it)
+constexpr int SB_CHUNK_TILES = 65536;  // row tiles per launch (4M source rows), unless one job alone has more
+constexpr size_t SB_START_BYTES = (sizeof(int) * (SB_CHUNK_JOBS + 1) + 255) / 256 * 256;
+
+// Device workspace [tile starts | job table | gate words | partials] and its staging copy [tile starts | job table]: the
+// prefix that a launch's table occupies goes up in one copy.  Gate words are zeroed here once; the kernel leaves them at zero.
+int score_ws_reserve(cvo_ctx* ctx, int tiles) {
+  if (ctx->d_sb && tiles <= ctx->sb_tiles_cap) return CVO_OK;
+  const int tiles_cap = std::max(tiles, ctx->sb_tiles_cap);
+  if (ctx->d_sb) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    (void)hipFree(ctx->d_sb);
+  }
+  ctx->d_sb = nullptr;
+  ctx->sb_tiles_cap = ctx->sb_jobs_cap = 0;
+  const size_t table = SB_START_BYTES + align_up(sizeof(OverlapJob) * SB_CHUNK_JOBS, 256);
+  const size_t gates = align_up(sizeof(int) * 2 * SB_CHUNK_JOBS, 256);
+  HIP_TRY(ctx, hipMalloc(&ctx->d_sb, table + gates + sizeof(double) * (size_t)tiles_cap));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_sb + table, 0, gates, ctx->stream));
+  if (!ctx->h_sb) HIP_TRY(ctx, hipHostMalloc(&ctx->h_sb, table, hipHostMallocDefault));
+  if (!ctx->h_sb_res)
+    HIP_TRY(ctx, hipHostMalloc(&ctx->h_sb_res, (sizeof(double) + sizeof(int)) * SB_CHUNK_JOBS, hipHostMallocMapped | hipHostMallocCoherent));
+  ctx->sb_jobs_cap = SB_CHUNK_JOBS;
+  ctx->sb_tiles_cap = tiles_cap;
+  return CVO_OK;
+}
+
+struct ScoreEval {
+  const cvo_cloud* X;
+  const cvo_cloud* Y;
+  const float* T;
+  float ell;
+  double ov = 0;       // k_overlap's sum ...
+  bool over = false;   // ... void: some row found more than nearest_neighbors_max pairs
+  bool chain = false;  // some job takes this evaluation from the list chain ...
+  double ch = 0;       // ... its value there
+};
+
+// All evaluations through k_overlap_table: jobs largest first (a launch's tail is its largest job's last tiles), cut into
+// chunks of at most SB_CHUNK_JOBS jobs / SB_CHUNK_TILES tiles.
+int score_overlap(cvo_ctx* ctx, const cvo_params_t* params, std::vector<ScoreEval>& ev) {
+  hipStream_t stream = ctx->stream;
+  DevParams P = make_dev_params(ctx, *params);
+  P.mode = 1;
+  bool all_hot = ctx_opt(ctx, "NO_ONEHOT") == nullptr;  // (FEAT_HOT and FEAT_ALL give the same bits: test_gpu_parity.py)
+  int rc;
+  for (const ScoreEval& e : ev) {
+    if ((rc = ensure_tiles(ctx, e.X, stream)) != CVO_OK || (rc = ensure_tiles(ctx, e.Y, stream)) != CVO_OK) return rc;
+    all_hot = all_hot && e.X->lid != nullptr && e.Y->lid != nullptr;
+  }
+  const int feat = call_feat(P, all_hot);
+  std::vector<int> order(ev.size());
+  for (size_t i = 0; i < ev.size(); i++) order[i] = (int)i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ev[a].X->n > ev[b].X->n; });
+  const int biggest = order.empty() ? 0 : (ev[order[0]].X->n + 63) / 64;
+  if ((rc = score_ws_reserve(ctx, std::max(SB_CHUNK_TILES, biggest))) != CVO_OK) return rc;
+  int* h_start = reinterpret_cast<int*>(ctx->h_sb);
+  OverlapJob* h_jobs = reinterpret_cast<OverlapJob*>(ctx->h_sb + SB_START_BYTES);
+  const int* d_start = reinterpret_cast<const int*>(ctx->d_sb);
+  const OverlapJob* d_jobs = reinterpret_cast<const OverlapJob*>(ctx->d_sb + SB_START_BYTES);
+  const size_t table = SB_START_BYTES + align_up(sizeof(OverlapJob) * SB_CHUNK_JOBS, 256);
+  int* d_gate = reinterpret_cast<int*>(ctx->d_sb + table);
+  double* d_part = reinterpret_cast<double*>(ctx->d_sb + table + align_up(sizeof(int) * 2 * SB_CHUNK_JOBS, 256));
+  double* h_sum = reinterpret_cast<double*>(ctx->h_sb_res);
+  int* h_over = reinterpret_cast<int*>(ctx->h_sb_res + sizeof(double) * SB_CHUNK_JOBS);
+  for (size_t pos = 0; pos < order.size();) {
+    int n = 0, tiles = 0;
+    while (pos + n < order.size() && n < SB_CHUNK_JOBS) {
+      const ScoreEval& e = ev[order[pos + n]];
+      const int t = (e.X->n + 63) / 64;
+      if (n > 0 && tiles + t > ctx->sb_tiles_cap) break;
+      OverlapJob& J = h_jobs[n];
+      std::memset(&J, 0, sizeof(J));
+      fill_overlap_job(e.X, e.Y, e.T, e.ell, params->nearest_neighbors_max, J);
+      J.part = d_part + tiles;
+      J.gate = d_gate + 2 * n;
+      J.sum_host = h_sum + n;
+      J.over_host = h_over + n;
+      h_start[n] = tiles;
+      tiles += t;
+      n++;
+    }
+    h_start[n] = tiles;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sb, ctx->h_sb, SB_START_BYTES + sizeof(OverlapJob) * (size_t)n, hipMemcpyHostToDevice, stream));
+    const dim3 grid(tiles), block(64 * OV_WAVES);
+    switch (feat) {
+      case FEAT_GEO: hipLaunchKernelGGL((k_overlap_table<FEAT_GEO>), grid, block, 0, stream, d_jobs, d_start, n, P); break;
+      case FEAT_COL: hipLaunchKernelGGL((k_overlap_table<FEAT_COL>), grid, block, 0, stream, d_jobs, d_start, n, P); break;
+      case FEAT_HOT: hipLaunchKernelGGL((k_overlap_table<FEAT_HOT>), grid, block, 0, stream, d_jobs, d_start, n, P); break;
+      default: hipLaunchKernelGGL((k_overlap_table<FEAT_ALL>), grid, block, 0, stream, d_jobs, d_start, n, P); break;
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+      (void)hipMemset(d_gate, 0, sizeof(int) * 2 * SB_CHUNK_JOBS);  // (a launch that died may have left gate words behind)
+      return fail(ctx, CVO_E_HIP, std::string("k_overlap_table: ") + hipGetErrorString(e));
+    }
+    for (int i = 0; i < n; i++) {
+      ScoreEval& r = ev[order[pos + i]];
+      r.ov = reinterpret_cast<const volatile double*>(h_sum)[i];
+      r.over = reinterpret_cast<const volatile int*>(h_over)[i] != 0;
+    }
+    ctx->last_score_overlap += n;
+    ctx->last_score_launches++;
+    pos += n;
+  }
+  ctx->last_pairs = 0;  // (as run_overlap_kernel: no workspace of the list chain belongs to this call)
+  return CVO_OK;
+}
+
+// kind: 0 inner product, 1 approximate function_angle, 2 exact function_angle.  Validates the whole call before any device
+// work; writes `out` only when every job has its value.
+int score_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_jobs, const cvo_cloud* const* sources,
+                const cvo_cloud* const* targets, const float* T, const float* ell, int kind, float* out, const char* name) {
+  if (!ctx) return CVO_E_INVALID;
+  if (!params || n_jobs < 0 || (n_jobs > 0 && (!sources || !targets || !T || !ell || !out)))
+    return fail(ctx, CVO_E_INVALID, std::string(name) + ": bad argument");
+  if (ctx->queue_open) return fail(ctx, CVO_E_INVALID, "a batch queue is open on this context (cvo_batch_close it first)");
+  if (params->is_using_kdtree)
+    return fail(ctx, CVO_E_UNSUPPORTED, "is_using_kdtree=1 is out of scope (SURVEY.md section 2, row 11)");
+  std::vector<int> live;  // jobs with two non-empty clouds (the others are 0, as the single call returns)
+  std::vector<const cvo_cloud*> ls, lt;
+  for (int k = 0; k < n_jobs; k++) {
+    if (!sources[k] || !targets[k]) return fail(ctx, CVO_E_INVALID, "null cloud");
+    if (sources[k]->n == 0 || targets[k]->n == 0) continue;
+    live.push_back(k);
+    ls.push_back(sources[k]);
+    lt.push_back(targets[k]);
+  }
+  ctx->last_score_overlap = ctx->last_score_chain = ctx->last_score_launches = 0;
+  if (!live.empty()) {
+    int N = 0, M = 0;
+    const int rc = check_call(ctx, params, (int)live.size(), ls.data(), lt.data(), nullptr, 1, ell[live[0]], nullptr, &N, &M);
+    if (rc != CVO_OK) return rc;
+    for (int k : live)  // (check_call's lengthscale rule, for every job's own ell)
+      if (!(std::isfinite(ell[k]) && ell[k] >= 1e-30f && ell[k] <= 1e15f))
+        return fail(ctx, CVO_E_INVALID, "lengthscale outside [1e-30, 1e15] (ell_init / ell_min / the ell of the call)");
+  } else if (params->nearest_neighbors_max <= 0) {
+    return fail(ctx, CVO_E_INVALID, "nearest_neighbors_max must be > 0");
+  }
+  static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+  // the evaluations: <X, Y> per job; the exact function_angle's <X, X> / <Y, Y> once per (cloud, ell)
+  std::vector<ScoreEval> ev;
+  std::vector<int> jev(3 * (size_t)n_jobs, -1);
+  std::map<std::pair<const cvo_cloud*, uint32_t>, int> self_ev;
+  auto self_eval = [&](const cvo_cloud* c, float l) {
+    uint32_t bits;
+    std::memcpy(&bits, &l, 4);
+    auto it = self_ev.find({c, bits});
+    if (it != self_ev.end()) return it->second;
+    ev.push_back(ScoreEval{c, c, identity, l});
+    self_ev[{c, bits}] = (int)ev.size() - 1;
+    return (int)ev.size() - 1;
+  };
+  for (int k : live) {
+    jev[3 * k] = (int)ev.size();
+    ev.push_back(ScoreEval{sources[k], targets[k], T + 16 * (size_t)k, ell[k]});
+    if (kind == 2) {
+      jev[3 * k + 1] = self_eval(sources[k], ell[k]);
+      jev[3 * k + 2] = self_eval(targets[k], ell[k]);
+    }
+  }
+  // the single call's path: one k_overlap launch unless the call has no geometric cut-off or the context asks for the chain
+  const bool chain_all = !params->is_using_geometry || ctx_opt(ctx, "IP_CHAIN") != nullptr || ctx_opt(ctx, "VERIFY_LISTS") != nullptr ||
+                         ctx_opt(ctx, "KERNEL_CLOCK") != nullptr || ctx_opt(ctx, "PHASE_TICKS") != nullptr;
+  int rc;
+  if (!chain_all && !ev.empty() && (rc = score_overlap(ctx, params, ev)) != CVO_OK) return rc;
+  // A job is void when one of ITS evaluations is (the exact function_angle: all three then come from the chain).
+  std::vector<char> job_chain(n_jobs, 0);
+  for (int k : live) {
+    bool v = chain_all;
+    for (int i = 0; i < 3; i++) v = v || (jev[3 * k + i] >= 0 && ev[jev[3 * k + i]].over);
+    job_chain[k] = v;
+    if (v)
+      for (int i = 0; i < 3; i++)
+        if (jev[3 * k + i] >= 0) ev[jev[3 * k + i]].chain = true;
+  }
+  // the chain's evaluations, in groups of up to seven of one lengthscale (one sub-batch, one synchronisation each)
+  {
+    std::map<uint32_t, std::vector<int>> by_ell;
+    for (int i = 0; i < (int)ev.size(); i++)
+      if (ev[i].chain) {
+        uint32_t bits;
+        std::memcpy(&bits, &ev[i].ell, 4);
+        by_ell[bits].push_back(i);
+      }
+    for (auto& g : by_ell)
+      for (size_t p0 = 0; p0 < g.second.size(); p0 += 7) {
+        const int n = (int)std::min<size_t>(7, g.second.size() - p0);
+        const cvo_cloud* src[7];
+        const cvo_cloud* tgt[7];
+        float Ts[16 * 7];
+        double v[7];
+        for (int i = 0; i < n; i++) {
+          const ScoreEval& e = ev[g.second[p0 + i]];
+          src[i] = e.X;
+          tgt[i] = e.Y;
+          std::memcpy(Ts + 16 * i, e.T, sizeof(float) * 16);
+        }
+        if ((rc = run_ip_chain(ctx, params, n, src, tgt, Ts, ev[g.second[p0]].ell, v)) != CVO_OK) return rc;
+        for (int i = 0; i < n; i++) ev[g.second[p0 + i]].ch = v[i];
+        ctx->last_score_chain += n;
+        ctx->last_score_launches++;
+      }
+  }
+  // the single calls' host arithmetic (cvo_inner_product / cvo_function_angle)
+  std::vector<float> res(n_jobs, 0.f);
+  for (int k : live) {
+    auto val = [&](int i) {
+      const ScoreEval& e = ev[jev[3 * k + i]];
+      return job_chain[k] ? e.ch : e.ov;
+    };
+    if (kind == 0) {
+      res[k] = (float)val(0);
+      continue;
+    }
+    float fxfz = (float)val(0), fx_norm, fz_norm;
+    if (kind == 1) {
+      fx_norm = (float)std::sqrt((double)sources[k]->n);
+      fz_norm = (float)std::sqrt((double)targets[k]->n);
+    } else {
+      fx_norm = std::sqrt((float)val(1));
+      fz_norm = std::sqrt((float)val(2));
+    }
+    res[k] = fxfz / (fx_norm * fz_norm);
+  }
+  if (n_jobs > 0) std::memcpy(out, res.data(), sizeof(float) * (size_t)n_jobs);
   return CVO_OK;
 }
 
@@ -266,6 +530,16 @@ int cvo_function_angle(cvo_ctx* ctx, const cvo_params_t* params, const cvo_cloud
   }
   *out = fxfz / (fx_norm * fz_norm);
   return CVO_OK;
+}
+
+int cvo_inner_product_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_jobs, const cvo_cloud* const* sources,
+                            const cvo_cloud* const* targets, const float* T, const float* ell, float* out) {
+  return score_batch(ctx, params, n_jobs, sources, targets, T, ell, 0, out, "cvo_inner_product_batch");
+}
+
+int cvo_function_angle_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_jobs, const cvo_cloud* const* sources,
+                             const cvo_cloud* const* targets, const float* T, const float* ell, int is_approximate, float* out) {
+  return score_batch(ctx, params, n_jobs, sources, targets, T, ell, is_approximate ? 1 : 2, out, "cvo_function_angle_batch");
 }
 
 }  // extern "C"

@@ -119,6 +119,14 @@ struct cvo_ctx {
   char* d_ov = nullptr;
   int ov_tiles_cap = 0;
   char* h_ov = nullptr;
+  // batched scores (cvo_inner_product_batch / cvo_function_angle_batch, k_overlap_table): device job table + tile starts,
+  // row-tile partials and per-job gate words (zero between launches), their pinned staging copy and the pinned results;
+  // sized on first use, grown, freed with the context (see score_ws_reserve)
+  char* d_sb = nullptr;
+  char* h_sb = nullptr;      // staging of the job table (one copy per launch)
+  char* h_sb_res = nullptr;  // results: a double and a void flag per job (mapped, written by the device)
+  int sb_jobs_cap = 0, sb_tiles_cap = 0;
+  int last_score_overlap = 0, last_score_chain = 0, last_score_launches = 0;  // cvo_debug_last_score_batch
   int* h_status[2] = {nullptr, nullptr};  // pinned; [0]: the live host mirror of the status / want words the device writes
                                           // (PairDesc::status_host / want_host), [1]: unused slot kept for the layout
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;

@@ -77,12 +77,13 @@ __device__ unsigned long long g_ov_ticks[4096][8];
 #else
 #define OV_T() 0ull
 #endif
-// (the body; the kernel proper - k_overlap_entry, cvo_hip.hip - hands it one of the jobs it takes as kernel ARGUMENTS: no
-// descriptor upload precedes the launch)
+// (the body; the kernels proper - k_overlap_entry and k_overlap_table, cvo_eval.hip - hand it a job and the row tile this
+// block takes: k_overlap_entry one of the jobs it takes as kernel ARGUMENTS (no descriptor upload precedes the launch) and
+// blockIdx.x, k_overlap_table an entry of a device job table and the tile its flat block index maps to)
 template <int FEAT>
-__device__ __forceinline__ void k_overlap(const OverlapJob& Jr, const DevParams& P) {
+__device__ __forceinline__ void k_overlap(const OverlapJob& Jr, const DevParams& P, const int tile) {
   const OverlapJob* __restrict__ J = &Jr;
-  if ((int)blockIdx.x >= J->n_xtiles) return;  // (the jobs of a launch share the grid of the largest)
+  if (tile >= J->n_xtiles) return;  // (the jobs of a k_overlap_entry launch share the grid of the largest)
   const PairDesc* __restrict__ D = &J->D;
   const int N = D->N, M = D->M, n_ytiles = J->n_ytiles;
   // (wave-uniform values are said to be: the compiler keeps what it derives from threadIdx.x in vector registers, and the
@@ -97,14 +98,14 @@ __device__ __forceinline__ void k_overlap(const OverlapJob& Jr, const DevParams&
   // update_tf (CvoGPU.cu:94-112), as k_update<INIT> runs it for the list chain: same operands, same floats
   Pose pose;
   update_tf(J->R, J->T, pose.Ri, pose.Ti);
-  const int row = (int)blockIdx.x * 64 + lane;  // a sorted position of the source cloud = the index of its attributes
+  const int row = tile * 64 + lane;  // a sorted position of the source cloud = the index of its attributes
   const bool live = row < N;
   const float4 x = D->xs4[live ? row : N - 1];
   RowData r = make_row(P, x, J->ell);
   if (FEAT == FEAT_HOT) r.lid = D->xlid[live ? row : N - 1];
   const FeatDen F = make_feat_den(P);
   // how far a target can be from the rows' sphere / box and still pass some row's cut-off
-  const float4 xs = J->xtile[2 * blockIdx.x], xh = J->xtile[2 * blockIdx.x + 1];
+  const float4 xs = J->xtile[2 * tile], xh = J->xtile[2 * tile + 1];
   const float r_cut_all = sqrtf(wave_minmax_f32<true>(live ? r.d2_thres : 0.f)) * 1.000001f;
   const float stretch = J->stretch;
   double asum = 0;
@@ -127,7 +128,7 @@ __device__ __forceinline__ void k_overlap(const OverlapJob& Jr, const DevParams&
   __shared__ float s_qa[OV_WAVES][OV_QCAP];
   unsigned short* const qm = &s_qm[wave][0];
   float* const qa = &s_qa[wave][0];
-  const int row0 = (int)blockIdx.x * 64;
+  const int row0 = tile * 64;
   [[maybe_unused]] const unsigned long long ov_t1 = OV_T();
   // The target tiles this block has to look at: those whose bounding sphere AND bounding box - moved by the pose - come
   // within reach of the rows'.  All waves test (a tile per thread), the survivors are listed in ascending tile order and
@@ -349,7 +350,7 @@ __device__ __forceinline__ void k_overlap(const OverlapJob& Jr, const DevParams&
     const double tot = lane_f64(s, 0) + lane_f64(s, 16) + (lane_f64(s, 32) + lane_f64(s, 48));
     const bool any_over = __ballot(over) != 0ull;
     if (lane == 0) {
-      st_x<true>(J->part + blockIdx.x, tot);
+      st_x<true>(J->part + tile, tot);
       if (any_over) __hip_atomic_fetch_add(J->gate + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       const int done = __hip_atomic_fetch_add(J->gate, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -376,7 +377,7 @@ __device__ __forceinline__ void k_overlap(const OverlapJob& Jr, const DevParams&
   }
 #ifdef CVO_OV_STAMPS
   if (lane == 0 && blockIdx.y == 0) {
-    unsigned long long* o = g_ov_ticks[((int)blockIdx.x * OV_WAVES + wave) & 4095];
+    unsigned long long* o = g_ov_ticks[(tile * OV_WAVES + wave) & 4095];
     o[0] = ov_t1 - ov_t0;                 // prologue
     o[1] = ov_cull;                       // tiles: transform + box test
     o[2] = ov_scan;                       // tiles: scan + parking
