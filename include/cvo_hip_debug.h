@@ -60,9 +60,11 @@ int cvo_debug_verified_rows(cvo_ctx* ctx, unsigned long long* rows);
  * Computed on the device at upload (k_kd_order) for clouds of 8 .. 16384 finite points, on the host otherwise and under
  * CVO_ORDER=host / virtual / CVO_NO_SORT; no result depends on it. */
 int cvo_debug_cloud_order(const cvo_cloud* cloud, int* out);
-/* What the last cvo_inner_product_batch / cvo_function_angle_batch did: evaluations summed by k_overlap_table (the exact
- * function_angle's <X, X> / <Y, Y> once per distinct cloud and lengthscale), evaluations repeated or run by the list chain
- * (void jobs, chain-only calls), and launches (k_overlap_table chunks + chain sub-batches).  Any pointer may be NULL. */
+/* What the last score call did - cvo_inner_product / cvo_function_angle (one job) or their _batch forms: evaluations summed
+ * by k_overlap (the exact function_angle's <X, X> / <Y, Y> once per distinct cloud and lengthscale), evaluations repeated
+ * or run by the list chain (void jobs, chain-only calls), and launches (k_overlap chunks + chain sub-batches).  E.g.
+ * (1, 0, 1) for an inner product no row voids, (3, 0, 1) for an exact function_angle of two distinct clouds.  A call that
+ * returns before any device work (a single call with an empty cloud) leaves the previous values.  Any pointer may be NULL. */
 int cvo_debug_last_score_batch(const cvo_ctx* ctx, int* overlap_evals, int* chain_evals, int* launches);
 /* Free / total bytes of the context's device (hipMemGetInfo), for leak checks without a second HIP runtime in the process. */
 int cvo_debug_device_memory(cvo_ctx* ctx, size_t* free_bytes, size_t* total_bytes);

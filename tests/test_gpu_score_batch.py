@@ -1,7 +1,9 @@
 """Batched scores (cvo_inner_product_batch / cvo_function_angle_batch, CvoGPU.inner_product_batch /
 function_angle_batch, the C++ veneer's overloads): every value equals (==) what the single call returns on the same
 context - overlap launches, void jobs repeated through the list chain, chain-only calls, deduplicated <X, X> / <Y, Y>,
-chunked launches of thousands of jobs."""
+chunked launches of thousands of jobs.  A single call is a one-job batch (score_batch), so these comparisons show that a
+job's value does not depend on its company; the values themselves are pinned by the oracle test here and by the oracle and
+list-chain comparisons of test_gpu_parity.py."""
 import ctypes as C
 import os
 import subprocess
@@ -124,6 +126,34 @@ def test_pose_sweep_deduplicates_self_products():
     want = np.array([gpu.function_angle(da, db, T, 0.3, False) for T in Ts], np.float32)
     assert np.array_equal(got, want)
     assert len(set(got.tolist())) > 1
+
+
+def test_single_calls_run_as_one_job_batches():
+    P, src, tgt, init = cases.config2(n=2000)
+    K = P.nearest_neighbors_max  # 512: no row finds that many pairs at ell 0.3; at 0.5 some find more than 6
+    gpu = CvoGPU(params=P)
+    da, db = gpu.upload(src), gpu.upload(tgt)
+    gpu.inner_product_gpu(da, db, init, 0.3)
+    assert gpu.debug_last_score_batch() == (1, 0, 1)
+    gpu.function_angle(da, db, init, 0.3, True)
+    assert gpu.debug_last_score_batch() == (1, 0, 1)
+    gpu.function_angle(da, db, init, 0.3, False)
+    assert gpu.debug_last_score_batch() == (3, 0, 1)
+    gpu.function_angle(da, da, init, 0.3, False)  # <X, X> once
+    assert gpu.debug_last_score_batch() == (2, 0, 1)
+    P.nearest_neighbors_max = 6  # void: the chain repeats the call's evaluations
+    gpu.params = P
+    gpu.inner_product_gpu(da, db, init, 0.5)
+    assert gpu.debug_last_score_batch() == (1, 1, 2)
+    gpu.function_angle(da, db, init, 0.5, False)
+    assert gpu.debug_last_score_batch() == (3, 3, 2)
+    P.nearest_neighbors_max = K
+    gpu.params = P
+    gpu.set_option("IP_CHAIN", "1")
+    gpu.inner_product_gpu(da, db, init, 0.3)
+    assert gpu.debug_last_score_batch() == (0, 1, 1)
+    gpu.function_angle(da, db, init, 0.3, False)
+    assert gpu.debug_last_score_batch() == (0, 3, 1)
 
 
 def test_batch_against_the_oracle(oracle):

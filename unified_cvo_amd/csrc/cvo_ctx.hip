@@ -89,14 +89,11 @@ PairLayout make_layout(int N, int M, int Kmax, int trace_capacity, bool long_lis
 
 void free_workspace(cvo_ctx* c) {
   if (c->arena) (void)hipFree(c->arena);
-  if (c->d_ov) (void)hipFree(c->d_ov);
-  if (c->h_ov) (void)hipHostFree(c->h_ov);
-  c->d_ov = c->h_ov = nullptr;
-  c->ov_tiles_cap = 0;
   if (c->d_sb) (void)hipFree(c->d_sb);
+  if (c->d_sb_table) (void)hipFree(c->d_sb_table);
   if (c->h_sb) (void)hipHostFree(c->h_sb);
   if (c->h_sb_res) (void)hipHostFree(c->h_sb_res);
-  c->d_sb = c->h_sb = c->h_sb_res = nullptr;
+  c->d_sb = c->d_sb_table = c->h_sb = c->h_sb_res = nullptr;
   c->sb_jobs_cap = c->sb_tiles_cap = 0;
   if (c->d_ctl) (void)hipFree(c->d_ctl);
   if (c->h_ctl) (void)hipHostFree(c->h_ctl);

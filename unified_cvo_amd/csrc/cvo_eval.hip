@@ -1,4 +1,6 @@
-// cvo_eval.hip -- single evaluations: inner_product_gpu / function_angle in one launch of k_overlap or through the list chain, run_single_eval for the association exports; their batched forms (k_overlap_table, cvo_*_batch).
+// cvo_eval.hip -- scores: inner_product_gpu / function_angle, one job (cvo_inner_product / cvo_function_angle) or many
+// (cvo_*_batch), all through score_batch: k_overlap (k_overlap_entry for up to three evaluations, k_overlap_table for more)
+// or the list chain; run_single_eval for the association exports.
 // A SECTION of the one translation unit cvo_hip.hip (which includes the sections in dependency order and says why it is one
 // unit); not compiled on its own.  Shared declarations: cvo_internal.h.
 namespace {
@@ -21,11 +23,8 @@ int run_single_eval(cvo_ctx* ctx, const cvo_params_t* params, const cvo_cloud* s
   return CVO_OK;
 }
 
-// inner_product_gpu for n (<= 8) pairs in ONE chain: INIT, the rebuild trio, [k_assoc_dense], k_assoc whose last block
-// posts A_sum to pinned host memory - one upload, one graph launch, one synchronisation.  The three inner products of the
-// exact function_angle (CvoGPU.cu:1835-1837) are such a batch.  Every value is what the one-pair path returns.
-// The inner products of a call in one launch of k_overlap (cvo_k_overlap.h).  *void_out: some row found more than
-// nearest_neighbors_max pairs - its first-K truncation needs the hits in ascending original index, i.e. the list chain.
+// Up to three evaluations in one launch of k_overlap (cvo_k_overlap.h) with the jobs as kernel ARGUMENTS: no table upload
+// precedes the launch.
 struct OverlapArgs {
   OverlapJob job[3];
   DevParams P;
@@ -107,89 +106,16 @@ int ensure_tiles(cvo_ctx* ctx, const cvo_cloud* c, hipStream_t s) {
   return CVO_OK;
 }
 
-int run_overlap_kernel(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_cloud* const* src, const cvo_cloud* const* tgt,
-                       const float* Tms, float ell, double* out, bool* void_out) {
-  int N = 0, M = 0;
-  int rc = check_call(ctx, params, n, src, tgt, nullptr, 1, ell, nullptr, &N, &M);
-  if (rc != CVO_OK) return rc;
-  if (n > 3) return fail(ctx, CVO_E_INVALID, "run_overlap_kernel: at most three pairs per launch");
-  hipStream_t stream = ctx->stream;
-  const int tiles_max = (N + 63) / 64;
-  if (!ctx->h_ov) HIP_TRY(ctx, hipHostMalloc(&ctx->h_ov, 64, hipHostMallocMapped | hipHostMallocCoherent));
-  if (tiles_max > ctx->ov_tiles_cap) {
-    if (ctx->d_ov) (void)hipFree(ctx->d_ov);
-    ctx->d_ov = nullptr;
-    ctx->ov_tiles_cap = 0;
-    const size_t bytes = 256 + 3 * sizeof(double) * (size_t)tiles_max;
-    HIP_TRY(ctx, hipMalloc(&ctx->d_ov, bytes));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_ov, 0, 256, stream));  // (the gate words; the kernel leaves them at zero)
-    ctx->ov_tiles_cap = tiles_max;
-  }
-  OverlapArgs A;
-  std::memset(&A, 0, sizeof(A));
-  A.P = make_dev_params(ctx, *params);
-  A.P.mode = 1;
-  bool all_hot = ctx_opt(ctx, "NO_ONEHOT") == nullptr;
-  for (int p = 0; p < n; p++) {
-    const cvo_cloud* X = src[p];
-    const cvo_cloud* Y = tgt[p];
-    if ((rc = ensure_tiles(ctx, X, stream)) != CVO_OK || (rc = ensure_tiles(ctx, Y, stream)) != CVO_OK) return rc;
-    all_hot = all_hot && X->lid != nullptr && Y->lid != nullptr;
-    OverlapJob& J = A.job[p];
-    fill_overlap_job(X, Y, Tms + 16 * (size_t)p, ell, params->nearest_neighbors_max, J);
-    J.part = reinterpret_cast<double*>(ctx->d_ov + 256) + (size_t)p * ctx->ov_tiles_cap;
-    J.gate = reinterpret_cast<int*>(ctx->d_ov) + 2 * p;
-    J.sum_host = reinterpret_cast<double*>(ctx->h_ov) + p;
-    J.over_host = reinterpret_cast<int*>(ctx->h_ov + 32) + p;
-  }
-  const int feat = call_feat(A.P, all_hot);
-  const dim3 grid(tiles_max, n), block(64 * OV_WAVES);
-  switch (feat) {
-    case FEAT_GEO: hipLaunchKernelGGL((k_overlap_entry<FEAT_GEO>), grid, block, 0, stream, A); break;
-    case FEAT_COL: hipLaunchKernelGGL((k_overlap_entry<FEAT_COL>), grid, block, 0, stream, A); break;
-    case FEAT_HOT: hipLaunchKernelGGL((k_overlap_entry<FEAT_HOT>), grid, block, 0, stream, A); break;
-    default: hipLaunchKernelGGL((k_overlap_entry<FEAT_ALL>), grid, block, 0, stream, A); break;
-  }
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  if (e != hipSuccess) {
-    (void)hipMemset(ctx->d_ov, 0, 256);  // (a launch that died may have left the gate words behind)
-    return fail(ctx, CVO_E_HIP, std::string("k_overlap: ") + hipGetErrorString(e));
-  }
-  *void_out = false;
-  for (int p = 0; p < n; p++) {
-    out[p] = reinterpret_cast<const volatile double*>(ctx->h_ov)[p];
-    if (reinterpret_cast<const volatile int*>(ctx->h_ov + 32)[p] != 0) *void_out = true;
-  }
-  ctx->last_pairs = 0;  // (no workspace of the list chain belongs to this call: the debug getters have nothing to read)
-  return CVO_OK;
-}
-
-int run_ip_chain(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_cloud* const* src, const cvo_cloud* const* tgt,
-                 const float* Tms, float ell, double* out);
-
-int run_inner_products(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_cloud* const* src, const cvo_cloud* const* tgt,
-                       const float* Tms, float ell, double* out) {
-  // One launch when the call has a geometric cut-off to cull by and nobody asked for the list chain (CVO_IP_CHAIN; the
-  // instrumented / verifying runs are the chain's); the chain when a row overflows K (first-K needs the original order).
-  if (ctx && params && params->is_using_geometry && !params->is_using_kdtree && n <= 3 && ctx_opt(ctx, "IP_CHAIN") == nullptr &&
-      ctx_opt(ctx, "VERIFY_LISTS") == nullptr && ctx_opt(ctx, "KERNEL_CLOCK") == nullptr && ctx_opt(ctx, "PHASE_TICKS") == nullptr) {
-    bool void_sum = false;
-    const int rc = run_overlap_kernel(ctx, params, n, src, tgt, Tms, ell, out, &void_sum);
-    if (rc != CVO_OK) return rc;
-    if (!void_sum) return CVO_OK;
-  }
-  return run_ip_chain(ctx, params, n, src, tgt, Tms, ell, out);
-}
-
-// The list chain for n (< 8: one sub-batch) inner products of one lengthscale (see run_inner_products).
+// The list chain for n (< 8: one sub-batch) inner products of one lengthscale: INIT, the rebuild trio, [k_assoc_dense],
+// k_assoc whose last block posts A_sum to pinned host memory - one upload, one graph launch, one synchronisation.  Every
+// value is what the one-pair chain returns (a pair's sums do not depend on its company).
 int run_ip_chain(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_cloud* const* src, const cvo_cloud* const* tgt,
                  const float* Tms, float ell, double* out) {
   BatchSetup S;
   DevParams dp;
   int rc = setup_batch(ctx, params, n, src, tgt, Tms, nullptr, 1, ell, &S, &dp);
   if (rc != CVO_OK) return rc;
-  if (S.G != 1) return fail(ctx, CVO_E_INVALID, "run_inner_products: too many pairs for one chain");
+  if (S.G != 1) return fail(ctx, CVO_E_INVALID, "run_ip_chain: too many pairs for one chain");
   const LaunchGeom& g = S.geom;
   constexpr int VI = cvo_ctx::GRAPH_VARIANTS - 1;
   GraphKey key;
@@ -235,16 +161,23 @@ int run_ip_chain(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_clou
   return CVO_OK;
 }
 
-// ---- batched scores (cvo_inner_product_batch / cvo_function_angle_batch) ------------------------------------------------
-// Every job's value is, bit for bit, what the single call returns: the same evaluations (k_overlap sums a job's row tiles in
-// tile order whatever shares the launch; the list chain's values do not depend on their company), the same void rule and
-// the same host arithmetic.  One launch of k_overlap_table and one synchronisation per chunk of the job list.
-constexpr int SB_CHUNK_JOBS = 1024;    // jobs per launch (pinned staging and device table are sized by it)
+// ---- scores: cvo_inner_product / cvo_function_angle (one job), cvo_inner_product_batch / cvo_function_angle_batch ------
+// A job's value does not depend on its company - k_overlap sums a job's row tiles in tile order whatever shares the launch,
+// the list chain's values do not depend on theirs - so every job of a batch gets, bit for bit, what the one-job call gets.
+// One launch of k_overlap and one synchronisation per chunk of the evaluation list.
+constexpr int SB_CHUNK_JOBS = 1024;    // jobs per launch (pinned results, device table and its staging are sized by it)
 constexpr int SB_CHUNK_TILES = 65536;  // row tiles per launch (4M source rows), unless one job alone has more
 constexpr size_t SB_START_BYTES = (sizeof(int) * (SB_CHUNK_JOBS + 1) + 255) / 256 * 256;
+constexpr size_t SB_TABLE_BYTES = SB_START_BYTES + (sizeof(OverlapJob) * SB_CHUNK_JOBS + 255) / 256 * 256;
+constexpr size_t SB_GATE_BYTES = (sizeof(int) * 2 * SB_CHUNK_JOBS + 255) / 256 * 256;
 
-// Device workspace [tile starts | job table | gate words | partials] and its staging copy [tile starts | job table]: the
-// prefix that a launch's table occupies goes up in one copy.  Gate words are zeroed here once; the kernel leaves them at zero.
+struct ScoreResult {  // what k_overlap posts for one evaluation: the sum and its void flag in one 16-byte slot
+  double sum;
+  int over;
+};
+
+// Device workspace [gate words | partials] and the pinned results (a small call's slots share one cache line).  Gate words
+// are zeroed here once; the kernel leaves them at zero.
 int score_ws_reserve(cvo_ctx* ctx, int tiles) {
   if (ctx->d_sb && tiles <= ctx->sb_tiles_cap) return CVO_OK;
   const int tiles_cap = std::max(tiles, ctx->sb_tiles_cap);
@@ -254,13 +187,10 @@ int score_ws_reserve(cvo_ctx* ctx, int tiles) {
   }
   ctx->d_sb = nullptr;
   ctx->sb_tiles_cap = ctx->sb_jobs_cap = 0;
-  const size_t table = SB_START_BYTES + align_up(sizeof(OverlapJob) * SB_CHUNK_JOBS, 256);
-  const size_t gates = align_up(sizeof(int) * 2 * SB_CHUNK_JOBS, 256);
-  HIP_TRY(ctx, hipMalloc(&ctx->d_sb, table + gates + sizeof(double) * (size_t)tiles_cap));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_sb + table, 0, gates, ctx->stream));
-  if (!ctx->h_sb) HIP_TRY(ctx, hipHostMalloc(&ctx->h_sb, table, hipHostMallocDefault));
+  HIP_TRY(ctx, hipMalloc(&ctx->d_sb, SB_GATE_BYTES + sizeof(double) * (size_t)tiles_cap));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_sb, 0, SB_GATE_BYTES, ctx->stream));
   if (!ctx->h_sb_res)
-    HIP_TRY(ctx, hipHostMalloc(&ctx->h_sb_res, (sizeof(double) + sizeof(int)) * SB_CHUNK_JOBS, hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(ctx, hipHostMalloc(&ctx->h_sb_res, sizeof(ScoreResult) * SB_CHUNK_JOBS, hipHostMallocMapped | hipHostMallocCoherent));
   ctx->sb_jobs_cap = SB_CHUNK_JOBS;
   ctx->sb_tiles_cap = tiles_cap;
   return CVO_OK;
@@ -277,76 +207,114 @@ struct ScoreEval {
   double ch = 0;       // ... its value there
 };
 
-// All evaluations through k_overlap_table: jobs largest first (a launch's tail is its largest job's last tiles), cut into
-// chunks of at most SB_CHUNK_JOBS jobs / SB_CHUNK_TILES tiles.
-int score_overlap(cvo_ctx* ctx, const cvo_params_t* params, std::vector<ScoreEval>& ev) {
+struct ScoreJob {
+  int ev[3] = {-1, -1, -1};  // its evaluations: <X, Y> (-1: an empty cloud, the job is 0) [, <X, X>, <Y, Y>]
+  bool chain = false;        // all of them from the list chain
+};
+
+// All evaluations through k_overlap, each with its own partials, gate words and pinned result slot in the score workspace.
+// Up to three (a single call's): ONE launch of k_overlap_entry on a grid of (largest tile count, n), no table copy in front
+// of it.  More: k_overlap_table, jobs largest first (a launch's tail is its largest job's last tiles), cut into chunks of at
+// most SB_CHUNK_JOBS jobs / SB_CHUNK_TILES tiles; the prefix of the pinned staging [tile starts | job table] that a chunk
+// occupies goes up in one copy.  That table and its staging are made by the first call that needs them.
+int score_overlap(cvo_ctx* ctx, const cvo_params_t* params, std::pmr::vector<ScoreEval>& ev) {
   hipStream_t stream = ctx->stream;
   DevParams P = make_dev_params(ctx, *params);
   P.mode = 1;
   bool all_hot = ctx_opt(ctx, "NO_ONEHOT") == nullptr;  // (FEAT_HOT and FEAT_ALL give the same bits: test_gpu_parity.py)
-  int rc;
+  int rc, tiles_max = 0;
+  size_t tiles_sum = 0;
   for (const ScoreEval& e : ev) {
     if ((rc = ensure_tiles(ctx, e.X, stream)) != CVO_OK || (rc = ensure_tiles(ctx, e.Y, stream)) != CVO_OK) return rc;
     all_hot = all_hot && e.X->lid != nullptr && e.Y->lid != nullptr;
+    tiles_max = std::max(tiles_max, (e.X->n + 63) / 64);
+    tiles_sum += (size_t)(e.X->n + 63) / 64;
   }
   const int feat = call_feat(P, all_hot);
-  std::vector<int> order(ev.size());
+  const bool by_args = ev.size() <= 3;
+  std::pmr::vector<int> order(ev.size(), ev.get_allocator());
   for (size_t i = 0; i < ev.size(); i++) order[i] = (int)i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ev[a].X->n > ev[b].X->n; });
-  const int biggest = order.empty() ? 0 : (ev[order[0]].X->n + 63) / 64;
-  if ((rc = score_ws_reserve(ctx, std::max(SB_CHUNK_TILES, biggest))) != CVO_OK) return rc;
-  int* h_start = reinterpret_cast<int*>(ctx->h_sb);
-  OverlapJob* h_jobs = reinterpret_cast<OverlapJob*>(ctx->h_sb + SB_START_BYTES);
-  const int* d_start = reinterpret_cast<const int*>(ctx->d_sb);
-  const OverlapJob* d_jobs = reinterpret_cast<const OverlapJob*>(ctx->d_sb + SB_START_BYTES);
-  const size_t table = SB_START_BYTES + align_up(sizeof(OverlapJob) * SB_CHUNK_JOBS, 256);
-  int* d_gate = reinterpret_cast<int*>(ctx->d_sb + table);
-  double* d_part = reinterpret_cast<double*>(ctx->d_sb + table + align_up(sizeof(int) * 2 * SB_CHUNK_JOBS, 256));
-  double* h_sum = reinterpret_cast<double*>(ctx->h_sb_res);
-  int* h_over = reinterpret_cast<int*>(ctx->h_sb_res + sizeof(double) * SB_CHUNK_JOBS);
+  if (!by_args) std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ev[a].X->n > ev[b].X->n; });
+  if ((rc = score_ws_reserve(ctx, by_args ? (int)tiles_sum : std::max(SB_CHUNK_TILES, tiles_max))) != CVO_OK) return rc;
+  OverlapArgs A;
+  std::memset(&A, 0, sizeof(A));
+  A.P = P;
+  OverlapJob* jobs = A.job;
+  int* h_start = nullptr;
+  if (!by_args) {
+    if (!ctx->d_sb_table) HIP_TRY(ctx, hipMalloc(&ctx->d_sb_table, SB_TABLE_BYTES));
+    if (!ctx->h_sb) HIP_TRY(ctx, hipHostMalloc(&ctx->h_sb, SB_TABLE_BYTES, hipHostMallocDefault));
+    h_start = reinterpret_cast<int*>(ctx->h_sb);
+    jobs = reinterpret_cast<OverlapJob*>(ctx->h_sb + SB_START_BYTES);
+  }
+  const int* d_start = reinterpret_cast<const int*>(ctx->d_sb_table);
+  const OverlapJob* d_jobs = reinterpret_cast<const OverlapJob*>(ctx->d_sb_table + SB_START_BYTES);
+  int* d_gate = reinterpret_cast<int*>(ctx->d_sb);
+  double* d_part = reinterpret_cast<double*>(ctx->d_sb + SB_GATE_BYTES);
+  ScoreResult* h_res = reinterpret_cast<ScoreResult*>(ctx->h_sb_res);
   for (size_t pos = 0; pos < order.size();) {
     int n = 0, tiles = 0;
     while (pos + n < order.size() && n < SB_CHUNK_JOBS) {
       const ScoreEval& e = ev[order[pos + n]];
       const int t = (e.X->n + 63) / 64;
       if (n > 0 && tiles + t > ctx->sb_tiles_cap) break;
-      OverlapJob& J = h_jobs[n];
+      OverlapJob& J = jobs[n];
       std::memset(&J, 0, sizeof(J));
       fill_overlap_job(e.X, e.Y, e.T, e.ell, params->nearest_neighbors_max, J);
       J.part = d_part + tiles;
       J.gate = d_gate + 2 * n;
-      J.sum_host = h_sum + n;
-      J.over_host = h_over + n;
-      h_start[n] = tiles;
+      J.sum_host = &h_res[n].sum;
+      J.over_host = &h_res[n].over;
+      if (!by_args) h_start[n] = tiles;
       tiles += t;
       n++;
     }
-    h_start[n] = tiles;
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sb, ctx->h_sb, SB_START_BYTES + sizeof(OverlapJob) * (size_t)n, hipMemcpyHostToDevice, stream));
-    const dim3 grid(tiles), block(64 * OV_WAVES);
-    switch (feat) {
-      case FEAT_GEO: hipLaunchKernelGGL((k_overlap_table<FEAT_GEO>), grid, block, 0, stream, d_jobs, d_start, n, P); break;
-      case FEAT_COL: hipLaunchKernelGGL((k_overlap_table<FEAT_COL>), grid, block, 0, stream, d_jobs, d_start, n, P); break;
-      case FEAT_HOT: hipLaunchKernelGGL((k_overlap_table<FEAT_HOT>), grid, block, 0, stream, d_jobs, d_start, n, P); break;
-      default: hipLaunchKernelGGL((k_overlap_table<FEAT_ALL>), grid, block, 0, stream, d_jobs, d_start, n, P); break;
+    const dim3 block(64 * OV_WAVES);
+    if (by_args) {
+      const dim3 grid(tiles_max, n);
+      switch (feat) {
+        case FEAT_GEO: hipLaunchKernelGGL((k_overlap_entry<FEAT_GEO>), grid, block, 0, stream, A); break;
+        case FEAT_COL: hipLaunchKernelGGL((k_overlap_entry<FEAT_COL>), grid, block, 0, stream, A); break;
+        case FEAT_HOT: hipLaunchKernelGGL((k_overlap_entry<FEAT_HOT>), grid, block, 0, stream, A); break;
+        default: hipLaunchKernelGGL((k_overlap_entry<FEAT_ALL>), grid, block, 0, stream, A); break;
+      }
+    } else {
+      h_start[n] = tiles;
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sb_table, ctx->h_sb, SB_START_BYTES + sizeof(OverlapJob) * (size_t)n, hipMemcpyHostToDevice,
+                                  stream));
+      const dim3 grid(tiles);
+      switch (feat) {
+        case FEAT_GEO: hipLaunchKernelGGL((k_overlap_table<FEAT_GEO>), grid, block, 0, stream, d_jobs, d_start, n, P); break;
+        case FEAT_COL: hipLaunchKernelGGL((k_overlap_table<FEAT_COL>), grid, block, 0, stream, d_jobs, d_start, n, P); break;
+        case FEAT_HOT: hipLaunchKernelGGL((k_overlap_table<FEAT_HOT>), grid, block, 0, stream, d_jobs, d_start, n, P); break;
+        default: hipLaunchKernelGGL((k_overlap_table<FEAT_ALL>), grid, block, 0, stream, d_jobs, d_start, n, P); break;
+      }
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e != hipSuccess) {
       (void)hipMemset(d_gate, 0, sizeof(int) * 2 * SB_CHUNK_JOBS);  // (a launch that died may have left gate words behind)
-      return fail(ctx, CVO_E_HIP, std::string("k_overlap_table: ") + hipGetErrorString(e));
+      return fail(ctx, CVO_E_HIP, std::string(by_args ? "k_overlap: " : "k_overlap_table: ") + hipGetErrorString(e));
     }
     for (int i = 0; i < n; i++) {
       ScoreEval& r = ev[order[pos + i]];
-      r.ov = reinterpret_cast<const volatile double*>(h_sum)[i];
-      r.over = reinterpret_cast<const volatile int*>(h_over)[i] != 0;
+      const volatile ScoreResult& v = h_res[i];
+      r.ov = v.sum;
+      r.over = v.over != 0;
     }
     ctx->last_score_overlap += n;
     ctx->last_score_launches++;
     pos += n;
   }
-  ctx->last_pairs = 0;  // (as run_overlap_kernel: no workspace of the list chain belongs to this call)
+  ctx->last_pairs = 0;  // (no workspace of the list chain belongs to this call: the debug getters have nothing to read)
   return CVO_OK;
+}
+
+// Calls the list chain evaluates whole: no geometric cut-off for k_overlap to cull by, or a context that asks for the chain
+// (CVO_IP_CHAIN; the instrumented / verifying runs are the chain's).
+bool chain_only(const cvo_ctx* ctx, const cvo_params_t* params) {
+  return !params->is_using_geometry || ctx_opt(ctx, "IP_CHAIN") != nullptr || ctx_opt(ctx, "VERIFY_LISTS") != nullptr ||
+         ctx_opt(ctx, "KERNEL_CLOCK") != nullptr || ctx_opt(ctx, "PHASE_TICKS") != nullptr;
 }
 
 // kind: 0 inner product, 1 approximate function_angle, 2 exact function_angle.  Validates the whole call before any device
@@ -359,8 +327,11 @@ int score_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_jobs, const cvo_
   if (ctx->queue_open) return fail(ctx, CVO_E_INVALID, "a batch queue is open on this context (cvo_batch_close it first)");
   if (params->is_using_kdtree)
     return fail(ctx, CVO_E_UNSUPPORTED, "is_using_kdtree=1 is out of scope (SURVEY.md section 2, row 11)");
-  std::vector<int> live;  // jobs with two non-empty clouds (the others are 0, as the single call returns)
-  std::vector<const cvo_cloud*> ls, lt;
+  // the call's bookkeeping lives in `scratch` while it fits (a single call allocates nothing), on the heap beyond
+  alignas(std::max_align_t) char scratch[4096];
+  std::pmr::monotonic_buffer_resource mem(scratch, sizeof(scratch));
+  std::pmr::vector<int> live(&mem);  // jobs with two non-empty clouds (the others are 0, as the single call returns)
+  std::pmr::vector<const cvo_cloud*> ls(&mem), lt(&mem);
   for (int k = 0; k < n_jobs; k++) {
     if (!sources[k] || !targets[k]) return fail(ctx, CVO_E_INVALID, "null cloud");
     if (sources[k]->n == 0 || targets[k]->n == 0) continue;
@@ -369,21 +340,24 @@ int score_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_jobs, const cvo_
     lt.push_back(targets[k]);
   }
   ctx->last_score_overlap = ctx->last_score_chain = ctx->last_score_launches = 0;
-  if (!live.empty()) {
+  const bool chain_all = chain_only(ctx, params);
+  if (live.empty()) {
+    if (params->nearest_neighbors_max <= 0) return fail(ctx, CVO_E_INVALID, "nearest_neighbors_max must be > 0");
+  } else if (live.size() > 1 || !chain_all) {
+    // (one chain-only job: its one run_ip_chain makes this check_call on the same clouds before any device work)
     int N = 0, M = 0;
     const int rc = check_call(ctx, params, (int)live.size(), ls.data(), lt.data(), nullptr, 1, ell[live[0]], nullptr, &N, &M);
     if (rc != CVO_OK) return rc;
     for (int k : live)  // (check_call's lengthscale rule, for every job's own ell)
       if (!(std::isfinite(ell[k]) && ell[k] >= 1e-30f && ell[k] <= 1e15f))
         return fail(ctx, CVO_E_INVALID, "lengthscale outside [1e-30, 1e15] (ell_init / ell_min / the ell of the call)");
-  } else if (params->nearest_neighbors_max <= 0) {
-    return fail(ctx, CVO_E_INVALID, "nearest_neighbors_max must be > 0");
   }
   static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   // the evaluations: <X, Y> per job; the exact function_angle's <X, X> / <Y, Y> once per (cloud, ell)
-  std::vector<ScoreEval> ev;
-  std::vector<int> jev(3 * (size_t)n_jobs, -1);
-  std::map<std::pair<const cvo_cloud*, uint32_t>, int> self_ev;
+  std::pmr::vector<ScoreEval> ev(&mem);
+  ev.reserve(live.size() * (kind == 2 ? 3 : 1));
+  std::pmr::vector<ScoreJob> jobs(n_jobs, &mem);
+  std::pmr::map<std::pair<const cvo_cloud*, uint32_t>, int> self_ev(&mem);
   auto self_eval = [&](const cvo_cloud* c, float l) {
     uint32_t bits;
     std::memcpy(&bits, &l, 4);
@@ -394,31 +368,27 @@ int score_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_jobs, const cvo_
     return (int)ev.size() - 1;
   };
   for (int k : live) {
-    jev[3 * k] = (int)ev.size();
+    jobs[k].ev[0] = (int)ev.size();
     ev.push_back(ScoreEval{sources[k], targets[k], T + 16 * (size_t)k, ell[k]});
     if (kind == 2) {
-      jev[3 * k + 1] = self_eval(sources[k], ell[k]);
-      jev[3 * k + 2] = self_eval(targets[k], ell[k]);
+      jobs[k].ev[1] = self_eval(sources[k], ell[k]);
+      jobs[k].ev[2] = self_eval(targets[k], ell[k]);
     }
   }
-  // the single call's path: one k_overlap launch unless the call has no geometric cut-off or the context asks for the chain
-  const bool chain_all = !params->is_using_geometry || ctx_opt(ctx, "IP_CHAIN") != nullptr || ctx_opt(ctx, "VERIFY_LISTS") != nullptr ||
-                         ctx_opt(ctx, "KERNEL_CLOCK") != nullptr || ctx_opt(ctx, "PHASE_TICKS") != nullptr;
   int rc;
   if (!chain_all && !ev.empty() && (rc = score_overlap(ctx, params, ev)) != CVO_OK) return rc;
   // A job is void when one of ITS evaluations is (the exact function_angle: all three then come from the chain).
-  std::vector<char> job_chain(n_jobs, 0);
   for (int k : live) {
-    bool v = chain_all;
-    for (int i = 0; i < 3; i++) v = v || (jev[3 * k + i] >= 0 && ev[jev[3 * k + i]].over);
-    job_chain[k] = v;
-    if (v)
+    ScoreJob& J = jobs[k];
+    J.chain = chain_all;
+    for (int i = 0; i < 3; i++) J.chain = J.chain || (J.ev[i] >= 0 && ev[J.ev[i]].over);
+    if (J.chain)
       for (int i = 0; i < 3; i++)
-        if (jev[3 * k + i] >= 0) ev[jev[3 * k + i]].chain = true;
+        if (J.ev[i] >= 0) ev[J.ev[i]].chain = true;
   }
   // the chain's evaluations, in groups of up to seven of one lengthscale (one sub-batch, one synchronisation each)
   {
-    std::map<uint32_t, std::vector<int>> by_ell;
+    std::pmr::map<uint32_t, std::pmr::vector<int>> by_ell(&mem);
     for (int i = 0; i < (int)ev.size(); i++)
       if (ev[i].chain) {
         uint32_t bits;
@@ -444,15 +414,20 @@ int score_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_jobs, const cvo_
         ctx->last_score_launches++;
       }
   }
-  // the single calls' host arithmetic (cvo_inner_product / cvo_function_angle)
-  std::vector<float> res(n_jobs, 0.f);
-  for (int k : live) {
+  // the host arithmetic of inner_product_gpu / function_angle (CvoGPU.cu:1814-1846); nothing fails from here on, so `out`
+  // is written only when every job has its value
+  for (int k = 0; k < n_jobs; k++) {
+    const ScoreJob& J = jobs[k];
     auto val = [&](int i) {
-      const ScoreEval& e = ev[jev[3 * k + i]];
-      return job_chain[k] ? e.ch : e.ov;
+      const ScoreEval& e = ev[J.ev[i]];
+      return J.chain ? e.ch : e.ov;
     };
+    if (J.ev[0] < 0) {  // an empty cloud
+      out[k] = 0.f;
+      continue;
+    }
     if (kind == 0) {
-      res[k] = (float)val(0);
+      out[k] = (float)val(0);
       continue;
     }
     float fxfz = (float)val(0), fx_norm, fz_norm;
@@ -463,9 +438,8 @@ int score_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_jobs, const cvo_
       fx_norm = std::sqrt((float)val(1));
       fz_norm = std::sqrt((float)val(2));
     }
-    res[k] = fxfz / (fx_norm * fz_norm);
+    out[k] = fxfz / (fx_norm * fz_norm);
   }
-  if (n_jobs > 0) std::memcpy(out, res.data(), sizeof(float) * (size_t)n_jobs);
   return CVO_OK;
 }
 
@@ -487,49 +461,18 @@ int cvo_inner_product(cvo_ctx* ctx, const cvo_params_t* params, const cvo_cloud*
     *out = 0.f;
     return CVO_OK;
   }
-  const cvo_cloud* src[1] = {source};
-  const cvo_cloud* tgt[1] = {target};
-  double v = 0;
-  const int rc = run_inner_products(ctx, params, 1, src, tgt, T, ell, &v);
-  if (rc != CVO_OK) return rc;
-  *out = (float)v;
-  return CVO_OK;
+  return score_batch(ctx, params, 1, &source, &target, T, &ell, 0, out, "cvo_inner_product");
 }
 
 int cvo_function_angle(cvo_ctx* ctx, const cvo_params_t* params, const cvo_cloud* source, const cvo_cloud* target,
                        const float T[16], float ell, int is_approximate, float* out) {
-  // function_angle, CvoGPU.cu:1814-1846
   if (!ctx || !out || !T) return fail(ctx, CVO_E_INVALID, "cvo_function_angle: bad argument");
   if (!source || !target) return fail(ctx, CVO_E_INVALID, "null cloud");
   if (source->n == 0 || target->n == 0) {
     *out = 0.f;
     return CVO_OK;
   }
-  const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-  float fxfz = 0, fx_norm = 0, fz_norm = 0;
-  if (is_approximate) {
-    const int rc = cvo_inner_product(ctx, params, source, target, T, ell, &fxfz);
-    if (rc != CVO_OK) return rc;
-    fx_norm = (float)std::sqrt((double)source->n);
-    fz_norm = (float)std::sqrt((double)target->n);
-  } else {
-    // the three inner products of CvoGPU.cu:1829-1837 - <fx, fz>, <fx, fx>, <fz, fz> - as one three-pair batch: one chain
-    // of launches instead of three (each value is what its own call returns: a pair's sums do not depend on its company)
-    const cvo_cloud* src[3] = {source, source, target};
-    const cvo_cloud* tgt[3] = {target, source, target};
-    float Ts[48];
-    std::memcpy(Ts, T, sizeof(float) * 16);
-    std::memcpy(Ts + 16, identity, sizeof(float) * 16);
-    std::memcpy(Ts + 32, identity, sizeof(float) * 16);
-    double v[3] = {0, 0, 0};
-    const int rc = run_inner_products(ctx, params, 3, src, tgt, Ts, ell, v);
-    if (rc != CVO_OK) return rc;
-    fxfz = (float)v[0];
-    fx_norm = std::sqrt((float)v[1]);
-    fz_norm = std::sqrt((float)v[2]);
-  }
-  *out = fxfz / (fx_norm * fz_norm);
-  return CVO_OK;
+  return score_batch(ctx, params, 1, &source, &target, T, &ell, is_approximate ? 1 : 2, out, "cvo_function_angle");
 }
 
 int cvo_inner_product_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_jobs, const cvo_cloud* const* sources,

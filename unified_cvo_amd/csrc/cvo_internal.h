@@ -14,6 +14,7 @@
 #include <cstring>
 #include <deque>
 #include <map>
+#include <memory_resource>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -115,15 +116,12 @@ struct cvo_ctx {
   int cap_pairs = 0;
   std::vector<PairDesc> h_descs;
   std::vector<PairState> h_states;
-  // k_overlap (one-launch inner products): row-tile partials + gate words of up to three jobs (device), results (pinned)
-  char* d_ov = nullptr;
-  int ov_tiles_cap = 0;
-  char* h_ov = nullptr;
-  // batched scores (cvo_inner_product_batch / cvo_function_angle_batch, k_overlap_table): device job table + tile starts,
-  // row-tile partials and per-job gate words (zero between launches), their pinned staging copy and the pinned results;
-  // sized on first use, grown, freed with the context (see score_ws_reserve)
+  // scores (cvo_inner_product / cvo_function_angle and their batches, k_overlap): per-job gate words (zero between
+  // launches) + row-tile partials and the pinned results, sized on first use and grown (see score_ws_reserve); the device
+  // job table + tile starts of k_overlap_table and its pinned staging, made by the first call that launches it
   char* d_sb = nullptr;
-  char* h_sb = nullptr;      // staging of the job table (one copy per launch)
+  char* d_sb_table = nullptr;
+  char* h_sb = nullptr;      // staging of the job table (one copy per k_overlap_table launch)
   char* h_sb_res = nullptr;  // results: a double and a void flag per job (mapped, written by the device)
   int sb_jobs_cap = 0, sb_tiles_cap = 0;
   int last_score_overlap = 0, last_score_chain = 0, last_score_launches = 0;  // cvo_debug_last_score_batch

@@ -77,9 +77,9 @@ __device__ unsigned long long g_ov_ticks[4096][8];
 #else
 #define OV_T() 0ull
 #endif
-// (the body; the kernels proper - k_overlap_entry and k_overlap_table, cvo_eval.hip - hand it a job and the row tile this
-// block takes: k_overlap_entry one of the jobs it takes as kernel ARGUMENTS (no descriptor upload precedes the launch) and
-// blockIdx.x, k_overlap_table an entry of a device job table and the tile its flat block index maps to)
+// (the body; the kernels proper, both launched by score_overlap in cvo_eval.hip, hand it a job and the row tile this block
+// takes: k_overlap_entry - up to three evaluations - one of the jobs it takes as kernel ARGUMENTS (no table upload precedes
+// the launch) and blockIdx.x, k_overlap_table - more - an entry of a device job table and the tile its flat index maps to)
 template <int FEAT>
 __device__ __forceinline__ void k_overlap(const OverlapJob& Jr, const DevParams& P, const int tile) {
   const OverlapJob* __restrict__ J = &Jr;
