@@ -111,12 +111,13 @@ void free_workspace(cvo_ctx* c) {
 }
 
 void drop_graphs(cvo_ctx* c) {
-  for (int g = 0; g < cvo_ctx::MAX_GROUPS; g++)
-    for (int v = 0; v < cvo_ctx::GRAPH_VARIANTS; v++)
-      if (c->graph_exec[g][v]) {
-        (void)hipGraphExecDestroy(c->graph_exec[g][v]);
-        c->graph_exec[g][v] = nullptr;
-      }
+  auto drop = [](CachedGraph& cg) {
+    if (cg.exec) (void)hipGraphExecDestroy(cg.exec);
+    cg.exec = nullptr;
+  };
+  for (auto& group : c->graphs)
+    for (CachedGraph& cg : group) drop(cg);
+  drop(c->chain_graph);
 }
 
 int ensure_workspace(cvo_ctx* c, int n_pairs, size_t bytes_per_pair) {

@@ -117,41 +117,17 @@ int run_ip_chain(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_clou
   if (rc != CVO_OK) return rc;
   if (S.G != 1) return fail(ctx, CVO_E_INVALID, "run_ip_chain: too many pairs for one chain");
   const LaunchGeom& g = S.geom;
-  constexpr int VI = cvo_ctx::GRAPH_VARIANTS - 1;
-  GraphKey key;
-  key.n_pairs = n;
-  key.T = S.T;
-  key.gx = S.gx;
-  key.gy = S.gy;
-  key.nba = S.d.nblk_assoc;
-  key.npb = (int)((unsigned)g.npb + ((unsigned)g.dense_blocks << 20));  // (dense_blocks <= 2048: twelve bits)
-  key.idx16 = g.idx16 ? 1 : 0;
-  key.general = g.feat;
-  key.flags = (g.instr ? 1 : 0) | (99 << 24);
-  key.arena = g.arena.base;
-  key.stride256 = g.arena.stride256;
-  key.Npad = g.arena.Npad;
-  if (!(ctx->graph_exec[0][VI] && ctx->graph_key[0][VI] == key)) {
-    if (ctx->graph_exec[0][VI]) (void)hipGraphExecDestroy(ctx->graph_exec[0][VI]);
-    ctx->graph_exec[0][VI] = nullptr;
-    hipGraph_t gr = nullptr;
-    HIP_TRY(ctx, hipStreamBeginCapture(g.stream, hipStreamCaptureModeThreadLocal));
+  GraphKey key = graph_key(g, ChunkPlan{});
+  key.csplit = key.horizon_cap = 0;  // (no k_coeff, k_verify or lean iteration in the chain: see GraphKey)
+  key.verify = false;
+  rc = capture_graph(ctx, ctx->chain_graph, key, g.stream, nullptr, 0, "inner product graph", [&] {
     launch_init(ctx, g);
     launch_rebuild(ctx, g);
-    launch_dense(g.stream, g.feat, g.N, g.n_pairs, g.dense_blocks, ctx->d_descs, ctx->d_params, ctx->d_states);
+    launch_dense(g.stream, g.feat, g.wide, g.n_pairs, g.dense_blocks, ctx->d_descs, ctx->d_params, ctx->d_states);
     launch_assoc(g.stream, g.idx16, g.feat, g.instr, g.nba, g.n_pairs, ctx->d_descs, ctx->d_params, ctx->d_states, g.arena, 8);
-    const hipError_t e_launch = hipGetLastError();
-    hipError_t e = hipStreamEndCapture(g.stream, &gr);
-    if (e == hipSuccess && e_launch != hipSuccess) e = e_launch;
-    if (e == hipSuccess) e = hipGraphInstantiate(&ctx->graph_exec[0][VI], gr, nullptr, nullptr, 0);
-    if (gr) (void)hipGraphDestroy(gr);
-    if (e != hipSuccess) {
-      ctx->graph_exec[0][VI] = nullptr;
-      return fail(ctx, CVO_E_HIP, std::string("inner product graph: ") + hipGetErrorString(e));
-    }
-    ctx->graph_key[0][VI] = key;
-  }
-  HIP_TRY(ctx, hipGraphLaunch(ctx->graph_exec[0][VI], g.stream));
+  });
+  if (rc != CVO_OK) return rc;
+  HIP_TRY(ctx, hipGraphLaunch(ctx->chain_graph.exec, g.stream));
   HIP_TRY(ctx, hipStreamSynchronize(g.stream));
   const volatile double* res = reinterpret_cast<const volatile double*>(ctx->h_status[1]);
   for (int p = 0; p < n; p++) {

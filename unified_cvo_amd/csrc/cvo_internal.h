@@ -18,6 +18,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "cvo_kernels.h"
@@ -59,18 +60,46 @@ struct PairLayout {  // byte offsets of one pair's workspace inside the arena
       coef_part, shadow, trace, total;
 };
 
-static const char* const kGraphNames[8] = {"full", "lean", "short", "full-nodense", "calm", "lean+dense", "short+dense", "calm+dense"};
+// The chunk a sub-batch runs next (launch_chunk; chosen by choose_chunk, cvo_sched.hip).  Full: a rebuild opportunity and
+// k_assoc_dense in every iteration; full without dense: the same minus k_assoc_dense; lean / short lean: a rebuild
+// opportunity every `period` iterations; calm: one per chunk.  The lean kinds run k_assoc_dense too when `dense` is set.
+enum class ChunkKind { Full, FullNoDense, Lean, ShortLean, Calm };
+static const char* const kChunkNames[] = {"full", "full-nodense", "lean", "short", "calm"};
 
+struct ChunkPlan {
+  ChunkKind kind = ChunkKind::Full;
+  bool dense = false;
+  int U = 0;       // iterations
+  int period = 0;  // lean kinds: iterations per rebuild opportunity (the calm chunk's is U)
+  bool every_iteration() const { return kind == ChunkKind::Full || kind == ChunkKind::FullNoDense; }  // a rebuild opportunity
+};
+
+// Where the workspaces of a launch's pairs are (kernel arguments of the row-block kernels, see row_off_*)
+struct ArenaArg {
+  const char* base;    // workspace of the launch's first pair
+  unsigned stride256;  // bytes / 256 between consecutive pairs
+  int Npad;
+};
+
+// What a cached graph was captured with: the chunk plan and every field of LaunchGeom its launches read, except k_verify's
+// grid (the kernel loops over the rows, so a graph captured at another N verifies the same rows).  The list chain
+// (run_ip_chain) leaves the plan, csplit, horizon_cap and verify at their defaults: it launches no k_coeff, k_verify or
+// lean iteration.  Device pointers of the context are not in it: reallocating them drops every graph (drop_graphs).
 struct GraphKey {
-  int n_pairs = 0, p0 = 0, T = 0, gx = 0, gy = 0, nba = 0, nbc = 0, npb = 0, idx16 = 0, general = 0, U = 0, flags = 0;
-  const void* arena = nullptr;  // kernel arguments of the row-block kernels (ArenaArg)
-  unsigned stride256 = 0;
-  int Npad = 0;
-  bool operator==(const GraphKey& o) const {
-    return n_pairs == o.n_pairs && p0 == o.p0 && T == o.T && gx == o.gx && gy == o.gy && nba == o.nba &&
-           nbc == o.nbc && npb == o.npb && idx16 == o.idx16 && general == o.general && U == o.U && flags == o.flags && arena == o.arena &&
-           stride256 == o.stride256 && Npad == o.Npad;
+  ChunkPlan plan;
+  int n_pairs = 0, p0 = 0, T = 0, gx = 0, gy = 0, npb = 0, nbl = 0, nba = 0, csplit = 0, dense_blocks = 0, horizon_cap = 0, feat = 0;
+  bool idx16 = false, wide = false, instr = false, verify = false;
+  ArenaArg arena{};
+  auto fields() const {
+    return std::tie(plan.kind, plan.dense, plan.U, plan.period, n_pairs, p0, T, gx, gy, npb, nbl, nba, csplit, dense_blocks,
+                    horizon_cap, feat, idx16, wide, instr, verify, arena.base, arena.stride256, arena.Npad);
   }
+  bool operator==(const GraphKey& o) const { return fields() == o.fields(); }
+};
+
+struct CachedGraph {
+  hipGraphExec_t exec = nullptr;
+  GraphKey key;
 };
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -135,12 +164,12 @@ struct cvo_ctx {
   hipStream_t gstream[MAX_GROUPS] = {};
   hipEvent_t ev_chk[2][MAX_GROUPS] = {};
   hipEvent_t ev_fork = nullptr, ev_join[MAX_GROUPS] = {};
-  // graph cache (one per group)
-  // [group][0 = full chunk, 1 = lean chunk, 2 = short lean chunk, 3 = full chunk without k_assoc_dense, 4 = calm chunk (lean, one rebuild opportunity); + 5 for the instrumented kernels (CVO_KERNEL_CLOCK /
-  // CVO_PHASE_TICKS), cached side by side so that a caller can time single steps of a loop without re-capturing]
-  static constexpr int GRAPH_VARIANTS = 49;  // 8 graphs (see cvo_align_batch) x instrumented or not x 3 chunk lengths + the inner-product chain
-  hipGraphExec_t graph_exec[MAX_GROUPS][GRAPH_VARIANTS] = {};
-  GraphKey graph_key[MAX_GROUPS][GRAPH_VARIANTS] = {};
+  // graph cache: per group, one entry per chunk-graph slot (graph_slot: the eight chunks x instrumented kernels
+  // (CVO_KERNEL_CLOCK / CVO_PHASE_TICKS) or not x the three chunk lengths, so that a caller can time single steps of a
+  // loop without re-capturing), each replaced when its key changes; and the list chain of run_ip_chain
+  static constexpr int GRAPH_SLOTS = 48;
+  CachedGraph graphs[MAX_GROUPS][GRAPH_SLOTS];
+  CachedGraph chain_graph;
   int last_chunks = 0, last_lean_launches = 0, last_full_launches = 0;
   // last call (debug hooks)
   int last_pairs = 0;

@@ -36,22 +36,14 @@ void launch_scan(hipStream_t s, int T, dim3 grid, const PairDesc* descs, const D
 // 1-D grid of the XCD-aware row-block kernels (see pair_block)
 inline dim3 row_grid(int nblk, int n_pairs) { return dim3((unsigned)(nblk * ((n_pairs + 7) / 8 * 8))); }
 
-void launch_list(hipStream_t s, bool idx16, int N, int n_pairs, const PairDesc* descs, const DevParams* dp,
+void launch_list(hipStream_t s, bool idx16, int nblk, int n_pairs, const PairDesc* descs, const DevParams* dp,
                  const PairState* st) {
-  const int nblk = (N + LIST_THREADS - 1) / LIST_THREADS;
   const dim3 blk(LIST_THREADS), grid = row_grid(nblk, n_pairs);
   if (idx16)
     hipLaunchKernelGGL((k_list<unsigned short, ASSOC_CAP16>), grid, blk, 0, s, descs, dp, st, nblk, n_pairs);
   else
     hipLaunchKernelGGL((k_list<int, ASSOC_CAP32>), grid, blk, 0, s, descs, dp, st, nblk, n_pairs);
 }
-
-// Where the workspaces of a launch's pairs are (kernel arguments of the row-block kernels, see row_off_*)
-struct ArenaArg {
-  const char* base;    // workspace of the launch's first pair
-  unsigned stride256;  // bytes / 256 between consecutive pairs
-  int Npad;
-};
 
 // instr: the instantiation with time stamps (CVO_KERNEL_CLOCK / CVO_PHASE_TICKS); the production kernels have none
 template <typename IdxT, int CAP, int FEAT>
@@ -98,9 +90,9 @@ void launch_coeff(hipStream_t s, bool instr, int nblk, int split, int n_pairs, c
 }
 
 // CVO_VERIFY_LISTS: literal re-derivation of every row after the association of an iteration (k_verify)
-void launch_verify(hipStream_t s, int feat, int N, int n_pairs, const PairDesc* descs, const DevParams* dp, const int* st,
+void launch_verify(hipStream_t s, int feat, int nblk, int n_pairs, const PairDesc* descs, const DevParams* dp, const int* st,
                    int lean) {
-  const dim3 grid((unsigned)std::min((N + 3) / 4, 2048), (unsigned)n_pairs);
+  const dim3 grid((unsigned)nblk, (unsigned)n_pairs);
   // (the self-check always takes the general form of the semantic kernel: one-hot rows through the row arithmetic)
   if (feat != FEAT_GEO)
     hipLaunchKernelGGL(k_verify<FEAT_ALL>, grid, dim3(256), 0, s, descs, dp, st, lean);
@@ -108,11 +100,12 @@ void launch_verify(hipStream_t s, int feat, int N, int n_pairs, const PairDesc* 
     hipLaunchKernelGGL(k_verify<FEAT_GEO>, grid, dim3(256), 0, s, descs, dp, st, lean);
 }
 
-void launch_dense(hipStream_t s, int feat, int N, int n_pairs, int dense_blocks, const PairDesc* descs, const DevParams* dp,
+// a small pair solved alone has a block per overflow row (dense_blocks_for): k_assoc_dense's instantiation with the wide-row phase
+inline bool dense_wide(int N, int n_pairs) { return n_pairs <= 1 && N <= DENSE_BLOCKS_MAX / 2; }
+
+void launch_dense(hipStream_t s, int feat, bool wide, int n_pairs, int dense_blocks, const PairDesc* descs, const DevParams* dp,
                   const PairState* st) {
   const dim3 grid(dense_blocks, n_pairs);
-  // a small pair solved alone has a block per overflow row (dense_blocks_for): the instantiation with the wide-row phase
-  const bool wide = n_pairs <= 1 && N <= DENSE_BLOCKS_MAX / 2;
 #define CVO_LAUNCH_DENSE(F)                                                                                  \
   do {                                                                                                       \
     if (wide)                                                                                                \
@@ -138,11 +131,12 @@ inline int call_feat(const DevParams& dp, bool all_one_hot) {
 }
 
 struct LaunchGeom {
-  int n_pairs, p0, T, gx, gy, nba, nbc, npb, N, csplit;
+  int n_pairs, p0, T, gx, gy, nba, npb, csplit;
+  int nbl, nbv;  // blocks of k_list (LIST_THREADS rows each) and k_verify (grid x) for the largest source cloud
   int dense_blocks = DENSE_BLOCKS_MIN;  // k_assoc_dense grid x = PairDesc::dense_blocks of every pair of the launch
-  int group = 0;        // sub-batch index (its stream)
   int horizon_cap = 1 << 20;  // the lean graph's period (DevParams::lean_U)
   bool idx16, instr, verify;
+  bool wide;  // k_assoc_dense's wide-row instantiation (dense_wide)
   int feat = FEAT_GEO;  // which instantiation of the association kernels the call needs (call_feat)
   hipStream_t stream;
   ArenaArg arena;  // of pair p0
@@ -159,7 +153,7 @@ void launch_rebuild(cvo_ctx* c, const LaunchGeom& g) {
   const PairState* states = c->d_states + g.p0;
   hipLaunchKernelGGL(k_prep, dim3(g.npb, g.n_pairs), dim3(PREP_THREADS), 0, g.stream, descs, c->d_params, states);
   launch_scan(g.stream, g.T, dim3(g.gx, g.gy, g.n_pairs), descs, c->d_params, states, 0);
-  launch_list(g.stream, g.idx16, g.N, g.n_pairs, descs, c->d_params, states);
+  launch_list(g.stream, g.idx16, g.nbl, g.n_pairs, descs, c->d_params, states);
 }
 
 // One optimiser iteration over the current lists: association, [overflow rows], coefficients + update (the last
@@ -172,10 +166,10 @@ void launch_core(cvo_ctx* c, const LaunchGeom& g, bool lean, int flags, bool den
   const int* st = c->d_status + 2 * g.p0;  // the sub-batch's status words (see setup_batch)
   const bool lean_dense = lean && dense;
   // rows beyond their cached lists first (a wave per row; per-row results), then every row's reduction in k_assoc
-  if (!lean || dense) launch_dense(g.stream, g.feat, g.N, g.n_pairs, g.dense_blocks, descs, c->d_params, c->d_states + g.p0);
+  if (!lean || dense) launch_dense(g.stream, g.feat, g.wide, g.n_pairs, g.dense_blocks, descs, c->d_params, c->d_states + g.p0);
   launch_assoc(g.stream, g.idx16, g.feat, g.instr, g.nba, g.n_pairs, descs, c->d_params, c->d_states + g.p0, g.arena,
                (lean ? 1 : 0) | (lean_dense ? 4 : 0));
-  if (g.verify) launch_verify(g.stream, g.feat, g.N, g.n_pairs, descs, c->d_params, st, (lean ? 1 : 0) | (lean_dense ? 4 : 0));
+  if (g.verify) launch_verify(g.stream, g.feat, g.nbv, g.n_pairs, descs, c->d_params, st, (lean ? 1 : 0) | (lean_dense ? 4 : 0));
   // ... their coefficient sums likewise (k_coeff_dense leaves per-row sums, k_coeff picks them up)
   if (!lean || dense)
     // (7 waves per SIMD against k_assoc_dense's 4: twice the blocks, so that a lone pair's rows get a wave each - the kernel
@@ -186,33 +180,58 @@ void launch_core(cvo_ctx* c, const LaunchGeom& g, bool lean, int flags, bool den
                flags | (lean ? 1 : 0) | (lean_dense ? 32 : 0) | (g.idx16 ? 0 : 64));
 }
 
-// A chunk of U iterations.  Full: every iteration can rebuild its candidate list and serve overflow rows.
-// Lean: rebuild opportunities only every lean_U iterations; pairs that need more wait for a full chunk.
-// lean_U == 0: the full chunk WITHOUT k_assoc_dense - a rebuild opportunity in every iteration with the full graph's
-// rebuild rule (no horizon), but a pair whose rows overflow their lists waits (and asks for the dense kernel: want = 4).
-// Large clouds run their fast first iterations here: the dense kernel, launched for nothing, is 5 us + a launch gap.
-void launch_chunk(cvo_ctx* c, const LaunchGeom& g, int U, bool lean, int lean_U, bool dense = false) {
-  if (lean && lean_U == 0) {
-    for (int u = 0; u < U; u++) {
+// A chunk (see ChunkPlan).  Full: every iteration can rebuild its candidate list and serve overflow rows.  Full without
+// dense: a rebuild opportunity in every iteration with the full graph's rebuild rule (no horizon), but a pair whose rows
+// overflow their lists waits (and asks for the dense kernel: want = 4); large clouds run their fast first iterations
+// here: the dense kernel, launched for nothing, is 5 us + a launch gap.  Lean kinds: rebuild opportunities only every
+// `period` iterations; pairs that need more wait for a full chunk.
+void launch_chunk(cvo_ctx* c, const LaunchGeom& g, const ChunkPlan& p) {
+  if (p.every_iteration()) {
+    for (int u = 0; u < p.U; u++) {
       launch_rebuild(c, g);
-      launch_core(c, g, true, 2);
+      launch_core(c, g, p.kind == ChunkKind::FullNoDense, 2);
     }
     return;
   }
-  if (!lean) {
-    for (int u = 0; u < U; u++) {
-      launch_rebuild(c, g);
-      launch_core(c, g, false, 2);
-    }
-    return;
-  }
-  for (int u = 0; u < U; u++) {
-    if (u % lean_U == 0) launch_rebuild(c, g);
-    const bool last = (u % lean_U == lean_U - 1) || u == U - 1;
+  for (int u = 0; u < p.U; u++) {
+    if (u % p.period == 0) launch_rebuild(c, g);
+    const bool last = (u % p.period == p.period - 1) || u == p.U - 1;
     // (horizon of the rebuild rule: the lean graph's period even in a calm chunk, whose one opportunity per chunk is a bet
     // on the list outliving the linear prediction - a pair that loses it waits for the next chunk)
-    launch_core(c, g, true, (last ? 2 : 0) | (std::min(lean_U, g.horizon_cap) << 8), dense);
+    launch_core(c, g, true, (last ? 2 : 0) | (std::min(p.period, g.horizon_cap) << 8), p.dense);
   }
+}
+
+GraphKey graph_key(const LaunchGeom& g, const ChunkPlan& plan) {
+  return {plan, g.n_pairs, g.p0, g.T, g.gx, g.gy, g.npb, g.nbl, g.nba, g.csplit, g.dense_blocks, g.horizon_cap, g.feat,
+          g.idx16, g.wide, g.instr, g.verify, g.arena};
+}
+
+// Makes `cg` hold a graph of what `launches` enqueues on stream s, unless it already holds one captured for `key`.  On
+// failure the n_flight streams of `flight` (other sub-batches may be in flight) are synchronised.
+template <typename Launches>
+int capture_graph(cvo_ctx* ctx, CachedGraph& cg, const GraphKey& key, hipStream_t s, const LaunchGeom* flight, int n_flight,
+                  const char* what, Launches&& launches) {
+  if (cg.exec && cg.key == key) return CVO_OK;
+  if (cg.exec) (void)hipGraphExecDestroy(cg.exec);
+  cg.exec = nullptr;
+  hipGraph_t gr = nullptr;
+  HIP_TRY(ctx, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  launches();
+  // (the capture is always ended, whatever the launches reported: a stream left in capture mode would poison
+  // every later call on this context)
+  const hipError_t e_launch = hipGetLastError();
+  hipError_t e = hipStreamEndCapture(s, &gr);
+  if (e == hipSuccess && e_launch != hipSuccess) e = e_launch;
+  if (e == hipSuccess) e = hipGraphInstantiate(&cg.exec, gr, nullptr, nullptr, 0);
+  if (gr) (void)hipGraphDestroy(gr);
+  if (e != hipSuccess) {
+    cg.exec = nullptr;
+    for (int q = 0; q < n_flight; q++) (void)hipStreamSynchronize(flight[q].stream);
+    return fail(ctx, CVO_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+  }
+  cg.key = key;
+  return CVO_OK;
 }
 
 }  // namespace

@@ -19,7 +19,6 @@ struct cvo_batch_queue {
   DevParams dp{};
   LoopCfg cfg{};
   int slots = 0, G = 1;
-  bool allow_lean = true, start_nodense = false, allow_calm = true;
   LaunchGeom geom[cvo_ctx::MAX_GROUPS];
   struct Job {
     long long ticket;
@@ -43,7 +42,8 @@ struct cvo_batch_queue {
   std::vector<Readout> readouts[cvo_ctx::MAX_GROUPS];
   std::map<long long, cvo_batch_result_t> done;
   long long next_ticket = 0, next_deliver = 0;
-  int launched[cvo_ctx::MAX_GROUPS] = {}, inspected[cvo_ctx::MAX_GROUPS] = {}, graph_next[cvo_ctx::MAX_GROUPS] = {};
+  int launched[cvo_ctx::MAX_GROUPS] = {}, inspected[cvo_ctx::MAX_GROUPS] = {};
+  ChunkPlan next[cvo_ctx::MAX_GROUPS];  // (kind and dense flag; queue_step gives it its length)
   int running[cvo_ctx::MAX_GROUPS] = {};  // occupied slots per group
   char* pinned = nullptr;                 // [slots] x (PairState out | PairDesc stage | PairState stage)
   PairState* h_out = nullptr;
@@ -54,16 +54,13 @@ struct cvo_batch_queue {
 
 namespace {
 
-int queue_group_of(const cvo_batch_queue* q, int p) {
-  int g = 0;
-  while (g + 1 < q->G && (int)((long)q->slots * (g + 1) / q->G) <= p) g++;
-  return g;
-}
+// The chunks a newcomer may join at once: a rebuild opportunity in every iteration, or every lean_U2 (see queue_step)
+inline bool queue_fast(const ChunkPlan& p) { return p.every_iteration() || p.kind == ChunkKind::ShortLean; }
 
 // Places `job` into free slot p: descriptor + initial state + k_update<INIT>, in stream order on the slot's sub-batch stream.
 int queue_fill(cvo_batch_queue* q, int p, const cvo_batch_queue::Job& job) {
   cvo_ctx* ctx = q->ctx;
-  const int g = queue_group_of(q, p);
+  const int g = group_of(q->slots, q->G, p);
   fill_pair(ctx, &q->S, &q->params, &q->opts, 0, 0.f, q->slots, p, job.X, job.Y, job.T, next_call_serial(), job.max_iter);
   q->h_desc_stage[p] = ctx->h_descs[p];
   q->h_state_stage[p] = ctx->h_states[p];
@@ -76,7 +73,7 @@ int queue_fill(cvo_batch_queue* q, int p, const cvo_batch_queue::Job& job) {
   q->slot[p].start_chunk = q->launched[g];
   q->slot[p].t0 = std::chrono::steady_clock::now();
   q->running[g]++;
-  q->graph_next[g] = q->start_nodense ? 3 : 0;  // a newcomer moves fast: a rebuild opportunity in every iteration
+  q->next[g] = first_chunk(q->cfg);  // a newcomer moves fast: a rebuild opportunity in every iteration
   q->n_refills++;
   return CVO_OK;
 }
@@ -110,11 +107,8 @@ int queue_step(cvo_batch_queue* q, int g, bool block, bool* progressed) {
         cvo_batch_result_t r{};
         r.ticket = ro[k].ticket;
         std::memcpy(r.transform, ps.out_T, sizeof(float) * 16);
-        r.info.iterations = ps.status ? ps.iterations : ps.k;
-        r.info.ret = ps.sync_err ? CVO_E_HIP : ps.ret;  // (a block partial never arrived: cvo_wave.h; never seen in practice)
-        r.info.final_ell = ps.ell;
-        r.info.final_num_neighbors = ps.K;
-        r.info.seconds = ro[k].seconds;
+        r.info = info_from_state(ps, ro[k].seconds);
+        if (ps.sync_err) r.info.ret = CVO_E_HIP;  // (a block partial never arrived: cvo_wave.h; never seen in practice)
         q->done[r.ticket] = r;
         ro[k] = ro.back();
         ro.pop_back();
@@ -124,12 +118,11 @@ int queue_step(cvo_batch_queue* q, int g, bool block, bool* progressed) {
     }
     // finished pairs: their state is read out behind everything enqueued so far; the slot goes to the next waiting pair
     const volatile int* hs = ctx->h_status[0] + 2 * p0;  // [status[ng] | want[ng]]
-    int want = -1;
-    bool dense = false;
+    GroupWant want;
     for (int k = 0; k < ng; k++) {
       cvo_batch_queue::Slot& sl = q->slot[p0 + k];
       if (sl.ticket < 0 || c < sl.start_chunk) {
-        if (sl.ticket >= 0) want = 2;  // (placed, not yet reported: still asks for the full graph)
+        if (sl.ticket >= 0) want.add(2);  // (placed, not yet reported: still asks for the full graph)
         continue;
       }
       if (hs[k] != 0) {
@@ -139,19 +132,16 @@ int queue_step(cvo_batch_queue* q, int g, bool block, bool* progressed) {
         sl.ticket = -1;
         q->running[g]--;
       } else {
-        const int w = hs[ng + k];
-        dense = dense || w == 4 || w >= 8;
-        want = std::max(want, w == 4 ? 2 : (w >= 8 ? w - 9 : w));
+        want.add(hs[ng + k]);
       }
     }
-    q->graph_next[g] = choose_graph(want, dense, q->allow_lean, q->start_nodense, q->allow_calm, q->cfg.lean_U2);
+    q->next[g] = choose_chunk(q->cfg, want);
     // Admission.  A newcomer moves fast: its lists last an iteration or two, so its sub-batch runs the full graph (six
     // launches per iteration, three of which find nothing to do for the settled pairs) until it has calmed down.  Free
     // slots are therefore refilled in cohorts: at once while the sub-batch runs a fast graph anyway or stands empty,
     // otherwise when a quarter of its slots have come free.
     if (!q->waiting.empty() && q->running[g] < ng) {
-      const int v = q->graph_next[g];
-      const bool fast = v == 0 || v == 3 || v == 2 || v == 6;
+      const bool fast = queue_fast(q->next[g]);
       int den = 4;  // (QUEUE_ADMIT: the share of free slots - 1 / den - at which a settled sub-batch takes newcomers)
       if (const char* e = ctx_opt(ctx, "QUEUE_ADMIT")) den = std::max(1, atoi(e));
       if (fast || q->running[g] == 0 || den * (ng - q->running[g]) >= ng)
@@ -166,16 +156,15 @@ int queue_step(cvo_batch_queue* q, int g, bool block, bool* progressed) {
   }
   // ---- launch
   if (q->running[g] > 0 && q->launched[g] - q->inspected[g] < 2) {
-    const int v = q->graph_next[g];
-    const bool fast = v == 0 || v == 3 || v == 2 || v == 6;
-    const int Uc = fast ? q->cfg.U : q->cfg.U_late;
-    int rc = ensure_graph(ctx, q->S, q->geom, q->G, q->cfg, g, v, Uc);
+    const ChunkPlan p = sized_chunk(q->cfg, q->next[g], queue_fast(q->next[g]) ? q->cfg.U : q->cfg.U_late);
+    hipGraphExec_t exec = nullptr;
+    const int rc = chunk_graph(ctx, q->geom, q->G, q->cfg, g, p, &exec);
     if (rc != CVO_OK) return rc;
-    HIP_TRY(ctx, hipGraphLaunch(ctx->graph_exec[g][graph_slot(q->cfg, v, Uc)], st));
+    HIP_TRY(ctx, hipGraphLaunch(exec, st));
     HIP_TRY(ctx, hipEventRecord(ctx->ev_chk[q->launched[g] & 1][g], st));
     q->launched[g]++;
     q->n_chunks++;
-    if (v == 0 || v == 3) q->n_full_chunks++;
+    if (p.every_iteration()) q->n_full_chunks++;
     *progressed = true;
   } else if (q->running[g] == 0 && !q->readouts[g].empty() && q->launched[g] == q->inspected[g]) {
     // read-outs behind the last chunk of a group that has gone idle: an event of their own
@@ -210,23 +199,11 @@ int cvo_batch_open(cvo_ctx* ctx, const cvo_params_t* params, int slots, int max_
     return rc;
   }
   q->G = q->S.G;
-  for (int g = 0; g < q->G; g++) {
-    const int p0 = (int)((long)slots * g / q->G), p1 = (int)((long)slots * (g + 1) / q->G);
-    q->geom[g] = q->S.geom;
-    q->geom[g].group = g;
-    q->geom[g].p0 = p0;
-    q->geom[g].n_pairs = p1 - p0;
-    q->geom[g].arena.base = q->S.geom.arena.base + q->S.L.total * (size_t)p0;
-    q->geom[g].stream = ctx->gstream[g];
-  }
+  for (int g = 0; g < q->G; g++) q->geom[g] = group_geom(ctx, q->S, slots, g);
   // Iterations per chunk: a finished pair idles until the chunk after next (the host learns of it one chunk behind), so a
   // queue of short solves wants short chunks; a boundary costs a stream ~10 us.  16 iterations for the fast graphs,
   // twice that for the lean ones, as cvo_align_batch.
-  int U = 16;
-  q->cfg = LoopCfg{U, 2 * U, std::max(1, std::min(q->dp.lean_U, U)), std::max(0, std::min(q->dp.lean_U2, U)), q->S.geom.instr ? 8 : 0};
-  q->allow_lean = ctx_opt(ctx, "NO_LEAN") == nullptr;
-  q->start_nodense = q->allow_lean && q->S.N > 4096;
-  q->allow_calm = q->dp.calm_U > 0;
+  q->cfg = loop_cfg(ctx, q->S, q->dp, 16, 32);
   q->slot.assign((size_t)slots, cvo_batch_queue::Slot());
   const size_t per = align_up(sizeof(PairState), 256) * 2 + align_up(sizeof(PairDesc), 256);
   hipError_t e = hipHostMalloc(&q->pinned, per * (size_t)slots, hipHostMallocDefault);

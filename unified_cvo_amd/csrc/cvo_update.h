@@ -70,8 +70,13 @@ __device__ __forceinline__ UpdDesc load_upd_desc(const PairDesc* __restrict__ D)
 // 1 = every lean_U2 iterations (short lean graph), 0 = every lean_U (lean graph), -1 = calm, one per chunk - and whether
 // k_assoc_dense has to run (overflow rows / the dense regime).  Encoded as: level without the dense kernel; 4 = level 2
 // with it; 8 + (level + 1) = a leaner level with it. 
-__device__ __forceinline__ int want_level(int w) { return w == 4 ? 2 : (w >= 8 ? w - 9 : w); }
-__device__ __forceinline__ int want_encode(int level, bool dense) { return !dense ? level : (level >= 2 ? 4 : 9 + level); }
+__host__ __device__ __forceinline__ int want_level(int w) { return w == 4 ? 2 : (w >= 8 ? w - 9 : w); }
+__host__ __device__ __forceinline__ int want_encode(int level, bool dense) { return !dense ? level : (level >= 2 ? 4 : 9 + level); }
+struct WantWord {
+  int level;
+  bool dense;
+};
+__host__ __device__ __forceinline__ WantWord want_decode(int w) { return {want_level(w), w == 4 || w >= 8}; }
 
 // What the scalar part of an iteration leaves OUTSIDE the staged state: the status / request words the host polls.  A
 // speculative run (update_speculate) only records them; the block that adopts its state posts them.
