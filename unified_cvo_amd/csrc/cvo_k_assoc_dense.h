@@ -128,6 +128,9 @@ __global__ __launch_bounds__(64 * DENSE_WAVES, (!WIDE && FEAT == FEAT_GEO) ? CVO
   // more rows than blocks the waves are better spent on a row each (the replay is a serial chain either way).
   const bool wide_mode = WIDE && n_ovf <= (int)gridDim.x;
   auto wide_row = [&](int n_cand) { return wide_mode && n_cand > WIDE_MIN && n_cand <= DENSE_WAVES * WIDE_CAP; };
+  constexpr auto quarter_of = [](int n_cand) { return (n_cand + 16 * DENSE_WAVES - 1) / (16 * DENSE_WAVES) * 16; };
+  static_assert(quarter_of(DENSE_WAVES * WIDE_CAP) <= WIDE_CAP, "a wave's quarter of the widest row fits its hit buffers");
+  static_assert(DENSE_WAVES * quarter_of(DENSE_WAVES * WIDE_CAP) >= DENSE_WAVES * WIDE_CAP, "the quarters cover the row");
   {
     const Pose pose = load_pose(st);
     const FeatDen F = make_feat_den(P);
@@ -316,8 +319,12 @@ __global__ __launch_bounds__(64 * DENSE_WAVES, (!WIDE && FEAT == FEAT_GEO) ? CVO
     }
     const int off = run_of(r_sorted);
     if (threadIdx.x == 0) D->dense_off[r_sorted] = off;
-    // this wave's quarter: a multiple of 128 candidates, two chunks of 64 per step (independent evaluations in flight together)
-    const int per = ((n_cand + 128 * DENSE_WAVES - 1) / (128 * DENSE_WAVES)) * 128;
+    // this wave's quarter, two chunks of 64 per step (independent evaluations in flight together): at most WIDE_CAP
+    // candidates, as its hits go to w_hit[wave][WIDE_CAP] / w_col[wave][WIDE_CAP] whatever K is (wide_row: n_cand <=
+    // DENSE_WAVES * WIDE_CAP).  Quarters of 128-multiples overran that for 1025 .. 1216 candidates (3 x 128 = 384 per wave).
+    // A multiple of 16 keeps every quarter's float4 loads 256-byte aligned; where the quarters split changes no bit (the
+    // slots come from the quarters' counts in order).
+    const int per = quarter_of(n_cand);
     const int lo = wave * per, hi = min(n_cand, lo + per);
     int nh = 0;
     for (int c0 = lo; c0 < hi; c0 += 128) {
