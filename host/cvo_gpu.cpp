@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <stdexcept>
 
 #include "cvo/CvoGPU.hpp"
@@ -238,6 +239,60 @@ std::vector<int> CvoGPU::align_batch(const std::vector<const CvoPointCloud*>& so
 CvoGPU::ResidentClouds::~ResidentClouds() {
   for (cvo_cloud* h : handles)
     if (h) cvo_cloud_free(h);
+}
+
+int CvoGPU::align(std::vector<CvoFrame::Ptr>& frames, const std::vector<bool>& frames_to_hold_const,
+                  const std::list<std::pair<CvoFrame::Ptr, CvoFrame::Ptr>>& edges, double* registration_seconds) const {
+  const int F = (int)frames.size();
+  if (frames_to_hold_const.size() != frames.size())
+    throw std::invalid_argument("align: frames_to_hold_const needs one flag per frame");
+  std::vector<int> ed;
+  for (const auto& e : edges)
+    for (const CvoFrame::Ptr& f : {e.first, e.second}) {
+      const auto it = std::find(frames.begin(), frames.end(), f);
+      if (!f || it == frames.end()) throw std::invalid_argument("align: an edge names a frame that is not in `frames`");
+      ed.push_back((int)(it - frames.begin()));
+    }
+  std::lock_guard<std::mutex> lk(call_mutex);
+  // the frames' resident clouds when they all are CvoFrameGPU of one context, else uploads on this object's context
+  cvo_ctx* c = nullptr;
+  std::vector<const cvo_cloud*> clouds(F, nullptr);
+  for (int k = 0; k < F; k++) {
+    const auto* g = dynamic_cast<const CvoFrameGPU*>(frames[k].get());
+    if (!g || (c && g->context() != c)) {
+      c = nullptr;
+      break;
+    }
+    c = g->context();
+    clouds[k] = g->points_gpu();
+  }
+  std::vector<DeviceCloud> own(c ? 0 : F);
+  if (!c) {
+    c = ctx;
+    for (int k = 0; k < F; k++) {
+      upload(c, *frames[k]->points, own[k]);
+      clouds[k] = own[k].h;
+    }
+  }
+  std::vector<double> poses(12 * (size_t)F);
+  std::vector<int> hold(F);
+  for (int k = 0; k < F; k++) {
+    std::copy(frames[k]->pose_vec, frames[k]->pose_vec + 12, poses.begin() + 12 * (size_t)k);
+    hold[k] = frames_to_hold_const[k] ? 1 : 0;
+  }
+  cvo_params_t p;
+  static_assert(sizeof(cvo_params_t) == sizeof(CvoParams), "cvo_params_t must stay layout-identical to cvo::CvoParams");
+  std::memcpy(&p, &params, sizeof(p));
+  cvo_multiframe_info_t info{};
+  check(c, cvo_multiframe_align(c, &p, F, clouds.data(), poses.data(), hold.data(), (int)edges.size(), ed.data(), &info,
+                                nullptr, 0, nullptr),
+        "cvo_multiframe_align");
+  for (int k = 0; k < F; k++) {
+    std::copy(poses.begin() + 12 * (size_t)k, poses.begin() + 12 * (size_t)k + 12, frames[k]->pose_vec);
+    frames[k]->transform_pointcloud();
+  }
+  if (registration_seconds) *registration_seconds = info.seconds;
+  return 0;
 }
 
 std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::upload_clouds(const std::vector<const CvoPointCloud*>& clouds,

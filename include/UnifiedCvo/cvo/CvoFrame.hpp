@@ -1,6 +1,6 @@
 // cvo::CvoFrame / cvo::CvoFrameGPU: a point cloud under a pose, the vertex type of the multi-frame graph
-// (upstream include/UnifiedCvo/cvo/CvoFrame.hpp:13-38, CvoFrameGPU.hpp:14-36).  Only what the edge kernel
-// (BinaryStateGPU::update_inner_product) needs; the Ceres side of the multi-frame solver is out of scope.
+// (upstream include/UnifiedCvo/cvo/CvoFrame.hpp:13-38, CvoFrameGPU.hpp:14-36): what the edge kernel
+// (BinaryStateGPU::update_inner_product) and the multi-frame CvoGPU::align need.
 #pragma once
 #include <memory>
 #include <vector>
@@ -38,6 +38,7 @@ struct CvoFrameGPU : public CvoFrame {
 
   const cvo_cloud* points_transformed_gpu() const { return transformed_; }
   cvo_ctx* context() const { return ctx_; }
+  const cvo_cloud* points_gpu() const { return init_; }  // the untransformed points, resident
 
  private:
   cvo_ctx* ctx_ = nullptr;

@@ -2,8 +2,9 @@
 // overloads) over the C-ABI of cvo_hip.h.  Differences forced by the missing dependencies: Mat4f instead
 // of Eigen::Matrix4f (same 16-float column-major layout; UnifiedCvo/eigen_interop.hpp converts where Eigen exists),
 // an array of the 192-byte CvoPoint record instead of pcl::PointCloud<CvoPoint> (UnifiedCvo/pcl_interop.hpp forwards
-// pcl clouds where PCL exists).  The multi-frame overloads (Ceres IRLS) are out of scope.
+// pcl clouds where PCL exists).  The multi-frame overload (upstream CvoGPU.hpp:101-109) runs cvo_multiframe_align.
 #pragma once
+#include <list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "cvo/Association.hpp"
+#include "cvo/CvoFrame.hpp"
 #include "cvo/CvoParams.hpp"
 #include "utils/CvoPoint.hpp"
 #include "utils/CvoPointCloud.hpp"
@@ -45,6 +47,16 @@ class CvoGPU {
   int align(const CvoPoint* source_cvo_points, int n_source, const CvoPoint* target_cvo_points, int n_target,
             const Mat4f& T_target_frame_to_source_frame, Mat4f& transform, Association* association = nullptr,
             double* registration_seconds = nullptr) const;
+
+  // Multi-frame registration (upstream CvoGPU.cu:1637-1683 = CvoBatchIRLS::solve, IRLS.cpp:77-215, with a
+  // Levenberg-Marquardt solve in place of Ceres; include/cvo_hip.h cvo_multiframe_align).  Writes every
+  // frame->pose_vec and refreshes a CvoFrameGPU's transformed cloud; frames_to_hold_const[k] pins frames[k].  Every
+  // frame of an edge must be in `frames`.  Frames that are all CvoFrameGPU of one device are solved from their
+  // resident clouds; otherwise the frames' points are uploaded for the call.  multiframe_using_cpu is ignored (the
+  // device edge state is always used).  Returns 0; argument and backend failures throw (std::invalid_argument /
+  // std::runtime_error).
+  int align(std::vector<CvoFrame::Ptr>& frames, const std::vector<bool>& frames_to_hold_const,
+            const std::list<std::pair<CvoFrame::Ptr, CvoFrame::Ptr>>& edges, double* registration_seconds) const;
 
   // New: independent frame pairs solved concurrently on this object's GPU.  Returns per-pair 0 / -1.
   std::vector<int> align_batch(const std::vector<const CvoPointCloud*>& sources,

@@ -1,7 +1,8 @@
 // cvo::BinaryStateGPU: one edge of the multi-frame graph (upstream include/UnifiedCvo/cvo/IRLS_State_GPU.hpp:21-96,
 // src/cvo/IRLS_State_GPU.cu:16-79, IRLS_State_GPU.cpp:54-57).  update_inner_product() recomputes the edge's kernel
-// matrix A between the two frames under their current poses and leaves it on the host for the solver; the Ceres
-// residual construction (add_residual_to_problem) is out of scope - get_inner_product_mat() exposes what it reads.
+// matrix A between the two frames under their current poses and leaves it on the host; get_inner_product_mat() exposes
+// it.  The least-squares solve over such edges (add_residual_to_problem + ceres::Solve) is cvo_multiframe_align, which
+// keeps A on the device.
 #pragma once
 #include <memory>
 

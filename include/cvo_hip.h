@@ -321,6 +321,38 @@ int cvo_edge_kernel_matrix(cvo_ctx* ctx, const cvo_params_t* params, const cvo_c
                            const cvo_cloud* frame2_transformed, float ell, int num_neighbors, float* mat, int* ind,
                            unsigned int* nonzeros, unsigned int* nonzero_sum);
 
+/* ---- multi-frame align: CvoGPU::align(frames, frames_to_hold_const, edges, registration_seconds)
+ * (CvoGPU.cu:1637-1683 -> CvoBatchIRLS::solve, IRLS.cpp:77-215) ---------------------------------------------------
+ * n_frames clouds (the frames' UNtransformed points) under poses[12 * f .. 12 * f + 11] (3x4 ROW-major doubles,
+ * CvoFrame::pose_vec), hold_const[f] != 0: frame f never moves (NULL = none held).  Edge k = (edges[2k], edges[2k+1]) =
+ * (frame1, frame2) is one BinaryStateGPU with K = multiframe_num_neighbors and ell = multiframe_ell_init.
+ * The outer loop is upstream's; each solve is a Levenberg-Marquardt trust-region loop with the Ceres defaults upstream
+ * does not override, on the device-reduced normal equations of the free frames.  The edge state
+ * is always the device one: multiframe_using_cpu (upstream's BinaryStateCPU, a nanoflann radius search) is ignored.
+ * The whole call is validated first; on any error nothing is written.  CVO_E_INVALID: a null cloud, a frame index out
+ * of range, a self-edge, an empty cloud in an edge.  CVO_E_UNSUPPORTED: n_frames > 64 or n_edges > 2048 (caps that keep
+ * the dense host system at most 384 x 384).  n_edges == 0: the poses stay as given.
+ * info (optional): totals of the call.  trace (optional): one row per outer iteration, up to trace_capacity rows;
+ * *n_trace = rows written.  termination: 0 = no solve (ell decayed or loop ended), 1 = function tolerance, 2 = gradient
+ * tolerance, 3 = parameter tolerance, 4 = minimum radius, 5 = iteration cap, 6 = too many invalid steps. */
+#define CVO_MULTIFRAME_MAX_FRAMES 64
+#define CVO_MULTIFRAME_MAX_EDGES 2048
+typedef struct cvo_multiframe_info_t {
+  int outer_iterations, solves, steps, accepted_steps; /* totals over the call */
+  float final_ell;
+  unsigned int last_total_nonzeros;
+  double seconds; /* registration_seconds (CvoGPU.cu:1676-1680) */
+} cvo_multiframe_info_t;
+typedef struct cvo_multiframe_trace_t { /* one row per outer iteration */
+  int iter, n_active_edges, solved, steps, accepted, termination;
+  float ell;
+  unsigned int total_nonzeros;
+  double cost_initial, cost_final;
+} cvo_multiframe_trace_t;
+int cvo_multiframe_align(cvo_ctx* ctx, const cvo_params_t* params, int n_frames, const cvo_cloud* const* clouds,
+                         double* poses, const int* hold_const, int n_edges, const int* edges,
+                         cvo_multiframe_info_t* info, cvo_multiframe_trace_t* trace, int trace_capacity, int* n_trace);
+
 const char* cvo_version(void);
 
 #ifdef __cplusplus

@@ -68,6 +68,12 @@ int cvo_debug_cloud_order(const cvo_cloud* cloud, int* out);
 int cvo_debug_last_score_batch(const cvo_ctx* ctx, int* overlap_evals, int* chain_evals, int* launches);
 /* Free / total bytes of the context's device (hipMemGetInfo), for leak checks without a second HIP runtime in the process. */
 int cvo_debug_device_memory(cvo_ctx* ctx, size_t* free_bytes, size_t* total_bytes);
+/* k_irls_normal on its own: the kernel matrix of the last evaluation on this context (cvo_edge_kernel_matrix) as edge
+ * (frame1, frame2) - the UNtransformed clouds the evaluated ones were moved from - at the poses pose1 / pose2 (3x4
+ * row-major doubles).  out[91] = cost, g[12], the upper triangle of the 12 x 12 H row by row (78). */
+int cvo_debug_irls_normal(cvo_ctx* ctx, const cvo_cloud* frame1, const cvo_cloud* frame2, const double pose1[12],
+                          const double pose2[12], double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,33 @@ class cvo_align_opts_t(C.Structure):
     ]
 
 
+class cvo_multiframe_info_t(C.Structure):
+    _fields_ = [
+        ("outer_iterations", C.c_int),
+        ("solves", C.c_int),
+        ("steps", C.c_int),
+        ("accepted_steps", C.c_int),
+        ("final_ell", C.c_float),
+        ("last_total_nonzeros", C.c_uint),
+        ("seconds", C.c_double),
+    ]
+
+
+class cvo_multiframe_trace_t(C.Structure):
+    _fields_ = [
+        ("iter", C.c_int),
+        ("n_active_edges", C.c_int),
+        ("solved", C.c_int),
+        ("steps", C.c_int),
+        ("accepted", C.c_int),
+        ("termination", C.c_int),
+        ("ell", C.c_float),
+        ("total_nonzeros", C.c_uint),
+        ("cost_initial", C.c_double),
+        ("cost_final", C.c_double),
+    ]
+
+
 class cvo_batch_result_t(C.Structure):
     _fields_ = [
         ("ticket", C.c_longlong),
@@ -145,6 +172,7 @@ EXPORTED = [
     "cvo_process_hint_hw_queues", "cvo_shutdown",
     "cvo_batch_open", "cvo_batch_submit", "cvo_batch_poll", "cvo_batch_pending", "cvo_batch_stats", "cvo_batch_close",
     "cvo_inner_product_batch", "cvo_function_angle_batch", "cvo_debug_last_score_batch",
+    "cvo_multiframe_align", "cvo_debug_irls_normal",
 ]
 
 _libs = {}
@@ -222,6 +250,11 @@ def lib(path=None):
     L.cvo_debug_verified_rows.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.cvo_debug_device_memory.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.cvo_debug_cloud_order.argtypes = [vp, C.POINTER(C.c_int)]
+    dp = C.POINTER(C.c_double)
+    L.cvo_multiframe_align.argtypes = [vp, C.POINTER(cvo_params_t), ip, C.POINTER(vp), dp, C.POINTER(C.c_int), ip,
+                                       C.POINTER(C.c_int), C.POINTER(cvo_multiframe_info_t),
+                                       C.POINTER(cvo_multiframe_trace_t), ip, C.POINTER(C.c_int)]
+    L.cvo_debug_irls_normal.argtypes = [vp, vp, vp, dp, dp, dp]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

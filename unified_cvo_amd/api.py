@@ -670,6 +670,78 @@ class CvoGPU:
                                                   nz.ctypes.data_as(C.POINTER(C.c_uint)), C.byref(total)))
         return mat, ind, nz, total.value
 
+    # -- multi-frame align (CvoGPU::align over frames and edges, CvoGPU.cu:1637-1683) ----------------
+    def align_multiframe(self, frames, hold_const, edges, trace=False):
+        """cvo_multiframe_align on CvoFrameGPU objects: edges = (frame1, frame2) pairs, as frames or as indices into
+        `frames`; hold_const: one flag per frame (None = none held).  Updates every frame's pose_vec (and its transformed
+        cloud); returns
+        (info, trace rows) - info a dict of cvo_multiframe_info_t, the rows dicts of cvo_multiframe_trace_t ([] unless
+        trace)."""
+        frames = list(frames)
+        F = len(frames)
+        pos = {id(f): i for i, f in enumerate(frames)}
+        flat = []
+        for a, b in edges:
+            for f in (a, b):
+                flat.append(int(f) if isinstance(f, (int, np.integer)) else pos[id(f)])
+        E = len(flat) // 2
+        handles = (C.c_void_p * max(F, 1))(*[f._init.handle for f in frames])
+        poses = np.ascontiguousarray(np.concatenate([np.asarray(f.pose_vec, np.float64).reshape(12) for f in frames])
+                                     if F else np.zeros(12), np.float64)
+        hold = None if hold_const is None else np.ascontiguousarray([1 if h else 0 for h in hold_const], np.int32)
+        if hold is not None and hold.shape[0] != F:
+            raise ValueError("hold_const: one flag per frame")
+        ed = np.ascontiguousarray(flat if E else [0, 0], np.int32)
+        info = _capi.cvo_multiframe_info_t()
+        cap = max(self.params.multiframe_max_iters + 2, 1) if trace else 0
+        rows = (_capi.cvo_multiframe_trace_t * max(cap, 1))()
+        n_trace = C.c_int()
+        p = self.params.to_ctypes()
+        ip = C.POINTER(C.c_int)
+        self._check(self.L.cvo_multiframe_align(
+            self.ctx, C.byref(p), F, handles, poses.ctypes.data_as(C.POINTER(C.c_double)),
+            None if hold is None else hold.ctypes.data_as(ip), E, ed.ctypes.data_as(ip), C.byref(info), rows, cap,
+            C.byref(n_trace)))
+        for i, f in enumerate(frames):
+            f.pose_vec[:] = poses[12 * i:12 * i + 12]
+            f.transform_pointcloud()  # the transformed copy follows the new pose (as CvoGPU::align does in C++)
+        names = [n for n, _ in _capi.cvo_multiframe_trace_t._fields_]
+        out = [{n: getattr(rows[i], n) for n in names} for i in range(n_trace.value)]
+        return {n: getattr(info, n) for n, _ in _capi.cvo_multiframe_info_t._fields_}, out
+
+    def multiframe_align_raw(self, clouds, poses, hold_const, edges, trace_capacity=0):
+        """cvo_multiframe_align as it is: clouds (DeviceCloud or None), poses (F x 12, copied), hold_const (None or F
+        ints), edges (flat ints).  Returns (rc, poses, info, trace rows, n_trace); rc is not checked (argument tests)."""
+        F = len(clouds)
+        handles = (C.c_void_p * max(F, 1))(*[None if c is None else c.handle for c in clouds])
+        P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1) if F else np.zeros(12), np.float64).copy()
+        hold = None if hold_const is None else np.ascontiguousarray(hold_const, np.int32)
+        ed = np.ascontiguousarray(list(edges) if len(edges) else [0, 0], np.int32)
+        info = _capi.cvo_multiframe_info_t()
+        rows = (_capi.cvo_multiframe_trace_t * max(trace_capacity, 1))()
+        n_trace = C.c_int(-7)
+        p = self.params.to_ctypes()
+        ip = C.POINTER(C.c_int)
+        rc = self.L.cvo_multiframe_align(self.ctx, C.byref(p), F, handles, P.ctypes.data_as(C.POINTER(C.c_double)),
+                                         None if hold is None else hold.ctypes.data_as(ip), len(edges) // 2,
+                                         ed.ctypes.data_as(ip), C.byref(info), rows, trace_capacity, C.byref(n_trace))
+        return rc, P, info, rows, n_trace.value
+
+    def debug_irls_normal(self, frame1, frame2, pose1, pose2):
+        """cvo_debug_irls_normal: k_irls_normal over the kernel matrix of the last evaluation (edge_kernel_matrix) with
+        the UNtransformed clouds frame1 / frame2 at 3x4 poses -> (cost, g[12], H 12x12 symmetric)."""
+        f1, f2 = self._dev(frame1), self._dev(frame2)
+        a = np.ascontiguousarray(np.asarray(pose1, np.float64).reshape(12))
+        b = np.ascontiguousarray(np.asarray(pose2, np.float64).reshape(12))
+        out = np.zeros(91, np.float64)
+        dp = C.POINTER(C.c_double)
+        self._check(self.L.cvo_debug_irls_normal(self.ctx, f1.handle, f2.handle, a.ctypes.data_as(dp),
+                                                 b.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+        H = np.zeros((12, 12))
+        H[np.triu_indices(12)] = out[13:]
+        H = H + np.triu(H, 1).T
+        return out[0], out[1:13].copy(), H
+
     # -- test / profiling hooks --------------------------------------------------------------------
     def debug_last_ell(self, n_rows, K):
         mat = np.zeros((n_rows, K), np.float32)

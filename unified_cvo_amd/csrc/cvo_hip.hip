@@ -11,6 +11,7 @@
 //   cvo_launch.hip  every kernel launch of the solver                  cvo_sched.hip   setup, chunk graphs, cvo_align_batch
 //   cvo_queue.hip   the batch queue                                    cvo_eval.hip    inner products, single evaluations
 //   cvo_export.hip  association / ELL exports                          cvo_debug.hip   test and profiling hooks
+//   cvo_irls.hip    multi-frame align (the least-squares solve of CvoBatchIRLS)
 #include "cvo_internal.h"
 
 #include "cvo_ctx.hip"
@@ -20,4 +21,5 @@
 #include "cvo_queue.hip"
 #include "cvo_eval.hip"
 #include "cvo_export.hip"
+#include "cvo_irls.hip"
 #include "cvo_debug.hip"

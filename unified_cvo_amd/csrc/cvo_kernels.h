@@ -62,3 +62,4 @@
 #include "cvo_k_coeff_dense.h"
 #include "cvo_k_debug.h"
 #include "cvo_k_cloud.h"
+#include "cvo_k_irls.h"

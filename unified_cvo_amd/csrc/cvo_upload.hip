@@ -465,6 +465,18 @@ int cvo_cloud_upload_aos192(cvo_ctx* ctx, int n, const void* pts, cvo_cloud** ou
 }
 
 // ---- multi-frame edge kernel ---------------------------------------------------------
+// cull centre and motion bound of a cloud moved by a pose (neither influences a result)
+static void transformed_bounds(const cvo_cloud* in, const float T[12], cvo_cloud* c) {
+  c->cx = T[0] * in->cx + T[1] * in->cy + T[2] * in->cz + T[3];
+  c->cy = T[4] * in->cx + T[5] * in->cy + T[6] * in->cz + T[7];
+  c->cz = T[8] * in->cx + T[9] * in->cy + T[10] * in->cz + T[11];
+  if (!std::isfinite(c->cx) || !std::isfinite(c->cy) || !std::isfinite(c->cz)) c->cx = c->cy = c->cz = 0.f;
+  double fro = 0;
+  for (int i = 0; i < 3; i++)
+    for (int j = 0; j < 3; j++) fro += (double)T[4 * i + j] * T[4 * i + j];
+  c->rmax = (float)((std::sqrt(fro) * in->rmax + std::sqrt((double)T[3] * T[3] + (double)T[7] * T[7] + (double)T[11] * T[11])) * 1.000001);
+}
+
 int cvo_cloud_transformed(cvo_ctx* ctx, const cvo_cloud* in, const float pose12[12], cvo_cloud** out) {
   if (!ctx || !in || !pose12 || !out) return fail(ctx, CVO_E_INVALID, "cvo_cloud_transformed: bad argument");
   if (in->ctx != ctx) return fail(ctx, CVO_E_INVALID, "cloud belongs to another context");
@@ -509,16 +521,7 @@ int cvo_cloud_transformed(cvo_ctx* ctx, const cvo_cloud* in, const float pose12[
       return fail(ctx, CVO_E_HIP, std::string("cvo_cloud_transformed: ") + hipGetErrorString(e));
     }
   }
-  // cull centre and motion bound of the moved cloud (neither influences a result)
-  const float* T = pose12;
-  c->cx = T[0] * in->cx + T[1] * in->cy + T[2] * in->cz + T[3];
-  c->cy = T[4] * in->cx + T[5] * in->cy + T[6] * in->cz + T[7];
-  c->cz = T[8] * in->cx + T[9] * in->cy + T[10] * in->cz + T[11];
-  if (!std::isfinite(c->cx) || !std::isfinite(c->cy) || !std::isfinite(c->cz)) c->cx = c->cy = c->cz = 0.f;
-  double fro = 0;
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) fro += (double)T[4 * i + j] * T[4 * i + j];
-  c->rmax = (float)((std::sqrt(fro) * in->rmax + std::sqrt((double)T[3] * T[3] + (double)T[7] * T[7] + (double)T[11] * T[11])) * 1.000001);
+  transformed_bounds(in, pose12, c);
   *out = c;
   return CVO_OK;
 }

@@ -90,6 +90,22 @@ def scene_pair(n, pair_id=0, m=None, noise=0.01):
     return src.astype(np.float32), tgt[perm].astype(np.float32), perm
 
 
+def scene_sequence(n_frames, n, seed=0, noise=0.01):
+    """The street scene of scene_pair seen from n_frames known poses (multi-frame align): frame f holds the scene's n
+    points expressed in its own frame, with independent noise and point order per frame.  Returns (xyz list, float32 n x
+    3 each; poses list, float64 3x4 row-major world <- frame, frame 0 = identity, frame f = gt_motion()^f)."""
+    world = scene_pair(n, pair_id=seed)[0].astype(np.float64)
+    clouds, poses = [], []
+    T = np.eye(4)
+    for f in range(n_frames):
+        rs = np.random.default_rng(9000 + 97 * seed + f)
+        local = (world - T[:3, 3]) @ T[:3, :3] + rs.normal(0.0, noise, world.shape)  # T^-1 world
+        clouds.append(local[rs.permutation(n)].astype(np.float32))
+        poses.append(T[:3].copy())
+        T = T @ gt_motion()
+    return clouds, poses
+
+
 def colour_features(xyz, rng, noise=0.0):
     """5 channels: rgb = 0.5 + 0.5 sin(w_c . xyz + phi_c), 2 gradient channels ~ N(0.5, 0.05)."""
     w = np.array([[0.9, 0.3, 0.2], [0.2, 1.1, 0.4], [0.5, 0.6, 0.8]])
