@@ -17,10 +17,6 @@ extern "C" int cvo_process_hint_hw_queues(void) {
 
 namespace {
 
-struct Dims {
-  int Mpad, nchunks, rbw_max, nblk_assoc, nblk_coeff, NG, NGpad, Npad;
-};
-
 PairLayout make_layout(int N, int M, int Kmax, int trace_capacity, bool long_lists, Dims* d) {
   const int Mpad = (int)align_up((size_t)M, 512);
   const int nchunks = Mpad / 64;

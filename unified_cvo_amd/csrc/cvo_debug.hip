@@ -77,24 +77,21 @@ int cvo_debug_time_kernels(cvo_ctx* ctx, int reps, float* ms_assoc, float* ms_co
   // the per-iteration launches of the optimiser loop (one per sub-batch), replayed on the state the last call
   // left behind: same lists, same rows, same arithmetic; k_coeff's last block runs the update without writing
   // anything back
-  const int n_pairs = ctx->last_pairs, G = ctx->last_groups;
-  const bool idx16 = ctx->last_M < 65536;
+  const int n_pairs = ctx->last_pairs, G = ctx->last.G;
   const DevParams& dp = ctx->last_params;
-  const int general = ctx->last_feat;
-  const bool instr = dp.kernel_clock || dp.phase_ticks;
-  const int nba = (ctx->last_N + ASSOC_THREADS - 1) / ASSOC_THREADS;
+  const LaunchGeom& g0 = ctx->last.geom;
+  const IterWords w = iteration_words({.idx32 = !g0.idx16, .rebuild_follows = true, .replay = true});
   float out[2] = {0.f, 0.f};
   for (int which = 0; which < 2; which++) {
     auto sweep = [&]() {
-      for (int g = 0; g < G; g++) {
-        const int p0 = (int)((long)n_pairs * g / G), p1 = (int)((long)n_pairs * (g + 1) / G);
-        const ArenaArg A{ctx->arena + ((size_t)ctx->last_stride256 << 8) * (size_t)p0, ctx->last_stride256, ctx->last_Npad};
+      for (int q = 0; q < G; q++) {
+        const LaunchGeom g = group_geom(ctx, ctx->last, n_pairs, q);
+        const PairDesc* descs = ctx->d_descs + g.p0;
         if (which == 0)
-          launch_assoc(ctx->stream, idx16, general, instr, nba, p1 - p0, ctx->d_descs + p0, ctx->d_params, ctx->d_states + p0, A,
-                       2);
+          launch_assoc(ctx->stream, g.idx16, g.feat, g.instr, g.nba, g.n_pairs, descs, ctx->d_params, ctx->d_states + g.p0, g.arena,
+                       w.assoc);
         else
-          launch_coeff(ctx->stream, instr, nba, ctx->last_csplit, p1 - p0, ctx->d_descs + p0, ctx->d_params, ctx->d_states + p0,
-                       A, 8 | 2);
+          launch_coeff(ctx->stream, g.instr, g.nba, g.csplit, g.n_pairs, descs, ctx->d_params, ctx->d_states + g.p0, g.arena, w.iter);
       }
     };
     sweep();  // warm-up
@@ -111,7 +108,7 @@ int cvo_debug_time_kernels(cvo_ctx* ctx, int reps, float* ms_assoc, float* ms_co
     HIP_TRY(ctx, hipMemcpyFromSymbol(h, HIP_SYMBOL(g_phase_ticks), sizeof(h)));
     const int np = n_pairs - (int)((long)n_pairs * (G - 1) / G);
     for (int which = 0; which < 2; which++) {
-      const int nb = std::min(4096, 8 * ((np + 7) / 8) * nba * (which ? ctx->last_csplit : 1));
+      const int nb = std::min(4096, 8 * ((np + 7) / 8) * g0.nba * (which ? g0.csplit : 1));
       double sum[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
       int cnt = 0;
       for (int b = 0; b < nb; b++) {
@@ -211,14 +208,14 @@ int cvo_debug_scan_stats(cvo_ctx* ctx, unsigned long long* tiles, int* rows_per_
   }
   *tiles = total;
   if (rows_per_tile) *rows_per_tile = ROWS_PER_GROUP;
-  if (targets_per_tile) *targets_per_tile = 64 * ctx->last_params.T;
+  if (targets_per_tile) *targets_per_tile = 64 * ctx->last.geom.T;
   return CVO_OK;
 }
 
 int cvo_debug_last_geometry(cvo_ctx* ctx, int* n_groups, int* pairs_per_group) {
   if (!ctx || ctx->last_pairs < 1) return fail(ctx, CVO_E_INVALID, "cvo_debug_last_geometry: bad argument");
-  if (n_groups) *n_groups = ctx->last_groups;
-  if (pairs_per_group) *pairs_per_group = (ctx->last_pairs + ctx->last_groups - 1) / ctx->last_groups;
+  if (n_groups) *n_groups = ctx->last.G;
+  if (pairs_per_group) *pairs_per_group = (ctx->last_pairs + ctx->last.G - 1) / ctx->last.G;
   return CVO_OK;
 }
 
@@ -227,14 +224,11 @@ int cvo_debug_time_scan(cvo_ctx* ctx, int reps, float* ms) {
     return fail(ctx, CVO_E_INVALID, "cvo_debug_time_scan: bad argument");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // the same launches the optimiser loop issues: one k_scan per sub-batch, here back to back on one stream
-  const int n_pairs = ctx->last_pairs, G = ctx->last_groups;
-  const DevParams& dp = ctx->last_params;
-  const int variant = 1;  // force the scan for pairs whose lists are current (k_scan's `force` bits: 2 = no emission, 4 = no fine tiles)
-  auto sweep = [&]() {
-    for (int g = 0; g < G; g++) {
-      const int p0 = (int)((long)n_pairs * g / G), p1 = (int)((long)n_pairs * (g + 1) / G);
-      launch_scan(ctx->stream, dp.T, dim3(ctx->last_gx, ctx->last_gy, p1 - p0), ctx->d_descs + p0, ctx->d_params,
-                  ctx->d_states + p0, variant);
+  const int n_pairs = ctx->last_pairs, G = ctx->last.G;
+  auto sweep = [&]() {  // (forced: the pairs' lists are current)
+    for (int q = 0; q < G; q++) {
+      const LaunchGeom g = group_geom(ctx, ctx->last, n_pairs, q);
+      launch_scan(ctx->stream, g.T, dim3(g.gx, g.gy, g.n_pairs), ctx->d_descs + g.p0, ctx->d_params, ctx->d_states + g.p0, true);
     }
   };
   sweep();  // warm-up
@@ -245,7 +239,7 @@ int cvo_debug_time_scan(cvo_ctx* ctx, int reps, float* ms) {
   // the extra scans leave slice bits behind; clean them so the workspace stays consistent
   for (int p = 0; p < n_pairs; p++) {
     const PairDesc& D = ctx->h_descs[p];
-    HIP_TRY(ctx, hipMemsetAsync(D.rowbits, 0, sizeof(unsigned) * (size_t)(ctx->last_N + 4) * D.rbw, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(D.rowbits, 0, sizeof(unsigned) * (size_t)(ctx->last.N + 4) * D.rbw, ctx->stream));
   }
   HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   float t = 0;

@@ -19,6 +19,13 @@ constexpr int FD_PAD = 8;
 constexpr int NC_PAD = 20;
 constexpr int IND_CAP = 512;  // capacity of each indicator FIFO (window + 1 must fit)
 
+// What a call runs (DevParams::mode)
+enum CallMode : int {
+  CALL_ALIGN = 0,   // the align loop
+  CALL_SINGLE = 1,  // single evaluation (inner product / association)
+  CALL_NONISO = 2,  // single evaluation with the non-isotropic kernel (CvoGPU.cu:217-327)
+};
+
 // Per-call constants (passed by value as a kernel argument).
 struct DevParams {
   float sp_thres, sigma2, c2, c_sigma2, s_ell, s_sigma, c, d;
@@ -33,11 +40,10 @@ struct DevParams {
   float stable_thr;
   int use_geo, use_col, use_sem, use_range_ell, use_geotype;
   int trace_dense, trace_every, trace_capacity;
-  int mode;  // 0 = align loop, 1 = single evaluation (inner product / association), 2 = single evaluation with the
-             // non-isotropic kernel (CvoGPU.cu:217-327)
-  float kinv[9];   // mode 2: inverse of the 3x3 kernel matrix, row-major
-  float d2_cull;   // mode 2: squared Euclidean radius beyond which no pair can reach sp_thres (cull only)
-  float s_ell_sq;  // mode 2: s_ell * s_ell kept in float, as that kernel's prologue does
+  int mode;  // CallMode
+  float kinv[9];   // CALL_NONISO: inverse of the 3x3 kernel matrix, row-major
+  float d2_cull;   // CALL_NONISO: squared Euclidean radius beyond which no pair can reach sp_thres (cull only)
+  float s_ell_sq;  // CALL_NONISO: s_ell * s_ell kept in float, as that kernel's prologue does
   int T;     // target chunks (of 64) per scan wave: 1, 2, 4 or 8
   int groups_per_block;  // row groups per k_scan block (a multiple of 64)
   // Candidate-list reuse (DESIGN.md "Reusing the candidate list"): the scan runs with the cut-off radius
@@ -96,7 +102,7 @@ struct PairState {
   unsigned nnz, max_nnz;
   double B, C, D, E;
   double dist;
-  double asum;  // sum of kernel values (mode 1)
+  double asum;  // sum of kernel values (CALL_SINGLE)
   unsigned long long ncand;
   unsigned long long ncand_list;  // candidates held by the current lists, summed over the rows (k_prep zeroes, k_list adds)
   unsigned long long noverflow;  // rows that took k_assoc's literal path
@@ -192,7 +198,7 @@ __device__ __forceinline__ EllEntry make_ell(float a, float yx, float yy, float 
 // What k_assoc_dense leaves per overflow row for the thread of k_assoc that owns the row's position.
 struct RowRes {
   float o[3], v[3];  // sum_j a_ij (x_i x y_j), sum_j a_ij (y_j - x_i): float, accumulated in ascending j (CvoGPU.cu:779-780)
-  double asum;       // sum_j a_ij (mode 1: A_sum)
+  double asum;       // sum_j a_ij (CALL_SINGLE: A_sum)
 };
 static_assert(sizeof(RowRes) == 32, "RowRes");
 
@@ -315,8 +321,88 @@ __host__ __device__ inline size_t ell_index(int N, int s, int pos, int off) {
 __host__ __device__ inline size_t ell_upper_capacity(int N, int K_max) {
   return K_max > ELL_LOWER_SLOTS ? (size_t)(K_max - ELL_LOWER_SLOTS) * (size_t)N : 0;
 }
-constexpr int COEFF_SPLIT_MAX = 32;
+constexpr int COEFF_SPLIT_MAX = 32;  // the largest coefficient split (coeff_split)
 constexpr int ROWS_PER_GROUP = 4;
+
+// ---- the flag words of the iteration kernels (composed on the host by iteration_words, cvo_launch.hip) --------------
+// k_assoc / k_verify
+enum AssocFlags : int {
+  ASSOC_LEAN = 1,        // a lean graph's slot: no rebuild kernels ran before it, a pair that needs them waits (slot_waits)
+  ASSOC_REPLAY = 2,      // timing replay (cvo_debug_time_kernels) on the state the last call left behind
+  ASSOC_LEAN_DENSE = 4,  // ... a lean slot that runs k_assoc_dense all the same: overflow rows do not make a pair wait
+  ASSOC_ASUM_ONLY = 8,   // single evaluation that only wants A_sum (the list chain of inner_product_gpu)
+};
+// k_coeff / k_update / update_body: the low bits are flags, the bits from ITER_HORIZON_SHIFT on the horizon - how many
+// iterations the list has to survive without another rebuild opportunity (0 in the full graph)
+enum IterFlags : int {
+  ITER_LEAN = 1,             // as ASSOC_LEAN
+  ITER_REBUILD_FOLLOWS = 2,  // the rebuild kernels run right after this iteration
+  ITER_FROM_COEFF = 4,       // the update runs inside k_coeff (bumps the generation of its last-block counter)
+  ITER_REPLAY = 8,           // timing replay: compute everything, write nothing back
+  ITER_LEAN_DENSE = 32,      // as ASSOC_LEAN_DENSE
+  ITER_IDX32 = 64,           // 32-bit candidate lists (targets of 65536 points or more): the row-class limit is ASSOC_CAP32
+};
+constexpr int ITER_HORIZON_SHIFT = 8;
+__host__ __device__ constexpr int iter_horizon(int flags) { return flags >> ITER_HORIZON_SHIFT; }
+
+// The pair does not advance in this slot: a lean slot, and its list has expired or it has rows for k_assoc_dense that
+// the slot does not run.  k_assoc, k_verify, k_coeff and k_update skip it alike (k_coeff tells the host what it waits for).
+// flags: the kernel's word, lean / lean_dense: its two bits (ASSOC_LEAN / ASSOC_LEAN_DENSE or ITER_LEAN / ITER_LEAN_DENSE);
+// st: the PairState, or the values of it a kernel has loaded already (SlotState) - read only in a lean slot.  (A pointer,
+// not a reference, and a branch, not a returned expression: the kernels compile to the code of the inline test it replaced.)
+struct SlotState {
+  int rebuild, n_ovf;
+};
+template <class St>
+__device__ __forceinline__ bool slot_waits(int flags, int lean, int lean_dense, const St* st) {
+  bool w = false;
+  if ((flags & lean) && (st->rebuild || (st->n_ovf > 0 && !(flags & lean_dense)))) w = true;
+  return w;
+}
+
+// The packed launch words of the row-block kernels (one argument keeps everything inside the preloaded kernel-argument
+// registers).  k_assoc: AssocFlags | row blocks | pairs; k_coeff: row blocks | coefficient split of the launch | pairs.
+constexpr int ASSOC_WORD_FLAG_BITS = 4, ASSOC_WORD_NBLK_BITS = 16;
+constexpr int COEFF_WORD_NBLK_BITS = 14, COEFF_WORD_SPLIT_BITS = 6;
+constexpr int LAUNCH_WORD_PAIR_SHIFT = 20, LAUNCH_WORD_PAIR_BITS = 12;
+// the largest launch both words can describe (setup_batch refuses larger ones)
+constexpr int LAUNCH_PAIRS_MAX = (1 << LAUNCH_WORD_PAIR_BITS) - 1;
+constexpr int LAUNCH_NBLK_MAX = (1 << COEFF_WORD_NBLK_BITS) - 1;
+struct AssocWord {
+  int flags, nblk, n_pairs;
+};
+struct CoeffWord {
+  int nblk, split, n_pairs;
+};
+__host__ __device__ constexpr int pack_assoc_word(int flags, int nblk, int n_pairs) {
+  return (flags & ((1 << ASSOC_WORD_FLAG_BITS) - 1)) | (nblk << ASSOC_WORD_FLAG_BITS) |
+         (int)((unsigned)n_pairs << LAUNCH_WORD_PAIR_SHIFT);
+}
+__host__ __device__ constexpr AssocWord unpack_assoc_word(int w) {
+  return {w & ((1 << ASSOC_WORD_FLAG_BITS) - 1), (w >> ASSOC_WORD_FLAG_BITS) & ((1 << ASSOC_WORD_NBLK_BITS) - 1),
+          (int)((unsigned)w >> LAUNCH_WORD_PAIR_SHIFT)};
+}
+__host__ __device__ constexpr int pack_coeff_word(int nblk, int split, int n_pairs) {
+  return nblk | (split << COEFF_WORD_NBLK_BITS) | (int)((unsigned)n_pairs << LAUNCH_WORD_PAIR_SHIFT);
+}
+__host__ __device__ constexpr CoeffWord unpack_coeff_word(int w) {
+  return {w & ((1 << COEFF_WORD_NBLK_BITS) - 1), (w >> COEFF_WORD_NBLK_BITS) & ((1 << COEFF_WORD_SPLIT_BITS) - 1),
+          (int)((unsigned)w >> LAUNCH_WORD_PAIR_SHIFT)};
+}
+static_assert(ASSOC_WORD_FLAG_BITS + ASSOC_WORD_NBLK_BITS == LAUNCH_WORD_PAIR_SHIFT &&
+                  COEFF_WORD_NBLK_BITS + COEFF_WORD_SPLIT_BITS == LAUNCH_WORD_PAIR_SHIFT &&
+                  LAUNCH_WORD_PAIR_SHIFT + LAUNCH_WORD_PAIR_BITS == 32,
+              "launch word fields");
+static_assert(LAUNCH_NBLK_MAX < (1 << ASSOC_WORD_NBLK_BITS), "k_assoc's row-block field holds every admitted launch");
+static_assert(COEFF_SPLIT_MAX < (1 << COEFF_WORD_SPLIT_BITS), "the coefficient split fits its field");
+static_assert(unpack_assoc_word(pack_assoc_word(15, LAUNCH_NBLK_MAX, LAUNCH_PAIRS_MAX)).flags == 15 &&
+                  unpack_assoc_word(pack_assoc_word(15, LAUNCH_NBLK_MAX, LAUNCH_PAIRS_MAX)).nblk == LAUNCH_NBLK_MAX &&
+                  unpack_assoc_word(pack_assoc_word(15, LAUNCH_NBLK_MAX, LAUNCH_PAIRS_MAX)).n_pairs == LAUNCH_PAIRS_MAX,
+              "k_assoc's launch word round trip");
+static_assert(unpack_coeff_word(pack_coeff_word(LAUNCH_NBLK_MAX, COEFF_SPLIT_MAX, LAUNCH_PAIRS_MAX)).nblk == LAUNCH_NBLK_MAX &&
+                  unpack_coeff_word(pack_coeff_word(LAUNCH_NBLK_MAX, COEFF_SPLIT_MAX, LAUNCH_PAIRS_MAX)).split == COEFF_SPLIT_MAX &&
+                  unpack_coeff_word(pack_coeff_word(LAUNCH_NBLK_MAX, COEFF_SPLIT_MAX, LAUNCH_PAIRS_MAX)).n_pairs == LAUNCH_PAIRS_MAX,
+              "k_coeff's launch word round trip");
 // k_assoc_dense blocks per pair (one overflow row per wave at a time; 4 waves per block).  A batch launches few per pair (its pairs fill the chip and
 // most of them have no overflow rows at all); a pair solved alone gets enough waves to fill it by itself: clustered
 // clouds put thousands of rows on this path (profiles/r4/scene.txt).

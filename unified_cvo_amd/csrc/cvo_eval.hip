@@ -10,12 +10,14 @@ int run_single_eval(cvo_ctx* ctx, const cvo_params_t* params, const cvo_cloud* s
   DevParams dp;
   const cvo_cloud* src[1] = {source};
   const cvo_cloud* tgt[1] = {target};
-  int rc = setup_batch(ctx, params, 1, src, tgt, Tm, nullptr, kernel_inv_and_cull ? 2 : 1, ell, S, &dp, kernel_inv_and_cull);
+  const CallMode mode = kernel_inv_and_cull ? CALL_NONISO : CALL_SINGLE;
+  int rc = setup_batch(ctx, params, 1, src, tgt, Tm, nullptr, mode, ell, S, &dp, kernel_inv_and_cull);
   if (rc != CVO_OK) return rc;
   launch_init(ctx, S->geom);
   launch_rebuild(ctx, S->geom);
-  launch_core(ctx, S->geom, false, 2);  // mode 1: k_coeff is a no-op ...
-  hipLaunchKernelGGL(k_update<false>, dim3(1), dim3(64), 0, ctx->stream, ctx->d_descs, ctx->d_params, ctx->d_status, 2);  // ... k_update collects the sums
+  launch_core(ctx, S->geom, {.idx32 = !S->geom.idx16, .rebuild_follows = true});  // (k_coeff is a no-op in a single evaluation ...
+  hipLaunchKernelGGL(k_update<false>, dim3(1), dim3(64), 0, ctx->stream, ctx->d_descs, ctx->d_params, ctx->d_status,
+                     iteration_words({.rebuild_follows = true}).iter);  // ... k_update collects the sums)
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipMemcpyAsync(ctx->h_states.data(), ctx->d_states, sizeof(PairState), hipMemcpyDeviceToHost,
                               ctx->stream));
@@ -113,7 +115,7 @@ int run_ip_chain(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_clou
                  const float* Tms, float ell, double* out) {
   BatchSetup S;
   DevParams dp;
-  int rc = setup_batch(ctx, params, n, src, tgt, Tms, nullptr, 1, ell, &S, &dp);
+  int rc = setup_batch(ctx, params, n, src, tgt, Tms, nullptr, CALL_SINGLE, ell, &S, &dp);
   if (rc != CVO_OK) return rc;
   if (S.G != 1) return fail(ctx, CVO_E_INVALID, "run_ip_chain: too many pairs for one chain");
   const LaunchGeom& g = S.geom;
@@ -124,7 +126,8 @@ int run_ip_chain(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_clou
     launch_init(ctx, g);
     launch_rebuild(ctx, g);
     launch_dense(g.stream, g.feat, g.wide, g.n_pairs, g.dense_blocks, ctx->d_descs, ctx->d_params, ctx->d_states);
-    launch_assoc(g.stream, g.idx16, g.feat, g.instr, g.nba, g.n_pairs, ctx->d_descs, ctx->d_params, ctx->d_states, g.arena, 8);
+    launch_assoc(g.stream, g.idx16, g.feat, g.instr, g.nba, g.n_pairs, ctx->d_descs, ctx->d_params, ctx->d_states, g.arena,
+                 iteration_words({.asum_only = true}).assoc);
   });
   if (rc != CVO_OK) return rc;
   HIP_TRY(ctx, hipGraphLaunch(ctx->chain_graph.exec, g.stream));
@@ -196,7 +199,7 @@ struct ScoreJob {
 int score_overlap(cvo_ctx* ctx, const cvo_params_t* params, std::pmr::vector<ScoreEval>& ev) {
   hipStream_t stream = ctx->stream;
   DevParams P = make_dev_params(ctx, *params);
-  P.mode = 1;
+  P.mode = CALL_SINGLE;
   bool all_hot = ctx_opt(ctx, "NO_ONEHOT") == nullptr;  // (FEAT_HOT and FEAT_ALL give the same bits: test_gpu_parity.py)
   int rc, tiles_max = 0;
   size_t tiles_sum = 0;
@@ -322,7 +325,8 @@ int score_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_jobs, const cvo_
   } else if (live.size() > 1 || !chain_all) {
     // (one chain-only job: its one run_ip_chain makes this check_call on the same clouds before any device work)
     int N = 0, M = 0;
-    const int rc = check_call(ctx, params, (int)live.size(), ls.data(), lt.data(), nullptr, 1, ell[live[0]], nullptr, &N, &M);
+    const int rc = check_call(ctx, params, (int)live.size(), ls.data(), lt.data(), nullptr, CALL_SINGLE, ell[live[0]], nullptr,
+                                &N, &M);
     if (rc != CVO_OK) return rc;
     for (int k : live)  // (check_call's lengthscale rule, for every job's own ell)
       if (!(std::isfinite(ell[k]) && ell[k] >= 1e-30f && ell[k] <= 1e15f))

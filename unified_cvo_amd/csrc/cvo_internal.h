@@ -97,6 +97,33 @@ struct GraphKey {
   bool operator==(const GraphKey& o) const { return fields() == o.fields(); }
 };
 
+// Sizes a workspace is laid out for (make_layout)
+struct Dims {
+  int Mpad, nchunks, rbw_max, nblk_assoc, nblk_coeff, NG, NGpad, Npad;
+};
+
+// What the launches of a sub-batch are (setup_batch, group_geom)
+struct LaunchGeom {
+  int n_pairs, p0, T, gx, gy, nba, npb, csplit;
+  int nbl, nbv;  // blocks of k_list (LIST_THREADS rows each) and k_verify (grid x) for the largest source cloud
+  int dense_blocks = DENSE_BLOCKS_MIN;  // k_assoc_dense grid x = PairDesc::dense_blocks of every pair of the launch
+  int horizon_cap = 1 << 20;  // the lean graph's period (DevParams::lean_U)
+  bool idx16, instr, verify;
+  bool wide;  // k_assoc_dense's wide-row instantiation (dense_wide)
+  int feat = FEAT_GEO;  // which instantiation of the association kernels the call needs (call_feat)
+  hipStream_t stream;
+  ArenaArg arena;  // of pair p0
+};
+
+// A call's sizes, workspace layout and launch geometry (setup_batch); N / M: its largest source / target cloud
+struct BatchSetup {
+  int N, M, T, gpb, gx, gy, G;
+  bool long_lists = false;
+  Dims d;
+  PairLayout L;
+  LaunchGeom geom;
+};
+
 struct CachedGraph {
   hipGraphExec_t exec = nullptr;
   GraphKey key;
@@ -171,20 +198,15 @@ struct cvo_ctx {
   CachedGraph graphs[MAX_GROUPS][GRAPH_SLOTS];
   CachedGraph chain_graph;
   int last_chunks = 0, last_lean_launches = 0, last_full_launches = 0;
-  // last call (debug hooks)
+  // The last call, as setup_batch made it (debug hooks, exports, the IRLS readers): its pairs (0 = no workspace of the
+  // last call can be read), setup, parameters and pair 0's source order (sorted row -> original row)
   int last_pairs = 0;
-  int last_N = 0, last_M = 0, last_Kmax = 0;
+  BatchSetup last{};
   DevParams last_params{};
-  int last_gx = 0, last_gy = 0, last_csplit = 1;
+  std::vector<int> last_xorder;
   bool queue_open = false;  // a cvo_batch_queue owns the workspace: the other align / evaluation calls are refused meanwhile
   cvo_batch_queue* queue = nullptr;  // ... that queue (cvo_ctx_destroy releases its device side, see queue_release)
   double clock_ms_per_tick = 0.0;  // s_memrealtime, calibrated on first use (cvo_debug_kernel_clock)
-  unsigned last_stride256 = 0;
-  int last_Npad = 0;
-  std::vector<int> last_xorder;  // pair 0's source order: sorted row -> original row
-  int last_groups = 1;           // sub-batches (streams) of the last call
-  int last_feat = 0;             // FEAT_* of the last call's association kernels
-  PairLayout last_layout{};
 };
 
 namespace {

@@ -354,7 +354,8 @@ __global__ __launch_bounds__(ASSOC_THREADS, FEAT != FEAT_GEO ? 1 : CVO_ASSOC_WAV
                                                           unsigned stride256, int Npad) {
   const unsigned long long tt0 = INSTR ? __builtin_readcyclecounter() : 0ull;
   // one packed argument keeps everything inside the preloaded kernel-argument registers
-  const int lean = lean_nblk_pairs & 0xf, nblk = (lean_nblk_pairs >> 4) & 0xffff, n_pairs = (int)((unsigned)lean_nblk_pairs >> 20);
+  const AssocWord aw = unpack_assoc_word(lean_nblk_pairs);
+  const int lean = aw.flags, nblk = aw.nblk, n_pairs = aw.n_pairs;
   PairBlock pb;
   if (!pair_block(nblk, n_pairs, pb)) return;
   const PairDesc* __restrict__ D = descs + pb.pair;
@@ -388,13 +389,13 @@ __global__ __launch_bounds__(ASSOC_THREADS, FEAT != FEAT_GEO ? 1 : CVO_ASSOC_WAV
     asm volatile("" ::"s"(n), "s"(k), "s"(a0), "s"(a1), "s"(a2), "s"(a3), "s"(a4), "s"(e), "s"(r0), "s"(t0), "s"(P.sp_thres),
                  "s"(P.log_geo), "s"(P.c), "s"(P.d), "s"(P.d2_c_thres));
   }
-  const bool replay = (lean & 2) != 0;  // cvo_debug_time_kernels: re-run on the state the last call left behind
+  const bool replay = (lean & ASSOC_REPLAY) != 0;
   if (!replay && status_v != 0) return;
-  // lean graph (no rebuild / dense kernels inside the iteration): a pair whose list has expired, or that has
-  // rows for k_assoc_dense, does not advance; it waits for the next rebuild opportunity / for the host to
-  // switch its group to the full graph (k_coeff skips it too and tells the host)
-  if ((lean & 1) && (rebuild_v || (n_ovf_v > 0 && !(lean & 4)))) return;  // (bit 2: k_assoc_dense follows in this graph)
-  pair_clock_begin(INSTR && P.kernel_clock && (lean & 3) == 1 && pb.bx == 0, const_cast<PairState*>(st), 0);
+  // a waiting pair does not advance: it waits for the next rebuild opportunity / for the host to switch its group to the
+  // full graph (k_coeff skips it too and tells the host)
+  const SlotState sv{rebuild_v, n_ovf_v};
+  if (slot_waits(lean, ASSOC_LEAN, ASSOC_LEAN_DENSE, &sv)) return;
+  pair_clock_begin(INSTR && P.kernel_clock && (lean & (ASSOC_LEAN | ASSOC_REPLAY)) == ASSOC_LEAN && pb.bx == 0, const_cast<PairState*>(st), 0);
   __shared__ AssocShared S;
   // tag of this launch's partials (cvo_wave.h): the call's serial and the pair's iteration count
   const int stamp_epoch = st->epoch, stamp_k = st->k;
@@ -407,11 +408,11 @@ __global__ __launch_bounds__(ASSOC_THREADS, FEAT != FEAT_GEO ? 1 : CVO_ASSOC_WAV
   if (threadIdx.x >= 64) return;
   // every row of the pair has been reduced (rows beyond their lists were evaluated by k_assoc_dense before this launch):
   // the block that stores its partial last finishes the twist of the iteration
-  if (P.mode == 0) {
-    const unsigned long long clk0 = pair_clock_peek(INSTR && P.kernel_clock && (lean & 3) == 1, st, 0);
+  if (P.mode == CALL_ALIGN) {
+    const unsigned long long clk0 = pair_clock_peek(INSTR && P.kernel_clock && (lean & (ASSOC_LEAN | ASSOC_REPLAY)) == ASSOC_LEAN, st, 0);
     const bool last = flow_gate(D, nblk, nblk, tag, stamp_epoch, stamp_k);
     if (last && threadIdx.x == 0 && clk0) D->st->clk_last_assoc = pair_clock_ticks(clk0);  // added up by the update
-  } else if (lean & 8) {  // single evaluation that only wants A_sum (inner_product_gpu)
+  } else if (lean & ASSOC_ASUM_ONLY) {
     asum_gate(D, nblk);
   }
   if (INSTR && P.phase_ticks && threadIdx.x == 0) {

@@ -240,7 +240,7 @@ __global__ __launch_bounds__(64 * DENSE_WAVES, (!WIDE && FEAT == FEAT_GEO) ? CVO
         // flight it - not the evaluation - was most of a long row's time; the double sum of the values only where somebody
         // reads it: the single evaluations)
         const int c = lane < 6 ? lane : 0;
-        const bool want_asum = P.mode != 0;
+        const bool want_asum = P.mode != CALL_ALIGN;
         int k = 0;
         for (; k + 16 <= nstaged; k += 16) {
           float2 e[16];
@@ -376,7 +376,7 @@ __global__ __launch_bounds__(64 * DENSE_WAVES, (!WIDE && FEAT == FEAT_GEO) ? CVO
     // (CvoGPU.cu:767-780) - the replay is one dependent chain per component and the only serial part of a wide row
     float acc = 0.f;
     double asum = 0;
-    const bool want_asum = P.mode != 0;
+    const bool want_asum = P.mode != CALL_ALIGN;
     auto fill = [&](int s0, float2(*buf)[6]) {
       const int t = (int)threadIdx.x - 128;
       const int sl = s0 + t;

@@ -135,8 +135,7 @@ __device__ __forceinline__ void coeff_rows(const DevParams& P, const PairDesc* _
 // ------------------------------------------------------------------------------------------
 // k_coeff: coefficient phase + (align loop) the update.  The block of a pair that finishes last runs update_body:
 // one launch less on the critical path of every iteration, and no block ever waits for another one.  Partials
-// cross blocks inside the launch, hence the coherent stores / loads (st_x / ld_x).
-// flags: bit 0 = lean graph, bit 5 = ... with k_assoc_dense in every iteration, the rest see update_body.
+// cross blocks inside the launch, hence the coherent stores / loads (st_x / ld_x).  flags: IterFlags (cvo_device.h).
 // ------------------------------------------------------------------------------------------
 template <bool INSTR>
 __global__ __launch_bounds__(ASSOC_THREADS, CVO_COEFF_WAVES) void k_coeff(const PairDesc* __restrict__ descs,
@@ -145,8 +144,8 @@ __global__ __launch_bounds__(ASSOC_THREADS, CVO_COEFF_WAVES) void k_coeff(const 
                                                          unsigned stride256, int Npad) {
   const unsigned long long tt0 = INSTR ? __builtin_readcyclecounter() : 0ull;
   // grid: per pair nblk row blocks x launch_split slices of the ELL slots; a pair uses csplit <= launch_split of them
-  const int nblk = nblk_split_pairs & 0x3fff, launch_split = (nblk_split_pairs >> 14) & 0x3f,
-            n_pairs = (int)((unsigned)nblk_split_pairs >> 20);
+  const CoeffWord cw = unpack_coeff_word(nblk_split_pairs);
+  const int nblk = cw.nblk, launch_split = cw.split, n_pairs = cw.n_pairs;
   // (+ 1: the pair's speculative block, update_speculate)
   PairBlock pb;
   if (!pair_block(nblk * launch_split + 1, n_pairs, pb)) return;
@@ -166,13 +165,14 @@ __global__ __launch_bounds__(ASSOC_THREADS, CVO_COEFF_WAVES) void k_coeff(const 
     // The speculative block: everything of the update that follows the step, on the predicted step, while the row blocks
     // work.  Not in the instrumented kernels, timing replays, traced calls (the record needs B..E) or single evaluations;
     // a waiting pair (lean graph) has nothing to advance.
-    if (INSTR || threadIdx.x >= 64 || (flags & (8 | 16))) return;
+    if (INSTR || threadIdx.x >= 64 || (flags & ITER_REPLAY)) return;
     const PairState* __restrict__ sh = states + pb.pair;
     const int status_h = sh->status, rebuild_h = sh->rebuild, ovf_h = sh->n_ovf;
     const DevParams Ph = *Pp;
-    if (status_h != 0 || Ph.mode != 0 || Ph.trace_capacity != 0) return;
-    if ((flags & 1) && (rebuild_h || (ovf_h > 0 && !(flags & 32)))) return;
-    update_speculate(D, states + pb.pair, Ph, flags | 4, S.u, D->call_serial);
+    if (status_h != 0 || Ph.mode != CALL_ALIGN || Ph.trace_capacity != 0) return;
+    const SlotState sw{rebuild_h, ovf_h};
+    if (slot_waits(flags, ITER_LEAN, ITER_LEAN_DENSE, &sw)) return;
+    update_speculate(D, states + pb.pair, Ph, flags | ITER_FROM_COEFF, S.u, D->call_serial);
     return;
   }
   const int cq = pb.bx % launch_split;
@@ -227,29 +227,29 @@ __global__ __launch_bounds__(ASSOC_THREADS, CVO_COEFF_WAVES) void k_coeff(const 
   // (rows beyond their cached lists - hundreds of nonzeros: clustered clouds, the K cap - are not walked here: k_coeff_dense,
   // a wave per row, has left their sums in PairDesc::rowcoef; the split is the pair's own, whatever company it is solved in)
   if (cq >= csplit) return;
-  const bool replay = (flags & 8) != 0;  // cvo_debug_time_kernels: same work, nothing written back
+  const bool replay = (flags & ITER_REPLAY) != 0;
   if (!replay && status_v != 0) return;
-  if (flags & 1) {
-    if (rebuild_v || (ovf > 0 && !(flags & 32))) {  // waiting, see k_assoc; tell the host which graph this pair needs
-      if (pb.bx == 0 && cq == 0 && threadIdx.x == 0) {
-        st->n_stalls++;
-        if (ovf > 0 && !(flags & 32)) {
-          st->want_full = 4;
-          *D->want_out = 4;
-          *D->want_host = 4;
-        }
+  const SlotState sv{rebuild_v, ovf};
+  if (slot_waits(flags, ITER_LEAN, ITER_LEAN_DENSE, &sv)) {  // tell the host which graph this pair needs
+    if (pb.bx == 0 && cq == 0 && threadIdx.x == 0) {
+      st->n_stalls++;
+      if (ovf > 0 && !(flags & ITER_LEAN_DENSE)) {  // a rebuild opportunity in every iteration, with k_assoc_dense
+        const int want = want_encode(2, true);
+        st->want_full = want;
+        *D->want_out = want;
+        *D->want_host = want;
       }
-      return;
     }
+    return;
   }
-  if (P.mode != 0) return;
+  if (P.mode != CALL_ALIGN) return;
   pair_clock_begin(INSTR && P.kernel_clock && !replay && pb.bx == 0 && cq == 0, st, 1);
   const int epoch = st_in->epoch;  // launches of this kernel the pair has completed (bumped by the updating block)
   __shared__ int s_last;
   const int N_ = D->N, pos_ = pb.bx * ASSOC_THREADS + threadIdx.x;
   if (pos_ >= N_) head.nnz = 0;
-  // the row's class as k_list and k_assoc see it: more candidates than row_max (bit 6: 32-entry lists, M >= 65536)
-  head.dense = pos_ < N_ && ovf > 0 && __float_as_int(head.x.w) > min(row_max_v, (flags & 64) ? ASSOC_CAP32 : ASSOC_CAP16);
+  // the row's class as k_list and k_assoc see it: more candidates than row_max
+  head.dense = pos_ < N_ && ovf > 0 && __float_as_int(head.x.w) > min(row_max_v, (flags & ITER_IDX32) ? ASSOC_CAP32 : ASSOC_CAP16);
   if (cq > 0 && (unsigned)cq < head.nnz) head.e_n = D->ell[(size_t)cq * N_ + pos_];  // (small clouds only: later slices)
   float twist[6];
   for (int c = 0; c < 3; c++) {
@@ -295,8 +295,8 @@ __global__ __launch_bounds__(ASSOC_THREADS, CVO_COEFF_WAVES) void k_coeff(const 
     g_phase_ticks[1][blockIdx.x & 4095][2] = tt2;
     g_phase_ticks[1][blockIdx.x & 4095][3] = tt3;
   }
-  if (!s_last || (flags & 16)) return;  // (bit 4: cost breakdown of cvo_debug_time_kernels, coefficient phase only)
-  update_body<false, true>(upd, P, flags | 4, n_flow_upd, S.u, twist, hot_regs, clk0, tag, !INSTR);
+  if (!s_last) return;
+  update_body<false, true>(upd, P, flags | ITER_FROM_COEFF, n_flow_upd, S.u, twist, hot_regs, clk0, tag, !INSTR);
   if (INSTR && P.phase_ticks && threadIdx.x == 0) {
     g_phase_ticks[1][4096 + pb.pair][0] = tt0;
     g_phase_ticks[1][4096 + pb.pair][1] = tt3;

@@ -31,7 +31,7 @@ __global__ __launch_bounds__(64 * DENSE_WAVES) void k_coeff_dense(const PairDesc
   if (st->status != 0) return;
   const PairDesc* __restrict__ D = descs + blockIdx.y;
   const DevParams P = *Pp;
-  if (P.mode != 0) return;
+  if (P.mode != CALL_ALIGN) return;
   const int n_ovf = st->n_ovf;
   if (n_ovf == 0 || st->rebuild) return;  // (see k_assoc_dense)
   const int N = D->N, csplit = D->csplit;

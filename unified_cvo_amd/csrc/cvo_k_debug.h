@@ -17,11 +17,11 @@ namespace cvo_dev {
 // ------------------------------------------------------------------------------------------
 template <int FEAT>
 __global__ __launch_bounds__(256) void k_verify(const PairDesc* __restrict__ descs, const DevParams* __restrict__ Pp,
-                                                const int* __restrict__ status, int lean) {
+                                                const int* __restrict__ status, int flags) {
   if (status[blockIdx.y] != 0) return;
   const PairDesc* __restrict__ D = descs + blockIdx.y;
   PairState* st = D->st;
-  if ((lean & 1) && (st->rebuild || (st->n_ovf > 0 && !(lean & 4)))) return;  // the pair did not advance in this slot (see k_assoc)
+  if (slot_waits(flags, ASSOC_LEAN, ASSOC_LEAN_DENSE, st)) return;  // (AssocFlags, as k_assoc's)
   const DevParams P = *Pp;
   const int N = D->N, M = D->M, K = st->K;
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;

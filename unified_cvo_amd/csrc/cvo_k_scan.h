@@ -62,7 +62,7 @@ constexpr int SCAN_TILE_CAP = 128;  // (row group, slice) tiles a wave queues in
 
 template <int T>
 __global__ __launch_bounds__(256) void k_scan(const PairDesc* __restrict__ descs, const DevParams* __restrict__ Pp,
-                                              const PairState* __restrict__ states, int force) {
+                                              const PairState* __restrict__ states, bool force) {
   constexpr int RG = ROWS_PER_GROUP;
   // per-wave tile queue: the row operands of every overlapping group, fetched by the lane that found it
   __shared__ f32x4 s_rows[4][SCAN_TILE_CAP][RG];
@@ -172,19 +172,18 @@ __global__ __launch_bounds__(256) void k_scan(const PairDesc* __restrict__ descs
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     // ---- fine level over the queued tiles: 3 FMA per pair, a v_min3 tree per row, one compare per row
-    const int nproc = (force & 4) ? 0 : ntiles;  // timing variants of cvo_debug_time_scan
     // software pipeline: the LDS reads of tile ti + 1 are in flight while tile ti is evaluated
     f32x4 nxt[RG];
 #pragma unroll
     for (int u = 0; u < RG; u++) nxt[u] = rows[0][u];  // wave-uniform address: LDS broadcast
     int tg_nxt = tile_g[0];
-    for (int ti = 0; ti < nproc; ti++) {
+    for (int ti = 0; ti < ntiles; ti++) {
       f32x4 cur[RG];
 #pragma unroll
       for (int u = 0; u < RG; u++) cur[u] = nxt[u];
       const int tg = tg_nxt;
       {
-        const int tn = min(ti + 1, nproc - 1);
+        const int tn = min(ti + 1, ntiles - 1);
 #pragma unroll
         for (int u = 0; u < RG; u++) nxt[u] = rows[tn][u];
         tg_nxt = tile_g[tn];
@@ -206,7 +205,7 @@ __global__ __launch_bounds__(256) void k_scan(const PairDesc* __restrict__ descs
         mu[u] = __ballot(mn < cur[u].w);
         any |= mu[u];
       }
-      if (any && !(force & 2)) {  // usual case once tiles are culled: the group has candidates among this wave's 64*T targets
+      if (any) {  // usual case once tiles are culled: the group has candidates among this wave's 64*T targets
         // Lane q = u*T+t receives the bitmap word of (row u, chunk t) with v_writelane; the T lanes of a row
         // the whole tile is emitted with one (contiguous) mask
         // store and one returnless atomic instruction.

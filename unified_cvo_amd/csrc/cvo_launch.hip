@@ -1,4 +1,4 @@
-// cvo_launch.hip -- every kernel launch of the solver: scan geometry, the launch wrappers of the row-block kernels, LaunchGeom, one iteration (launch_core) and one chunk of iterations (launch_chunk) as the graphs capture them.
+// cvo_launch.hip -- every kernel launch of the solver: scan geometry, the launch wrappers of the row-block kernels, the flag words of an iteration (iteration_words), one iteration (launch_core) and one chunk of iterations (launch_chunk) as the graphs capture them.
 // A SECTION of the one translation unit cvo_hip.hip (which includes the sections in dependency order and says why it is one
 // unit); not compiled on its own.  Shared declarations: cvo_internal.h.
 #ifndef CVO_COEFF_DENSE_MULTI_FROM
@@ -24,7 +24,8 @@ void choose_scan_config(const cvo_ctx* ctx, int n_pairs, int NG, int Mpad, int* 
   *gpb_out = gpb;
 }
 
-void launch_scan(hipStream_t s, int T, dim3 grid, const PairDesc* descs, const DevParams* dp, const PairState* st, int force) {
+// force: scan the pairs whose lists are current too (cvo_debug_time_scan); otherwise a pair is scanned when its list expired
+void launch_scan(hipStream_t s, int T, dim3 grid, const PairDesc* descs, const DevParams* dp, const PairState* st, bool force) {
   switch (T) {
     case 1: hipLaunchKernelGGL(k_scan<1>, grid, dim3(256), 0, s, descs, dp, st, force); break;
     case 2: hipLaunchKernelGGL(k_scan<2>, grid, dim3(256), 0, s, descs, dp, st, force); break;
@@ -58,9 +59,9 @@ void launch_assoc_t(hipStream_t s, bool instr, dim3 grid, const PairDesc* descs,
 
 // feat: FEAT_GEO / FEAT_ALL / FEAT_COL / FEAT_HOT (cvo_pair_math.h), chosen per call by call_feat()
 void launch_assoc(hipStream_t s, bool idx16, int feat, bool instr, int nblk, int n_pairs, const PairDesc* descs,
-                  const DevParams* dp, const PairState* st, const ArenaArg& A, int lean) {
+                  const DevParams* dp, const PairState* st, const ArenaArg& A, int flags) {
   const dim3 grid = row_grid(nblk, n_pairs);
-  const int packed = (lean & 0xf) | (nblk << 4) | (int)((unsigned)n_pairs << 20);  // (ensure_workspace bounds both)
+  const int packed = pack_assoc_word(flags, nblk, n_pairs);  // (setup_batch bounds both)
 #define CVO_ASSOC_CASE(F)                                                                              \
   case F:                                                                                              \
     if (idx16)                                                                                         \
@@ -80,7 +81,7 @@ void launch_assoc(hipStream_t s, bool idx16, int feat, bool instr, int nblk, int
 
 void launch_coeff(hipStream_t s, bool instr, int nblk, int split, int n_pairs, const PairDesc* descs, const DevParams* dp,
                   PairState* st, const ArenaArg& A, int flags) {
-  const int packed = nblk | (split << 14) | (int)((unsigned)n_pairs << 20);  // 14 + 6 + 12 bits
+  const int packed = pack_coeff_word(nblk, split, n_pairs);  // (setup_batch bounds nblk and n_pairs)
   if (instr)
     hipLaunchKernelGGL(k_coeff<true>, row_grid(nblk * split + 1, n_pairs), dim3(ASSOC_THREADS), 0, s, descs, dp, st, A.base, flags,
                        packed, A.stride256, A.Npad);
@@ -91,13 +92,13 @@ void launch_coeff(hipStream_t s, bool instr, int nblk, int split, int n_pairs, c
 
 // CVO_VERIFY_LISTS: literal re-derivation of every row after the association of an iteration (k_verify)
 void launch_verify(hipStream_t s, int feat, int nblk, int n_pairs, const PairDesc* descs, const DevParams* dp, const int* st,
-                   int lean) {
+                   int flags) {
   const dim3 grid((unsigned)nblk, (unsigned)n_pairs);
   // (the self-check always takes the general form of the semantic kernel: one-hot rows through the row arithmetic)
   if (feat != FEAT_GEO)
-    hipLaunchKernelGGL(k_verify<FEAT_ALL>, grid, dim3(256), 0, s, descs, dp, st, lean);
+    hipLaunchKernelGGL(k_verify<FEAT_ALL>, grid, dim3(256), 0, s, descs, dp, st, flags);
   else
-    hipLaunchKernelGGL(k_verify<FEAT_GEO>, grid, dim3(256), 0, s, descs, dp, st, lean);
+    hipLaunchKernelGGL(k_verify<FEAT_GEO>, grid, dim3(256), 0, s, descs, dp, st, flags);
 }
 
 // a small pair solved alone has a block per overflow row (dense_blocks_for): k_assoc_dense's instantiation with the wide-row phase
@@ -124,27 +125,38 @@ void launch_dense(hipStream_t s, int feat, bool wide, int n_pairs, int dense_blo
 
 // which instantiation of the association kernels a call needs (FEAT_*, cvo_pair_math.h)
 inline int call_feat(const DevParams& dp, bool all_one_hot) {
-  if (dp.mode == 2) return FEAT_ALL;
+  if (dp.mode == CALL_NONISO) return FEAT_ALL;
   if (!(dp.use_col || dp.use_sem || dp.use_geotype)) return FEAT_GEO;
   if (!dp.use_sem) return FEAT_COL;
   return all_one_hot ? FEAT_HOT : FEAT_ALL;
 }
 
-struct LaunchGeom {
-  int n_pairs, p0, T, gx, gy, nba, npb, csplit;
-  int nbl, nbv;  // blocks of k_list (LIST_THREADS rows each) and k_verify (grid x) for the largest source cloud
-  int dense_blocks = DENSE_BLOCKS_MIN;  // k_assoc_dense grid x = PairDesc::dense_blocks of every pair of the launch
-  int horizon_cap = 1 << 20;  // the lean graph's period (DevParams::lean_U)
-  bool idx16, instr, verify;
-  bool wide;  // k_assoc_dense's wide-row instantiation (dense_wide)
-  int feat = FEAT_GEO;  // which instantiation of the association kernels the call needs (call_feat)
-  hipStream_t stream;
-  ArenaArg arena;  // of pair p0
+// What an iteration slot of a graph is.  iteration_words turns it into the flag words of its kernels; no other host code
+// writes a flag value.
+struct IterSlot {
+  bool lean = false;             // a lean graph's slot: a pair that needs the rebuild kernels or k_assoc_dense waits
+  bool lean_dense = false;       // ... a lean slot that runs k_assoc_dense all the same
+  bool idx32 = false;            // 32-bit candidate lists (a LaunchGeom without idx16)
+  bool rebuild_follows = false;  // the rebuild kernels run right after this iteration
+  int horizon = 0;               // iterations the list has to survive without another rebuild opportunity (0: full graph)
+  bool replay = false;           // timing replay of cvo_debug_time_kernels: nothing is written back
+  bool asum_only = false;        // a single evaluation whose association only posts A_sum (run_ip_chain)
 };
+struct IterWords {
+  int assoc;  // AssocFlags of k_assoc / k_verify
+  int iter;   // IterFlags of k_coeff / k_update
+};
+inline IterWords iteration_words(const IterSlot& s) {
+  const bool lean_dense = s.lean && s.lean_dense;
+  return {(s.lean ? ASSOC_LEAN : 0) | (s.replay ? ASSOC_REPLAY : 0) | (lean_dense ? ASSOC_LEAN_DENSE : 0) |
+              (s.asum_only ? ASSOC_ASUM_ONLY : 0),
+          (s.lean ? ITER_LEAN : 0) | (s.rebuild_follows ? ITER_REBUILD_FOLLOWS : 0) | (s.replay ? ITER_REPLAY : 0) |
+              (lean_dense ? ITER_LEAN_DENSE : 0) | (s.idx32 ? ITER_IDX32 : 0) | (s.horizon << ITER_HORIZON_SHIFT)};
+}
 
 void launch_init(cvo_ctx* c, const LaunchGeom& g) {
   hipLaunchKernelGGL(k_update<true>, dim3(g.n_pairs), dim3(64), 0, g.stream, c->d_descs + g.p0, c->d_params,
-                     c->d_status + 2 * g.p0, 0);
+                     c->d_status + 2 * g.p0, iteration_words({}).iter);
 }
 
 // The rebuild kernels: no-ops (early exit) unless k_update flagged the pair's candidate list as expired.
@@ -152,32 +164,29 @@ void launch_rebuild(cvo_ctx* c, const LaunchGeom& g) {
   const PairDesc* descs = c->d_descs + g.p0;
   const PairState* states = c->d_states + g.p0;
   hipLaunchKernelGGL(k_prep, dim3(g.npb, g.n_pairs), dim3(PREP_THREADS), 0, g.stream, descs, c->d_params, states);
-  launch_scan(g.stream, g.T, dim3(g.gx, g.gy, g.n_pairs), descs, c->d_params, states, 0);
+  launch_scan(g.stream, g.T, dim3(g.gx, g.gy, g.n_pairs), descs, c->d_params, states, false);
   launch_list(g.stream, g.idx16, g.nbl, g.n_pairs, descs, c->d_params, states);
 }
 
 // One optimiser iteration over the current lists: association, [overflow rows], coefficients + update (the last
-// block of k_coeff).  Lean: no k_assoc_dense, pairs with overflow rows or an expired list wait.  `flags` see
-// update_body.
-// `dense`: a lean graph that runs k_assoc_dense all the same (pairs with overflow rows / in the dense regime that need
-// no rebuild opportunity in every iteration).
-void launch_core(cvo_ctx* c, const LaunchGeom& g, bool lean, int flags, bool dense = false) {
+// block of k_coeff).  Lean: no k_assoc_dense, pairs with overflow rows or an expired list wait - unless the slot is
+// lean_dense (pairs with overflow rows / in the dense regime that need no rebuild opportunity in every iteration).
+void launch_core(cvo_ctx* c, const LaunchGeom& g, const IterSlot& slot) {
   const PairDesc* descs = c->d_descs + g.p0;
   const int* st = c->d_status + 2 * g.p0;  // the sub-batch's status words (see setup_batch)
-  const bool lean_dense = lean && dense;
+  const IterWords w = iteration_words(slot);
+  const bool dense = !slot.lean || slot.lean_dense;
   // rows beyond their cached lists first (a wave per row; per-row results), then every row's reduction in k_assoc
-  if (!lean || dense) launch_dense(g.stream, g.feat, g.wide, g.n_pairs, g.dense_blocks, descs, c->d_params, c->d_states + g.p0);
-  launch_assoc(g.stream, g.idx16, g.feat, g.instr, g.nba, g.n_pairs, descs, c->d_params, c->d_states + g.p0, g.arena,
-               (lean ? 1 : 0) | (lean_dense ? 4 : 0));
-  if (g.verify) launch_verify(g.stream, g.feat, g.nbv, g.n_pairs, descs, c->d_params, st, (lean ? 1 : 0) | (lean_dense ? 4 : 0));
+  if (dense) launch_dense(g.stream, g.feat, g.wide, g.n_pairs, g.dense_blocks, descs, c->d_params, c->d_states + g.p0);
+  launch_assoc(g.stream, g.idx16, g.feat, g.instr, g.nba, g.n_pairs, descs, c->d_params, c->d_states + g.p0, g.arena, w.assoc);
+  if (g.verify) launch_verify(g.stream, g.feat, g.nbv, g.n_pairs, descs, c->d_params, st, w.assoc);
   // ... their coefficient sums likewise (k_coeff_dense leaves per-row sums, k_coeff picks them up)
-  if (!lean || dense)
+  if (dense)
     // (7 waves per SIMD against k_assoc_dense's 4: twice the blocks, so that a lone pair's rows get a wave each - the kernel
     // then lasts as long as its longest row, not as two)
     hipLaunchKernelGGL((k_coeff_dense<4>), dim3(g.n_pairs <= 4 ? std::min(2 * g.dense_blocks, (int)DENSE_BLOCKS_MAX) : g.dense_blocks, g.n_pairs), dim3(256), 0, g.stream, descs,
                        c->d_params, c->d_states + g.p0, g.n_pairs >= CVO_COEFF_DENSE_MULTI_FROM ? 8 : 1);
-  launch_coeff(g.stream, g.instr, g.nba, g.csplit, g.n_pairs, descs, c->d_params, c->d_states + g.p0, g.arena,
-               flags | (lean ? 1 : 0) | (lean_dense ? 32 : 0) | (g.idx16 ? 0 : 64));
+  launch_coeff(g.stream, g.instr, g.nba, g.csplit, g.n_pairs, descs, c->d_params, c->d_states + g.p0, g.arena, w.iter);
 }
 
 // A chunk (see ChunkPlan).  Full: every iteration can rebuild its candidate list and serve overflow rows.  Full without
@@ -187,9 +196,10 @@ void launch_core(cvo_ctx* c, const LaunchGeom& g, bool lean, int flags, bool den
 // `period` iterations; pairs that need more wait for a full chunk.
 void launch_chunk(cvo_ctx* c, const LaunchGeom& g, const ChunkPlan& p) {
   if (p.every_iteration()) {
+    const IterSlot slot{.lean = p.kind == ChunkKind::FullNoDense, .idx32 = !g.idx16, .rebuild_follows = true};
     for (int u = 0; u < p.U; u++) {
       launch_rebuild(c, g);
-      launch_core(c, g, p.kind == ChunkKind::FullNoDense, 2);
+      launch_core(c, g, slot);
     }
     return;
   }
@@ -198,7 +208,8 @@ void launch_chunk(cvo_ctx* c, const LaunchGeom& g, const ChunkPlan& p) {
     const bool last = (u % p.period == p.period - 1) || u == p.U - 1;
     // (horizon of the rebuild rule: the lean graph's period even in a calm chunk, whose one opportunity per chunk is a bet
     // on the list outliving the linear prediction - a pair that loses it waits for the next chunk)
-    launch_core(c, g, true, (last ? 2 : 0) | (std::min(p.period, g.horizon_cap) << 8), p.dense);
+    launch_core(c, g, {.lean = true, .lean_dense = p.dense, .idx32 = !g.idx16, .rebuild_follows = last,
+                       .horizon = std::min(p.period, g.horizon_cap)});
   }
 }
 

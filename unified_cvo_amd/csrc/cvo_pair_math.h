@@ -21,7 +21,7 @@ __device__ __forceinline__ RowData make_row(const DevParams& P, const float4 x, 
   const float l = compute_range_ell(ell, a_to_sensor);
   float thr = 1.f;
   if (P.use_geo) thr = (float)(-2.0 * l * l * (double)P.log_geo);
-  if (P.mode == 2) thr = P.d2_cull;  // non-isotropic kernel: no cut-off of its own, this one only steers the scan
+  if (P.mode == CALL_NONISO) thr = P.d2_cull;  // non-isotropic kernel: no cut-off of its own, this one only steers the scan
   const double den = 2.0 * l * l;
   return RowData{x.x, x.y, x.z, l, thr, 0, den, rcp_refined(den)};
 }
@@ -42,7 +42,7 @@ __device__ __forceinline__ FeatDen make_feat_den(const DevParams& P) {
   FeatDen f;
   f.c_den = 2.0 * P.c2;
   f.c_rcp = rcp_refined(f.c_den);
-  f.s_den = P.mode == 2 ? 2.0 * P.s_ell_sq : 2.0 * P.s_ell * P.s_ell;
+  f.s_den = P.mode == CALL_NONISO ? 2.0 * P.s_ell_sq : 2.0 * P.s_ell * P.s_ell;
   f.s_rcp = rcp_refined(f.s_den);
   f.ek = make_exp_consts();
   {  // (the general branch of eval_pair_yt, word for word, on the only two distances one-hot rows can have)
@@ -91,7 +91,7 @@ __device__ __forceinline__ IterView load_iter_view(const PairState* st) {
 //   FEAT_HOT  + ONE-HOT semantics: every cloud of the call has exact one-hot class rows (checked at upload), so the 19-term
 //             squared distance of CvoGPU.cu:563-569 is 0 (same class) or exactly 2 (different) and the semantic kernel one of
 //             two constants - a 4-byte class id per candidate instead of two 80-byte rows (config 4);
-//   FEAT_ALL  everything: soft class distributions, the non-isotropic kernel of mode 2.
+//   FEAT_ALL  everything: soft class distributions, the non-isotropic kernel of CALL_NONISO.
 constexpr int FEAT_GEO = 0, FEAT_ALL = 1, FEAT_COL = 2, FEAT_HOT = 3;
 // i / j index the FEATURE arrays (colour, class distributions, geometric types), which clouds keep in spatial order:
 // i = the row's sorted position, j = the target's sorted position.
@@ -109,7 +109,7 @@ __device__ __forceinline__ bool eval_pair_yt(const DevParams& P, const PairDesc*
     geo_sim = dab * dab / (n2a * n2b);
     if ((double)geo_sim < 0.01) return false;
   }
-  if (MODE2 && P.use_geo && P.mode == 2) {  // (the host launches the FEAT_ALL instantiations for mode 2)
+  if (MODE2 && P.use_geo && P.mode == CALL_NONISO) {  // (the host launches the FEAT_ALL instantiations for CALL_NONISO)
     // mahananobis_distance (CvoGPU.cu:152-171): dist = a - b, (dist^T * kernel_inv) * dist; no cut-off (236-238, 279-284)
     const float d0 = r.x - yt.x, d1 = r.y - yt.y, d2v = r.z - yt.z;
     const float r0 = dot3_dev(d0, d1, d2v, P.kinv[0], P.kinv[3], P.kinv[6]);
@@ -160,7 +160,7 @@ __device__ __forceinline__ bool eval_pair_yt(const DevParams& P, const PairDesc*
         tmp = a.w - b.w; res = __builtin_fmaf(tmp, tmp, res);
       }
     }
-    if (res < P.d2_s_thres)  // (F.s_den: 2.0 * s_ell^2 kept in float for mode 2, 2.0 * s_ell * s_ell otherwise)
+    if (res < P.d2_s_thres)  // (F.s_den: 2.0 * s_ell^2 kept in float for CALL_NONISO, 2.0 * s_ell * s_ell otherwise)
       sk = (float)((double)(P.s_sigma * P.s_sigma) * exp_ocml<true>(div_by((double)(-res), F.s_den, F.s_rcp), F.ek));
     else
       return false;
@@ -237,7 +237,7 @@ __device__ __forceinline__ void visit_pair_yt(const DevParams& P, const PairDesc
     A.v0 = __builtin_fmaf(dx, a, A.v0);
     A.v1 = __builtin_fmaf(dy, a, A.v1);
     A.v2 = __builtin_fmaf(dz, a, A.v2);
-    if (P.mode != 0) A.asum += (double)a;  // A_sum (SparseKernelMat.cu:62-68): only the single evaluations read it
+    if (P.mode != CALL_ALIGN) A.asum += (double)a;  // A_sum (SparseKernelMat.cu:62-68): only the single evaluations read it
   }
 }
 

@@ -61,13 +61,14 @@ inline bool queue_fast(const ChunkPlan& p) { return p.every_iteration() || p.kin
 int queue_fill(cvo_batch_queue* q, int p, const cvo_batch_queue::Job& job) {
   cvo_ctx* ctx = q->ctx;
   const int g = group_of(q->slots, q->G, p);
-  fill_pair(ctx, &q->S, &q->params, &q->opts, 0, 0.f, q->slots, p, job.X, job.Y, job.T, next_call_serial(), job.max_iter);
+  fill_pair(ctx, &q->S, &q->params, &q->opts, CALL_ALIGN, 0.f, q->slots, p, job.X, job.Y, job.T, next_call_serial(), job.max_iter);
   q->h_desc_stage[p] = ctx->h_descs[p];
   q->h_state_stage[p] = ctx->h_states[p];
   hipStream_t st = q->geom[g].stream;
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_descs + p, q->h_desc_stage + p, sizeof(PairDesc), hipMemcpyHostToDevice, st));
   HIP_TRY(ctx, hipMemcpyAsync(ctx->d_states + p, q->h_state_stage + p, sizeof(PairState), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_update<true>, dim3(1), dim3(64), 0, st, ctx->d_descs + p, ctx->d_params, ctx->d_status, 0);
+  hipLaunchKernelGGL(k_update<true>, dim3(1), dim3(64), 0, st, ctx->d_descs + p, ctx->d_params, ctx->d_status,
+                     iteration_words({}).iter);
   HIP_TRY(ctx, hipGetLastError());
   q->slot[p].ticket = job.ticket;
   q->slot[p].start_chunk = q->launched[g];
@@ -193,7 +194,7 @@ int cvo_batch_open(cvo_ctx* ctx, const cvo_params_t* params, int slots, int max_
   if (opts) q->opts.max_iterations = opts->max_iterations;
   q->slots = slots;
   const QueueDims qd{max_source_points, max_target_points, min_source_points > 0 ? min_source_points : max_source_points};
-  int rc = setup_batch(ctx, params, slots, nullptr, nullptr, nullptr, &q->opts, 0, 0.f, &q->S, &q->dp, nullptr, &qd);
+  int rc = setup_batch(ctx, params, slots, nullptr, nullptr, nullptr, &q->opts, CALL_ALIGN, 0.f, &q->S, &q->dp, nullptr, &qd);
   if (rc != CVO_OK) {
     delete q;
     return rc;

@@ -73,14 +73,6 @@ DevParams make_dev_params(const cvo_ctx* ctx, const cvo_params_t& p) {
 // Scan geometry: T chunks of 64 sorted targets per wave (smaller slices cull better, larger ones
 // amortise the row operands) and the number of row groups per block, chosen so that a launch has a
 
-struct BatchSetup {
-  int N, M, T, gpb, gx, gy, G;
-  bool long_lists = false;
-  Dims d;
-  PairLayout L;
-  LaunchGeom geom;
-};
-
 // Sub-batches (see cvo_ctx) are contiguous blocks of pairs: sub-batch g of G holds pairs [p0, p1) of n
 struct GroupRange {
   int p0, p1;
@@ -99,7 +91,7 @@ struct QueueDims {
 };
 
 // Descriptor + initial state of the pair that occupies slot p of the workspace (host copies; the caller uploads them).
-void fill_pair(cvo_ctx* ctx, const BatchSetup* S, const cvo_params_t* params, const cvo_align_opts_t* opts, int mode, float mode_ell,
+void fill_pair(cvo_ctx* ctx, const BatchSetup* S, const cvo_params_t* params, const cvo_align_opts_t* opts, CallMode mode, float mode_ell,
                int n_slots, int p, const cvo_cloud* X, const cvo_cloud* Y, const float* Tm, unsigned long long serial, int max_iter) {
   const int trace_cap = (opts && opts->trace) ? opts->trace_capacity : 0;
   const int Kmax = params->nearest_neighbors_max;
@@ -197,9 +189,9 @@ void fill_pair(cvo_ctx* ctx, const BatchSetup* S, const cvo_params_t* params, co
       for (int j = 0; j < 3; j++) st.R[3 * i + j] = Tm[4 * j + i];  // CvoGPU.cu:1363-1364
       st.T[i] = Tm[12 + i];
     }
-    st.ell = mode == 0 ? params->ell_init : mode_ell;  // CvoState.cu:30
+    st.ell = mode == CALL_ALIGN ? params->ell_init : mode_ell;  // CvoState.cu:30
     st.K = Kmax;                                        // CvoGPU.cu:1385
-    if (mode == 0 && opts && opts->override_state) {  // (validated by the caller)
+    if (mode == CALL_ALIGN && opts && opts->override_state) {  // (validated by the caller)
       st.ell = opts->ell0;
       st.K = opts->K0;
     }
@@ -220,7 +212,7 @@ unsigned long long next_call_serial() {
 // ranges the kernels' arithmetic is stated for, the attribute arrays the call's kernels will read.  N / M: the largest
 // source / target cloud of the call.
 int check_call(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo_cloud* const* sources, const cvo_cloud* const* targets,
-               const cvo_align_opts_t* opts, int mode, float mode_ell, const QueueDims* qd, int* N_out, int* M_out) {
+               const cvo_align_opts_t* opts, CallMode mode, float mode_ell, const QueueDims* qd, int* N_out, int* M_out) {
   if (!ctx) return CVO_E_INVALID;
   if (ctx->queue_open && !qd) return fail(ctx, CVO_E_INVALID, "a batch queue is open on this context (cvo_batch_close it first)");
   if (!params || n_pairs <= 0 || (!qd && (!sources || !targets))) return fail(ctx, CVO_E_INVALID, "null argument");
@@ -235,13 +227,13 @@ int check_call(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo_
     // 2 s_ell^2 far from zero, denormals and infinity.  Lengthscales outside [1e-30, 1e15] (and non-finite ones) are refused
     // here instead of silently leaving that domain; coordinates are bounded the same way below.
     auto ok_scale = [](float v) { return std::isfinite(v) && v >= 1e-30f && v <= 1e15f; };
-    const float ell0 = mode == 0 ? ((opts && opts->override_state) ? opts->ell0 : params->ell_init) : mode_ell;
-    if (!ok_scale(ell0) || (mode == 0 && !ok_scale(params->ell_min)))
+    const float ell0 = mode == CALL_ALIGN ? ((opts && opts->override_state) ? opts->ell0 : params->ell_init) : mode_ell;
+    if (!ok_scale(ell0) || (mode == CALL_ALIGN && !ok_scale(params->ell_min)))
       return fail(ctx, CVO_E_INVALID, "lengthscale outside [1e-30, 1e15] (ell_init / ell_min / the ell of the call)");
     if (params->is_using_intensity && !ok_scale(params->c_ell)) return fail(ctx, CVO_E_INVALID, "c_ell outside [1e-30, 1e15]");
     if (params->is_using_semantics && !ok_scale(params->s_ell)) return fail(ctx, CVO_E_INVALID, "s_ell outside [1e-30, 1e15]");
   }
-  if (mode == 0 && opts && opts->override_state) {
+  if (mode == CALL_ALIGN && opts && opts->override_state) {
     // the ELL holds nearest_neighbors_max slots per row and the kernels write slot nnz while nnz < K
     if (opts->K0 < 1 || opts->K0 > params->nearest_neighbors_max)
       return fail(ctx, CVO_E_INVALID, "cvo_align_opts_t.K0 must lie in [1, nearest_neighbors_max]");
@@ -265,7 +257,7 @@ int check_call(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo_
   (void)hipGetLastError();  // a stale error of an unrelated earlier call must not be attributed to this one
   {  // attribute arrays the kernels of this call read but a cloud was uploaded without: zeros, as upstream has them
     const bool nf = params->is_using_intensity != 0, nl = params->is_using_semantics != 0,
-               ng = params->is_using_geometric_type != 0 && mode != 2;
+               ng = params->is_using_geometric_type != 0 && mode != CALL_NONISO;
     if ((nf || nl || ng) && !qd)
       for (int p = 0; p < n_pairs; p++) {
         int rc0 = ensure_attributes(ctx, sources[p], nf, nl, ng);
@@ -279,7 +271,7 @@ int check_call(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo_
 }
 
 int setup_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo_cloud* const* sources,
-                const cvo_cloud* const* targets, const float* init_T, const cvo_align_opts_t* opts, int mode,
+                const cvo_cloud* const* targets, const float* init_T, const cvo_align_opts_t* opts, CallMode mode,
                 float mode_ell, BatchSetup* S, DevParams* dp_out, const float* kernel_inv_and_cull = nullptr,
                 const QueueDims* qd = nullptr) {
   int N = 0, M = 0;
@@ -323,19 +315,24 @@ int setup_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo
       return fail(ctx, CVO_E_NOMEM, msg);
     }
   }
-  int rc = ensure_workspace(ctx, n_pairs, S->L.total);
-  if (rc != CVO_OK) return rc;
   // sub-batches on separate streams (see cvo_ctx): the scan geometry is chosen for one group's launch
   S->G = n_pairs >= 32 ? 4 : (n_pairs >= 8 ? 2 : 1);
   if (const char* e = ctx_opt(ctx, "STREAMS")) S->G = std::max(1, std::min(atoi(e), (int)cvo_ctx::MAX_GROUPS));
   S->G = std::min(S->G, n_pairs);
-  if ((n_pairs + S->G - 1) / S->G > 4095 || S->d.nblk_assoc > 16383)
-    return fail(ctx, CVO_E_INVALID, "batch too large for one call: at most 4095 pairs per stream and 2097024 source points per cloud");
+  // (refused before the workspace grows; the limits are those of the packed launch words)
+  if ((n_pairs + S->G - 1) / S->G > LAUNCH_PAIRS_MAX || S->d.nblk_assoc > LAUNCH_NBLK_MAX) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "batch too large for one call: at most %d pairs per stream and %d source points per cloud",
+             LAUNCH_PAIRS_MAX, LAUNCH_NBLK_MAX * ASSOC_THREADS);
+    return fail(ctx, CVO_E_INVALID, msg);
+  }
+  int rc = ensure_workspace(ctx, n_pairs, S->L.total);
+  if (rc != CVO_OK) return rc;
   choose_scan_config(ctx, (n_pairs + S->G - 1) / S->G, S->d.NG, S->d.Mpad, &S->T, &S->gpb);
 
   DevParams dp = make_dev_params(ctx, *params);
   dp.mode = mode;
-  if (mode == 2) {  // non-isotropic kernel: 9 floats of the inverse (row-major) + the squared cull radius
+  if (mode == CALL_NONISO) {  // non-isotropic kernel: 9 floats of the inverse (row-major) + the squared cull radius
     for (int q = 0; q < 9; q++) dp.kinv[q] = kernel_inv_and_cull[q];
     dp.d2_cull = kernel_inv_and_cull[9];
     dp.s_ell_sq = params->s_ell * params->s_ell;
@@ -373,7 +370,7 @@ int setup_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo
   if (opts && opts->kernel_clock) dp.kernel_clock = 1;
   dp.trace_capacity = trace_cap;
   // the columns of the ELL entries (ell_j) are only written when somebody can ask for them afterwards
-  dp.keep_columns = (mode != 0 || trace_cap > 0 || dp.verify_lists || params->is_exporting_association ||
+  dp.keep_columns = (mode != CALL_ALIGN || trace_cap > 0 || dp.verify_lists || params->is_exporting_association ||
                      ctx_opt(ctx, "KEEP_COLUMNS")) ? 1 : 0;
   dp.trace_dense = opts ? opts->trace_dense : 0;
   dp.trace_every = opts ? opts->trace_every : 0;
@@ -431,7 +428,7 @@ int setup_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo
   for (int p = 0; p < n_pairs && !qd; p++) S->geom.csplit = std::max(S->geom.csplit, coeff_split(sources[p]->n));
   S->geom.npb = S->d.Mpad / PREP_THREADS + (S->d.NGpad * ROWS_PER_GROUP + PREP_THREADS - 1) / PREP_THREADS;
   S->geom.idx16 = M < 65536;
-  // (the non-isotropic kernel of mode 2 lives in the GENERAL instantiations only: single evaluations, never the loop)
+  // (the non-isotropic kernel of CALL_NONISO lives in the GENERAL instantiations only: single evaluations, never the loop)
   {
     // every cloud of the call with exact one-hot class rows (ids made at upload): the semantic kernel by class id
     bool all_hot = !qd && ctx_opt(ctx, "NO_ONEHOT") == nullptr;
@@ -442,19 +439,9 @@ int setup_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo
   S->geom.verify = dp.verify_lists != 0;
   S->geom.horizon_cap = std::max(1, dp.lean_U);
   if (!qd) ctx->last_xorder = sources[0]->h_order;
-  ctx->last_groups = S->G;
-  ctx->last_feat = S->geom.feat;
   ctx->last_pairs = n_pairs;
-  ctx->last_N = N;
-  ctx->last_M = M;
-  ctx->last_Kmax = Kmax;
+  ctx->last = *S;
   ctx->last_params = dp;
-  ctx->last_csplit = S->geom.csplit;
-  ctx->last_stride256 = S->geom.arena.stride256;
-  ctx->last_Npad = S->geom.arena.Npad;
-  ctx->last_gx = S->gx;
-  ctx->last_gy = S->gy;
-  ctx->last_layout = S->L;
   return CVO_OK;
 }
 
@@ -546,7 +533,7 @@ int cvo_align_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const
   BatchSetup S;
   DevParams dp;
   const auto t_host0 = std::chrono::steady_clock::now();
-  int rc = setup_batch(ctx, params, n_pairs, sources, targets, init_T, opts, 0, 0.f, &S, &dp);
+  int rc = setup_batch(ctx, params, n_pairs, sources, targets, init_T, opts, CALL_ALIGN, 0.f, &S, &dp);
   if (rc != CVO_OK) return rc;
   const auto t_host1 = std::chrono::steady_clock::now();
 

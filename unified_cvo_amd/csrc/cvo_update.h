@@ -62,10 +62,8 @@ __device__ __forceinline__ UpdDesc load_upd_desc(const PairDesc* __restrict__ D)
 }
 
 // Executed by the first wave of the calling block (the other threads only take part in the barriers).
-// flags: bit 1 = the rebuild kernels run right after this iteration, bit 2 = called from k_coeff, bit 3 = replay for
-// timing (nothing is written back), bits 8.. = how many
-// iterations the list has to survive without another rebuild opportunity (0 in the full graph).  n_flow_parts: association partials to
-// sum (the lean graph has no k_assoc_dense, so its slots are not read).
+// flags: IterFlags (cvo_device.h).  n_flow_parts: association partials to sum (the lean graph has no k_assoc_dense, so its
+// slots are not read).
 // PairState::want_full, the graph a pair asks the host for: a LEVEL - 2 = a rebuild opportunity in every iteration,
 // 1 = every lean_U2 iterations (short lean graph), 0 = every lean_U (lean graph), -1 = calm, one per chunk - and whether
 // k_assoc_dense has to run (overflow rows / the dense regime).  Encoded as: level without the dense kernel; 4 = level 2
@@ -111,9 +109,9 @@ __device__ __forceinline__ void update_advance(const UpdDesc& D, const DevParams
                                                const unsigned long long* s_n, const float step_w, const float* twist,
                                                const float e_front, const float s_front, const unsigned long long clk0,
                                                const bool spec, UpdOut& out) {
-  const bool trio_follows = INIT || (flags & 2) != 0;
-  const bool dry = (flags & 8) != 0;  // timing replay: compute everything, write nothing back
-  const int horizon = flags >> 8;
+  const bool trio_follows = INIT || (flags & ITER_REBUILD_FOLLOWS) != 0;
+  const bool dry = (flags & ITER_REPLAY) != 0;
+  const int horizon = iter_horizon(flags);
   int done = 0;
   if (!INIT && st->sync_err) {  // a partial of this launch or of k_assoc's never arrived (cvo_wave.h): the pair ends here
     done = 1;
@@ -127,7 +125,7 @@ __device__ __forceinline__ void update_advance(const UpdDesc& D, const DevParams
     }
   }
   if (!INIT) {
-    if (flags & 4) st->epoch++;  // generation of k_coeff's last-block counter
+    if (flags & ITER_FROM_COEFF) st->epoch++;  // generation of k_coeff's last-block counter
     const unsigned nnz = (unsigned)s_n[0], max_nnz = (unsigned)s_n[1];
     st->nnz = nnz;
     st->max_nnz = max_nnz;
@@ -135,7 +133,7 @@ __device__ __forceinline__ void update_advance(const UpdDesc& D, const DevParams
     st->ncand_total += st->ncand_list;
     st->noverflow = s_n[3];
     st->K_last = st->K;  // the stride upstream wrote this iteration's A matrix with (gpu_association_to_cpu)
-    if (P.mode != 0) {  // single evaluation: A_sum (SparseKernelMat.cu:62-68)
+    if (P.mode != CALL_ALIGN) {  // single evaluation: A_sum (SparseKernelMat.cu:62-68)
       st->asum = s_c[0];
       done = 1;
     } else {
@@ -312,7 +310,7 @@ __device__ __forceinline__ void update_advance(const UpdDesc& D, const DevParams
     const bool shrink_due = ell_next < P.rebuild_shrink * st->ell_build;
     const bool shrink_now = shrink_due && trio_follows &&
                             ((st->k & P.shrink_align) == 0 || ell_next < 0.85f * P.rebuild_shrink * st->ell_build);
-    bool rebuild = INIT || P.mode != 0 || !(used <= 1.f) || ell_next > st->ell_build || shrink_now;
+    bool rebuild = INIT || P.mode != CALL_ALIGN || !(used <= 1.f) || ell_next > st->ell_build || shrink_now;
     // ... or would expire before the next rebuild opportunity of the lean graph
     if (trio_follows && horizon > 0 && !(used + P.horizon_margin * (float)horizon * rate <= 1.f)) rebuild = true;
     // ... and, in a batch, at the common iteration counts of the optional rebuilds: a list that would not survive
@@ -325,7 +323,7 @@ __device__ __forceinline__ void update_advance(const UpdDesc& D, const DevParams
     // rows overflow their lists anyway, lists are pointless - every row goes to k_assoc_dense (the reference's
     // literal ordered scan), nothing is rebuilt while that lasts, and the pair returns to lists once the rows have
     // thinned out (mean nonzeros per row below 12, far from the 32 / 64 a list holds).
-    if (!INIT && P.mode == 0 && P.dense_regime) {
+    if (!INIT && P.mode == CALL_ALIGN && P.dense_regime) {
       const bool was = c_dense != 0;
       // (with long lists an overflow row costs what its candidates cost: the literal scan of everything only pays when
       // most rows are beyond even those, when the target cloud is small - 2048 targets are 32 lane steps, no bitmap, no
@@ -369,7 +367,7 @@ __device__ __forceinline__ void update_advance(const UpdDesc& D, const DevParams
       if (INIT) st->skin_scale = 1.f;
       else if (c_scan > 0 && !c_dense) st->skin_scale = fmaxf(0.5f * st->skin_scale, 1.f / 64.f);
       else st->skin_scale = fminf(1.f, 1.1f * st->skin_scale);
-      if (!INIT && P.mode == 0 && P.use_geo && radius > 0.f && P.skin_frac > 0.f && !c_dense) {
+      if (!INIT && P.mode == CALL_ALIGN && P.use_geo && radius > 0.f && P.skin_frac > 0.f && !c_dense) {
         const float rel = step_move * frcp(radius);
         s = st->skin_scale * P.skin_frac * fminf(fmaxf(1.5f * fsqrt(rel), P.skin_min), P.skin_max);
         const float s_lean = fmaxf(s, P.lean_skin * (float)P.lean_U * rel);
@@ -424,7 +422,7 @@ __device__ __forceinline__ void update_advance(const UpdDesc& D, const DevParams
   CVO_UPD_STAMP(4);
   for (int q = 0; q < 9; q++) st->Rinv[q] = Ri[q];
   for (int q = 0; q < 3; q++) st->Tinv[q] = Ti[q];
-  if (done || INIT || P.mode != 0) {  // the returned matrix (final update_tf, CvoGPU.cu:1562): only read once the pair is done
+  if (done || INIT || P.mode != CALL_ALIGN) {  // the returned matrix (final update_tf, CvoGPU.cu:1562): only read once the pair is done
     for (int i = 0; i < 3; i++) {
       for (int j = 0; j < 3; j++) st->out_T[4 * j + i] = Ri[3 * i + j];
       st->out_T[12 + i] = Ti[i];
@@ -549,7 +547,7 @@ __device__ __forceinline__ void update_body(const UpdDesc& D, const DevParams& P
                                             const unsigned* preloaded_hot, unsigned long long clk0 = 0ull, unsigned tag = 0u,
                                             bool may_adopt = false) {
   PairState* const gst = D.st;
-  const bool dry = (flags & 8) != 0;  // timing replay: compute everything, write nothing back
+  const bool dry = (flags & ITER_REPLAY) != 0;
   double* const s_c = U.c;
   unsigned long long* const s_n = U.n;
   unsigned* const s_hot = U.hot;
@@ -576,7 +574,7 @@ __device__ __forceinline__ void update_body(const UpdDesc& D, const DevParams& P
   bool spec_try = false;
   float pred = 0.f;
   unsigned long long g0 = 0ull, g1 = 0ull;
-  if (!INIT && COH && may_adopt && !dry && P.mode == 0 && P.trace_capacity == 0) {
+  if (!INIT && COH && may_adopt && !dry && P.mode == CALL_ALIGN && P.trace_capacity == 0) {
     __builtin_amdgcn_wave_barrier();  // (the staged state: LDS writes of this wave, read back below)
     pred = st->step;
     spec_try = step_is_clamp(P, pred);
@@ -608,7 +606,7 @@ __device__ __forceinline__ void update_body(const UpdDesc& D, const DevParams& P
       const int b = bl + 16 * u;
       vq[u] = b < nba ? ld_g<false>(cnt32 + ((size_t)b * 4 + c) * 2) : 0u;
     }
-    if (P.mode == 0) {
+    if (P.mode == CALL_ALIGN) {
       // four blocks (eight coherent granule loads) in flight per lane and round (64 row-block slices = one round), summed in
       // block order; a granule that does not carry this launch's tag yet has not landed: the round is read again (cvo_wave.h)
       for (int b0 = bl; b0 < nbc; b0 += 64) {
@@ -682,7 +680,7 @@ __device__ __forceinline__ void update_body(const UpdDesc& D, const DevParams& P
   CVO_UPD_STAMP(1);
   // the step of this iteration: the cubic's real roots are searched on three lanes side by side
   float step_w = 0.f;
-  if (!INIT && act && P.mode == 0) step_w = select_step<true>(s_c[0], s_c[1], s_c[2], s_c[3], P.min_step, P.max_step);
+  if (!INIT && act && P.mode == CALL_ALIGN) step_w = select_step<true>(s_c[0], s_c[1], s_c[2], s_c[3], P.min_step, P.max_step);
   CVO_UPD_STAMP(2);
   UpdOut out;
   bool adopt = false;
@@ -737,7 +735,7 @@ __global__ __launch_bounds__(64) void k_update(const PairDesc* __restrict__ desc
                                                const int* __restrict__ status, int flags) {
   if (!INIT && status[blockIdx.x] != 0) return;
   const PairDesc* __restrict__ D = descs + blockIdx.x;
-  if (!INIT && (flags & 1) && (D->st->rebuild || (D->st->n_ovf > 0 && !(flags & 32)))) return;  // lean graph: the pair is waiting (k_assoc)
+  if (!INIT && slot_waits(flags, ITER_LEAN, ITER_LEAN_DENSE, D->st)) return;
   if (INIT && threadIdx.x == 0) {  // the pair's cross-block counters start at zero
     *D->status_out = 0;   // (a slot of a batch queue: the words of its previous occupant say "finished")
     *D->status_host = 0;
