@@ -240,18 +240,37 @@ __device__ __forceinline__ void assoc_phase(const DevParams& P, const PairDesc* 
       int j2 = cnt > 1 ? j2s : 0;
       if (INSTR) tt1 = __builtin_readcyclecounter();
       float4 y1 = ldg_xyz(ysrc + j1);
-      for (int k = 0; k < cnt && A.nnz < (unsigned)K; k++) {
-        const int j = j1;
-        const float4 ycur = y1;
-        j1 = j2;
-        if (k + 1 < cnt) y1 = ldg_xyz(ysrc + j1);
-        if (k + 2 < cnt) j2 = (int)cj[(size_t)(k + 2) * N];
-        // (Tried in round 3: a first pass that only transforms and tests the distance, parking what passes in LDS, and
-        // the kernel values in a second pass over the parked entries - bit-identical, -8 % for a lone pair's resident
-        // iteration, +5 % for the 64-pair batch: most waves hold rows of one to three candidates, where the exp already
-        // runs once or twice per wave either way, and the second loop and its LDS traffic are pure overhead.)
-        const V3 ytv = transform_point(pose.Ri, pose.Ti, ycur.x, ycur.y, ycur.z);
-        visit_pair_yt<FEAT>(P, D, F, i, pos, N, r, pxe, j, make_float4(ytv.x, ytv.y, ytv.z, 0.f), A);
+      // (the next target is requested unconditionally: j1 is always a valid position - a candidate, or 0 before the
+      // list's end - so its load needs no exec-mask region of its own; past the end it re-reads the current target's line)
+      const CVO_GLOBAL IdxT* cjn = cj + (size_t)2 * N;  // list slot k + 2
+      if (geo_fast_path<FEAT>(P)) {
+        // The production case - geometric kernel on, alignment, no column export - with the uniform tests of
+        // visit_pair_yt decided once per row instead of once per candidate (same operations, same order)
+        for (int k = 0; k < cnt && A.nnz < (unsigned)K; k++) {
+          const int j = j1;
+          const float4 ycur = y1;
+          j1 = j2;
+          y1 = ldg_xyz(ysrc + j1);
+          if (k + 2 < cnt) j2 = (int)*cjn;
+          cjn += N;
+          const V3 ytv = transform_point(pose.Ri, pose.Ti, ycur.x, ycur.y, ycur.z);
+          visit_pair_geo(P, F, N, r, pxe, j, ytv, A);
+        }
+      } else {
+        for (int k = 0; k < cnt && A.nnz < (unsigned)K; k++) {
+          const int j = j1;
+          const float4 ycur = y1;
+          j1 = j2;
+          y1 = ldg_xyz(ysrc + j1);
+          if (k + 2 < cnt) j2 = (int)*cjn;
+          cjn += N;
+          // (Tried in round 3: a first pass that only transforms and tests the distance, parking what passes in LDS, and
+          // the kernel values in a second pass over the parked entries - bit-identical, -8 % for a lone pair's resident
+          // iteration, +5 % for the 64-pair batch: most waves hold rows of one to three candidates, where the exp already
+          // runs once or twice per wave either way, and the second loop and its LDS traffic are pure overhead.)
+          const V3 ytv = transform_point(pose.Ri, pose.Ti, ycur.x, ycur.y, ycur.z);
+          visit_pair_yt<FEAT>(P, D, F, i, pos, N, r, pxe, j, make_float4(ytv.x, ytv.y, ytv.z, 0.f), A);
+        }
       }
       D->nnz_row[pos] = A.nnz;
       {

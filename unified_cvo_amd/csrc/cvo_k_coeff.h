@@ -175,8 +175,9 @@ __global__ __launch_bounds__(ASSOC_THREADS, CVO_COEFF_WAVES) void k_coeff(const 
     update_speculate(D, states + pb.pair, Ph, flags | ITER_FROM_COEFF, S.u, D->call_serial);
     return;
   }
-  const int cq = pb.bx % launch_split;
-  pb.bx /= launch_split;
+  // (the launch split is a power of two, coeff_split(): a mask and a shift, not a 32-bit division)
+  const int cq = pb.bx & (launch_split - 1);
+  pb.bx >>= __builtin_ctz((unsigned)launch_split);
   // head of the row loop, from kernel-argument addresses (row_off_*): count, coordinates and the first ELL entry
   // of this block's slice - requested before the count is known, used only if it exists
   CoeffRowHead head;

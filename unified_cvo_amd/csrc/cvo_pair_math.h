@@ -213,31 +213,54 @@ constexpr int ELL_STAGE = CVO_ELL_STAGE_SLOTS;
 
 // One pair (i, j) that passed the geometric cut-off, with its transformed target: the rest of CvoGPU.cu:528-589 (kernel
 // values, a > sp_thres, ELL store) + the flow terms of 758-782.
+// A kernel value a > sp_thres: ELL entry, column export, flow terms.  GENERAL = false: the caller has established that
+// neither the column export nor A_sum is wanted (geo_fast_path).
+template <bool GENERAL>
+__device__ __forceinline__ void take_pair(const DevParams& P, const PairDesc* __restrict__ D, int pos, int N, const V3& pxe,
+                                          int j, const float4 yt, float a, RowAcc& A) {
+  // The row's first ELL_STAGE nonzeros are parked in the thread's own LDS column and leave after the loop as
+  // write-through stores (assoc_phase); only rows longer than that store from inside the loop.
+  if (A.nnz < (unsigned)ELL_STAGE)
+    A.stage[A.nnz * ASSOC_THREADS] = ell_to_vec(make_ell(a, yt.x, yt.y, yt.z, j));
+  else
+    *A.slot = make_ell(a, yt.x, yt.y, yt.z, j);
+  if (GENERAL && P.keep_columns) D->ell_j[(size_t)A.nnz * N + pos] = D->yorder[j];  // (list entries are sorted positions)
+  A.slot += N;
+  A.nnz++;
+  const V3 pye{yt.x, yt.y, yt.z};
+  const V3 cr = cross_dev(pxe, pye);
+  const float dx = pye.x - pxe.x, dy = pye.y - pxe.y, dz = pye.z - pxe.z;
+  A.o0 = __builtin_fmaf(cr.x, a, A.o0);
+  A.o1 = __builtin_fmaf(cr.y, a, A.o1);
+  A.o2 = __builtin_fmaf(cr.z, a, A.o2);
+  A.v0 = __builtin_fmaf(dx, a, A.v0);
+  A.v1 = __builtin_fmaf(dy, a, A.v1);
+  A.v2 = __builtin_fmaf(dz, a, A.v2);
+  if (GENERAL && P.mode != CALL_ALIGN) A.asum += (double)a;  // A_sum (SparseKernelMat.cu:62-68): only the single evaluations read it
+}
 template <int FEAT>
 __device__ __forceinline__ void visit_pair_yt(const DevParams& P, const PairDesc* __restrict__ D, const FeatDen& F, int i, int pos,
                                               int N, const RowData& r, const V3& pxe, int j, const float4 yt, RowAcc& A) {
   float a;
   if (!eval_pair_yt<FEAT>(P, D, F, i, r, j, yt, a)) return;
-  if (a > P.sp_thres) {
-    // The row's first ELL_STAGE nonzeros are parked in the thread's own LDS column and leave after the loop as
-    // write-through stores (assoc_phase); only rows longer than that store from inside the loop.
-    if (A.nnz < (unsigned)ELL_STAGE)
-      A.stage[A.nnz * ASSOC_THREADS] = ell_to_vec(make_ell(a, yt.x, yt.y, yt.z, j));
-    else
-      *A.slot = make_ell(a, yt.x, yt.y, yt.z, j);
-    if (P.keep_columns) D->ell_j[(size_t)A.nnz * N + pos] = D->yorder[j];  // (list entries are sorted positions)
-    A.slot += N;
-    A.nnz++;
-    const V3 pye{yt.x, yt.y, yt.z};
-    const V3 cr = cross_dev(pxe, pye);
-    const float dx = pye.x - pxe.x, dy = pye.y - pxe.y, dz = pye.z - pxe.z;
-    A.o0 = __builtin_fmaf(cr.x, a, A.o0);
-    A.o1 = __builtin_fmaf(cr.y, a, A.o1);
-    A.o2 = __builtin_fmaf(cr.z, a, A.o2);
-    A.v0 = __builtin_fmaf(dx, a, A.v0);
-    A.v1 = __builtin_fmaf(dy, a, A.v1);
-    A.v2 = __builtin_fmaf(dz, a, A.v2);
-    if (P.mode != CALL_ALIGN) A.asum += (double)a;  // A_sum (SparseKernelMat.cu:62-68): only the single evaluations read it
+  if (a > P.sp_thres) take_pair<true>(P, D, pos, N, pxe, j, yt, a, A);
+}
+// The geometry-only alignment (FEAT_GEO, use_geo on, CALL_ALIGN, no column export): the case of the headline workload.
+// Wave-uniform, decided once per row so that the candidate loop carries none of the tests visit_pair_yt makes per
+// candidate on the launch's parameters (each one an exec-mask region or a branch inside the loop).
+template <int FEAT>
+__device__ __forceinline__ bool geo_fast_path(const DevParams& P) {
+  return FEAT == FEAT_GEO && P.use_geo && !P.keep_columns && P.mode == CALL_ALIGN;
+}
+// visit_pair_yt<FEAT_GEO> under geo_fast_path: eval_pair_yt's geometric branch (a = k: the other factors are 1) and
+// take_pair, operation for operation; the two gates nest, so the loop has two exec-mask regions instead of four
+__device__ __forceinline__ void visit_pair_geo(const DevParams& P, const FeatDen& F, int N, const RowData& r, const V3& pxe,
+                                               int j, const V3 ytv, RowAcc& A) {
+  const float dx = ytv.x - r.x, dy = ytv.y - r.y, dz = ytv.z - r.z;
+  const float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+  if (d2 < r.d2_thres) {  // exp(-d2 / (2.0 * l * l)), CvoGPU.cu:552; d2 >= 0, so the exponent is <= 0
+    const float a = (float)((double)P.sigma2 * exp_ocml<true>(div_by((double)(-d2), r.den, r.rcp), F.ek));
+    if (a > P.sp_thres) take_pair<false>(P, nullptr, 0, N, pxe, j, make_float4(ytv.x, ytv.y, ytv.z, 0.f), a, A);
   }
 }
 
