@@ -46,6 +46,9 @@ int cvo_debug_list_builds(cvo_ctx* ctx, unsigned long long* builds, unsigned lon
  * lists (served by k_assoc_dense), those of them beyond a long list as well (literal scan of all targets), and whether
  * the pair ended in the dense regime (no lists at all). */
 int cvo_debug_row_classes(cvo_ctx* ctx, int pair, int* overflow_rows, int* scanned_rows, int* dense_regime);
+/* The speculative update of pair `pair` of the last align call: iterations whose scalar tail was adopted from the speculative
+ * run on the predicted step (update_speculate), and the iterations run.  0 adopted for traced calls and CVO_NO_SPECULATE. */
+int cvo_debug_speculation(cvo_ctx* ctx, int pair, int* adopted, int* iterations);
 /* Number of candidate pairs in the bitmap the last iteration used (superset of nnz). */
 int cvo_debug_last_candidates(cvo_ctx* ctx, unsigned long long* out);
 /* Runs the device's scalar restatements of the reference's host-side maths (cubic roots of poly_solver_order3,

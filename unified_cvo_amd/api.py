@@ -791,6 +791,12 @@ class CvoGPU:
         self._check(self.L.cvo_debug_row_classes(self.ctx, pair, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, bool(c.value)
 
+    def debug_speculation(self, pair=0):
+        """(iterations adopted from the speculative update, iterations run) of pair `pair` of the last align call."""
+        a, it = C.c_int(), C.c_int()
+        self._check(self.L.cvo_debug_speculation(self.ctx, pair, C.byref(a), C.byref(it)))
+        return a.value, it.value
+
     def advice(self):
         """Performance-relevant observations about the process set-up (cvo_ctx_advice): "" when there is nothing to say,
         e.g. a text about GPU_MAX_HW_QUEUES when HIP was initialised with fewer than 8 hardware queues."""

@@ -197,6 +197,14 @@ int cvo_debug_row_classes(cvo_ctx* ctx, int pair, int* overflow_rows, int* scann
   return CVO_OK;
 }
 
+int cvo_debug_speculation(cvo_ctx* ctx, int pair, int* adopted, int* iterations) {
+  if (!ctx || pair < 0 || pair >= ctx->last_pairs) return fail(ctx, CVO_E_INVALID, "cvo_debug_speculation: bad argument");
+  const PairState& st = ctx->h_states[pair];
+  if (adopted) *adopted = st.n_adopted;
+  if (iterations) *iterations = st.status ? st.iterations : st.k;  // (as cvo_align_info_t reports them)
+  return CVO_OK;
+}
+
 int cvo_debug_scan_stats(cvo_ctx* ctx, unsigned long long* tiles, int* rows_per_tile, int* targets_per_tile) {
   if (!ctx || !tiles || ctx->last_pairs < 1) return fail(ctx, CVO_E_INVALID, "cvo_debug_scan_stats: bad argument");
   HIP_TRY(ctx, hipSetDevice(ctx->device));

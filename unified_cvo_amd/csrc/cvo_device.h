@@ -80,6 +80,8 @@ struct DevParams {
                               // the elected block's bounded poll must end the pair (PairState::sync_err), not hang the device
   int debug_no_motion_bound;  // CVO_DEBUG_NO_MOTION_BOUND (tests only): the update pretends no target ever moves, so
                               // lists outlive their validity - what CVO_VERIFY_LISTS exists to catch
+  int no_speculate;  // CVO_NO_SPECULATE: k_coeff runs no speculative update (update_speculate) although the call is untraced -
+                     // the A/B of the adopted path against the computed one (tests/test_gpu_speculation.py); bit-identical
 };
 
 // Running state of one frame pair; lives in HBM, only touched by one thread of k_step.

@@ -141,7 +141,7 @@ static const char* const kOptionNames[] = {
     "SKIN", "SKIN_MAX", "LEAN_SKIN", "HORIZON_MARGIN", "SHRINK_ALIGN", "LEAN_U", "NO_LEAN", "NO_DENSE_REGIME", "FIXED_CHUNKS", "FIRST_U",
     "FIRST_CHUNKS", "STREAMS", "QUEUE_ADMIT",
     // A/B switches of the tests: every one of them leaves the results bit-identical
-    "NO_SORT", "ORDER", "NO_LONG_LISTS", "ROW_MAX", "NO_ONEHOT", "IP_CHAIN", "KEEP_COLUMNS",
+    "NO_SORT", "ORDER", "NO_LONG_LISTS", "ROW_MAX", "NO_ONEHOT", "IP_CHAIN", "KEEP_COLUMNS", "NO_SPECULATE",
     // diagnostics
     "VERBOSE", "KERNEL_CLOCK", "PHASE_TICKS", "VERIFY_LISTS", "DEBUG_NO_MOTION_BOUND", "DEBUG_DROP_PARTIAL"};
 

@@ -163,13 +163,13 @@ __global__ __launch_bounds__(ASSOC_THREADS, CVO_COEFF_WAVES) void k_coeff(const 
   if (pb.bx == nblk * launch_split) {
 #endif
     // The speculative block: everything of the update that follows the step, on the predicted step, while the row blocks
-    // work.  Not in the instrumented kernels, timing replays, traced calls (the record needs B..E) or single evaluations;
-    // a waiting pair (lean graph) has nothing to advance.
+    // work.  Not in the instrumented kernels, timing replays, traced calls (the record needs B..E), single evaluations or
+    // under CVO_NO_SPECULATE; a waiting pair (lean graph) has nothing to advance.
     if (INSTR || threadIdx.x >= 64 || (flags & ITER_REPLAY)) return;
     const PairState* __restrict__ sh = states + pb.pair;
     const int status_h = sh->status, rebuild_h = sh->rebuild, ovf_h = sh->n_ovf;
     const DevParams Ph = *Pp;
-    if (status_h != 0 || Ph.mode != CALL_ALIGN || Ph.trace_capacity != 0) return;
+    if (status_h != 0 || Ph.mode != CALL_ALIGN || Ph.trace_capacity != 0 || Ph.no_speculate) return;
     const SlotState sw{rebuild_h, ovf_h};
     if (slot_waits(flags, ITER_LEAN, ITER_LEAN_DENSE, &sw)) return;
     update_speculate(D, states + pb.pair, Ph, flags | ITER_FROM_COEFF, S.u, D->call_serial);

@@ -372,6 +372,7 @@ int setup_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo
   // the columns of the ELL entries (ell_j) are only written when somebody can ask for them afterwards
   dp.keep_columns = (mode != CALL_ALIGN || trace_cap > 0 || dp.verify_lists || params->is_exporting_association ||
                      ctx_opt(ctx, "KEEP_COLUMNS")) ? 1 : 0;
+  dp.no_speculate = ctx_opt(ctx, "NO_SPECULATE") ? 1 : 0;
   dp.trace_dense = opts ? opts->trace_dense : 0;
   dp.trace_every = opts ? opts->trace_every : 0;
   *dp_out = dp;

@@ -570,7 +570,9 @@ __device__ __forceinline__ void update_body(const UpdDesc& D, const DevParams& P
   // Speculation (update_speculate): when the previous step sat on a clamp, another block of this launch has run everything
   // that follows the step with that same step while the row blocks worked; if the step of this iteration turns out to be the
   // predicted one, its state is adopted instead of computed here - on this pair's serial chain.  The shadow's granules are
-  // requested now, next to the partials.
+  // requested now, next to the partials.  (CVO_NO_SPECULATE is read by k_coeff's speculative block alone: without its run no
+  // granule carries this launch's tag, so nothing is adopted here - testing the switch here too would cost k_coeff SGPR
+  // spills.)
   bool spec_try = false;
   float pred = 0.f;
   unsigned long long g0 = 0ull, g1 = 0ull;
