@@ -17,70 +17,83 @@ extern "C" int cvo_process_hint_hw_queues(void) {
 
 namespace {
 
-PairLayout make_layout(int N, int M, int Kmax, int trace_capacity, bool long_lists, Dims* d) {
-  const int Mpad = (int)align_up((size_t)M, 512);
-  const int nchunks = Mpad / 64;
-  const int rbw_max = (int)align_up((size_t)(nchunks + 31) / 32, 4);  // slice bits per row, enough for T = 1
-  const int nba = (N + ASSOC_THREADS - 1) / ASSOC_THREADS;
-  const int nbc = nba;  // the coefficient phase uses the association's row blocks
-  const int NG = (N + ROWS_PER_GROUP - 1) / ROWS_PER_GROUP;
-  const int NGpad = (int)align_up((size_t)NG, 64) + 64;
-  PairLayout L{};
-  // the row arrays of the per-iteration kernels first, at the fixed offsets of cvo_device.h (row_off_*)
-  const int Npad = (int)align_up((size_t)N, ROW_PAD);
-  L.cand_cnt = row_off_cand_cnt(Npad);
-  L.ip = row_off_ip(Npad);
-  L.nnz_row = row_off_nnz(Npad);
-  L.xp4 = row_off_xp4(Npad);
-  L.cand_j = row_off_cand_j(Npad);  // ASSOC_CAP16 x u16 == ASSOC_CAP32 x i32 == 128 bytes per row
-  L.ell = row_off_ell(Npad);
-  L.ell_j = align_up(L.ell + sizeof(EllEntry) * (size_t)Npad * Kmax, 256);
-  size_t off = align_up(L.ell_j + sizeof(int) * (size_t)Npad * Kmax, 256);
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
+Dims make_dims(int N, int M) {
+  Dims d{};
+  d.Mpad = (int)align_up((size_t)M, 512);
+  d.nchunks = d.Mpad / 64;
+  d.rbw_max = (int)align_up((size_t)(d.nchunks + 31) / 32, 4);  // slice bits per row, enough for T = 1
+  d.nblk_assoc = (N + ASSOC_THREADS - 1) / ASSOC_THREADS;
+  d.NG = (N + ROWS_PER_GROUP - 1) / ROWS_PER_GROUP;
+  d.NGpad = (int)align_up((size_t)d.NG, 64) + 64;
+  d.Npad = (int)align_up((size_t)N, ROW_PAD);
+  return d;
+}
+
+// THE list of the regions of one pair's workspace: points the descriptor's pointers at the slot that begins at `base` and
+// returns the slot's size.  Sizing a slot is the same walk from base 0 into a descriptor nobody uses (plan_batch).  N:
+// the call's largest source cloud, d: make_dims of the call's largest clouds; every region ends on a multiple of 256 bytes.
+size_t place_regions(PairDesc& D, uintptr_t base, int N, const Dims& d, int Kmax, int trace_capacity, bool long_lists) {
+  size_t off = 0;
+  auto at = [&](auto*& ptr, size_t offset) { ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + offset); };
+  auto take = [&](auto*& ptr, size_t count) {  // `count` elements of the pointer's own type
+    at(ptr, off);
+    off = align_up(off + sizeof(*ptr) * count, 256);
   };
-  L.ycull = take(sizeof(float4) * (size_t)Mpad);
-  L.xcull = take(sizeof(float4) * (size_t)(N + XCULL_PAD));
-  L.gbox = take(sizeof(float4) * 2 * (size_t)NGpad);
-  L.cellbox = take(sizeof(float4) * 2 * (size_t)(NGpad / 16));
-  L.sbox = take(sizeof(float4) * 2 * (size_t)nchunks);
-  L.masks = take(sizeof(unsigned long long) * ((size_t)N + 8) * nchunks);
-  L.rowbits = take(sizeof(unsigned) * (size_t)(N + 4) * rbw_max);
-  L.row_cnt = take(sizeof(int) * (size_t)N);
-  L.tile_count = take(sizeof(unsigned long long));
-  L.ovf_rows = take(sizeof(int) * (size_t)N);
-  L.ovf_bits = take(sizeof(unsigned long long) * (((size_t)N + 63) / 64 + 4));
-  L.gate = take(sizeof(int));
-  L.gate_flow = take(sizeof(int));
-  L.dense_off = take(sizeof(int) * (size_t)N);
-  L.dense_rel = take(sizeof(int) * (size_t)N);
-  L.ovf_wsum = take(sizeof(int) * (((size_t)N + 63) / 64 + 4));
-  L.word_base = take(sizeof(int) * (((size_t)N + 63) / 64 + 5));
-  L.done = take(sizeof(int));
-  L.rowperm = take(sizeof(int) * (size_t)N);
-  L.iorig = take(sizeof(int) * (size_t)N);
-  L.long_stamp = take(sizeof(unsigned long long) * (size_t)N);
-  L.long_j = long_lists ? take(sizeof(unsigned short) * (size_t)N * LONG_CAP) : 0;
-  L.rowres = take(sizeof(RowRes) * (size_t)N);
+  const size_t n = (size_t)N, words = (n + 63) / 64, nba = (size_t)d.nblk_assoc;
+  // the row arrays of the per-iteration kernels first, at the fixed offsets of cvo_device.h (row_off_*)
+  at(D.cand_cnt, row_off_cand_cnt(d.Npad));
+  at(D.ip, row_off_ip(d.Npad));
+  at(D.nnz_row, row_off_nnz(d.Npad));
+  at(D.xp4, row_off_xp4(d.Npad));
+  at(D.cand_j, row_off_cand_j(d.Npad));  // ASSOC_CAP16 x u16 == ASSOC_CAP32 x i32 == 128 bytes per row
+  off = row_off_ell(d.Npad);
+  take(D.ell, (size_t)d.Npad * Kmax);
+  take(D.ell_j, (size_t)d.Npad * Kmax);
+  take(D.ycull, (size_t)d.Mpad);
+  take(D.xcull, n + XCULL_PAD);
+  take(D.gbox, 2 * (size_t)d.NGpad);
+  take(D.cellbox, 2 * (size_t)(d.NGpad / 16));
+  take(D.sbox, 2 * (size_t)d.nchunks);
+  take(D.masks, (n + 8) * d.nchunks);
+  take(D.rowbits, (size_t)(N + 4) * d.rbw_max);
+  take(D.row_cnt, n);
+  take(D.tile_count, 1);
+  take(D.ovf_rows, n);
+  take(D.ovf_bits, words + 4);
+  take(D.gate, 1);
+  take(D.gate_flow, 1);
+  take(D.dense_off, n);
+  take(D.dense_rel, n);
+  take(D.ovf_wsum, words + 4);
+  take(D.word_base, words + 5);
+  take(D.done, 1);
+  take(D.rowperm, n);
+  take(D.iorig, n);
+  take(D.long_stamp, n);
+  if (long_lists) take(D.long_j, n * LONG_CAP);
+  take(D.rowres, n);
   // (rows x the pair's own coefficient split, coeff_split(): one slice above 4096 points, at most 32768 / rows below)
-  L.rowcoef = take(sizeof(double) * 4 * (size_t)std::max(N, 32768));
-  L.flow_part = take(sizeof(unsigned long long) * FLOW_GRANULES * (size_t)nba);
-  L.cnt_part = take(sizeof(unsigned long long) * 4 * (size_t)nba);
-  L.coef_part = take(sizeof(unsigned long long) * COEF_GRANULES * (size_t)nbc * COEFF_SPLIT_MAX);
-  L.shadow = take(sizeof(unsigned long long) * SHADOW_WORDS);
-  L.trace = take(sizeof(cvo_trace_t) * (size_t)std::max(trace_capacity, 0));
-  L.total = off;
-  d->Mpad = Mpad;
-  d->nchunks = nchunks;
-  d->rbw_max = rbw_max;
-  d->nblk_assoc = nba;
-  d->nblk_coeff = nbc;
-  d->NG = NG;
-  d->NGpad = NGpad;
-  d->Npad = Npad;
-  return L;
+  take(D.rowcoef, 4 * (size_t)std::max(N, 32768));
+  take(D.flow_part, FLOW_GRANULES * nba);
+  take(D.cnt_part, 4 * nba);
+  take(D.coef_part, COEF_GRANULES * nba * COEFF_SPLIT_MAX);  // (the coefficient phase uses the association's row blocks)
+  take(D.shadow, SHADOW_WORDS);
+  if (trace_capacity > 0) take(D.trace, (size_t)trace_capacity);
+  return off;
+}
+
+void free_control_block(cvo_ctx* c) {
+  if (c->d_ctl) (void)hipFree(c->d_ctl);
+  if (c->h_ctl) (void)hipHostFree(c->h_ctl);
+  for (int i = 0; i < 2; i++)
+    if (c->h_status[i]) (void)hipHostFree(c->h_status[i]);
+  c->d_ctl = c->h_ctl = nullptr;
+  c->d_params = nullptr;
+  c->d_descs = nullptr;
+  c->d_states = nullptr;
+  c->d_status = nullptr;
+  c->h_status[0] = c->h_status[1] = nullptr;
+  c->cap_pairs = 0;
 }
 
 void free_workspace(cvo_ctx* c) {
@@ -91,19 +104,9 @@ void free_workspace(cvo_ctx* c) {
   if (c->h_sb_res) (void)hipHostFree(c->h_sb_res);
   c->d_sb = c->d_sb_table = c->h_sb = c->h_sb_res = nullptr;
   c->sb_jobs_cap = c->sb_tiles_cap = 0;
-  if (c->d_ctl) (void)hipFree(c->d_ctl);
-  if (c->h_ctl) (void)hipHostFree(c->h_ctl);
-  for (int i = 0; i < 2; i++)
-    if (c->h_status[i]) (void)hipHostFree(c->h_status[i]);
+  free_control_block(c);
   c->arena = nullptr;
-  c->d_ctl = c->h_ctl = nullptr;
-  c->d_params = nullptr;
-  c->d_descs = nullptr;
-  c->d_states = nullptr;
-  c->d_status = nullptr;
-  c->h_status[0] = c->h_status[1] = nullptr;
   c->arena_bytes = 0;
-  c->cap_pairs = 0;
 }
 
 void drop_graphs(cvo_ctx* c) {
@@ -118,16 +121,7 @@ void drop_graphs(cvo_ctx* c) {
 
 int ensure_workspace(cvo_ctx* c, int n_pairs, size_t bytes_per_pair) {
   if (n_pairs > c->cap_pairs) {
-    if (c->d_ctl) (void)hipFree(c->d_ctl);
-    if (c->h_ctl) (void)hipHostFree(c->h_ctl);
-    for (int i = 0; i < 2; i++)
-      if (c->h_status[i]) (void)hipHostFree(c->h_status[i]);
-    c->d_ctl = c->h_ctl = nullptr;
-    c->d_params = nullptr;
-    c->d_descs = nullptr;
-    c->d_states = nullptr;
-    c->d_status = nullptr;
-    c->cap_pairs = 0;
+    free_control_block(c);
     // control block: [DevParams | status words: per sub-batch status[n_g], want[n_g] | PairDesc[n] | PairState[n]]
     c->ctl_off_status = align_up(sizeof(DevParams), 256);
     c->ctl_off_descs = align_up(c->ctl_off_status + sizeof(int) * 2 * (size_t)n_pairs, 256);
@@ -250,8 +244,8 @@ int cvo_ctx_create(int device, cvo_ctx** out) {
   if (hipSetDevice(device) != hipSuccess) return CVO_E_HIP;
   cvo_ctx* c = new cvo_ctx();
   c->device = device;
-  for (const char* name : kOptionNames)  // the ONLY place the library reads the environment
-    if (const char* v = std::getenv((std::string("CVO_") + name).c_str())) c->opt[name] = v;
+  for (const OptionSpec& o : kOptions)  // the ONLY place the library reads the environment
+    if (const char* v = std::getenv((std::string("CVO_") + o.name).c_str())) parse_option(c->opt, o, v);
   bool pooled = false;
   {
     std::lock_guard<std::mutex> lk(g_stream_pool_mutex);
@@ -376,15 +370,11 @@ void cvo_shutdown(void) {
 int cvo_ctx_set_option(cvo_ctx* ctx, const char* name, const char* value) {
   if (!ctx || !name) return CVO_E_INVALID;
   if (std::strncmp(name, "CVO_", 4) == 0) name += 4;
-  bool known = false;
-  for (const char* k : kOptionNames) known = known || std::strcmp(k, name) == 0;
-  if (!known) return fail(ctx, CVO_E_INVALID, std::string("cvo_ctx_set_option: unknown option ") + name);
+  const OptionSpec* spec = std::find_if(std::begin(kOptions), std::end(kOptions), [&](const OptionSpec& o) { return std::strcmp(o.name, name) == 0; });
+  if (spec == std::end(kOptions)) return fail(ctx, CVO_E_INVALID, std::string("cvo_ctx_set_option: unknown option ") + name);
   // (an open queue has chunks in flight on graphs that bake the switches in, and re-captures from its own copy of them)
   if (ctx->queue_open) return fail(ctx, CVO_E_INVALID, "cvo_ctx_set_option: a batch queue is open on this context (cvo_batch_close it first)");
-  if (value)
-    ctx->opt[name] = value;
-  else
-    ctx->opt.erase(name);
+  parse_option(ctx->opt, *spec, value);
   drop_graphs(ctx);  // cached graphs bake some of the switches in
   return CVO_OK;
 }

@@ -11,7 +11,7 @@ int run_single_eval(cvo_ctx* ctx, const cvo_params_t* params, const cvo_cloud* s
   const cvo_cloud* src[1] = {source};
   const cvo_cloud* tgt[1] = {target};
   const CallMode mode = kernel_inv_and_cull ? CALL_NONISO : CALL_SINGLE;
-  int rc = setup_batch(ctx, params, 1, src, tgt, Tm, nullptr, mode, ell, S, &dp, kernel_inv_and_cull);
+  int rc = setup_batch(ctx, {params, 1, src, tgt, Tm, nullptr, mode, ell, kernel_inv_and_cull, nullptr}, S, &dp);
   if (rc != CVO_OK) return rc;
   launch_init(ctx, S->geom);
   launch_rebuild(ctx, S->geom);
@@ -115,7 +115,7 @@ int run_ip_chain(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_clou
                  const float* Tms, float ell, double* out) {
   BatchSetup S;
   DevParams dp;
-  int rc = setup_batch(ctx, params, n, src, tgt, Tms, nullptr, CALL_SINGLE, ell, &S, &dp);
+  int rc = setup_batch(ctx, {params, n, src, tgt, Tms, nullptr, CALL_SINGLE, ell, nullptr, nullptr}, &S, &dp);
   if (rc != CVO_OK) return rc;
   if (S.G != 1) return fail(ctx, CVO_E_INVALID, "run_ip_chain: too many pairs for one chain");
   const LaunchGeom& g = S.geom;
@@ -198,9 +198,8 @@ struct ScoreJob {
 // occupies goes up in one copy.  That table and its staging are made by the first call that needs them.
 int score_overlap(cvo_ctx* ctx, const cvo_params_t* params, std::pmr::vector<ScoreEval>& ev) {
   hipStream_t stream = ctx->stream;
-  DevParams P = make_dev_params(ctx, *params);
-  P.mode = CALL_SINGLE;
-  bool all_hot = ctx_opt(ctx, "NO_ONEHOT") == nullptr;  // (FEAT_HOT and FEAT_ALL give the same bits: test_gpu_parity.py)
+  const DevParams P = make_dev_params(ctx, *params, CALL_SINGLE);
+  bool all_hot = !ctx->opt.no_onehot;  // (FEAT_HOT and FEAT_ALL give the same bits: test_gpu_parity.py)
   int rc, tiles_max = 0;
   size_t tiles_sum = 0;
   for (const ScoreEval& e : ev) {
@@ -292,8 +291,8 @@ int score_overlap(cvo_ctx* ctx, const cvo_params_t* params, std::pmr::vector<Sco
 // Calls the list chain evaluates whole: no geometric cut-off for k_overlap to cull by, or a context that asks for the chain
 // (CVO_IP_CHAIN; the instrumented / verifying runs are the chain's).
 bool chain_only(const cvo_ctx* ctx, const cvo_params_t* params) {
-  return !params->is_using_geometry || ctx_opt(ctx, "IP_CHAIN") != nullptr || ctx_opt(ctx, "VERIFY_LISTS") != nullptr ||
-         ctx_opt(ctx, "KERNEL_CLOCK") != nullptr || ctx_opt(ctx, "PHASE_TICKS") != nullptr;
+  const CtxOptions& o = ctx->opt;
+  return !params->is_using_geometry || o.ip_chain || o.verify_lists || o.kernel_clock || o.phase_ticks;
 }
 
 // kind: 0 inner product, 1 approximate function_angle, 2 exact function_angle.  Validates the whole call before any device

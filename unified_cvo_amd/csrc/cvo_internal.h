@@ -1,12 +1,13 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
 // cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
-// pair, graph keys, option lookup and the error helpers.  Included once, by cvo_hip.hip.
+// pair, graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -24,6 +25,8 @@
 #include "cvo_kernels.h"
 
 using namespace cvo_dev;
+
+#include "cvo_options.h"
 
 #define CVO_VERSION_STRING "unified_cvo_amd 0.1 (gfx950)"
 
@@ -54,11 +57,6 @@ struct cvo_cloud {
 };
 
 namespace {
-
-struct PairLayout {  // byte offsets of one pair's workspace inside the arena
-  size_t ycull, xcull, gbox, cellbox, sbox, masks, rowbits, row_cnt, tile_count, ovf_rows, ovf_bits, gate, gate_flow, dense_off, dense_rel, ovf_wsum, word_base, done, cand_cnt, rowperm, iorig, long_j, long_stamp, xp4, ip, cand_j, rowres, rowcoef, ell, ell_j, nnz_row, flow_part, cnt_part,
-      coef_part, shadow, trace, total;
-};
 
 // The chunk a sub-batch runs next (launch_chunk; chosen by choose_chunk, cvo_sched.hip).  Full: a rebuild opportunity and
 // k_assoc_dense in every iteration; full without dense: the same minus k_assoc_dense; lean / short lean: a rebuild
@@ -97,12 +95,12 @@ struct GraphKey {
   bool operator==(const GraphKey& o) const { return fields() == o.fields(); }
 };
 
-// Sizes a workspace is laid out for (make_layout)
+// Sizes a workspace is laid out for (make_dims)
 struct Dims {
-  int Mpad, nchunks, rbw_max, nblk_assoc, nblk_coeff, NG, NGpad, Npad;
+  int Mpad, nchunks, rbw_max, nblk_assoc, NG, NGpad, Npad;
 };
 
-// What the launches of a sub-batch are (setup_batch, group_geom)
+// What the launches of a sub-batch are (plan_batch, group_geom)
 struct LaunchGeom {
   int n_pairs, p0, T, gx, gy, nba, npb, csplit;
   int nbl, nbv;  // blocks of k_list (LIST_THREADS rows each) and k_verify (grid x) for the largest source cloud
@@ -115,12 +113,12 @@ struct LaunchGeom {
   ArenaArg arena;  // of pair p0
 };
 
-// A call's sizes, workspace layout and launch geometry (setup_batch); N / M: its largest source / target cloud
+// A call's sizes, workspace layout and launch geometry (plan_batch); N / M: its largest source / target cloud
 struct BatchSetup {
-  int N, M, T, gpb, gx, gy, G;
+  int N, M, G;
   bool long_lists = false;
   Dims d;
-  PairLayout L;
+  size_t slot_bytes;  // one pair's workspace (place_regions): pair p's begins at arena + p * slot_bytes
   LaunchGeom geom;
 };
 
@@ -133,21 +131,9 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
-// Tuning / diagnostic switches of a context (none changes a result).  Read from the environment ONCE, when the context
-// is created (CVO_<NAME>), and settable afterwards with cvo_ctx_set_option: no library call reads the process
-// environment while it runs.
-static const char* const kOptionNames[] = {
-    // list reuse / graphs (scripts/skin_sweep.py, early_sweep.py, first_chunk_sweep.sh)
-    "SKIN", "SKIN_MAX", "LEAN_SKIN", "HORIZON_MARGIN", "SHRINK_ALIGN", "LEAN_U", "NO_LEAN", "NO_DENSE_REGIME", "FIXED_CHUNKS", "FIRST_U",
-    "FIRST_CHUNKS", "STREAMS", "QUEUE_ADMIT",
-    // A/B switches of the tests: every one of them leaves the results bit-identical
-    "NO_SORT", "ORDER", "NO_LONG_LISTS", "ROW_MAX", "NO_ONEHOT", "IP_CHAIN", "KEEP_COLUMNS", "NO_SPECULATE",
-    // diagnostics
-    "VERBOSE", "KERNEL_CLOCK", "PHASE_TICKS", "VERIFY_LISTS", "DEBUG_NO_MOTION_BOUND", "DEBUG_DROP_PARTIAL"};
-
 struct cvo_ctx {
   int device = 0;
-  std::map<std::string, std::string> opt;  // see kOptionNames
+  CtxOptions opt;                          // the switches (cvo_options.h)
   std::mutex upload_mutex;                 // cvo_cloud_upload / _aos192 share upload_stream and the error string
   std::mutex kd_mutex;                     // the ordering launches of concurrent uploads share upload_stream and d_kd_jobs
   KdJob* d_kd_jobs = nullptr;              // job descriptors of the running k_kd_order launch
@@ -182,12 +168,13 @@ struct cvo_ctx {
   int sb_jobs_cap = 0, sb_tiles_cap = 0;
   int last_score_overlap = 0, last_score_chain = 0, last_score_launches = 0;  // cvo_debug_last_score_batch
   int* h_status[2] = {nullptr, nullptr};  // pinned; [0]: the live host mirror of the status / want words the device writes
-                                          // (PairDesc::status_host / want_host), [1]: unused slot kept for the layout
+                                          // (PairDesc::status_host / want_host), [1]: a double per pair, the sum a single
+                                          // evaluation leaves for the host (PairDesc::asum_host, read by score_batch)
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   // A batch is split into up to MAX_GROUPS sub-batches, each enqueued on its own stream: the pairs are
   // independent, so one group's latency-bound kernels (k_update: one wave per pair) and launch tails
   // overlap the other groups' wide kernels.  Group 0 runs on `stream`.
-  static constexpr int MAX_GROUPS = 8;
+  static constexpr int MAX_GROUPS = MAX_STREAMS;
   hipStream_t gstream[MAX_GROUPS] = {};
   hipEvent_t ev_chk[2][MAX_GROUPS] = {};
   hipEvent_t ev_fork = nullptr, ev_join[MAX_GROUPS] = {};
@@ -198,7 +185,7 @@ struct cvo_ctx {
   CachedGraph graphs[MAX_GROUPS][GRAPH_SLOTS];
   CachedGraph chain_graph;
   int last_chunks = 0, last_lean_launches = 0, last_full_launches = 0;
-  // The last call, as setup_batch made it (debug hooks, exports, the IRLS readers): its pairs (0 = no workspace of the
+  // The last call, as commit_batch made it (debug hooks, exports, the IRLS readers): its pairs (0 = no workspace of the
   // last call can be read), setup, parameters and pair 0's source order (sorted row -> original row)
   int last_pairs = 0;
   BatchSetup last{};
@@ -210,17 +197,6 @@ struct cvo_ctx {
 };
 
 namespace {
-
-// value of option NAME (without the CVO_ prefix) or nullptr when it is not set
-const char* ctx_opt(const cvo_ctx* ctx, const char* name) {
-  if (!ctx) return nullptr;
-  auto it = ctx->opt.find(name);
-  return it == ctx->opt.end() ? nullptr : it->second.c_str();
-}
-bool ctx_opt_on(const cvo_ctx* ctx, const char* name) {  // set, and not to "0"
-  const char* v = ctx_opt(ctx, name);
-  return v && atoi(v) != 0;
-}
 
 int fail(cvo_ctx* ctx, int code, const std::string& msg) {
   if (ctx) ctx->err = msg;

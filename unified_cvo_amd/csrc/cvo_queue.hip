@@ -143,9 +143,7 @@ int queue_step(cvo_batch_queue* q, int g, bool block, bool* progressed) {
     // otherwise when a quarter of its slots have come free.
     if (!q->waiting.empty() && q->running[g] < ng) {
       const bool fast = queue_fast(q->next[g]);
-      int den = 4;  // (QUEUE_ADMIT: the share of free slots - 1 / den - at which a settled sub-batch takes newcomers)
-      if (const char* e = ctx_opt(ctx, "QUEUE_ADMIT")) den = std::max(1, atoi(e));
-      if (fast || q->running[g] == 0 || den * (ng - q->running[g]) >= ng)
+      if (fast || q->running[g] == 0 || ctx->opt.queue_admit * (ng - q->running[g]) >= ng)
         for (int k = 0; k < ng && !q->waiting.empty(); k++)
           if (q->slot[p0 + k].ticket < 0) {
             const cvo_batch_queue::Job job = q->waiting.front();
@@ -194,7 +192,7 @@ int cvo_batch_open(cvo_ctx* ctx, const cvo_params_t* params, int slots, int max_
   if (opts) q->opts.max_iterations = opts->max_iterations;
   q->slots = slots;
   const QueueDims qd{max_source_points, max_target_points, min_source_points > 0 ? min_source_points : max_source_points};
-  int rc = setup_batch(ctx, params, slots, nullptr, nullptr, nullptr, &q->opts, CALL_ALIGN, 0.f, &q->S, &q->dp, nullptr, &qd);
+  int rc = setup_batch(ctx, {params, slots, nullptr, nullptr, nullptr, &q->opts, CALL_ALIGN, 0.f, nullptr, &qd}, &q->S, &q->dp);
   if (rc != CVO_OK) {
     delete q;
     return rc;

@@ -1,10 +1,34 @@
-// cvo_sched.hip -- the optimiser loop on the host: parameters -> DevParams, descriptors and initial states of a batch (setup_batch), the eight chunk graphs of a sub-batch and which one runs next, cvo_align_batch / cvo_align_ex / cvo_align.
+// cvo_sched.hip -- the optimiser loop on the host: parameters -> DevParams, the plan of a call and its descriptors and initial states (setup_batch = check_call, plan_batch, commit_batch), the eight chunk graphs of a sub-batch and which one runs next, cvo_align_batch / cvo_align_ex / cvo_align.
 // A SECTION of the one translation unit cvo_hip.hip (which includes the sections in dependency order and says why it is one
 // unit); not compiled on its own.  Shared declarations: cvo_internal.h.
 namespace {
 
-DevParams make_dev_params(const cvo_ctx* ctx, const cvo_params_t& p) {
+// Sizes of a batch queue (cvo_batch_open): the slots of the workspace are laid out for clouds of up to n_max / m_max points
+// and the launches for source clouds of at least n_min (the coefficient split of a pair follows from its own size).
+struct QueueDims {
+  int n_max, m_max, n_min;
+};
+
+// A call as setup_batch and its steps see it (qd: the sizes of a batch queue, whose slots have no occupants yet)
+struct BatchCall {
+  const cvo_params_t* params;
+  int n_pairs;
+  const cvo_cloud *const *sources, *const *targets;
+  const float* init_T;
+  const cvo_align_opts_t* opts;
+  CallMode mode;
+  float mode_ell;
+  const float* kernel_inv_and_cull;  // CALL_NONISO: 9 floats of the inverse kernel matrix (row-major) + the squared cull radius
+  const QueueDims* qd;
+};
+
+// The parameter block of a launch: the reference's parameters, the context's switches and - for everything but a k_overlap
+// launch (score_overlap), which reads the kernel parameters alone - what the call `c` and its plan so far (S: sizes, long
+// lists, sub-batches) decide, the scan geometry among it.
+DevParams make_dev_params(const cvo_ctx* ctx, const cvo_params_t& p, CallMode mode, const BatchCall* c = nullptr, const BatchSetup* S = nullptr) {
+  const CtxOptions& o = ctx->opt;
   DevParams d{};
+  d.mode = mode;
   d.sp_thres = p.sp_thres;
   d.sigma2 = p.sigma * p.sigma;
   d.c2 = p.c_ell * p.c_ell;
@@ -41,37 +65,61 @@ DevParams make_dev_params(const cvo_ctx* ctx, const cvo_params_t& p) {
     auto mid = [](float v) { const float a = std::fabs(v); return std::isfinite(v) && a >= 0x1p-20f && a <= 0x1p20f; };
     d.fast_div_cd = mid(p.c) && mid(p.d) ? 1 : 0;
   }
-  // List-reuse knobs, re-tuned in round 4 (scripts/skin_sweep.py, profiles/r4/skin_sweep.txt): the linear "outlives the
-  // next h iterations at the current speed" predictions are pessimistic once the pose jitters around its optimum (the
-  // allowance used since a build stays at a few percent while every iteration moves ~10 % of it), so thinner skins and
-  // a smaller margin win on every configuration: headline batch 62.05 -> 60.6 ms, config 3 single pair 21.5 -> 18.8 us
-  // per iteration.  (Round-2 values: 2.0 / 1.3 / 1.25.)
-  d.skin_frac = 1.0f;
-  d.lean_skin = 0.5f;
-  d.dense_regime = ctx_opt(ctx, "NO_DENSE_REGIME") ? 0 : 1;
+  // the list-reuse policy (defaults and their measurements: CtxOptions)
+  d.skin_frac = o.skin;
+  d.lean_skin = o.lean_skin;
+  d.dense_regime = o.no_dense_regime ? 0 : 1;
   d.skin_blend = 0.25f;
-  d.skin_min = 0.05f;
-  d.skin_max = 0.35f;  // (0.25 until round 6; re-swept on the un-aligned shrink rebuilds: 0.25 / 0.3 / 0.35 / 0.4 / 0.5 -> 55.55 / 55.22 / 55.06 / 55.19 /
-                       // 55.25 ms for the 64-pair step, 16 pairs -1.3 %, config 3 batch +0.3 %, single pairs unchanged: profiles/r6/shrink_align.txt)
-  if (const char* e = ctx_opt(ctx, "SKIN_MAX")) d.skin_max = std::max(d.skin_min, (float)atof(e));
-  if (const char* e = ctx_opt(ctx, "LEAN_SKIN")) d.lean_skin = std::max(0.1f, (float)atof(e));
-  d.horizon_margin = 0.3f;
-  if (const char* e = ctx_opt(ctx, "HORIZON_MARGIN")) d.horizon_margin = std::max(0.f, (float)atof(e));
+  d.skin_min = SKIN_MIN;
+  d.skin_max = o.skin_max;
+  d.horizon_margin = o.horizon_margin;
 #ifndef CVO_REBUILD_SHRINK
 #define CVO_REBUILD_SHRINK 0.9f
 #endif
   d.rebuild_shrink = CVO_REBUILD_SHRINK;
-  if (const char* e = ctx_opt(ctx, "SKIN")) d.skin_frac = std::max(0.f, (float)atof(e));
-  d.phase_ticks = ctx_opt(ctx, "PHASE_TICKS") ? 1 : 0;
-  d.kernel_clock = ctx_opt_on(ctx, "KERNEL_CLOCK") ? 1 : 0;
-  d.verify_lists = ctx_opt_on(ctx, "VERIFY_LISTS") ? 1 : 0;
-  d.debug_no_motion_bound = ctx_opt(ctx, "DEBUG_NO_MOTION_BOUND") ? 1 : 0;
-  d.debug_drop_partial = ctx_opt(ctx, "DEBUG_DROP_PARTIAL") ? atoi(ctx_opt(ctx, "DEBUG_DROP_PARTIAL")) : 0;
+  d.phase_ticks = o.phase_ticks;
+  d.kernel_clock = o.kernel_clock;
+  d.verify_lists = o.verify_lists;
+  d.debug_no_motion_bound = o.debug_no_motion_bound;
+  d.debug_drop_partial = o.debug_drop_partial;
+  if (!c) return d;
+
+  const cvo_align_opts_t* opts = c->opts;
+  const int trace_cap = (opts && opts->trace) ? opts->trace_capacity : 0;
+  if (mode == CALL_NONISO) {  // non-isotropic kernel
+    for (int q = 0; q < 9; q++) d.kinv[q] = c->kernel_inv_and_cull[q];
+    d.d2_cull = c->kernel_inv_and_cull[9];
+    d.s_ell_sq = p.s_ell * p.s_ell;
+    d.use_geotype = 0;  // CvoGPU.cu:1950-1951
+    // that kernel's prologue keeps s_ell^2 in float (CvoGPU.cu:236, 252)
+    if (p.is_using_semantics) d.d2_s_thres = (float)(-2.0 * d.s_ell_sq * (double)std::log(p.sp_thres / s_sigma2));
+  }
+  choose_scan_config(ctx, (c->n_pairs + S->G - 1) / S->G, S->d.NG, S->d.Mpad, &d.T, &d.groups_per_block);  // for one sub-batch's launch
+  d.long_lists = S->long_lists ? 1 : 0;
+  d.row_max_cap = o.row_max;
+  // (clustered 10k scenes, scripts/scene_batch.py: 8 for a lone pair; 24 against 64 wins 9 % at 8 pairs in flight, nothing at
+  // 16, and LOSES 5 % at 32 and 10 % at 64 - a chip full of pairs wants its rows in the thread-per-row kernel, whose lanes
+  // are all rows, not in steps of 128 candidate slots per row)
+  d.row_max_busy = c->n_pairs <= 4 ? 8 : (c->n_pairs <= 16 ? 24 : (int)ASSOC_CAP16);
+  d.lean_U = o.lean_U;
+  // Calm pairs (see PairState::want_full).  In the end game the pose jitters around its optimum: the motion PER ITERATION
+  // stays at ~10 % of a list's allowance while the allowance used SINCE THE BUILD stays below 5 % for hundreds of
+  // iterations (CVO_VERBOSE=2 prints both), so a linear "outlives the next 64 iterations" test never fires.  Four
+  // iterations of linear margin it is: 62.3 -> 61.4 ms per headline step, single pairs -1.5 ... -2.5 %, no additional waits.
+  d.calm_U = 4;
+  d.lean_U2 = 2;
+  if (d.lean_U2 >= d.lean_U) d.lean_U2 = 0;
+  d.shrink_align = o.shrink_align;
+  if (opts && opts->max_iterations > 0) d.max_iter = std::min(d.max_iter, opts->max_iterations);
+  if (opts && opts->kernel_clock) d.kernel_clock = 1;
+  d.trace_capacity = trace_cap;
+  // the columns of the ELL entries (ell_j) are only written when somebody can ask for them afterwards
+  d.keep_columns = (mode != CALL_ALIGN || trace_cap > 0 || d.verify_lists || p.is_exporting_association || o.keep_columns) ? 1 : 0;
+  d.no_speculate = o.no_speculate;
+  d.trace_dense = opts ? opts->trace_dense : 0;
+  d.trace_every = opts ? opts->trace_every : 0;
   return d;
 }
-
-// Scan geometry: T chunks of 64 sorted targets per wave (smaller slices cull better, larger ones
-// amortise the row operands) and the number of row groups per block, chosen so that a launch has a
 
 // Sub-batches (see cvo_ctx) are contiguous blocks of pairs: sub-batch g of G holds pairs [p0, p1) of n
 struct GroupRange {
@@ -84,121 +132,77 @@ inline int group_of(int n, int G, int p) {
   return g;
 }
 
-// Sizes of a batch queue (cvo_batch_open): the slots of the workspace are laid out for clouds of up to n_max / m_max points
-// and the launches for source clouds of at least n_min (the coefficient split of a pair follows from its own size).
-struct QueueDims {
-  int n_max, m_max, n_min;
-};
-
 // Descriptor + initial state of the pair that occupies slot p of the workspace (host copies; the caller uploads them).
 void fill_pair(cvo_ctx* ctx, const BatchSetup* S, const cvo_params_t* params, const cvo_align_opts_t* opts, CallMode mode, float mode_ell,
                int n_slots, int p, const cvo_cloud* X, const cvo_cloud* Y, const float* Tm, unsigned long long serial, int max_iter) {
   const int trace_cap = (opts && opts->trace) ? opts->trace_capacity : 0;
   const int Kmax = params->nearest_neighbors_max;
+  PairDesc& D = ctx->h_descs[p];
+  std::memset(&D, 0, sizeof(D));
+  place_regions(D, (uintptr_t)ctx->arena + S->slot_bytes * (size_t)p, S->N, S->d, Kmax, trace_cap, S->long_lists);
+  D.N = X->n;
+  D.M = Y->n;
+  D.call_serial = serial;
+  D.max_iter = max_iter;
+  // paddings are derived from the batch maxima so every pair shares one launch geometry
+  D.Mpad = S->d.Mpad;
+  D.nchunks = S->d.nchunks;
+  D.nslices = S->d.Mpad / (64 * S->geom.T);
+  D.rbw = (int)align_up((size_t)(S->d.Mpad / (64 * S->geom.T) + 31) / 32, 4);
+  D.nblk_assoc = S->d.nblk_assoc;
+  // coefficient phase: small clouds get several blocks per row block (see coeff_rows); a function of the pair's own
+  // size only, so that a pair is reduced in the same order whether it is solved alone or inside a batch
+  D.csplit = coeff_split(X->n);
+  D.nblk_coeff = S->d.nblk_assoc * D.csplit;
+  D.NG = (X->n + ROWS_PER_GROUP - 1) / ROWS_PER_GROUP;
+  D.NGpad = S->d.NGpad;
+  D.ymax = Y->rmax;
+  D.sqrt_nm = std::sqrt((double)X->n * (double)Y->n);
+  D.cx = X->cx;
+  D.cy = X->cy;
+  D.cz = X->cz;
+  D.x4 = X->x4;
+  D.xs4 = X->xs4;
+  D.xfeat = X->feat;
+  D.xlabel = X->label;
+  D.xgeo = X->geo;
+  D.xorder = X->order;
+  D.y4 = Y->x4;
+  D.ys4 = Y->xs4;
+  D.yfeat = Y->feat;
+  D.ylabel = Y->label;
+  D.ygeo = Y->geo;
+  D.xlid = X->lid;
+  D.ylid = Y->lid;
+  D.yorder = Y->order;
+  D.yinv = Y->inv;
+  D.st = ctx->d_states + p;
   {
-    char* base = ctx->arena + S->L.total * (size_t)p;
-    PairDesc& D = ctx->h_descs[p];
-    std::memset(&D, 0, sizeof(D));
-    D.N = X->n;
-    D.M = Y->n;
-    D.call_serial = serial;
-    D.max_iter = max_iter;
-    // paddings are derived from the batch maxima so every pair shares one launch geometry
-    D.Mpad = S->d.Mpad;
-    D.nchunks = S->d.nchunks;
-    D.nslices = S->d.Mpad / (64 * S->T);
-    D.rbw = (int)align_up((size_t)(S->d.Mpad / (64 * S->T) + 31) / 32, 4);
-    D.nblk_assoc = S->d.nblk_assoc;
-    // coefficient phase: small clouds get several blocks per row block (see coeff_rows); a function of the pair's own
-    // size only, so that a pair is reduced in the same order whether it is solved alone or inside a batch
-    D.csplit = coeff_split(X->n);
-    D.nblk_coeff = S->d.nblk_assoc * D.csplit;
-    D.NG = (X->n + ROWS_PER_GROUP - 1) / ROWS_PER_GROUP;
-    D.NGpad = S->d.NGpad;
-    D.ymax = Y->rmax;
-    D.sqrt_nm = std::sqrt((double)X->n * (double)Y->n);
-    D.cx = X->cx;
-    D.cy = X->cy;
-    D.cz = X->cz;
-    D.x4 = X->x4;
-    D.xs4 = X->xs4;
-    D.xfeat = X->feat;
-    D.xlabel = X->label;
-    D.xgeo = X->geo;
-    D.xorder = X->order;
-    D.y4 = Y->x4;
-    D.ys4 = Y->xs4;
-    D.yfeat = Y->feat;
-    D.ylabel = Y->label;
-    D.ygeo = Y->geo;
-    D.xlid = X->lid;
-    D.ylid = Y->lid;
-    D.yorder = Y->order;
-    D.yinv = Y->inv;
-    D.ycull = (float4*)(base + S->L.ycull);
-    D.xcull = (float4*)(base + S->L.xcull);
-    D.gbox = (float4*)(base + S->L.gbox);
-    D.cellbox = (float4*)(base + S->L.cellbox);
-    D.sbox = (float4*)(base + S->L.sbox);
-    D.masks = (unsigned long long*)(base + S->L.masks);
-    D.rowbits = (unsigned*)(base + S->L.rowbits);
-    D.row_cnt = (int*)(base + S->L.row_cnt);
-    D.tile_count = (unsigned long long*)(base + S->L.tile_count);
-    D.ovf_rows = (int*)(base + S->L.ovf_rows);
-    D.ovf_bits = (unsigned long long*)(base + S->L.ovf_bits);
-    D.cand_cnt = (int*)(base + S->L.cand_cnt);
-    D.rowperm = (int*)(base + S->L.rowperm);
-    D.xp4 = (float4*)(base + S->L.xp4);
-    D.ip = (int*)(base + S->L.ip);
-    D.iorig = (int*)(base + S->L.iorig);
-    D.long_j = S->long_lists ? (unsigned short*)(base + S->L.long_j) : nullptr;
-    D.long_stamp = (unsigned long long*)(base + S->L.long_stamp);
-    D.cand_j = (void*)(base + S->L.cand_j);
-    D.ell = (EllEntry*)(base + S->L.ell);
-    D.ell_j = (int*)(base + S->L.ell_j);
-    D.nnz_row = (unsigned*)(base + S->L.nnz_row);
-    D.rowres = (RowRes*)(base + S->L.rowres);
-    D.rowcoef = (double*)(base + S->L.rowcoef);
-    D.flow_part = (unsigned long long*)(base + S->L.flow_part);
-    D.cnt_part = (unsigned long long*)(base + S->L.cnt_part);
-    D.coef_part = (unsigned long long*)(base + S->L.coef_part);
-    D.shadow = (unsigned long long*)(base + S->L.shadow);
-    D.st = ctx->d_states + p;
-    D.trace = trace_cap > 0 ? (cvo_trace_t*)(base + S->L.trace) : nullptr;
-    {
-      // status / requested-graph mirrors the host polls: every sub-batch owns ONE contiguous block [status[n_g] | want[n_g]]
-      // at 2 * p0(g), fetched with one copy per chunk (two copies per chunk and stream were two 5 us blits)
-      const auto [p0, p1] = group_bounds(n_slots, S->G, group_of(n_slots, S->G, p));
-      D.status_out = ctx->d_status + 2 * p0 + (p - p0);
-      D.want_out = ctx->d_status + 2 * p0 + (p1 - p0) + (p - p0);
-      D.status_host = ctx->h_status[0] + 2 * p0 + (p - p0);
-      D.want_host = ctx->h_status[0] + 2 * p0 + (p1 - p0) + (p - p0);
-    }
-    D.asum_host = reinterpret_cast<double*>(ctx->h_status[1]) + p;  // (2 ints per pair = one double)
-    D.gate = (int*)(base + S->L.gate);
-    D.gate_flow = (int*)(base + S->L.gate_flow);
-    D.dense_off = (int*)(base + S->L.dense_off);
-    D.dense_rel = (int*)(base + S->L.dense_rel);
-    D.ovf_wsum = (int*)(base + S->L.ovf_wsum);
-    D.word_base = (int*)(base + S->L.word_base);
-    D.done = (int*)(base + S->L.done);
-
-    PairState& st = ctx->h_states[p];
-    std::memset(&st, 0, sizeof(st));
-    for (int i = 0; i < 3; i++) {
-      for (int j = 0; j < 3; j++) st.R[3 * i + j] = Tm[4 * j + i];  // CvoGPU.cu:1363-1364
-      st.T[i] = Tm[12 + i];
-    }
-    st.ell = mode == CALL_ALIGN ? params->ell_init : mode_ell;  // CvoState.cu:30
-    st.K = Kmax;                                        // CvoGPU.cu:1385
-    if (mode == CALL_ALIGN && opts && opts->override_state) {  // (validated by the caller)
-      st.ell = opts->ell0;
-      st.K = opts->K0;
-    }
-    st.K_last = 0;  // set by the update of every EXECUTED iteration: > 0 <=> at least one association pass ran
-    // (the pair's counters - gate, gate_flow, done, tile_count - are zeroed by k_update<INIT>; the slice bits of a row
-    // are cleared by k_prep before every build, the first one included: five memsets per pair used to cost 10 us each call)
+    // status / requested-graph mirrors the host polls: every sub-batch owns ONE contiguous block [status[n_g] | want[n_g]]
+    // at 2 * p0(g), fetched with one copy per chunk (two copies per chunk and stream were two 5 us blits)
+    const auto [p0, p1] = group_bounds(n_slots, S->G, group_of(n_slots, S->G, p));
+    D.status_out = ctx->d_status + 2 * p0 + (p - p0);
+    D.want_out = ctx->d_status + 2 * p0 + (p1 - p0) + (p - p0);
+    D.status_host = ctx->h_status[0] + 2 * p0 + (p - p0);
+    D.want_host = ctx->h_status[0] + 2 * p0 + (p1 - p0) + (p - p0);
   }
+  D.asum_host = reinterpret_cast<double*>(ctx->h_status[1]) + p;  // (2 ints per pair = one double)
+
+  PairState& st = ctx->h_states[p];
+  std::memset(&st, 0, sizeof(st));
+  for (int i = 0; i < 3; i++) {
+    for (int j = 0; j < 3; j++) st.R[3 * i + j] = Tm[4 * j + i];  // CvoGPU.cu:1363-1364
+    st.T[i] = Tm[12 + i];
+  }
+  st.ell = mode == CALL_ALIGN ? params->ell_init : mode_ell;  // CvoState.cu:30
+  st.K = Kmax;                                        // CvoGPU.cu:1385
+  if (mode == CALL_ALIGN && opts && opts->override_state) {  // (validated by the caller)
+    st.ell = opts->ell0;
+    st.K = opts->K0;
+  }
+  st.K_last = 0;  // set by the update of every EXECUTED iteration: > 0 <=> at least one association pass ran
+  // (the pair's counters - gate, gate_flow, done, tile_count - are zeroed by k_update<INIT>; the slice bits of a row
+  // are cleared by k_prep before every build, the first one included: five memsets per pair used to cost 10 us each call)
 }
 
 unsigned long long next_call_serial() {
@@ -206,8 +210,6 @@ unsigned long long next_call_serial() {
   return g_call_serial.fetch_add(1);
 }
 
-// Builds descriptors + initial states for a batch and uploads them.  qd != nullptr: plans the workspace of a batch queue
-// (cvo_batch_open) for n_pairs SLOTS without occupants - every slot starts out finished, cvo_batch_submit fills them.
 // What every entry point checks before it touches the device: the arguments of the call, the parameter and coordinate
 // ranges the kernels' arithmetic is stated for, the attribute arrays the call's kernels will read.  N / M: the largest
 // source / target cloud of the call.
@@ -270,39 +272,38 @@ int check_call(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo_
   return CVO_OK;
 }
 
-int setup_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo_cloud* const* sources,
-                const cvo_cloud* const* targets, const float* init_T, const cvo_align_opts_t* opts, CallMode mode,
-                float mode_ell, BatchSetup* S, DevParams* dp_out, const float* kernel_inv_and_cull = nullptr,
-                const QueueDims* qd = nullptr) {
-  int N = 0, M = 0;
-  {
-    const int rc0 = check_call(ctx, params, n_pairs, sources, targets, opts, mode, mode_ell, qd, &N, &M);
-    if (rc0 != CVO_OK) return rc0;
-  }
-  const int trace_cap = (opts && opts->trace) ? opts->trace_capacity : 0;
-  const int Kmax = params->nearest_neighbors_max;
+// Plans a checked call over clouds of up to N x M points: sizes, the slot of a pair (without the long lists when device
+// memory is short), sub-batches, scan geometry, the parameter block and the launch geometry.  Changes nothing but *S and
+// *dp and asks the device for nothing but its free memory; refuses what no workspace could hold.
+int plan_batch(cvo_ctx* ctx, const BatchCall& c, int N, int M, BatchSetup* S, DevParams* dp) {
+  const CtxOptions& o = ctx->opt;
+  const int n_pairs = c.n_pairs;
+  const int trace_cap = (c.opts && c.opts->trace) ? c.opts->trace_capacity : 0;
+  const int Kmax = c.params->nearest_neighbors_max;
   S->N = N;
   S->M = M;
   // k_list packs a row's candidate count next to an 8-bit row number; the candidate bitmap of a pair takes
   // N * M / 8 bytes (DESIGN.md "Data layout"), every pair of a batch sized by the batch maxima
   if (M >= (1 << 23)) return fail(ctx, CVO_E_INVALID, "target clouds are limited to 8388607 points");
   // (the update reduces an iteration's nonzero count in 32 bits: rows x nearest_neighbors_max must fit)
-  if ((unsigned long long)N * (unsigned long long)std::max(params->nearest_neighbors_max, 1) >= (1ull << 32))
+  if ((unsigned long long)N * (unsigned long long)std::max(Kmax, 1) >= (1ull << 32))
     return fail(ctx, CVO_E_INVALID, "source rows x nearest_neighbors_max must stay below 2^32");
+  S->d = make_dims(N, M);
   // overflow rows keep sorted candidate lists of their own (PairDesc::long_j) when sorted positions fit 16 bits
-  S->long_lists = M <= 65535 && ctx_opt(ctx, "NO_LONG_LISTS") == nullptr;
-  S->L = make_layout(N, M, Kmax, trace_cap, S->long_lists, &S->d);
+  S->long_lists = M <= 65535 && !o.no_long_lists;
+  auto slot_bytes = [&](bool long_lists) { PairDesc unused{}; return place_regions(unused, 0, N, S->d, Kmax, trace_cap, long_lists); };
+  S->slot_bytes = slot_bytes(S->long_lists);
   {
     size_t free_b = 0, total_b = 0;
-    size_t need = S->L.total * (size_t)n_pairs;
+    size_t need = S->slot_bytes * (size_t)n_pairs;
     const bool tight = need > ctx->arena_bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + ctx->arena_bytes;
     if (tight && S->long_lists) {
       // the long lists of overflow rows (N x 2 KB per pair) are a speed feature: without them such rows are scanned
       // literally.  Give them up before giving up the call.
       S->long_lists = false;
-      S->L = make_layout(N, M, Kmax, trace_cap, false, &S->d);
-      need = S->L.total * (size_t)n_pairs;
-      if (ctx_opt(ctx, "VERBOSE")) fprintf(stderr, "[cvo] workspace: long lists dropped to fit device memory\n");
+      S->slot_bytes = slot_bytes(false);
+      need = S->slot_bytes * (size_t)n_pairs;
+      if (o.verbose) fprintf(stderr, "[cvo] workspace: long lists dropped to fit device memory\n");
     }
     if (need > ctx->arena_bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + ctx->arena_bytes) {
       char msg[320];
@@ -315,74 +316,62 @@ int setup_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo
       return fail(ctx, CVO_E_NOMEM, msg);
     }
   }
-  // sub-batches on separate streams (see cvo_ctx): the scan geometry is chosen for one group's launch
-  S->G = n_pairs >= 32 ? 4 : (n_pairs >= 8 ? 2 : 1);
-  if (const char* e = ctx_opt(ctx, "STREAMS")) S->G = std::max(1, std::min(atoi(e), (int)cvo_ctx::MAX_GROUPS));
-  S->G = std::min(S->G, n_pairs);
-  // (refused before the workspace grows; the limits are those of the packed launch words)
+  // sub-batches on separate streams (see cvo_ctx)
+  S->G = std::min(n_pairs, o.streams ? o.streams : (n_pairs >= 32 ? 4 : (n_pairs >= 8 ? 2 : 1)));
+  // (the limits are those of the packed launch words)
   if ((n_pairs + S->G - 1) / S->G > LAUNCH_PAIRS_MAX || S->d.nblk_assoc > LAUNCH_NBLK_MAX) {
     char msg[160];
     snprintf(msg, sizeof msg, "batch too large for one call: at most %d pairs per stream and %d source points per cloud",
              LAUNCH_PAIRS_MAX, LAUNCH_NBLK_MAX * ASSOC_THREADS);
     return fail(ctx, CVO_E_INVALID, msg);
   }
-  int rc = ensure_workspace(ctx, n_pairs, S->L.total);
-  if (rc != CVO_OK) return rc;
-  choose_scan_config(ctx, (n_pairs + S->G - 1) / S->G, S->d.NG, S->d.Mpad, &S->T, &S->gpb);
+  *dp = make_dev_params(ctx, *c.params, c.mode, &c, S);
+  const int T = dp->T, gpb = dp->groups_per_block;
 
-  DevParams dp = make_dev_params(ctx, *params);
-  dp.mode = mode;
-  if (mode == CALL_NONISO) {  // non-isotropic kernel: 9 floats of the inverse (row-major) + the squared cull radius
-    for (int q = 0; q < 9; q++) dp.kinv[q] = kernel_inv_and_cull[q];
-    dp.d2_cull = kernel_inv_and_cull[9];
-    dp.s_ell_sq = params->s_ell * params->s_ell;
-    dp.use_geotype = 0;  // CvoGPU.cu:1950-1951
-    // that kernel's prologue keeps s_ell^2 in float (CvoGPU.cu:236, 252)
-    if (params->is_using_semantics)
-      dp.d2_s_thres = (float)(-2.0 * dp.s_ell_sq * (double)std::log(params->sp_thres / (params->s_sigma * params->s_sigma)));
+  LaunchGeom& geom = S->geom;
+  geom.n_pairs = n_pairs;
+  geom.p0 = 0;
+  geom.stream = ctx->stream;
+  geom.T = T;
+  geom.gx = (S->d.Mpad / (64 * T) + 3) / 4;
+  geom.gy = ((int)align_up((size_t)S->d.NG, 64) + gpb - 1) / gpb;
+  geom.nba = S->d.nblk_assoc;
+  geom.nbl = (N + LIST_THREADS - 1) / LIST_THREADS;
+  geom.nbv = std::min((N + 3) / 4, 2048);
+  geom.wide = dense_wide(N, n_pairs);
+  geom.dense_blocks = dense_blocks_for(N, n_pairs);
+  geom.arena.stride256 = (unsigned)(S->slot_bytes >> 8);  // (arena.base: commit_batch, the arena may yet grow)
+  geom.arena.Npad = S->d.Npad;
+  geom.csplit = c.qd ? coeff_split(c.qd->n_min) : 1;
+  for (int p = 0; p < n_pairs && !c.qd; p++) geom.csplit = std::max(geom.csplit, coeff_split(c.sources[p]->n));
+  geom.npb = S->d.Mpad / PREP_THREADS + (S->d.NGpad * ROWS_PER_GROUP + PREP_THREADS - 1) / PREP_THREADS;
+  geom.idx16 = M < 65536;
+  // (the non-isotropic kernel of CALL_NONISO lives in the GENERAL instantiations only: single evaluations, never the loop)
+  {
+    // every cloud of the call with exact one-hot class rows (ids made at upload): the semantic kernel by class id
+    bool all_hot = !c.qd && !o.no_onehot;
+    for (int p = 0; p < n_pairs && all_hot; p++) all_hot = c.sources[p]->lid != nullptr && c.targets[p]->lid != nullptr;
+    geom.feat = call_feat(*dp, all_hot);
   }
-  dp.T = S->T;
-  dp.groups_per_block = S->gpb;
-  dp.long_lists = S->long_lists ? 1 : 0;
-  dp.row_max_cap = ASSOC_CAP16;
-  // (clustered 10k scenes, scripts/scene_batch.py: 8 for a lone pair; 24 against 64 wins 9 % at 8 pairs in flight, nothing at
-  // 16, and LOSES 5 % at 32 and 10 % at 64 - a chip full of pairs wants its rows in the thread-per-row kernel, whose lanes
-  // are all rows, not in steps of 128 candidate slots per row)
-  dp.row_max_busy = n_pairs <= 4 ? 8 : (n_pairs <= 16 ? 24 : (int)ASSOC_CAP16);
-  if (const char* e = ctx_opt(ctx, "ROW_MAX")) dp.row_max_cap = std::max(1, std::min(atoi(e), (int)ASSOC_CAP16));
-  dp.lean_U = 8;
-  if (const char* e = ctx_opt(ctx, "LEAN_U")) dp.lean_U = std::max(1, atoi(e));
-  // Calm pairs (see PairState::want_full).  In the end game the pose jitters around its optimum: the motion PER ITERATION
-  // stays at ~10 % of a list's allowance while the allowance used SINCE THE BUILD stays below 5 % for hundreds of
-  // iterations (CVO_VERBOSE=2 prints both), so a linear "outlives the next 64 iterations" test never fires.  Four
-  // iterations of linear margin it is: 62.3 -> 61.4 ms per headline step, single pairs -1.5 ... -2.5 %, no additional waits.
-  dp.calm_U = 4;
-  dp.lean_U2 = 2;
-  if (dp.lean_U2 >= dp.lean_U) dp.lean_U2 = 0;
-  // (Round 4 made the optional shrink rebuilds of a batch wait for iteration counts that are multiples of 64 so that the pairs
-  // of a sub-batch share a pass of the rebuild kernels: -1.7 % then.  Re-measured in round 6, with cheaper rebuild kernels and
-  // a shorter serial tail: the stale lists' extra candidates cost more than the shared passes save - 64 x 10k geometric 56.55 ->
-  // 55.67 ms, 64 x config 3 163.5 -> 158.1, 64 clustered scenes 793 -> 779, 16 / 32 pairs 0 / -1.6 % (profiles/r6/shrink_align.txt).
-  // The mask stays as a switch.)
-  dp.shrink_align = 0;
-  if (const char* e = ctx_opt(ctx, "SHRINK_ALIGN")) dp.shrink_align = std::max(0, atoi(e));
-  if (opts && opts->max_iterations > 0) dp.max_iter = std::min(dp.max_iter, opts->max_iterations);
-  if (opts && opts->kernel_clock) dp.kernel_clock = 1;
-  dp.trace_capacity = trace_cap;
-  // the columns of the ELL entries (ell_j) are only written when somebody can ask for them afterwards
-  dp.keep_columns = (mode != CALL_ALIGN || trace_cap > 0 || dp.verify_lists || params->is_exporting_association ||
-                     ctx_opt(ctx, "KEEP_COLUMNS")) ? 1 : 0;
-  dp.no_speculate = ctx_opt(ctx, "NO_SPECULATE") ? 1 : 0;
-  dp.trace_dense = opts ? opts->trace_dense : 0;
-  dp.trace_every = opts ? opts->trace_every : 0;
-  *dp_out = dp;
+  geom.instr = dp->kernel_clock || dp->phase_ticks;
+  geom.verify = dp->verify_lists != 0;
+  geom.horizon_cap = std::max(1, dp->lean_U);
+  return CVO_OK;
+}
 
+// Makes a planned call the context's current one: grows the workspace, fills descriptors and initial states, uploads the
+// control block.  c.qd != nullptr: the call's pairs are the SLOTS of a batch queue (cvo_batch_open) without occupants -
+// every slot starts out finished, cvo_batch_submit fills them.
+int commit_batch(cvo_ctx* ctx, const BatchCall& c, BatchSetup* S, const DevParams& dp) {
+  const int n_pairs = c.n_pairs;
+  if (const int rc = ensure_workspace(ctx, n_pairs, S->slot_bytes); rc != CVO_OK) return rc;
+  S->geom.arena.base = ctx->arena;
   ctx->h_descs.resize(n_pairs);
   ctx->h_states.resize(n_pairs);
-  if (!qd) {
+  if (!c.qd) {
     const unsigned long long serial = next_call_serial();
     for (int p = 0; p < n_pairs; p++)
-      fill_pair(ctx, S, params, opts, mode, mode_ell, n_pairs, p, sources[p], targets[p], init_T + 16 * (size_t)p, serial, dp.max_iter);
+      fill_pair(ctx, S, c.params, c.opts, c.mode, c.mode_ell, n_pairs, p, c.sources[p], c.targets[p], c.init_T + 16 * (size_t)p, serial, dp.max_iter);
   } else {  // empty slots: finished pairs, which every kernel skips
     for (int p = 0; p < n_pairs; p++) {
       std::memset(&ctx->h_descs[p], 0, sizeof(PairDesc));
@@ -394,10 +383,10 @@ int setup_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo
   // partial arrays of pairs whose N is smaller than the batch maximum are fully covered by nblk.
   // one copy from the pinned staging block (no call is in flight on this context: every call ends synchronised)
   std::memcpy(ctx->h_ctl, &dp, sizeof(DevParams));
-  std::memset(ctx->h_ctl + ctx->ctl_off_status, qd ? 1 : 0, sizeof(int) * 2 * (size_t)ctx->cap_pairs);  // (queue: any non-zero word = finished)
+  std::memset(ctx->h_ctl + ctx->ctl_off_status, c.qd ? 1 : 0, sizeof(int) * 2 * (size_t)ctx->cap_pairs);  // (queue: any non-zero word = finished)
   std::memcpy(ctx->h_ctl + ctx->ctl_off_descs, ctx->h_descs.data(), sizeof(PairDesc) * (size_t)n_pairs);
   std::memcpy(ctx->h_ctl + ctx->ctl_off_states, ctx->h_states.data(), sizeof(PairState) * (size_t)n_pairs);
-  std::memset(ctx->h_status[0], qd ? 1 : 0, sizeof(int) * 2 * (size_t)ctx->cap_pairs);
+  std::memset(ctx->h_status[0], c.qd ? 1 : 0, sizeof(int) * 2 * (size_t)ctx->cap_pairs);
   {
     // (descriptors and states of at most n_pairs <= cap_pairs slots are used; the block is laid out for cap_pairs)
     const size_t upto = ctx->ctl_off_states + sizeof(PairState) * (size_t)n_pairs;
@@ -409,41 +398,21 @@ int setup_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const cvo
                                   hipMemcpyHostToDevice, ctx->stream));
     }
   }
-  S->gx = (S->d.Mpad / (64 * S->T) + 3) / 4;
-  S->gy = ((int)align_up((size_t)S->d.NG, 64) + S->gpb - 1) / S->gpb;
-  S->geom.n_pairs = n_pairs;
-  S->geom.p0 = 0;
-  S->geom.stream = ctx->stream;
-  S->geom.T = S->T;
-  S->geom.gx = S->gx;
-  S->geom.gy = S->gy;
-  S->geom.nba = S->d.nblk_assoc;
-  S->geom.nbl = (N + LIST_THREADS - 1) / LIST_THREADS;
-  S->geom.nbv = std::min((N + 3) / 4, 2048);
-  S->geom.wide = dense_wide(N, n_pairs);
-  S->geom.dense_blocks = dense_blocks_for(N, n_pairs);
-  S->geom.arena.base = ctx->arena;
-  S->geom.arena.stride256 = (unsigned)(S->L.total >> 8);
-  S->geom.arena.Npad = S->d.Npad;
-  S->geom.csplit = qd ? coeff_split(qd->n_min) : 1;
-  for (int p = 0; p < n_pairs && !qd; p++) S->geom.csplit = std::max(S->geom.csplit, coeff_split(sources[p]->n));
-  S->geom.npb = S->d.Mpad / PREP_THREADS + (S->d.NGpad * ROWS_PER_GROUP + PREP_THREADS - 1) / PREP_THREADS;
-  S->geom.idx16 = M < 65536;
-  // (the non-isotropic kernel of CALL_NONISO lives in the GENERAL instantiations only: single evaluations, never the loop)
-  {
-    // every cloud of the call with exact one-hot class rows (ids made at upload): the semantic kernel by class id
-    bool all_hot = !qd && ctx_opt(ctx, "NO_ONEHOT") == nullptr;
-    for (int p = 0; p < n_pairs && all_hot; p++) all_hot = sources[p]->lid != nullptr && targets[p]->lid != nullptr;
-    S->geom.feat = call_feat(dp, all_hot);
-  }
-  S->geom.instr = dp.kernel_clock || dp.phase_ticks;
-  S->geom.verify = dp.verify_lists != 0;
-  S->geom.horizon_cap = std::max(1, dp.lean_U);
-  if (!qd) ctx->last_xorder = sources[0]->h_order;
+  if (!c.qd) ctx->last_xorder = c.sources[0]->h_order;
   ctx->last_pairs = n_pairs;
   ctx->last = *S;
   ctx->last_params = dp;
   return CVO_OK;
+}
+
+// Checks, plans and commits a call (or, with qd, the workspace of a batch queue): on success the control block is on its
+// way to the device on the context's stream and *S / *dp say what to launch.
+int setup_batch(cvo_ctx* ctx, const BatchCall& c, BatchSetup* S, DevParams* dp) {
+  int N = 0, M = 0;
+  int rc = check_call(ctx, c.params, c.n_pairs, c.sources, c.targets, c.opts, c.mode, c.mode_ell, c.qd, &N, &M);
+  if (rc == CVO_OK) rc = plan_batch(ctx, c, N, M, S, dp);
+  if (rc == CVO_OK) rc = commit_batch(ctx, c, S, *dp);
+  return rc;
 }
 
 // ---- the chunk graphs of a sub-batch (shared by cvo_align_batch and the batch queue) ----------------------------
@@ -454,7 +423,7 @@ struct LoopCfg {
 };
 
 LoopCfg loop_cfg(const cvo_ctx* ctx, const BatchSetup& S, const DevParams& dp, int U, int U_late) {
-  const bool allow_lean = ctx_opt(ctx, "NO_LEAN") == nullptr;
+  const bool allow_lean = !ctx->opt.no_lean;
   // (start_nodense: the first iterations move fast, a rebuild opportunity in every iteration - for large clouds without
   // the dense kernel: rows that overflow their lists are a small-cloud / huge-lengthscale matter, a pair that has some
   // waits two chunks for the real full graph)
@@ -468,7 +437,7 @@ LaunchGeom group_geom(const cvo_ctx* ctx, const BatchSetup& S, int n, int g) {
   LaunchGeom geom = S.geom;
   geom.p0 = p0;
   geom.n_pairs = p1 - p0;
-  geom.arena.base += S.L.total * (size_t)p0;
+  geom.arena.base += S.slot_bytes * (size_t)p0;
   geom.stream = ctx->gstream[g];
   geom.wide = dense_wide(S.N, geom.n_pairs);
   return geom;
@@ -534,26 +503,24 @@ int cvo_align_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const
   BatchSetup S;
   DevParams dp;
   const auto t_host0 = std::chrono::steady_clock::now();
-  int rc = setup_batch(ctx, params, n_pairs, sources, targets, init_T, opts, CALL_ALIGN, 0.f, &S, &dp);
+  int rc = setup_batch(ctx, {params, n_pairs, sources, targets, init_T, opts, CALL_ALIGN, 0.f, nullptr, nullptr}, &S, &dp);
   if (rc != CVO_OK) return rc;
   const auto t_host1 = std::chrono::steady_clock::now();
 
-  const int max_iter = dp.max_iter;
+  const int max_iter = dp.max_iter, verbose = ctx->opt.verbose;
   // Iterations per chunk (= per host check).  A chunk boundary costs a stream ~10 us (graph launch, the event; the
   // status words reach the host by themselves), a longer chunk lets a finished or re-planned sub-batch run on for nothing: 16 iterations for
   // the first 256 (short warm-started solves end there, and the early requests change quickly), 32 afterwards.
   int U = (opts && opts->iters_per_launch > 0) ? opts->iters_per_launch : 16;
   U = std::max(1, std::min(U, std::max(1, max_iter)));
-  const bool adaptive_chunks = !(opts && opts->iters_per_launch > 0) && !ctx_opt(ctx, "FIXED_CHUNKS") && max_iter >= 512;
+  const bool adaptive_chunks = !(opts && opts->iters_per_launch > 0) && !ctx->opt.fixed_chunks && max_iter >= 512;
   const int U_late = adaptive_chunks ? 2 * U : U;
   const int n_early_chunks = adaptive_chunks ? 256 / U : 0;
   // The first two chunks of a call are chosen blind (the host learns what a pair wants one chunk behind) and are full
   // graphs: short ones, so that a warm-started pair whose lists outlive dozens of iterations from the start is not held
   // on six launches per iteration for 32 of its few hundred iterations.
-  int U_first = adaptive_chunks ? std::max(1, U / 4) : U;
-  if (adaptive_chunks && ctx_opt(ctx, "FIRST_U")) U_first = std::max(1, std::min(atoi(ctx_opt(ctx, "FIRST_U")), U));
-  int n_first_chunks = U_first != U ? 2 : 0;
-  if (U_first != U && ctx_opt(ctx, "FIRST_CHUNKS")) n_first_chunks = std::max(0, atoi(ctx_opt(ctx, "FIRST_CHUNKS")));
+  const int U_first = !adaptive_chunks ? U : (ctx->opt.first_U ? std::min(ctx->opt.first_U, U) : std::max(1, U / 4));
+  const int n_first_chunks = U_first != U ? ctx->opt.first_chunks : 0;
   const int graph_mode = opts ? opts->use_graph : 0;
   const bool use_graph = graph_mode != 1;
 
@@ -587,7 +554,7 @@ int cvo_align_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const
     for (; ch < chunk_cap && !all_done; ch++) {
       const int slot = ch & 1;
       const int Uc = ch < n_first_chunks ? U_first : (ch < n_early_chunks + n_first_chunks ? U : U_late);
-      if (ctx_opt(ctx, "VERBOSE") && atoi(ctx_opt(ctx, "VERBOSE")) >= 3) {
+      if (verbose >= 3) {
         fprintf(stderr, "[cvo] chunk %d (%d iterations): graphs", ch, Uc);
         for (int g = 0; g < G; g++) fprintf(stderr, " %s%s", kChunkNames[(int)next[g].kind], next[g].dense ? "+dense" : "");
         fprintf(stderr, "\n");
@@ -626,7 +593,7 @@ int cvo_align_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const
           for (int q = 0; q < ng; q++)
             if (hs[q] == 0) want.add(hs[ng + q]);
           next[g] = choose_chunk(cfg, want);
-          if (ctx_opt(ctx, "VERBOSE") && atoi(ctx_opt(ctx, "VERBOSE")) >= 2 && ch < 12) {
+          if (verbose >= 2 && ch < 12) {
             int nw = 0;
             for (int q = 0; q < ng; q++) nw += hs[ng + q] != 0;
             fprintf(stderr, "[cvo] after chunk %d group %d: %d of %d pairs ask for the full graph\n", ch - 1, g, nw, geom[g].n_pairs);
@@ -635,7 +602,7 @@ int cvo_align_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const
       }
     }
     ctx->last_chunks = ch;
-    if (ctx_opt(ctx, "VERBOSE")) fprintf(stderr, "[cvo] host loop: %.2f ms in hipGraphLaunch, %.2f ms waiting for the device\n", t_launch, t_wait);
+    if (verbose) fprintf(stderr, "[cvo] host loop: %.2f ms in hipGraphLaunch, %.2f ms waiting for the device\n", t_launch, t_wait);
     ctx->last_lean_launches = n_lean_launch;
     ctx->last_full_launches = n_full_launch;
     if (!all_done) {  // the in-flight chunk may have finished the stragglers; otherwise report it
@@ -657,7 +624,7 @@ int cvo_align_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const
   const auto t_host2 = std::chrono::steady_clock::now();
   float ms = 0;
   HIP_TRY(ctx, hipEventElapsedTime(&ms, ctx->ev_start, ctx->ev_stop));
-  if (ctx_opt(ctx, "VERBOSE"))
+  if (verbose)
     fprintf(stderr, "[cvo] host: setup %.2f ms, enqueue + wait %.2f ms\n",
             std::chrono::duration<double, std::milli>(t_host1 - t_host0).count(),
             std::chrono::duration<double, std::milli>(t_host2 - t_host1).count());
@@ -675,7 +642,7 @@ int cvo_align_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const
       return fail(ctx, CVO_E_VERIFY, msg);
     }
   }
-  if (ctx_opt(ctx, "VERBOSE")) {
+  if (verbose) {
     long builds = 0, stalls = 0, its = 0, adopted = 0;
     for (int p = 0; p < n_pairs; p++) {
       adopted += ctx->h_states[p].n_adopted;
@@ -683,7 +650,7 @@ int cvo_align_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const
       stalls += ctx->h_states[p].n_stalls;
       its += ctx->h_states[p].status ? ctx->h_states[p].iterations : ctx->h_states[p].k;
     }
-    if (atoi(ctx_opt(ctx, "VERBOSE")) >= 2)
+    if (verbose >= 2)
       for (int p = 0; p < std::min(n_pairs, 4); p++)
         fprintf(stderr, "[cvo]   pair %d: k %d, list allowance used %.3f, per iteration %.5f, want %d, builds %d, ell %.4f (built at %.4f)\n", p,
                 ctx->h_states[p].k, ctx->h_states[p].last_used, ctx->h_states[p].last_rate, ctx->h_states[p].want_full,

@@ -137,12 +137,10 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
     const float* p = reinterpret_cast<const float*>(h.xyz + (size_t)i * h.xyz_stride);
     finite = std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
   }
-  const char* ord = ctx_opt(ctx, "ORDER");
-  const bool device_order = n >= 8 && n <= KD_MAX_POINTS && finite && ctx_opt(ctx, "NO_SORT") == nullptr &&
-                            !(ord && (std::strcmp(ord, "host") == 0 || std::strcmp(ord, "virtual") == 0));
+  const bool device_order = n >= 8 && n <= KD_MAX_POINTS && finite && !ctx->opt.no_sort && ctx->opt.order == CloudOrder::Device;
   // one-hot class rows?  (exactly: the fast path replaces arithmetic on the rows by two constants)
   std::vector<int> lid_host;
-  if (h.label && n > 0 && ctx_opt(ctx, "NO_ONEHOT") == nullptr) {
+  if (h.label && n > 0 && !ctx->opt.no_onehot) {
     lid_host.resize((size_t)n);
     bool onehot = true;
     for (int i = 0; i < n && onehot; i++) {
@@ -222,7 +220,7 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
     if (has_lid) std::memcpy(&stage[o_rawlid], lid_host.data(), sizeof(int) * (size_t)n);
   } else {
     std::vector<int> order;
-    spatial_order(x4, n, order, ctx_opt(ctx, "NO_SORT") != nullptr, ord && std::strcmp(ord, "virtual") == 0);
+    spatial_order(x4, n, order, ctx->opt.no_sort, ctx->opt.order == CloudOrder::Virtual);
     // colour, class distributions and geometric types are kept in SPATIAL order only (position r holds the attributes of
     // point order[r]): the kernels index them by sorted position, like the coordinates they gather per candidate
     if (h.feat) {
