@@ -254,3 +254,46 @@ def inner_product_cpu(P, x, y, T_t2s, ell, fx=None, fy=None, lx=None, ly=None):
         d2c = ((fx.astype(np.float64)[:, None, :] - fy.astype(np.float64)[None, :, :]) ** 2).sum(-1)
         A = A * float(np.float32(P.c_sigma)) ** 2 * np.exp(-d2c / (2.0 * float(np.float32(P.c_ell)) ** 2))
     return float(A[near & (A > sp)].sum())
+
+
+def gate_shares(P, x, y, fx, fy, lx, ly, gx, gy, ell):
+    """The share of the pairs REACHING each gate that it rejects, in the order the pair arithmetic tests them (geometric
+    type, distance, colour, semantics, then a > sp_thres on the product), float64, all N x M pairs, no first-K truncation:
+    dict(gate -> (reached, rejected)) for the gates that are switched on."""
+    n, m = x.shape[0], y.shape[0]
+    sp = np.float64(np.float32(P.sp_thres))
+    alive = np.ones((n, m), bool)
+    A = np.ones((n, m))
+    out = {}
+
+    def gate(name, ok, factor):
+        nonlocal alive, A
+        reached = int(alive.sum())
+        alive = alive & ok
+        out[name] = (reached, reached - int(alive.sum()))
+        A = A * factor
+
+    if P.is_using_geometric_type:
+        g, h = gx.astype(np.float64), gy.astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            gs = (g @ h.T) ** 2 / ((g * g).sum(1)[:, None] * (h * h).sum(1)[None, :])
+        gate("geotype", ~(gs < 0.01), gs)
+    if P.is_using_geometry:
+        s2 = np.float64(np.float32(P.sigma)) ** 2
+        xx, yy = x.astype(np.float64), y.astype(np.float64)
+        l = (np.linalg.norm(xx, axis=1) / 500.0 + 1.0) * ell
+        d2 = ((xx[:, None, :] - yy[None, :, :]) ** 2).sum(-1)
+        gate("geometry", d2 < (-2.0 * l * l * np.log(sp / s2))[:, None], s2 * np.exp(-d2 / (2.0 * l[:, None] ** 2)))
+    if P.is_using_intensity:
+        c2 = np.float64(np.float32(P.c_ell)) ** 2
+        cs2 = np.float64(np.float32(P.c_sigma)) ** 2
+        d2c = ((fx.astype(np.float64)[:, None, :] - fy.astype(np.float64)[None, :, :]) ** 2).sum(-1)
+        gate("colour", d2c < -2.0 * c2 * np.log(sp / cs2), cs2 * np.exp(-d2c / (2.0 * c2)))
+    if P.is_using_semantics:
+        se2 = np.float64(np.float32(P.s_ell)) ** 2
+        ss2 = np.float64(np.float32(P.s_sigma)) ** 2
+        d2s = ((lx.astype(np.float64)[:, None, :] - ly.astype(np.float64)[None, :, :]) ** 2).sum(-1)
+        gate("semantics", d2s < -2.0 * se2 * np.log(sp / ss2), ss2 * np.exp(-d2s / (2.0 * se2)))
+    with np.errstate(invalid="ignore"):
+        gate("product", A > sp, 1.0)
+    return out

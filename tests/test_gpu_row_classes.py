@@ -43,9 +43,10 @@ def _expected_classes(rc):
       * an overflow row is scanned literally when it is beyond a long list (more than LONG_CAP candidates), or always when
         there are no long lists (M > 65535: cvo_sched.hip, long_lists = M <= 65535) - cvo_k_list.h:291."""
     cap = ASSOC_CAP16 if rc.M < 65536 else ASSOC_CAP32
-    ovf = rc.counts > cap
+    cand = rc.cand_counts  # (a row's class follows its geometric candidates; its hits may be fewer: test_gpu_feature_gates.py)
+    ovf = cand > cap
     long_lists = rc.M <= 65535
-    scan = ovf & (rc.counts > LONG_CAP) if long_lists else ovf
+    scan = ovf & (cand > LONG_CAP) if long_lists else ovf
     return int(ovf.sum()), int(scan.sum())
 
 
@@ -53,10 +54,11 @@ def _oracle_clouds(oracle, src, tgt):
     return oracle.Cloud.from_pointcloud(src), oracle.Cloud.from_pointcloud(tgt)
 
 
-def _iteration0(oracle, rc, K, classes=True):
+def _iteration0(oracle, rc, K, classes=True, tol_f64=TOL_F64):
     """One align iteration at (ell, K) from the identity: the ELL against the closed form (bit-exact pattern, values to
-    TOL_F64) and the oracle (bit-exact pattern, values to an ulp), trace 0 against the oracle, and the row classes."""
-    P = _params(rc.fsrc is not None, K)
+    TOL_F64) and the oracle (bit-exact pattern, values to an ulp), trace 0 against the oracle, and the row classes.  A cloud
+    of a rejecting feature kind brings its own switches and cut-offs (and its caller the bound against float64)."""
+    P = _params(rc.fsrc is not None, K) if rc.kind is None else rc.params(max(K, 512))
     src, tgt = rc.clouds()
     gpu = CvoGPU(params=P)
     g = gpu.align(src, tgt, EYE, max_iterations=1, ell0=rc.ell, K0=K, trace_capacity=2, trace_dense=2)
@@ -65,7 +67,7 @@ def _iteration0(oracle, rc, K, classes=True):
     valid = np.arange(K)[None, :] < cnz[:, None]
     assert np.array_equal(nz, cnz), (K, np.flatnonzero(nz != cnz)[:8])
     assert np.array_equal(np.where(valid, ind, -1), cind), (K, np.flatnonzero((np.where(valid, ind, -1) != cind).any(1))[:8])
-    assert np.allclose(np.where(valid, mat, 0), cmat, rtol=TOL_F64, atol=0), K
+    assert np.allclose(np.where(valid, mat, 0), cmat, rtol=tol_f64, atol=0), K
     ox, oy = _oracle_clouds(oracle, src, tgt)
     o = oracle.iteration(oracle.params_from(P), ox, oy, EYE[:3, :3], EYE[:3, 3], rc.ell, K, want_ell=True)
     assert np.array_equal(nz, o["nonzeros"]) and np.array_equal(ind, o["ind"])

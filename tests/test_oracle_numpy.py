@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import cases
+import feature_mixes as fm
 import np_reference as npr
 from unified_cvo_amd import CvoParams, CvoPointCloud, synth
 
@@ -90,6 +91,49 @@ def test_geometric_type_gate(oracle):
     A = _dense_from_ell(o, 200, 200)
     different = (gx[:, None, 0] != gy[None, :, 0])
     assert not (A[different] > 0).any()
+
+
+def _mix_case(oracle, mix, labels, moved, ell, K):
+    """One setting of the four switches through _check as it stands, and _check's allowance for pairs within float
+    rounding of a cut-off must come out unused: oracle and numpy keep exactly the same pairs."""
+    d, init = fm.arrays(300, labels)
+    P = fm.params(mix, moved=moved)
+    src, tgt = fm.clouds(d)
+    o, r = _check(oracle, P, src, tgt, init[:3, :3], init[:3, 3], ell, K, fx=d["fx"], fy=d["fy"], lx=d["lx"], ly=d["ly"],
+                  gx=d["gx"], gy=d["gy"])
+    A = _dense_from_ell(o, 300, 300)
+    assert ((A > 0) != r["keep"]).sum() == 0
+    assert o["trace"].nnz == r["nnz"] and o["trace"].max_nnz == r["max_nnz"]
+    return d, init, P, r
+
+
+@pytest.mark.parametrize("ell,K", fm.SHIPPED_STATES)
+@pytest.mark.parametrize("mix", fm.MIXES, ids=fm.MIX_IDS)
+def test_switch_matrix_shipped_cutoffs(oracle, mix, ell, K):
+    """All 16 settings of (geometry, intensity, semantics, geometric_type) with the shipped cut-offs, soft class rows and
+    mixed geometric types ([0.3, 0.9] and [0.8, -0.5] among them)."""
+    _mix_case(oracle, mix, "soft", False, ell, K)
+
+
+@pytest.mark.parametrize("ell,K", fm.MOVED_STATES)
+@pytest.mark.parametrize("labels", ["soft", "hot", "hot_soft"])
+@pytest.mark.parametrize("mix", fm.MIXES, ids=fm.MIX_IDS)
+def test_switch_matrix_moved_cutoffs_every_gate_rejects(oracle, mix, labels, ell, K):
+    """The same 16 settings with sigma, sp_thres, c_ell and s_ell moved (feature_mixes.MOVED): every switched-on gate
+    rejects between a tenth and nine tenths of the pairs that reach it - the product gate too wherever geometry meets
+    another factor; with a single factor the factor's own cut-off is a > sp_thres and the product gate rejects nothing."""
+    d, init, P, r = _mix_case(oracle, mix, labels, True, ell, K)
+    R, T = init[:3, :3].astype(np.float64), init[:3, 3].astype(np.float64)
+    y = (d["y"].astype(np.float64) - T) @ R
+    shares = npr.gate_shares(P, d["x"], y, d["fx"], d["fy"], d["lx"], d["ly"], d["gx"], d["gy"], ell)
+    assert set(shares) == {n for n, on in zip(("geometry", "colour", "semantics", "geotype"), mix) if on} | {"product"}
+    for name, (reached, rejected) in shares.items():
+        if name != "product" or (mix[0] and sum(mix) > 1):
+            assert 0.1 * reached <= rejected <= 0.9 * reached, (name, reached, rejected)
+        elif sum(mix) <= 1:
+            assert rejected == 0, (name, reached, rejected)
+    if K >= 300:  # no first-K truncation: the pairs that survive all five gates are the reference's nonzeros
+        assert shares["product"][0] - shares["product"][1] == r["nnz"]
 
 
 def test_range_ell_only_in_step_size(oracle):
