@@ -48,6 +48,30 @@ void upload(cvo_ctx* ctx, const CvoPointCloud& pc, DeviceCloud& out) {
         "cvo_cloud_upload");
 }
 
+// The same arrays without the upload (voxel selection: the library gathers the kept rows itself)
+struct FlatCloud {
+  int n = 0;
+  std::vector<float> xyz, feat, label, geo;
+  explicit FlatCloud(const CvoPointCloud& pc) : n(pc.num_points()), xyz(3 * (size_t)pc.num_points()), geo(2 * (size_t)pc.num_points(), 0.f) {
+    for (int i = 0; i < n; i++)
+      for (int c = 0; c < 3; c++) xyz[3 * (size_t)i + c] = pc.positions()[i][c];
+    const MatXf& F = pc.features();
+    if (F.rows() == n && F.cols() > 0) {
+      feat.assign(CVO_FEATURE_DIMENSIONS * (size_t)n, 0.f);
+      for (int i = 0; i < n; i++)
+        for (int c = 0; c < CVO_FEATURE_DIMENSIONS && c < F.cols(); c++) feat[CVO_FEATURE_DIMENSIONS * (size_t)i + c] = F(i, c);
+    }
+    const MatXf& L = pc.labels();
+    if (pc.num_classes() > 0 && L.rows() == n) {
+      label.assign(CVO_NUM_CLASSES * (size_t)n, 0.f);
+      for (int i = 0; i < n; i++)
+        for (int c = 0; c < pc.num_classes() && c < CVO_NUM_CLASSES; c++) label[CVO_NUM_CLASSES * (size_t)i + c] = L(i, c);
+    }
+    const std::vector<float>& g = pc.geometric_types();
+    for (size_t i = 0; i < geo.size() && i < g.size(); i++) geo[i] = g[i];
+  }
+};
+
 void fill_association(cvo_ctx* ctx, const cvo_params_t& p, cvo_cloud* s, cvo_cloud* t, const Mat4f& T, float ell,
                       Association& a) {
   const int n = cvo_cloud_size(s);
@@ -337,6 +361,64 @@ std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::upload_clouds(const std::vector<
     check(ctx, cvo_cloud_upload_many(ctx, k, n.data(), px.data(), pf.data(), pl.data(), pg.data(), host_threads, out->handles.data()),
           "cvo_cloud_upload_many");
   return out;
+}
+
+CvoPointCloud CvoGPU::voxel_downsample(const CvoPointCloud& cloud, float voxel_size, std::vector<int>* kept) const {
+  std::lock_guard<std::mutex> lk(call_mutex);
+  const int n = cloud.num_points();
+  std::vector<float> xyz(3 * (size_t)n);
+  for (int i = 0; i < n; i++)
+    for (int c = 0; c < 3; c++) xyz[3 * (size_t)i + c] = cloud.positions()[i][c];
+  std::vector<int> k((size_t)std::max(n, 1));
+  int nk = 0;
+  check(ctx, cvo_voxel_select(ctx, n, xyz.data(), voxel_size > 0.f ? voxel_size : params.multiframe_downsample_voxel_size, k.data(), &nk),
+        "cvo_voxel_select");
+  k.resize((size_t)nk);
+  CvoPointCloud out = cloud.select(k);
+  if (kept) *kept = std::move(k);
+  return out;
+}
+
+std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::upload_clouds_voxel(const std::vector<const CvoPointCloud*>& clouds,
+                                                                    float voxel_size) const {
+  std::lock_guard<std::mutex> lk(call_mutex);
+  const float s = voxel_size > 0.f ? voxel_size : params.multiframe_downsample_voxel_size;
+  std::unique_ptr<ResidentClouds> out(new ResidentClouds());
+  out->handles.assign(clouds.size(), nullptr);
+  out->kept_.resize(clouds.size());
+  for (size_t c = 0; c < clouds.size(); c++) {  // (on a throw `out` releases the clouds already made)
+    const FlatCloud f(*clouds[c]);
+    std::vector<int>& k = out->kept_[c];
+    k.resize((size_t)std::max(f.n, 1));
+    int nk = 0;
+    check(ctx, cvo_cloud_upload_voxel(ctx, f.n, f.xyz.data(), f.feat.empty() ? nullptr : f.feat.data(),
+                                      f.label.empty() ? nullptr : f.label.data(), f.geo.data(), s, &out->handles[c], k.data(), &nk),
+          "cvo_cloud_upload_voxel");
+    k.resize((size_t)nk);
+  }
+  return out;
+}
+
+int CvoGPU::align(const ResidentClouds& clouds, std::vector<double>& poses, const std::vector<bool>& frames_to_hold_const,
+                  const std::vector<std::pair<int, int>>& edges, double* registration_seconds) const {
+  const int F = clouds.size();
+  if ((int)frames_to_hold_const.size() != F || poses.size() != 12 * (size_t)F)
+    throw std::invalid_argument("align: one hold flag and 12 pose entries per cloud");
+  std::vector<int> ed, hold(F);
+  for (const auto& e : edges) {
+    ed.push_back(e.first);
+    ed.push_back(e.second);
+  }
+  for (int k = 0; k < F; k++) hold[k] = frames_to_hold_const[k] ? 1 : 0;
+  std::lock_guard<std::mutex> lk(call_mutex);
+  std::vector<const cvo_cloud*> h(clouds.handles.begin(), clouds.handles.end());
+  cvo_params_t p;
+  std::memcpy(&p, &params, sizeof(p));
+  cvo_multiframe_info_t info{};
+  check(ctx, cvo_multiframe_align(ctx, &p, F, h.data(), poses.data(), hold.data(), (int)edges.size(), ed.data(), &info, nullptr, 0, nullptr),
+        "cvo_multiframe_align");
+  if (registration_seconds) *registration_seconds = info.seconds;
+  return 0;
 }
 
 std::vector<int> CvoGPU::align_batch(const ResidentClouds& sources, const ResidentClouds& targets, const std::vector<Mat4f>& inits,

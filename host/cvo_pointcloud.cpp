@@ -218,6 +218,31 @@ CvoPointCloud operator+(CvoPointCloud a, const CvoPointCloud& b) {
   return a;
 }
 
+CvoPointCloud CvoPointCloud::select(const std::vector<int>& indices) const {
+  const int n = (int)indices.size();
+  CvoPointCloud out(feature_dimensions_, num_classes_);
+  out.num_points_ = n;
+  out.positions_.resize((size_t)n);
+  const bool has_f = features_.rows() == num_points_ && features_.cols() > 0, has_l = labels_.rows() == num_points_ && labels_.cols() > 0;
+  if (has_f) out.features_.resize(n, features_.cols());
+  if (has_l) out.labels_.resize(n, labels_.cols());
+  out.geometric_types_.assign(geometric_types_.size() >= 2 * (size_t)num_points_ ? 2 * (size_t)n : 0, 0.f);
+  for (int r = 0; r < n; r++) {
+    const int i = indices[(size_t)r];
+    if (i < 0 || i >= num_points_) throw std::out_of_range("CvoPointCloud::select: index " + std::to_string(i));
+    out.positions_[(size_t)r] = positions_[(size_t)i];
+    if (has_f)
+      for (int c = 0; c < features_.cols(); c++) out.features_(r, c) = features_(i, c);
+    if (has_l)
+      for (int c = 0; c < labels_.cols(); c++) out.labels_(r, c) = labels_(i, c);
+    if (!out.geometric_types_.empty()) {
+      out.geometric_types_[2 * (size_t)r] = geometric_types_[2 * (size_t)i];
+      out.geometric_types_[2 * (size_t)r + 1] = geometric_types_[2 * (size_t)i + 1];
+    }
+  }
+  return out;
+}
+
 void CvoPointCloud::reserve(int num_points, int feature_dims, int num_classes) {
   num_points_ = num_points;
   num_classes_ = num_classes;

@@ -71,15 +71,31 @@ class CvoGPU {
     ResidentClouds(const ResidentClouds&) = delete;
     ResidentClouds& operator=(const ResidentClouds&) = delete;
     int size() const { return (int)handles.size(); }
+    int num_points(int k) const { return cvo_cloud_size(handles[(size_t)k]); }
+    // upload_clouds_voxel: the indices of cloud k's points that were kept, ascending (empty after upload_clouds)
+    const std::vector<int>& kept(int k) const { return kept_[(size_t)k]; }
 
    private:
     friend class CvoGPU;
     ResidentClouds() = default;
     std::vector<cvo_cloud*> handles;
+    std::vector<std::vector<int>> kept_;
   };
   std::unique_ptr<ResidentClouds> upload_clouds(const std::vector<const CvoPointCloud*>& clouds, int host_threads = 0) const;
   std::vector<int> align_batch(const ResidentClouds& sources, const ResidentClouds& targets, const std::vector<Mat4f>& inits,
                                std::vector<Mat4f>& transforms, double* seconds = nullptr) const;
+  // New: voxel-grid downsampling on the device - what the drivers do with cvo::VoxelMap before align()
+  // (main_multi_frame_irls_tum.cpp:290-335; utils/VoxelMap.hpp is the host class): of every occupied voxel of side
+  // voxel_size the point with the LOWEST index is kept, in ascending index (cvo_voxel_select, include/cvo_hip.h).
+  // voxel_size <= 0 takes params.multiframe_downsample_voxel_size.  voxel_downsample returns the kept points as a host
+  // cloud (*kept: their indices); upload_clouds_voxel leaves them resident, attributes gathered on the host for the
+  // survivors only (a loop over cvo_cloud_upload_voxel).  Refusals (non-finite coordinates, |k| >= 2^20) throw.
+  CvoPointCloud voxel_downsample(const CvoPointCloud& cloud, float voxel_size = 0.f, std::vector<int>* kept = nullptr) const;
+  std::unique_ptr<ResidentClouds> upload_clouds_voxel(const std::vector<const CvoPointCloud*>& clouds, float voxel_size = 0.f) const;
+  // New: multi-frame registration over resident clouds (cvo_multiframe_align as it is): poses 12 doubles per cloud (3x4
+  // row-major, updated in place), edges pairs of indices into `clouds`.
+  int align(const ResidentClouds& clouds, std::vector<double>& poses, const std::vector<bool>& frames_to_hold_const,
+            const std::vector<std::pair<int, int>>& edges, double* registration_seconds = nullptr) const;
   // New: a STREAM of resident pairs through `slots` in-flight slots (cvo_batch_open / _submit / _poll, include/cvo_hip.h):
   // a pair that finishes hands its slice of the workspace to the next one at the next chunk boundary, so the GPU stays
   // full however different the pairs' iteration counts are - upstream's own use is a frame stream with warm starts

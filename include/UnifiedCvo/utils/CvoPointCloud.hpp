@@ -33,6 +33,10 @@ class CvoPointCloud {
   static CvoPointCloud from_xyz(const float* xyz, int n);                                // type (1,0), F = 0
   static CvoPointCloud from_xyzrgb(const float* xyz, const unsigned char* rgb, int n);   // type (0,1), F = 5
 
+  // New: the cloud of the rows `indices`, in that order (what a voxel selection keeps: CvoGPU::voxel_downsample).
+  // Throws std::out_of_range on an index outside the cloud.
+  CvoPointCloud select(const std::vector<int>& indices) const;
+
   static void transform(const Mat4f& pose, const CvoPointCloud& input, CvoPointCloud& output);
   friend CvoPointCloud operator+(CvoPointCloud a, const CvoPointCloud& b);
 

@@ -191,6 +191,22 @@ int cvo_cloud_upload_aos192(cvo_ctx* ctx, int n, const void* cvo_points, cvo_clo
  * out: n_clouds handles (all NULL on error). */
 int cvo_cloud_upload_many(cvo_ctx* ctx, int n_clouds, const int* n, const float* const* xyz, const float* const* feat,
                           const float* const* label, const float* const* geotype, int threads, cvo_cloud** out);
+/* ---- voxel-grid downsampling: replaces cvo::VoxelMap<PointT> as the drivers use it (VoxelMap.hpp, VoxelMap_impl.hpp:126-170) ----
+ * Voxel of a point: k = (lrint(x / s), lrint(y / s), lrint(z / s)) with the correctly rounded float quotient and ties to
+ * even.  Of every occupied voxel ONE point is kept, the one with the lowest index (upstream draws a member at random);
+ * kept[] holds the kept points' indices in ascending order, *n_kept their number.  CVO_E_INVALID, nothing written: a voxel
+ * size that is not finite or <= 0, a non-finite coordinate, |k| >= 2^20 on any axis (cvo_last_error names the point, the axis
+ * and the extent).  CVO_E_UNSUPPORTED: n > 2^24.  n = 0 is an empty selection.  The selection runs on the context's upload
+ * stream: like an upload it neither waits for nor delays a solve in flight.  Frames of fewer than 4096 points take the CPU
+ * twin, which is faster there; switch VOXEL_HOST=1 / 0: the CPU twin / the kernels for every size. */
+/* one point per occupied voxel of side voxel_size (VoxelMap.hpp / VoxelMap_impl.hpp:126-149, deterministic: lowest index) */
+int cvo_voxel_select(cvo_ctx* ctx, int n, const float* xyz, float voxel_size, int* kept /* n ints */, int* n_kept);
+int cvo_voxel_select_host(int n, const float* xyz, float voxel_size, int* kept, int* n_kept);   /* CPU twin, no context */
+/* Selection + upload: only the coordinates cross to the device for the selection; the cloud returned is the one
+ * cvo_cloud_upload makes of the kept rows (same spatial order, one-hot detection, lazily attached zero slabs). */
+int cvo_cloud_upload_voxel(cvo_ctx* ctx, int n, const float* xyz, const float* feat, const float* label,
+                           const float* geotype, float voxel_size, cvo_cloud** out,
+                           int* kept /* n ints or NULL */, int* n_kept /* or NULL */);
 int cvo_cloud_size(const cvo_cloud* c);
 void cvo_cloud_free(cvo_cloud* c);
 

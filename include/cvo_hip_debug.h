@@ -76,6 +76,12 @@ int cvo_debug_device_memory(cvo_ctx* ctx, size_t* free_bytes, size_t* total_byte
  * row-major doubles).  out[91] = cost, g[12], the upper triangle of the 12 x 12 H row by row (78). */
 int cvo_debug_irls_normal(cvo_ctx* ctx, const cvo_cloud* frame1, const cvo_cloud* frame2, const double pose1[12],
                           const double pose2[12], double* out);
+/* The context's last voxel selection (cvo_voxel_select / cvo_cloud_upload_voxel) on the device: slots of the hash table,
+ * slots taken (= voxels), slots visited by all inserts, the longest probe sequence of one insert (1 = its home slot), and the
+ * points that reached the table in HBM (all of them without the block-local pre-pass).  All 0 after a selection on the host
+ * (VOXEL_HOST=1, or fewer than 4096 points by default) or of an empty cloud.  Any pointer may be NULL. */
+int cvo_debug_voxel_stats(cvo_ctx* ctx, unsigned long long* capacity, unsigned long long* occupied,
+                          unsigned long long* probes_total, unsigned long long* probe_longest, unsigned long long* entered);
 
 #ifdef __cplusplus
 }

@@ -173,6 +173,7 @@ EXPORTED = [
     "cvo_batch_open", "cvo_batch_submit", "cvo_batch_poll", "cvo_batch_pending", "cvo_batch_stats", "cvo_batch_close",
     "cvo_inner_product_batch", "cvo_function_angle_batch", "cvo_debug_last_score_batch",
     "cvo_multiframe_align", "cvo_debug_irls_normal",
+    "cvo_voxel_select", "cvo_voxel_select_host", "cvo_cloud_upload_voxel", "cvo_debug_voxel_stats",
 ]
 
 _libs = {}
@@ -256,6 +257,11 @@ def lib(path=None):
                                        C.POINTER(C.c_int), C.POINTER(cvo_multiframe_info_t),
                                        C.POINTER(cvo_multiframe_trace_t), ip, C.POINTER(C.c_int)]
     L.cvo_debug_irls_normal.argtypes = [vp, vp, vp, dp, dp, dp]
+    ipp = C.POINTER(C.c_int)
+    L.cvo_voxel_select.argtypes = [vp, ip, fp, C.c_float, ipp, ipp]
+    L.cvo_voxel_select_host.argtypes = [ip, fp, C.c_float, ipp, ipp]
+    L.cvo_cloud_upload_voxel.argtypes = [vp, ip, fp, fp, fp, fp, C.c_float, C.POINTER(vp), ipp, ipp]
+    L.cvo_debug_voxel_stats.argtypes = [vp] + [C.POINTER(C.c_ulonglong)] * 5
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

@@ -162,6 +162,18 @@ class CvoPointCloud:
         r._reserved = True
         return r
 
+    def select(self, indices):
+        """A new cloud of the rows `indices`, in that order (what a voxel selection keeps)."""
+        idx = np.asarray(indices, np.int64).reshape(-1)
+        r = CvoPointCloud(self.feature_dimensions_, self.num_classes_)
+        r.num_points_ = int(idx.shape[0])
+        r.positions_ = np.ascontiguousarray(self.positions_[idx])
+        r.features_ = np.ascontiguousarray(self.features_[idx]) if self.features_.shape[0] == self.num_points_ else self.features_
+        r.labels_ = np.ascontiguousarray(self.labels_[idx]) if self.labels_.shape[0] == self.num_points_ else self.labels_
+        r.geometric_types_ = np.ascontiguousarray(self.geometric_types_.reshape(-1, 2)[idx])
+        r._reserved = True
+        return r
+
     # -- what CvoPointCloud_to_gpu builds per point (CvoGPU_impl.cu:206-263) ----------------------
     def device_arrays(self):
         n = self.num_points_
@@ -398,6 +410,43 @@ class CvoGPU:
 
     def upload(self, pc):
         return DeviceCloud(self, pc)
+
+    def _voxel_size(self, voxel_size):
+        return float(self.params.multiframe_downsample_voxel_size if voxel_size is None else voxel_size)
+
+    def voxel_select(self, xyz, voxel_size=None):
+        """cvo_voxel_select: indices (int32, ascending) of the points a voxel grid of side `voxel_size` keeps - of every
+        occupied voxel the point with the lowest index.  voxel_size None: params.multiframe_downsample_voxel_size."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = xyz.shape[0]
+        kept = np.zeros(max(n, 1), np.int32)
+        nk = C.c_int()
+        self._check(self.L.cvo_voxel_select(self.ctx, n, _fptr(xyz), self._voxel_size(voxel_size),
+                                            kept.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nk)))
+        return kept[:nk.value].copy()
+
+    def upload_voxel(self, pc, voxel_size=None):
+        """cvo_cloud_upload_voxel: the resident cloud of the points voxel_select keeps (attributes follow their point);
+        `.kept` holds their indices in `pc`.  Indistinguishable from upload(pc.select(kept))."""
+        xyz, feat, label, geo = pc.device_arrays()
+        n = xyz.shape[0]
+        kept = np.zeros(max(n, 1), np.int32)
+        nk = C.c_int()
+        h = C.c_void_p()
+        self._check(self.L.cvo_cloud_upload_voxel(self.ctx, n, _fptr(xyz), _fptr(feat), _fptr(label), _fptr(geo),
+                                                  self._voxel_size(voxel_size), C.byref(h),
+                                                  kept.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nk)))
+        d = DeviceCloud.__new__(DeviceCloud)
+        d.gpu, d.n, d._keep, d.handle = self, nk.value, None, h
+        d.kept = kept[:nk.value].copy()
+        return d
+
+    def debug_voxel_stats(self):
+        """cvo_debug_voxel_stats of the last selection on the device: a dict of capacity, occupied, probes_total,
+        probe_longest, entered (all 0 after a selection on the host)."""
+        v = [C.c_ulonglong() for _ in range(5)]
+        self._check(self.L.cvo_debug_voxel_stats(self.ctx, *[C.byref(x) for x in v]))
+        return dict(zip(("capacity", "occupied", "probes_total", "probe_longest", "entered"), [x.value for x in v]))
 
     def upload_many(self, clouds, threads=None):
         """Uploads a list of clouds with cvo_cloud_upload_many: a pool of host threads inside the library, each cloud

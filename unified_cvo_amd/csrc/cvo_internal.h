@@ -1,5 +1,5 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_voxel.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
 // pair, graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -193,6 +193,12 @@ struct cvo_ctx {
   std::vector<int> last_xorder;
   bool queue_open = false;  // a cvo_batch_queue owns the workspace: the other align / evaluation calls are refused meanwhile
   cvo_batch_queue* queue = nullptr;  // ... that queue (cvo_ctx_destroy releases its device side, see queue_release)
+  // voxel selection (cvo_voxel.hip): one growable device region - coordinates, table, per-point slots, block counts, kept
+  // indices, VoxelCtl - used on upload_stream under upload_mutex; the last selection's table size and counters
+  char* vox_scratch = nullptr;
+  size_t vox_scratch_bytes = 0;
+  unsigned long long vox_capacity = 0;  // 0: the last selection ran on the host (or none has run)
+  VoxelCtl vox_last{};
   double clock_ms_per_tick = 0.0;  // s_memrealtime, calibrated on first use (cvo_debug_kernel_clock)
 };
 

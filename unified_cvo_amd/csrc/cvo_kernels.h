@@ -63,3 +63,4 @@
 #include "cvo_k_debug.h"
 #include "cvo_k_cloud.h"
 #include "cvo_k_irls.h"
+#include "cvo_k_voxel.h"

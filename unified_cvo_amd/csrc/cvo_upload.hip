@@ -111,6 +111,8 @@ struct HostCloud {
   const char* feat;  size_t feat_stride;   // FD floats, or NULL
   const char* label; size_t label_stride;  // NC floats, or NULL
   const char* geo;   size_t geo_stride;    // 2 floats, or NULL
+  const int* rows = nullptr;               // optional: point i of the cloud is row rows[i] of the arrays (cvo_cloud_upload_voxel)
+  size_t row(int i) const { return rows ? (size_t)rows[i] : (size_t)i; }
 };
 
 // A cloud whose spatial ordering runs on the device (k_kd_order): staged and copied, not yet ordered.  The staging
@@ -134,7 +136,7 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
   // CVO_NO_SORT, CVO_ORDER=host).
   bool finite = true;
   for (int i = 0; i < n && finite; i++) {
-    const float* p = reinterpret_cast<const float*>(h.xyz + (size_t)i * h.xyz_stride);
+    const float* p = reinterpret_cast<const float*>(h.xyz + h.row(i) * h.xyz_stride);
     finite = std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
   }
   const bool device_order = n >= 8 && n <= KD_MAX_POINTS && finite && !ctx->opt.no_sort && ctx->opt.order == CloudOrder::Device;
@@ -144,7 +146,7 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
     lid_host.resize((size_t)n);
     bool onehot = true;
     for (int i = 0; i < n && onehot; i++) {
-      const float* l = reinterpret_cast<const float*>(h.label + (size_t)i * h.label_stride);
+      const float* l = reinterpret_cast<const float*>(h.label + h.row(i) * h.label_stride);
       int hot = -1, ones = 0;
       for (int c = 0; c < NC; c++) {
         if (l[c] == 1.0f) {
@@ -186,7 +188,7 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
   float* x4 = reinterpret_cast<float*>(&stage[o_x4]);
   double sx = 0, sy = 0, sz = 0, r2max = 0;
   for (int i = 0; i < n; i++) {
-    const float* p = reinterpret_cast<const float*>(h.xyz + (size_t)i * h.xyz_stride);
+    const float* p = reinterpret_cast<const float*>(h.xyz + h.row(i) * h.xyz_stride);
     x4[4 * (size_t)i] = p[0];
     x4[4 * (size_t)i + 1] = p[1];
     x4[4 * (size_t)i + 2] = p[2];
@@ -207,15 +209,15 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
   if (device_order) {
     if (h.feat) {
       float* f = reinterpret_cast<float*>(&stage[o_rawf]);
-      for (int i = 0; i < n; i++) std::memcpy(&f[FD * (size_t)i], h.feat + (size_t)i * h.feat_stride, sizeof(float) * FD);
+      for (int i = 0; i < n; i++) std::memcpy(&f[FD * (size_t)i], h.feat + h.row(i) * h.feat_stride, sizeof(float) * FD);
     }
     if (h.label) {
       float* l = reinterpret_cast<float*>(&stage[o_rawl]);
-      for (int i = 0; i < n; i++) std::memcpy(&l[NC * (size_t)i], h.label + (size_t)i * h.label_stride, sizeof(float) * NC);
+      for (int i = 0; i < n; i++) std::memcpy(&l[NC * (size_t)i], h.label + h.row(i) * h.label_stride, sizeof(float) * NC);
     }
     if (h.geo) {
       float* g = reinterpret_cast<float*>(&stage[o_rawg]);
-      for (int i = 0; i < n; i++) std::memcpy(&g[2 * (size_t)i], h.geo + (size_t)i * h.geo_stride, sizeof(float) * 2);
+      for (int i = 0; i < n; i++) std::memcpy(&g[2 * (size_t)i], h.geo + h.row(i) * h.geo_stride, sizeof(float) * 2);
     }
     if (has_lid) std::memcpy(&stage[o_rawlid], lid_host.data(), sizeof(int) * (size_t)n);
   } else {
@@ -225,15 +227,15 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
     // point order[r]): the kernels index them by sorted position, like the coordinates they gather per candidate
     if (h.feat) {
       float* f8 = reinterpret_cast<float*>(&stage[o_feat]);
-      for (int r = 0; r < n; r++) std::memcpy(&f8[FD_PAD * (size_t)r], h.feat + (size_t)order[r] * h.feat_stride, sizeof(float) * FD);
+      for (int r = 0; r < n; r++) std::memcpy(&f8[FD_PAD * (size_t)r], h.feat + h.row(order[r]) * h.feat_stride, sizeof(float) * FD);
     }
     if (h.label) {
       float* l20 = reinterpret_cast<float*>(&stage[o_label]);
-      for (int r = 0; r < n; r++) std::memcpy(&l20[NC_PAD * (size_t)r], h.label + (size_t)order[r] * h.label_stride, sizeof(float) * NC);
+      for (int r = 0; r < n; r++) std::memcpy(&l20[NC_PAD * (size_t)r], h.label + h.row(order[r]) * h.label_stride, sizeof(float) * NC);
     }
     if (h.geo) {
       float* g2 = reinterpret_cast<float*>(&stage[o_geo]);
-      for (int r = 0; r < n; r++) std::memcpy(&g2[2 * (size_t)r], h.geo + (size_t)order[r] * h.geo_stride, sizeof(float) * 2);
+      for (int r = 0; r < n; r++) std::memcpy(&g2[2 * (size_t)r], h.geo + h.row(order[r]) * h.geo_stride, sizeof(float) * 2);
     }
     if (has_lid) {
       int* li = reinterpret_cast<int*>(&stage[o_lid]);

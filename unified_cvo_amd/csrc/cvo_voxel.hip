@@ -1,0 +1,214 @@
+// cvo_voxel.hip -- voxel-grid downsampling (cvo::VoxelMap): cvo_voxel_select (kernels of cvo_k_voxel.h on the upload stream),
+// cvo_voxel_select_host (the same contract on one CPU thread), cvo_cloud_upload_voxel (selection, then the ordinary upload
+// path over the survivors' rows), cvo_debug_voxel_stats.
+// A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.  Shared declarations: cvo_internal.h.
+namespace {
+
+// The refusals of the contract, with the text cvo_last_error returns: voxel size, non-finite coordinates, |k| >= 2^20.
+int voxel_validate(int n, const float* xyz, float s, std::string* msg) {
+  if (!std::isfinite(s) || !(s > 0.f)) {
+    if (msg) *msg = "voxel size must be finite and > 0, got " + std::to_string(s);
+    return CVO_E_INVALID;
+  }
+  for (int i = 0; i < n; i++) {
+    unsigned long long key;
+    const unsigned bad = vox_key(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], s, &key);
+    if (!bad) continue;
+    if (msg) {
+      char buf[256];
+      if (bad & VOX_BAD_FINITE) {
+        snprintf(buf, sizeof buf, "point %d has a non-finite coordinate", i);
+      } else {
+        const int axis = bad & VOX_BAD_X ? 0 : (bad & VOX_BAD_Y ? 1 : 2);
+        snprintf(buf, sizeof buf, "point %d: %c = %g is voxel %.0f of side %g; the grid extends to |k| < %d per axis (+-%g)", i, "xyz"[axis],
+                 (double)xyz[3 * (size_t)i + axis], (double)rintf(xyz[3 * (size_t)i + axis] / s), (double)s, VOX_KMAX,
+                 (double)s * VOX_KMAX);
+      }
+      *msg = buf;
+    }
+    return CVO_E_INVALID;
+  }
+  return CVO_OK;
+}
+
+// One thread, one pass: points arrive in ascending index, so the point that takes a slot is its voxel's lowest.
+void voxel_select_cpu(int n, const float* xyz, float s, std::vector<int>& kept) {
+  kept.clear();
+  size_t cap = 64;
+  while (cap < 2 * (size_t)n) cap *= 2;
+  std::vector<unsigned long long> keys(cap, VOX_EMPTY);
+  for (int i = 0; i < n; i++) {
+    unsigned long long key = 0;
+    (void)vox_key(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], s, &key);
+    size_t g = (size_t)vox_mix(key) & (cap - 1);
+    while (keys[g] != VOX_EMPTY && keys[g] != key) g = (g + 1) & (cap - 1);
+    if (keys[g] == VOX_EMPTY) {
+      keys[g] = key;
+      kept.push_back(i);
+    }
+  }
+}
+
+// The kernels, on upload_stream (the caller holds upload_mutex).  xyz: n x 3 host floats, n >= 1, s validated.
+int voxel_select_device(cvo_ctx* ctx, int n, const float* xyz, float s, std::vector<int>& kept) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  size_t cap = 1024;
+  while (cap < 2 * (size_t)n) cap *= 2;
+  const int nb = (n + VOX_THREADS - 1) / VOX_THREADS;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off = align_up(off + bytes, 256);
+    return o;
+  };
+  const size_t o_ctl = take(sizeof(VoxelCtl)), o_stats = take(sizeof(VoxelBlockStats) * VOX_INSERT_BLOCKS), o_keys = take(sizeof(unsigned long long) * cap), o_first = take(sizeof(unsigned) * cap),
+               o_xyz = take(sizeof(float) * 3 * (size_t)n), o_slot = take(sizeof(unsigned) * (size_t)n),
+               o_blocks = take(sizeof(unsigned) * (size_t)nb), o_kept = take(sizeof(int) * (size_t)n);
+  if (off > ctx->vox_scratch_bytes) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
+    if (ctx->vox_scratch) (void)hipFree(ctx->vox_scratch);
+    ctx->vox_scratch = nullptr;
+    ctx->vox_scratch_bytes = 0;
+    const hipError_t e = hipMalloc(&ctx->vox_scratch, off);
+    if (e != hipSuccess) return fail(ctx, CVO_E_NOMEM, std::string("voxel scratch hipMalloc: ") + hipGetErrorString(e));
+    ctx->vox_scratch_bytes = off;
+  }
+  char* b = ctx->vox_scratch;
+  VoxelCtl* ctl = (VoxelCtl*)(b + o_ctl);
+  unsigned long long* keys = (unsigned long long*)(b + o_keys);
+  unsigned* first = (unsigned*)(b + o_first);
+  float* d_xyz = (float*)(b + o_xyz);
+  unsigned* slot = (unsigned*)(b + o_slot);
+  unsigned* blocks = (unsigned*)(b + o_blocks);
+  int* d_kept = (int*)(b + o_kept);
+  VoxelBlockStats* stats = (VoxelBlockStats*)(b + o_stats);
+  hipStream_t st = ctx->upload_stream;
+  const unsigned mask = (unsigned)(cap - 1);
+  HIP_TRY(ctx, hipMemsetAsync(ctl, 0, sizeof(VoxelCtl), st));
+  HIP_TRY(ctx, hipMemsetAsync(keys, 0xFF, o_xyz - o_keys, st));  // keys and first[] are adjacent: one fill
+  HIP_TRY(ctx, hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+  const int grid = std::min(nb, VOX_INSERT_BLOCKS);
+  if (ctx->opt.voxel_prepass)
+    hipLaunchKernelGGL(k_voxel_insert<true>, dim3(grid), dim3(VOX_THREADS), 0, st, n, (const float*)d_xyz, s, mask, keys, first, slot, ctl, stats);
+  else
+    hipLaunchKernelGGL(k_voxel_insert<false>, dim3(grid), dim3(VOX_THREADS), 0, st, n, (const float*)d_xyz, s, mask, keys, first, slot, ctl, stats);
+  hipLaunchKernelGGL(k_voxel_flag, dim3(nb), dim3(VOX_THREADS), 0, st, n, mask, (const unsigned*)first, (const unsigned*)slot, blocks);
+  hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, st, nb, blocks, ctl, grid, (const VoxelBlockStats*)stats);
+  hipLaunchKernelGGL(k_voxel_compact, dim3(nb), dim3(VOX_THREADS), 0, st, n, mask, (const unsigned*)first, (const unsigned*)slot,
+                     (const unsigned*)blocks, d_kept);
+  HIP_TRY(ctx, hipGetLastError());
+  VoxelCtl h{};
+  HIP_TRY(ctx, hipMemcpyAsync(&h, ctl, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (h.status) {
+    std::string msg;
+    (void)voxel_validate(n, xyz, s, &msg);
+    return fail(ctx, CVO_E_INVALID, "voxel selection: " + msg);
+  }
+  if (h.n_kept > (unsigned)n) return fail(ctx, CVO_E_HIP, "voxel selection: the device kept more points than it was given");
+  kept.resize(h.n_kept);
+  if (h.n_kept) {
+    HIP_TRY(ctx, hipMemcpyAsync(kept.data(), d_kept, sizeof(int) * (size_t)h.n_kept, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+  }
+  ctx->vox_capacity = cap;
+  ctx->vox_last = h;
+  return CVO_OK;
+}
+
+// Below this many points the CPU twin is the faster route (scripts/voxel_probe.py --sizes 2000 10000 50000: 0.02 ms against
+// the kernels' flat 0.09 ms of launches, copies and two synchronisations at 2000 points, 0.12 against 0.09 at 10 000): the
+// default route of small frames.  VOXEL_HOST=0 / 1 forces one route for every size.
+constexpr int VOX_HOST_BELOW = 4096;
+
+// Argument checks + the route the context's switches choose.  The caller holds upload_mutex.
+int voxel_select(cvo_ctx* ctx, const char* who, int n, const float* xyz, float s, std::vector<int>& kept) {
+  if (n > VOX_MAX_POINTS) return fail(ctx, CVO_E_UNSUPPORTED, std::string(who) + ": more than 2^24 points");
+  std::string msg;
+  if (voxel_validate(0, nullptr, s, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": " + msg);
+  kept.clear();
+  if (n == 0 || ctx->opt.voxel_host > 0 || (ctx->opt.voxel_host < 0 && n < VOX_HOST_BELOW)) {
+    if (voxel_validate(n, xyz, s, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": " + msg);
+    voxel_select_cpu(n, xyz, s, kept);
+    ctx->vox_capacity = 0;  // (no table: cvo_debug_voxel_stats reads zeros)
+    ctx->vox_last = VoxelCtl{};
+    return CVO_OK;
+  }
+  return voxel_select_device(ctx, n, xyz, s, kept);
+}
+
+}  // namespace
+
+extern "C" {
+
+int cvo_voxel_select_host(int n, const float* xyz, float voxel_size, int* kept, int* n_kept) {
+  if (n < 0 || (n > 0 && (!xyz || !kept)) || !n_kept) return CVO_E_INVALID;
+  if (n > VOX_MAX_POINTS) return CVO_E_UNSUPPORTED;
+  try {
+    const int rc = voxel_validate(n, xyz, voxel_size, nullptr);
+    if (rc != CVO_OK) return rc;
+    std::vector<int> k;
+    voxel_select_cpu(n, xyz, voxel_size, k);
+    if (!k.empty()) std::memcpy(kept, k.data(), sizeof(int) * k.size());
+    *n_kept = (int)k.size();
+  } catch (const std::exception&) {
+    return CVO_E_NOMEM;
+  }
+  return CVO_OK;
+}
+
+int cvo_voxel_select(cvo_ctx* ctx, int n, const float* xyz, float voxel_size, int* kept, int* n_kept) {
+  if (!ctx || n < 0 || (n > 0 && (!xyz || !kept)) || !n_kept) return fail(ctx, CVO_E_INVALID, "cvo_voxel_select: bad argument");
+  try {
+    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+    std::vector<int> k;
+    const int rc = voxel_select(ctx, "cvo_voxel_select", n, xyz, voxel_size, k);
+    if (rc != CVO_OK) return rc;
+    if (!k.empty()) std::memcpy(kept, k.data(), sizeof(int) * k.size());
+    *n_kept = (int)k.size();
+  } catch (const std::exception& e) {
+    return fail(ctx, CVO_E_NOMEM, std::string("cvo_voxel_select: ") + e.what());
+  }
+  return CVO_OK;
+}
+
+// Coordinates go to the device alone (12 bytes per point); the survivors' rows are gathered on the host straight into the
+// staging buffer of the ordinary upload (HostCloud::rows), so the cloud is the one cvo_cloud_upload makes of those rows.
+int cvo_cloud_upload_voxel(cvo_ctx* ctx, int n, const float* xyz, const float* feat, const float* label, const float* geotype,
+                           float voxel_size, cvo_cloud** out, int* kept, int* n_kept) {
+  if (!ctx || !out || n < 0 || (n > 0 && !xyz)) return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_voxel: bad argument");
+  try {
+    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+    std::vector<int> k;
+    int rc = voxel_select(ctx, "cvo_cloud_upload_voxel", n, xyz, voxel_size, k);
+    if (rc != CVO_OK) return rc;
+    HostCloud h{(int)k.size(), (const char*)xyz, 12, (const char*)feat, sizeof(float) * FD, (const char*)label, sizeof(float) * NC,
+                (const char*)geotype, 8};
+    h.rows = k.data();
+    std::vector<StagedCloud> one(1);
+    rc = upload_host_cloud(ctx, h, ctx->upload_stream, &one[0]);
+    if (rc != CVO_OK) return rc;
+    rc = finish_uploads(ctx, one);
+    if (rc != CVO_OK) return rc;
+    *out = one[0].c;
+    if (kept && !k.empty()) std::memcpy(kept, k.data(), sizeof(int) * k.size());
+    if (n_kept) *n_kept = (int)k.size();
+  } catch (const std::exception& e) {
+    return fail(ctx, CVO_E_NOMEM, std::string("cvo_cloud_upload_voxel: ") + e.what());
+  }
+  return CVO_OK;
+}
+
+int cvo_debug_voxel_stats(cvo_ctx* ctx, unsigned long long* capacity, unsigned long long* occupied, unsigned long long* probes_total,
+                          unsigned long long* probe_longest, unsigned long long* entered) {
+  if (!ctx) return CVO_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  if (capacity) *capacity = ctx->vox_capacity;
+  if (occupied) *occupied = ctx->vox_last.occupied;
+  if (probes_total) *probes_total = ctx->vox_last.probes;
+  if (probe_longest) *probe_longest = ctx->vox_last.longest;
+  if (entered) *entered = ctx->vox_last.entered;
+  return CVO_OK;
+}
+
+}  // extern "C"
