@@ -15,7 +15,9 @@
 #include "cvo/CvoFrame.hpp"
 #include "cvo/CvoParams.hpp"
 #include "utils/CvoPoint.hpp"
+#include "utils/Calibration.hpp"
 #include "utils/CvoPointCloud.hpp"
+#include "utils/ImageRGBD.hpp"
 #include "utils/data_type.hpp"
 
 namespace cvo {
@@ -92,6 +94,20 @@ class CvoGPU {
   // survivors only (a loop over cvo_cloud_upload_voxel).  Refusals (non-finite coordinates, |k| >= 2^20) throw.
   CvoPointCloud voxel_downsample(const CvoPointCloud& cloud, float voxel_size = 0.f, std::vector<int>* kept = nullptr) const;
   std::unique_ptr<ResidentClouds> upload_clouds_voxel(const std::vector<const CvoPointCloud*>& clouds, float voxel_size = 0.f) const;
+  // New: the RGB-D front end on the device (cvo_rgbd_points / cvo_cloud_upload_rgbd, include/cvo_hip.h).  rgbd_points is
+  // CvoPointCloud(raw_image, calib, method) with the selector and the depth test run by the kernels.  upload_rgbd is the
+  // multi-frame RGB-D drivers' per-frame block (main_multi_frame_irls_tum.cpp:279-335) in one call: FULL and DSO_EDGES
+  // candidates, voxel grids of side leaf (surface) and leaf / edge_divisor (edge; 4 TUM, 5 Tartan / KITTI, 10 covis), the
+  // survivors as colour points of type EDGE / SURFACE, edge first, resident (size() == 1).  leaf <= 0 takes
+  // params.multiframe_downsample_voxel_size.  pixel / is_edge (optional): v * cols + u and the set of every point.
+  // Defined in host/cvo_rgbd.cpp for DepthType uint16_t / float.
+  template <typename DepthType>
+  CvoPointCloud rgbd_points(const ImageRGBD<DepthType>& raw_image, const Calibration& calib, CvoPointCloud::PointSelectionMethod method,
+                            std::vector<int>* pixel = nullptr) const;
+  template <typename DepthType>
+  std::unique_ptr<ResidentClouds> upload_rgbd(const ImageRGBD<DepthType>& raw_image, const Calibration& calib, float leaf = 0.f,
+                                              float edge_divisor = 4.f, std::vector<int>* pixel = nullptr,
+                                              std::vector<unsigned char>* is_edge = nullptr) const;
   // New: multi-frame registration over resident clouds (cvo_multiframe_align as it is): poses 12 doubles per cloud (3x4
   // row-major, updated in place), edges pairs of indices into `clouds`.
   int align(const ResidentClouds& clouds, std::vector<double>& poses, const std::vector<bool>& frames_to_hold_const,

@@ -1,5 +1,6 @@
 // Host point-cloud container: the accessor subset of upstream utils/CvoPointCloud.hpp:126-188 that the
-// align() path and its drivers use.  Image / LiDAR constructors are out of scope.
+// align() path and its drivers use, and the RGB-D image constructor (FULL / DSO_EDGES).  The stereo and LiDAR
+// constructors are out of scope.
 #pragma once
 #include <string>
 #include <vector>
@@ -15,9 +16,15 @@
 
 namespace cvo {
 
+class Calibration;
+template <typename DepthType>
+class ImageRGBD;
+
 class CvoPointCloud {
  public:
   enum GeometryType { EDGE = 0, SURFACE = 1 };
+  // upstream CvoPointCloud.hpp:39-49, same names and values
+  enum PointSelectionMethod { CV_FAST, RANDOM, DSO_EDGES, DSO_EDGES_WITH_RANDOM, LIDAR_EDGES, CANNY_EDGES, EDGES_ONLY, LOAM, FULL };
 
   CvoPointCloud();
   CvoPointCloud(int feature_dimensions, int num_classes);
@@ -29,6 +36,15 @@ class CvoPointCloud {
   explicit CvoPointCloud(const std::string& filename);
   // upstream CvoPointCloud.cpp:1157-1199: "N F C" then per point "u v idepth f_1..f_F x y z l_1..l_C"; 0 / -1
   int read_cvo_pointcloud_from_file(const std::string& filename);
+
+  // upstream CvoPointCloud.cpp:459-553 for DepthType uint16_t / float (utils/ImageRGBD.hpp, utils/Calibration.hpp) and
+  // pt_selection_method FULL or DSO_EDGES, on the host (cvo_rgbd_points_host, include/cvo_hip.h, states the contract: F =
+  // channels + 2, point order, the gradient-index quirk); every other method throws std::invalid_argument (OpenCV
+  // detectors and rand() are not restated).  The image is taken as it is: no denoising (utils/RawImage.hpp).
+  // pixel (optional): v * cols + u of every point.  Defined in host/cvo_rgbd.cpp.
+  template <typename DepthType>
+  CvoPointCloud(const ImageRGBD<DepthType>& raw_image, const Calibration& calib, PointSelectionMethod pt_selection_method,
+                std::vector<int>* pixel = nullptr);
 
   static CvoPointCloud from_xyz(const float* xyz, int n);                                // type (1,0), F = 0
   static CvoPointCloud from_xyzrgb(const float* xyz, const unsigned char* rgb, int n);   // type (0,1), F = 5

@@ -207,6 +207,57 @@ int cvo_voxel_select_host(int n, const float* xyz, float voxel_size, int* kept, 
 int cvo_cloud_upload_voxel(cvo_ctx* ctx, int n, const float* xyz, const float* feat, const float* label,
                            const float* geotype, float voxel_size, cvo_cloud** out,
                            int* kept /* n ints or NULL */, int* n_kept /* or NULL */);
+/* ---- RGB-D front end: replaces CvoPointCloud(ImageRGBD<T>, Calibration, PointSelectionMethod) (CvoPointCloud.cpp:459-553,
+ * CvoPixelSelector.cpp:51-474, RawImage.cpp:55-82) and the per-frame block of the multi-frame RGB-D drivers
+ * (main_multi_frame_irls_tum.cpp:279-335) ----
+ * A frame: the colour image AS RawImage HOLDS IT AFTER ITS DENOISING (cv::fastNlMeansDenoising is not part of this
+ * library), rows x cols x channels bytes, BGR order for 3 channels; optionally the 8-bit gray plane the gradient is taken
+ * of (NULL: 1-channel images as they are, 3-channel ones through OpenCV 3's 8-bit COLOR_BGR2GRAY,
+ * (1868 B + 9617 G + 4899 R + 8192) >> 14; OpenCV 4 differs by one level at rare pixels, so parity with a given OpenCV
+ * needs the caller's plane); the depth image, uint16_t or float; the calibration; optionally num_classes floats per pixel. */
+#define CVO_DEPTH_U16 0
+#define CVO_DEPTH_F32 1
+/* cvo::CvoPointCloud::PointSelectionMethod (CvoPointCloud.hpp:39-49), same values; the two that are built */
+#define CVO_SELECT_DSO_EDGES 2
+#define CVO_SELECT_FULL 8
+typedef struct cvo_rgbd_frame_t {
+  int rows, cols, channels;    /* channels: 1 or 3 */
+  const uint8_t* image;        /* rows x cols x channels */
+  const uint8_t* gray;         /* rows x cols, or NULL */
+  const void* depth;           /* rows x cols of depth_type */
+  int depth_type;              /* CVO_DEPTH_U16 / CVO_DEPTH_F32 */
+  float fx, fy, cx, cy;        /* Calibration::intrinsic() */
+  float scaling_factor;        /* Calibration::scaling_factor(): z = depth / scaling_factor */
+  int num_classes;             /* 0 = no semantics */
+  const float* semantic;       /* rows x cols x num_classes, or NULL */
+} cvo_rgbd_frame_t;
+/* The points of the reference constructor, in its order.  FULL: every pixel, COLUMN-major (u outer, v inner), geometric type
+ * (0.5, 0.5).  DSO_EDGES: the pixels of dso_select_pixels(num_want = 10000) - per 32 x 32 block the 0.5 quantile of
+ * int(sqrtf(g2)) + 7, smoothed 3 x 3 and squared, read at (x >> 5) + (y >> 5) * (cols / 32) literally (aliasing when cols
+ * or rows is no multiple of 32); per pot x pot cell the first pixel with the largest g2 above it; potential schedule 3, then
+ * 4 .. 7 while more than 10 000, then once 3 + times - 2 if fewer than 6666 - type (0.9, 0.1).  A pixel is kept iff
+ * depth != 0 && !isnan(depth), and - with semantics - its first-maximum class is not 10.  z = depth / scaling_factor,
+ * x = ((u - cx) z) / fx, y = ((v - cy) z) / fy in float.  pixel[i] = v * cols + u of point i (room for
+ * rows x cols ints: no method yields more); the row outputs may be NULL: xyz n x 3, feat n x (channels + 2) - the channels
+ * / 255.0, then gradient_[v cols + u] / 500.0 + 0.5 and gradient_[v cols + u + 1] / 500.0 + 0.5, the reference's indexing of
+ * its interleaved (dx, dy) array by the PIXEL index -, label n x num_classes, geotype n x 2.
+ * CVO_E_INVALID, nothing written: rows / cols < 1, channels not 1 or 3, a missing pointer, fx / fy / scaling_factor not
+ * finite or <= 0.  CVO_E_UNSUPPORTED: the other selection methods (OpenCV detectors, rand()), more than 2^24 pixels, an
+ * image shape whose literal threshold index leaves the reference's allocation.  Images under 32 pixels on a side are
+ * valid (no whole block: every threshold is zero).  Runs on the upload stream like a voxel selection; switch RGBD_HOST=1 / 0:
+ * the CPU twin / the kernels for every size (unset: frames under 32768 pixels take the CPU twin). */
+int cvo_rgbd_points(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat,
+                    float* label, float* geotype);
+int cvo_rgbd_points_host(const cvo_rgbd_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat,
+                         float* label, float* geotype);   /* CPU twin, no context */
+/* The drivers' recipe in one call: the DSO_EDGES points through a voxel grid of side leaf / edge_divisor, the FULL points
+ * through one of side leaf (the cvo_voxel_select contract and its refusals); every survivor as export_to_pcd<PointXYZRGB> and
+ * the (XYZRGB, GeometryType) constructor leave it - F = 5: the first three features through min(255, int(f * 255)) and back
+ * over 255.0 (the identity on the colour bytes), 0, 0; type EDGE (1, 0) / SURFACE (0, 1); no labels -, edge rows first.  The cloud
+ * is the one cvo_cloud_upload makes of those rows.  pixel / is_edge (optional, room for 2 x rows x cols
+ * entries): pixel index and set of every point; *n their number.  leaf, edge_divisor: finite and > 0. */
+int cvo_cloud_upload_rgbd(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, float leaf, float edge_divisor, cvo_cloud** out,
+                          int* pixel, unsigned char* is_edge, int* n);
 int cvo_cloud_size(const cvo_cloud* c);
 void cvo_cloud_free(cvo_cloud* c);
 

@@ -82,6 +82,13 @@ int cvo_debug_irls_normal(cvo_ctx* ctx, const cvo_cloud* frame1, const cvo_cloud
  * (VOXEL_HOST=1, or fewer than 4096 points by default) or of an empty cloud.  Any pointer may be NULL. */
 int cvo_debug_voxel_stats(cvo_ctx* ctx, unsigned long long* capacity, unsigned long long* occupied,
                           unsigned long long* probes_total, unsigned long long* probe_longest, unsigned long long* entered);
+/* The context's last cvo_rgbd_points / cvo_cloud_upload_rgbd: the potentials the selector's schedule tried (*n_tried <= 6 of
+ * them) and the pixels selected at each; pixels of the standing selection, how many of them became points (depth, class),
+ * the FULL pass's points, the frame's pixels with a depth (FULL passes only), and whether the kernels ran (0: CPU twin).
+ * Parts a call did not compute are 0.  Any pointer may be NULL. */
+int cvo_debug_rgbd_stats(cvo_ctx* ctx, int* n_tried, int* potentials /* 8 */, int* counts /* 8 */,
+                         unsigned long long* edge_selected, unsigned long long* edge_points,
+                         unsigned long long* surface_points, unsigned long long* with_depth, int* on_device);
 
 #ifdef __cplusplus
 }

@@ -159,6 +159,28 @@ class cvo_batch_result_t(C.Structure):
     ]
 
 
+class cvo_rgbd_frame_t(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int),
+        ("cols", C.c_int),
+        ("channels", C.c_int),
+        ("image", C.c_void_p),
+        ("gray", C.c_void_p),
+        ("depth", C.c_void_p),
+        ("depth_type", C.c_int),
+        ("fx", C.c_float),
+        ("fy", C.c_float),
+        ("cx", C.c_float),
+        ("cy", C.c_float),
+        ("scaling_factor", C.c_float),
+        ("num_classes", C.c_int),
+        ("semantic", C.c_void_p),
+    ]
+
+
+CVO_DEPTH_U16, CVO_DEPTH_F32 = 0, 1
+CVO_SELECT_DSO_EDGES, CVO_SELECT_FULL = 2, 8
+
 # every symbol include/cvo_hip.h declares (tests/test_capi_symbols.py checks the two lists agree)
 EXPORTED = [
     "cvo_params_default", "cvo_ctx_create", "cvo_ctx_destroy", "cvo_last_error", "cvo_ctx_stream",
@@ -174,6 +196,7 @@ EXPORTED = [
     "cvo_inner_product_batch", "cvo_function_angle_batch", "cvo_debug_last_score_batch",
     "cvo_multiframe_align", "cvo_debug_irls_normal",
     "cvo_voxel_select", "cvo_voxel_select_host", "cvo_cloud_upload_voxel", "cvo_debug_voxel_stats",
+    "cvo_rgbd_points", "cvo_rgbd_points_host", "cvo_cloud_upload_rgbd", "cvo_debug_rgbd_stats",
 ]
 
 _libs = {}
@@ -262,6 +285,11 @@ def lib(path=None):
     L.cvo_voxel_select_host.argtypes = [ip, fp, C.c_float, ipp, ipp]
     L.cvo_cloud_upload_voxel.argtypes = [vp, ip, fp, fp, fp, fp, C.c_float, C.POINTER(vp), ipp, ipp]
     L.cvo_debug_voxel_stats.argtypes = [vp] + [C.POINTER(C.c_ulonglong)] * 5
+    fr = C.POINTER(cvo_rgbd_frame_t)
+    L.cvo_rgbd_points.argtypes = [vp, fr, ip, ipp, ipp, fp, fp, fp, fp]
+    L.cvo_rgbd_points_host.argtypes = [fr, ip, ipp, ipp, fp, fp, fp, fp]
+    L.cvo_cloud_upload_rgbd.argtypes = [vp, fr, C.c_float, C.c_float, C.POINTER(vp), ipp, C.POINTER(C.c_ubyte), ipp]
+    L.cvo_debug_rgbd_stats.argtypes = [vp, ipp, ipp, ipp] + [C.POINTER(C.c_ulonglong)] * 4 + [ipp]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

@@ -192,6 +192,67 @@ class CvoPointCloud:
         return xyz, feat, label, geo
 
 
+class RGBDFrame:
+    """What cvo::ImageRGBD<DepthType> and cvo::Calibration hold of one RGB-D frame (cvo_rgbd_frame_t): `image` (rows, cols)
+    or (rows, cols, 3) uint8 in BGR order, as RawImage holds it AFTER its denoising; `depth` (rows, cols) uint16 or float32;
+    the intrinsics and the depth scaling factor; optionally the 8-bit `gray` plane the gradient is taken of (overrides the
+    BGR -> gray formula) and `semantic` (rows, cols, num_classes) float32."""
+
+    def __init__(self, image, depth, fx, fy, cx, cy, scaling_factor, gray=None, semantic=None):
+        self.image = np.ascontiguousarray(image, np.uint8)
+        if self.image.ndim == 3 and self.image.shape[2] == 1:
+            self.image = np.ascontiguousarray(self.image[..., 0])
+        self.rows, self.cols = self.image.shape[:2]
+        self.channels = 1 if self.image.ndim == 2 else self.image.shape[2]
+        depth = np.asarray(depth)
+        self.depth = np.ascontiguousarray(depth, np.uint16 if depth.dtype == np.uint16 else np.float32)
+        if self.depth.shape != (self.rows, self.cols):
+            raise ValueError(f"depth is {self.depth.shape}, the image {self.rows} x {self.cols}")
+        self.fx, self.fy, self.cx, self.cy, self.scaling_factor = (float(v) for v in (fx, fy, cx, cy, scaling_factor))
+        self.gray = None if gray is None else np.ascontiguousarray(gray, np.uint8).reshape(self.rows, self.cols)
+        self.semantic = None if semantic is None else np.ascontiguousarray(semantic, np.float32).reshape(self.rows, self.cols, -1)
+        self.num_classes = 0 if self.semantic is None else self.semantic.shape[2]
+
+    def c_struct(self):
+        """cvo_rgbd_frame_t over this frame's arrays (which must outlive it)."""
+        ptr = lambda a: None if a is None else a.ctypes.data
+        return _capi.cvo_rgbd_frame_t(self.rows, self.cols, self.channels, ptr(self.image), ptr(self.gray), ptr(self.depth),
+                                      _capi.CVO_DEPTH_U16 if self.depth.dtype == np.uint16 else _capi.CVO_DEPTH_F32,
+                                      self.fx, self.fy, self.cx, self.cy, self.scaling_factor, self.num_classes, ptr(self.semantic))
+
+
+FULL, DSO_EDGES = _capi.CVO_SELECT_FULL, _capi.CVO_SELECT_DSO_EDGES  # cvo::CvoPointCloud::PointSelectionMethod
+
+
+def _rgbd_points(call, frame, method):
+    """Shared by CvoGPU.rgbd_points and rgbd_points_host: runs `call(frame struct, method, outputs...)` -> (rc, cloud)."""
+    n_max = max(frame.rows * frame.cols, 1)
+    F, nc = frame.channels + 2, frame.num_classes
+    pixel = np.zeros(n_max, np.int32)
+    xyz, feat, geo = np.zeros((n_max, 3), np.float32), np.zeros((n_max, F), np.float32), np.zeros((n_max, 2), np.float32)
+    label = np.zeros((n_max, nc), np.float32) if nc else None
+    n = C.c_int()
+    fs = frame.c_struct()
+    rc = call(C.byref(fs), int(method), pixel.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n), _fptr(xyz), _fptr(feat), _fptr(label), _fptr(geo))
+    if rc != 0:
+        return rc, None
+    k = n.value
+    pc = CvoPointCloud.from_arrays(xyz[:k], feat[:k], None if label is None else label[:k], geo[:k])
+    pc.pixel = pixel[:k].copy()
+    return rc, pc
+
+
+def rgbd_points_host(frame, method):
+    """cvo_rgbd_points_host: the CPU twin of CvoGPU.rgbd_points, no context."""
+    L = _capi.lib()
+    rc, pc = _rgbd_points(L.cvo_rgbd_points_host, frame, method)
+    if rc != 0:
+        e = CvoError(f"error {rc}: cvo_rgbd_points_host refused the frame or the method")
+        e.code = rc
+        raise e
+    return pc
+
+
 class DeviceCloud:
     """A cloud resident in HBM (cvo_cloud*)."""
 
@@ -447,6 +508,40 @@ class CvoGPU:
         v = [C.c_ulonglong() for _ in range(5)]
         self._check(self.L.cvo_debug_voxel_stats(self.ctx, *[C.byref(x) for x in v]))
         return dict(zip(("capacity", "occupied", "probes_total", "probe_longest", "entered"), [x.value for x in v]))
+
+    def rgbd_points(self, frame, method):
+        """cvo_rgbd_points: CvoPointCloud(ImageRGBD, Calibration, method) for method FULL / DSO_EDGES - a CvoPointCloud with
+        F = channels + 2 and `.pixel`, the index v * cols + u of every point, in the reference's order."""
+        rc, pc = _rgbd_points(lambda *a: self.L.cvo_rgbd_points(self.ctx, *a), frame, method)
+        self._check(rc)
+        return pc
+
+    def upload_rgbd(self, frame, leaf=None, edge_divisor=4):
+        """cvo_cloud_upload_rgbd: the multi-frame drivers' per-frame block as one call - the resident cloud of the voxel-selected
+        edge points (grid leaf / edge_divisor, type (1, 0)) followed by the voxel-selected surface points (grid leaf, type
+        (0, 1)); `.pixel` and `.is_edge` per point.  leaf None: params.multiframe_downsample_voxel_size."""
+        cap = max(2 * frame.rows * frame.cols, 1)
+        pixel, is_edge = np.zeros(cap, np.int32), np.zeros(cap, np.uint8)
+        n = C.c_int()
+        h = C.c_void_p()
+        fs = frame.c_struct()
+        self._check(self.L.cvo_cloud_upload_rgbd(self.ctx, C.byref(fs), self._voxel_size(leaf), float(edge_divisor), C.byref(h),
+                                                 pixel.ctypes.data_as(C.POINTER(C.c_int)), is_edge.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                 C.byref(n)))
+        d = DeviceCloud.__new__(DeviceCloud)
+        d.gpu, d.n, d._keep, d.handle = self, n.value, None, h
+        d.pixel, d.is_edge = pixel[:n.value].copy(), is_edge[:n.value].astype(bool)
+        return d
+
+    def debug_rgbd_stats(self):
+        """cvo_debug_rgbd_stats of the last rgbd_points / upload_rgbd: potentials tried and the count at each, the standing
+        selection, the points of both sets, the pixels with a depth, whether the kernels ran."""
+        nt, pots, cnts, dev = C.c_int(), (C.c_int * 8)(), (C.c_int * 8)(), C.c_int()
+        v = [C.c_ulonglong() for _ in range(4)]
+        self._check(self.L.cvo_debug_rgbd_stats(self.ctx, C.byref(nt), pots, cnts, *[C.byref(x) for x in v], C.byref(dev)))
+        out = dict(zip(("edge_selected", "edge_points", "surface_points", "with_depth"), [x.value for x in v]))
+        out.update(potentials=list(pots[:nt.value]), counts=list(cnts[:nt.value]), on_device=bool(dev.value))
+        return out
 
     def upload_many(self, clouds, threads=None):
         """Uploads a list of clouds with cvo_cloud_upload_many: a pool of host threads inside the library, each cloud

@@ -13,12 +13,14 @@
 //   cvo_export.hip  association / ELL exports                          cvo_debug.hip   test and profiling hooks
 //   cvo_irls.hip    multi-frame align (the least-squares solve of CvoBatchIRLS)
 //   cvo_voxel.hip   voxel-grid downsampling: selection on the device or the host, upload of the survivors
+//   cvo_rgbd.hip    RGB-D front end: depth + colour frame to candidate points and to a resident cloud
 #include "cvo_internal.h"
 
 #include "cvo_ctx.hip"
 #include "cvo_launch.hip"
 #include "cvo_upload.hip"
 #include "cvo_voxel.hip"
+#include "cvo_rgbd.hip"
 #include "cvo_sched.hip"
 #include "cvo_queue.hip"
 #include "cvo_eval.hip"

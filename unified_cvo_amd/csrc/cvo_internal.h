@@ -1,5 +1,5 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_voxel.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
 // pair, graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -131,6 +131,13 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
+// what cvo_debug_rgbd_stats reports of the context's last RGB-D call (cvo_rgbd.hip)
+struct RgbdStatsAcc {
+  int n_tried = 0, tried[8] = {}, count[8] = {};  // the selector's schedule: potentials tried, pixels selected at each
+  unsigned long long edge_selected = 0, edge_points = 0, surface_points = 0, with_depth = 0;
+  int on_device = 0;
+};
+
 struct cvo_ctx {
   int device = 0;
   CtxOptions opt;                          // the switches (cvo_options.h)
@@ -199,6 +206,12 @@ struct cvo_ctx {
   size_t vox_scratch_bytes = 0;
   unsigned long long vox_capacity = 0;  // 0: the last selection ran on the host (or none has run)
   VoxelCtl vox_last{};
+  // RGB-D front end (cvo_rgbd.hip): one growable device region - image, depth, exclusion bytes, g2, thresholds, cell hits,
+  // candidate pixels and their coordinates - used on upload_stream under upload_mutex like the voxel region
+  char* rgbd_scratch = nullptr;
+  size_t rgbd_scratch_bytes = 0;
+  std::vector<unsigned char> rgbd_excl;  // staging of the exclusion bytes of a semantic frame
+  RgbdStatsAcc rgbd_last{};
   double clock_ms_per_tick = 0.0;  // s_memrealtime, calibrated on first use (cvo_debug_kernel_clock)
 };
 

@@ -64,3 +64,4 @@
 #include "cvo_k_cloud.h"
 #include "cvo_k_irls.h"
 #include "cvo_k_voxel.h"
+#include "cvo_k_rgbd.h"

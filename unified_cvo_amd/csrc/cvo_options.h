@@ -42,6 +42,7 @@ struct CtxOptions {
   CloudOrder order = CloudOrder::Device;
   int row_max = ASSOC_CAP16;  // DevParams::row_max_cap; ASSOC_CAP16 = off
   int voxel_host = -1;        // cvo_voxel_select / cvo_cloud_upload_voxel: 1 = the CPU twin, 0 = the kernels, -1 = by size (cvo_voxel.hip)
+  int rgbd_host = -1;         // cvo_rgbd_points / cvo_cloud_upload_rgbd: 1 = the CPU twin, 0 = the kernels, -1 = by size (cvo_rgbd.hip)
   int voxel_prepass = 1;      // k_voxel_insert resolves a block's duplicates in LDS first
   // ---- diagnostics ----
   int verbose = 0;  // 0 silent, 1 / 2 / 3: INTEGRATION.md
@@ -90,6 +91,7 @@ constexpr OptionSpec kOptions[] = {
     opt_flag("NO_SPECULATE", &CtxOptions::no_speculate),
     opt_int("VOXEL_HOST", &CtxOptions::voxel_host, -1, 1),
     opt_int("VOXEL_PREPASS", &CtxOptions::voxel_prepass, 0, 1),
+    opt_int("RGBD_HOST", &CtxOptions::rgbd_host, -1, 1),
     {"VERBOSE", OptKind::Level, nullptr, &CtxOptions::verbose, nullptr, 0, 0},
     opt_flag("KERNEL_CLOCK", &CtxOptions::kernel_clock),
     opt_flag("PHASE_TICKS", &CtxOptions::phase_ticks),

@@ -49,8 +49,11 @@ void voxel_select_cpu(int n, const float* xyz, float s, std::vector<int>& kept) 
   }
 }
 
-// The kernels, on upload_stream (the caller holds upload_mutex).  xyz: n x 3 host floats, n >= 1, s validated.
-int voxel_select_device(cvo_ctx* ctx, int n, const float* xyz, float s, std::vector<int>& kept) {
+// The kernels, on upload_stream (the caller holds upload_mutex); n >= 1, s validated.  The coordinates are n x 3 host
+// floats `xyz`, staged into the scratch region here, or - d_xyz != nullptr - already on the device, written by earlier
+// work on upload_stream (the RGB-D front end; xyz may then be nullptr).  kept (optional): the kept indices; d_kept_out
+// (optional): where they are on the device, valid until the next selection.  ctx->vox_last.n_kept: their number.
+int voxel_run_device(cvo_ctx* ctx, int n, const float* xyz, const float* d_xyz_given, float s, std::vector<int>* kept, const int** d_kept_out) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   size_t cap = 1024;
   while (cap < 2 * (size_t)n) cap *= 2;
@@ -62,7 +65,7 @@ int voxel_select_device(cvo_ctx* ctx, int n, const float* xyz, float s, std::vec
     return o;
   };
   const size_t o_ctl = take(sizeof(VoxelCtl)), o_stats = take(sizeof(VoxelBlockStats) * VOX_INSERT_BLOCKS), o_keys = take(sizeof(unsigned long long) * cap), o_first = take(sizeof(unsigned) * cap),
-               o_xyz = take(sizeof(float) * 3 * (size_t)n), o_slot = take(sizeof(unsigned) * (size_t)n),
+               o_xyz = take(d_xyz_given ? 0 : sizeof(float) * 3 * (size_t)n), o_slot = take(sizeof(unsigned) * (size_t)n),
                o_blocks = take(sizeof(unsigned) * (size_t)nb), o_kept = take(sizeof(int) * (size_t)n);
   if (off > ctx->vox_scratch_bytes) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
@@ -77,7 +80,7 @@ int voxel_select_device(cvo_ctx* ctx, int n, const float* xyz, float s, std::vec
   VoxelCtl* ctl = (VoxelCtl*)(b + o_ctl);
   unsigned long long* keys = (unsigned long long*)(b + o_keys);
   unsigned* first = (unsigned*)(b + o_first);
-  float* d_xyz = (float*)(b + o_xyz);
+  const float* d_xyz = d_xyz_given ? d_xyz_given : (const float*)(b + o_xyz);
   unsigned* slot = (unsigned*)(b + o_slot);
   unsigned* blocks = (unsigned*)(b + o_blocks);
   int* d_kept = (int*)(b + o_kept);
@@ -86,12 +89,12 @@ int voxel_select_device(cvo_ctx* ctx, int n, const float* xyz, float s, std::vec
   const unsigned mask = (unsigned)(cap - 1);
   HIP_TRY(ctx, hipMemsetAsync(ctl, 0, sizeof(VoxelCtl), st));
   HIP_TRY(ctx, hipMemsetAsync(keys, 0xFF, o_xyz - o_keys, st));  // keys and first[] are adjacent: one fill
-  HIP_TRY(ctx, hipMemcpyAsync(d_xyz, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+  if (!d_xyz_given) HIP_TRY(ctx, hipMemcpyAsync(b + o_xyz, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
   const int grid = std::min(nb, VOX_INSERT_BLOCKS);
   if (ctx->opt.voxel_prepass)
-    hipLaunchKernelGGL(k_voxel_insert<true>, dim3(grid), dim3(VOX_THREADS), 0, st, n, (const float*)d_xyz, s, mask, keys, first, slot, ctl, stats);
+    hipLaunchKernelGGL(k_voxel_insert<true>, dim3(grid), dim3(VOX_THREADS), 0, st, n, d_xyz, s, mask, keys, first, slot, ctl, stats);
   else
-    hipLaunchKernelGGL(k_voxel_insert<false>, dim3(grid), dim3(VOX_THREADS), 0, st, n, (const float*)d_xyz, s, mask, keys, first, slot, ctl, stats);
+    hipLaunchKernelGGL(k_voxel_insert<false>, dim3(grid), dim3(VOX_THREADS), 0, st, n, d_xyz, s, mask, keys, first, slot, ctl, stats);
   hipLaunchKernelGGL(k_voxel_flag, dim3(nb), dim3(VOX_THREADS), 0, st, n, mask, (const unsigned*)first, (const unsigned*)slot, blocks);
   hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, st, nb, blocks, ctl, grid, (const VoxelBlockStats*)stats);
   hipLaunchKernelGGL(k_voxel_compact, dim3(nb), dim3(VOX_THREADS), 0, st, n, mask, (const unsigned*)first, (const unsigned*)slot,
@@ -102,15 +105,24 @@ int voxel_select_device(cvo_ctx* ctx, int n, const float* xyz, float s, std::vec
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (h.status) {
     std::string msg;
+    std::vector<float> back;
+    if (!xyz) {  // (the refusal names the point: fetch what the device was given)
+      back.resize(3 * (size_t)n);
+      HIP_TRY(ctx, hipMemcpy(back.data(), d_xyz, sizeof(float) * back.size(), hipMemcpyDeviceToHost));
+      xyz = back.data();
+    }
     (void)voxel_validate(n, xyz, s, &msg);
     return fail(ctx, CVO_E_INVALID, "voxel selection: " + msg);
   }
   if (h.n_kept > (unsigned)n) return fail(ctx, CVO_E_HIP, "voxel selection: the device kept more points than it was given");
-  kept.resize(h.n_kept);
-  if (h.n_kept) {
-    HIP_TRY(ctx, hipMemcpyAsync(kept.data(), d_kept, sizeof(int) * (size_t)h.n_kept, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (kept) {
+    kept->resize(h.n_kept);
+    if (h.n_kept) {
+      HIP_TRY(ctx, hipMemcpyAsync(kept->data(), d_kept, sizeof(int) * (size_t)h.n_kept, hipMemcpyDeviceToHost, st));
+      HIP_TRY(ctx, hipStreamSynchronize(st));
+    }
   }
+  if (d_kept_out) *d_kept_out = d_kept;
   ctx->vox_capacity = cap;
   ctx->vox_last = h;
   return CVO_OK;
@@ -134,7 +146,7 @@ int voxel_select(cvo_ctx* ctx, const char* who, int n, const float* xyz, float s
     ctx->vox_last = VoxelCtl{};
     return CVO_OK;
   }
-  return voxel_select_device(ctx, n, xyz, s, kept);
+  return voxel_run_device(ctx, n, xyz, nullptr, s, &kept, nullptr);
 }
 
 }  // namespace

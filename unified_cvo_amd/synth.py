@@ -171,3 +171,61 @@ def to_colmajor16(T):
 
 def from_colmajor16(v):
     return np.asarray(v, dtype=np.float64).reshape(4, 4).T
+
+
+RGBD_KINDS = {
+    # texture amplitude, noise amplitude (grey levels), share of the image left flat, checker amplitude
+    "textured": (60.0, 14.0, 0.0, 40.0),
+    "smoother": (40.0, 60.0, 0.5, 40.0),
+    "flat": (60.0, 6.0, 0.8, 40.0),
+    "edge": (40.0, 60.0, 0.66, 40.0),
+    "noisy": (40.0, 60.0, 0.0, 40.0),
+}
+
+
+def rgbd_frame(kind="textured", rows=480, cols=640, seed=0, depth="u16", channels=3, num_classes=0, shift=0.0):
+    """A seeded synthetic RGB-D frame as a dict of arrays (the fields of api.RGBDFrame): sinusoid-plus-checker texture
+    with per-pixel noise (`kind`: RGBD_KINDS, chosen so that the DSO-style selector's potential schedule takes each of
+    its branches), a slanted-wall-and-floor depth image with holes - uint16 at scaling_factor 5000 or float32 metres with
+    NaN holes -, TUM-like intrinsics scaled to the image.  The checker's 3-4-5 steps put perfect-square gradient
+    magnitudes (dx = 3, dy = 4) into every frame.  shift: the camera's sideways motion in pixels (a second view).
+    num_classes > 0: one-hot semantic rows in vertical bands, class 10 among them."""
+    amp, noise, flat, chk = RGBD_KINDS[kind]
+    rs = np.random.default_rng(424200 + seed)
+    v, u = np.meshgrid(np.arange(rows, dtype=np.float64), np.arange(cols, dtype=np.float64) + shift, indexing="ij")
+    planes = []
+    for c in range(3):
+        t = 128.0 + amp * np.sin(0.11 * u + 0.05 * v + c) * np.cos(0.07 * v - 0.03 * u + 2 * c)
+        t += chk * ((np.floor(u / 16.0) + np.floor(v / 16.0)) % 2 - 0.5)
+        planes.append(t)
+    img = np.stack(planes, axis=-1) + rs.uniform(-noise, noise, (rows, cols, 3))
+    if flat > 0:
+        img[:, :int(cols * flat)] = 97.0
+    img = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+    # a staircase whose steps give dx = 3, dy = 4 (and 5, 12) at its inner corners: perfect-square g2
+    r0, c0 = rows // 2, cols // 2
+    if rows >= 24 and cols >= 24:
+        yy, xx = np.meshgrid(np.arange(16), np.arange(16), indexing="ij")
+        img[r0:r0 + 16, c0:c0 + 16] = (100 + 3 * xx + 4 * yy)[..., None].astype(np.uint8)
+        img[r0 - 16:r0, c0 - 16:c0] = (20 + 5 * xx + 12 * yy)[..., None].astype(np.uint8)
+    if channels == 1:
+        img = np.ascontiguousarray(img[..., 1])
+    z = 1.2 + 2.5 * (v / max(rows - 1, 1)) + 0.8 * np.sin(0.013 * u) + 0.4 * (u > cols * 0.55)
+    hole = (rs.random((rows, cols)) < 0.03) | ((u - shift > cols * 0.3) & (u - shift < cols * 0.34) & (v < rows * 0.5))
+    if depth == "u16":
+        d = np.clip(np.rint(z * 5000.0), 1, 65535).astype(np.uint16)
+        d[hole] = 0
+        scale = 5000.0
+    else:
+        d = z.astype(np.float32)
+        d[hole] = np.nan
+        d[::7, ::11] = 0.0
+        scale = 1.0
+    out = dict(image=img, depth=d, fx=525.0 * cols / 640.0, fy=525.0 * rows / 480.0, cx=319.5 * cols / 640.0,
+               cy=239.5 * rows / 480.0, scaling_factor=scale, gray=None, semantic=None)
+    if num_classes > 0:
+        cls = (np.floor(u / 23.0).astype(np.int64) + np.floor(v / 31.0).astype(np.int64)) % num_classes
+        sem = np.full((rows, cols, num_classes), 0.01, np.float32)
+        np.put_along_axis(sem, cls[..., None], 0.9, axis=2)
+        out["semantic"] = sem
+    return out
