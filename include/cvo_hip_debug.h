@@ -76,6 +76,19 @@ int cvo_debug_device_memory(cvo_ctx* ctx, size_t* free_bytes, size_t* total_byte
  * row-major doubles).  out[91] = cost, g[12], the upper triangle of the 12 x 12 H row by row (78). */
 int cvo_debug_irls_normal(cvo_ctx* ctx, const cvo_cloud* frame1, const cvo_cloud* frame2, const double pose1[12],
                           const double pose2[12], double* out);
+/* k_irls_eval / k_irls_finish on a caller-made launch table: resident UNtransformed clouds (n_frames of them), poses
+ * (12 doubles per frame, 3x4 row-major), n_edges edges (edge_frames: frame1, frame2 per edge) whose entry slots are
+ * [slot_off[e], slot_off[e + 1]) of ent_r / ent_c / ent_w (row of frame 1, column of frame 2, weight; c < 0: an empty
+ * slot).  The table (first block per edge, block count) is built by the builder cvo_multiframe_align uses, over every
+ * edge given, zero-slot edges included.  out: n_edges x 91 doubles (cost, g[12], upper H[78]) when normal != 0, else
+ * n_edges costs.  Everything is checked on the host before any launch: frames in range, slot_off non-decreasing,
+ * 0 <= r < n1 and c < n2 for every stored entry (CVO_E_INVALID otherwise). */
+int cvo_debug_irls_eval(cvo_ctx* ctx, int n_frames, const cvo_cloud* const* clouds, const double* poses, int n_edges,
+                        const int* edge_frames, const int* slot_off, const int* ent_r, const int* ent_c, const float* ent_w,
+                        int normal, double* out);
+/* k_irls_gather on the matrix of the last evaluation on this context (cvo_edge_kernel_matrix) at its neighbour budget K
+ * (CVO_E_INVALID for another K): the N x K entry slots, row-major by sorted position, as r / c / w arrays. */
+int cvo_debug_irls_gather(cvo_ctx* ctx, int K, int* r, int* c, float* w);
 /* The context's last voxel selection (cvo_voxel_select / cvo_cloud_upload_voxel) on the device: slots of the hash table,
  * slots taken (= voxels), slots visited by all inserts, the longest probe sequence of one insert (1 = its home slot), and the
  * points that reached the table in HBM (all of them without the block-local pre-pass).  All 0 after a selection on the host

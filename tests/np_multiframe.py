@@ -190,6 +190,8 @@ def multiframe_align(params, xyz, poses, hold_const, edges, A_fn):
     """CvoBatchIRLS::solve.  params: a CvoParams-like object; xyz: F clouds (n x 3 float32, untransformed); poses:
     F x 12 doubles; edges: list of (frame1, frame2).  Returns (poses, trace rows as dicts)."""
     X = np.array(poses, np.float64).reshape(-1, 12).copy()
+    if not np.all(np.isfinite(X)):  # cvo_multiframe_align: CVO_E_INVALID before anything is written
+        raise ValueError("non-finite pose")
     F = X.shape[0]
     free = np.array([not (hold_const is not None and hold_const[f]) for f in range(F)])
     K0 = int(params.multiframe_num_neighbors)

@@ -1,5 +1,7 @@
 """Multi-frame align on the MI355X: k_irls_normal against numpy, the whole call against the float64 restatement
-(tests/np_multiframe.py) fed by the library's own edge kernel, the argument contract of cvo_multiframe_align."""
+(tests/np_multiframe.py) fed by the library's own edge kernel - on the suite's usual parameters, and on draws that reach
+the trust-region loop's other branches (rejected steps, terminations 1, 2 and 3, the ell decay, the `converged` exit, the
+neighbour-budget shrink) - and the argument contract of cvo_multiframe_align."""
 import numpy as np
 import pytest
 
@@ -186,11 +188,18 @@ def test_multiframe_edge_cases():
         ([devs[0]] * 65, [0, 1], _capi.CVO_E_UNSUPPORTED),
         (devs, [0, 1] * 2049, _capi.CVO_E_UNSUPPORTED),
     ]
-    for cl, ed, code in bad:
-        X_in = np.tile(X0[0], len(cl))
+    bad = [row + (None,) for row in bad]
+    for f, q, v in ((1, 7, np.nan), (0, 0, np.inf), (2, 11, -np.inf)):  # a non-finite pose, in or out of an edge
+        X_bad = X0.reshape(-1).copy()
+        X_bad[12 * f + q] = v
+        bad.append((devs, [0, 1], _capi.CVO_E_INVALID, X_bad))
+        with pytest.raises(ValueError):
+            nm.multiframe_align(P, xyz, X_bad, None, [(0, 1)], None)
+    for cl, ed, code, X_bad in bad:
+        X_in = np.tile(X0[0], len(cl)) if X_bad is None else X_bad
         rc, X, info, rows, nt = gpu.multiframe_align_raw(cl, X_in, None, ed, trace_capacity=4)
         assert rc == code, (ed[:4], rc)
-        assert np.array_equal(X, X_in) and nt == -7 and info.outer_iterations == 0
+        assert np.array_equal(X.view(np.uint64), X_in.view(np.uint64)) and nt == -7 and info.outer_iterations == 0
 
 
 def test_multiframe_driver_matches_python(tmp_path):
@@ -228,3 +237,177 @@ def test_multiframe_driver_matches_python(tmp_path):
     py = np.stack([f.pose_vec for f in frames])
     assert info["solves"] > 0 and not np.array_equal(py, X0)
     assert np.array_equal(cpp, py)
+
+
+# ---- the branches of the outer loop and of the trust-region loop ------------------------------------------------
+# With the suite's usual parameters (sigma 0.1, 8 steps per solve) every step is accepted, every solve ends on the
+# iteration cap (termination 5) and ell never decays.  The draws below reach the other branches; each test asserts that
+# the RESTATEMENT's rows contain the branch it is there for, so a test that stops reaching its branch fails.
+# Terminations 4 (trust-region radius below its minimum) and 6 (five invalid steps in a row) are not asserted anywhere:
+# no finite input tried reached them.
+
+def _branch_params(sigma=0.1, steps=8, per_ell=3, max_iters=6, ell=(0.3, 0.1, 0.7), K0=96):
+    P = cases.load_params("geometric_gpu")
+    P.sigma = sigma
+    P.multiframe_ell_init, P.multiframe_ell_min, P.multiframe_ell_decay_rate = ell
+    P.multiframe_num_neighbors, P.multiframe_max_iters = K0, max_iters
+    P.multiframe_iterations_per_ell, P.multiframe_iterations_per_solve, P.multiframe_min_nonzeros = per_ell, steps, 100
+    return P
+
+
+BRANCH_EDGES = [(1, 0), (2, 1), (0, 2)]   # two reversed edges; frame 1, in the middle, is held
+BRANCH_HOLD = [False, True, False]
+
+
+def _branch_scene(n_frames=3):
+    """Frames of 900 / 700 / 500 (/ 300) points of one street scene, perturbed as _sequence does."""
+    xyz, gt, X0 = _sequence(n_frames, 900, seed=5)
+    return [x[:n] for x, n in zip(xyz, (900, 700, 500, 300))], X0
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float64).view(np.uint64)
+
+
+def _against_restatement(P, xyz, X0, hold, edges):
+    """The pattern of test_multiframe_align_matches_restatement, with cost_initial compared as well.  Returns
+    (gpu, devices, info, the restatement's rows, the library's poses)."""
+    gpu = CvoGPU(params=P)
+    frames = [CvoFrameGPU(gpu, CvoPointCloud.from_xyz(x), X0[f].reshape(3, 4)) for f, x in enumerate(xyz)]
+    info, trace = gpu.align_multiframe(frames, hold, edges, trace=True)
+    devs = [f._init for f in frames]
+
+    def A_fn(k, pose1, pose2, ell, K):
+        a, b = edges[k]
+        t1, t2 = gpu.transformed(devs[a], pose1), gpu.transformed(devs[b], pose2)
+        try:
+            return gpu.edge_kernel_matrix(t1, t2, ell, K)
+        finally:
+            t1.free()
+            t2.free()
+
+    X, rows = nm.multiframe_align(P, xyz, X0, hold, edges, A_fn)
+    print([(r["iter"], r["solved"], r["steps"], r["accepted"], r["termination"], round(r["ell"], 4),
+            "".join(e[0] for e in r["events"])) for r in rows])
+    assert info["outer_iterations"] == len(trace) == len(rows)
+    for a, b in zip(trace, rows):
+        for key in ("iter", "n_active_edges", "total_nonzeros", "solved", "steps", "accepted", "termination"):
+            assert a[key] == b[key], (key, a, b)
+        assert a["ell"] == pytest.approx(b["ell"], rel=1e-7)
+        assert a["cost_initial"] == pytest.approx(b["cost_initial"], rel=1e-8)
+        assert a["cost_final"] == pytest.approx(b["cost_final"], rel=1e-8)
+    got = np.stack([f.pose_vec for f in frames])
+    for f in range(len(xyz)):
+        if hold is not None and hold[f]:
+            assert np.array_equal(_bits(got[f]), _bits(X0[f]))
+    assert np.max(np.abs(got - X)) <= 1e-6
+    assert info["solves"] == sum(r["solved"] for r in rows)
+    assert info["steps"] == sum(r["steps"] for r in rows)
+    assert info["accepted_steps"] == sum(r["accepted"] for r in rows)
+    return gpu, devs, info, rows, got
+
+
+def _decay_rows(rows, max_iters):
+    """Rows of outer iterations that decayed ell: not solved, and not the row the loop leaves on."""
+    return [i for i, r in enumerate(rows[:-1]) if not r["solved"] and r["n_active_edges"] > 0 and r["iter"] < max_iters
+            and rows[i + 1]["ell"] < r["ell"]]
+
+
+@pytest.mark.parametrize("sigma", [3.0, 10.0])
+def test_multiframe_rejected_steps_and_function_tolerance(sigma):
+    """sigma 3 / 10, up to 30 steps per solve: solves whose steps are rejected (mu /= decrease; decrease *= 2, several
+    in a row, then accepted ones) and that end on the function tolerance (1); at sigma 10 also the iteration cap (5),
+    the parameter tolerance (3) and an unsolved row in the same run."""
+    P = _branch_params(sigma=sigma, steps=30, max_iters=8)
+    xyz, X0 = _branch_scene()
+    gpu, devs, info, rows, got = _against_restatement(P, xyz, X0, BRANCH_HOLD, BRANCH_EDGES)
+    solved = [r for r in rows if r["solved"]]
+    assert len(solved) >= 5
+    assert any("reject" in r["events"] for r in solved)
+    assert any(r["events"][i:i + 3] == ["reject", "reject", "accept"] for r in solved for i in range(len(r["events"])))
+    assert any(r["termination"] == nm.TERM_FUNCTION for r in solved)
+    assert all(r["steps"] > r["accepted"] > 0 for r in solved)
+    if sigma == 10.0:
+        assert len(_decay_rows(rows, P.multiframe_max_iters)) >= 1
+        assert {r["termination"] for r in solved} >= {nm.TERM_FUNCTION, nm.TERM_ITERATIONS}
+
+
+def test_multiframe_ell_decays_and_solves_again():
+    """100 steps per solve (every solve ends on the parameter tolerance, 3), iterations_per_ell 2, 40 outer iterations:
+    ell decays at least twice, the double `ell` and the float per-edge lengthscales together (a drift between the two
+    shows in total_nonzeros), last_nonzeros is reset (the row after a decay solves although its nonzeros fell)."""
+    P = _branch_params(steps=100, per_ell=2, max_iters=40)
+    xyz, X0 = _branch_scene()
+    gpu, devs, info, rows, got = _against_restatement(P, xyz, X0, BRANCH_HOLD, BRANCH_EDGES)
+    decays = _decay_rows(rows, P.multiframe_max_iters)
+    assert len(decays) >= 2
+    for i in decays:
+        assert rows[i + 1]["solved"] and rows[i + 1]["total_nonzeros"] < rows[i]["total_nonzeros"]
+        assert rows[i + 1]["ell"] == pytest.approx(rows[i]["ell"] * 0.7, rel=1e-6)
+    assert all(r["termination"] == nm.TERM_PARAMETER and 1 < r["steps"] < 100 for r in rows if r["solved"])
+    assert info["final_ell"] == pytest.approx(0.3 * 0.7 ** len(decays), rel=1e-6)
+
+
+def test_multiframe_converges_below_ell_min():
+    """ell 0.3, minimum 0.25, rate 0.5: one decay to 0.15, and the next outer iteration whose nonzeros do not grow
+    leaves the loop by `converged` (ell < ell_min), long before max_iters = 60."""
+    P = _branch_params(steps=30, per_ell=1, max_iters=60, ell=(0.3, 0.25, 0.5))
+    xyz, X0 = _branch_scene()
+    gpu, devs, info, rows, got = _against_restatement(P, xyz, X0, BRANCH_HOLD, BRANCH_EDGES)
+    assert len(_decay_rows(rows, 60)) == 1
+    assert rows[-1]["iter"] < 60 and not rows[-1]["solved"] and rows[-1]["n_active_edges"] == 3
+    assert rows[-1]["ell"] == pytest.approx(0.15, rel=1e-6)
+    assert info["final_ell"] == pytest.approx(0.15, rel=1e-6) and info["outer_iterations"] == len(rows) < 60
+
+
+def test_multiframe_budget_shrinks_and_unused_frame_stays():
+    """Reversed edges, the held frame in the middle, frames of 900 / 700 / 500 points and a fourth, free frame that is
+    in no edge.  Every row count of outer iteration 0 is below K0 / 1.1, so from the second outer iteration on every
+    edge is evaluated and gathered under a smaller budget Kn = int(1.1 max) < K0 (the restatement passes that Kn to
+    edge_kernel_matrix; the driver strides its entry list by it).  The unused frame's pose and the held frame's come back
+    bit for bit."""
+    P = _branch_params(max_iters=4)
+    xyz, X0 = _branch_scene(4)
+    hold = BRANCH_HOLD + [False]
+    gpu, devs, info, rows, got = _against_restatement(P, xyz, X0, hold, BRANCH_EDGES)
+    K0 = P.multiframe_num_neighbors
+    Xf = X0.astype(np.float32)
+    budgets = []
+    for a, b in BRANCH_EDGES:
+        t1, t2 = gpu.transformed(devs[a], Xf[a]), gpu.transformed(devs[b], Xf[b])
+        nz = gpu.edge_kernel_matrix(t1, t2, P.multiframe_ell_init, K0)[2]
+        t1.free()
+        t2.free()
+        assert 0 < int(nz.max()) < K0 / 1.1
+        budgets.append(int(int(nz.max()) * 1.1))
+    assert all(k < K0 for k in budgets) and len(set(budgets)) == 3
+    assert sum(r["solved"] for r in rows) >= 3
+    assert np.array_equal(_bits(got[3]), _bits(X0[3])) and np.array_equal(_bits(got[1]), _bits(X0[1]))
+    assert not np.array_equal(got[0], X0[0]) and not np.array_equal(got[2], X0[2])
+
+
+def test_multiframe_every_frame_held():
+    """No free frame: every solved row has 0 steps and ends on the gradient tolerance (2) at once - the largest
+    component of an empty difference is 0 - and every pose comes back bit for bit."""
+    P = _branch_params(max_iters=4)
+    xyz, X0 = _branch_scene()
+    gpu, devs, info, rows, got = _against_restatement(P, xyz, X0, [True] * 3, BRANCH_EDGES)
+    solved = [r for r in rows if r["solved"]]
+    assert len(solved) >= 3
+    assert all(r["steps"] == 0 and r["accepted"] == 0 and r["termination"] == nm.TERM_GRADIENT for r in solved)
+    assert all(r["cost_initial"] == r["cost_final"] > 0 for r in solved)
+    assert np.array_equal(_bits(got), _bits(X0))
+
+
+def test_multiframe_same_cloud_same_pose():
+    """Every frame the same cloud under the same pose: the residuals of (r, c) and (c, r) nearly cancel, the gradient
+    is small but above its tolerance, and the first step is below the parameter tolerance: each solved row has exactly
+    1 step, 0 accepted steps and termination 3, and no pose changes by a bit."""
+    P = _branch_params(max_iters=4)
+    xyz, X0 = _branch_scene()
+    xyz, X0 = [xyz[0]] * 3, np.stack([X0[1]] * 3)
+    gpu, devs, info, rows, got = _against_restatement(P, xyz, X0, None, [(0, 1), (1, 2), (0, 2)])
+    solved = [r for r in rows if r["solved"]]
+    assert len(solved) >= 3
+    assert all(r["steps"] == 1 and r["accepted"] == 0 and r["termination"] == nm.TERM_PARAMETER for r in solved)
+    assert np.array_equal(_bits(got), _bits(X0))

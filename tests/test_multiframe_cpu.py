@@ -7,6 +7,7 @@ import subprocess
 import numpy as np
 
 import cases
+import irls_cases as ic
 import np_multiframe as nm
 from unified_cvo_amd import _capi, synth
 
@@ -146,3 +147,58 @@ def test_library_exports_multiframe_entry_points_with_declared_struct_sizes():
     assert ctypes.sizeof(_capi.cvo_multiframe_trace_t) == 48
     header = open(os.path.join(cases.ROOT, "include", "cvo_hip.h")).read()
     assert "CVO_MULTIFRAME_MAX_FRAMES 64" in header and "CVO_MULTIFRAME_MAX_EDGES 2048" in header
+
+
+def test_exact_irls_inputs_and_their_integer_reference():
+    """tests/irls_cases.py, the reference of the bit-equality tests of k_irls_eval: its integers are the float64
+    restatement's (cost, g, H) up to that one's rounding, the bound that makes every summation order exact (sum |term|
+    below 2^53 quanta) holds with room on tables of the largest sizes the GPU tests use, and the half matrices tell R
+    from R^T."""
+    rs = np.random.default_rng(20)
+    sizes = (300, 40, 173, 97)
+    xyz = [ic.exact_cloud(rs, n) for n in sizes]
+    poses = ic.exact_poses(rs, 4)
+    for f, T in enumerate(poses):
+        R = T.reshape(3, 4)[:, :3]
+        assert set(np.abs(R).ravel()) <= {0.0, 0.5, 1.0} and np.all(np.abs(xyz[f]) <= 2)
+        if f % 2 == 0:
+            assert not np.array_equal(R, R.T) and not np.allclose(R @ R.T, np.eye(3))
+        else:
+            assert np.allclose(R @ R.T, np.eye(3)) and np.count_nonzero(R) == 3 and not np.any(np.diag(R))
+    t = ic.Table()
+    for k, (f1, f2, n) in enumerate([(0, 1, 12289), (3, 0, 4097), (2, 3, 0), (1, 2, 300), (3, 1, 65)]):
+        t.add(f1, f2, *ic.entries(rs, sizes[f1], sizes[f2], n, empty="interleaved" if k % 2 else "none"))
+    want, worst = ic.exact_table(xyz, poses, t)
+    assert worst < ic.EXACT_LIMIT // 64, worst
+    assert not want[2].any()
+    for k in range(t.n_edges):
+        f1, f2, r, c, w = t.edge(k)
+        keep = c >= 0
+        cost, g, H = nm.edge_normal(xyz[f1][r[keep]].astype(np.float64), xyz[f2][c[keep]].astype(np.float64),
+                                    w[keep].astype(np.float64), poses[f1], poses[f2])
+        got = np.concatenate([[cost], g, H[ic.TRIU]])
+        _, mag = ic.exact_edge(xyz[f1], xyz[f2], r, c, w, poses[f1], poses[f2])
+        S = ic.to_doubles(mag)
+        assert np.all(np.abs(got - want[k]) <= 1e-13 * S), k
+        if keep.any():
+            # R for R^T in J changes the result on these poses (a signed permutation alone could hide it)
+            Tt = poses[f1].reshape(3, 4).copy()
+            Tt[:, :3] = Tt[:, :3].T
+            wrong, _ = ic.exact_edge(xyz[f1], xyz[f2], r, c, w, Tt.reshape(12), poses[f2])
+            assert not np.array_equal(ic.to_doubles(wrong), want[k])
+    for T in poses:   # row 0 of every rotation block differs from its column 0
+        R = T.reshape(3, 4)[:, :3]
+        assert not np.array_equal(R[0], R[:, 0])
+
+
+def test_restatement_refuses_non_finite_poses():
+    xyz = [np.zeros((4, 3), np.float32)] * 2
+    X0 = np.stack([np.eye(4)[:3].reshape(12)] * 2)
+    for bad in (np.nan, np.inf, -np.inf):
+        X = X0.copy()
+        X[1, 7] = bad
+        try:
+            nm.multiframe_align(cases.load_params("geometric_gpu"), xyz, X, None, [(0, 1)], None)
+        except ValueError:
+            continue
+        raise AssertionError("a non-finite pose was accepted")

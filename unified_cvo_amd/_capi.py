@@ -194,7 +194,7 @@ EXPORTED = [
     "cvo_process_hint_hw_queues", "cvo_shutdown",
     "cvo_batch_open", "cvo_batch_submit", "cvo_batch_poll", "cvo_batch_pending", "cvo_batch_stats", "cvo_batch_close",
     "cvo_inner_product_batch", "cvo_function_angle_batch", "cvo_debug_last_score_batch",
-    "cvo_multiframe_align", "cvo_debug_irls_normal",
+    "cvo_multiframe_align", "cvo_debug_irls_normal", "cvo_debug_irls_eval", "cvo_debug_irls_gather",
     "cvo_voxel_select", "cvo_voxel_select_host", "cvo_cloud_upload_voxel", "cvo_debug_voxel_stats",
     "cvo_rgbd_points", "cvo_rgbd_points_host", "cvo_cloud_upload_rgbd", "cvo_debug_rgbd_stats",
 ]
@@ -281,6 +281,8 @@ def lib(path=None):
                                        C.POINTER(cvo_multiframe_trace_t), ip, C.POINTER(C.c_int)]
     L.cvo_debug_irls_normal.argtypes = [vp, vp, vp, dp, dp, dp]
     ipp = C.POINTER(C.c_int)
+    L.cvo_debug_irls_eval.argtypes = [vp, ip, C.POINTER(vp), dp, ip, ipp, ipp, ipp, ipp, fp, ip, dp]
+    L.cvo_debug_irls_gather.argtypes = [vp, ip, ipp, ipp, fp]
     L.cvo_voxel_select.argtypes = [vp, ip, fp, C.c_float, ipp, ipp]
     L.cvo_voxel_select_host.argtypes = [ip, fp, C.c_float, ipp, ipp]
     L.cvo_cloud_upload_voxel.argtypes = [vp, ip, fp, fp, fp, fp, C.c_float, C.POINTER(vp), ipp, ipp]

@@ -886,6 +886,43 @@ class CvoGPU:
         H = H + np.triu(H, 1).T
         return out[0], out[1:13].copy(), H
 
+    def debug_irls_eval(self, clouds, poses, edge_frames, slot_off, ent_r, ent_c, ent_w, normal=True):
+        """cvo_debug_irls_eval: k_irls_eval + k_irls_finish on a caller-made table.  clouds: resident untransformed
+        clouds; poses: F x 12; edge_frames: E x 2; slot_off: E + 1 offsets into ent_r / ent_c (int32) / ent_w (float32),
+        c < 0 an empty slot.  Returns E x 91 doubles (cost, g[12], upper H[78]) or, cost-only, E doubles.  Raises on
+        any index out of range (checked on the host before a launch)."""
+        devs = [self._dev(c) for c in clouds]
+        F = len(devs)
+        handles = (C.c_void_p * max(F, 1))(*[d.handle for d in devs])
+        X = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1) if F else np.zeros(12))
+        ef = np.ascontiguousarray(np.asarray(edge_frames, np.int32).reshape(-1))
+        E = ef.shape[0] // 2
+        so = np.ascontiguousarray(slot_off, np.int32)
+        r, c = np.ascontiguousarray(ent_r, np.int32), np.ascontiguousarray(ent_c, np.int32)
+        w = np.ascontiguousarray(ent_w, np.float32)
+        if X.shape[0] != 12 * max(F, 1) or so.shape[0] != E + 1 or not (r.shape == c.shape == w.shape) or \
+                (E and r.shape[0] < so[-1]):
+            raise ValueError("debug_irls_eval: array sizes do not match")
+        out = np.zeros((E, 91) if normal else (E,), np.float64)
+        ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+        pad = np.zeros(1, np.int32)
+        self._check(self.L.cvo_debug_irls_eval(
+            self.ctx, F, handles, X.ctypes.data_as(dp), E, (ef if E else pad).ctypes.data_as(ip), so.ctypes.data_as(ip),
+            (r if r.size else pad).ctypes.data_as(ip), (c if c.size else pad).ctypes.data_as(ip),
+            _fptr(w if w.size else np.zeros(1, np.float32)), 1 if normal else 0,
+            (out if E else np.zeros(1)).ctypes.data_as(dp)))
+        return out
+
+    def debug_irls_gather(self, n_rows, K):
+        """cvo_debug_irls_gather: the entry list k_irls_gather makes of the last evaluation (edge_kernel_matrix with
+        this K) -> (r, c, w), each [n_rows x K] by sorted position; slots past a row's count are (-1, -1, 0)."""
+        r = np.zeros((n_rows, K), np.int32)
+        c = np.zeros((n_rows, K), np.int32)
+        w = np.zeros((n_rows, K), np.float32)
+        ip = C.POINTER(C.c_int)
+        self._check(self.L.cvo_debug_irls_gather(self.ctx, K, r.ctypes.data_as(ip), c.ctypes.data_as(ip), _fptr(w)))
+        return r, c, w
+
     # -- test / profiling hooks --------------------------------------------------------------------
     def debug_last_ell(self, n_rows, K):
         mat = np.zeros((n_rows, K), np.float32)

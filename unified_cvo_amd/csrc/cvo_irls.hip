@@ -114,6 +114,24 @@ int irls_eval(cvo_ctx* ctx, const IrlsDevice& dv, const std::vector<double>& X, 
 
 inline int irls_blocks(int n) { return (n + IRLS_BLOCK_ENTRIES - 1) / IRLS_BLOCK_ENTRIES; }
 
+// Appends one edge to a launch table: its first block (blk0) follows the blocks of the edges before it.  Returns the
+// table's block count so far (the launch's n_blocks once every edge is in).  The only place blk0 is assigned.
+int irls_table_add(std::vector<IrlsEdge>& tab, int n_blocks, const cvo_cloud* c1, const cvo_cloud* c2, int f1, int f2,
+                   const IrlsEntry* ent, int slots) {
+  IrlsEdge ed;
+  ed.x1 = c1->x4;
+  ed.x2 = c2->x4;
+  ed.ent = ent;
+  ed.n = slots;
+  ed.n1 = c1->n;
+  ed.n2 = c2->n;
+  ed.f1 = f1;
+  ed.f2 = f2;
+  ed.blk0 = n_blocks;
+  tab.push_back(ed);
+  return n_blocks + irls_blocks(slots);
+}
+
 // k_irls_gather of the matrix the last evaluation left in pair 0's workspace into `ent` ([N x K] slots)
 int irls_gather(cvo_ctx* ctx, int N, int K, IrlsEntry* ent) {
   const size_t slots = (size_t)N * K;
@@ -143,6 +161,8 @@ int cvo_multiframe_align(cvo_ctx* ctx, const cvo_params_t* params, int n_frames,
   for (int f = 0; f < n_frames; f++) {
     if (!clouds[f]) return fail(ctx, CVO_E_INVALID, "cvo_multiframe_align: null cloud");
     if (clouds[f]->ctx != ctx) return fail(ctx, CVO_E_INVALID, "cloud belongs to another context");
+    for (int q = 0; q < 12; q++)  // a NaN pose would read as a small gradient (std::max drops it) and reach the kernels
+      if (!std::isfinite(poses[12 * (size_t)f + q])) return fail(ctx, CVO_E_INVALID, "cvo_multiframe_align: non-finite pose");
   }
   for (int k = 0; k < n_edges; k++) {
     const int a = edges[2 * k], b = edges[2 * k + 1];
@@ -281,18 +301,7 @@ int cvo_multiframe_align(cvo_ctx* ctx, const cvo_params_t* params, int n_frames,
       for (int k = 0; k < E; k++) {
         if (!active[k]) continue;
         const int a = edges[2 * k], b = edges[2 * k + 1];
-        IrlsEdge ed;
-        ed.x1 = clouds[a]->x4;
-        ed.x2 = clouds[b]->x4;
-        ed.ent = ent + ent_off[k];
-        ed.n = clouds[a]->n * (int)Kn[k];
-        ed.n1 = clouds[a]->n;
-        ed.n2 = clouds[b]->n;
-        ed.f1 = a;
-        ed.f2 = b;
-        ed.blk0 = nb;
-        nb += irls_blocks(ed.n);
-        tab.push_back(ed);
+        nb = irls_table_add(tab, nb, clouds[a], clouds[b], a, b, ent + ent_off[k], clouds[a]->n * (int)Kn[k]);
       }
       dv.n_edges = (int)tab.size();
       dv.n_blocks = nb;
@@ -491,17 +500,9 @@ int cvo_debug_irls_normal(cvo_ctx* ctx, const cvo_cloud* frame1, const cvo_cloud
     return fail(ctx, CVO_E_NOMEM, "cvo_debug_irls_normal: device allocation failed");
   int rc = irls_gather(ctx, D.N, K, (IrlsEntry*)d_ent.p);
   if (rc != CVO_OK) return rc;
-  IrlsEdge ed;
-  ed.x1 = frame1->x4;
-  ed.x2 = frame2->x4;
-  ed.ent = (const IrlsEntry*)d_ent.p;
-  ed.n = (int)slots;
-  ed.n1 = frame1->n;
-  ed.n2 = frame2->n;
-  ed.f1 = 0;
-  ed.f2 = 1;
-  ed.blk0 = 0;
-  HIP_TRY(ctx, hipMemcpyAsync(d_edges.p, &ed, sizeof(ed), hipMemcpyHostToDevice, ctx->stream));
+  std::vector<IrlsEdge> tab;
+  (void)irls_table_add(tab, 0, frame1, frame2, 0, 1, (const IrlsEntry*)d_ent.p, (int)slots);
+  HIP_TRY(ctx, hipMemcpyAsync(d_edges.p, tab.data(), sizeof(IrlsEdge), hipMemcpyHostToDevice, ctx->stream));
   IrlsDevice dv;
   dv.edges = (IrlsEdge*)d_edges.p;
   dv.poses = (double*)d_poses.p;
@@ -514,6 +515,98 @@ int cvo_debug_irls_normal(cvo_ctx* ctx, const cvo_cloud* frame1, const cvo_cloud
   rc = irls_eval(ctx, dv, X, true, o);
   if (rc != CVO_OK) return rc;
   std::memcpy(out, o.data(), sizeof(double) * IRLS_W);
+  return CVO_OK;
+}
+
+int cvo_debug_irls_eval(cvo_ctx* ctx, int n_frames, const cvo_cloud* const* clouds, const double* poses, int n_edges,
+                        const int* edge_frames, const int* slot_off, const int* ent_r, const int* ent_c, const float* ent_w,
+                        int normal, double* out) {
+  // ---- validation on the host, before any launch: the kernel's own range guard is never what stops a bad index ----
+  if (!ctx || n_frames < 0 || n_edges < 0 || (n_frames > 0 && (!clouds || !poses)) ||
+      (n_edges > 0 && (!edge_frames || !slot_off || !out)))
+    return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_eval: bad argument");
+  if (n_frames > CVO_MULTIFRAME_MAX_FRAMES || n_edges > CVO_MULTIFRAME_MAX_EDGES)
+    return fail(ctx, CVO_E_UNSUPPORTED, "cvo_debug_irls_eval: at most 64 frames and 2048 edges");
+  for (int f = 0; f < n_frames; f++) {
+    if (!clouds[f]) return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_eval: null cloud");
+    if (clouds[f]->ctx != ctx) return fail(ctx, CVO_E_INVALID, "cloud belongs to another context");
+  }
+  if (n_edges == 0) return CVO_OK;
+  if (slot_off[0] < 0) return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_eval: negative slot offset");
+  for (int k = 0; k < n_edges; k++) {
+    const int a = edge_frames[2 * k], b = edge_frames[2 * k + 1];
+    if (a < 0 || a >= n_frames || b < 0 || b >= n_frames)
+      return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_eval: edge frame index out of range");
+    if (slot_off[k + 1] < slot_off[k]) return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_eval: slot offsets decrease");
+  }
+  const size_t first = (size_t)slot_off[0], total = (size_t)slot_off[n_edges];
+  if (total > first && (!ent_r || !ent_c || !ent_w)) return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_eval: bad argument");
+  std::vector<IrlsEntry> h_ent(total - first);
+  for (int k = 0; k < n_edges; k++) {
+    const int n1 = clouds[edge_frames[2 * k]]->n, n2 = clouds[edge_frames[2 * k + 1]]->n;
+    for (size_t i = (size_t)slot_off[k]; i < (size_t)slot_off[k + 1]; i++) {
+      if (ent_c[i] >= 0 && (ent_r[i] < 0 || ent_r[i] >= n1 || ent_c[i] >= n2))
+        return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_eval: stored entry out of range");
+      h_ent[i - first] = IrlsEntry{ent_r[i], ent_c[i], ent_w[i], 0.f};
+    }
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // ---- the launch table, by the driver's builder ----
+  DevAlloc d_ent, d_edges, d_poses, d_part, d_out;
+  if (hipMalloc(&d_ent.p, std::max<size_t>(sizeof(IrlsEntry) * h_ent.size(), 256)) != hipSuccess)
+    return fail(ctx, CVO_E_NOMEM, "cvo_debug_irls_eval: device allocation failed");
+  std::vector<IrlsEdge> tab;
+  int nb = 0;
+  for (int k = 0; k < n_edges; k++) {
+    const int a = edge_frames[2 * k], b = edge_frames[2 * k + 1];
+    nb = irls_table_add(tab, nb, clouds[a], clouds[b], a, b, (const IrlsEntry*)d_ent.p + ((size_t)slot_off[k] - first),
+                        slot_off[k + 1] - slot_off[k]);
+  }
+  if (hipMalloc(&d_edges.p, sizeof(IrlsEdge) * tab.size()) != hipSuccess ||
+      hipMalloc(&d_poses.p, sizeof(double) * 12 * (size_t)n_frames) != hipSuccess ||
+      hipMalloc(&d_part.p, sizeof(double) * IRLS_W * (size_t)std::max(nb, 1)) != hipSuccess ||
+      hipMalloc(&d_out.p, sizeof(double) * IRLS_W * tab.size()) != hipSuccess)
+    return fail(ctx, CVO_E_NOMEM, "cvo_debug_irls_eval: device allocation failed");
+  if (!h_ent.empty())
+    HIP_TRY(ctx, hipMemcpyAsync(d_ent.p, h_ent.data(), sizeof(IrlsEntry) * h_ent.size(), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(d_edges.p, tab.data(), sizeof(IrlsEdge) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
+  IrlsDevice dv;
+  dv.edges = (IrlsEdge*)d_edges.p;
+  dv.poses = (double*)d_poses.p;
+  dv.part = (double*)d_part.p;
+  dv.out = (double*)d_out.p;
+  dv.n_edges = n_edges;
+  dv.n_blocks = nb;
+  std::vector<double> X(poses, poses + 12 * (size_t)n_frames), o;
+  const int rc = irls_eval(ctx, dv, X, normal != 0, o);
+  if (rc != CVO_OK) return rc;
+  std::memcpy(out, o.data(), sizeof(double) * o.size());
+  return CVO_OK;
+}
+
+int cvo_debug_irls_gather(cvo_ctx* ctx, int K, int* r, int* c, float* w) {
+  if (!ctx || !r || !c || !w) return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_gather: bad argument");
+  if (ctx->last_pairs < 1 || !ctx->last_params.keep_columns)
+    return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_gather: no evaluation with column indices on this context");
+  if (K != ctx->last_params.K_max)  // the budget the rows were stored under: what the driver gathers at
+    return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_gather: K is not the neighbour budget of the last evaluation");
+  const int N = ctx->h_descs[0].N;
+  if (N <= 0 || K <= 0 || (size_t)N * K > (size_t)INT32_MAX) return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_gather: bad size");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t slots = (size_t)N * K;
+  DevAlloc d_ent;
+  if (hipMalloc(&d_ent.p, sizeof(IrlsEntry) * slots) != hipSuccess)
+    return fail(ctx, CVO_E_NOMEM, "cvo_debug_irls_gather: device allocation failed");
+  const int rc = irls_gather(ctx, N, K, (IrlsEntry*)d_ent.p);
+  if (rc != CVO_OK) return rc;
+  std::vector<IrlsEntry> h(slots);
+  HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_ent.p, sizeof(IrlsEntry) * slots, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  for (size_t i = 0; i < slots; i++) {
+    r[i] = h[i].r;
+    c[i] = h[i].c;
+    w[i] = h[i].w;
+  }
   return CVO_OK;
 }
 
