@@ -18,6 +18,7 @@
 #include "utils/Calibration.hpp"
 #include "utils/CvoPointCloud.hpp"
 #include "utils/ImageRGBD.hpp"
+#include "utils/ImageStereo.hpp"
 #include "utils/data_type.hpp"
 
 namespace cvo {
@@ -108,6 +109,20 @@ class CvoGPU {
   std::unique_ptr<ResidentClouds> upload_rgbd(const ImageRGBD<DepthType>& raw_image, const Calibration& calib, float leaf = 0.f,
                                               float edge_divisor = 4.f, std::vector<int>* pixel = nullptr,
                                               std::vector<unsigned char>* is_edge = nullptr) const;
+  // New: the stereo front end on the device (cvo_stereo_points / cvo_cloud_upload_stereo / _recipe, include/cvo_hip.h), from
+  // the frame's own disparity.  stereo_points is CvoPointCloud(raw_image, calib, method) with the selector, the keep predicate
+  // and the back-projection run by the kernels.  upload_stereo is the pairwise KITTI driver's cloud
+  // (main_cvo_gpu_align_raw_image.cpp:61-91), resident (size() == 1).  upload_stereo_recipe is the multi-frame KITTI driver's
+  // per-frame block (main_multi_frame_irls_kitti.cpp:235-292): upload_rgbd's recipe on the stereo points, divisor 5.
+  // Defined in host/cvo_stereo.cpp.
+  CvoPointCloud stereo_points(const ImageStereo& raw_image, const Calibration& calib,
+                              CvoPointCloud::PointSelectionMethod method = CvoPointCloud::CV_FAST, std::vector<int>* pixel = nullptr) const;
+  std::unique_ptr<ResidentClouds> upload_stereo(const ImageStereo& raw_image, const Calibration& calib,
+                                                CvoPointCloud::PointSelectionMethod method = CvoPointCloud::CV_FAST,
+                                                std::vector<int>* pixel = nullptr) const;
+  std::unique_ptr<ResidentClouds> upload_stereo_recipe(const ImageStereo& raw_image, const Calibration& calib, float leaf = 0.f,
+                                                       float edge_divisor = 5.f, std::vector<int>* pixel = nullptr,
+                                                       std::vector<unsigned char>* is_edge = nullptr) const;
   // New: multi-frame registration over resident clouds (cvo_multiframe_align as it is): poses 12 doubles per cloud (3x4
   // row-major, updated in place), edges pairs of indices into `clouds`.
   int align(const ResidentClouds& clouds, std::vector<double>& poses, const std::vector<bool>& frames_to_hold_const,

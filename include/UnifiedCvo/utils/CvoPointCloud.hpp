@@ -1,6 +1,6 @@
 // Host point-cloud container: the accessor subset of upstream utils/CvoPointCloud.hpp:126-188 that the
-// align() path and its drivers use, and the RGB-D image constructor (FULL / DSO_EDGES).  The stereo and LiDAR
-// constructors are out of scope.
+// align() path and its drivers use, the RGB-D image constructor (FULL / DSO_EDGES) and the stereo image constructor from a
+// given disparity (CV_FAST / DSO_EDGES / FULL).  The LiDAR constructors are out of scope.
 #pragma once
 #include <string>
 #include <vector>
@@ -19,6 +19,7 @@ namespace cvo {
 class Calibration;
 template <typename DepthType>
 class ImageRGBD;
+class ImageStereo;
 
 class CvoPointCloud {
  public:
@@ -44,6 +45,13 @@ class CvoPointCloud {
   // pixel (optional): v * cols + u of every point.  Defined in host/cvo_rgbd.cpp.
   template <typename DepthType>
   CvoPointCloud(const ImageRGBD<DepthType>& raw_image, const Calibration& calib, PointSelectionMethod pt_selection_method,
+                std::vector<int>* pixel = nullptr);
+
+  // upstream CvoPointCloud.cpp:680-773 (utils/ImageStereo.hpp: the disparity is the caller's, libelas is not part of this
+  // library) for pt_selection_method CV_FAST (upstream's default), DSO_EDGES or FULL, on the host (cvo_stereo_points_host,
+  // include/cvo_hip.h, states the contract: the keep predicate, the float arithmetic, F = channels + 2); every other method
+  // throws std::invalid_argument.  pixel (optional): v * cols + u of every point.  Defined in host/cvo_stereo.cpp.
+  CvoPointCloud(const ImageStereo& raw_image, const Calibration& calib, PointSelectionMethod pt_selection_method = CV_FAST,
                 std::vector<int>* pixel = nullptr);
 
   static CvoPointCloud from_xyz(const float* xyz, int n);                                // type (1,0), F = 0

@@ -258,6 +258,70 @@ int cvo_rgbd_points_host(const cvo_rgbd_frame_t* frame, int method, int* pixel, 
  * entries): pixel index and set of every point; *n their number.  leaf, edge_divisor: finite and > 0. */
 int cvo_cloud_upload_rgbd(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, float leaf, float edge_divisor, cvo_cloud** out,
                           int* pixel, unsigned char* is_edge, int* n);
+/* ---- CV_FAST point selection: replaces select_points_from_image's CV_FAST branch (CvoPointCloud.cpp:273-312) ----
+ * cv::FAST(gray, keypoints, t, nonmax = false), TYPE_9_16: a pixel with 3 <= x < cols - 3, 3 <= y < rows - 3 is a corner at t
+ * iff 9 cyclically contiguous pixels of its radius-3 ring are all brighter than I_p + t or all darker than I_p - t (strict;
+ * t clamped to 0 .. 255); keypoints in row-major order.  The reference's schedule, literally: the first call is ALWAYS at 5;
+ * while more than num_want keypoints, ++thresh and call again, stopping at break_thresh; then while fewer than num_min,
+ * --thresh and call again, stopping at 0; the keypoints of the LAST call stand (with no loop taken: those at 5, not at
+ * thresh).  One departure: a lowering loop that would pass below 0 ends there.  pixel: v * cols + u of every keypoint
+ * (room for rows x cols ints); *threshold_used (optional): the last call's threshold.  Images under 7 pixels on a side are
+ * valid and have no corners.  CVO_E_INVALID, nothing written: rows / cols < 1, a missing pointer, a schedule with a negative
+ * field, thresh > 255 or num_min > num_want.  CVO_E_UNSUPPORTED: more than 2^24 pixels.  Runs on the upload stream; switch
+ * STEREO_HOST as for the stereo front end below.  RGB-D users get upstream's CV_FAST pixels with CVO_FAST_RGBD. */
+#define CVO_SELECT_CV_FAST 0
+typedef struct cvo_fast_schedule_t {
+  int thresh, num_want, num_min, break_thresh;
+} cvo_fast_schedule_t;
+#define CVO_FAST_RGBD {9, 15000, 12000, 13}
+#define CVO_FAST_STEREO {4, 24000, 15000, 50}
+#define CVO_FAST_STEREO_SEMANTIC {4, 28000, 15000, 50}   /* a stereo frame with classes */
+int cvo_fast_select(cvo_ctx* ctx, int rows, int cols, const uint8_t* gray, const cvo_fast_schedule_t* schedule,
+                    int* pixel /* rows*cols */, int* n, int* threshold_used);
+int cvo_fast_select_host(int rows, int cols, const uint8_t* gray, const cvo_fast_schedule_t* schedule, int* pixel, int* n,
+                         int* threshold_used);   /* CPU twin, no context */
+/* ---- stereo front end: replaces CvoPointCloud(ImageStereo, Calibration, PointSelectionMethod) (CvoPointCloud.cpp:680-773,
+ * StaticStereo.cpp:84-107, is_good_point :39-49) FROM A GIVEN DISPARITY MAP (upstream computes it with libelas, which is not
+ * part of this library; its invalid marker -10 is rejected like every disparity below 0.05) and the per-frame block of the
+ * multi-frame KITTI driver (main_multi_frame_irls_kitti.cpp:235-292) ----
+ * image / gray / semantic: as in cvo_rgbd_frame_t (the LEFT image, after RawImage's denoising). */
+typedef struct cvo_stereo_frame_t {
+  int rows, cols, channels;    /* channels: 1 or 3 */
+  const uint8_t* image;        /* rows x cols x channels */
+  const uint8_t* gray;         /* rows x cols, or NULL */
+  const float* disparity;      /* rows x cols, left disparity in pixels */
+  float fx, fy, cx, cy;        /* Calibration::intrinsic() */
+  float baseline;              /* Calibration::baseline(); its absolute value is used */
+  int num_classes;             /* 0 = no semantics */
+  const float* semantic;       /* rows x cols x num_classes, or NULL */
+} cvo_stereo_frame_t;
+/* The points of the reference constructor, in its order.  Candidates: CV_FAST - cvo_fast_select with CVO_FAST_STEREO
+ * (CVO_FAST_STEREO_SEMANTIC with classes), type (1, 0); DSO_EDGES and FULL - exactly cvo_rgbd_points' candidates, types
+ * (0.9, 0.1) and (0.5, 0.5).  A candidate (u, v) is kept iff 1 <= u <= cols - 2 && 1 <= v <= rows - 2; its disparity is not
+ * below 0.05f (0.05f itself is kept; a NaN passes this and every later test, as upstream); 2 <= u <= cols - 2 &&
+ * 100 <= v <= rows - 30 (a frame with fewer than 130 rows yields no points); !(|xyz| >= 55); and - with semantics - its
+ * first-maximum class is not 10.  In float, every operation rounded on its own: depth = |baseline| fx / disparity,
+ * xyz = (Kinv (u, v, 1)) depth with Eigen 3.3's cofactor inverse (invdet = 1 / (fx fy), Kinv00 = fy invdet, Kinv11 =
+ * fx invdet, Kinv02 = -(cx fy) invdet, Kinv12 = -(fx cy) invdet, Kinv22 = (fx fy) invdet), |xyz| = sqrtf((x x + y y) + z z).
+ * Outputs as cvo_rgbd_points: pixel (room for rows x cols ints), xyz, feat n x (channels + 2), label, geotype.
+ * CVO_E_INVALID, nothing written: rows / cols < 1, channels not 1 or 3, a missing pointer, fx / fy / baseline not finite
+ * or zero.  CVO_E_UNSUPPORTED: the other selection methods, more than 2^24 pixels, for DSO_EDGES an image shape whose
+ * literal threshold index leaves the reference's allocation.  Runs on the upload stream; switch STEREO_HOST=1 / 0: the CPU
+ * twin / the kernels for every size (unset: frames under 10000 pixels take the CPU twin; the recipe below: under 24000). */
+int cvo_stereo_points(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat,
+                      float* label, float* geotype);
+int cvo_stereo_points_host(const cvo_stereo_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat,
+                           float* label, float* geotype);   /* CPU twin, no context */
+/* The pairwise driver's cloud (main_cvo_gpu_align_raw_image.cpp:61-91): the constructor's rows through cvo_cloud_upload -
+ * the channels + 2 features zero-padded to 5 (a mono frame has 3), labels padded or cut to 19 classes.  Rows with a
+ * non-finite coordinate (NaN disparity) are treated as cvo_cloud_upload treats them.  pixel (optional), *n (optional). */
+int cvo_cloud_upload_stereo(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, int method, cvo_cloud** out, int* pixel, int* n);
+/* The multi-frame KITTI driver's block: cvo_cloud_upload_rgbd's recipe on the stereo points - DSO_EDGES points through a voxel
+ * grid of side leaf / edge_divisor (the driver's divisor is 5), FULL points through one of side leaf, rows F = 5 colour
+ * bytes, types EDGE / SURFACE, edge first.  The voxel contract's refusals pass through (a NaN disparity inside the kept
+ * region is one: a non-finite coordinate).  pixel / is_edge: room for 2 x rows x cols entries. */
+int cvo_cloud_upload_stereo_recipe(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, float leaf, float edge_divisor, cvo_cloud** out,
+                                   int* pixel, unsigned char* is_edge, int* n);
 int cvo_cloud_size(const cvo_cloud* c);
 void cvo_cloud_free(cvo_cloud* c);
 

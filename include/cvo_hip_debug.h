@@ -102,6 +102,13 @@ int cvo_debug_voxel_stats(cvo_ctx* ctx, unsigned long long* capacity, unsigned l
 int cvo_debug_rgbd_stats(cvo_ctx* ctx, int* n_tried, int* potentials /* 8 */, int* counts /* 8 */,
                          unsigned long long* edge_selected, unsigned long long* edge_points,
                          unsigned long long* surface_points, unsigned long long* with_depth, int* on_device);
+/* The context's last cvo_fast_select / cvo_stereo_points / cvo_cloud_upload_stereo / _recipe: the thresholds (CV_FAST) or
+ * potentials (DSO_EDGES) the selector's schedule evaluated - *n_tried of them, the first `capacity` written - and the pixels
+ * at each; the FAST threshold whose keypoints stand (-1: no FAST selection ran); the 257 pixel counts per FAST score
+ * -1 .. 255; the pixels the keep predicate saw and the points it kept (the recipe: both passes); whether the kernels ran.
+ * Any pointer may be NULL. */
+int cvo_debug_stereo_stats(cvo_ctx* ctx, int capacity, int* n_tried, int* thresholds, int* counts, int* threshold_used,
+                           unsigned* histogram /* 257 */, unsigned long long* candidates, unsigned long long* kept, int* on_device);
 
 #ifdef __cplusplus
 }

@@ -178,8 +178,31 @@ class cvo_rgbd_frame_t(C.Structure):
     ]
 
 
+class cvo_fast_schedule_t(C.Structure):
+    _fields_ = [("thresh", C.c_int), ("num_want", C.c_int), ("num_min", C.c_int), ("break_thresh", C.c_int)]
+
+
+class cvo_stereo_frame_t(C.Structure):
+    _fields_ = [
+        ("rows", C.c_int),
+        ("cols", C.c_int),
+        ("channels", C.c_int),
+        ("image", C.c_void_p),
+        ("gray", C.c_void_p),
+        ("disparity", C.c_void_p),
+        ("fx", C.c_float),
+        ("fy", C.c_float),
+        ("cx", C.c_float),
+        ("cy", C.c_float),
+        ("baseline", C.c_float),
+        ("num_classes", C.c_int),
+        ("semantic", C.c_void_p),
+    ]
+
+
 CVO_DEPTH_U16, CVO_DEPTH_F32 = 0, 1
-CVO_SELECT_DSO_EDGES, CVO_SELECT_FULL = 2, 8
+CVO_SELECT_CV_FAST, CVO_SELECT_DSO_EDGES, CVO_SELECT_FULL = 0, 2, 8
+CVO_FAST_RGBD, CVO_FAST_STEREO, CVO_FAST_STEREO_SEMANTIC = (9, 15000, 12000, 13), (4, 24000, 15000, 50), (4, 28000, 15000, 50)
 
 # every symbol include/cvo_hip.h declares (tests/test_capi_symbols.py checks the two lists agree)
 EXPORTED = [
@@ -197,6 +220,8 @@ EXPORTED = [
     "cvo_multiframe_align", "cvo_debug_irls_normal", "cvo_debug_irls_eval", "cvo_debug_irls_gather",
     "cvo_voxel_select", "cvo_voxel_select_host", "cvo_cloud_upload_voxel", "cvo_debug_voxel_stats",
     "cvo_rgbd_points", "cvo_rgbd_points_host", "cvo_cloud_upload_rgbd", "cvo_debug_rgbd_stats",
+    "cvo_fast_select", "cvo_fast_select_host", "cvo_stereo_points", "cvo_stereo_points_host", "cvo_cloud_upload_stereo",
+    "cvo_cloud_upload_stereo_recipe", "cvo_debug_stereo_stats",
 ]
 
 _libs = {}
@@ -292,6 +317,14 @@ def lib(path=None):
     L.cvo_rgbd_points_host.argtypes = [fr, ip, ipp, ipp, fp, fp, fp, fp]
     L.cvo_cloud_upload_rgbd.argtypes = [vp, fr, C.c_float, C.c_float, C.POINTER(vp), ipp, C.POINTER(C.c_ubyte), ipp]
     L.cvo_debug_rgbd_stats.argtypes = [vp, ipp, ipp, ipp] + [C.POINTER(C.c_ulonglong)] * 4 + [ipp]
+    sched, sf, up = C.POINTER(cvo_fast_schedule_t), C.POINTER(cvo_stereo_frame_t), C.POINTER(C.c_ubyte)
+    L.cvo_fast_select.argtypes = [vp, ip, ip, up, sched, ipp, ipp, ipp]
+    L.cvo_fast_select_host.argtypes = [ip, ip, up, sched, ipp, ipp, ipp]
+    L.cvo_stereo_points.argtypes = [vp, sf, ip, ipp, ipp, fp, fp, fp, fp]
+    L.cvo_stereo_points_host.argtypes = [sf, ip, ipp, ipp, fp, fp, fp, fp]
+    L.cvo_cloud_upload_stereo.argtypes = [vp, sf, ip, C.POINTER(vp), ipp, ipp]
+    L.cvo_cloud_upload_stereo_recipe.argtypes = [vp, sf, C.c_float, C.c_float, C.POINTER(vp), ipp, up, ipp]
+    L.cvo_debug_stereo_stats.argtypes = [vp, ip, ipp, ipp, ipp, ipp, C.POINTER(C.c_uint)] + [C.POINTER(C.c_ulonglong)] * 2 + [ipp]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

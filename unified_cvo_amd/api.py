@@ -253,6 +253,71 @@ def rgbd_points_host(frame, method):
     return pc
 
 
+CV_FAST = _capi.CVO_SELECT_CV_FAST
+FAST_RGBD, FAST_STEREO, FAST_STEREO_SEMANTIC = _capi.CVO_FAST_RGBD, _capi.CVO_FAST_STEREO, _capi.CVO_FAST_STEREO_SEMANTIC
+
+
+class StereoFrame:
+    """What cvo::ImageStereo and cvo::Calibration hold of one stereo frame (cvo_stereo_frame_t): the LEFT `image` (rows, cols)
+    or (rows, cols, 3) uint8 in BGR order, after RawImage's denoising; the left `disparity` (rows, cols) float32 in pixels,
+    from the caller's matcher (upstream: libelas, invalid = -10); the intrinsics and the baseline; optionally the 8-bit `gray`
+    plane and `semantic` (rows, cols, num_classes) float32, as in RGBDFrame."""
+
+    def __init__(self, image, disparity, fx, fy, cx, cy, baseline, gray=None, semantic=None):
+        self.image = np.ascontiguousarray(image, np.uint8)
+        if self.image.ndim == 3 and self.image.shape[2] == 1:
+            self.image = np.ascontiguousarray(self.image[..., 0])
+        self.rows, self.cols = self.image.shape[:2]
+        self.channels = 1 if self.image.ndim == 2 else self.image.shape[2]
+        self.disparity = np.ascontiguousarray(disparity, np.float32)
+        if self.disparity.shape != (self.rows, self.cols):
+            raise ValueError(f"disparity is {self.disparity.shape}, the image {self.rows} x {self.cols}")
+        self.fx, self.fy, self.cx, self.cy, self.baseline = (float(v) for v in (fx, fy, cx, cy, baseline))
+        self.gray = None if gray is None else np.ascontiguousarray(gray, np.uint8).reshape(self.rows, self.cols)
+        self.semantic = None if semantic is None else np.ascontiguousarray(semantic, np.float32).reshape(self.rows, self.cols, -1)
+        self.num_classes = 0 if self.semantic is None else self.semantic.shape[2]
+
+    def c_struct(self):
+        """cvo_stereo_frame_t over this frame's arrays (which must outlive it)."""
+        ptr = lambda a: None if a is None else a.ctypes.data
+        return _capi.cvo_stereo_frame_t(self.rows, self.cols, self.channels, ptr(self.image), ptr(self.gray), ptr(self.disparity),
+                                        self.fx, self.fy, self.cx, self.cy, self.baseline, self.num_classes, ptr(self.semantic))
+
+
+def _raise(rc, text):
+    e = CvoError(f"error {rc}: {text}")
+    e.code = rc
+    raise e
+
+
+def _fast_select(call, gray, schedule):
+    """Shared by CvoGPU.fast_select and fast_select_host -> (rc, pixel indices, threshold used)."""
+    gray = np.ascontiguousarray(gray, np.uint8)
+    rows, cols = gray.shape
+    pixel = np.zeros(max(rows * cols, 1), np.int32)
+    n, used = C.c_int(), C.c_int()
+    sched = _capi.cvo_fast_schedule_t(*[int(v) for v in schedule])
+    rc = call(rows, cols, gray.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(sched), pixel.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n), C.byref(used))
+    return rc, pixel[:n.value].copy(), used.value
+
+
+def fast_select_host(gray, schedule=FAST_STEREO):
+    """cvo_fast_select_host: the CV_FAST selection of an 8-bit gray plane under `schedule` (thresh, num_want, num_min,
+    break_thresh) on one CPU thread -> (pixel indices v * cols + u in row-major order, the threshold whose keypoints stand)."""
+    rc, pixel, used = _fast_select(_capi.lib().cvo_fast_select_host, gray, schedule)
+    if rc != 0:
+        _raise(rc, "cvo_fast_select_host refused the plane or the schedule")
+    return pixel, used
+
+
+def stereo_points_host(frame, method=CV_FAST):
+    """cvo_stereo_points_host: the CPU twin of CvoGPU.stereo_points, no context."""
+    rc, pc = _rgbd_points(_capi.lib().cvo_stereo_points_host, frame, method)
+    if rc != 0:
+        _raise(rc, "cvo_stereo_points_host refused the frame or the method")
+    return pc
+
+
 class DeviceCloud:
     """A cloud resident in HBM (cvo_cloud*)."""
 
@@ -542,6 +607,59 @@ class CvoGPU:
         out = dict(zip(("edge_selected", "edge_points", "surface_points", "with_depth"), [x.value for x in v]))
         out.update(potentials=list(pots[:nt.value]), counts=list(cnts[:nt.value]), on_device=bool(dev.value))
         return out
+
+    def fast_select(self, gray, schedule=FAST_STEREO):
+        """cvo_fast_select: as fast_select_host, by the context's route (switch STEREO_HOST)."""
+        rc, pixel, used = _fast_select(lambda *a: self.L.cvo_fast_select(self.ctx, *a), gray, schedule)
+        self._check(rc)
+        return pixel, used
+
+    def stereo_points(self, frame, method=CV_FAST):
+        """cvo_stereo_points: CvoPointCloud(ImageStereo, Calibration, method) for method CV_FAST / DSO_EDGES / FULL from the frame's
+        disparity - a CvoPointCloud with F = channels + 2 and `.pixel`, in the reference's order."""
+        rc, pc = _rgbd_points(lambda *a: self.L.cvo_stereo_points(self.ctx, *a), frame, method)
+        self._check(rc)
+        return pc
+
+    def _resident(self, h, n, pixel, is_edge=None):
+        d = DeviceCloud.__new__(DeviceCloud)
+        d.gpu, d.n, d._keep, d.handle = self, n, None, h
+        d.pixel = pixel[:n].copy()
+        if is_edge is not None:
+            d.is_edge = is_edge[:n].astype(bool)
+        return d
+
+    def upload_stereo(self, frame, method=CV_FAST):
+        """cvo_cloud_upload_stereo: the pairwise stereo driver's cloud - stereo_points' rows, resident (mono frames: the 3
+        features zero-padded to 5); `.pixel` per point."""
+        pixel = np.zeros(max(frame.rows * frame.cols, 1), np.int32)
+        n, h, fs = C.c_int(), C.c_void_p(), frame.c_struct()
+        self._check(self.L.cvo_cloud_upload_stereo(self.ctx, C.byref(fs), int(method), C.byref(h), pixel.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n)))
+        return self._resident(h, n.value, pixel)
+
+    def upload_stereo_recipe(self, frame, leaf=None, edge_divisor=5):
+        """cvo_cloud_upload_stereo_recipe: the multi-frame KITTI driver's per-frame block - upload_rgbd's recipe on the stereo
+        points (edge grid leaf / edge_divisor, the driver's divisor is 5); `.pixel` and `.is_edge` per point."""
+        cap = max(2 * frame.rows * frame.cols, 1)
+        pixel, is_edge = np.zeros(cap, np.int32), np.zeros(cap, np.uint8)
+        n, h, fs = C.c_int(), C.c_void_p(), frame.c_struct()
+        self._check(self.L.cvo_cloud_upload_stereo_recipe(self.ctx, C.byref(fs), self._voxel_size(leaf), float(edge_divisor), C.byref(h),
+                                                          pixel.ctypes.data_as(C.POINTER(C.c_int)), is_edge.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                                          C.byref(n)))
+        return self._resident(h, n.value, pixel, is_edge)
+
+    def debug_stereo_stats(self):
+        """cvo_debug_stereo_stats of the last fast_select / stereo_points / upload_stereo / upload_stereo_recipe: thresholds (or
+        potentials) tried and the count at each, the FAST threshold used, the 257 counts per FAST score -1 .. 255, candidates,
+        kept, whether the kernels ran."""
+        cap = 1024
+        nt, used, dev = C.c_int(), C.c_int(), C.c_int()
+        tried, cnts, hist = (C.c_int * cap)(), (C.c_int * cap)(), (C.c_uint * 257)()
+        cand, kept = C.c_ulonglong(), C.c_ulonglong()
+        self._check(self.L.cvo_debug_stereo_stats(self.ctx, cap, C.byref(nt), tried, cnts, C.byref(used), hist, C.byref(cand), C.byref(kept), C.byref(dev)))
+        k = min(nt.value, cap)
+        return dict(tried=list(tried[:k]), counts=list(cnts[:k]), threshold_used=used.value, histogram=np.array(hist[:], np.int64),
+                    candidates=cand.value, kept=kept.value, on_device=bool(dev.value))
 
     def upload_many(self, clouds, threads=None):
         """Uploads a list of clouds with cvo_cloud_upload_many: a pool of host threads inside the library, each cloud

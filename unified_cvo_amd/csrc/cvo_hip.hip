@@ -14,6 +14,8 @@
 //   cvo_irls.hip    multi-frame align (the least-squares solve of CvoBatchIRLS)
 //   cvo_voxel.hip   voxel-grid downsampling: selection on the device or the host, upload of the survivors
 //   cvo_rgbd.hip    RGB-D front end: depth + colour frame to candidate points and to a resident cloud
+//   cvo_fast.hip    the CV_FAST point selection: FAST-9/16 scores, the reference's threshold schedule
+//   cvo_stereo.hip  stereo front end: left frame + disparity to candidate points and to a resident cloud
 #include "cvo_internal.h"
 
 #include "cvo_ctx.hip"
@@ -21,6 +23,8 @@
 #include "cvo_upload.hip"
 #include "cvo_voxel.hip"
 #include "cvo_rgbd.hip"
+#include "cvo_fast.hip"
+#include "cvo_stereo.hip"
 #include "cvo_sched.hip"
 #include "cvo_queue.hip"
 #include "cvo_eval.hip"

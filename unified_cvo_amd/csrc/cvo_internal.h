@@ -138,6 +138,15 @@ struct RgbdStatsAcc {
   int on_device = 0;
 };
 
+// what cvo_debug_stereo_stats reports of the context's last stereo / FAST call (cvo_fast.hip, cvo_stereo.hip)
+struct StereoStatsAcc {
+  std::vector<int> tried, count;  // the selector's schedule: FAST thresholds (CV_FAST) or potentials (DSO_EDGES) tried, pixels at each
+  int threshold_used = -1;        // the FAST threshold whose keypoints stand; -1: no FAST selection ran
+  unsigned hist[257] = {};        // FAST: pixels per score -1 .. 255
+  unsigned long long candidates = 0, kept = 0;  // pixels the keep predicate saw (FULL: every pixel), points it kept
+  int on_device = 0;
+};
+
 struct cvo_ctx {
   int device = 0;
   CtxOptions opt;                          // the switches (cvo_options.h)
@@ -212,6 +221,7 @@ struct cvo_ctx {
   size_t rgbd_scratch_bytes = 0;
   std::vector<unsigned char> rgbd_excl;  // staging of the exclusion bytes of a semantic frame
   RgbdStatsAcc rgbd_last{};
+  StereoStatsAcc stereo_last{};  // (the stereo front end and cvo_fast_select share the RGB-D region)
   double clock_ms_per_tick = 0.0;  // s_memrealtime, calibrated on first use (cvo_debug_kernel_clock)
 };
 

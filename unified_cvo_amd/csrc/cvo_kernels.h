@@ -65,3 +65,5 @@
 #include "cvo_k_irls.h"
 #include "cvo_k_voxel.h"
 #include "cvo_k_rgbd.h"
+#include "cvo_k_fast.h"
+#include "cvo_k_stereo.h"

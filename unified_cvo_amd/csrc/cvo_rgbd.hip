@@ -225,6 +225,8 @@ struct RgbdDevice {
   int *hit = nullptr, *sel = nullptr, *pix = nullptr, *out = nullptr;
   unsigned* blocks = nullptr;
   VoxelCtl* ctl = nullptr;
+  unsigned char* score = nullptr;  // FAST score bytes and the frame's 257-bin histogram (cvo_fast.hip), when asked for
+  unsigned* fast_hist = nullptr;
   int img_channels = 1;
   RgbdCells cells{};
   int n_cells = 0, nb_cells = 0;
@@ -232,7 +234,8 @@ struct RgbdDevice {
 };
 
 // lays the frame's buffers out in the context's RGB-D scratch region and copies image, depth and exclusion bytes up
-int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select, RgbdDevice& d) {
+// (need_fast: room for the FAST detector's score bytes and histogram as well; a frame without a depth image copies none)
+int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select, RgbdDevice& d, bool need_fast = false) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int w = f.cols, h = f.rows;
   const size_t np = (size_t)w * h;
@@ -247,7 +250,7 @@ int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select,
   d.nb_cells = d.n_cells / RGBD_THREADS;
   const GrayView g = gray_view(f);
   d.img_channels = g.channels;
-  const size_t img_bytes = np * (size_t)g.channels, depth_bytes = np * (f.depth_type == CVO_DEPTH_U16 ? 2 : 4);
+  const size_t img_bytes = np * (size_t)g.channels, depth_bytes = f.depth ? np * (f.depth_type == CVO_DEPTH_U16 ? 2 : 4) : 0;
   const size_t n_ths = (size_t)(w / 32) * (h / 32) + RGBD_THS_SLACK, nb = std::max((np + RGBD_THREADS - 1) / RGBD_THREADS, (size_t)d.nb_cells);
   size_t cap = 0;  // candidates of both sets: every pixel (FULL) + the largest selection
   for (int k = 0; k < RGBD_POTS; k++) cap = std::max(cap, (size_t)rgbd_cells(RGBD_POT_MIN + k, w, h));
@@ -261,7 +264,8 @@ int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select,
   const size_t o_ctl = take(sizeof(VoxelCtl)), o_img = take(need_select ? img_bytes : 0), o_depth = take(depth_bytes),
                o_excl = take(f.num_classes > 0 ? np : 0), o_g2 = take(need_select ? sizeof(float) * np : 0), o_ths = take(2 * sizeof(float) * n_ths),
                o_hit = take(sizeof(int) * (size_t)d.n_cells), o_sel = take(sizeof(int) * (size_t)d.n_cells), o_blocks = take(sizeof(unsigned) * nb),
-               o_pix = take(sizeof(int) * cap), o_out = take(sizeof(int) * cap), o_xyz = take(sizeof(float) * 3 * cap);
+               o_pix = take(sizeof(int) * cap), o_out = take(sizeof(int) * cap), o_xyz = take(sizeof(float) * 3 * cap),
+               o_score = take(need_fast ? np : 0), o_fhist = take(need_fast ? sizeof(unsigned) * FAST_BINS : 0);
   if (off > ctx->rgbd_scratch_bytes) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
     if (ctx->rgbd_scratch) (void)hipFree(ctx->rgbd_scratch);
@@ -285,9 +289,11 @@ int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select,
   d.pix = (int*)(b + o_pix);
   d.out = (int*)(b + o_out);
   d.xyz = (float*)(b + o_xyz);
+  d.score = (unsigned char*)(b + o_score);
+  d.fast_hist = (unsigned*)(b + o_fhist);
   hipStream_t st = ctx->upload_stream;
   if (need_select) HIP_TRY(ctx, hipMemcpyAsync(d.img, g.p, img_bytes, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(d.depth, f.depth, depth_bytes, hipMemcpyHostToDevice, st));
+  if (depth_bytes) HIP_TRY(ctx, hipMemcpyAsync(d.depth, f.depth, depth_bytes, hipMemcpyHostToDevice, st));
   if (d.excl) {
     ctx->rgbd_excl.resize(np);  // (lives until the stream has been synchronised: a member, not a local)
     for (size_t p = 0; p < np; p++) ctx->rgbd_excl[p] = rgbd_excluded(f, p) ? 1 : 0;

@@ -1,0 +1,418 @@
+// cvo_stereo.hip -- stereo front end: cvo_stereo_points (CvoPointCloud(ImageStereo, Calibration, CV_FAST / DSO_EDGES / FULL)
+// from a GIVEN disparity map: libelas is not part of this library), cvo_stereo_points_host (the same on one CPU thread, no
+// context), cvo_cloud_upload_stereo (the pairwise KITTI driver's cloud: those rows through the ordinary upload),
+// cvo_cloud_upload_stereo_recipe (the multi-frame KITTI driver's per-frame block, main_multi_frame_irls_kitti.cpp:235-292),
+// cvo_debug_stereo_stats.  The candidates come from cvo_fast.hip (CV_FAST) and the RGB-D section (DSO_EDGES, FULL), features,
+// labels, recipe rows and the voxel passes are the RGB-D section's; what is new here is the keep predicate and the
+// back-projection (cvo_k_stereo.h).  On the device only pixels, disparity and an exclusion byte go up and only pixel indices
+// come back.  A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.
+namespace {
+
+int stereo_validate(const cvo_stereo_frame_t* f, std::string* msg) {
+  auto bad = [&](const std::string& m) {
+    *msg = m;
+    return CVO_E_INVALID;
+  };
+  auto usable = [](float v) { return std::isfinite(v) && v != 0.f; };
+  if (!f) return bad("frame is NULL");
+  if (f->rows < 1 || f->cols < 1) return bad("rows and cols must be >= 1, got " + std::to_string(f->rows) + " x " + std::to_string(f->cols));
+  if (f->channels != 1 && f->channels != 3) return bad("channels must be 1 or 3, got " + std::to_string(f->channels));
+  if (!f->image) return bad("image is NULL");
+  if (!f->disparity) return bad("disparity is NULL");
+  if (!usable(f->fx) || !usable(f->fy)) return bad("fx and fy must be finite and not 0, got " + std::to_string(f->fx) + ", " + std::to_string(f->fy));
+  if (!usable(f->baseline)) return bad("baseline must be finite and not 0, got " + std::to_string(f->baseline));
+  if (f->num_classes < 0 || (f->num_classes > 0 && !f->semantic)) return bad("num_classes > 0 needs the semantic image");
+  if ((long long)f->rows * f->cols > VOX_MAX_POINTS) {
+    *msg = "more than 2^24 pixels";
+    return CVO_E_UNSUPPORTED;
+  }
+  return CVO_OK;
+}
+
+int stereo_method(int method, std::string* msg) {
+  if (method == CVO_SELECT_CV_FAST || method == CVO_SELECT_FULL || method == CVO_SELECT_DSO_EDGES) return CVO_OK;
+  *msg = "point selection method " + std::to_string(method) + " is not supported (CV_FAST, DSO_EDGES and FULL are)";
+  return method >= 0 && method <= CVO_SELECT_FULL ? CVO_E_UNSUPPORTED : CVO_E_INVALID;
+}
+
+// the frame as the RGB-D section reads it: the disparity in place of a float depth image (its gray plane, gradient,
+// exclusion bytes, selector and staging do not look at the calibration)
+cvo_rgbd_frame_t stereo_view(const cvo_stereo_frame_t& f) {
+  cvo_rgbd_frame_t v{};
+  v.rows = f.rows;
+  v.cols = f.cols;
+  v.channels = f.channels;
+  v.image = f.image;
+  v.gray = f.gray;
+  v.depth = f.disparity;
+  v.depth_type = CVO_DEPTH_F32;
+  v.fx = v.fy = v.scaling_factor = 1.f;
+  v.num_classes = f.num_classes;
+  v.semantic = f.semantic;
+  return v;
+}
+
+// the smallest float whose correctly rounded root is >= 55 (the host's sqrtf is IEEE)
+float stereo_far2() {
+  float t = 55.f * 55.f;
+  for (float below = std::nextafterf(t, 0.f); std::sqrt(below) >= 55.f; below = std::nextafterf(t, 0.f)) t = below;
+  return t;
+}
+
+// Eigen 3.3's compute_inverse_size3 on K, in float, every operation rounded on its own
+StereoCalib stereo_calib(const cvo_stereo_frame_t& f) {
+#pragma clang fp contract(off)
+  static const float far2 = stereo_far2();
+  const float invdet = 1.f / (f.fx * f.fy);
+  StereoCalib k;
+  k.k00 = f.fy * invdet;
+  k.k11 = f.fx * invdet;
+  k.k02 = -(f.cx * f.fy) * invdet;
+  k.k12 = -(f.fx * f.cy) * invdet;
+  k.k22 = (f.fx * f.fy) * invdet;
+  k.bf = std::fabs(f.baseline) * f.fx;
+  k.far2 = far2;
+  return k;
+}
+
+cvo_fast_schedule_t stereo_schedule(const cvo_stereo_frame_t& f) {
+  return f.num_classes > 0 ? cvo_fast_schedule_t CVO_FAST_STEREO_SEMANTIC : cvo_fast_schedule_t CVO_FAST_STEREO;
+}
+
+void stereo_geotype(int method, float* t) {
+  t[0] = method == CVO_SELECT_FULL ? 0.5f : (method == CVO_SELECT_CV_FAST ? 1.f : 0.9f);
+  t[1] = method == CVO_SELECT_FULL ? 0.5f : (method == CVO_SELECT_CV_FAST ? 0.f : 0.1f);
+}
+
+void stereo_copy_dso_schedule(const RgbdStatsAcc& r, StereoStatsAcc& st) {
+  st.tried.assign(r.tried, r.tried + r.n_tried);
+  st.count.assign(r.count, r.count + r.n_tried);
+}
+
+// ---- CPU twin: pixels the constructor keeps, in its order, and their coordinates ----
+void stereo_points_cpu(const cvo_stereo_frame_t& f, int method, std::vector<int>& pix, std::vector<float>& xyz, StereoStatsAcc& st) {
+  const int w = f.cols, h = f.rows;
+  const cvo_rgbd_frame_t view = stereo_view(f);
+  const StereoCalib k = stereo_calib(f);
+  pix.clear();
+  xyz.clear();
+  float p3[3];
+  auto consider = [&](int p) {
+    st.candidates++;
+    if (!stereo_point(k, p % w, p / w, w, h, f.disparity[p], p3) || rgbd_excluded(view, (size_t)p)) return;
+    pix.push_back(p);
+    xyz.insert(xyz.end(), p3, p3 + 3);
+  };
+  if (method == CVO_SELECT_FULL) {
+    for (int u = 0; u < w; u++)
+      for (int v = 0; v < h; v++) consider(v * w + u);
+  } else {
+    std::vector<int> cand;
+    if (method == CVO_SELECT_CV_FAST) {
+      fast_select_cpu(gray_view(view), w, h, stereo_schedule(f), cand, st);
+    } else {
+      RgbdStatsAcc r;
+      rgbd_select_cpu(view, cand, r);
+      stereo_copy_dso_schedule(r, st);
+    }
+    for (int p : cand) consider(p);
+  }
+  st.kept += pix.size();
+}
+
+// ---- device route ----
+// keep predicate + back-projection of a candidate list (nullptr: FULL) into d.pix / d.xyz from `at` on.  One synchronisation.
+int stereo_device_backproject(cvo_ctx* ctx, const cvo_stereo_frame_t& f, RgbdDevice& d, const int* list, int n, int at, int* n_out) {
+  *n_out = 0;
+  if (n == 0) return CVO_OK;
+  hipStream_t st = ctx->upload_stream;
+  const int nb = (n + RGBD_THREADS - 1) / RGBD_THREADS;
+  const StereoCalib k = stereo_calib(f);
+  hipLaunchKernelGGL(k_stereo_bp_flag, dim3(nb), dim3(RGBD_THREADS), 0, st, n, list, d.w, d.h, (const float*)d.depth, (const unsigned char*)d.excl, k,
+                     d.blocks);
+  hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, st, nb, d.blocks, d.ctl, 0, (const VoxelBlockStats*)nullptr);
+  hipLaunchKernelGGL(k_stereo_bp_write, dim3(nb), dim3(RGBD_THREADS), 0, st, n, list, d.w, d.h, (const float*)d.depth, (const unsigned char*)d.excl, k,
+                     (const unsigned*)d.blocks, d.pix + at, d.xyz + 3 * (size_t)at);
+  HIP_TRY(ctx, hipGetLastError());
+  VoxelCtl c{};
+  HIP_TRY(ctx, hipMemcpyAsync(&c, d.ctl, sizeof c, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (c.n_kept > (unsigned)n) return fail(ctx, CVO_E_HIP, "stereo back-projection: the device kept more pixels than it was given");
+  *n_out = (int)c.n_kept;
+  return CVO_OK;
+}
+
+// candidates of a method on the device: *list == nullptr is FULL's column-major order
+int stereo_device_candidates(cvo_ctx* ctx, const cvo_stereo_frame_t& f, int method, RgbdDevice& d, StereoStatsAcc& st, const int** list, int* n) {
+  *list = nullptr;
+  *n = f.cols * f.rows;
+  int rc = CVO_OK;
+  if (method == CVO_SELECT_CV_FAST) {
+    rc = fast_device_select(ctx, d, stereo_schedule(f), st, list, n);
+  } else if (method == CVO_SELECT_DSO_EDGES) {
+    RgbdStatsAcc r;
+    rc = rgbd_device_select(ctx, d, r, list, n);
+    stereo_copy_dso_schedule(r, st);
+  }
+  st.candidates += (unsigned long long)*n;
+  return rc;
+}
+
+int stereo_points_device(cvo_ctx* ctx, const cvo_stereo_frame_t& f, int method, std::vector<int>& pix, std::vector<float>& xyz, StereoStatsAcc& st) {
+  RgbdDevice d;
+  int rc = rgbd_device_stage(ctx, stereo_view(f), method != CVO_SELECT_FULL, d, method == CVO_SELECT_CV_FAST);
+  if (rc != CVO_OK) return rc;
+  const int* list = nullptr;
+  int n = 0, kept = 0;
+  if ((rc = stereo_device_candidates(ctx, f, method, d, st, &list, &n)) != CVO_OK) return rc;
+  if ((rc = stereo_device_backproject(ctx, f, d, list, n, 0, &kept)) != CVO_OK) return rc;
+  st.kept = (unsigned long long)kept;
+  if ((rc = rgbd_fetch(ctx, d.pix, kept, pix)) != CVO_OK) return rc;
+  xyz.resize(3 * (size_t)kept);
+  if (kept) {
+    HIP_TRY(ctx, hipMemcpyAsync(xyz.data(), d.xyz, sizeof(float) * 3 * (size_t)kept, hipMemcpyDeviceToHost, ctx->upload_stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
+  }
+  return CVO_OK;
+}
+
+// the constructor's points by the context's route
+int stereo_points_any(cvo_ctx* ctx, const cvo_stereo_frame_t& f, int method, std::vector<int>& pix, std::vector<float>& xyz, StereoStatsAcc& st) {
+  if (stereo_on_host(ctx, f.rows, f.cols)) {
+    stereo_points_cpu(f, method, pix, xyz, st);
+    return CVO_OK;
+  }
+  st.on_device = 1;
+  return stereo_points_device(ctx, f, method, pix, xyz, st);
+}
+
+// rows of the kept pixels other than xyz (host, both routes): the RGB-D constructor's features and labels
+void stereo_point_rows(const cvo_stereo_frame_t& f, int method, const std::vector<int>& pix, float* feat, float* label, float* geotype) {
+  const cvo_rgbd_frame_t view = stereo_view(f);
+  const GrayView g = gray_view(view);
+  const int F = f.channels + 2;
+  float t[2];
+  stereo_geotype(method, t);
+  for (size_t i = 0; i < pix.size(); i++) {
+    if (feat) rgbd_features(view, g, pix[i], feat + F * i);
+    if (label && f.num_classes > 0)
+      std::memcpy(label + i * (size_t)f.num_classes, f.semantic + (size_t)pix[i] * f.num_classes, sizeof(float) * (size_t)f.num_classes);
+    if (geotype) {
+      geotype[2 * i] = t[0];
+      geotype[2 * i + 1] = t[1];
+    }
+  }
+}
+
+// both candidate sets through the voxel grid: pixel indices and coordinates of the survivors, edge first
+int stereo_recipe_pixels(cvo_ctx* ctx, const char* who, const cvo_stereo_frame_t& f, float leaf, float divisor, std::vector<int>& pix,
+                         std::vector<float>& xyz, int* n_edge, StereoStatsAcc& st) {
+  const float s_edge = leaf / divisor;
+  std::string msg;
+  if (voxel_validate(0, nullptr, s_edge, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": leaf / edge_divisor: " + msg);
+  pix.clear();
+  xyz.clear();
+  *n_edge = 0;
+  if (stereo_on_host(ctx, f.rows, f.cols, STEREO_RECIPE_HOST_BELOW)) {
+    for (int pass = 0; pass < 2; pass++) {
+      std::vector<int> cand, kept;
+      std::vector<float> cxyz;
+      stereo_points_cpu(f, pass == 0 ? CVO_SELECT_DSO_EDGES : CVO_SELECT_FULL, cand, cxyz, st);
+      const float s = pass == 0 ? s_edge : leaf;
+      if (voxel_validate((int)cand.size(), cxyz.data(), s, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": " + msg);
+      voxel_select_cpu((int)cand.size(), cxyz.data(), s, kept);
+      for (int k : kept) {
+        pix.push_back(cand[(size_t)k]);
+        xyz.insert(xyz.end(), &cxyz[3 * (size_t)k], &cxyz[3 * (size_t)k] + 3);
+      }
+      if (pass == 0) *n_edge = (int)kept.size();
+    }
+    return CVO_OK;
+  }
+  st.on_device = 1;
+  RgbdDevice d;
+  int rc = rgbd_device_stage(ctx, stereo_view(f), true, d);
+  if (rc != CVO_OK) return rc;
+  const int* list = nullptr;
+  int n_sel = 0, n_e = 0, n_s = 0;
+  if ((rc = stereo_device_candidates(ctx, f, CVO_SELECT_DSO_EDGES, d, st, &list, &n_sel)) != CVO_OK) return rc;
+  if ((rc = stereo_device_backproject(ctx, f, d, list, n_sel, 0, &n_e)) != CVO_OK) return rc;
+  st.candidates += (unsigned long long)f.cols * f.rows;
+  if ((rc = stereo_device_backproject(ctx, f, d, nullptr, f.cols * f.rows, n_e, &n_s)) != CVO_OK) return rc;
+  st.kept = (unsigned long long)n_e + n_s;
+  hipStream_t stream = ctx->upload_stream;
+  int total = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    const int n = pass == 0 ? n_e : n_s, at = pass == 0 ? 0 : n_e;
+    if (n == 0) continue;
+    const int* d_kept = nullptr;
+    rc = voxel_run_device(ctx, n, nullptr, d.xyz + 3 * (size_t)at, pass == 0 ? s_edge : leaf, nullptr, &d_kept);
+    if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + ctx->err);
+    const int nk = (int)ctx->vox_last.n_kept;
+    hipLaunchKernelGGL(k_rgbd_gather, dim3((nk + RGBD_THREADS - 1) / RGBD_THREADS), dim3(RGBD_THREADS), 0, stream, nk, n, d_kept,
+                       (const int*)(d.pix + at), d.out + total);
+    HIP_TRY(ctx, hipGetLastError());
+    total += nk;
+    if (pass == 0) *n_edge = nk;
+  }
+  if ((rc = rgbd_fetch(ctx, d.out, total, pix)) != CVO_OK) return rc;
+  // the survivors' coordinates on the host: the same arithmetic (stereo_point is shared), a few thousand points
+  const StereoCalib k = stereo_calib(f);
+  xyz.resize(3 * pix.size());
+  for (size_t i = 0; i < pix.size(); i++)
+    if ((unsigned)pix[i] >= (unsigned)(f.cols * f.rows) || !stereo_point(k, pix[i] % f.cols, pix[i] / f.cols, f.cols, f.rows, f.disparity[pix[i]], &xyz[3 * i]))
+      return fail(ctx, CVO_E_HIP, std::string(who) + ": the device kept a pixel the predicate rejects");
+  return CVO_OK;
+}
+
+// the refusals every entry point shares (method nullptr: the recipe, which runs DSO_EDGES and FULL)
+int stereo_check(cvo_ctx* ctx, const char* who, const cvo_stereo_frame_t* frame, const int* method, std::string* msg) {
+  const bool dso = !method || *method == CVO_SELECT_DSO_EDGES;
+  int rc = stereo_validate(frame, msg);
+  if (rc == CVO_OK && method) rc = stereo_method(*method, msg);
+  if (rc == CVO_OK && dso) rc = rgbd_threshold_range(frame->cols, frame->rows, msg);
+  if (rc != CVO_OK && ctx) return fail(ctx, rc, std::string(who) + ": " + *msg);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cvo_stereo_points_host(const cvo_stereo_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat, float* label, float* geotype) {
+  std::string msg;
+  const int rc = stereo_check(nullptr, "", frame, &method, &msg);
+  if (rc != CVO_OK) return rc;
+  if (!pixel || !n) return CVO_E_INVALID;
+  try {
+    std::vector<int> pix;
+    std::vector<float> p3;
+    StereoStatsAcc st;
+    stereo_points_cpu(*frame, method, pix, p3, st);
+    stereo_point_rows(*frame, method, pix, feat, label, geotype);
+    if (xyz && !p3.empty()) std::memcpy(xyz, p3.data(), sizeof(float) * p3.size());
+    if (!pix.empty()) std::memcpy(pixel, pix.data(), sizeof(int) * pix.size());
+    *n = (int)pix.size();
+  } catch (const std::exception&) {
+    return CVO_E_NOMEM;
+  }
+  return CVO_OK;
+}
+
+int cvo_stereo_points(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat, float* label,
+                      float* geotype) {
+  if (!ctx) return CVO_E_INVALID;
+  std::string msg;
+  int rc = stereo_check(ctx, "cvo_stereo_points", frame, &method, &msg);
+  if (rc != CVO_OK) return rc;
+  if (!pixel || !n) return fail(ctx, CVO_E_INVALID, "cvo_stereo_points: pixel and n are required");
+  try {
+    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+    std::vector<int> pix;
+    std::vector<float> p3;
+    StereoStatsAcc st;
+    if ((rc = stereo_points_any(ctx, *frame, method, pix, p3, st)) != CVO_OK) return rc;
+    stereo_point_rows(*frame, method, pix, feat, label, geotype);
+    if (xyz && !p3.empty()) std::memcpy(xyz, p3.data(), sizeof(float) * p3.size());
+    if (!pix.empty()) std::memcpy(pixel, pix.data(), sizeof(int) * pix.size());
+    *n = (int)pix.size();
+    ctx->stereo_last = st;
+  } catch (const std::exception& e) {
+    return fail(ctx, CVO_E_NOMEM, std::string("cvo_stereo_points: ") + e.what());
+  }
+  return CVO_OK;
+}
+
+int cvo_cloud_upload_stereo(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, int method, cvo_cloud** out, int* pixel, int* n) {
+  if (!ctx) return CVO_E_INVALID;
+  std::string msg;
+  int rc = stereo_check(ctx, "cvo_cloud_upload_stereo", frame, &method, &msg);
+  if (rc != CVO_OK) return rc;
+  if (!out) return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_stereo: out is NULL");
+  try {
+    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+    std::vector<int> pix;
+    std::vector<float> p3;
+    StereoStatsAcc st;
+    if ((rc = stereo_points_any(ctx, *frame, method, pix, p3, st)) != CVO_OK) return rc;
+    // the rows as cvo_cloud_upload takes them: F = channels + 2 features zero-padded to FD, labels padded / cut to NC
+    const size_t np = pix.size(), F = (size_t)frame->channels + 2, C = (size_t)frame->num_classes;
+    std::vector<float> ft(F * np), lb(C * np), geo(2 * np), feat((size_t)FD * np, 0.f), label(C ? (size_t)NC * np : 0, 0.f);
+    stereo_point_rows(*frame, method, pix, ft.data(), C ? lb.data() : nullptr, geo.data());
+    for (size_t i = 0; i < np; i++) {
+      std::memcpy(&feat[(size_t)FD * i], &ft[F * i], sizeof(float) * std::min(F, (size_t)FD));
+      if (C) std::memcpy(&label[(size_t)NC * i], &lb[C * i], sizeof(float) * std::min(C, (size_t)NC));
+    }
+    HostCloud h{(int)np, (const char*)p3.data(), 12, (const char*)feat.data(), sizeof(float) * FD, C ? (const char*)label.data() : nullptr,
+                sizeof(float) * NC, (const char*)geo.data(), 8};
+    std::vector<StagedCloud> one(1);
+    if ((rc = upload_host_cloud(ctx, h, ctx->upload_stream, &one[0])) != CVO_OK) return rc;
+    if ((rc = finish_uploads(ctx, one)) != CVO_OK) return rc;
+    *out = one[0].c;
+    if (pixel && np) std::memcpy(pixel, pix.data(), sizeof(int) * np);
+    if (n) *n = (int)np;
+    ctx->stereo_last = st;
+  } catch (const std::exception& e) {
+    return fail(ctx, CVO_E_NOMEM, std::string("cvo_cloud_upload_stereo: ") + e.what());
+  }
+  return CVO_OK;
+}
+
+int cvo_cloud_upload_stereo_recipe(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, float leaf, float edge_divisor, cvo_cloud** out, int* pixel,
+                                   unsigned char* is_edge, int* n) {
+  if (!ctx) return CVO_E_INVALID;
+  std::string msg;
+  int rc = stereo_check(ctx, "cvo_cloud_upload_stereo_recipe", frame, nullptr, &msg);
+  if (rc != CVO_OK) return rc;
+  if (!out) return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_stereo_recipe: out is NULL");
+  if (voxel_validate(0, nullptr, leaf, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_stereo_recipe: leaf: " + msg);
+  if (!std::isfinite(edge_divisor) || !(edge_divisor > 0.f))
+    return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_stereo_recipe: edge_divisor must be finite and > 0, got " + std::to_string(edge_divisor));
+  try {
+    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+    std::vector<int> pix;
+    std::vector<float> xyz;
+    StereoStatsAcc st;
+    int n_edge = 0;
+    if ((rc = stereo_recipe_pixels(ctx, "cvo_cloud_upload_stereo_recipe", *frame, leaf, edge_divisor, pix, xyz, &n_edge, st)) != CVO_OK) return rc;
+    const size_t np = pix.size();
+    std::vector<float> feat((size_t)FD * np), geo(2 * np);
+    const cvo_rgbd_frame_t view = stereo_view(*frame);
+    const GrayView g = gray_view(view);
+    float unused[3];
+    for (size_t i = 0; i < np; i++) rgbd_recipe_row(view, g, pix[i], (int)i < n_edge, unused, &feat[(size_t)FD * i], &geo[2 * i]);
+    HostCloud h{(int)np, (const char*)xyz.data(), 12, (const char*)feat.data(), sizeof(float) * FD, nullptr, 0, (const char*)geo.data(), 8};
+    std::vector<StagedCloud> one(1);
+    if ((rc = upload_host_cloud(ctx, h, ctx->upload_stream, &one[0])) != CVO_OK) return rc;
+    if ((rc = finish_uploads(ctx, one)) != CVO_OK) return rc;
+    *out = one[0].c;
+    if (pixel && np) std::memcpy(pixel, pix.data(), sizeof(int) * np);
+    if (is_edge)
+      for (size_t i = 0; i < np; i++) is_edge[i] = (int)i < n_edge ? 1 : 0;
+    if (n) *n = (int)np;
+    ctx->stereo_last = st;
+  } catch (const std::exception& e) {
+    return fail(ctx, CVO_E_NOMEM, std::string("cvo_cloud_upload_stereo_recipe: ") + e.what());
+  }
+  return CVO_OK;
+}
+
+int cvo_debug_stereo_stats(cvo_ctx* ctx, int capacity, int* n_tried, int* thresholds, int* counts, int* threshold_used, unsigned* histogram,
+                           unsigned long long* candidates, unsigned long long* kept, int* on_device) {
+  if (!ctx || capacity < 0) return CVO_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  const StereoStatsAcc& s = ctx->stereo_last;
+  if (n_tried) *n_tried = (int)s.tried.size();
+  for (int i = 0; i < (int)s.tried.size() && i < capacity; i++) {
+    if (thresholds) thresholds[i] = s.tried[(size_t)i];
+    if (counts) counts[i] = s.count[(size_t)i];
+  }
+  if (threshold_used) *threshold_used = s.threshold_used;
+  if (histogram) std::memcpy(histogram, s.hist, sizeof s.hist);
+  if (candidates) *candidates = s.candidates;
+  if (kept) *kept = s.kept;
+  if (on_device) *on_device = s.on_device;
+  return CVO_OK;
+}
+
+}  // extern "C"

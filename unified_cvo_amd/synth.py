@@ -229,3 +229,34 @@ def rgbd_frame(kind="textured", rows=480, cols=640, seed=0, depth="u16", channel
         np.put_along_axis(sem, cls[..., None], 0.9, axis=2)
         out["semantic"] = sem
     return out
+
+
+def stereo_frame(kind="textured", rows=376, cols=1241, seed=0, channels=3, num_classes=0, shift=0.0, nan_pixels=True):
+    """A seeded synthetic stereo frame as a dict of arrays (the fields of api.StereoFrame): the left image is rgbd_frame's
+    texture; the disparity is fx * baseline over rgbd_frame's synthetic depth stretched to street depths (4 .. 50 m) with KITTI-like intrinsics
+    scaled to the image (fx * baseline = 707.09 * 0.54 at 1241 columns).  Holes are coded -10 (libelas's invalid marker); a few
+    pixels inside the region the constructor keeps hold exactly 0.05f, the float just below it, 0, +inf and - nan_pixels -
+    NaN; a far band has depths around the 55 m cut."""
+    base = rgbd_frame(kind, rows, cols, seed, "f32", channels, num_classes, shift)
+    v, u = np.meshgrid(np.arange(rows, dtype=np.float64), np.arange(cols, dtype=np.float64) + shift, indexing="ij")
+    fx = 707.09 * cols / 1241.0
+    fy = 707.09 * rows / 376.0
+    baseline = 0.54
+    z = np.where(np.isnan(base["depth"]), 1.0, base["depth"]).astype(np.float64)
+    depth = 4.0 + 10.0 * (4.9 - z)                                     # 4 .. 41 m, nearer towards the bottom
+    depth = np.where((u - shift > cols * 0.7) & (u - shift < cols * 0.8), 40.0 + 20.0 * (1.0 - v / max(rows - 1, 1)), depth)  # 40 .. 60 m band
+    disp = (fx * baseline / depth).astype(np.float32)
+    disp[np.isnan(base["depth"]) | (base["depth"] == 0)] = -10.0
+    r0 = min(max(rows - 60, 0), max(rows - 1, 0))                      # a row inside 100 <= v <= rows - 30 when there is one
+    specials = [np.float32(0.05), np.nextafter(np.float32(0.05), np.float32(0)), np.float32(0.0), np.float32(np.inf)]
+    if nan_pixels:
+        specials += [np.float32(np.nan)] * 3
+    for k, val in enumerate(specials):
+        c = 10 + 7 * k
+        if c < cols:
+            disp[r0, c] = val
+            if r0 >= 1:
+                disp[r0 - 1, c] = val
+    out = dict(image=base["image"], disparity=disp, fx=fx, fy=fy, cx=601.8873 * cols / 1241.0, cy=183.1104 * rows / 376.0,
+               baseline=baseline, gray=None, semantic=base["semantic"])
+    return out
