@@ -27,9 +27,14 @@ def ring_differences(gray):
 
 def _has_run_of_9(bits):
     """bits (16, ...) bool around the ring: is there a cyclic run of 9 set bits?"""
-    ext = np.concatenate([bits, bits[:8]]).astype(np.int8)
-    c = np.concatenate([np.zeros((1,) + ext.shape[1:], np.int8), np.cumsum(ext, axis=0, dtype=np.int8)])
-    return np.any(c[9:25] - c[0:16] == 9, axis=0)
+    m = np.zeros(bits.shape[1:], np.uint32)  # the ring as a word: bit k = bits[k], bits 16 .. 31 the ring again
+    for k in range(16):
+        m |= bits[k].astype(np.uint32) << np.uint32(k)
+    m |= m << np.uint32(16)
+    run = m.copy()                           # bit k of run: bits k .. k + 8 of the doubled ring are all set
+    for j in range(1, 9):
+        run &= m >> np.uint32(j)
+    return (run & np.uint32(0xFFFF)) != 0
 
 
 def corners(gray, t, d=None):

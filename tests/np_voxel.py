@@ -18,6 +18,19 @@ def reference(xyz, s):
     return np.sort(first).astype(np.int32)
 
 
+def reference_packed(xyz, s):
+    """reference() for frames of millions of points: ONE np.unique over the packed key kx | ky << 21 | kz << 42 of the
+    voxel indices moved to 0 .. 2^21 - 1 (needs |k| < 2^20, what the selection accepts) instead of a row-wise one.
+    test_voxel_cpu.py holds the two equal."""
+    k = voxel_keys(xyz, s)
+    if k.shape[0] == 0:
+        return np.zeros(0, np.int32)
+    assert np.abs(k).max() < 2 ** 20
+    k += 2 ** 20
+    _, first = np.unique(k[:, 0] | (k[:, 1] << 21) | (k[:, 2] << 42), return_index=True)
+    return np.sort(first).astype(np.int32)
+
+
 def scan_order(xyz):
     """The same points in the order a camera delivers them: sorted by image row, then column, of their pinhole
     projection (640 columns over the scene's field of view).  Neighbours in the order share voxels."""

@@ -27,6 +27,13 @@ def test_score_histogram_gives_the_count_at_every_threshold():
         assert np.array_equal(direct, s > t), t
 
 
+def test_run_of_9_on_every_ring():
+    """np_fast._has_run_of_9 works on packed ring words; a plain loop over each of the 65536 rings decides the same."""
+    rings = (np.arange(65536)[None, :] >> np.arange(16)[:, None] & 1).astype(bool)      # (16, 65536): bit k of ring r
+    plain = [any(all(r >> ((k + j) % 16) & 1 for j in range(9)) for k in range(16)) for r in range(65536)]
+    assert np.array_equal(np_fast._has_run_of_9(rings), plain) and sum(plain) == 1025
+
+
 @pytest.mark.parametrize("name", list(HANDMADE))
 def test_twin_equals_the_statement_on_handmade_rings(name):
     img, thresholds = HANDMADE[name]

@@ -24,15 +24,16 @@ def gpu():
     g.close()
 
 
-def _check(gpu, img, sched, name):
-    """The device's selection, schedule record and histogram against the statement's."""
-    pix, used, tried, counts = np_fast.select(img, sched)
+def _check(gpu, img, sched, name, statement=None):
+    """The device's selection, schedule record and histogram against the statement's.  statement: (np_fast.select(img,
+    sched), the score histogram), when the caller has them (test_gpu_large_frames.py shares them between settings)."""
+    (pix, used, tried, counts), hist = statement or (np_fast.select(img, sched), np_fast.histogram(np_fast.score(img)))
     got, got_used = gpu.fast_select(img, sched)
     st = gpu.debug_stereo_stats()
     assert st["on_device"], name
     assert np.array_equal(got, pix) and got_used == used, name
     assert st["tried"] == tried and st["counts"] == counts and st["threshold_used"] == used, (name, st["tried"], tried)
-    assert np.array_equal(st["histogram"], np_fast.histogram(np_fast.score(img))), name
+    assert np.array_equal(st["histogram"], hist), name
     assert st["candidates"] == st["kept"] == len(pix), name
 
 

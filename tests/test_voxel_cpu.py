@@ -40,6 +40,13 @@ def test_host_twin_equals_numpy(case):
     assert np.all(kept[nk:] == SENTINEL)
 
 
+@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+def test_packed_reference_equals_the_row_wise_one(case):
+    """np_voxel.reference_packed (one np.unique over 63-bit keys: what the 2^24-point test can afford) against reference."""
+    _, xyz, s = case
+    assert np.array_equal(np_voxel.reference_packed(xyz, s), np_voxel.reference(xyz, s))
+
+
 def test_reference_rounds_ties_to_even_and_divides():
     assert np_voxel.voxel_keys([[0.375, 0.625, -0.375]], 0.25).tolist() == [[2, 2, -2]]
     rc, kept, nk = select_host([[0.375, 0.625, -0.375], [0.5, 0.5, -0.5], [0.25, 0.75, -0.25]], 0.25)

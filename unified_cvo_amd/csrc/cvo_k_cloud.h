@@ -44,8 +44,11 @@ struct KdJob {
   int* lid;                  // out: the ids in spatial order
 };
 
+// Unsigned integers in the order of the (finite) floats.  -0.0 takes the key of +0.0: the host twin compares floats, to
+// which the two zeros are equal, and then point indices (on the bits, not by adding 0.0f: no rounding or flush mode matters).
 __device__ __forceinline__ unsigned kd_ordered(float v) {
-  const unsigned b = __float_as_uint(v);
+  unsigned b = __float_as_uint(v);
+  if (b == 0x80000000u) b = 0u;
   return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
 }
 // split of a segment of nn points (spatial_order / kd_split in cvo_hip.hip): 0 = the segment is done
