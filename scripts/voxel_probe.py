@@ -13,7 +13,8 @@ makes it) and in scan order (tests/np_voxel.scan_order: image rows, then columns
 around upload_voxel, which returns after the stream has been synchronised; the median and the spread of --reps calls
 after two warm-up calls per route.  voxel_select alone (coordinates up, indices back) is timed the same way.
 --kernels runs every (frame, leaf, pre-pass) once more than it warms up, so that the per-kernel statistics of the trace
-(k_voxel_insert<true> / <false>, k_voxel_flag, k_voxel_scan, k_voxel_compact) average over equal numbers of both forms.
+(k_voxel_insert<true> / <false>, k_compact_count<VoxelFirst>, k_voxel_scan, k_compact_write<VoxelFirst>) average over equal
+numbers of both forms.
 """
 import argparse
 import json
@@ -64,7 +65,8 @@ def trace_summary(path, sizes):
     import csv
     rows = sorted(csv.DictReader(open(path)), key=lambda r: int(r["Start_Timestamp"]))
     us = lambda r: (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
-    by = {k: [us(r) for r in rows if "k_voxel_" + k in r["Kernel_Name"]] for k in ("insert", "flag", "scan", "compact")}
+    names = {"insert": "k_voxel_insert", "count": "k_compact_count", "scan": "k_voxel_scan", "write": "k_compact_write"}
+    by = {k: [us(r) for r in rows if name in r["Kernel_Name"]] for k, name in names.items()}
     forms = ["<true>" in r["Kernel_Name"] for r in rows if "k_voxel_insert" in r["Kernel_Name"]]
     i = 0
     for n in sizes:
@@ -73,9 +75,9 @@ def trace_summary(path, sizes):
                 for name, _ in ROUTES[:2]:
                     sl = slice(5 * i, 5 * i + 5)
                     assert all(f == (name == "prepass") for f in forms[sl]), "not a --kernels trace of these sizes"
-                    rest = sum(sum(by[k][sl]) / 5 for k in ("flag", "scan", "compact"))
+                    rest = sum(sum(by[k][sl]) / 5 for k in ("count", "scan", "write"))
                     print(f"{n:8d} {order:8s} leaf {s:<4} {name:8s} k_voxel_insert us " + " ".join(f"{v:6.1f}" for v in by["insert"][sl])
-                          + f" | flag + scan + compact {rest:5.1f}")
+                          + f" | count + scan + write {rest:5.1f}")
                     i += 1
 
 

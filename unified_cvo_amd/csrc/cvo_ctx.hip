@@ -326,8 +326,8 @@ void cvo_ctx_destroy(cvo_ctx* c) {
   drop_graphs(c);
   free_workspace(c);
   if (c->d_kd_jobs) (void)hipFree(c->d_kd_jobs);
-  if (c->vox_scratch) (void)hipFree(c->vox_scratch);
-  if (c->rgbd_scratch) (void)hipFree(c->rgbd_scratch);
+  c->vox_scratch.release();
+  c->rgbd_scratch.release();
   for (int g = 0; g < cvo_ctx::MAX_GROUPS; g++) {
     for (int i = 0; i < 2; i++)
       if (c->ev_chk[i][g]) (void)hipEventDestroy(c->ev_chk[i][g]);

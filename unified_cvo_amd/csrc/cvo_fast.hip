@@ -106,7 +106,7 @@ void fast_select_cpu(const GrayView& g, int w, int h, const cvo_fast_schedule_t&
 int fast_device_select(cvo_ctx* ctx, RgbdDevice& d, const cvo_fast_schedule_t& s, StereoStatsAcc& stats, const int** list, int* n) {
   hipStream_t st = ctx->upload_stream;
   const int w = d.w, h = d.h, np = w * h;
-  const int nb_score = ((w + FAST_TILE_W - 1) / FAST_TILE_W) * ((h + FAST_TILE_H - 1) / FAST_TILE_H), nb = (np + RGBD_THREADS - 1) / RGBD_THREADS;
+  const int nb_score = ((w + FAST_TILE_W - 1) / FAST_TILE_W) * ((h + FAST_TILE_H - 1) / FAST_TILE_H);
   HIP_TRY(ctx, hipMemsetAsync(d.fast_hist, 0, sizeof(unsigned) * FAST_BINS, st));
   if (ctx->opt.fast_tile)
     hipLaunchKernelGGL(k_fast_score<true>, dim3(nb_score), dim3(RGBD_THREADS), 0, st, w, h, d.img_channels, (const unsigned char*)d.img, d.score, d.fast_hist);
@@ -126,11 +126,7 @@ int fast_device_select(cvo_ctx* ctx, RgbdDevice& d, const cvo_fast_schedule_t& s
   *list = d.out;
   *n = count[t];
   if (*n == 0) return CVO_OK;
-  hipLaunchKernelGGL(k_fast_flag, dim3(nb), dim3(RGBD_THREADS), 0, st, np, (const unsigned char*)d.score, t, d.blocks);
-  hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, st, nb, d.blocks, d.ctl, 0, (const VoxelBlockStats*)nullptr);
-  hipLaunchKernelGGL(k_fast_compact, dim3(nb), dim3(RGBD_THREADS), 0, st, np, (const unsigned char*)d.score, t, (const unsigned*)d.blocks, d.out);
-  HIP_TRY(ctx, hipGetLastError());
-  return CVO_OK;
+  return compact(ctx, np, FastAbove{d.score, t, d.out}, d.blocks, d.ctl);  // (no synchronisation: the selection stays on the device)
 }
 
 // a gray plane as the frame the RGB-D staging lays out: one channel, no depth, no classes
@@ -155,17 +151,14 @@ int cvo_fast_select_host(int rows, int cols, const uint8_t* gray, const cvo_fast
   if (rc == CVO_OK) rc = fast_validate_schedule(schedule, &msg);
   if (rc != CVO_OK) return rc;
   if (!pixel || !n) return CVO_E_INVALID;
-  try {
+  return frontend_call(nullptr, "", [&] {
     std::vector<int> pix;
     StereoStatsAcc st;
     fast_select_cpu(GrayView{gray, 1}, cols, rows, *schedule, pix, st);
-    if (!pix.empty()) std::memcpy(pixel, pix.data(), sizeof(int) * pix.size());
-    *n = (int)pix.size();
+    copy_kept(pix, pixel, n);
     if (threshold_used) *threshold_used = st.threshold_used;
-  } catch (const std::exception&) {
-    return CVO_E_NOMEM;
-  }
-  return CVO_OK;
+    return CVO_OK;
+  });
 }
 
 int cvo_fast_select(cvo_ctx* ctx, int rows, int cols, const uint8_t* gray, const cvo_fast_schedule_t* schedule, int* pixel, int* n,
@@ -179,8 +172,7 @@ int cvo_fast_select(cvo_ctx* ctx, int rows, int cols, const uint8_t* gray, const
     msg = "pixel and n are required";
   }
   if (rc != CVO_OK) return fail(ctx, rc, "cvo_fast_select: " + msg);
-  try {
-    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  return frontend_call(ctx, "cvo_fast_select", [&] {
     std::vector<int> pix;
     StereoStatsAcc st;
     if (stereo_on_host(ctx, rows, cols)) {
@@ -189,20 +181,17 @@ int cvo_fast_select(cvo_ctx* ctx, int rows, int cols, const uint8_t* gray, const
       st.on_device = 1;
       RgbdDevice d;
       const int* list = nullptr;
-      int k = 0;
+      int k = 0, rc;
       if ((rc = rgbd_device_stage(ctx, fast_plane_frame(rows, cols, gray), true, d, true)) != CVO_OK) return rc;
       if ((rc = fast_device_select(ctx, d, *schedule, st, &list, &k)) != CVO_OK) return rc;
       if ((rc = rgbd_fetch(ctx, list, k, pix)) != CVO_OK) return rc;
     }
     st.candidates = st.kept = pix.size();
-    if (!pix.empty()) std::memcpy(pixel, pix.data(), sizeof(int) * pix.size());
-    *n = (int)pix.size();
+    copy_kept(pix, pixel, n);
     if (threshold_used) *threshold_used = st.threshold_used;
     ctx->stereo_last = st;
-  } catch (const std::exception& e) {
-    return fail(ctx, CVO_E_NOMEM, std::string("cvo_fast_select: ") + e.what());
-  }
-  return CVO_OK;
+    return CVO_OK;
+  });
 }
 
 }  // extern "C"

@@ -1,0 +1,71 @@
+// cvo_frontend.hip -- what the front ends (cvo_voxel.hip, cvo_rgbd.hip, cvo_fast.hip, cvo_stereo.hip) share on the host: the
+// growable scratch regions (type and layout: cvo_internal.h), the launches of an ordered compaction (cvo_k_compact.h) and
+// the read-back of its total, the frame of an entry point and the copy-out of the kept indices.
+// A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.  Shared declarations: cvo_internal.h.
+
+// Room for `need` bytes: a region that is too small is given back once upload_stream has drained and allocated anew.
+int DeviceScratch::reserve(cvo_ctx* ctx, size_t need, const char* what) {
+  if (need <= bytes) return CVO_OK;
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
+  release();
+  const hipError_t e = hipMalloc(&p, need);
+  if (e != hipSuccess) {
+    p = nullptr;
+    return fail(ctx, CVO_E_NOMEM, std::string(what) + " hipMalloc: " + hipGetErrorString(e));
+  }
+  bytes = need;
+  return CVO_OK;
+}
+
+namespace {
+
+// An ordered compaction of n elements whose per-block counts are already in `blocks` (k_rgbd_select makes them itself):
+// k_voxel_scan turns them into offsets and leaves the total in ctl->n_kept - summing n_stats block statistics of
+// k_voxel_insert on the way -, k_compact_write<P> writes the survivors.  On upload_stream, no synchronisation.
+template <class P>
+int compact_counted(cvo_ctx* ctx, int n, const P& pred, unsigned* blocks, VoxelCtl* ctl, int n_stats = 0, const VoxelBlockStats* stats = nullptr) {
+  const int nb = (n + COMPACT_THREADS - 1) / COMPACT_THREADS;
+  hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, ctx->upload_stream, nb, blocks, ctl, n_stats, stats);
+  hipLaunchKernelGGL(k_compact_write<P>, dim3(nb), dim3(COMPACT_THREADS), 0, ctx->upload_stream, n, pred, (const unsigned*)blocks);
+  HIP_TRY(ctx, hipGetLastError());
+  return CVO_OK;
+}
+
+// count -> scan -> write
+template <class P>
+int compact(cvo_ctx* ctx, int n, const P& pred, unsigned* blocks, VoxelCtl* ctl, int n_stats = 0, const VoxelBlockStats* stats = nullptr) {
+  hipLaunchKernelGGL(k_compact_count<P>, dim3((n + COMPACT_THREADS - 1) / COMPACT_THREADS), dim3(COMPACT_THREADS), 0, ctx->upload_stream, n, pred, blocks);
+  return compact_counted(ctx, n, pred, blocks, ctl, n_stats, stats);
+}
+
+// what a compaction left in ctl: one copy, one synchronisation.  A total above n is refused as `who`: the device kept more `what` than it was given.
+int compact_total(cvo_ctx* ctx, const VoxelCtl* ctl, int n, const char* who, const char* what, VoxelCtl* h) {
+  HIP_TRY(ctx, hipMemcpyAsync(h, ctl, sizeof *h, hipMemcpyDeviceToHost, ctx->upload_stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
+  if (h->n_kept > (unsigned)n) return fail(ctx, CVO_E_HIP, std::string(who) + ": the device kept more " + what + " than it was given");
+  return CVO_OK;
+}
+
+// The frame of a front end's entry point once its arguments are checked: body() under the context's upload_mutex; an
+// exception (the allocation of a host buffer) becomes CVO_E_NOMEM with its text.  The _host entry points have no context:
+// nothing to lock, the bare code.
+template <class Body>
+int frontend_call(cvo_ctx* ctx, const char* who, Body body) {
+  try {
+    std::unique_lock<std::mutex> lk;
+    if (ctx) lk = std::unique_lock<std::mutex>(ctx->upload_mutex);
+    return body();
+  } catch (const std::exception& e) {
+    return fail(ctx, CVO_E_NOMEM, std::string(who) + ": " + e.what());
+  }
+}
+
+// the kept indices, their number and - n_edge >= 0 - the flag of the first n_edge of them, to the caller's arrays that are given
+void copy_kept(const std::vector<int>& kept, int* out, int* n, unsigned char* is_edge = nullptr, int n_edge = -1) {
+  if (out && !kept.empty()) std::memcpy(out, kept.data(), sizeof(int) * kept.size());
+  if (is_edge)
+    for (size_t i = 0; i < kept.size(); i++) is_edge[i] = (int)i < n_edge ? 1 : 0;
+  if (n) *n = (int)kept.size();
+}
+
+}  // namespace

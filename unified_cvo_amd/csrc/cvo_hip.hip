@@ -12,6 +12,7 @@
 //   cvo_queue.hip   the batch queue                                    cvo_eval.hip    inner products, single evaluations
 //   cvo_export.hip  association / ELL exports                          cvo_debug.hip   test and profiling hooks
 //   cvo_irls.hip    multi-frame align (the least-squares solve of CvoBatchIRLS)
+//   cvo_frontend.hip  what the four front ends below share: scratch regions, the ordered-compaction launcher, the entry frame
 //   cvo_voxel.hip   voxel-grid downsampling: selection on the device or the host, upload of the survivors
 //   cvo_rgbd.hip    RGB-D front end: depth + colour frame to candidate points and to a resident cloud
 //   cvo_fast.hip    the CV_FAST point selection: FAST-9/16 scores, the reference's threshold schedule
@@ -21,6 +22,7 @@
 #include "cvo_ctx.hip"
 #include "cvo_launch.hip"
 #include "cvo_upload.hip"
+#include "cvo_frontend.hip"
 #include "cvo_voxel.hip"
 #include "cvo_rgbd.hip"
 #include "cvo_fast.hip"

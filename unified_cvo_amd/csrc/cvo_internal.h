@@ -1,5 +1,5 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
 // pair, graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -147,6 +147,28 @@ struct StereoStatsAcc {
   int on_device = 0;
 };
 
+// offsets of a call's buffers in one device allocation, 256-byte aligned; `off` ends as the bytes to allocate
+struct ScratchLayout {
+  size_t off = 0;
+  size_t take(size_t bytes) {
+    const size_t o = off;
+    off = align_up(off + bytes, 256);
+    return o;
+  }
+};
+
+// a growable device region of a front end, laid out anew by every call and used on upload_stream under upload_mutex
+struct DeviceScratch {
+  char* p = nullptr;
+  size_t bytes = 0;
+  int reserve(cvo_ctx* ctx, size_t need, const char* what);  // cvo_frontend.hip; what: "voxel scratch", "RGB-D scratch"
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
+};
+
 struct cvo_ctx {
   int device = 0;
   CtxOptions opt;                          // the switches (cvo_options.h)
@@ -210,15 +232,13 @@ struct cvo_ctx {
   bool queue_open = false;  // a cvo_batch_queue owns the workspace: the other align / evaluation calls are refused meanwhile
   cvo_batch_queue* queue = nullptr;  // ... that queue (cvo_ctx_destroy releases its device side, see queue_release)
   // voxel selection (cvo_voxel.hip): one growable device region - coordinates, table, per-point slots, block counts, kept
-  // indices, VoxelCtl - used on upload_stream under upload_mutex; the last selection's table size and counters
-  char* vox_scratch = nullptr;
-  size_t vox_scratch_bytes = 0;
+  // indices, VoxelCtl -; the last selection's table size and counters
+  DeviceScratch vox_scratch;
   unsigned long long vox_capacity = 0;  // 0: the last selection ran on the host (or none has run)
   VoxelCtl vox_last{};
   // RGB-D front end (cvo_rgbd.hip): one growable device region - image, depth, exclusion bytes, g2, thresholds, cell hits,
-  // candidate pixels and their coordinates - used on upload_stream under upload_mutex like the voxel region
-  char* rgbd_scratch = nullptr;
-  size_t rgbd_scratch_bytes = 0;
+  // candidate pixels and their coordinates (the recipes use both regions at once)
+  DeviceScratch rgbd_scratch;
   std::vector<unsigned char> rgbd_excl;  // staging of the exclusion bytes of a semantic frame
   RgbdStatsAcc rgbd_last{};
   StereoStatsAcc stereo_last{};  // (the stereo front end and cvo_fast_select share the RGB-D region)

@@ -9,7 +9,7 @@
 //                   detector's keypoint counts at all 256 thresholds, so the host replays the threshold schedule on 257
 //                   numbers.  TILE: the block's 64 x 16 pixels and their 3-pixel halo go through LDS (a BGR image is
 //                   converted once per pixel, not 17 times); otherwise every lane reads its ring through the cache.
-//   k_fast_flag / k_fast_compact   ordered (row-major) compaction of the pixels with score > t.
+//   FastAbove       predicate of the ordered (row-major) compaction (cvo_k_compact.h): the pixels with score > t.
 //
 // All integer arithmetic: nothing to round.  Part of the kernel set of cvo_kernels.h.
 #pragma once
@@ -91,16 +91,16 @@ __global__ __launch_bounds__(RGBD_THREADS) void k_fast_score(int w, int h, int c
     if (bins[b]) atomicAdd(&hist[b], bins[b]);
 }
 
-__global__ __launch_bounds__(RGBD_THREADS) void k_fast_flag(int n, const unsigned char* __restrict__ score, int t, unsigned* __restrict__ block_count) {
-  const int p = blockIdx.x * RGBD_THREADS + (int)threadIdx.x;
-  rgbd_block_count(p < n && (int)score[p] > t, block_count);
-}
-
-__global__ __launch_bounds__(RGBD_THREADS) void k_fast_compact(int n, const unsigned char* __restrict__ score, int t,
-                                                              const unsigned* __restrict__ block_offset, int* __restrict__ out) {
-  const int p = blockIdx.x * RGBD_THREADS + (int)threadIdx.x;
-  const unsigned at = rgbd_block_place(p < n && (int)score[p] > t, block_offset);
-  if (at < (unsigned)n) out[at] = p;  // (at most n pixels are kept: never out of bounds; ~0u of the others fails the test)
-}
+struct FastAbove {
+  typedef int Item;  // the pixel
+  const unsigned char* score;
+  int t;
+  int* out;
+  __device__ bool keep(int p, int n, Item* item) const {
+    *item = p;
+    return p < n && (int)score[p] > t;
+  }
+  __device__ void write(unsigned at, const Item& p) const { out[at] = p; }
+};
 
 }  // namespace cvo_dev

@@ -9,10 +9,12 @@
 //   k_rgbd_select       one lane per pot x pot cell, for EVERY potential the schedule can ask for (2 .. 7) in one launch:
 //                       the first pixel in row-major order with the largest g2 strictly above its threshold.  Cells are
 //                       enumerated in the reference's nesting (blocks of 4 pot, 2 pot, pot, each row-major), padded to whole
-//                       4 pot blocks, so an ORDERED compaction (k_voxel_scan over the block counts, k_rgbd_compact) gives
-//                       output_uv of select() (:270-426) for each potential.  No atomic decides a position.
-//   k_rgbd_bp_flag / k_rgbd_bp_write   depth test (dep != 0 && !isnan(dep)) and exclusion byte over a pixel list - FULL's
-//                       column-major order or a selected list -, ordered compaction, xyz of the survivors.
+//                       4 pot blocks, so an ORDERED compaction (k_voxel_scan over the block counts it writes itself,
+//                       k_compact_write<RgbdCellHit>) gives output_uv of select() (:270-426) for each potential.  No atomic
+//                       decides a position.
+//   RgbdKeep            predicate of the ordered compaction (cvo_k_compact.h) over a pixel list - FULL's column-major order
+//                       or a selected list -: depth test (dep != 0 && !isnan(dep)) and exclusion byte; writes the pixel
+//                       index and xyz of the survivors.
 //   k_rgbd_gather       out[i] = pixel[kept[i]]: only the survivors' pixel indices go back to the host.
 //
 // Every value here is exact or correctly rounded: g2 is a multiple of 0.25 below 2^16, the root is an integer root of
@@ -23,7 +25,7 @@
 
 namespace cvo_dev {
 
-constexpr int RGBD_THREADS = VOX_THREADS;  // (k_voxel_scan scans the block counts of the compactions here)
+constexpr int RGBD_THREADS = COMPACT_THREADS;  // (k_rgbd_select counts per block for the ordered compaction)
 constexpr int RGBD_POT_MIN = 2, RGBD_POT_MAX = 7, RGBD_POTS = RGBD_POT_MAX - RGBD_POT_MIN + 1;
 constexpr int RGBD_THS_SLACK = 100;        // thsSmoothed has (w/32)(h/32) + 100 entries (CvoPixelSelector.cpp:63)
 enum : int { RGBD_DEPTH_U16 = 0, RGBD_DEPTH_F32 = 1 };
@@ -143,32 +145,6 @@ __host__ __device__ inline int rgbd_cells(int pot, int w, int h) {
   return ((w + 4 * pot - 1) / (4 * pot)) * ((h + 4 * pot - 1) / (4 * pot)) * 16;
 }
 
-// per-block count of `keep` -> block_count[blockIdx.x]; every thread of the block calls it
-__device__ __forceinline__ void rgbd_block_count(bool keep, unsigned* __restrict__ block_count) {
-  __shared__ unsigned wcnt[RGBD_THREADS / 64];
-  const unsigned long long m = __ballot(keep);
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = (unsigned)__popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned c = 0;
-    for (int v = 0; v < RGBD_THREADS / 64; v++) c += wcnt[v];
-    block_count[blockIdx.x] = c;
-  }
-}
-
-// position of a kept element in the ordered output, or ~0u; every thread of the block calls it
-__device__ __forceinline__ unsigned rgbd_block_place(bool keep, const unsigned* __restrict__ block_offset) {
-  __shared__ unsigned wcnt[RGBD_THREADS / 64];
-  const unsigned long long m = __ballot(keep);
-  const unsigned lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) wcnt[wv] = (unsigned)__popcll(m);
-  __syncthreads();
-  if (!keep) return ~0u;
-  unsigned at = block_offset[blockIdx.x] + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-  for (unsigned v = 0; v < wv; v++) at += wcnt[v];
-  return at;
-}
-
 __global__ __launch_bounds__(RGBD_THREADS) void k_rgbd_select(int w, int h, RgbdCells cells, const float* __restrict__ g2,
                                                               const float* __restrict__ sm, int* __restrict__ hit,
                                                               unsigned* __restrict__ block_count) {
@@ -183,16 +159,20 @@ __global__ __launch_bounds__(RGBD_THREADS) void k_rgbd_select(int w, int h, Rgbd
   const int pot = RGBD_POT_MIN + k, c = gid - first;
   const int best = c < rgbd_cells(pot, w, h) ? rgbd_cell_best(c, pot, w, h, g2, sm) : -1;
   hit[gid] = best;
-  rgbd_block_count(best >= 0, block_count);
+  compact_block_count(best >= 0, block_count);
 }
 
-__global__ __launch_bounds__(RGBD_THREADS) void k_rgbd_compact(int n, const int* __restrict__ hit, const unsigned* __restrict__ block_offset,
-                                                               int* __restrict__ out) {
-  const int gid = blockIdx.x * RGBD_THREADS + (int)threadIdx.x;
-  const int v = gid < n ? hit[gid] : -1;
-  const unsigned at = rgbd_block_place(v >= 0, block_offset);
-  if (at < (unsigned)n) out[at] = v;  // (at most n cells hit: never out of bounds; ~0u of the others fails the test)
-}
+// the write side of k_rgbd_select's compaction: hit[] in order, without the cells that hit nothing
+struct RgbdCellHit {
+  typedef int Item;  // the cell's pixel
+  const int* hit;
+  int* out;
+  __device__ bool keep(int i, int n, Item* v) const {
+    *v = i < n ? hit[i] : -1;
+    return *v >= 0;
+  }
+  __device__ void write(unsigned at, const Item& v) const { out[at] = v; }
+};
 
 // the depth of pixel p in metres x scaling factor, and whether the reference keeps it: dep != 0 && !isnan(dep)
 __host__ __device__ inline bool rgbd_depth(const void* depth, int depth_type, size_t p, float* dep) {
@@ -228,32 +208,29 @@ __device__ __forceinline__ bool rgbd_candidate(int i, int n, const int* __restri
   return rgbd_depth(depth, depth_type, (size_t)p, dep) && !(excl && excl[p]);
 }
 
-__global__ __launch_bounds__(RGBD_THREADS) void k_rgbd_bp_flag(int n, const int* __restrict__ list, int w, int h, const void* __restrict__ depth,
-                                                               int depth_type, const unsigned char* __restrict__ excl,
-                                                               unsigned* __restrict__ block_count) {
-  int pix = 0;
-  float dep = 0.f;
-  const bool keep = rgbd_candidate(blockIdx.x * RGBD_THREADS + (int)threadIdx.x, n, list, w, h, depth, depth_type, excl, &pix, &dep);
-  rgbd_block_count(keep, block_count);
-}
-
-__global__ __launch_bounds__(RGBD_THREADS) void k_rgbd_bp_write(int n, const int* __restrict__ list, int w, int h, const void* __restrict__ depth,
-                                                                int depth_type, const unsigned char* __restrict__ excl, RgbdCalib calib,
-                                                                const unsigned* __restrict__ block_offset, int* __restrict__ pix_out,
-                                                                float* __restrict__ xyz) {
-  int pix = 0;
-  float dep = 0.f;
-  const bool keep = rgbd_candidate(blockIdx.x * RGBD_THREADS + (int)threadIdx.x, n, list, w, h, depth, depth_type, excl, &pix, &dep);
-  const unsigned at = rgbd_block_place(keep, block_offset);
-  if (at < (unsigned)n) {
+struct RgbdKeep {
+  struct Item {
+    int pix;
+    float dep;
+  };
+  const int* list;
+  int w, h;
+  const void* depth;
+  int depth_type;
+  const unsigned char* excl;
+  RgbdCalib calib;
+  int* pix_out;
+  float* xyz;
+  __device__ bool keep(int i, int n, Item* c) const { return rgbd_candidate(i, n, list, w, h, depth, depth_type, excl, &c->pix, &c->dep); }
+  __device__ void write(unsigned at, const Item& c) const {
     float p[3];
-    rgbd_backproject(calib, pix % w, pix / w, dep, p);
-    pix_out[at] = pix;
+    rgbd_backproject(calib, c.pix % w, c.pix / w, c.dep, p);
+    pix_out[at] = c.pix;
     xyz[3 * (size_t)at] = p[0];
     xyz[3 * (size_t)at + 1] = p[1];
     xyz[3 * (size_t)at + 2] = p[2];
   }
-}
+};
 
 __global__ __launch_bounds__(RGBD_THREADS) void k_rgbd_gather(int n, int n_src, const int* __restrict__ kept, const int* __restrict__ pix,
                                                               int* __restrict__ out) {

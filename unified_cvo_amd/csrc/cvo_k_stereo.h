@@ -1,9 +1,10 @@
 // cvo_k_stereo.h -- stereo front end: from candidate pixels and a disparity map to the points of
 // CvoPointCloud(ImageStereo, Calibration, method) (CvoPointCloud.cpp:680-773, StaticStereo.cpp:84-107, is_good_point :39-49).
 //
-//   k_stereo_bp_flag / k_stereo_bp_write   the keep predicate and the back-projection over a pixel list - FAST's row-major
-//                       list, a DSO selection - or over FULL's column-major order (list == nullptr), ordered compaction,
-//                       xyz of the survivors.  The candidates come from cvo_k_fast.h / cvo_k_rgbd.h.
+//   StereoKeep          predicate of the ordered compaction (cvo_k_compact.h): the keep predicate and the back-projection
+//                       over a pixel list - FAST's row-major list, a DSO selection - or over FULL's column-major order
+//                       (list == nullptr); writes the pixel index and xyz of the survivors.  The candidates come from
+//                       cvo_k_fast.h / cvo_k_rgbd.h.
 //
 // stereo_point IS the contract's arithmetic, shared with the CPU twin: every product and sum is rounded on its own (the
 // translation unit is compiled with -ffp-contract=off, and the pragma below holds where it is not), the division is IEEE,
@@ -48,29 +49,25 @@ __device__ __forceinline__ bool stereo_candidate(int i, int n, const int* __rest
   return stereo_point(k, p % w, p / w, w, h, disparity[p], xyz) && !(excl && excl[p]);
 }
 
-__global__ __launch_bounds__(RGBD_THREADS) void k_stereo_bp_flag(int n, const int* __restrict__ list, int w, int h,
-                                                                const float* __restrict__ disparity, const unsigned char* __restrict__ excl,
-                                                                StereoCalib calib, unsigned* __restrict__ block_count) {
-  int pix = 0;
-  float p[3];
-  const bool keep = stereo_candidate(blockIdx.x * RGBD_THREADS + (int)threadIdx.x, n, list, w, h, disparity, excl, calib, &pix, p);
-  rgbd_block_count(keep, block_count);
-}
-
-__global__ __launch_bounds__(RGBD_THREADS) void k_stereo_bp_write(int n, const int* __restrict__ list, int w, int h,
-                                                                 const float* __restrict__ disparity, const unsigned char* __restrict__ excl,
-                                                                 StereoCalib calib, const unsigned* __restrict__ block_offset,
-                                                                 int* __restrict__ pix_out, float* __restrict__ xyz) {
-  int pix = 0;
-  float p[3] = {0.f, 0.f, 0.f};
-  const bool keep = stereo_candidate(blockIdx.x * RGBD_THREADS + (int)threadIdx.x, n, list, w, h, disparity, excl, calib, &pix, p);
-  const unsigned at = rgbd_block_place(keep, block_offset);
-  if (at < (unsigned)n) {
-    pix_out[at] = pix;
-    xyz[3 * (size_t)at] = p[0];
-    xyz[3 * (size_t)at + 1] = p[1];
-    xyz[3 * (size_t)at + 2] = p[2];
+struct StereoKeep {
+  struct Item {
+    int pix;
+    float p[3];
+  };
+  const int* list;
+  int w, h;
+  const float* disparity;
+  const unsigned char* excl;
+  StereoCalib calib;
+  int* pix_out;
+  float* xyz;
+  __device__ bool keep(int i, int n, Item* c) const { return stereo_candidate(i, n, list, w, h, disparity, excl, calib, &c->pix, c->p); }
+  __device__ void write(unsigned at, const Item& c) const {
+    pix_out[at] = c.pix;
+    xyz[3 * (size_t)at] = c.p[0];
+    xyz[3 * (size_t)at + 1] = c.p[1];
+    xyz[3 * (size_t)at + 2] = c.p[2];
   }
-}
+};
 
 }  // namespace cvo_dev

@@ -4,19 +4,21 @@
 //   k_voxel_insert   one point per lane: voxel key, open-addressing insert into a table in HBM with a returning 64-bit
 //                    compare-and-swap, unsigned min of the point's index on the slot.  Optionally (PRE) the 1024 points of a
 //                    block first meet in an LDS table and only the block's lowest index of every voxel goes to HBM.
-//   k_voxel_flag     keep = "my index is my slot's minimum"; one count per block of 1024 points.
-//   k_voxel_scan     exclusive scan of the block counts (one block).
-//   k_voxel_compact  writes the kept indices in ascending order.
+//   VoxelFirst       the predicate of the ordered compaction (cvo_k_compact.h): keep = "my index is my slot's minimum";
+//                    k_compact_count<VoxelFirst> counts per block of 1024 points, k_compact_write<VoxelFirst> writes the
+//                    kept indices in ascending order.
+//   k_voxel_scan     exclusive scan of the block counts of ANY compaction (one block).
 //
 // Which slot a voxel lands in depends on the order the waves arrive in; no output does: min commutes and the compaction is
 // ordered by index.  Part of the kernel set of cvo_kernels.h; compiled only as part of cvo_hip.hip.
 #pragma once
 #include "cvo_device.h"
+#include "cvo_k_compact.h"
 #include "cvo_wave.h"
 
 namespace cvo_dev {
 
-constexpr int VOX_THREADS = 1024;                 // points per block of every kernel here
+constexpr int VOX_THREADS = COMPACT_THREADS;      // points per block of every kernel here
 constexpr int VOX_INSERT_BLOCKS = 512;            // most blocks k_voxel_insert is launched with (two per CU; it strides)
 constexpr int VOX_LDS_SLOTS = 2048;               // block-local table of the pre-pass: 2 slots per point, never full
 constexpr int VOX_MAX_POINTS = 1 << 24;           // (the scan holds VOX_MAX_POINTS / VOX_THREADS block counts in one block)
@@ -152,19 +154,17 @@ __device__ __forceinline__ bool vox_keep(int i, int n, unsigned mask, const unsi
   return g <= mask && first[g] == (unsigned)i;
 }
 
-__global__ __launch_bounds__(VOX_THREADS) void k_voxel_flag(int n, unsigned mask, const unsigned* __restrict__ first,
-                                                            const unsigned* __restrict__ slot, unsigned* __restrict__ block_count) {
-  __shared__ unsigned wcnt[VOX_THREADS / 64];
-  const int i = blockIdx.x * VOX_THREADS + (int)threadIdx.x;
-  const unsigned long long m = __ballot(vox_keep(i, n, mask, first, slot));
-  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = (unsigned)__popcll(m);
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned c = 0;
-    for (int w = 0; w < VOX_THREADS / 64; w++) c += wcnt[w];
-    block_count[blockIdx.x] = c;
+struct VoxelFirst {
+  typedef int Item;  // the point's index
+  unsigned mask;
+  const unsigned *first, *slot;
+  int* kept;
+  __device__ bool keep(int i, int n, Item* item) const {
+    *item = i;
+    return vox_keep(i, n, mask, first, slot);
   }
-}
+  __device__ void write(unsigned at, const Item& i) const { kept[at] = i; }
+};
 
 // block_count[0 .. nb) -> its exclusive prefix sums, in place; the total -> ctl->n_kept.  One block; nb <= VOX_MAX_POINTS / VOX_THREADS.
 // Also sums the n_stats <= VOX_INSERT_BLOCKS block statistics of k_voxel_insert into ctl.
@@ -206,23 +206,6 @@ __global__ __launch_bounds__(VOX_THREADS) void k_voxel_scan(int nb, unsigned* bl
     ctl->occupied = tot[1];
     ctl->entered = tot[2];
     ctl->longest = longest;
-  }
-}
-
-__global__ __launch_bounds__(VOX_THREADS) void k_voxel_compact(int n, unsigned mask, const unsigned* __restrict__ first,
-                                                               const unsigned* __restrict__ slot, const unsigned* __restrict__ block_offset,
-                                                               int* __restrict__ kept) {
-  __shared__ unsigned wcnt[VOX_THREADS / 64];
-  const int i = blockIdx.x * VOX_THREADS + (int)threadIdx.x;
-  const bool keep = vox_keep(i, n, mask, first, slot);
-  const unsigned long long m = __ballot(keep);
-  const unsigned lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) wcnt[w] = (unsigned)__popcll(m);
-  __syncthreads();
-  if (keep) {
-    unsigned at = block_offset[blockIdx.x] + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-    for (unsigned v = 0; v < w; v++) at += wcnt[v];
-    if (at < (unsigned)n) kept[at] = i;  // (at most n points are kept: never out of bounds)
   }
 }
 

@@ -10,26 +10,41 @@ namespace {
 constexpr int RGBD_HOST_BELOW = 32768;
 constexpr int RGBD_NUM_WANT = 10000;  // dso_select_pixels' num_want (CvoPointCloud.cpp:327)
 
-int rgbd_validate(const cvo_rgbd_frame_t* f, std::string* msg) {
+// The refusals the frame types share, in the order the entry points report them: shape, image, then `calibration()` - the
+// type's own depth / disparity and calibration checks: what is wrong, or "" -, classes, 2^24 pixels.
+template <class Calibration>
+int frame_validate(int rows, int cols, int channels, const unsigned char* image, int num_classes, const float* semantic, std::string* msg,
+                   Calibration calibration) {
   auto bad = [&](const std::string& m) {
     *msg = m;
     return CVO_E_INVALID;
   };
-  auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
-  if (!f) return bad("frame is NULL");
-  if (f->rows < 1 || f->cols < 1) return bad("rows and cols must be >= 1, got " + std::to_string(f->rows) + " x " + std::to_string(f->cols));
-  if (f->channels != 1 && f->channels != 3) return bad("channels must be 1 or 3, got " + std::to_string(f->channels));
-  if (!f->image) return bad("image is NULL");
-  if (!f->depth) return bad("depth is NULL");
-  if (f->depth_type != CVO_DEPTH_U16 && f->depth_type != CVO_DEPTH_F32) return bad("depth_type must be CVO_DEPTH_U16 or CVO_DEPTH_F32");
-  if (!positive(f->fx) || !positive(f->fy)) return bad("fx and fy must be finite and > 0, got " + std::to_string(f->fx) + ", " + std::to_string(f->fy));
-  if (!positive(f->scaling_factor)) return bad("scaling_factor must be finite and > 0, got " + std::to_string(f->scaling_factor));
-  if (f->num_classes < 0 || (f->num_classes > 0 && !f->semantic)) return bad("num_classes > 0 needs the semantic image");
-  if ((long long)f->rows * f->cols > VOX_MAX_POINTS) {
+  if (rows < 1 || cols < 1) return bad("rows and cols must be >= 1, got " + std::to_string(rows) + " x " + std::to_string(cols));
+  if (channels != 1 && channels != 3) return bad("channels must be 1 or 3, got " + std::to_string(channels));
+  if (!image) return bad("image is NULL");
+  const std::string wrong = calibration();
+  if (!wrong.empty()) return bad(wrong);
+  if (num_classes < 0 || (num_classes > 0 && !semantic)) return bad("num_classes > 0 needs the semantic image");
+  if ((long long)rows * cols > VOX_MAX_POINTS) {
     *msg = "more than 2^24 pixels";
     return CVO_E_UNSUPPORTED;
   }
   return CVO_OK;
+}
+
+int rgbd_validate(const cvo_rgbd_frame_t* f, std::string* msg) {
+  if (!f) {
+    *msg = "frame is NULL";
+    return CVO_E_INVALID;
+  }
+  auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
+  return frame_validate(f->rows, f->cols, f->channels, f->image, f->num_classes, f->semantic, msg, [&]() -> std::string {
+    if (!f->depth) return "depth is NULL";
+    if (f->depth_type != CVO_DEPTH_U16 && f->depth_type != CVO_DEPTH_F32) return "depth_type must be CVO_DEPTH_U16 or CVO_DEPTH_F32";
+    if (!positive(f->fx) || !positive(f->fy)) return "fx and fy must be finite and > 0, got " + std::to_string(f->fx) + ", " + std::to_string(f->fy);
+    if (!positive(f->scaling_factor)) return "scaling_factor must be finite and > 0, got " + std::to_string(f->scaling_factor);
+    return "";
+  });
 }
 
 int rgbd_method(int method, std::string* msg) {
@@ -184,10 +199,12 @@ void rgbd_features(const cvo_rgbd_frame_t& f, const GrayView& g, int p, float* o
   out[ch + 1] = (float)((double)rgbd_gradient_at(g, f.cols, f.rows, (size_t)p + 1) / 500.0 + 0.5);
 }
 
+// the rows of the kept pixels that are asked for (a stereo frame comes as its stereo_view and has its xyz already)
 void rgbd_point_rows(const cvo_rgbd_frame_t& f, int method, const std::vector<int>& pix, float* xyz, float* feat, float* label, float* geotype) {
   const GrayView g = gray_view(f);
   const int F = f.channels + 2;
-  const float t0 = method == CVO_SELECT_FULL ? 0.5f : 0.9f, t1 = method == CVO_SELECT_FULL ? 0.5f : 0.1f;
+  const float t0 = method == CVO_SELECT_FULL ? 0.5f : (method == CVO_SELECT_CV_FAST ? 1.f : 0.9f);  // (CV_FAST: the stereo constructor's pure edges)
+  const float t1 = method == CVO_SELECT_FULL ? 0.5f : (method == CVO_SELECT_CV_FAST ? 0.f : 0.1f);
   for (size_t i = 0; i < pix.size(); i++) {
     if (xyz) rgbd_xyz(f, pix[i], xyz + 3 * i);
     if (feat) rgbd_features(f, g, pix[i], feat + F * i);
@@ -255,27 +272,15 @@ int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select,
   size_t cap = 0;  // candidates of both sets: every pixel (FULL) + the largest selection
   for (int k = 0; k < RGBD_POTS; k++) cap = std::max(cap, (size_t)rgbd_cells(RGBD_POT_MIN + k, w, h));
   cap += np;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
-  const size_t o_ctl = take(sizeof(VoxelCtl)), o_img = take(need_select ? img_bytes : 0), o_depth = take(depth_bytes),
-               o_excl = take(f.num_classes > 0 ? np : 0), o_g2 = take(need_select ? sizeof(float) * np : 0), o_ths = take(2 * sizeof(float) * n_ths),
-               o_hit = take(sizeof(int) * (size_t)d.n_cells), o_sel = take(sizeof(int) * (size_t)d.n_cells), o_blocks = take(sizeof(unsigned) * nb),
-               o_pix = take(sizeof(int) * cap), o_out = take(sizeof(int) * cap), o_xyz = take(sizeof(float) * 3 * cap),
-               o_score = take(need_fast ? np : 0), o_fhist = take(need_fast ? sizeof(unsigned) * FAST_BINS : 0);
-  if (off > ctx->rgbd_scratch_bytes) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
-    if (ctx->rgbd_scratch) (void)hipFree(ctx->rgbd_scratch);
-    ctx->rgbd_scratch = nullptr;
-    ctx->rgbd_scratch_bytes = 0;
-    const hipError_t e = hipMalloc(&ctx->rgbd_scratch, off);
-    if (e != hipSuccess) return fail(ctx, CVO_E_NOMEM, std::string("RGB-D scratch hipMalloc: ") + hipGetErrorString(e));
-    ctx->rgbd_scratch_bytes = off;
-  }
-  char* b = ctx->rgbd_scratch;
+  ScratchLayout l;
+  const size_t o_ctl = l.take(sizeof(VoxelCtl)), o_img = l.take(need_select ? img_bytes : 0), o_depth = l.take(depth_bytes),
+               o_excl = l.take(f.num_classes > 0 ? np : 0), o_g2 = l.take(need_select ? sizeof(float) * np : 0), o_ths = l.take(2 * sizeof(float) * n_ths),
+               o_hit = l.take(sizeof(int) * (size_t)d.n_cells), o_sel = l.take(sizeof(int) * (size_t)d.n_cells), o_blocks = l.take(sizeof(unsigned) * nb),
+               o_pix = l.take(sizeof(int) * cap), o_out = l.take(sizeof(int) * cap), o_xyz = l.take(sizeof(float) * 3 * cap),
+               o_score = l.take(need_fast ? np : 0), o_fhist = l.take(need_fast ? sizeof(unsigned) * FAST_BINS : 0);
+  const int rc = ctx->rgbd_scratch.reserve(ctx, l.off, "RGB-D scratch");
+  if (rc != CVO_OK) return rc;
+  char* b = ctx->rgbd_scratch.p;
   d.ctl = (VoxelCtl*)(b + o_ctl);
   d.img = (unsigned char*)(b + o_img);
   d.depth = b + o_depth;
@@ -317,9 +322,8 @@ int rgbd_device_select(cvo_ctx* ctx, RgbdDevice& d, RgbdStatsAcc& stats, const i
   }
   hipLaunchKernelGGL(k_rgbd_select, dim3(d.nb_cells), dim3(RGBD_THREADS), 0, st, w, h, d.cells, (const float*)d.g2, (const float*)d.sm, d.hit,
                      d.blocks);
-  hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, st, d.nb_cells, d.blocks, d.ctl, 0, (const VoxelBlockStats*)nullptr);
-  hipLaunchKernelGGL(k_rgbd_compact, dim3(d.nb_cells), dim3(RGBD_THREADS), 0, st, d.n_cells, (const int*)d.hit, (const unsigned*)d.blocks, d.sel);
-  HIP_TRY(ctx, hipGetLastError());
+  const int rc = compact_counted(ctx, d.n_cells, RgbdCellHit{d.hit, d.sel}, d.blocks, d.ctl);
+  if (rc != CVO_OK) return rc;
   d.sel_offset.assign((size_t)d.nb_cells + 1, 0u);
   VoxelCtl c{};
   HIP_TRY(ctx, hipMemcpyAsync(d.sel_offset.data(), d.blocks, sizeof(unsigned) * (size_t)d.nb_cells, hipMemcpyDeviceToHost, st));
@@ -335,25 +339,25 @@ int rgbd_device_select(cvo_ctx* ctx, RgbdDevice& d, RgbdStatsAcc& stats, const i
   return CVO_OK;
 }
 
-// depth test + exclusion + back-projection of a candidate list (nullptr: FULL) into d.pix / d.xyz from `at` on; *n_out
-// survivors.  One synchronisation.
-int rgbd_device_backproject(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, RgbdDevice& d, const int* list, int n, int at, int* n_out) {
+// a frame type's keep predicate and back-projection (RgbdKeep, StereoKeep) over the n candidates of pred.list (nullptr:
+// FULL) into d.pix / d.xyz from `at` on; *n_out survivors.  One synchronisation.
+template <class P>
+int frame_device_backproject(cvo_ctx* ctx, const char* who, RgbdDevice& d, P pred, int n, int at, int* n_out) {
   *n_out = 0;
   if (n == 0) return CVO_OK;
-  hipStream_t st = ctx->upload_stream;
-  const int nb = (n + RGBD_THREADS - 1) / RGBD_THREADS;
-  hipLaunchKernelGGL(k_rgbd_bp_flag, dim3(nb), dim3(RGBD_THREADS), 0, st, n, list, d.w, d.h, (const void*)d.depth, f.depth_type,
-                     (const unsigned char*)d.excl, d.blocks);
-  hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, st, nb, d.blocks, d.ctl, 0, (const VoxelBlockStats*)nullptr);
-  hipLaunchKernelGGL(k_rgbd_bp_write, dim3(nb), dim3(RGBD_THREADS), 0, st, n, list, d.w, d.h, (const void*)d.depth, f.depth_type,
-                     (const unsigned char*)d.excl, rgbd_calib(f), (const unsigned*)d.blocks, d.pix + at, d.xyz + 3 * (size_t)at);
-  HIP_TRY(ctx, hipGetLastError());
+  pred.pix_out = d.pix + at;
+  pred.xyz = d.xyz + 3 * (size_t)at;
+  int rc = compact(ctx, n, pred, d.blocks, d.ctl);
+  if (rc != CVO_OK) return rc;
   VoxelCtl c{};
-  HIP_TRY(ctx, hipMemcpyAsync(&c, d.ctl, sizeof c, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  if (c.n_kept > (unsigned)n) return fail(ctx, CVO_E_HIP, "RGB-D back-projection: the device kept more pixels than it was given");
+  if ((rc = compact_total(ctx, d.ctl, n, who, "pixels", &c)) != CVO_OK) return rc;
   *n_out = (int)c.n_kept;
   return CVO_OK;
+}
+
+int rgbd_device_backproject(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, RgbdDevice& d, const int* list, int n, int at, int* n_out) {
+  return frame_device_backproject(ctx, "RGB-D back-projection", d, RgbdKeep{list, d.w, d.h, d.depth, f.depth_type, d.excl, rgbd_calib(f), nullptr, nullptr},
+                                  n, at, n_out);
 }
 
 int rgbd_fetch(cvo_ctx* ctx, const int* d_src, int n, std::vector<int>& out) {
@@ -394,43 +398,41 @@ bool rgbd_on_host(const cvo_ctx* ctx, const cvo_rgbd_frame_t& f) {
   return ctx->opt.rgbd_host > 0 || (ctx->opt.rgbd_host < 0 && (long long)f.cols * f.rows < RGBD_HOST_BELOW);
 }
 
-// both candidate sets through the voxel grid: pixel indices of the survivors, edge first; n_edge of them are edges
-int rgbd_recipe_pixels(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t& f, float leaf, float divisor, std::vector<int>& pix, int* n_edge,
-                       RgbdStatsAcc& st) {
+// The drivers' per-frame recipe for either frame type: both candidate sets - edges, then FULL - through the voxel grid
+// (leaf / divisor for the edges); pixel indices of the survivors, edge first, n_edge of them edges, and - xyz != nullptr, host
+// route only - their coordinates.  `view`: the frame as rgbd_device_stage reads it.
+//   host_pass(method, cand, cxyz)   host route: a pass's candidates and their coordinates (the CPU twins)
+//   device_pass(d, &n_e, &n_s)      device route: selection and both back-projections into d.pix / d.xyz, edges from 0, FULL from n_e
+template <class HostPass, class DevicePass>
+int recipe_pixels(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t& view, bool on_host, float leaf, float divisor, std::vector<int>& pix,
+                  std::vector<float>* xyz, int* n_edge, HostPass host_pass, DevicePass device_pass) {
   const float s_edge = leaf / divisor;
   std::string msg;
   if (voxel_validate(0, nullptr, s_edge, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": leaf / edge_divisor: " + msg);
   pix.clear();
-  if (rgbd_on_host(ctx, f)) {
-    st.on_device = 0;
+  *n_edge = 0;
+  if (on_host) {
     for (int pass = 0; pass < 2; pass++) {
       std::vector<int> cand, kept;
-      rgbd_candidates_cpu(f, pass == 0 ? CVO_SELECT_DSO_EDGES : CVO_SELECT_FULL, cand, st);
-      std::vector<float> xyz(3 * cand.size());
-      for (size_t i = 0; i < cand.size(); i++) rgbd_xyz(f, cand[i], &xyz[3 * i]);
+      std::vector<float> cxyz;
+      host_pass(pass == 0 ? CVO_SELECT_DSO_EDGES : CVO_SELECT_FULL, cand, cxyz);
       const float s = pass == 0 ? s_edge : leaf;
-      if (voxel_validate((int)cand.size(), xyz.data(), s, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": " + msg);
-      voxel_select_cpu((int)cand.size(), xyz.data(), s, kept);
-      for (int k : kept) pix.push_back(cand[(size_t)k]);
+      if (voxel_validate((int)cand.size(), cxyz.data(), s, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": " + msg);
+      voxel_select_cpu((int)cand.size(), cxyz.data(), s, kept);
+      for (int k : kept) {
+        pix.push_back(cand[(size_t)k]);
+        if (xyz) xyz->insert(xyz->end(), &cxyz[3 * (size_t)k], &cxyz[3 * (size_t)k] + 3);
+      }
       if (pass == 0) *n_edge = (int)kept.size();
     }
     return CVO_OK;
   }
-  st.on_device = 1;
   RgbdDevice d;
-  int rc = rgbd_device_stage(ctx, f, true, d);
+  int rc = rgbd_device_stage(ctx, view, true, d);
   if (rc != CVO_OK) return rc;
-  const int* list = nullptr;
-  int n_sel = 0, n_e = 0, n_s = 0;
-  if ((rc = rgbd_device_select(ctx, d, st, &list, &n_sel)) != CVO_OK) return rc;
-  if ((rc = rgbd_device_backproject(ctx, f, d, list, n_sel, 0, &n_e)) != CVO_OK) return rc;
-  if ((rc = rgbd_device_backproject(ctx, f, d, nullptr, f.cols * f.rows, n_e, &n_s)) != CVO_OK) return rc;
-  st.edge_points = (unsigned long long)n_e;
-  st.surface_points = (unsigned long long)n_s;
-  st.with_depth = d.excl ? rgbd_count_depth(f) : (unsigned long long)n_s;
-  hipStream_t stream = ctx->upload_stream;
+  int n_e = 0, n_s = 0;
+  if ((rc = device_pass(d, &n_e, &n_s)) != CVO_OK) return rc;
   int total = 0;
-  *n_edge = 0;
   for (int pass = 0; pass < 2; pass++) {
     const int n = pass == 0 ? n_e : n_s, at = pass == 0 ? 0 : n_e;
     if (n == 0) continue;
@@ -438,13 +440,37 @@ int rgbd_recipe_pixels(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t& f,
     rc = voxel_run_device(ctx, n, nullptr, d.xyz + 3 * (size_t)at, pass == 0 ? s_edge : leaf, nullptr, &d_kept);
     if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + ctx->err);
     const int nk = (int)ctx->vox_last.n_kept;
-    hipLaunchKernelGGL(k_rgbd_gather, dim3((nk + RGBD_THREADS - 1) / RGBD_THREADS), dim3(RGBD_THREADS), 0, stream, nk, n, d_kept,
+    hipLaunchKernelGGL(k_rgbd_gather, dim3((nk + RGBD_THREADS - 1) / RGBD_THREADS), dim3(RGBD_THREADS), 0, ctx->upload_stream, nk, n, d_kept,
                        (const int*)(d.pix + at), d.out + total);
     HIP_TRY(ctx, hipGetLastError());
     total += nk;
     if (pass == 0) *n_edge = nk;
   }
   return rgbd_fetch(ctx, d.out, total, pix);
+}
+
+// the recipe of an RGB-D frame
+int rgbd_recipe_pixels(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t& f, float leaf, float divisor, std::vector<int>& pix, int* n_edge,
+                       RgbdStatsAcc& st) {
+  st.on_device = rgbd_on_host(ctx, f) ? 0 : 1;
+  return recipe_pixels(
+      ctx, who, f, !st.on_device, leaf, divisor, pix, nullptr, n_edge,
+      [&](int method, std::vector<int>& cand, std::vector<float>& cxyz) {
+        rgbd_candidates_cpu(f, method, cand, st);
+        cxyz.resize(3 * cand.size());
+        for (size_t i = 0; i < cand.size(); i++) rgbd_xyz(f, cand[i], &cxyz[3 * i]);
+      },
+      [&](RgbdDevice& d, int* n_e, int* n_s) {
+        const int* list = nullptr;
+        int n_sel = 0, rc;
+        if ((rc = rgbd_device_select(ctx, d, st, &list, &n_sel)) != CVO_OK) return rc;
+        if ((rc = rgbd_device_backproject(ctx, f, d, list, n_sel, 0, n_e)) != CVO_OK) return rc;
+        if ((rc = rgbd_device_backproject(ctx, f, d, nullptr, f.cols * f.rows, *n_e, n_s)) != CVO_OK) return rc;
+        st.edge_points = (unsigned long long)*n_e;
+        st.surface_points = (unsigned long long)*n_s;
+        st.with_depth = d.excl ? rgbd_count_depth(f) : (unsigned long long)*n_s;
+        return CVO_OK;
+      });
 }
 
 }  // namespace
@@ -458,17 +484,14 @@ int cvo_rgbd_points_host(const cvo_rgbd_frame_t* frame, int method, int* pixel, 
   if (rc == CVO_OK && method == CVO_SELECT_DSO_EDGES) rc = rgbd_threshold_range(frame->cols, frame->rows, &msg);
   if (rc != CVO_OK) return rc;
   if (!pixel || !n) return CVO_E_INVALID;
-  try {
+  return frontend_call(nullptr, "", [&] {
     std::vector<int> pix;
     RgbdStatsAcc st;
     rgbd_candidates_cpu(*frame, method, pix, st);
     rgbd_point_rows(*frame, method, pix, xyz, feat, label, geotype);
-    if (!pix.empty()) std::memcpy(pixel, pix.data(), sizeof(int) * pix.size());
-    *n = (int)pix.size();
-  } catch (const std::exception&) {
-    return CVO_E_NOMEM;
-  }
-  return CVO_OK;
+    copy_kept(pix, pixel, n);
+    return CVO_OK;
+  });
 }
 
 int cvo_rgbd_points(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat, float* label,
@@ -483,24 +506,21 @@ int cvo_rgbd_points(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, int method, int
     msg = "pixel and n are required";
   }
   if (rc != CVO_OK) return fail(ctx, rc, "cvo_rgbd_points: " + msg);
-  try {
-    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  return frontend_call(ctx, "cvo_rgbd_points", [&] {
     std::vector<int> pix;
     RgbdStatsAcc st;
     if (rgbd_on_host(ctx, *frame)) {
       rgbd_candidates_cpu(*frame, method, pix, st);
     } else {
       st.on_device = 1;
-      if ((rc = rgbd_points_device(ctx, *frame, method, pix, st)) != CVO_OK) return rc;
+      const int rc = rgbd_points_device(ctx, *frame, method, pix, st);
+      if (rc != CVO_OK) return rc;
     }
     rgbd_point_rows(*frame, method, pix, xyz, feat, label, geotype);
-    if (!pix.empty()) std::memcpy(pixel, pix.data(), sizeof(int) * pix.size());
-    *n = (int)pix.size();
+    copy_kept(pix, pixel, n);
     ctx->rgbd_last = st;
-  } catch (const std::exception& e) {
-    return fail(ctx, CVO_E_NOMEM, std::string("cvo_rgbd_points: ") + e.what());
-  }
-  return CVO_OK;
+    return CVO_OK;
+  });
 }
 
 int cvo_cloud_upload_rgbd(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, float leaf, float edge_divisor, cvo_cloud** out, int* pixel,
@@ -522,30 +542,21 @@ int cvo_cloud_upload_rgbd(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, float lea
     msg = "edge_divisor must be finite and > 0, got " + std::to_string(edge_divisor);
   }
   if (rc != CVO_OK) return fail(ctx, rc, "cvo_cloud_upload_rgbd: " + msg);
-  try {
-    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  return frontend_call(ctx, "cvo_cloud_upload_rgbd", [&] {
     std::vector<int> pix;
     RgbdStatsAcc st;
-    int n_edge = 0;
+    int n_edge = 0, rc;
     if ((rc = rgbd_recipe_pixels(ctx, "cvo_cloud_upload_rgbd", *frame, leaf, edge_divisor, pix, &n_edge, st)) != CVO_OK) return rc;
     const size_t np = pix.size();
     std::vector<float> xyz(3 * np), feat((size_t)FD * np), geo(2 * np);
     const GrayView g = gray_view(*frame);
     for (size_t i = 0; i < np; i++) rgbd_recipe_row(*frame, g, pix[i], (int)i < n_edge, &xyz[3 * i], &feat[(size_t)FD * i], &geo[2 * i]);
-    HostCloud h{(int)np, (const char*)xyz.data(), 12, (const char*)feat.data(), sizeof(float) * FD, nullptr, 0, (const char*)geo.data(), 8};
-    std::vector<StagedCloud> one(1);
-    if ((rc = upload_host_cloud(ctx, h, ctx->upload_stream, &one[0])) != CVO_OK) return rc;
-    if ((rc = finish_uploads(ctx, one)) != CVO_OK) return rc;
-    *out = one[0].c;
-    if (pixel && np) std::memcpy(pixel, pix.data(), sizeof(int) * np);
-    if (is_edge)
-      for (size_t i = 0; i < np; i++) is_edge[i] = (int)i < n_edge ? 1 : 0;
-    if (n) *n = (int)np;
+    const HostCloud h{(int)np, (const char*)xyz.data(), 12, (const char*)feat.data(), sizeof(float) * FD, nullptr, 0, (const char*)geo.data(), 8};
+    if ((rc = upload_one_locked(ctx, h, out)) != CVO_OK) return rc;
+    copy_kept(pix, pixel, n, is_edge, n_edge);
     ctx->rgbd_last = st;
-  } catch (const std::exception& e) {
-    return fail(ctx, CVO_E_NOMEM, std::string("cvo_cloud_upload_rgbd: ") + e.what());
-  }
-  return CVO_OK;
+    return CVO_OK;
+  });
 }
 
 int cvo_debug_rgbd_stats(cvo_ctx* ctx, int* n_tried, int* potentials, int* counts, unsigned long long* edge_selected,

@@ -9,24 +9,17 @@
 namespace {
 
 int stereo_validate(const cvo_stereo_frame_t* f, std::string* msg) {
-  auto bad = [&](const std::string& m) {
-    *msg = m;
+  if (!f) {
+    *msg = "frame is NULL";
     return CVO_E_INVALID;
-  };
-  auto usable = [](float v) { return std::isfinite(v) && v != 0.f; };
-  if (!f) return bad("frame is NULL");
-  if (f->rows < 1 || f->cols < 1) return bad("rows and cols must be >= 1, got " + std::to_string(f->rows) + " x " + std::to_string(f->cols));
-  if (f->channels != 1 && f->channels != 3) return bad("channels must be 1 or 3, got " + std::to_string(f->channels));
-  if (!f->image) return bad("image is NULL");
-  if (!f->disparity) return bad("disparity is NULL");
-  if (!usable(f->fx) || !usable(f->fy)) return bad("fx and fy must be finite and not 0, got " + std::to_string(f->fx) + ", " + std::to_string(f->fy));
-  if (!usable(f->baseline)) return bad("baseline must be finite and not 0, got " + std::to_string(f->baseline));
-  if (f->num_classes < 0 || (f->num_classes > 0 && !f->semantic)) return bad("num_classes > 0 needs the semantic image");
-  if ((long long)f->rows * f->cols > VOX_MAX_POINTS) {
-    *msg = "more than 2^24 pixels";
-    return CVO_E_UNSUPPORTED;
   }
-  return CVO_OK;
+  auto usable = [](float v) { return std::isfinite(v) && v != 0.f; };
+  return frame_validate(f->rows, f->cols, f->channels, f->image, f->num_classes, f->semantic, msg, [&]() -> std::string {
+    if (!f->disparity) return "disparity is NULL";
+    if (!usable(f->fx) || !usable(f->fy)) return "fx and fy must be finite and not 0, got " + std::to_string(f->fx) + ", " + std::to_string(f->fy);
+    if (!usable(f->baseline)) return "baseline must be finite and not 0, got " + std::to_string(f->baseline);
+    return "";
+  });
 }
 
 int stereo_method(int method, std::string* msg) {
@@ -79,11 +72,6 @@ cvo_fast_schedule_t stereo_schedule(const cvo_stereo_frame_t& f) {
   return f.num_classes > 0 ? cvo_fast_schedule_t CVO_FAST_STEREO_SEMANTIC : cvo_fast_schedule_t CVO_FAST_STEREO;
 }
 
-void stereo_geotype(int method, float* t) {
-  t[0] = method == CVO_SELECT_FULL ? 0.5f : (method == CVO_SELECT_CV_FAST ? 1.f : 0.9f);
-  t[1] = method == CVO_SELECT_FULL ? 0.5f : (method == CVO_SELECT_CV_FAST ? 0.f : 0.1f);
-}
-
 void stereo_copy_dso_schedule(const RgbdStatsAcc& r, StereoStatsAcc& st) {
   st.tried.assign(r.tried, r.tried + r.n_tried);
   st.count.assign(r.count, r.count + r.n_tried);
@@ -121,25 +109,9 @@ void stereo_points_cpu(const cvo_stereo_frame_t& f, int method, std::vector<int>
 }
 
 // ---- device route ----
-// keep predicate + back-projection of a candidate list (nullptr: FULL) into d.pix / d.xyz from `at` on.  One synchronisation.
 int stereo_device_backproject(cvo_ctx* ctx, const cvo_stereo_frame_t& f, RgbdDevice& d, const int* list, int n, int at, int* n_out) {
-  *n_out = 0;
-  if (n == 0) return CVO_OK;
-  hipStream_t st = ctx->upload_stream;
-  const int nb = (n + RGBD_THREADS - 1) / RGBD_THREADS;
-  const StereoCalib k = stereo_calib(f);
-  hipLaunchKernelGGL(k_stereo_bp_flag, dim3(nb), dim3(RGBD_THREADS), 0, st, n, list, d.w, d.h, (const float*)d.depth, (const unsigned char*)d.excl, k,
-                     d.blocks);
-  hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, st, nb, d.blocks, d.ctl, 0, (const VoxelBlockStats*)nullptr);
-  hipLaunchKernelGGL(k_stereo_bp_write, dim3(nb), dim3(RGBD_THREADS), 0, st, n, list, d.w, d.h, (const float*)d.depth, (const unsigned char*)d.excl, k,
-                     (const unsigned*)d.blocks, d.pix + at, d.xyz + 3 * (size_t)at);
-  HIP_TRY(ctx, hipGetLastError());
-  VoxelCtl c{};
-  HIP_TRY(ctx, hipMemcpyAsync(&c, d.ctl, sizeof c, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  if (c.n_kept > (unsigned)n) return fail(ctx, CVO_E_HIP, "stereo back-projection: the device kept more pixels than it was given");
-  *n_out = (int)c.n_kept;
-  return CVO_OK;
+  return frame_device_backproject(ctx, "stereo back-projection", d,
+                                  StereoKeep{list, d.w, d.h, (const float*)d.depth, d.excl, stereo_calib(f), nullptr, nullptr}, n, at, n_out);
 }
 
 // candidates of a method on the device: *list == nullptr is FULL's column-major order
@@ -186,76 +158,26 @@ int stereo_points_any(cvo_ctx* ctx, const cvo_stereo_frame_t& f, int method, std
   return stereo_points_device(ctx, f, method, pix, xyz, st);
 }
 
-// rows of the kept pixels other than xyz (host, both routes): the RGB-D constructor's features and labels
-void stereo_point_rows(const cvo_stereo_frame_t& f, int method, const std::vector<int>& pix, float* feat, float* label, float* geotype) {
-  const cvo_rgbd_frame_t view = stereo_view(f);
-  const GrayView g = gray_view(view);
-  const int F = f.channels + 2;
-  float t[2];
-  stereo_geotype(method, t);
-  for (size_t i = 0; i < pix.size(); i++) {
-    if (feat) rgbd_features(view, g, pix[i], feat + F * i);
-    if (label && f.num_classes > 0)
-      std::memcpy(label + i * (size_t)f.num_classes, f.semantic + (size_t)pix[i] * f.num_classes, sizeof(float) * (size_t)f.num_classes);
-    if (geotype) {
-      geotype[2 * i] = t[0];
-      geotype[2 * i + 1] = t[1];
-    }
-  }
-}
-
-// both candidate sets through the voxel grid: pixel indices and coordinates of the survivors, edge first
+// the recipe of a stereo frame: pixel indices and coordinates of the survivors, edge first
 int stereo_recipe_pixels(cvo_ctx* ctx, const char* who, const cvo_stereo_frame_t& f, float leaf, float divisor, std::vector<int>& pix,
                          std::vector<float>& xyz, int* n_edge, StereoStatsAcc& st) {
-  const float s_edge = leaf / divisor;
-  std::string msg;
-  if (voxel_validate(0, nullptr, s_edge, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": leaf / edge_divisor: " + msg);
-  pix.clear();
+  const bool on_host = stereo_on_host(ctx, f.rows, f.cols, STEREO_RECIPE_HOST_BELOW);
   xyz.clear();
-  *n_edge = 0;
-  if (stereo_on_host(ctx, f.rows, f.cols, STEREO_RECIPE_HOST_BELOW)) {
-    for (int pass = 0; pass < 2; pass++) {
-      std::vector<int> cand, kept;
-      std::vector<float> cxyz;
-      stereo_points_cpu(f, pass == 0 ? CVO_SELECT_DSO_EDGES : CVO_SELECT_FULL, cand, cxyz, st);
-      const float s = pass == 0 ? s_edge : leaf;
-      if (voxel_validate((int)cand.size(), cxyz.data(), s, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": " + msg);
-      voxel_select_cpu((int)cand.size(), cxyz.data(), s, kept);
-      for (int k : kept) {
-        pix.push_back(cand[(size_t)k]);
-        xyz.insert(xyz.end(), &cxyz[3 * (size_t)k], &cxyz[3 * (size_t)k] + 3);
-      }
-      if (pass == 0) *n_edge = (int)kept.size();
-    }
-    return CVO_OK;
-  }
-  st.on_device = 1;
-  RgbdDevice d;
-  int rc = rgbd_device_stage(ctx, stereo_view(f), true, d);
-  if (rc != CVO_OK) return rc;
-  const int* list = nullptr;
-  int n_sel = 0, n_e = 0, n_s = 0;
-  if ((rc = stereo_device_candidates(ctx, f, CVO_SELECT_DSO_EDGES, d, st, &list, &n_sel)) != CVO_OK) return rc;
-  if ((rc = stereo_device_backproject(ctx, f, d, list, n_sel, 0, &n_e)) != CVO_OK) return rc;
-  st.candidates += (unsigned long long)f.cols * f.rows;
-  if ((rc = stereo_device_backproject(ctx, f, d, nullptr, f.cols * f.rows, n_e, &n_s)) != CVO_OK) return rc;
-  st.kept = (unsigned long long)n_e + n_s;
-  hipStream_t stream = ctx->upload_stream;
-  int total = 0;
-  for (int pass = 0; pass < 2; pass++) {
-    const int n = pass == 0 ? n_e : n_s, at = pass == 0 ? 0 : n_e;
-    if (n == 0) continue;
-    const int* d_kept = nullptr;
-    rc = voxel_run_device(ctx, n, nullptr, d.xyz + 3 * (size_t)at, pass == 0 ? s_edge : leaf, nullptr, &d_kept);
-    if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + ctx->err);
-    const int nk = (int)ctx->vox_last.n_kept;
-    hipLaunchKernelGGL(k_rgbd_gather, dim3((nk + RGBD_THREADS - 1) / RGBD_THREADS), dim3(RGBD_THREADS), 0, stream, nk, n, d_kept,
-                       (const int*)(d.pix + at), d.out + total);
-    HIP_TRY(ctx, hipGetLastError());
-    total += nk;
-    if (pass == 0) *n_edge = nk;
-  }
-  if ((rc = rgbd_fetch(ctx, d.out, total, pix)) != CVO_OK) return rc;
+  const int rc = recipe_pixels(
+      ctx, who, stereo_view(f), on_host, leaf, divisor, pix, &xyz, n_edge,
+      [&](int method, std::vector<int>& cand, std::vector<float>& cxyz) { stereo_points_cpu(f, method, cand, cxyz, st); },
+      [&](RgbdDevice& d, int* n_e, int* n_s) {
+        st.on_device = 1;
+        const int* list = nullptr;
+        int n_sel = 0, rc;
+        if ((rc = stereo_device_candidates(ctx, f, CVO_SELECT_DSO_EDGES, d, st, &list, &n_sel)) != CVO_OK) return rc;
+        if ((rc = stereo_device_backproject(ctx, f, d, list, n_sel, 0, n_e)) != CVO_OK) return rc;
+        st.candidates += (unsigned long long)f.cols * f.rows;
+        if ((rc = stereo_device_backproject(ctx, f, d, nullptr, f.cols * f.rows, *n_e, n_s)) != CVO_OK) return rc;
+        st.kept = (unsigned long long)*n_e + *n_s;
+        return CVO_OK;
+      });
+  if (rc != CVO_OK || on_host) return rc;
   // the survivors' coordinates on the host: the same arithmetic (stereo_point is shared), a few thousand points
   const StereoCalib k = stereo_calib(f);
   xyz.resize(3 * pix.size());
@@ -284,96 +206,83 @@ int cvo_stereo_points_host(const cvo_stereo_frame_t* frame, int method, int* pix
   const int rc = stereo_check(nullptr, "", frame, &method, &msg);
   if (rc != CVO_OK) return rc;
   if (!pixel || !n) return CVO_E_INVALID;
-  try {
+  return frontend_call(nullptr, "", [&] {
     std::vector<int> pix;
     std::vector<float> p3;
     StereoStatsAcc st;
     stereo_points_cpu(*frame, method, pix, p3, st);
-    stereo_point_rows(*frame, method, pix, feat, label, geotype);
+    rgbd_point_rows(stereo_view(*frame), method, pix, nullptr, feat, label, geotype);
     if (xyz && !p3.empty()) std::memcpy(xyz, p3.data(), sizeof(float) * p3.size());
-    if (!pix.empty()) std::memcpy(pixel, pix.data(), sizeof(int) * pix.size());
-    *n = (int)pix.size();
-  } catch (const std::exception&) {
-    return CVO_E_NOMEM;
-  }
-  return CVO_OK;
+    copy_kept(pix, pixel, n);
+    return CVO_OK;
+  });
 }
 
 int cvo_stereo_points(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat, float* label,
                       float* geotype) {
   if (!ctx) return CVO_E_INVALID;
   std::string msg;
-  int rc = stereo_check(ctx, "cvo_stereo_points", frame, &method, &msg);
+  const int rc = stereo_check(ctx, "cvo_stereo_points", frame, &method, &msg);
   if (rc != CVO_OK) return rc;
   if (!pixel || !n) return fail(ctx, CVO_E_INVALID, "cvo_stereo_points: pixel and n are required");
-  try {
-    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  return frontend_call(ctx, "cvo_stereo_points", [&] {
     std::vector<int> pix;
     std::vector<float> p3;
     StereoStatsAcc st;
-    if ((rc = stereo_points_any(ctx, *frame, method, pix, p3, st)) != CVO_OK) return rc;
-    stereo_point_rows(*frame, method, pix, feat, label, geotype);
+    const int rc = stereo_points_any(ctx, *frame, method, pix, p3, st);
+    if (rc != CVO_OK) return rc;
+    rgbd_point_rows(stereo_view(*frame), method, pix, nullptr, feat, label, geotype);
     if (xyz && !p3.empty()) std::memcpy(xyz, p3.data(), sizeof(float) * p3.size());
-    if (!pix.empty()) std::memcpy(pixel, pix.data(), sizeof(int) * pix.size());
-    *n = (int)pix.size();
+    copy_kept(pix, pixel, n);
     ctx->stereo_last = st;
-  } catch (const std::exception& e) {
-    return fail(ctx, CVO_E_NOMEM, std::string("cvo_stereo_points: ") + e.what());
-  }
-  return CVO_OK;
+    return CVO_OK;
+  });
 }
 
 int cvo_cloud_upload_stereo(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, int method, cvo_cloud** out, int* pixel, int* n) {
   if (!ctx) return CVO_E_INVALID;
   std::string msg;
-  int rc = stereo_check(ctx, "cvo_cloud_upload_stereo", frame, &method, &msg);
+  const int rc = stereo_check(ctx, "cvo_cloud_upload_stereo", frame, &method, &msg);
   if (rc != CVO_OK) return rc;
   if (!out) return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_stereo: out is NULL");
-  try {
-    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  return frontend_call(ctx, "cvo_cloud_upload_stereo", [&] {
     std::vector<int> pix;
     std::vector<float> p3;
     StereoStatsAcc st;
-    if ((rc = stereo_points_any(ctx, *frame, method, pix, p3, st)) != CVO_OK) return rc;
+    int rc = stereo_points_any(ctx, *frame, method, pix, p3, st);
+    if (rc != CVO_OK) return rc;
     // the rows as cvo_cloud_upload takes them: F = channels + 2 features zero-padded to FD, labels padded / cut to NC
     const size_t np = pix.size(), F = (size_t)frame->channels + 2, C = (size_t)frame->num_classes;
     std::vector<float> ft(F * np), lb(C * np), geo(2 * np), feat((size_t)FD * np, 0.f), label(C ? (size_t)NC * np : 0, 0.f);
-    stereo_point_rows(*frame, method, pix, ft.data(), C ? lb.data() : nullptr, geo.data());
+    rgbd_point_rows(stereo_view(*frame), method, pix, nullptr, ft.data(), C ? lb.data() : nullptr, geo.data());
     for (size_t i = 0; i < np; i++) {
       std::memcpy(&feat[(size_t)FD * i], &ft[F * i], sizeof(float) * std::min(F, (size_t)FD));
       if (C) std::memcpy(&label[(size_t)NC * i], &lb[C * i], sizeof(float) * std::min(C, (size_t)NC));
     }
-    HostCloud h{(int)np, (const char*)p3.data(), 12, (const char*)feat.data(), sizeof(float) * FD, C ? (const char*)label.data() : nullptr,
-                sizeof(float) * NC, (const char*)geo.data(), 8};
-    std::vector<StagedCloud> one(1);
-    if ((rc = upload_host_cloud(ctx, h, ctx->upload_stream, &one[0])) != CVO_OK) return rc;
-    if ((rc = finish_uploads(ctx, one)) != CVO_OK) return rc;
-    *out = one[0].c;
-    if (pixel && np) std::memcpy(pixel, pix.data(), sizeof(int) * np);
-    if (n) *n = (int)np;
+    const HostCloud h{(int)np, (const char*)p3.data(), 12, (const char*)feat.data(), sizeof(float) * FD, C ? (const char*)label.data() : nullptr,
+                      sizeof(float) * NC, (const char*)geo.data(), 8};
+    if ((rc = upload_one_locked(ctx, h, out)) != CVO_OK) return rc;
+    copy_kept(pix, pixel, n);
     ctx->stereo_last = st;
-  } catch (const std::exception& e) {
-    return fail(ctx, CVO_E_NOMEM, std::string("cvo_cloud_upload_stereo: ") + e.what());
-  }
-  return CVO_OK;
+    return CVO_OK;
+  });
 }
 
 int cvo_cloud_upload_stereo_recipe(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, float leaf, float edge_divisor, cvo_cloud** out, int* pixel,
                                    unsigned char* is_edge, int* n) {
   if (!ctx) return CVO_E_INVALID;
   std::string msg;
-  int rc = stereo_check(ctx, "cvo_cloud_upload_stereo_recipe", frame, nullptr, &msg);
+  const int rc = stereo_check(ctx, "cvo_cloud_upload_stereo_recipe", frame, nullptr, &msg);
   if (rc != CVO_OK) return rc;
   if (!out) return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_stereo_recipe: out is NULL");
   if (voxel_validate(0, nullptr, leaf, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_stereo_recipe: leaf: " + msg);
   if (!std::isfinite(edge_divisor) || !(edge_divisor > 0.f))
     return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_stereo_recipe: edge_divisor must be finite and > 0, got " + std::to_string(edge_divisor));
-  try {
-    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  return frontend_call(ctx, "cvo_cloud_upload_stereo_recipe", [&] {
     std::vector<int> pix;
     std::vector<float> xyz;
     StereoStatsAcc st;
-    int n_edge = 0;
+    int n_edge = 0, rc;
     if ((rc = stereo_recipe_pixels(ctx, "cvo_cloud_upload_stereo_recipe", *frame, leaf, edge_divisor, pix, xyz, &n_edge, st)) != CVO_OK) return rc;
     const size_t np = pix.size();
     std::vector<float> feat((size_t)FD * np), geo(2 * np);
@@ -381,20 +290,12 @@ int cvo_cloud_upload_stereo_recipe(cvo_ctx* ctx, const cvo_stereo_frame_t* frame
     const GrayView g = gray_view(view);
     float unused[3];
     for (size_t i = 0; i < np; i++) rgbd_recipe_row(view, g, pix[i], (int)i < n_edge, unused, &feat[(size_t)FD * i], &geo[2 * i]);
-    HostCloud h{(int)np, (const char*)xyz.data(), 12, (const char*)feat.data(), sizeof(float) * FD, nullptr, 0, (const char*)geo.data(), 8};
-    std::vector<StagedCloud> one(1);
-    if ((rc = upload_host_cloud(ctx, h, ctx->upload_stream, &one[0])) != CVO_OK) return rc;
-    if ((rc = finish_uploads(ctx, one)) != CVO_OK) return rc;
-    *out = one[0].c;
-    if (pixel && np) std::memcpy(pixel, pix.data(), sizeof(int) * np);
-    if (is_edge)
-      for (size_t i = 0; i < np; i++) is_edge[i] = (int)i < n_edge ? 1 : 0;
-    if (n) *n = (int)np;
+    const HostCloud h{(int)np, (const char*)xyz.data(), 12, (const char*)feat.data(), sizeof(float) * FD, nullptr, 0, (const char*)geo.data(), 8};
+    if ((rc = upload_one_locked(ctx, h, out)) != CVO_OK) return rc;
+    copy_kept(pix, pixel, n, is_edge, n_edge);
     ctx->stereo_last = st;
-  } catch (const std::exception& e) {
-    return fail(ctx, CVO_E_NOMEM, std::string("cvo_cloud_upload_stereo_recipe: ") + e.what());
-  }
-  return CVO_OK;
+    return CVO_OK;
+  });
 }
 
 int cvo_debug_stereo_stats(cvo_ctx* ctx, int capacity, int* n_tried, int* thresholds, int* counts, int* threshold_used, unsigned* histogram,

@@ -339,9 +339,8 @@ static int finish_uploads(cvo_ctx* ctx, std::vector<StagedCloud>& clouds) {
   return CVO_OK;
 }
 
-// One cloud on the context's upload stream (cvo_cloud_upload, cvo_cloud_upload_aos192).
-static int upload_one(cvo_ctx* ctx, const HostCloud& h, cvo_cloud** out) {
-  std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+// One cloud on the context's upload stream; the caller holds upload_mutex (the front ends' uploads, upload_one).
+static int upload_one_locked(cvo_ctx* ctx, const HostCloud& h, cvo_cloud** out) {
   std::vector<StagedCloud> one(1);
   int rc = upload_host_cloud(ctx, h, ctx->upload_stream, &one[0]);
   if (rc != CVO_OK) return rc;
@@ -349,6 +348,12 @@ static int upload_one(cvo_ctx* ctx, const HostCloud& h, cvo_cloud** out) {
   if (rc != CVO_OK) return rc;
   *out = one[0].c;
   return CVO_OK;
+}
+
+// ... taking the mutex (cvo_cloud_upload, cvo_cloud_upload_aos192)
+static int upload_one(cvo_ctx* ctx, const HostCloud& h, cvo_cloud** out) {
+  std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  return upload_one_locked(ctx, h, out);
 }
 
 int cvo_cloud_upload(cvo_ctx* ctx, int n, const float* xyz, const float* feat, const float* label,

@@ -58,31 +58,18 @@ int voxel_run_device(cvo_ctx* ctx, int n, const float* xyz, const float* d_xyz_g
   size_t cap = 1024;
   while (cap < 2 * (size_t)n) cap *= 2;
   const int nb = (n + VOX_THREADS - 1) / VOX_THREADS;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
-  const size_t o_ctl = take(sizeof(VoxelCtl)), o_stats = take(sizeof(VoxelBlockStats) * VOX_INSERT_BLOCKS), o_keys = take(sizeof(unsigned long long) * cap), o_first = take(sizeof(unsigned) * cap),
-               o_xyz = take(d_xyz_given ? 0 : sizeof(float) * 3 * (size_t)n), o_slot = take(sizeof(unsigned) * (size_t)n),
-               o_blocks = take(sizeof(unsigned) * (size_t)nb), o_kept = take(sizeof(int) * (size_t)n);
-  if (off > ctx->vox_scratch_bytes) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
-    if (ctx->vox_scratch) (void)hipFree(ctx->vox_scratch);
-    ctx->vox_scratch = nullptr;
-    ctx->vox_scratch_bytes = 0;
-    const hipError_t e = hipMalloc(&ctx->vox_scratch, off);
-    if (e != hipSuccess) return fail(ctx, CVO_E_NOMEM, std::string("voxel scratch hipMalloc: ") + hipGetErrorString(e));
-    ctx->vox_scratch_bytes = off;
-  }
-  char* b = ctx->vox_scratch;
+  ScratchLayout l;
+  const size_t o_ctl = l.take(sizeof(VoxelCtl)), o_stats = l.take(sizeof(VoxelBlockStats) * VOX_INSERT_BLOCKS), o_keys = l.take(sizeof(unsigned long long) * cap), o_first = l.take(sizeof(unsigned) * cap),
+               o_xyz = l.take(d_xyz_given ? 0 : sizeof(float) * 3 * (size_t)n), o_slot = l.take(sizeof(unsigned) * (size_t)n),
+               o_blocks = l.take(sizeof(unsigned) * (size_t)nb), o_kept = l.take(sizeof(int) * (size_t)n);
+  int rc = ctx->vox_scratch.reserve(ctx, l.off, "voxel scratch");
+  if (rc != CVO_OK) return rc;
+  char* b = ctx->vox_scratch.p;
   VoxelCtl* ctl = (VoxelCtl*)(b + o_ctl);
   unsigned long long* keys = (unsigned long long*)(b + o_keys);
   unsigned* first = (unsigned*)(b + o_first);
   const float* d_xyz = d_xyz_given ? d_xyz_given : (const float*)(b + o_xyz);
   unsigned* slot = (unsigned*)(b + o_slot);
-  unsigned* blocks = (unsigned*)(b + o_blocks);
   int* d_kept = (int*)(b + o_kept);
   VoxelBlockStats* stats = (VoxelBlockStats*)(b + o_stats);
   hipStream_t st = ctx->upload_stream;
@@ -95,14 +82,11 @@ int voxel_run_device(cvo_ctx* ctx, int n, const float* xyz, const float* d_xyz_g
     hipLaunchKernelGGL(k_voxel_insert<true>, dim3(grid), dim3(VOX_THREADS), 0, st, n, d_xyz, s, mask, keys, first, slot, ctl, stats);
   else
     hipLaunchKernelGGL(k_voxel_insert<false>, dim3(grid), dim3(VOX_THREADS), 0, st, n, d_xyz, s, mask, keys, first, slot, ctl, stats);
-  hipLaunchKernelGGL(k_voxel_flag, dim3(nb), dim3(VOX_THREADS), 0, st, n, mask, (const unsigned*)first, (const unsigned*)slot, blocks);
-  hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, st, nb, blocks, ctl, grid, (const VoxelBlockStats*)stats);
-  hipLaunchKernelGGL(k_voxel_compact, dim3(nb), dim3(VOX_THREADS), 0, st, n, mask, (const unsigned*)first, (const unsigned*)slot,
-                     (const unsigned*)blocks, d_kept);
-  HIP_TRY(ctx, hipGetLastError());
+  if ((rc = compact(ctx, n, VoxelFirst{mask, first, slot, d_kept}, (unsigned*)(b + o_blocks), ctl, grid, stats)) != CVO_OK) return rc;
   VoxelCtl h{};
-  HIP_TRY(ctx, hipMemcpyAsync(&h, ctl, sizeof h, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
+  // (the "kept more than it was given" refusal now comes before the one of h.status; at most n points are ever kept, so the
+  // two cannot meet)
+  if ((rc = compact_total(ctx, ctl, n, "voxel selection", "points", &h)) != CVO_OK) return rc;
   if (h.status) {
     std::string msg;
     std::vector<float> back;
@@ -114,7 +98,6 @@ int voxel_run_device(cvo_ctx* ctx, int n, const float* xyz, const float* d_xyz_g
     (void)voxel_validate(n, xyz, s, &msg);
     return fail(ctx, CVO_E_INVALID, "voxel selection: " + msg);
   }
-  if (h.n_kept > (unsigned)n) return fail(ctx, CVO_E_HIP, "voxel selection: the device kept more points than it was given");
   if (kept) {
     kept->resize(h.n_kept);
     if (h.n_kept) {
@@ -156,32 +139,25 @@ extern "C" {
 int cvo_voxel_select_host(int n, const float* xyz, float voxel_size, int* kept, int* n_kept) {
   if (n < 0 || (n > 0 && (!xyz || !kept)) || !n_kept) return CVO_E_INVALID;
   if (n > VOX_MAX_POINTS) return CVO_E_UNSUPPORTED;
-  try {
+  return frontend_call(nullptr, "", [&] {
     const int rc = voxel_validate(n, xyz, voxel_size, nullptr);
     if (rc != CVO_OK) return rc;
     std::vector<int> k;
     voxel_select_cpu(n, xyz, voxel_size, k);
-    if (!k.empty()) std::memcpy(kept, k.data(), sizeof(int) * k.size());
-    *n_kept = (int)k.size();
-  } catch (const std::exception&) {
-    return CVO_E_NOMEM;
-  }
-  return CVO_OK;
+    copy_kept(k, kept, n_kept);
+    return CVO_OK;
+  });
 }
 
 int cvo_voxel_select(cvo_ctx* ctx, int n, const float* xyz, float voxel_size, int* kept, int* n_kept) {
   if (!ctx || n < 0 || (n > 0 && (!xyz || !kept)) || !n_kept) return fail(ctx, CVO_E_INVALID, "cvo_voxel_select: bad argument");
-  try {
-    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  return frontend_call(ctx, "cvo_voxel_select", [&] {
     std::vector<int> k;
     const int rc = voxel_select(ctx, "cvo_voxel_select", n, xyz, voxel_size, k);
     if (rc != CVO_OK) return rc;
-    if (!k.empty()) std::memcpy(kept, k.data(), sizeof(int) * k.size());
-    *n_kept = (int)k.size();
-  } catch (const std::exception& e) {
-    return fail(ctx, CVO_E_NOMEM, std::string("cvo_voxel_select: ") + e.what());
-  }
-  return CVO_OK;
+    copy_kept(k, kept, n_kept);
+    return CVO_OK;
+  });
 }
 
 // Coordinates go to the device alone (12 bytes per point); the survivors' rows are gathered on the host straight into the
@@ -189,26 +165,17 @@ int cvo_voxel_select(cvo_ctx* ctx, int n, const float* xyz, float voxel_size, in
 int cvo_cloud_upload_voxel(cvo_ctx* ctx, int n, const float* xyz, const float* feat, const float* label, const float* geotype,
                            float voxel_size, cvo_cloud** out, int* kept, int* n_kept) {
   if (!ctx || !out || n < 0 || (n > 0 && !xyz)) return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_voxel: bad argument");
-  try {
-    std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  return frontend_call(ctx, "cvo_cloud_upload_voxel", [&] {
     std::vector<int> k;
     int rc = voxel_select(ctx, "cvo_cloud_upload_voxel", n, xyz, voxel_size, k);
     if (rc != CVO_OK) return rc;
     HostCloud h{(int)k.size(), (const char*)xyz, 12, (const char*)feat, sizeof(float) * FD, (const char*)label, sizeof(float) * NC,
                 (const char*)geotype, 8};
     h.rows = k.data();
-    std::vector<StagedCloud> one(1);
-    rc = upload_host_cloud(ctx, h, ctx->upload_stream, &one[0]);
-    if (rc != CVO_OK) return rc;
-    rc = finish_uploads(ctx, one);
-    if (rc != CVO_OK) return rc;
-    *out = one[0].c;
-    if (kept && !k.empty()) std::memcpy(kept, k.data(), sizeof(int) * k.size());
-    if (n_kept) *n_kept = (int)k.size();
-  } catch (const std::exception& e) {
-    return fail(ctx, CVO_E_NOMEM, std::string("cvo_cloud_upload_voxel: ") + e.what());
-  }
-  return CVO_OK;
+    if ((rc = upload_one_locked(ctx, h, out)) != CVO_OK) return rc;
+    copy_kept(k, kept, n_kept);
+    return CVO_OK;
+  });
 }
 
 int cvo_debug_voxel_stats(cvo_ctx* ctx, unsigned long long* capacity, unsigned long long* occupied, unsigned long long* probes_total,
