@@ -123,6 +123,12 @@ class CvoGPU {
   std::unique_ptr<ResidentClouds> upload_stereo_recipe(const ImageStereo& raw_image, const Calibration& calib, float leaf = 0.f,
                                                        float edge_divisor = 5.f, std::vector<int>* pixel = nullptr,
                                                        std::vector<unsigned char>* is_edge = nullptr) const;
+  // New: the LiDAR front end on the device (cvo_cloud_upload_lidar, include/cvo_hip.h): the cloud of
+  // CvoPointCloud(xyzi, n, [semantic, num_classes,] target, beam_num) - LOAM selection with the HDL-64 configuration -
+  // selected by the kernels, resident (size() == 1).  semantic: nullptr or n class ids.  rand as in the constructors.
+  // Defined in host/cvo_lidar.cpp.
+  std::unique_ptr<ResidentClouds> upload_lidar(const float* xyzi, int n, const std::vector<int>* semantic, int num_classes, int beam_num,
+                                               std::vector<int>* index = nullptr, cvo_lidar_rand_t* rand = nullptr) const;
   // New: multi-frame registration over resident clouds (cvo_multiframe_align as it is): poses 12 doubles per cloud (3x4
   // row-major, updated in place), edges pairs of indices into `clouds`.
   int align(const ResidentClouds& clouds, std::vector<double>& poses, const std::vector<bool>& frames_to_hold_const,

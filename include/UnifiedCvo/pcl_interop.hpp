@@ -33,6 +33,40 @@ float function_angle(const CvoGPU& cvo, const pcl::PointCloud<PointT>& source, c
                             is_approximate);
 }
 
+
+// The LiDAR constructors of upstream's CvoPointCloud (CvoPointCloud.cpp:964-1136) and CvoGPU::upload_lidar for a
+// pcl::PointCloud<pcl::PointXYZI>::Ptr (any point type with x, y, z and intensity members).
+template <typename PointT>
+std::vector<float> lidar_xyzi(const pcl::PointCloud<PointT>& pc) {
+  std::vector<float> xyzi(4 * pc.size());
+  for (size_t i = 0; i < pc.size(); i++) {
+    const PointT& p = pc.points[i];
+    xyzi[4 * i] = p.x;
+    xyzi[4 * i + 1] = p.y;
+    xyzi[4 * i + 2] = p.z;
+    xyzi[4 * i + 3] = p.intensity;
+  }
+  return xyzi;
+}
+template <typename CloudPtr>
+CvoPointCloud lidar_pointcloud(const CloudPtr& pc, int target_num_points, int beam_num,
+                               CvoPointCloud::PointSelectionMethod method = CvoPointCloud::LOAM, cvo_lidar_rand_t* rand = nullptr) {
+  const std::vector<float> xyzi = lidar_xyzi(*pc);
+  return CvoPointCloud(xyzi.data(), (int)pc->size(), target_num_points, beam_num, method, nullptr, rand);
+}
+template <typename CloudPtr>
+CvoPointCloud lidar_pointcloud(const CloudPtr& pc, const std::vector<int>& semantic, int num_classes, int target_num_points, int beam_num,
+                               CvoPointCloud::PointSelectionMethod method = CvoPointCloud::LOAM, cvo_lidar_rand_t* rand = nullptr) {
+  const std::vector<float> xyzi = lidar_xyzi(*pc);
+  return CvoPointCloud(xyzi.data(), (int)pc->size(), semantic, num_classes, target_num_points, beam_num, method, nullptr, rand);
+}
+template <typename CloudPtr>
+std::unique_ptr<CvoGPU::ResidentClouds> upload_lidar(const CvoGPU& cvo, const CloudPtr& pc, const std::vector<int>* semantic, int num_classes,
+                                                     int beam_num, cvo_lidar_rand_t* rand = nullptr) {
+  const std::vector<float> xyzi = lidar_xyzi(*pc);
+  return cvo.upload_lidar(xyzi.data(), (int)pc->size(), semantic, num_classes, beam_num, nullptr, rand);
+}
+
 }  // namespace cvo
 #endif
 #endif

@@ -1,6 +1,6 @@
 // Host point-cloud container: the accessor subset of upstream utils/CvoPointCloud.hpp:126-188 that the
 // align() path and its drivers use, the RGB-D image constructor (FULL / DSO_EDGES) and the stereo image constructor from a
-// given disparity (CV_FAST / DSO_EDGES / FULL).  The LiDAR constructors are out of scope.
+// given disparity (CV_FAST / DSO_EDGES / FULL) and the LiDAR constructors (LOAM) over plain arrays.
 #pragma once
 #include <string>
 #include <vector>
@@ -20,6 +20,9 @@ class Calibration;
 template <typename DepthType>
 class ImageRGBD;
 class ImageStereo;
+}  // namespace cvo
+struct cvo_lidar_rand_t;
+namespace cvo {
 
 class CvoPointCloud {
  public:
@@ -53,6 +56,19 @@ class CvoPointCloud {
   // throws std::invalid_argument.  pixel (optional): v * cols + u of every point.  Defined in host/cvo_stereo.cpp.
   CvoPointCloud(const ImageStereo& raw_image, const Calibration& calib, PointSelectionMethod pt_selection_method = CV_FAST,
                 std::vector<int>* pixel = nullptr);
+
+  // upstream CvoPointCloud.cpp:964-1038 and :1040-1136 (pcl::PointCloud<pcl::PointXYZI>::Ptr; the PCL-typed overloads are
+  // in pcl_interop.hpp) for pt_selection_method LOAM, the default, on the host (cvo_lidar_select_host, include/cvo_hip.h:
+  // edge_detection, then LeGO-LOAM's selection with the HDL-64 configuration and beam_num): xyzi is n x 4 floats - x, y, z,
+  // intensity in upstream's axes, in scan order; F = 1 (intensity), type (1, 0), one-hot labels with `semantic` (n class ids,
+  // -1 = unlabelled).  target_num_points is accepted and unused, as upstream leaves it.  RANDOM and LIDAR_EDGES throw
+  // std::invalid_argument.  rand: the stream the thinning draws from (cvo_lidar_rand_seed); nullptr = one stream per
+  // process that starts as an unseeded std::rand() does, as upstream draws.  index (optional): the point of every row.
+  // Defined in host/cvo_lidar.cpp.
+  CvoPointCloud(const float* xyzi, int n, int target_num_points, int beam_num, PointSelectionMethod pt_selection_method = LOAM,
+                std::vector<int>* index = nullptr, cvo_lidar_rand_t* rand = nullptr);
+  CvoPointCloud(const float* xyzi, int n, const std::vector<int>& semantic, int num_classes, int target_num_points, int beam_num,
+                PointSelectionMethod pt_selection_method = LOAM, std::vector<int>* index = nullptr, cvo_lidar_rand_t* rand = nullptr);
 
   static CvoPointCloud from_xyz(const float* xyz, int n);                                // type (1,0), F = 0
   static CvoPointCloud from_xyzrgb(const float* xyz, const unsigned char* rgb, int n);   // type (0,1), F = 5

@@ -322,6 +322,62 @@ int cvo_cloud_upload_stereo(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, int m
  * region is one: a non-finite coordinate).  pixel / is_edge: room for 2 x rows x cols entries. */
 int cvo_cloud_upload_stereo_recipe(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, float leaf, float edge_divisor, cvo_cloud** out,
                                    int* pixel, unsigned char* is_edge, int* n);
+/* ---- LiDAR front end: replaces CvoPointCloud(PointCloud<PointXYZI>::Ptr, target_num_points, beam_num, LOAM) and its
+ * semantic twin (CvoPointCloud.cpp:964-1136): LidarPointSelector::edge_detection, then LeGoLoamPointSelection::cloudHandler
+ * (ring ids from the 4 -> 1 quadrant transitions, range image, ground, components with the validity rule, the segmented
+ * cloud, smoothness, occlusion marks, up to 20 edges per sixth of a ring, the std::rand() % 4 thinning of the rest) ----
+ * The statement of what is computed, departures from upstream's text included, is tests/np_lidar.py. */
+typedef struct cvo_lidar_scan_t {
+  int n;                       /* points, in the order the sensor returned them */
+  const float* xyzi;           /* n x 4: x, y, z, intensity in upstream's axes (x = -raw.y, y = -raw.z, z = raw.x) */
+  const int* semantic;         /* n class ids, -1 = unlabelled; NULL = no semantics */
+  int num_classes;             /* 0 without semantics */
+} cvo_lidar_scan_t;
+typedef struct cvo_lidar_config_t {
+  int n_scan, horizon_scan;    /* the range image: at most 128 x 4096 */
+  float ang_res_x;             /* degrees per column */
+  int ground_scan_ind;         /* rows 0 .. ground_scan_ind are tested for ground; below n_scan */
+  float sensor_min_range, sensor_mount_angle /* degrees, |.| <= 45 */;
+  float segment_theta, segment_alpha_x, segment_alpha_y;   /* radians, in (0, pi / 2) */
+  int segment_valid_point_num, segment_valid_line_num;
+  float edge_threshold, surf_threshold;
+  double intensity_bound, depth_bound, distance_bound;     /* edge_detection's */
+  int beam_num;                /* edge_detection's ring limit */
+  /* derived by cvo_lidar_config_derive, the only libm calls of the front end: tan(segment_theta), sin / cos of the two
+   * alphas, tan(mount -/+ 10 degrees), tan(mount -/+ 3 degrees).  Every angle test is a cross-multiplication with these. */
+  double tan_theta, sin_alpha_x, cos_alpha_x, sin_alpha_y, cos_alpha_y, tan_ground_lo, tan_ground_hi, tan_self_lo, tan_self_hi;
+} cvo_lidar_config_t;
+/* glibc's default rand() (the additive-feedback TYPE_3 generator), restated: the stream extractFeatures draws from. */
+typedef struct cvo_lidar_rand_t {
+  unsigned int r[31];
+  int front, rear;
+} cvo_lidar_rand_t;
+/* The HDL-64 values of LeGoLoamPointSelection.hpp:296-341 and the constructors' bounds (distance 40, semantic: 75), derived
+ * fields included.  cvo_lidar_config_derive recomputes the derived fields after a change of the angles. */
+void cvo_lidar_config_default(cvo_lidar_config_t* cfg, int semantic);
+void cvo_lidar_config_derive(cvo_lidar_config_t* cfg);
+/* srand(seed): seed 1 is the stream of a process that never called srand. */
+void cvo_lidar_rand_seed(cvo_lidar_rand_t* state, unsigned int seed);
+/* One draw, as rand() returns it: the stepping function the library's calls use. */
+unsigned int cvo_lidar_rand_next(cvo_lidar_rand_t* state);
+/* The indices of the selected points: edge_detection's list, then LeGO-LOAM's - per ring and sixth the edges in pick order,
+ * then the thinned rest ascending -, duplicates kept (a point can be in both lists).  is_edge (optional): 1 for
+ * edge_detection's points and LeGO-LOAM's edges, 0 for thinned points.  With semantics, unlabelled points are in neither
+ * list (their draws are still consumed).  index / is_edge: room for 2 x n entries.  `rand` advances by exactly the draws
+ * upstream would make (one per non-edge point of every sixth), so a driver chains frames with one state.
+ * CVO_E_INVALID, nothing written and no draw consumed: a missing pointer, n < 1, a config field that is not positive or out
+ * of range (n_scan > 128, horizon_scan > 4096, ground_scan_ind >= n_scan, ...), derived fields that do not match the
+ * angles, a label outside -1 .. num_classes - 1, a coordinate that is not finite or not below 1e15 in magnitude.
+ * CVO_E_UNSUPPORTED: more than 2^24 points.  cvo_lidar_select runs on the upload stream; switch LIDAR_HOST=1 / 0: the CPU
+ * twin / the kernels for every size (unset: scans under 12000 points take the CPU twin). */
+int cvo_lidar_select_host(const cvo_lidar_scan_t* scan, const cvo_lidar_config_t* cfg, cvo_lidar_rand_t* rand, int* index,
+                          unsigned char* is_edge, int* n);   /* CPU twin, no context */
+int cvo_lidar_select(cvo_ctx* ctx, const cvo_lidar_scan_t* scan, const cvo_lidar_config_t* cfg, cvo_lidar_rand_t* rand,
+                     int* index, unsigned char* is_edge, int* n);
+/* The constructor's cloud: the selected points through cvo_cloud_upload with F = 1 (intensity, zero-padded to 5), type
+ * (1, 0) and - with semantics - one-hot labels, padded or cut to 19 classes.  index (optional), *n (optional). */
+int cvo_cloud_upload_lidar(cvo_ctx* ctx, const cvo_lidar_scan_t* scan, const cvo_lidar_config_t* cfg, cvo_lidar_rand_t* rand,
+                           cvo_cloud** out, int* index, int* n);
 int cvo_cloud_size(const cvo_cloud* c);
 void cvo_cloud_free(cvo_cloud* c);
 

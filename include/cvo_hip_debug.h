@@ -109,6 +109,13 @@ int cvo_debug_rgbd_stats(cvo_ctx* ctx, int* n_tried, int* potentials /* 8 */, in
  * Any pointer may be NULL. */
 int cvo_debug_stereo_stats(cvo_ctx* ctx, int capacity, int* n_tried, int* thresholds, int* counts, int* threshold_used,
                            unsigned* histogram /* 257 */, unsigned long long* candidates, unsigned long long* kept, int* on_device);
+/* The context's last cvo_lidar_select / cvo_cloud_upload_lidar, counts[9]: range-image cells that hold a point, ground
+ * cells, valid components, invalid components, segmented points, LeGO-LOAM edge picks, draws consumed, thinned points kept,
+ * edge_detection's points; whether the kernels ran.  Any pointer may be NULL. */
+int cvo_debug_lidar_stats(cvo_ctx* ctx, unsigned long long* counts /* 9 */, int* on_device);
+/* lidar_atan2_deg of cvo_lidar_math.h - the one copy the CPU twin and the kernels compile - on n pairs, on the host:
+ * out[i] = atan2(y[i], x[i]) in degrees.  No context. */
+int cvo_debug_lidar_atan2(int n, const double* y, const double* x, double* out);
 
 #ifdef __cplusplus
 }

@@ -200,6 +200,45 @@ class cvo_stereo_frame_t(C.Structure):
     ]
 
 
+class cvo_lidar_scan_t(C.Structure):
+    _fields_ = [("n", C.c_int), ("xyzi", C.c_void_p), ("semantic", C.c_void_p), ("num_classes", C.c_int)]
+
+
+class cvo_lidar_config_t(C.Structure):
+    _fields_ = [
+        ("n_scan", C.c_int),
+        ("horizon_scan", C.c_int),
+        ("ang_res_x", C.c_float),
+        ("ground_scan_ind", C.c_int),
+        ("sensor_min_range", C.c_float),
+        ("sensor_mount_angle", C.c_float),
+        ("segment_theta", C.c_float),
+        ("segment_alpha_x", C.c_float),
+        ("segment_alpha_y", C.c_float),
+        ("segment_valid_point_num", C.c_int),
+        ("segment_valid_line_num", C.c_int),
+        ("edge_threshold", C.c_float),
+        ("surf_threshold", C.c_float),
+        ("intensity_bound", C.c_double),
+        ("depth_bound", C.c_double),
+        ("distance_bound", C.c_double),
+        ("beam_num", C.c_int),
+        ("tan_theta", C.c_double),
+        ("sin_alpha_x", C.c_double),
+        ("cos_alpha_x", C.c_double),
+        ("sin_alpha_y", C.c_double),
+        ("cos_alpha_y", C.c_double),
+        ("tan_ground_lo", C.c_double),
+        ("tan_ground_hi", C.c_double),
+        ("tan_self_lo", C.c_double),
+        ("tan_self_hi", C.c_double),
+    ]
+
+
+class cvo_lidar_rand_t(C.Structure):
+    _fields_ = [("r", C.c_uint * 31), ("front", C.c_int), ("rear", C.c_int)]
+
+
 CVO_DEPTH_U16, CVO_DEPTH_F32 = 0, 1
 CVO_SELECT_CV_FAST, CVO_SELECT_DSO_EDGES, CVO_SELECT_FULL = 0, 2, 8
 CVO_FAST_RGBD, CVO_FAST_STEREO, CVO_FAST_STEREO_SEMANTIC = (9, 15000, 12000, 13), (4, 24000, 15000, 50), (4, 28000, 15000, 50)
@@ -222,6 +261,8 @@ EXPORTED = [
     "cvo_rgbd_points", "cvo_rgbd_points_host", "cvo_cloud_upload_rgbd", "cvo_debug_rgbd_stats",
     "cvo_fast_select", "cvo_fast_select_host", "cvo_stereo_points", "cvo_stereo_points_host", "cvo_cloud_upload_stereo",
     "cvo_cloud_upload_stereo_recipe", "cvo_debug_stereo_stats",
+    "cvo_lidar_config_default", "cvo_lidar_config_derive", "cvo_lidar_rand_seed", "cvo_lidar_rand_next", "cvo_lidar_select", "cvo_lidar_select_host",
+    "cvo_cloud_upload_lidar", "cvo_debug_lidar_stats", "cvo_debug_lidar_atan2",
 ]
 
 _libs = {}
@@ -325,6 +366,20 @@ def lib(path=None):
     L.cvo_cloud_upload_stereo.argtypes = [vp, sf, ip, C.POINTER(vp), ipp, ipp]
     L.cvo_cloud_upload_stereo_recipe.argtypes = [vp, sf, C.c_float, C.c_float, C.POINTER(vp), ipp, up, ipp]
     L.cvo_debug_stereo_stats.argtypes = [vp, ip, ipp, ipp, ipp, ipp, C.POINTER(C.c_uint)] + [C.POINTER(C.c_ulonglong)] * 2 + [ipp]
+    ls, lc, lr = C.POINTER(cvo_lidar_scan_t), C.POINTER(cvo_lidar_config_t), C.POINTER(cvo_lidar_rand_t)
+    L.cvo_lidar_config_default.argtypes = [lc, ip]
+    L.cvo_lidar_config_default.restype = None
+    L.cvo_lidar_config_derive.argtypes = [lc]
+    L.cvo_lidar_config_derive.restype = None
+    L.cvo_lidar_rand_seed.argtypes = [lr, C.c_uint]
+    L.cvo_lidar_rand_seed.restype = None
+    L.cvo_lidar_rand_next.argtypes = [lr]
+    L.cvo_lidar_rand_next.restype = C.c_uint
+    L.cvo_debug_lidar_atan2.argtypes = [ip, dp, dp, dp]
+    L.cvo_lidar_select_host.argtypes = [ls, lc, lr, ipp, up, ipp]
+    L.cvo_lidar_select.argtypes = [vp, ls, lc, lr, ipp, up, ipp]
+    L.cvo_cloud_upload_lidar.argtypes = [vp, ls, lc, lr, C.POINTER(vp), ipp, ipp]
+    L.cvo_debug_lidar_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), ipp]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

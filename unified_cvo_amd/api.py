@@ -318,6 +318,91 @@ def stereo_points_host(frame, method=CV_FAST):
     return pc
 
 
+class LidarScan:
+    """One raw LiDAR scan (cvo_lidar_scan_t): `xyzi` (n, 4) float32 - x, y, z, intensity in upstream's axes after
+    KittiHandler::read_next_lidar (x = -raw.y, y = -raw.z, z = raw.x), in the order the sensor returned them - and optionally
+    `semantic` (n,) int32 class ids, -1 = unlabelled, with `num_classes`."""
+
+    def __init__(self, xyzi, semantic=None, num_classes=0):
+        self.xyzi = np.ascontiguousarray(xyzi, np.float32).reshape(-1, 4)
+        self.n = len(self.xyzi)
+        self.semantic = None if semantic is None else np.ascontiguousarray(semantic, np.int32).reshape(self.n)
+        self.num_classes = int(num_classes)
+
+    def c_struct(self):
+        """cvo_lidar_scan_t over this scan's arrays (which must outlive it)."""
+        return _capi.cvo_lidar_scan_t(self.n, self.xyzi.ctypes.data, None if self.semantic is None else self.semantic.ctypes.data, self.num_classes)
+
+
+class LidarConfig:
+    """cvo_lidar_config_t: what upstream compiles into LeGoLoamPointSelection.hpp and the LiDAR constructors.  The HDL-64
+    defaults (distance bound 40, `semantic`: 75); keyword arguments override fields, the derived constants follow."""
+
+    def __init__(self, semantic=False, **fields):
+        self.c = _capi.cvo_lidar_config_t()
+        _capi.lib().cvo_lidar_config_default(C.byref(self.c), int(bool(semantic)))
+        self.set(**fields)
+
+    def set(self, **fields):
+        for name, value in fields.items():
+            if name not in dict(_capi.cvo_lidar_config_t._fields_):
+                raise AttributeError(name)
+            setattr(self.c, name, value)
+        _capi.lib().cvo_lidar_config_derive(C.byref(self.c))
+        return self
+
+    def __getattr__(self, name):
+        return getattr(self.__dict__["c"], name)
+
+
+class LidarRand:
+    """cvo_lidar_rand_t: the state of glibc's default rand(), which the thinning draws from; one state chained through the
+    frames of a run reproduces a process that made no other draw.  Seed 1 is an unseeded process."""
+
+    def __init__(self, seed=1):
+        self.c = _capi.cvo_lidar_rand_t()
+        self.seed(seed)
+
+    def seed(self, seed):
+        _capi.lib().cvo_lidar_rand_seed(C.byref(self.c), int(seed))
+
+    def state(self):
+        return list(self.c.r), self.c.front, self.c.rear
+
+    def next(self):
+        """cvo_lidar_rand_next: one draw, as rand() would return it, by the stepping function the library's calls use."""
+        return int(_capi.lib().cvo_lidar_rand_next(C.byref(self.c)))
+
+
+def debug_lidar_atan2(y, x):
+    """cvo_debug_lidar_atan2: the library's own atan2 in degrees (cvo_lidar_math.h, what the twin and the kernels compile),
+    evaluated on the host for arrays y, x of doubles."""
+    y, x = np.ascontiguousarray(np.broadcast_arrays(y, x)[0], np.float64), np.ascontiguousarray(np.broadcast_arrays(y, x)[1], np.float64)
+    out = np.zeros(y.shape, np.float64)
+    dp = C.POINTER(C.c_double)
+    rc = _capi.lib().cvo_debug_lidar_atan2(int(y.size), y.ctypes.data_as(dp), x.ctypes.data_as(dp), out.ctypes.data_as(dp))
+    if rc != 0:
+        _raise(rc, "cvo_debug_lidar_atan2 refused its arguments")
+    return out
+
+
+def _lidar_select(call, scan, config, rand):
+    """Shared by CvoGPU.lidar_select and lidar_select_host -> (rc, indices, is_edge)."""
+    cap = max(2 * scan.n, 1)
+    index, is_edge = np.zeros(cap, np.int32), np.zeros(cap, np.uint8)
+    n, s = C.c_int(), scan.c_struct()
+    rc = call(C.byref(s), C.byref(config.c), C.byref(rand.c), index.ctypes.data_as(C.POINTER(C.c_int)), is_edge.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(n))
+    return rc, index[:n.value].copy(), is_edge[:n.value].astype(bool)
+
+
+def lidar_select_host(scan, config, rand):
+    """cvo_lidar_select_host: the CPU twin of CvoGPU.lidar_select, no context -> (indices, is_edge)."""
+    rc, index, is_edge = _lidar_select(_capi.lib().cvo_lidar_select_host, scan, config, rand)
+    if rc != 0:
+        _raise(rc, "cvo_lidar_select_host refused the scan or the config")
+    return index, is_edge
+
+
 class DeviceCloud:
     """A cloud resident in HBM (cvo_cloud*)."""
 
@@ -660,6 +745,32 @@ class CvoGPU:
         k = min(nt.value, cap)
         return dict(tried=list(tried[:k]), counts=list(cnts[:k]), threshold_used=used.value, histogram=np.array(hist[:], np.int64),
                     candidates=cand.value, kept=kept.value, on_device=bool(dev.value))
+
+    def lidar_select(self, scan, config, rand):
+        """cvo_lidar_select: the LOAM point selection of CvoPointCloud(PointCloud<PointXYZI>::Ptr, n, beams) - edge_detection's
+        indices, then LeGO-LOAM's - by the context's route (switch LIDAR_HOST) -> (indices, is_edge).  `rand` advances by the
+        draws upstream would make."""
+        rc, index, is_edge = _lidar_select(lambda *a: self.L.cvo_lidar_select(self.ctx, *a), scan, config, rand)
+        self._check(rc)
+        return index, is_edge
+
+    def upload_lidar(self, scan, config, rand):
+        """cvo_cloud_upload_lidar: the constructor's cloud - the selected points with F = 1 (intensity), type (1, 0) and, with
+        semantics, one-hot labels - resident; `.pixel` is the point index per row."""
+        index = np.zeros(max(2 * scan.n, 1), np.int32)
+        n, h, s = C.c_int(), C.c_void_p(), scan.c_struct()
+        self._check(self.L.cvo_cloud_upload_lidar(self.ctx, C.byref(s), C.byref(config.c), C.byref(rand.c), C.byref(h),
+                                                  index.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n)))
+        return self._resident(h, n.value, index)
+
+    def debug_lidar_stats(self):
+        """cvo_debug_lidar_stats of the last lidar_select / upload_lidar."""
+        counts, dev = (C.c_ulonglong * 9)(), C.c_int()
+        self._check(self.L.cvo_debug_lidar_stats(self.ctx, counts, C.byref(dev)))
+        names = ("projected", "ground", "valid", "invalid", "segmented", "edges", "draws", "thinned", "edge_detected")
+        out = dict(zip(names, (int(v) for v in counts)))
+        out["on_device"] = bool(dev.value)
+        return out
 
     def upload_many(self, clouds, threads=None):
         """Uploads a list of clouds with cvo_cloud_upload_many: a pool of host threads inside the library, each cloud

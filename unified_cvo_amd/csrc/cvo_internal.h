@@ -1,5 +1,5 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
 // pair, graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -147,6 +147,12 @@ struct StereoStatsAcc {
   int on_device = 0;
 };
 
+// what cvo_debug_lidar_stats reports of the context's last LiDAR call (cvo_lidar.hip)
+struct LidarStatsAcc {
+  unsigned long long projected = 0, ground = 0, valid = 0, invalid = 0, segmented = 0, edges = 0, draws = 0, thinned = 0, edge_detected = 0;
+  int on_device = 0;
+};
+
 // offsets of a call's buffers in one device allocation, 256-byte aligned; `off` ends as the bytes to allocate
 struct ScratchLayout {
   size_t off = 0;
@@ -242,6 +248,10 @@ struct cvo_ctx {
   std::vector<unsigned char> rgbd_excl;  // staging of the exclusion bytes of a semantic frame
   RgbdStatsAcc rgbd_last{};
   StereoStatsAcc stereo_last{};  // (the stereo front end and cvo_fast_select share the RGB-D region)
+  // LiDAR front end (cvo_lidar.hip): one growable device region - the scan, the range image's per-cell arrays, the
+  // segmented cloud's arrays, the picks
+  DeviceScratch lidar_scratch;
+  LidarStatsAcc lidar_last{};
   double clock_ms_per_tick = 0.0;  // s_memrealtime, calibrated on first use (cvo_debug_kernel_clock)
 };
 

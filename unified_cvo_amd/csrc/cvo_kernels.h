@@ -68,3 +68,4 @@
 #include "cvo_k_rgbd.h"
 #include "cvo_k_fast.h"
 #include "cvo_k_stereo.h"
+#include "cvo_k_lidar.h"
