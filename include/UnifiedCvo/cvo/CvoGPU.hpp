@@ -129,6 +129,14 @@ class CvoGPU {
   // Defined in host/cvo_lidar.cpp.
   std::unique_ptr<ResidentClouds> upload_lidar(const float* xyzi, int n, const std::vector<int>* semantic, int num_classes, int beam_num,
                                                std::vector<int>* index = nullptr, cvo_lidar_rand_t* rand = nullptr) const;
+  // New: the first statement of upstream's RawImage constructor on the device (cvo_nlm_denoise / cvo_nlm_denoise_lab,
+  // include/cvo_hip.h): cv::fastNlMeansDenoising of an 8-bit image of 1 .. 3 interleaved channels, and the middle of
+  // cv::fastNlMeansDenoisingColored on a Lab image (BGR <-> Lab stays the caller's).  dst may be src.  Refusals throw
+  // std::invalid_argument.  Defined in host/cvo_nlm.cpp.
+  void nlm_denoise(int rows, int cols, int channels, const unsigned char* src, unsigned char* dst, float h = 10.f, int template_window = 7,
+                   int search_window = 21) const;
+  void nlm_denoise_lab(int rows, int cols, const unsigned char* lab, unsigned char* dst, float h = 10.f, float h_color = 10.f,
+                       int template_window = 7, int search_window = 21) const;
   // New: multi-frame registration over resident clouds (cvo_multiframe_align as it is): poses 12 doubles per cloud (3x4
   // row-major, updated in place), edges pairs of indices into `clouds`.
   int align(const ResidentClouds& clouds, std::vector<double>& poses, const std::vector<bool>& frames_to_hold_const,

@@ -44,7 +44,7 @@ class CvoPointCloud {
   // upstream CvoPointCloud.cpp:459-553 for DepthType uint16_t / float (utils/ImageRGBD.hpp, utils/Calibration.hpp) and
   // pt_selection_method FULL or DSO_EDGES, on the host (cvo_rgbd_points_host, include/cvo_hip.h, states the contract: F =
   // channels + 2, point order, the gradient-index quirk); every other method throws std::invalid_argument (OpenCV
-  // detectors and rand() are not restated).  The image is taken as it is: no denoising (utils/RawImage.hpp).
+  // detectors and rand() are not restated).  The image is taken as it is: denoise it first with CvoGPU::nlm_denoise(_lab) (utils/RawImage.hpp).
   // pixel (optional): v * cols + u of every point.  Defined in host/cvo_rgbd.cpp.
   template <typename DepthType>
   CvoPointCloud(const ImageRGBD<DepthType>& raw_image, const Calibration& calib, PointSelectionMethod pt_selection_method,

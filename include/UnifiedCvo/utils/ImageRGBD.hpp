@@ -1,5 +1,5 @@
 // cvo::ImageRGBD<DepthType> (upstream utils/ImageRGBD.hpp): a RawImage with its depth image, DepthType uint16_t or float.
-// Raw buffers in place of cv::Mat; no denoising (see RawImage.hpp).
+// Raw buffers in place of cv::Mat; no denoising inside the class: CvoGPU::nlm_denoise(_lab) first (see RawImage.hpp).
 #pragma once
 #include <vector>
 

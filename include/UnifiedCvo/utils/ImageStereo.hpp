@@ -1,5 +1,5 @@
 // cvo::ImageStereo (upstream utils/ImageStereo.hpp): the left RawImage with its left disparity map, in pixels.
-// Raw buffers in place of cv::Mat; no denoising (see RawImage.hpp).
+// Raw buffers in place of cv::Mat; no denoising inside the class: CvoGPU::nlm_denoise(_lab) first (see RawImage.hpp).
 //
 // NOT here: upstream's ImageStereo(left, right) constructor computes the disparity with libelas
 // (StaticStereo::disparity, StaticStereo.cpp:20-64).  libelas is not part of this library: the caller runs its own matcher

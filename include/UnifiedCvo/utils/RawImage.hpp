@@ -1,8 +1,10 @@
 // cvo::RawImage (upstream utils/RawImage.hpp, RawImage.cpp) over raw buffers in place of cv::Mat: the colour image, the
 // float gray plane, its central-difference gradient and - optionally - a per-pixel class distribution.
 //
-// NOT here: upstream's constructor first runs cv::fastNlMeansDenoising(Colored) on the image (RawImage.cpp:21-24).  That
-// is OpenCV's algorithm; a caller who wants upstream's numbers denoises with OpenCV and hands the RESULT to this class.
+// NOT in this class: upstream's constructor first runs cv::fastNlMeansDenoising(Colored) on the image (RawImage.cpp:21-24).
+// The library has that step as a call of its own - cvo_nlm_denoise / cvo_nlm_denoise_lab (include/cvo_hip.h),
+// CvoGPU::nlm_denoise / nlm_denoise_lab - and a caller who wants upstream's numbers hands its RESULT to this class (colour
+// frames: BGR -> Lab with the caller's OpenCV, nlm_denoise_lab, Lab -> BGR).
 // The gray plane of a 3-channel (BGR) image is OpenCV 3's 8-bit COLOR_BGR2GRAY, (1868 B + 9617 G + 4899 R + 8192) >> 14;
 // OpenCV 4 differs by one level at rare pixels, so set_gray() takes the plane of the caller's own OpenCV.
 // Header-only, host compiler only.

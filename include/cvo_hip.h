@@ -210,8 +210,8 @@ int cvo_cloud_upload_voxel(cvo_ctx* ctx, int n, const float* xyz, const float* f
 /* ---- RGB-D front end: replaces CvoPointCloud(ImageRGBD<T>, Calibration, PointSelectionMethod) (CvoPointCloud.cpp:459-553,
  * CvoPixelSelector.cpp:51-474, RawImage.cpp:55-82) and the per-frame block of the multi-frame RGB-D drivers
  * (main_multi_frame_irls_tum.cpp:279-335) ----
- * A frame: the colour image AS RawImage HOLDS IT AFTER ITS DENOISING (cv::fastNlMeansDenoising is not part of this
- * library), rows x cols x channels bytes, BGR order for 3 channels; optionally the 8-bit gray plane the gradient is taken
+ * A frame: the colour image AS RawImage HOLDS IT AFTER ITS DENOISING (cvo_nlm_denoise / cvo_nlm_denoise_lab below),
+ * rows x cols x channels bytes, BGR order for 3 channels; optionally the 8-bit gray plane the gradient is taken
  * of (NULL: 1-channel images as they are, 3-channel ones through OpenCV 3's 8-bit COLOR_BGR2GRAY,
  * (1868 B + 9617 G + 4899 R + 8192) >> 14; OpenCV 4 differs by one level at rare pixels, so parity with a given OpenCV
  * needs the caller's plane); the depth image, uint16_t or float; the calibration; optionally num_classes floats per pixel. */
@@ -284,7 +284,7 @@ int cvo_fast_select_host(int rows, int cols, const uint8_t* gray, const cvo_fast
  * StaticStereo.cpp:84-107, is_good_point :39-49) FROM A GIVEN DISPARITY MAP (upstream computes it with libelas, which is not
  * part of this library; its invalid marker -10 is rejected like every disparity below 0.05) and the per-frame block of the
  * multi-frame KITTI driver (main_multi_frame_irls_kitti.cpp:235-292) ----
- * image / gray / semantic: as in cvo_rgbd_frame_t (the LEFT image, after RawImage's denoising). */
+ * image / gray / semantic: as in cvo_rgbd_frame_t (the LEFT image, after RawImage's denoising: cvo_nlm_denoise). */
 typedef struct cvo_stereo_frame_t {
   int rows, cols, channels;    /* channels: 1 or 3 */
   const uint8_t* image;        /* rows x cols x channels */
@@ -378,6 +378,46 @@ int cvo_lidar_select(cvo_ctx* ctx, const cvo_lidar_scan_t* scan, const cvo_lidar
  * (1, 0) and - with semantics - one-hot labels, padded or cut to 19 classes.  index (optional), *n (optional). */
 int cvo_cloud_upload_lidar(cvo_ctx* ctx, const cvo_lidar_scan_t* scan, const cvo_lidar_config_t* cfg, cvo_lidar_rand_t* rand,
                            cvo_cloud** out, int* index, int* n);
+/* ---- non-local-means denoising: replaces RawImage's first statement (RawImage.cpp:21-24),
+ * cv::fastNlMeansDenoising(image, image, 10, 7, 21) for gray frames and the middle of
+ * cv::fastNlMeansDenoisingColored(image, image, 10, 10, 7, 21) for colour ones ----
+ * OpenCV's FastNlMeansDenoisingInvoker for 8-bit images with the squared distance, restated from OpenCV's published
+ * algorithm (parity with a given OpenCV binary is unpinned: OpenCV is not part of this library's tests); the statement is
+ * tests/np_nlm.py.  th = template_window / 2, sh = search_window / 2, tw = 2 th + 1, sw = 2 sh + 1 (an even size grows by
+ * one), b = th + sh.  The image is extended by b on every side with BORDER_REFLECT_101 (repeated on images smaller than
+ * b + 1).  mult = INT_MAX / (sw sw 255); shift: the smallest p with (1 << p) >= tw tw; m = (1 << shift) / (tw tw);
+ * weight[d] = lrint(mult exp(-(d m) / hh)) in double, ties to even, for d < int(255 255 channels / m + 1), hh = h h channels
+ * evaluated in float, entries under 0.001 mult set to 0.  For every pixel and every offset of [-sh, sh]^2: dist = the sum
+ * over the tw x tw template and the channels of the squared differences of the two patches, w = weight[dist >> shift];
+ * out[c] = min(255, (sum w q[c] + sum w / 2) / sum w) in unsigned 32-bit arithmetic, q the offset pixel.
+ * channels: 1, 2 or 3, interleaved; 3 is OpenCV's fastNlMeansDenoising of a CV_8UC3 image, NOT the Colored call.
+ * dst == src (in place) is allowed.  CVO_E_INVALID, nothing written: a missing pointer, rows / cols < 1, channels outside
+ * 1 .. 3, h / h_color not finite or <= 0 (upstream's h = 0 branch is not reproduced), a window < 1.  CVO_E_UNSUPPORTED, on
+ * both routes: th > 3 or sh > 10 (upstream only ever asks for 7 / 21), more than 2^24 pixels.  cvo_nlm_denoise runs on the
+ * context's upload stream like the front ends: it neither waits for nor delays a solve.  Switch NLM_HOST=1 / 0: the CPU twin
+ * (one thread) / the kernel of cvo_k_nlm.h for every size (unset: images under 256 pixels take the CPU twin). */
+typedef struct cvo_nlm_config_t {
+  float h;
+  int template_window, search_window;
+} cvo_nlm_config_t;
+void cvo_nlm_config_default(cvo_nlm_config_t* cfg);   /* 10, 7, 21: RawImage's call */
+/* The one place the table is built (double, the host's exp); the twin and the device route take it from here.  Writes the
+ * first min(capacity, *n_table) entries to weight (NULL: the sizes only); *n_nonzero: the length of the nonzero leading run.
+ * Any output pointer may be NULL.  Refusals as above. */
+int cvo_nlm_weights(const cvo_nlm_config_t* cfg, int channels, int* weight, int capacity, int* n_table, int* n_nonzero,
+                    int* mult, int* shift);
+int cvo_nlm_denoise_host(int rows, int cols, int channels, const uint8_t* src, const cvo_nlm_config_t* cfg,
+                         uint8_t* dst);   /* CPU twin, no context */
+int cvo_nlm_denoise(cvo_ctx* ctx, int rows, int cols, int channels, const uint8_t* src, const cvo_nlm_config_t* cfg,
+                    uint8_t* dst);
+/* The middle of fastNlMeansDenoisingColored: plane 0 of a rows x cols x 3 Lab image denoised as a 1-channel image with
+ * cfg->h, planes 1-2 as one 2-channel image with h_color, the same windows, re-interleaved; on the device one upload, one
+ * download, one synchronisation.  BGR <-> Lab stays the caller's (cv::cvtColor with COLOR_LBGR2Lab / COLOR_Lab2LBGR):
+ * OpenCV's 8-bit Lab is table-driven fixed point that differs between versions - the position `gray` takes for BGR -> gray. */
+int cvo_nlm_denoise_lab_host(int rows, int cols, const uint8_t* lab, const cvo_nlm_config_t* cfg, float h_color,
+                             uint8_t* dst);   /* CPU twin, no context */
+int cvo_nlm_denoise_lab(cvo_ctx* ctx, int rows, int cols, const uint8_t* lab, const cvo_nlm_config_t* cfg, float h_color,
+                        uint8_t* dst);
 int cvo_cloud_size(const cvo_cloud* c);
 void cvo_cloud_free(cvo_cloud* c);
 

@@ -116,6 +116,11 @@ int cvo_debug_lidar_stats(cvo_ctx* ctx, unsigned long long* counts /* 9 */, int*
 /* lidar_atan2_deg of cvo_lidar_math.h - the one copy the CPU twin and the kernels compile - on n pairs, on the host:
  * out[i] = atan2(y[i], x[i]) in degrees.  No context. */
 int cvo_debug_lidar_atan2(int n, const double* y, const double* x, double* out);
+/* The context's last cvo_nlm_denoise / cvo_nlm_denoise_lab: whether the kernel ran; mult, shift and the length of the
+ * table's nonzero leading run (of the chroma pass for _lab); the kernel's tile (0 x 0 on the CPU twin); whether every
+ * pass held its whole nonzero run in LDS.  Any pointer may be NULL. */
+int cvo_debug_nlm_stats(cvo_ctx* ctx, int* on_device, int* mult, int* shift, int* n_nonzero, int* tile_w, int* tile_h,
+                        int* table_in_lds);
 
 #ifdef __cplusplus
 }

@@ -239,6 +239,10 @@ class cvo_lidar_rand_t(C.Structure):
     _fields_ = [("r", C.c_uint * 31), ("front", C.c_int), ("rear", C.c_int)]
 
 
+class cvo_nlm_config_t(C.Structure):
+    _fields_ = [("h", C.c_float), ("template_window", C.c_int), ("search_window", C.c_int)]
+
+
 CVO_DEPTH_U16, CVO_DEPTH_F32 = 0, 1
 CVO_SELECT_CV_FAST, CVO_SELECT_DSO_EDGES, CVO_SELECT_FULL = 0, 2, 8
 CVO_FAST_RGBD, CVO_FAST_STEREO, CVO_FAST_STEREO_SEMANTIC = (9, 15000, 12000, 13), (4, 24000, 15000, 50), (4, 28000, 15000, 50)
@@ -263,6 +267,8 @@ EXPORTED = [
     "cvo_cloud_upload_stereo_recipe", "cvo_debug_stereo_stats",
     "cvo_lidar_config_default", "cvo_lidar_config_derive", "cvo_lidar_rand_seed", "cvo_lidar_rand_next", "cvo_lidar_select", "cvo_lidar_select_host",
     "cvo_cloud_upload_lidar", "cvo_debug_lidar_stats", "cvo_debug_lidar_atan2",
+    "cvo_nlm_config_default", "cvo_nlm_weights", "cvo_nlm_denoise_host", "cvo_nlm_denoise", "cvo_nlm_denoise_lab_host",
+    "cvo_nlm_denoise_lab", "cvo_debug_nlm_stats",
 ]
 
 _libs = {}
@@ -380,6 +386,15 @@ def lib(path=None):
     L.cvo_lidar_select.argtypes = [vp, ls, lc, lr, ipp, up, ipp]
     L.cvo_cloud_upload_lidar.argtypes = [vp, ls, lc, lr, C.POINTER(vp), ipp, ipp]
     L.cvo_debug_lidar_stats.argtypes = [vp, C.POINTER(C.c_ulonglong), ipp]
+    nc, bp = C.POINTER(cvo_nlm_config_t), C.POINTER(C.c_ubyte)
+    L.cvo_nlm_config_default.argtypes = [nc]
+    L.cvo_nlm_config_default.restype = None
+    L.cvo_nlm_weights.argtypes = [nc, ip, ipp, ip, ipp, ipp, ipp, ipp]
+    L.cvo_nlm_denoise_host.argtypes = [ip, ip, ip, bp, nc, bp]
+    L.cvo_nlm_denoise.argtypes = [vp, ip, ip, ip, bp, nc, bp]
+    L.cvo_nlm_denoise_lab_host.argtypes = [ip, ip, bp, nc, C.c_float, bp]
+    L.cvo_nlm_denoise_lab.argtypes = [vp, ip, ip, bp, nc, C.c_float, bp]
+    L.cvo_debug_nlm_stats.argtypes = [vp] + [ipp] * 7
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

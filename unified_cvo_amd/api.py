@@ -194,7 +194,7 @@ class CvoPointCloud:
 
 class RGBDFrame:
     """What cvo::ImageRGBD<DepthType> and cvo::Calibration hold of one RGB-D frame (cvo_rgbd_frame_t): `image` (rows, cols)
-    or (rows, cols, 3) uint8 in BGR order, as RawImage holds it AFTER its denoising; `depth` (rows, cols) uint16 or float32;
+    or (rows, cols, 3) uint8 in BGR order, as RawImage holds it AFTER its denoising (CvoGPU.nlm_denoise / nlm_denoise_lab); `depth` (rows, cols) uint16 or float32;
     the intrinsics and the depth scaling factor; optionally the 8-bit `gray` plane the gradient is taken of (overrides the
     BGR -> gray formula) and `semantic` (rows, cols, num_classes) float32."""
 
@@ -259,7 +259,7 @@ FAST_RGBD, FAST_STEREO, FAST_STEREO_SEMANTIC = _capi.CVO_FAST_RGBD, _capi.CVO_FA
 
 class StereoFrame:
     """What cvo::ImageStereo and cvo::Calibration hold of one stereo frame (cvo_stereo_frame_t): the LEFT `image` (rows, cols)
-    or (rows, cols, 3) uint8 in BGR order, after RawImage's denoising; the left `disparity` (rows, cols) float32 in pixels,
+    or (rows, cols, 3) uint8 in BGR order, after RawImage's denoising (CvoGPU.nlm_denoise / nlm_denoise_lab); the left `disparity` (rows, cols) float32 in pixels,
     from the caller's matcher (upstream: libelas, invalid = -10); the intrinsics and the baseline; optionally the 8-bit `gray`
     plane and `semantic` (rows, cols, num_classes) float32, as in RGBDFrame."""
 
@@ -316,6 +316,68 @@ def stereo_points_host(frame, method=CV_FAST):
     if rc != 0:
         _raise(rc, "cvo_stereo_points_host refused the frame or the method")
     return pc
+
+
+def _nlm_config(h, template_window, search_window):
+    return _capi.cvo_nlm_config_t(float(h), int(template_window), int(search_window))
+
+
+def nlm_weights(h=10, template_window=7, search_window=21, channels=1):
+    """cvo_nlm_weights: the weight table of the non-local-means denoising, built where the twin and the device route take it
+    -> dict(weight: all n_table entries, n_nonzero, mult, shift)."""
+    cfg = _nlm_config(h, template_window, search_window)
+    nt, nz, mult, shift = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    call = _capi.lib().cvo_nlm_weights
+    rc = call(C.byref(cfg), int(channels), None, 0, C.byref(nt), C.byref(nz), C.byref(mult), C.byref(shift))
+    if rc != 0:
+        _raise(rc, "cvo_nlm_weights refused the configuration")
+    weight = np.zeros(nt.value, np.int32)
+    rc = call(C.byref(cfg), int(channels), weight.ctypes.data_as(C.POINTER(C.c_int)), nt.value, None, None, None, None)
+    if rc != 0:
+        _raise(rc, "cvo_nlm_weights refused the configuration")
+    return dict(weight=weight, n_nonzero=nz.value, mult=mult.value, shift=shift.value)
+
+
+def _nlm_image(image, channels=None):
+    """An 8-bit image as (rows, cols, channels) contiguous bytes; (rows, cols) is one channel."""
+    image = np.ascontiguousarray(image, np.uint8)
+    if image.ndim == 2:
+        image = image[:, :, None]
+    if image.ndim != 3 or (channels is not None and image.shape[2] != channels):
+        raise ValueError(f"an image of shape {image.shape} is not rows x cols x {channels or 'channels'}")
+    return image
+
+
+def _nlm_denoise(call, image, cfg, out, *extra):
+    """Shared by the four denoising calls -> (rc, denoised image of the input's shape).  out: None, or the array written
+    (the input itself for an in-place call)."""
+    img = _nlm_image(image, 3 if extra else None)
+    rows, cols, ch = img.shape
+    dst = np.zeros_like(img) if out is None else out
+    if dst.dtype != np.uint8 or not dst.flags.c_contiguous or dst.size != img.size:
+        raise ValueError("out must be contiguous bytes of the image's size")
+    bp = C.POINTER(C.c_ubyte)
+    shape = () if extra else (ch,)
+    rc = call(rows, cols, *shape, img.ctypes.data_as(bp), C.byref(cfg), *extra, dst.ctypes.data_as(bp))
+    return rc, dst.reshape(np.shape(image)) if out is None else dst
+
+
+def nlm_denoise_host(image, h=10, template_window=7, search_window=21, out=None):
+    """cvo_nlm_denoise_host: cv::fastNlMeansDenoising of an 8-bit image of 1, 2 or 3 interleaved channels on one CPU thread
+    (RawImage's call: 10, 7, 21).  out=image denoises in place."""
+    rc, dst = _nlm_denoise(_capi.lib().cvo_nlm_denoise_host, image, _nlm_config(h, template_window, search_window), out)
+    if rc != 0:
+        _raise(rc, "cvo_nlm_denoise_host refused the image or the configuration")
+    return dst
+
+
+def nlm_denoise_lab_host(lab, h=10, h_color=10, template_window=7, search_window=21, out=None):
+    """cvo_nlm_denoise_lab_host: the middle of cv::fastNlMeansDenoisingColored on a rows x cols x 3 Lab image - L with h, ab
+    as one 2-channel image with h_color - on one CPU thread."""
+    rc, dst = _nlm_denoise(_capi.lib().cvo_nlm_denoise_lab_host, lab, _nlm_config(h, template_window, search_window), out, float(h_color))
+    if rc != 0:
+        _raise(rc, "cvo_nlm_denoise_lab_host refused the image or the configuration")
+    return dst
 
 
 class LidarScan:
@@ -770,6 +832,28 @@ class CvoGPU:
         names = ("projected", "ground", "valid", "invalid", "segmented", "edges", "draws", "thinned", "edge_detected")
         out = dict(zip(names, (int(v) for v in counts)))
         out["on_device"] = bool(dev.value)
+        return out
+
+    def nlm_denoise(self, image, h=10, template_window=7, search_window=21, out=None):
+        """cvo_nlm_denoise: as nlm_denoise_host, by the context's route (switch NLM_HOST)."""
+        rc, dst = _nlm_denoise(lambda *a: self.L.cvo_nlm_denoise(self.ctx, *a), image, _nlm_config(h, template_window, search_window), out)
+        self._check(rc)
+        return dst
+
+    def nlm_denoise_lab(self, lab, h=10, h_color=10, template_window=7, search_window=21, out=None):
+        """cvo_nlm_denoise_lab: as nlm_denoise_lab_host, by the context's route: one upload, two launches, one download."""
+        rc, dst = _nlm_denoise(lambda *a: self.L.cvo_nlm_denoise_lab(self.ctx, *a), lab, _nlm_config(h, template_window, search_window), out,
+                               float(h_color))
+        self._check(rc)
+        return dst
+
+    def debug_nlm_stats(self):
+        """cvo_debug_nlm_stats of the last nlm_denoise / nlm_denoise_lab."""
+        names = ("on_device", "mult", "shift", "n_nonzero", "tile_w", "tile_h", "table_in_lds")
+        v = [C.c_int() for _ in names]
+        self._check(self.L.cvo_debug_nlm_stats(self.ctx, *[C.byref(x) for x in v]))
+        out = dict(zip(names, (x.value for x in v)))
+        out["on_device"], out["table_in_lds"] = bool(out["on_device"]), bool(out["table_in_lds"])
         return out
 
     def upload_many(self, clouds, threads=None):

@@ -1,5 +1,5 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
 // pair, graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -153,6 +153,11 @@ struct LidarStatsAcc {
   int on_device = 0;
 };
 
+// what cvo_debug_nlm_stats reports of the context's last denoising call (cvo_nlm.hip)
+struct NlmStatsAcc {
+  int on_device = 0, mult = 0, shift = 0, n_nonzero = 0, tile_w = 0, tile_h = 0, table_in_lds = 0;
+};
+
 // offsets of a call's buffers in one device allocation, 256-byte aligned; `off` ends as the bytes to allocate
 struct ScratchLayout {
   size_t off = 0;
@@ -252,6 +257,9 @@ struct cvo_ctx {
   // segmented cloud's arrays, the picks
   DeviceScratch lidar_scratch;
   LidarStatsAcc lidar_last{};
+  // denoising (cvo_nlm.hip): one growable device region - the image, the denoised image, the weight tables
+  DeviceScratch nlm_scratch;
+  NlmStatsAcc nlm_last{};
   double clock_ms_per_tick = 0.0;  // s_memrealtime, calibrated on first use (cvo_debug_kernel_clock)
 };
 

@@ -69,3 +69,4 @@
 #include "cvo_k_fast.h"
 #include "cvo_k_stereo.h"
 #include "cvo_k_lidar.h"
+#include "cvo_k_nlm.h"
