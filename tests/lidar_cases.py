@@ -26,7 +26,7 @@ class Image:
         rings = R if rings is None else rings
         g = np.random.default_rng(seed)
         self.R, self.H, self.rings = R, H, rings
-        step = (ELEV_HI - ELEV_LO) / (R - 1)
+        step = (ELEV_HI - ELEV_LO) / (max(R, 2) - 1)
         self.elev_step = step
         elev = np.radians(ELEV_LO + step * np.arange(rings))[:, None]
         jitter = g.uniform(-0.4, 0.4, (rings, H))
@@ -102,6 +102,12 @@ class Image:
 
     def points(self):
         """-> xyzi (n, 4) float32 in scan order and, per point, its (ring, step)."""
+        if not self.extra and not self.override:  # one return per step at the most: the same points without the loop
+            hit = ~np.isnan(self.t)
+            hit[sorted(self.drop_rings)] = False
+            raw = self.d[hit] * self.t[hit][:, None]
+            xyzi = np.stack([-raw[:, 1], -raw[:, 2], raw[:, 0], self.inten[hit]], -1).astype(np.float32)
+            return xyzi, list(zip(*(a.tolist() for a in np.nonzero(hit))))
         out, where = [], []
         for r in range(self.rings):
             if r in self.drop_rings:
@@ -216,6 +222,8 @@ def _build(name):
         im = Image(seed=10, **SMALL)
         g = np.random.default_rng(10)
         im.inten[g.random(im.inten.shape) < 0.05] = 0.0
+    elif name in EDGE_CASES:
+        im, cfg = _build_edge(name)
     else:
         raise KeyError(name)
     return im, cfg, sem, nc
@@ -233,11 +241,131 @@ CASES = ("room16", "hdl64", "cap", "seam", "size4", "size5_valid", "size5_seed_a
 SMALL_CASES = tuple(c for c in CASES if c not in ("hdl64", "cap"))
 
 
+# ---- Scans drawn for the kernels' structure, not for the algorithm's branches ("structural classes"):
+# the sort sizes of k_lidar_pick, the four words of a component's row mask, the block / wave / lane boundaries of
+# k_lidar_project's ring id, the merge orders of k_lidar_union, the empty results of the device route and the validator's
+# limits.  A result may be empty here, so these are not in CASES.
+
+def config_for(R, H, **kw):
+    """A config for an R x H image of this generator: the angular steps of the image, one beam per row."""
+    f = dict(n_scan=R, horizon_scan=H, ang_res_x=360.0 / H, segment_alpha_x=float(np.radians(360.0 / H)),
+             segment_alpha_y=float(np.radians((ELEV_HI - ELEV_LO) / (max(R, 2) - 1))), beam_num=R, ground_scan_ind=0)
+    f.update(kw)
+    return LidarConfig(**f)
+
+
+WIDE = {"wide700": 700, "wide1200": 1200, "wide2400": 2400, "wide4096": 4096}  # four rings, no ground rows: sixths of H / 6 entries
+SKIP = {"skip%d" % d: d for d in (1, 2, 63, 65, 191, 193, 255)}  # room16 without its first d points: ring k starts at 256 k - d
+LAST_OPENS = 15 * SMALL["H"] + 1  # room16 cut after the first point of ring 15
+LONE_RING = 7  # one_point_ring: the ring that keeps one cell
+
+# tall128's blobs, (row, col) cells with the seed (the lowest row-major cell) first -> (size, valid).  A component's rows are
+# counted without its seed and sit in word row / 32 of the mask: three rows or more make a small component valid.
+TALL_BLOBS = (
+    (((31, 100), (31, 101), (32, 100), (33, 100), (33, 101)), True),     # rows 31 | 32, 33: words 0 and 1
+    (((63, 140), (64, 140), (64, 141), (65, 140), (65, 141)), False),    # the seed alone in row 63: rows 64, 65 count
+    (((63, 180), (63, 181), (64, 180), (65, 180), (65, 181)), True),     # row 63 in word 1, rows 64, 65 in word 2
+    (((95, 60), (95, 61), (96, 60), (97, 60), (97, 61)), True),          # rows 95 | 96, 97: words 2 and 3
+    (tuple((r, c) for r in (126, 127) for c in (20, 21, 22)), False),    # six cells, two rows of word 3
+    (((125, 220), (125, 221), (126, 220), (127, 220), (127, 221)), True),  # three rows of word 3, the image's last row
+)
+SHAPES = {  # name -> (seed cell, size): one valid component each
+    "serpent": ((13, 130), 243),  # two long rows joined at their far end: the trees of both rows merge last
+    "comb": ((12, 130), 304),     # a spine below 61 teeth: every tooth is a tree of its own until the spine's row
+    "loop": ((14, 0), 256),       # a full row: closes through the column seam
+}
+ALONE = {"blob30_alone": [(14, c) for c in range(185, 215)], "blob11_alone": [(14, c) for c in range(185, 196)],
+         "blob5_alone": [(13, 200), (13, 201), (13, 202), (14, 201), (15, 201)]}
+
+EDGE_CASES = (tuple(WIDE) + ("tall128", "tall128_ground") + tuple(SKIP) + ("last_opens", "one_point_ring") + tuple(SHAPES) +
+              ("n1", "n3", "all_near") + tuple(ALONE) + ("R1", "w255", "w257", "max"))
+
+
+def _keep_ring_ends(im, rows, H):
+    """Carve whole rows but for a ring's first and last step (columns H / 2 and H / 2 - 1): the 4 -> 1 transitions stay, and
+    with them the ring id of every later point."""
+    im.carve(rows, [c for c in range(H) if c not in (H // 2 - 1, H // 2)])
+
+
+def _build_edge(name):
+    """-> (Image, config)"""
+    R, H = SMALL["R"], SMALL["H"]
+    cfg = small_config()
+    if name in WIDE:
+        im = Image(4, WIDE[name], seed=2, half=(20.0, 15.0))
+        cfg = config_for(4, WIDE[name], ground_scan_ind=0)
+        if name == "wide4096":  # at 100 m adjacent columns of a 4096-wide image are connected, at _pilasters' 40 m they are not
+            for s in range(4096):
+                im.t[3, s] = 100.0 + 0.07 * ((s // 12) % 2)
+    elif name in ("tall128", "tall128_ground"):
+        im = Image(128, H, seed=4)
+        cfg = config_for(128, H, ground_scan_ind=20 if name == "tall128" else 127)
+        for cells, _ in TALL_BLOBS:
+            rows, cols = [r for r, _ in cells], [c for _, c in cells]
+            im.carve(range(max(min(rows) - 2, 0), min(max(rows) + 3, 128)), range(min(cols) - 3, max(cols) + 4))
+        for cells, _ in TALL_BLOBS:
+            im.put(cells, 6.0)
+    elif name in SKIP or name in ("last_opens", "n1", "n3", "all_near"):
+        im = Image(seed=1, **SMALL)  # room16; case() cuts or scales its points
+    elif name == "one_point_ring":
+        # Two transitions cannot be adjacent (a point is not in quadrants 4 and 1), so a ring between two others has at least
+        # two points, its first and its last step; the last one here is under sensor_min_range: the ring holds one cell.
+        # (A ring of one point by its id is the first of skip255 and the last of last_opens.)
+        im = Image(seed=1, **SMALL)
+        for s in range(1, H - 1):
+            im.t[LONE_RING, s] = np.nan
+        im.t[LONE_RING, H - 1] = 0.5
+    elif name in SHAPES:
+        im = Image(seed=3, **SMALL)
+        _keep_ring_ends(im, range(11 if name == "comb" else 12, 16), H)
+        if name == "serpent":
+            im.put([(r, c) for r in (13, 15) for c in range(130, 251)] + [(14, 250)], 6.0)
+        elif name == "comb":
+            cfg = small_config(ground_scan_ind=8)
+            im.put([(15, c) for c in range(130, 251)] + [(r, c) for r in (12, 13, 14) for c in range(130, 251, 2)], 6.0)
+        else:
+            im.put([(14, c) for c in range(H)], 6.0)
+    elif name in ALONE:
+        # nothing but the blob holds a cell: every ring keeps its first and last step for the ring ids, under sensor_min_range
+        im = Image(seed=3, **SMALL)
+        im.t[:, :] = np.nan
+        im.t[:, 0] = im.t[:, H - 1] = 0.5
+        im.put(ALONE[name], 6.0)
+    elif name == "R1":
+        im = Image(1, H, seed=12)
+        cfg = config_for(1, H, ground_scan_ind=0)
+    elif name in ("w255", "w257"):
+        W = int(name[1:])
+        im = Image(R, W, seed=13)
+        cfg = config_for(R, W, ground_scan_ind=12)
+    elif name == "max":  # the largest image the validator admits
+        im = Image(128, 4096, seed=8, half=(20.0, 15.0))
+        cfg = config_for(128, 4096, ground_scan_ind=100)
+    else:
+        raise KeyError(name)
+    return im, cfg
+
+
+def _cut(name, xyzi):
+    """The edge cases that edit the point list rather than the image."""
+    if name in SKIP:
+        return xyzi[SKIP[name]:]
+    if name == "last_opens":
+        return xyzi[:LAST_OPENS]
+    if name in ("n1", "n3"):
+        return xyzi[:int(name[1:])]
+    if name == "all_near":  # every point under sensor_min_range; the intensities stay
+        return xyzi * np.array([0.01, 0.01, 0.01, 1.0], np.float32)
+    return xyzi
+
+
 @functools.lru_cache(maxsize=None)
 def case(name):
     """-> (LidarScan, LidarConfig)"""
     im, cfg, sem, nc = _build(name)
     xyzi, where = im.points()
+    if name in EDGE_CASES:
+        xyzi = _cut(name, xyzi)
     if name == "semantic":
         g = np.random.default_rng(11)
         sem = g.integers(0, nc, len(xyzi)).astype(np.int32)
@@ -267,3 +395,15 @@ def component_of(st, cfg, row, col):
         if cell in c["cells"]:
             return c
     return None
+
+
+COUNTS = ("projected", "ground", "valid", "invalid", "segmented", "edges", "draws", "thinned", "edge_detected")  # debug_lidar_stats and the statement
+
+
+def same_resident(gpu, d, want_cloud):
+    """The resident cloud `d` orders as an ordinary upload of `want_cloud` does."""
+    u = gpu.upload(want_cloud)
+    try:
+        assert d.n == u.n and np.array_equal(d.debug_order(), u.debug_order())
+    finally:
+        u.free()

@@ -13,7 +13,8 @@ from unified_cvo_amd import CvoGPU, CvoPointCloud, CvoError, LidarRand, LidarSca
 pytestmark = pytest.mark.gpu
 
 HOST_BELOW = 12000  # scans with fewer points take the CPU twin unless LIDAR_HOST says otherwise
-COUNTS = ("projected", "ground", "valid", "invalid", "segmented", "edges", "draws", "thinned", "edge_detected")
+COUNTS = lc.COUNTS
+_same_resident = lc.same_resident
 
 
 @pytest.fixture(scope="module")
@@ -21,14 +22,6 @@ def gpu():
     g = CvoGPU(params=cases.load_params("geometric_gpu"))
     yield g
     g.close()
-
-
-def _same_resident(gpu, d, want_cloud):
-    u = gpu.upload(want_cloud)
-    try:
-        assert d.n == u.n and np.array_equal(d.debug_order(), u.debug_order())
-    finally:
-        u.free()
 
 
 @pytest.mark.parametrize("name", lc.CASES)

@@ -72,6 +72,114 @@ def test_the_cases_reach_their_branches():
     assert np.all(chosen != 0)
 
 
+@pytest.mark.parametrize("name", lc.EDGE_CASES)
+def test_twin_equals_the_statement_at_the_edges(name):
+    """The structural cases (lc.EDGE_CASES): indices, is_edge and draws, all exact; a result may be empty here."""
+    scan, cfg = lc.case(name)
+    want = lc.statement(name)
+    rand = LidarRand(1)
+    start = _copy(rand)
+    index, is_edge = lidar_select_host(scan, cfg, rand)
+    assert index.dtype == want["index"].dtype and np.array_equal(index, want["index"]) and np.array_equal(is_edge, want["is_edge"]), name
+    for _ in range(want["draws"]):
+        start.next()
+    assert start.state() == rand.state(), name
+
+
+def _np2(length):
+    n = 64
+    while n < length:
+        n *= 2
+    return n
+
+
+def _transitions(st):
+    return np.nonzero(np.diff(st["ring"]))[0] + 1
+
+
+# which of these counts are zero in the empty and tiny cases; every other one of the four is positive
+ZERO = {"n1": ("segmented", "draws", "edges"), "n3": ("segmented", "draws", "edges"), "all_near": ("projected", "segmented", "draws", "edges"),
+        "blob30_alone": ("edges",), "blob11_alone": ("segmented", "draws", "edges"), "blob5_alone": ("draws", "edges"), "R1": ("edges",),
+        "w255": (), "w257": ()}
+
+
+def test_the_edge_cases_reach_their_edges():
+    """Statement-side: every structural class the edge cases were drawn for is there, so that a case that stops reaching its
+    edge fails here and does not pass vacuously on the device."""
+    # k_lidar_pick's sort: the power of two at or above a sixth's entries, 64 at the least; 1024 is the class whose
+    # compare-exchange loop makes a second trip
+    classes = {name: {_np2(ep - sp) for _, _, sp, ep in lc.statement(name)["sixths"]} for name in lc.WIDE}
+    assert classes == {"wide700": {64, 128}, "wide1200": {128, 256}, "wide2400": {256, 512}, "wide4096": {1024}}, classes
+    lens = {name: sorted(ep - sp for _, _, sp, ep in lc.statement(name)["sixths"]) for name in lc.WIDE}
+    assert (lens["wide700"][0], lens["wide700"][-1]) == (60, 114) and (lens["wide1200"][0], lens["wide1200"][-1]) == (101, 198)
+    assert 1024 not in {_np2(ep - sp) for name in lc.CASES for _, _, sp, ep in lc.statement(name)["sixths"]}  # (the sixteen stop at 512)
+    wide, cfg = lc.statement("wide4096"), lc.case("wide4096")[1]
+    thr = np.float32(cfg.edge_threshold)
+    above = [int(np.count_nonzero(wide["curvature"][sp:ep + 1] > thr)) for i, _, sp, ep in wide["sixths"] if i == 3]
+    assert [ep - sp for i, _, sp, ep in wide["sixths"] if i == 3] == [680] * 6 and min(above) >= 113 and max(above) <= 115, above
+    # every sixth of the case is above 512 entries, six of them stop at the cap: the order of the sort's top decides the output
+    assert min(lens["wide4096"]) > 512 and wide["capped"] == 6 and wide["edges"] == 153
+    # the row mask: four words of 32 rows; a small component's validity is its row count, the seed's row left out
+    tall, cfg = lc.statement("tall128"), lc.case("tall128")[1]
+    assert cfg.n_scan == 128 and cfg.ground_scan_ind == 20
+    words = set()
+    for cells, valid in lc.TALL_BLOBS:
+        c = lc.component_of(tall, cfg, *cells[0])
+        want = sorted(r * cfg.horizon_scan + col for r, col in cells)
+        assert c is not None and sorted(c["cells"]) == want and c["valid"] == valid and c["seed"] == want[0] == c["cells"][0], cells
+        rows = {cell // cfg.horizon_scan for cell in c["cells"][1:]}
+        assert (len(rows) >= 3) == valid and len(cells) in (5, 6)
+        words.add(tuple(sorted({r // 32 for r in rows})))
+    assert words == {(0, 1), (2,), (1, 2), (2, 3), (3,)}  # every word, and a small component across each word boundary
+    ground, cfg = lc.statement("tall128_ground"), lc.case("tall128_ground")[1]
+    assert cfg.ground_scan_ind == cfg.n_scan - 1 == 127 and ground["ground"] > tall["ground"] and ground["segmented"] > 0
+    assert ground["ground_cells"][22 * cfg.horizon_scan:].any() and not tall["ground_cells"][22 * cfg.horizon_scan:].any()
+    # the ring id: block offset + wave counts + inclusive lane count, in blocks of 1024 and waves of 64
+    res = {name: {int(t) % 1024 for t in _transitions(lc.statement(name))} for name in lc.SKIP}
+    assert 1023 in res["skip1"] and 1022 in res["skip2"] and 63 in res["skip193"] and 65 in res["skip191"] and 1 in res["skip255"]
+    assert {r % 64 for r in res["skip65"]} == {63} and {r % 64 for r in res["skip193"]} == {63} and {r % 64 for r in res["skip63"]} == {1}
+    assert {r % 8 for name in lc.CASES if name != "extra_rings" for r in _transitions(lc.statement(name))[:3]} == {0}  # (the sixteen: lanes 0, 8, 16 ...)
+    first = lc.statement("skip255")
+    assert _transitions(first)[0] == 1 and 1025 in _transitions(first) and np.count_nonzero(first["ring"] == 0) == 1  # a ring of one point
+    for name in lc.SKIP:
+        assert lc.case(name)[0].n == 4096 - lc.SKIP[name] and lc.statement(name)["ring"].max() == 15, name
+    last, scan = lc.statement("last_opens"), lc.case("last_opens")[0]
+    assert _transitions(last)[-1] == scan.n - 1 and np.count_nonzero(last["ring"] == 15) == 1 and last["win"][15 * lc.SMALL["H"]:].max() == scan.n - 1
+    lone, H = lc.statement("one_point_ring"), lc.SMALL["H"]
+    assert np.count_nonzero(lone["ring"] == lc.LONE_RING) == 2 and np.count_nonzero(lone["win"][lc.LONE_RING * H:(lc.LONE_RING + 1) * H] >= 0) == 1
+    assert lone["ring"].max() == 15 and np.count_nonzero(lone["ring"] == lc.LONE_RING + 1) == H
+    # shapes that make k_lidar_union merge many trees late
+    for name, (seed, size) in lc.SHAPES.items():
+        st, cfg = lc.statement(name), lc.case(name)[1]
+        c = lc.component_of(st, cfg, *seed)
+        assert c is not None and len(c["cells"]) == size and c["valid"] and c["seed"] == seed[0] * H + seed[1], name
+    loop = lc.component_of(lc.statement("loop"), lc.case("loop")[1], 14, 0)
+    assert sorted(loop["cells"]) == list(range(14 * H, 15 * H))  # closed through the seam
+    assert lc.case("comb")[1].ground_scan_ind == 8
+    # empty and tiny results
+    for name, zero in ZERO.items():
+        st = lc.statement(name)
+        assert all((st[k] == 0) == (k in zero) for k in ("projected", "segmented", "draws", "edges")), (name, {k: st[k] for k in zero})
+    assert [lc.case(name)[0].n for name in ("n1", "n3")] == [1, 3] and all(len(lc.statement(name)["index"]) == 0 for name in ("n1", "n3"))
+    assert [name for name in lc.EDGE_CASES if len(lc.statement(name)["index"]) == 0] == ["n1", "n3"]  # (edge_detection picks elsewhere)
+    near = lc.statement("all_near")
+    assert near["edge_detected"] == 1097 == len(near["index"])
+    alone = lc.statement("blob30_alone")
+    assert (alone["segmented"], alone["draws"], alone["valid"], alone["invalid"]) == (30, 20, 1, 0) and set(np.array(alone["seg_cell"]) // H) == {14}
+    b11 = lc.statement("blob11_alone")
+    assert (b11["projected"], b11["valid"], b11["invalid"]) == (11, 0, 1)
+    assert 0 < lc.statement("blob5_alone")["segmented"] < 11  # no position has a curvature
+    r1, cfg = lc.statement("R1"), lc.case("R1")[1]
+    assert cfg.n_scan == 1 and cfg.ground_scan_ind == 0 and lc.case("R1")[0].n == 256 and r1["ring"].max() == 0 and r1["segmented"] > 10
+    assert [lc.case(name)[1].horizon_scan for name in ("w255", "w257")] == [255, 257]
+    # the largest image the validator admits
+    scan, cfg = lc.case("max")
+    big = lc.statement("max")
+    assert (cfg.n_scan, cfg.horizon_scan, cfg.ground_scan_ind) == (128, 4096, 100) and scan.n == big["projected"] == 128 * 4096
+    assert big["segmented"] > 100000 and 1024 in {_np2(ep - sp) for _, _, sp, ep in big["sixths"]}
+    assert all(lc.case(name)[0].n <= 33000 for name in lc.EDGE_CASES if name != "max")
+
+
 def test_shared_atan2_against_numpy():
     """lidar_atan2_deg of cvo_lidar_math.h - the copy the twin and the kernels compile, through cvo_debug_lidar_atan2 - on a
     dense grid that includes the axes and on 200 000 points of the unit circle: within 1e-6 degrees of numpy's arctan2, and
