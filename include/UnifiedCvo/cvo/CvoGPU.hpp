@@ -133,6 +133,11 @@ class CvoGPU {
   // include/cvo_hip.h): cv::fastNlMeansDenoising of an 8-bit image of 1 .. 3 interleaved channels, and the middle of
   // cv::fastNlMeansDenoisingColored on a Lab image (BGR <-> Lab stays the caller's).  dst may be src.  Refusals throw
   // std::invalid_argument.  Defined in host/cvo_nlm.cpp.
+  // New: the library's own stereo matcher on the device (cvo_stereo_disparity, include/cvo_hip.h): the float left disparity
+  // of a rectified pair of rows x cols gray planes, invalid = -10, by semi-global matching over a census cost - NOT upstream's
+  // libelas.  config == nullptr: cvo_sgm_config_default.  Refusals throw std::invalid_argument.  Defined in host/cvo_sgm.cpp.
+  std::vector<float> stereo_disparity(int rows, int cols, const unsigned char* left, const unsigned char* right,
+                                      const cvo_sgm_config_t* config = nullptr) const;
   void nlm_denoise(int rows, int cols, int channels, const unsigned char* src, unsigned char* dst, float h = 10.f, int template_window = 7,
                    int search_window = 21) const;
   void nlm_denoise_lab(int rows, int cols, const unsigned char* lab, unsigned char* dst, float h = 10.f, float h_color = 10.f,

@@ -1,18 +1,30 @@
 // cvo::ImageStereo (upstream utils/ImageStereo.hpp): the left RawImage with its left disparity map, in pixels.
 // Raw buffers in place of cv::Mat; no denoising inside the class: CvoGPU::nlm_denoise(_lab) first (see RawImage.hpp).
 //
-// NOT here: upstream's ImageStereo(left, right) constructor computes the disparity with libelas
-// (StaticStereo::disparity, StaticStereo.cpp:20-64).  libelas is not part of this library: the caller runs its own matcher
-// and hands the RESULT to this class (libelas codes invalid pixels as -10; every disparity below 0.05 is rejected).
+// Upstream's ImageStereo(left, right) constructor computes the disparity with libelas (StaticStereo::disparity,
+// StaticStereo.cpp:20-64).  libelas is not part of this library.  The (left, right, ...) constructor below computes it with
+// the library's OWN matcher (cvo_stereo_disparity, include/cvo_hip.h: semi-global matching over a census cost, stated in
+// tests/np_sgm.py) - another algorithm, so its map, and the poses that follow from it, differ from upstream's.  A caller who
+// wants libelas's (or any other matcher's) map runs that matcher and hands the RESULT to the other constructors (invalid
+// pixels are coded -10 by both; every disparity below 0.05 is rejected).
 #pragma once
 #include <vector>
 
+#include "cvo_hip.h"
 #include "utils/RawImage.hpp"
 
 namespace cvo {
 
+class CvoGPU;
+
 class ImageStereo : public RawImage {
  public:
+  // New: upstream's missing constructor over raw buffers.  left / right: rows x cols x channels bytes (1 channel, or BGR, which
+  // goes to gray by RawImage's formula); the disparity is cvo_stereo_disparity's on gpu's context (CvoGPU::stereo_disparity),
+  // or - gpu == nullptr - the CPU twin's (cvo_stereo_disparity_host, one thread).  config == nullptr: cvo_sgm_config_default.
+  // Refusals throw std::invalid_argument.  Defined in host/cvo_sgm.cpp.
+  ImageStereo(const uint8_t* left_image, const uint8_t* right_image, int rows, int cols, int channels, const CvoGPU* gpu = nullptr,
+              const cvo_sgm_config_t* config = nullptr);
   ImageStereo(const uint8_t* left_image, int rows, int cols, int channels, const std::vector<float>& left_disparity)
       : RawImage(left_image, rows, cols, channels), disparity_(left_disparity) {
     check();

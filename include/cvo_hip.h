@@ -282,7 +282,8 @@ int cvo_fast_select_host(int rows, int cols, const uint8_t* gray, const cvo_fast
                          int* threshold_used);   /* CPU twin, no context */
 /* ---- stereo front end: replaces CvoPointCloud(ImageStereo, Calibration, PointSelectionMethod) (CvoPointCloud.cpp:680-773,
  * StaticStereo.cpp:84-107, is_good_point :39-49) FROM A GIVEN DISPARITY MAP (upstream computes it with libelas, which is not
- * part of this library; its invalid marker -10 is rejected like every disparity below 0.05) and the per-frame block of the
+ * part of this library - cvo_stereo_disparity below is the library's own matcher, another algorithm; the invalid marker -10 of
+ * both is rejected like every disparity below 0.05) and the per-frame block of the
  * multi-frame KITTI driver (main_multi_frame_irls_kitti.cpp:235-292) ----
  * image / gray / semantic: as in cvo_rgbd_frame_t (the LEFT image, after RawImage's denoising: cvo_nlm_denoise). */
 typedef struct cvo_stereo_frame_t {
@@ -418,6 +419,44 @@ int cvo_nlm_denoise_lab_host(int rows, int cols, const uint8_t* lab, const cvo_n
                              uint8_t* dst);   /* CPU twin, no context */
 int cvo_nlm_denoise_lab(cvo_ctx* ctx, int rows, int cols, const uint8_t* lab, const cvo_nlm_config_t* cfg, float h_color,
                         uint8_t* dst);
+/* ---- stereo matcher: what cvo::ImageStereo(left, right) needs a disparity from.  NOT upstream's matcher: upstream computes
+ * the left disparity with libelas (StaticStereo::disparity), whose support-point triangulation and filters are not restated;
+ * this is the library's own semi-global matching over a census cost, so poses from its map differ from poses from libelas's,
+ * and parity with any other SGM implementation is unpinned.  The statement is tests/np_sgm.py; the CPU twin and the kernels of
+ * cvo_k_sgm.h equal it exactly.  left / right: rectified 8-bit gray planes of rows x cols.
+ * Census: 9 wide x 7 high, coordinates clamped to the image, bit = neighbour < centre for the 62 neighbours in row-major window
+ * order, first neighbour most significant.  Cost: C(v, u, d) = popcount(cL[v, u] ^ cR[v, u - d]) for u - d >= 0, else 62, for d
+ * in [0, max_disparity).  Paths (dv, du) in the order (0,1) (0,-1) (1,0) (-1,0) (1,1) (1,-1) (-1,1) (-1,-1), the first `paths`
+ * of them: with q = p - r inside the image and m = min_k L(q, k), L(p, d) = C(p, d) + min(L(q, d), L(q, d - 1) + p1,
+ * L(q, d + 1) + p1, m + p2) - m (terms outside [0, max_disparity) left out), else L(p, d) = C(p, d); S = sum of the L (a
+ * byte each, 16 bits the sum).  Winner d* = first argmin S, s1 its sum, s2 = min S over |d - d*| > 1; invalid when
+ * s2 (100 - uniqueness) < 100 s1.  Sub-pixel for 0 < d* < max_disparity - 1 and den = S(d* - 1) + S(d* + 1) - 2 s1 > 0:
+ * (float)d* + (float)(S(d* - 1) - S(d* + 1)) / (float)(2 den), else (float)d*.  Left-right check (lr_max_diff >= 0): dR(v, x) =
+ * first argmin_d S(v, x + d, d) over x + d < cols; invalid when u - d* < 0 or |dR(v, u - d*) - d*| > lr_max_diff.  Invalid
+ * pixels are written as -10.f, the marker cvo_stereo_points rejects.  No speckle filter, median filter or hole filling.
+ * CVO_E_INVALID, nothing written: a missing pointer, rows / cols < 1, max_disparity not 64 / 128 / 256, not 0 <= p1 <= p2 <= 193,
+ * uniqueness outside 0 .. 99, paths not 4 or 8.  CVO_E_UNSUPPORTED: more than 2^24 pixels, rows x cols x max_disparity x 2 bytes
+ * of sums above 2 GiB.  cols < max_disparity and 1 x 1 frames are valid.  cvo_stereo_disparity runs on the context's upload
+ * stream like the front ends.  Switch SGM_HOST=1 / 0: the CPU twin (one thread) / the kernels for every size (unset: frames
+ * under 128 pixels take the CPU twin: measured, profiles/sgm/crossover.txt). */
+typedef struct cvo_sgm_config_t {
+  int max_disparity;           /* 64, 128 or 256 */
+  int p1, p2;                  /* 0 <= p1 <= p2 <= 193 */
+  int uniqueness;              /* percent, 0 .. 99 */
+  int lr_max_diff;             /* < 0: no left-right check */
+  int paths;                   /* 4 or 8 */
+} cvo_sgm_config_t;
+void cvo_sgm_config_default(cvo_sgm_config_t* cfg);   /* 128, 10, 120, 5, 1, 8 */
+int cvo_stereo_disparity_host(int rows, int cols, const uint8_t* left, const uint8_t* right, const cvo_sgm_config_t* cfg,
+                              float* disparity);   /* CPU twin, no context */
+int cvo_stereo_disparity(cvo_ctx* ctx, int rows, int cols, const uint8_t* left, const uint8_t* right, const cvo_sgm_config_t* cfg,
+                         float* disparity);
+/* "Two images in, cloud out": cvo_stereo_disparity of (the frame's gray plane - frame->gray, a 1-channel image, or the BGR
+ * image through the front end's own gray formula -, right_gray), downloaded, then cvo_cloud_upload_stereo exactly as it is
+ * on a copy of the frame that carries the map.  frame->disparity is not read and may be NULL.  Refusals: the matcher's, then
+ * cvo_cloud_upload_stereo's. */
+int cvo_cloud_upload_stereo_pair(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, const uint8_t* right_gray, const cvo_sgm_config_t* cfg,
+                                 int method, cvo_cloud** out, int* pixel, int* n);
 int cvo_cloud_size(const cvo_cloud* c);
 void cvo_cloud_free(cvo_cloud* c);
 

@@ -121,6 +121,15 @@ int cvo_debug_lidar_atan2(int n, const double* y, const double* x, double* out);
  * pass held its whole nonzero run in LDS.  Any pointer may be NULL. */
 int cvo_debug_nlm_stats(cvo_ctx* ctx, int* on_device, int* mult, int* shift, int* n_nonzero, int* tile_w, int* tile_h,
                         int* table_in_lds);
+/* The context's last cvo_stereo_disparity (cvo_cloud_upload_stereo_pair's included): whether the kernels ran; max_disparity and
+ * paths; the lines launched per direction (8 ints, 0 for a direction not run and on the CPU twin); the frame's shape; the
+ * census kernel's tile (0 x 0 on the CPU twin).  Any pointer may be NULL. */
+int cvo_debug_sgm_stats(cvo_ctx* ctx, int* on_device, int* max_disparity, int* paths, int* lines /* 8 */, int* rows, int* cols,
+                        int* tile_w, int* tile_h);
+/* What that call left in the context's region, if it ran on the device (CVO_E_INVALID otherwise): the census planes (rows x
+ * cols 64-bit words each) and S (rows x cols x max_disparity 16-bit sums).  Any pointer may be NULL.  Tests use it to find
+ * the first stage that differs from the statement without running anything again. */
+int cvo_debug_sgm_readback(cvo_ctx* ctx, unsigned long long* census_left, unsigned long long* census_right, unsigned short* S);
 
 #ifdef __cplusplus
 }

@@ -243,6 +243,10 @@ class cvo_nlm_config_t(C.Structure):
     _fields_ = [("h", C.c_float), ("template_window", C.c_int), ("search_window", C.c_int)]
 
 
+class cvo_sgm_config_t(C.Structure):
+    _fields_ = [("max_disparity", C.c_int), ("p1", C.c_int), ("p2", C.c_int), ("uniqueness", C.c_int), ("lr_max_diff", C.c_int), ("paths", C.c_int)]
+
+
 CVO_DEPTH_U16, CVO_DEPTH_F32 = 0, 1
 CVO_SELECT_CV_FAST, CVO_SELECT_DSO_EDGES, CVO_SELECT_FULL = 0, 2, 8
 CVO_FAST_RGBD, CVO_FAST_STEREO, CVO_FAST_STEREO_SEMANTIC = (9, 15000, 12000, 13), (4, 24000, 15000, 50), (4, 28000, 15000, 50)
@@ -269,6 +273,8 @@ EXPORTED = [
     "cvo_cloud_upload_lidar", "cvo_debug_lidar_stats", "cvo_debug_lidar_atan2",
     "cvo_nlm_config_default", "cvo_nlm_weights", "cvo_nlm_denoise_host", "cvo_nlm_denoise", "cvo_nlm_denoise_lab_host",
     "cvo_nlm_denoise_lab", "cvo_debug_nlm_stats",
+    "cvo_sgm_config_default", "cvo_stereo_disparity_host", "cvo_stereo_disparity", "cvo_cloud_upload_stereo_pair", "cvo_debug_sgm_stats",
+    "cvo_debug_sgm_readback",
 ]
 
 _libs = {}
@@ -395,6 +401,14 @@ def lib(path=None):
     L.cvo_nlm_denoise_lab_host.argtypes = [ip, ip, bp, nc, C.c_float, bp]
     L.cvo_nlm_denoise_lab.argtypes = [vp, ip, ip, bp, nc, C.c_float, bp]
     L.cvo_debug_nlm_stats.argtypes = [vp] + [ipp] * 7
+    sc, fp = C.POINTER(cvo_sgm_config_t), C.POINTER(C.c_float)
+    L.cvo_sgm_config_default.argtypes = [sc]
+    L.cvo_sgm_config_default.restype = None
+    L.cvo_stereo_disparity_host.argtypes = [ip, ip, bp, bp, sc, fp]
+    L.cvo_stereo_disparity.argtypes = [vp, ip, ip, bp, bp, sc, fp]
+    L.cvo_cloud_upload_stereo_pair.argtypes = [vp, C.POINTER(cvo_stereo_frame_t), bp, sc, ip, C.POINTER(vp), ipp, ipp]
+    L.cvo_debug_sgm_stats.argtypes = [vp] + [ipp] * 8
+    L.cvo_debug_sgm_readback.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ushort)]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

@@ -260,7 +260,8 @@ FAST_RGBD, FAST_STEREO, FAST_STEREO_SEMANTIC = _capi.CVO_FAST_RGBD, _capi.CVO_FA
 class StereoFrame:
     """What cvo::ImageStereo and cvo::Calibration hold of one stereo frame (cvo_stereo_frame_t): the LEFT `image` (rows, cols)
     or (rows, cols, 3) uint8 in BGR order, after RawImage's denoising (CvoGPU.nlm_denoise / nlm_denoise_lab); the left `disparity` (rows, cols) float32 in pixels,
-    from the caller's matcher (upstream: libelas, invalid = -10); the intrinsics and the baseline; optionally the 8-bit `gray`
+    from the caller's matcher (upstream: libelas, invalid = -10) or from CvoGPU.stereo_disparity - the library's own matcher, another
+    algorithm than libelas -; the intrinsics and the baseline; optionally the 8-bit `gray`
     plane and `semantic` (rows, cols, num_classes) float32, as in RGBDFrame."""
 
     def __init__(self, image, disparity, fx, fy, cx, cy, baseline, gray=None, semantic=None):
@@ -269,8 +270,8 @@ class StereoFrame:
             self.image = np.ascontiguousarray(self.image[..., 0])
         self.rows, self.cols = self.image.shape[:2]
         self.channels = 1 if self.image.ndim == 2 else self.image.shape[2]
-        self.disparity = np.ascontiguousarray(disparity, np.float32)
-        if self.disparity.shape != (self.rows, self.cols):
+        self.disparity = None if disparity is None else np.ascontiguousarray(disparity, np.float32)  # (None: for CvoGPU.upload_stereo_pair only)
+        if self.disparity is not None and self.disparity.shape != (self.rows, self.cols):
             raise ValueError(f"disparity is {self.disparity.shape}, the image {self.rows} x {self.cols}")
         self.fx, self.fy, self.cx, self.cy, self.baseline = (float(v) for v in (fx, fy, cx, cy, baseline))
         self.gray = None if gray is None else np.ascontiguousarray(gray, np.uint8).reshape(self.rows, self.cols)
@@ -316,6 +317,40 @@ def stereo_points_host(frame, method=CV_FAST):
     if rc != 0:
         _raise(rc, "cvo_stereo_points_host refused the frame or the method")
     return pc
+
+
+class SGMConfig:
+    """cvo_sgm_config_t: the stereo matcher's configuration (semi-global matching over a census cost; tests/np_sgm.py states it).
+    max_disparity 64 / 128 / 256, 0 <= p1 <= p2 <= 193, uniqueness 0 .. 99 percent, lr_max_diff < 0 turns the left-right check
+    off, paths 4 or 8."""
+
+    def __init__(self, max_disparity=128, p1=10, p2=120, uniqueness=5, lr_max_diff=1, paths=8):
+        self.max_disparity, self.p1, self.p2 = int(max_disparity), int(p1), int(p2)
+        self.uniqueness, self.lr_max_diff, self.paths = int(uniqueness), int(lr_max_diff), int(paths)
+
+    def c_struct(self):
+        return _capi.cvo_sgm_config_t(self.max_disparity, self.p1, self.p2, self.uniqueness, self.lr_max_diff, self.paths)
+
+
+def _stereo_disparity(call, left, right, config):
+    """Shared by CvoGPU.stereo_disparity and stereo_disparity_host -> (rc, disparity (rows, cols) float32)."""
+    left, right = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
+    if left.ndim != 2 or left.shape != right.shape:
+        raise ValueError(f"left {left.shape} and right {right.shape} must be gray planes of one shape")
+    cfg = (config or SGMConfig()).c_struct()
+    out = np.zeros(left.shape, np.float32)
+    bp = C.POINTER(C.c_ubyte)
+    rc = call(left.shape[0], left.shape[1], left.ctypes.data_as(bp), right.ctypes.data_as(bp), C.byref(cfg), out.ctypes.data_as(C.POINTER(C.c_float)))
+    return rc, out
+
+
+def stereo_disparity_host(left, right, config=None):
+    """cvo_stereo_disparity_host: the left disparity of a rectified pair of 8-bit gray planes on one CPU thread, float32,
+    invalid = -10.  The library's own matcher, not libelas."""
+    rc, out = _stereo_disparity(_capi.lib().cvo_stereo_disparity_host, left, right, config)
+    if rc != 0:
+        _raise(rc, "cvo_stereo_disparity_host refused the planes or the configuration")
+    return out
 
 
 def _nlm_config(h, template_window, search_window):
@@ -783,6 +818,45 @@ class CvoGPU:
         n, h, fs = C.c_int(), C.c_void_p(), frame.c_struct()
         self._check(self.L.cvo_cloud_upload_stereo(self.ctx, C.byref(fs), int(method), C.byref(h), pixel.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n)))
         return self._resident(h, n.value, pixel)
+
+    def stereo_disparity(self, left, right, config=None):
+        """cvo_stereo_disparity: as stereo_disparity_host, by the context's route (switch SGM_HOST)."""
+        rc, out = _stereo_disparity(lambda *a: self.L.cvo_stereo_disparity(self.ctx, *a), left, right, config)
+        self._check(rc)
+        return out
+
+    def upload_stereo_pair(self, frame, right_gray, config=None, method=CV_FAST):
+        """cvo_cloud_upload_stereo_pair: stereo_disparity of (the frame's gray plane, right_gray), then upload_stereo with that
+        map; frame.disparity may be None and is not read."""
+        right = np.ascontiguousarray(right_gray, np.uint8)
+        if right.shape != (frame.rows, frame.cols):
+            raise ValueError(f"right_gray is {right.shape}, the frame {frame.rows} x {frame.cols}")
+        pixel = np.zeros(max(frame.rows * frame.cols, 1), np.int32)
+        n, h, fs, cfg = C.c_int(), C.c_void_p(), frame.c_struct(), (config or SGMConfig()).c_struct()
+        self._check(self.L.cvo_cloud_upload_stereo_pair(self.ctx, C.byref(fs), right.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(cfg), int(method),
+                                                        C.byref(h), pixel.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n)))
+        return self._resident(h, n.value, pixel)
+
+    def debug_sgm_stats(self):
+        """cvo_debug_sgm_stats of the last stereo_disparity / upload_stereo_pair."""
+        names = ("on_device", "max_disparity", "paths", "rows", "cols", "tile_w", "tile_h")
+        v = {k: C.c_int() for k in names}
+        lines = (C.c_int * 8)()
+        self._check(self.L.cvo_debug_sgm_stats(self.ctx, C.byref(v["on_device"]), C.byref(v["max_disparity"]), C.byref(v["paths"]), lines,
+                                               C.byref(v["rows"]), C.byref(v["cols"]), C.byref(v["tile_w"]), C.byref(v["tile_h"])))
+        out = {k: x.value for k, x in v.items()}
+        out["on_device"], out["lines"] = bool(out["on_device"]), list(lines)
+        return out
+
+    def debug_sgm_readback(self):
+        """cvo_debug_sgm_readback: the census planes and S of the last stereo_disparity that ran on the device ->
+        dict(census_left, census_right (rows, cols) uint64, S (rows, cols, max_disparity) uint16)."""
+        st = self.debug_sgm_stats()
+        shape = (st["rows"], st["cols"])
+        cl, cr, S = np.zeros(shape, np.uint64), np.zeros(shape, np.uint64), np.zeros(shape + (st["max_disparity"],), np.uint16)
+        self._check(self.L.cvo_debug_sgm_readback(self.ctx, cl.ctypes.data_as(C.POINTER(C.c_ulonglong)), cr.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                                  S.ctypes.data_as(C.POINTER(C.c_ushort))))
+        return dict(census_left=cl, census_right=cr, S=S)
 
     def upload_stereo_recipe(self, frame, leaf=None, edge_divisor=5):
         """cvo_cloud_upload_stereo_recipe: the multi-frame KITTI driver's per-frame block - upload_rgbd's recipe on the stereo

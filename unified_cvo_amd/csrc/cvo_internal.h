@@ -1,5 +1,5 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
 // pair, graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -158,6 +158,14 @@ struct NlmStatsAcc {
   int on_device = 0, mult = 0, shift = 0, n_nonzero = 0, tile_w = 0, tile_h = 0, table_in_lds = 0;
 };
 
+// what cvo_debug_sgm_stats reports of the context's last cvo_stereo_disparity (cvo_sgm.hip), and where cvo_debug_sgm_readback
+// finds the census planes and S of a call that ran on the device
+struct SgmStatsAcc {
+  int on_device = 0, rows = 0, cols = 0, D = 0, paths = 0, tile_w = 0, tile_h = 0;
+  int lines[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lines launched per direction
+  size_t o_census_left = 0, o_census_right = 0, o_S = 0;
+};
+
 // offsets of a call's buffers in one device allocation, 256-byte aligned; `off` ends as the bytes to allocate
 struct ScratchLayout {
   size_t off = 0;
@@ -260,6 +268,10 @@ struct cvo_ctx {
   // denoising (cvo_nlm.hip): one growable device region - the image, the denoised image, the weight tables
   DeviceScratch nlm_scratch;
   NlmStatsAcc nlm_last{};
+  // stereo matcher (cvo_sgm.hip): one growable device region - the two gray planes, their census planes, the sums S of
+  // rows x cols x max_disparity hypotheses (16 bits each), the disparity map
+  DeviceScratch sgm_scratch;
+  SgmStatsAcc sgm_last{};
   double clock_ms_per_tick = 0.0;  // s_memrealtime, calibrated on first use (cvo_debug_kernel_clock)
 };
 

@@ -70,3 +70,4 @@
 #include "cvo_k_stereo.h"
 #include "cvo_k_lidar.h"
 #include "cvo_k_nlm.h"
+#include "cvo_k_sgm.h"

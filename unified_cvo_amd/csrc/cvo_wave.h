@@ -68,6 +68,14 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
   return max(max((unsigned)__builtin_amdgcn_readlane((int)v, 0), (unsigned)__builtin_amdgcn_readlane((int)v, 16)),
              max((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
 }
+__device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
+  v = min(v, (unsigned)dpp_i32<DPP_XOR1>((int)v));
+  v = min(v, (unsigned)dpp_i32<DPP_XOR2>((int)v));
+  v = min(v, (unsigned)dpp_i32<DPP_HALF_MIRROR>((int)v));
+  v = min(v, (unsigned)dpp_i32<DPP_MIRROR>((int)v));
+  return min(min((unsigned)__builtin_amdgcn_readlane((int)v, 0), (unsigned)__builtin_amdgcn_readlane((int)v, 16)),
+             min((unsigned)__builtin_amdgcn_readlane((int)v, 32), (unsigned)__builtin_amdgcn_readlane((int)v, 48)));
+}
 // min / max of a float over the wave on the DPP paths (every lane gets the result; NaNs are dropped as fminf / fmaxf drop them)
 template <bool MAX>
 __device__ __forceinline__ float wave_minmax_f32(float v) {
