@@ -1,4 +1,4 @@
-// What the front-end check drivers (cvo_rgbd_check, cvo_stereo_check, cvo_lidar_check, cvo_nlm_check, cvo_sgm_check) share: arrays from .npy files or raw files given as
+// What the front-end check drivers (cvo_rgbd_check, cvo_stereo_check, cvo_lidar_check, cvo_nlm_check, cvo_sgm_check, cvo_dfilter_check) share: arrays from .npy files or raw files given as
 // name:rows:cols[:channels][:u16|f32], and the FNV-1a hash they print over a cloud's rows.
 #pragma once
 #include <cstdlib>

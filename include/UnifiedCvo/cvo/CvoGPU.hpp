@@ -135,9 +135,16 @@ class CvoGPU {
   // std::invalid_argument.  Defined in host/cvo_nlm.cpp.
   // New: the library's own stereo matcher on the device (cvo_stereo_disparity, include/cvo_hip.h): the float left disparity
   // of a rectified pair of rows x cols gray planes, invalid = -10, by semi-global matching over a census cost - NOT upstream's
-  // libelas.  config == nullptr: cvo_sgm_config_default.  Refusals throw std::invalid_argument.  Defined in host/cvo_sgm.cpp.
+  // libelas.  config == nullptr: cvo_sgm_config_default.  dfilter given: cvo_stereo_disparity_filtered - the matcher, then
+  // disparity_filter of its map, which stays on the device in between.  Refusals throw std::invalid_argument.  Defined in
+  // host/cvo_sgm.cpp.
   std::vector<float> stereo_disparity(int rows, int cols, const unsigned char* left, const unsigned char* right,
-                                      const cvo_sgm_config_t* config = nullptr) const;
+                                      const cvo_sgm_config_t* config = nullptr, const cvo_dfilter_config_t* dfilter = nullptr) const;
+  // New: libelas's three disparity post-passes on the device (cvo_disparity_filter, include/cvo_hip.h): removeSmallSegments,
+  // gapInterpolation and adaptiveMean of a rows x cols float map whose invalid pixels are negative (they leave as -10), the
+  // matcher's or any other's.  config == nullptr: cvo_dfilter_config_default (libelas's ROBOTICS setting).  Refusals throw
+  // std::invalid_argument.  Defined in host/cvo_sgm.cpp.
+  std::vector<float> disparity_filter(int rows, int cols, const float* disparity, const cvo_dfilter_config_t* config = nullptr) const;
   void nlm_denoise(int rows, int cols, int channels, const unsigned char* src, unsigned char* dst, float h = 10.f, int template_window = 7,
                    int search_window = 21) const;
   void nlm_denoise_lab(int rows, int cols, const unsigned char* lab, unsigned char* dst, float h = 10.f, float h_color = 10.f,

@@ -433,7 +433,8 @@ int cvo_nlm_denoise_lab(cvo_ctx* ctx, int rows, int cols, const uint8_t* lab, co
  * s2 (100 - uniqueness) < 100 s1.  Sub-pixel for 0 < d* < max_disparity - 1 and den = S(d* - 1) + S(d* + 1) - 2 s1 > 0:
  * (float)d* + (float)(S(d* - 1) - S(d* + 1)) / (float)(2 den), else (float)d*.  Left-right check (lr_max_diff >= 0): dR(v, x) =
  * first argmin_d S(v, x + d, d) over x + d < cols; invalid when u - d* < 0 or |dR(v, u - d*) - d*| > lr_max_diff.  Invalid
- * pixels are written as -10.f, the marker cvo_stereo_points rejects.  No speckle filter, median filter or hole filling.
+ * pixels are written as -10.f, the marker cvo_stereo_points rejects.  The matcher itself filters nothing; libelas's three
+ * post-passes are cvo_disparity_filter below (cvo_stereo_disparity_filtered runs both).
  * CVO_E_INVALID, nothing written: a missing pointer, rows / cols < 1, max_disparity not 64 / 128 / 256, not 0 <= p1 <= p2 <= 193,
  * uniqueness outside 0 .. 99, paths not 4 or 8.  CVO_E_UNSUPPORTED: more than 2^24 pixels, rows x cols x max_disparity x 2 bytes
  * of sums above 2 GiB.  cols < max_disparity and 1 x 1 frames are valid.  cvo_stereo_disparity runs on the context's upload
@@ -457,6 +458,45 @@ int cvo_stereo_disparity(cvo_ctx* ctx, int rows, int cols, const uint8_t* left, 
  * cvo_cloud_upload_stereo's. */
 int cvo_cloud_upload_stereo_pair(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, const uint8_t* right_gray, const cvo_sgm_config_t* cfg,
                                  int method, cvo_cloud** out, int* pixel, int* n);
+/* ---- disparity post-filter: the three passes libelas runs on the left map after matching (StaticStereo::disparity, ROBOTICS
+ * parameters, postprocess_only_left) - removeSmallSegments, gapInterpolation, adaptiveMean, in that order - on any float map
+ * whose invalid pixels are negative (the matcher's -10 included).  The statement is tests/np_dfilter.py, restated from
+ * elas.cpp; the CPU twin and the kernels of cvo_k_dfilter.h equal it exactly, and it equals libelas's own compiled passes
+ * exactly (tests/golden/dfilter_elas.npz) outside the pixels where libelas's result depends on uninitialised memory: its
+ * adaptiveMean reads the never-written part of a malloc'ed buffer, which reaches column 3 and rows 4 - 6 and rows - 6 .. rows - 4
+ * of its output; here that buffer starts as a copy of the map.  Built: the full-resolution branch.  NOT built, because
+ * upstream never turns them on: param.subsampling, the add_corners extrapolation, the median filter; libelas's matcher is
+ * not built either, and the filtered map is downloaded and uploaded again before the front end reads it.
+ * Speckle: 4-connected segments of valid (>= 0) pixels, neighbours joined when fabsf(a - b) <= speckle_sim_threshold; segments
+ * of fewer than speckle_size pixels, and every negative value, become -10.f; speckle_size <= 1: no-op.  Gap: rows, then
+ * columns on the rows' result: a run of 1 .. ipol_gap_width invalid pixels with a valid pixel on both sides inside the line
+ * is filled with (d1 + d2) / 2 when fabsf(d1 - d2) < 3, else min(d1, d2); width 0: no-op.  Adaptive mean (adaptive_mean != 0):
+ * a horizontal, then a vertical 8-tap pass (centre - 4 .. centre + 3) whose weights are max(0, 4 - masked |difference|) with
+ * libelas's mask as compiled (the bit pattern 0x4F000000: 4 below a difference of 2, 2 in [2, 8), 0 from 8) and whose sums
+ * run in libelas's ring order, which depends on the coordinate mod 8; invalid pixels enter as -10.
+ * CVO_E_INVALID, nothing written: a missing pointer, rows / cols < 1, speckle_sim_threshold not finite or negative,
+ * speckle_size or ipol_gap_width < 0, a value that is not finite, a negative value that is not < -speckle_sim_threshold
+ * (libelas's result would depend on its seed order).  CVO_E_UNSUPPORTED: more than 2^24 pixels.  out == in is allowed.
+ * cvo_disparity_filter runs on the context's upload stream like the front ends.  Switch DFILTER_HOST=1 / 0: the CPU twin (one
+ * thread) / the kernels for every size (unset: maps under 32768 pixels take the CPU twin: measured, profiles/dfilter/crossover.txt). */
+typedef struct cvo_dfilter_config_t {
+  float speckle_sim_threshold; /* finite, >= 0 */
+  int speckle_size;            /* >= 0; <= 1: no speckle pass */
+  int ipol_gap_width;          /* >= 0; 0: no gap pass */
+  int adaptive_mean;           /* 0: no mean pass */
+} cvo_dfilter_config_t;
+void cvo_dfilter_config_default(cvo_dfilter_config_t* cfg);   /* 1, 200, 3, 1: libelas's ROBOTICS setting */
+int cvo_disparity_filter_host(int rows, int cols, const float* in, const cvo_dfilter_config_t* cfg, float* out);   /* CPU twin, no context */
+int cvo_disparity_filter(cvo_ctx* ctx, int rows, int cols, const float* in, const cvo_dfilter_config_t* cfg, float* out);
+/* cvo_stereo_disparity, then cvo_disparity_filter of its map: the map stays on the device between the two, one download at
+ * the end.  Refusals: the matcher's, then the filter's configuration (a speckle_sim_threshold of 10 or more included: the
+ * matcher's -10 would not lie below it). */
+int cvo_stereo_disparity_filtered(cvo_ctx* ctx, int rows, int cols, const uint8_t* left, const uint8_t* right, const cvo_sgm_config_t* sgm_cfg,
+                                  const cvo_dfilter_config_t* dfilter_cfg, float* disparity);
+/* cvo_cloud_upload_stereo_pair with cvo_stereo_disparity_filtered in the place of cvo_stereo_disparity. */
+int cvo_cloud_upload_stereo_pair_filtered(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, const uint8_t* right_gray,
+                                          const cvo_sgm_config_t* sgm_cfg, const cvo_dfilter_config_t* dfilter_cfg, int method,
+                                          cvo_cloud** out, int* pixel, int* n);
 int cvo_cloud_size(const cvo_cloud* c);
 void cvo_cloud_free(cvo_cloud* c);
 

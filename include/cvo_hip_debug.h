@@ -130,6 +130,15 @@ int cvo_debug_sgm_stats(cvo_ctx* ctx, int* on_device, int* max_disparity, int* p
  * cols 64-bit words each) and S (rows x cols x max_disparity 16-bit sums).  Any pointer may be NULL.  Tests use it to find
  * the first stage that differs from the statement without running anything again. */
 int cvo_debug_sgm_readback(cvo_ctx* ctx, unsigned long long* census_left, unsigned long long* census_right, unsigned short* S);
+/* The context's last cvo_disparity_filter (the _filtered entry points' included): whether the kernels ran; the map's shape;
+ * the kernels' tile (0 x 0 on the CPU twin); counts[3]: segments of valid pixels the speckle pass found, valid pixels it
+ * removed, pixels the gap pass filled (rows + columns).  after_speckle / after_gap / mean_tmp: the maps a call that ran on
+ * the device left in the context's region after the speckle pass, after the gap pass and after the mean's horizontal pass
+ * (rows x cols floats each; CVO_E_INVALID when the call ran on the host, or for mean_tmp when the mean did not run, for the
+ * others when no stage up to theirs ran).  Any pointer may be NULL.  Tests use the maps to name the first stage that differs
+ * from the statement without running anything again. */
+int cvo_debug_dfilter_stats(cvo_ctx* ctx, int* on_device, int* rows, int* cols, int* tile_w, int* tile_h,
+                            unsigned long long* counts /* 3 */, float* after_speckle, float* after_gap, float* mean_tmp);
 
 #ifdef __cplusplus
 }

@@ -247,6 +247,10 @@ class cvo_sgm_config_t(C.Structure):
     _fields_ = [("max_disparity", C.c_int), ("p1", C.c_int), ("p2", C.c_int), ("uniqueness", C.c_int), ("lr_max_diff", C.c_int), ("paths", C.c_int)]
 
 
+class cvo_dfilter_config_t(C.Structure):
+    _fields_ = [("speckle_sim_threshold", C.c_float), ("speckle_size", C.c_int), ("ipol_gap_width", C.c_int), ("adaptive_mean", C.c_int)]
+
+
 CVO_DEPTH_U16, CVO_DEPTH_F32 = 0, 1
 CVO_SELECT_CV_FAST, CVO_SELECT_DSO_EDGES, CVO_SELECT_FULL = 0, 2, 8
 CVO_FAST_RGBD, CVO_FAST_STEREO, CVO_FAST_STEREO_SEMANTIC = (9, 15000, 12000, 13), (4, 24000, 15000, 50), (4, 28000, 15000, 50)
@@ -275,6 +279,8 @@ EXPORTED = [
     "cvo_nlm_denoise_lab", "cvo_debug_nlm_stats",
     "cvo_sgm_config_default", "cvo_stereo_disparity_host", "cvo_stereo_disparity", "cvo_cloud_upload_stereo_pair", "cvo_debug_sgm_stats",
     "cvo_debug_sgm_readback",
+    "cvo_dfilter_config_default", "cvo_disparity_filter_host", "cvo_disparity_filter", "cvo_stereo_disparity_filtered",
+    "cvo_cloud_upload_stereo_pair_filtered", "cvo_debug_dfilter_stats",
 ]
 
 _libs = {}
@@ -409,6 +415,14 @@ def lib(path=None):
     L.cvo_cloud_upload_stereo_pair.argtypes = [vp, C.POINTER(cvo_stereo_frame_t), bp, sc, ip, C.POINTER(vp), ipp, ipp]
     L.cvo_debug_sgm_stats.argtypes = [vp] + [ipp] * 8
     L.cvo_debug_sgm_readback.argtypes = [vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), C.POINTER(C.c_ushort)]
+    dc = C.POINTER(cvo_dfilter_config_t)
+    L.cvo_dfilter_config_default.argtypes = [dc]
+    L.cvo_dfilter_config_default.restype = None
+    L.cvo_disparity_filter_host.argtypes = [ip, ip, fp, dc, fp]
+    L.cvo_disparity_filter.argtypes = [vp, ip, ip, fp, dc, fp]
+    L.cvo_stereo_disparity_filtered.argtypes = [vp, ip, ip, bp, bp, sc, dc, fp]
+    L.cvo_cloud_upload_stereo_pair_filtered.argtypes = [vp, C.POINTER(cvo_stereo_frame_t), bp, sc, dc, ip, C.POINTER(vp), ipp, ipp]
+    L.cvo_debug_dfilter_stats.argtypes = [vp] + [ipp] * 5 + [C.POINTER(C.c_ulonglong), fp, fp, fp]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

@@ -353,6 +353,44 @@ def stereo_disparity_host(left, right, config=None):
     return out
 
 
+class DFilterConfig:
+    """cvo_dfilter_config_t: the disparity post-filter's configuration (libelas's removeSmallSegments, gapInterpolation and
+    adaptiveMean; tests/np_dfilter.py states them).  The defaults are libelas's ROBOTICS setting.  speckle_size <= 1,
+    ipol_gap_width 0 and adaptive_mean 0 turn the three passes off."""
+
+    def __init__(self, speckle_sim_threshold=1.0, speckle_size=200, ipol_gap_width=3, adaptive_mean=1):
+        self.speckle_sim_threshold, self.speckle_size = float(speckle_sim_threshold), int(speckle_size)
+        self.ipol_gap_width, self.adaptive_mean = int(ipol_gap_width), int(adaptive_mean)
+
+    def c_struct(self):
+        return _capi.cvo_dfilter_config_t(self.speckle_sim_threshold, self.speckle_size, self.ipol_gap_width, self.adaptive_mean)
+
+
+def _disparity_filter(call, disparity, config, out=None):
+    """Shared by CvoGPU.disparity_filter and disparity_filter_host -> (rc, filtered (rows, cols) float32).  out: the array to
+    write, which may be `disparity` itself."""
+    d = np.ascontiguousarray(disparity, np.float32)
+    if d.ndim != 2:
+        raise ValueError(f"disparity {d.shape} must be a (rows, cols) map")
+    cfg = (config or DFilterConfig()).c_struct()
+    if out is None:
+        out = np.zeros(d.shape, np.float32)
+    elif out.dtype != np.float32 or out.shape != d.shape or not out.flags.c_contiguous:
+        raise ValueError("out must be a contiguous float32 array of the map's shape")
+    fp = C.POINTER(C.c_float)
+    rc = call(d.shape[0], d.shape[1], d.ctypes.data_as(fp), C.byref(cfg), out.ctypes.data_as(fp))
+    return rc, out
+
+
+def disparity_filter_host(disparity, config=None, out=None):
+    """cvo_disparity_filter_host: libelas's three post-passes (speckle, gap, adaptive mean) on a float32 disparity map whose
+    invalid pixels are negative, on one CPU thread; invalid pixels leave as -10."""
+    rc, out = _disparity_filter(_capi.lib().cvo_disparity_filter_host, disparity, config, out)
+    if rc != 0:
+        _raise(rc, "cvo_disparity_filter_host refused the map or the configuration")
+    return out
+
+
 def _nlm_config(h, template_window, search_window):
     return _capi.cvo_nlm_config_t(float(h), int(template_window), int(search_window))
 
@@ -819,22 +857,60 @@ class CvoGPU:
         self._check(self.L.cvo_cloud_upload_stereo(self.ctx, C.byref(fs), int(method), C.byref(h), pixel.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n)))
         return self._resident(h, n.value, pixel)
 
-    def stereo_disparity(self, left, right, config=None):
-        """cvo_stereo_disparity: as stereo_disparity_host, by the context's route (switch SGM_HOST)."""
-        rc, out = _stereo_disparity(lambda *a: self.L.cvo_stereo_disparity(self.ctx, *a), left, right, config)
+    def stereo_disparity(self, left, right, config=None, dfilter=None):
+        """cvo_stereo_disparity: as stereo_disparity_host, by the context's route (switch SGM_HOST).  dfilter (a DFilterConfig):
+        cvo_stereo_disparity_filtered - the matcher, then disparity_filter of its map, which stays on the device in between."""
+        if dfilter is None:
+            call = lambda *a: self.L.cvo_stereo_disparity(self.ctx, *a)  # noqa: E731
+        else:
+            df = dfilter.c_struct()
+            call = lambda *a: self.L.cvo_stereo_disparity_filtered(self.ctx, *a[:-1], C.byref(df), a[-1])  # noqa: E731
+        rc, out = _stereo_disparity(call, left, right, config)
         self._check(rc)
         return out
 
-    def upload_stereo_pair(self, frame, right_gray, config=None, method=CV_FAST):
+    def disparity_filter(self, disparity, config=None, out=None):
+        """cvo_disparity_filter: as disparity_filter_host, by the context's route (switch DFILTER_HOST)."""
+        rc, out = _disparity_filter(lambda *a: self.L.cvo_disparity_filter(self.ctx, *a), disparity, config, out)
+        self._check(rc)
+        return out
+
+    def debug_dfilter_stats(self, readback=False):
+        """cvo_debug_dfilter_stats of the last disparity_filter / filtered stereo_disparity / upload_stereo_pair -> dict(on_device,
+        rows, cols, tile_w, tile_h, segments, removed, filled); readback: also the maps the device kept of the stages that ran -
+        after_speckle, after_gap, mean_tmp (a stage that did not run: None)."""
+        names = ("on_device", "rows", "cols", "tile_w", "tile_h")
+        v = {k: C.c_int() for k in names}
+        counts = (C.c_ulonglong * 3)()
+        self._check(self.L.cvo_debug_dfilter_stats(self.ctx, *[C.byref(v[k]) for k in names], counts, None, None, None))
+        out = {k: x.value for k, x in v.items()}
+        out["on_device"] = bool(out["on_device"])
+        out["segments"], out["removed"], out["filled"] = (int(c) for c in counts)
+        if readback:
+            fp = C.POINTER(C.c_float)
+            for i, name in enumerate(("after_speckle", "after_gap", "mean_tmp")):
+                m = np.zeros((out["rows"], out["cols"]), np.float32)
+                ptrs = [None, None, None]
+                ptrs[i] = m.ctypes.data_as(fp)
+                rc = self.L.cvo_debug_dfilter_stats(self.ctx, None, None, None, None, None, None, *ptrs)
+                out[name] = m if rc == 0 else None
+        return out
+
+    def upload_stereo_pair(self, frame, right_gray, config=None, method=CV_FAST, dfilter=None):
         """cvo_cloud_upload_stereo_pair: stereo_disparity of (the frame's gray plane, right_gray), then upload_stereo with that
-        map; frame.disparity may be None and is not read."""
+        map; frame.disparity may be None and is not read.  dfilter (a DFilterConfig): cvo_cloud_upload_stereo_pair_filtered."""
         right = np.ascontiguousarray(right_gray, np.uint8)
         if right.shape != (frame.rows, frame.cols):
             raise ValueError(f"right_gray is {right.shape}, the frame {frame.rows} x {frame.cols}")
         pixel = np.zeros(max(frame.rows * frame.cols, 1), np.int32)
         n, h, fs, cfg = C.c_int(), C.c_void_p(), frame.c_struct(), (config or SGMConfig()).c_struct()
-        self._check(self.L.cvo_cloud_upload_stereo_pair(self.ctx, C.byref(fs), right.ctypes.data_as(C.POINTER(C.c_ubyte)), C.byref(cfg), int(method),
-                                                        C.byref(h), pixel.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n)))
+        rp, pp = right.ctypes.data_as(C.POINTER(C.c_ubyte)), pixel.ctypes.data_as(C.POINTER(C.c_int))
+        if dfilter is None:
+            self._check(self.L.cvo_cloud_upload_stereo_pair(self.ctx, C.byref(fs), rp, C.byref(cfg), int(method), C.byref(h), pp, C.byref(n)))
+        else:
+            df = dfilter.c_struct()
+            self._check(self.L.cvo_cloud_upload_stereo_pair_filtered(self.ctx, C.byref(fs), rp, C.byref(cfg), C.byref(df), int(method), C.byref(h), pp,
+                                                                     C.byref(n)))
         return self._resident(h, n.value, pixel)
 
     def debug_sgm_stats(self):

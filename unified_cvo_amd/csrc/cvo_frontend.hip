@@ -1,4 +1,4 @@
-// cvo_frontend.hip -- what the front ends (cvo_voxel.hip, cvo_rgbd.hip, cvo_fast.hip, cvo_stereo.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip) share on the host: the
+// cvo_frontend.hip -- what the front ends (cvo_voxel.hip, cvo_rgbd.hip, cvo_fast.hip, cvo_stereo.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip) share on the host: the
 // growable scratch regions (type and layout: cvo_internal.h), the launches of an ordered compaction (cvo_k_compact.h) and
 // the read-back of its total, the frame of an entry point and the copy-out of the kept indices.
 // A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.  Shared declarations: cvo_internal.h.

@@ -1,5 +1,5 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
 // pair, graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -163,7 +163,16 @@ struct NlmStatsAcc {
 struct SgmStatsAcc {
   int on_device = 0, rows = 0, cols = 0, D = 0, paths = 0, tile_w = 0, tile_h = 0;
   int lines[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lines launched per direction
-  size_t o_census_left = 0, o_census_right = 0, o_S = 0;
+  size_t o_census_left = 0, o_census_right = 0, o_S = 0, o_disparity = 0;
+};
+
+// what cvo_debug_dfilter_stats reports of the context's last disparity filter (cvo_dfilter.hip), and where it finds the maps
+// after each stage of a call that ran on the device (a stage that did not run: its input's)
+struct DFilterStatsAcc {
+  int on_device = 0, rows = 0, cols = 0, tile_w = 0, tile_h = 0;
+  unsigned long long segments = 0, removed = 0, filled = 0;  // speckle: segments of valid pixels, valid pixels removed; gap: pixels filled
+  size_t o_speckle = 0, o_gap = 0, o_tmp = 0;
+  bool speckle_resident = false, gap_resident = false, tmp_resident = false;
 };
 
 // offsets of a call's buffers in one device allocation, 256-byte aligned; `off` ends as the bytes to allocate
@@ -272,6 +281,14 @@ struct cvo_ctx {
   // rows x cols x max_disparity hypotheses (16 bits each), the disparity map
   DeviceScratch sgm_scratch;
   SgmStatsAcc sgm_last{};
+  // disparity post-filter (cvo_dfilter.hip): one growable device region - the map, the union-find arrays, the gap scan's
+  // indices, the map after each stage, the result with its counters
+  DeviceScratch dfilter_scratch;
+  // ... and its pinned host staging, kept between calls: the map on its way up, the result with its counters on its way down
+  // (a pageable 1.9 MB copy either way, into fresh pages every call, cost the call tens of milliseconds: DESIGN.md section 3)
+  char* dfilter_staging = nullptr;
+  size_t dfilter_staging_bytes = 0;
+  DFilterStatsAcc dfilter_last{};
   double clock_ms_per_tick = 0.0;  // s_memrealtime, calibrated on first use (cvo_debug_kernel_clock)
 };
 

@@ -71,3 +71,4 @@
 #include "cvo_k_lidar.h"
 #include "cvo_k_nlm.h"
 #include "cvo_k_sgm.h"
+#include "cvo_k_dfilter.h"

@@ -149,7 +149,8 @@ void sgm_launch_select(hipStream_t st, const SgmSelectArgs& a) {
 }
 
 // One upload, census, the directions' launches, the selection, one download, one synchronisation; on upload_stream under
-// upload_mutex.  The census planes and S stay in the region for cvo_debug_sgm_readback until the next call.
+// upload_mutex.  The census planes and S stay in the region for cvo_debug_sgm_readback until the next call.  out == nullptr:
+// enqueued only, neither downloaded nor waited for - the map is at stats.o_disparity for the filter of cvo_dfilter.hip.
 int sgm_device(cvo_ctx* ctx, const SgmConst& k, const unsigned char* left, const unsigned char* right, float* out, SgmStatsAcc& stats) {
   hipStream_t st = ctx->upload_stream;
   const size_t np = (size_t)k.rows * k.cols;
@@ -193,10 +194,13 @@ int sgm_device(cvo_ctx* ctx, const SgmConst& k, const unsigned char* left, const
     sgm_launch_select<256>(st, s);
   }
   HIP_TRY(ctx, hipGetLastError());
-  std::vector<float> host(np);  // (nothing is written unless the call succeeds)
-  HIP_TRY(ctx, hipMemcpyAsync(host.data(), base + o_disp, 4 * np, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
-  std::memcpy(out, host.data(), 4 * np);
+  if (out) {
+    std::vector<float> host(np);  // (nothing is written unless the call succeeds)
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), base + o_disp, 4 * np, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::memcpy(out, host.data(), 4 * np);
+  }
+  stats.o_disparity = o_disp;
   stats.o_census_left = o_cl;
   stats.o_census_right = o_cr;
   stats.o_S = o_S;
@@ -232,6 +236,36 @@ int sgm_disparity(cvo_ctx* ctx, const char* who, int rows, int cols, const uint8
   });
 }
 
+// cvo_cloud_upload_stereo_pair and its _filtered form (cvo_dfilter.hip): match(rows, cols, left, disparity) makes the map
+template <class Match>
+int upload_stereo_pair(cvo_ctx* ctx, const char* who, const cvo_stereo_frame_t* frame, const uint8_t* right_gray, const cvo_sgm_config_t* cfg, int method,
+                       cvo_cloud** out, int* pixel, int* n, Match match) {
+  if (!frame || !out) return fail(ctx, CVO_E_INVALID, std::string(who) + ": frame and out are required");
+  std::string msg;
+  float placeholder = 0.f;  // (the matcher's refusals come first; they do not look at the map)
+  int rc = sgm_validate(frame->rows, frame->cols, frame->image, right_gray, cfg, &placeholder, &msg);
+  if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
+  try {
+    const size_t np = (size_t)frame->rows * frame->cols;
+    std::vector<float> disparity(np);
+    cvo_stereo_frame_t f = *frame;
+    f.disparity = disparity.data();
+    if ((rc = stereo_check(ctx, who, &f, &method, &msg)) != CVO_OK) return rc;
+    // the left plane: the frame's gray plane, or the gray the front end itself takes of the image
+    std::vector<uint8_t> gray;
+    const uint8_t* left = f.gray ? f.gray : f.image;
+    if (!f.gray && f.channels != 1) {
+      gray.resize(np);
+      for (size_t p = 0; p < np; p++) gray[p] = (uint8_t)rgbd_gray(f.image, f.channels, p);
+      left = gray.data();
+    }
+    if ((rc = match(f.rows, f.cols, left, disparity.data())) != CVO_OK) return rc;
+    return cvo_cloud_upload_stereo(ctx, &f, method, out, pixel, n);
+  } catch (const std::exception& e) {
+    return fail(ctx, CVO_E_NOMEM, std::string(who) + ": " + e.what());
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -259,31 +293,8 @@ int cvo_stereo_disparity(cvo_ctx* ctx, int rows, int cols, const uint8_t* left, 
 int cvo_cloud_upload_stereo_pair(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, const uint8_t* right_gray, const cvo_sgm_config_t* cfg, int method,
                                  cvo_cloud** out, int* pixel, int* n) {
   if (!ctx) return CVO_E_INVALID;
-  const char* who = "cvo_cloud_upload_stereo_pair";
-  if (!frame || !out) return fail(ctx, CVO_E_INVALID, std::string(who) + ": frame and out are required");
-  std::string msg;
-  float placeholder = 0.f;  // (the matcher's refusals come first; they do not look at the map)
-  int rc = sgm_validate(frame->rows, frame->cols, frame->image, right_gray, cfg, &placeholder, &msg);
-  if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
-  try {
-    const size_t np = (size_t)frame->rows * frame->cols;
-    std::vector<float> disparity(np);
-    cvo_stereo_frame_t f = *frame;
-    f.disparity = disparity.data();
-    if ((rc = stereo_check(ctx, who, &f, &method, &msg)) != CVO_OK) return rc;
-    // the left plane: the frame's gray plane, or the gray the front end itself takes of the image
-    std::vector<uint8_t> gray;
-    const uint8_t* left = f.gray ? f.gray : f.image;
-    if (!f.gray && f.channels != 1) {
-      gray.resize(np);
-      for (size_t p = 0; p < np; p++) gray[p] = (uint8_t)rgbd_gray(f.image, f.channels, p);
-      left = gray.data();
-    }
-    if ((rc = cvo_stereo_disparity(ctx, f.rows, f.cols, left, right_gray, cfg, disparity.data())) != CVO_OK) return rc;
-    return cvo_cloud_upload_stereo(ctx, &f, method, out, pixel, n);
-  } catch (const std::exception& e) {
-    return fail(ctx, CVO_E_NOMEM, std::string(who) + ": " + e.what());
-  }
+  return upload_stereo_pair(ctx, "cvo_cloud_upload_stereo_pair", frame, right_gray, cfg, method, out, pixel, n,
+                            [&](int rows, int cols, const uint8_t* left, float* disparity) { return cvo_stereo_disparity(ctx, rows, cols, left, right_gray, cfg, disparity); });
 }
 
 int cvo_debug_sgm_stats(cvo_ctx* ctx, int* on_device, int* max_disparity, int* paths, int* lines, int* rows, int* cols, int* tile_w, int* tile_h) {
