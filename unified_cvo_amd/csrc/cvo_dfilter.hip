@@ -1,6 +1,6 @@
 // cvo_dfilter.hip -- the disparity post-filter: cvo_disparity_filter(_host) (libelas's removeSmallSegments, gapInterpolation
-// and adaptiveMean, full-resolution branch, on a float map whose invalid pixels are negative), cvo_stereo_disparity_filtered
-// and cvo_cloud_upload_stereo_pair_filtered (the matcher of cvo_sgm.hip, then the filter, the map resident in between), and
+// and adaptiveMean, full-resolution branch, on a float map whose invalid pixels are negative), dfilter_run for the chains of
+// cvo_stereo_pair.hip (the matcher of cvo_sgm.hip, then the filter, the map resident in between), and
 // cvo_debug_dfilter_stats.  tests/np_dfilter.py states what is computed; the CPU twin (dfilter_cpu) uses the same arithmetic
 // (cvo_dfilter_math.h) as the kernels of cvo_k_dfilter.h.  A SECTION of the one translation unit cvo_hip.hip; not compiled on
 // its own.
@@ -10,7 +10,7 @@ namespace {
 constexpr int DFILTER_HOST_BELOW = 32768;
 constexpr long long DFILTER_MAX_PIXELS = 1ll << 24;
 
-bool dfilter_on_host(const cvo_ctx* ctx, long long np) { return ctx->opt.dfilter_host > 0 || (ctx->opt.dfilter_host < 0 && np < DFILTER_HOST_BELOW); }
+bool dfilter_on_host(const cvo_ctx* ctx, long long np) { return route_on_host(ctx->opt.dfilter_host, np, DFILTER_HOST_BELOW); }
 
 int dfilter_validate_config(int rows, int cols, const cvo_dfilter_config_t* cfg, std::string* msg) {
   if (!cfg) return *msg = "a required pointer is missing", CVO_E_INVALID;
@@ -242,9 +242,7 @@ int dfilter_device(cvo_ctx* ctx, const DFilterConst& k, const float* in, const f
 // the filter of a checked map, by the context's route; the caller holds upload_mutex.  in: on the host; d_in: the same map
 // resident, or nullptr
 int dfilter_run(cvo_ctx* ctx, const DFilterConst& k, const float* in, const float* d_in, float* out) {
-  DFilterStatsAcc stats;
-  stats.rows = k.rows;
-  stats.cols = k.cols;
+  DFilterStatsAcc stats(k);
   const size_t np = (size_t)k.rows * k.cols;
   if (!ctx || dfilter_on_host(ctx, (long long)np)) {
     std::vector<float> d(in, in + np);
@@ -294,58 +292,6 @@ int cvo_disparity_filter_host(int rows, int cols, const float* in, const cvo_dfi
 int cvo_disparity_filter(cvo_ctx* ctx, int rows, int cols, const float* in, const cvo_dfilter_config_t* cfg, float* out) {
   if (!ctx) return CVO_E_INVALID;
   return dfilter_entry(ctx, "cvo_disparity_filter", rows, cols, in, cfg, out);
-}
-
-int cvo_stereo_disparity_filtered(cvo_ctx* ctx, int rows, int cols, const uint8_t* left, const uint8_t* right, const cvo_sgm_config_t* sgm_cfg,
-                                  const cvo_dfilter_config_t* dfilter_cfg, float* disparity) {
-  if (!ctx) return CVO_E_INVALID;
-  const char* who = "cvo_stereo_disparity_filtered";
-  std::string msg;
-  int rc = sgm_validate(rows, cols, left, right, sgm_cfg, disparity, &msg);
-  if (rc == CVO_OK) rc = dfilter_validate_for_matcher(rows, cols, dfilter_cfg, &msg);
-  if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
-  return frontend_call(ctx, who, [&] {
-    const SgmConst k = sgm_const(rows, cols, *sgm_cfg);
-    const DFilterConst f = dfilter_const(rows, cols, *dfilter_cfg);
-    const size_t np = (size_t)rows * cols;
-    SgmStatsAcc stats;
-    stats.rows = rows;
-    stats.cols = cols;
-    stats.D = k.D;
-    stats.paths = k.paths;
-    std::vector<float> raw;  // the raw map on the host: not needed when both stages run on the device
-    const float* resident = nullptr;
-    if (sgm_on_host(ctx, (long long)np)) {
-      raw.resize(np);
-      sgm_cpu(k, left, right, raw.data());
-    } else {
-      // the map stays in the matcher's region; it is downloaded only for a filter that takes the CPU twin
-      stats.on_device = 1;
-      const bool filter_on_host = dfilter_on_host(ctx, (long long)np);
-      if (filter_on_host) raw.resize(np);
-      const int rc = sgm_device(ctx, k, left, right, filter_on_host ? raw.data() : nullptr, stats);
-      if (rc != CVO_OK) return rc;
-      resident = (const float*)(ctx->sgm_scratch.p + stats.o_disparity);
-    }
-    ctx->sgm_last = stats;
-    return dfilter_run(ctx, f, raw.data(), resident, disparity);
-  });
-}
-
-int cvo_cloud_upload_stereo_pair_filtered(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, const uint8_t* right_gray, const cvo_sgm_config_t* sgm_cfg,
-                                          const cvo_dfilter_config_t* dfilter_cfg, int method, cvo_cloud** out, int* pixel, int* n) {
-  if (!ctx) return CVO_E_INVALID;
-  const char* who = "cvo_cloud_upload_stereo_pair_filtered";
-  std::string msg;
-  float placeholder = 0.f;
-  // the filter's refusals follow the matcher's (which upload_stereo_pair reports) and precede the front end's
-  if (frame && out && sgm_validate(frame->rows, frame->cols, frame->image, right_gray, sgm_cfg, &placeholder, &msg) == CVO_OK) {
-    const int rc = dfilter_validate_for_matcher(frame->rows, frame->cols, dfilter_cfg, &msg);
-    if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
-  }
-  return upload_stereo_pair(ctx, who, frame, right_gray, sgm_cfg, method, out, pixel, n, [&](int rows, int cols, const uint8_t* left, float* disparity) {
-    return cvo_stereo_disparity_filtered(ctx, rows, cols, left, right_gray, sgm_cfg, dfilter_cfg, disparity);
-  });
 }
 
 int cvo_debug_dfilter_stats(cvo_ctx* ctx, int* on_device, int* rows, int* cols, int* tile_w, int* tile_h, unsigned long long* counts,

@@ -14,7 +14,7 @@ namespace {
 constexpr int STEREO_HOST_BELOW = 10000, STEREO_RECIPE_HOST_BELOW = 24000;
 
 bool stereo_on_host(const cvo_ctx* ctx, int rows, int cols, int below = STEREO_HOST_BELOW) {
-  return ctx->opt.stereo_host > 0 || (ctx->opt.stereo_host < 0 && (long long)rows * cols < below);
+  return route_on_host(ctx->opt.stereo_host, (long long)rows * cols, below);
 }
 
 int fast_validate_schedule(const cvo_fast_schedule_t* s, std::string* msg) {
@@ -141,29 +141,9 @@ cvo_rgbd_frame_t fast_plane_frame(int rows, int cols, const unsigned char* gray)
   return f;
 }
 
-}  // namespace
-
-extern "C" {
-
-int cvo_fast_select_host(int rows, int cols, const uint8_t* gray, const cvo_fast_schedule_t* schedule, int* pixel, int* n, int* threshold_used) {
-  std::string msg;
-  int rc = fast_validate_plane(rows, cols, gray, &msg);
-  if (rc == CVO_OK) rc = fast_validate_schedule(schedule, &msg);
-  if (rc != CVO_OK) return rc;
-  if (!pixel || !n) return CVO_E_INVALID;
-  return frontend_call(nullptr, "", [&] {
-    std::vector<int> pix;
-    StereoStatsAcc st;
-    fast_select_cpu(GrayView{gray, 1}, cols, rows, *schedule, pix, st);
-    copy_kept(pix, pixel, n);
-    if (threshold_used) *threshold_used = st.threshold_used;
-    return CVO_OK;
-  });
-}
-
-int cvo_fast_select(cvo_ctx* ctx, int rows, int cols, const uint8_t* gray, const cvo_fast_schedule_t* schedule, int* pixel, int* n,
-                    int* threshold_used) {
-  if (!ctx) return CVO_E_INVALID;
+// the body of cvo_fast_select_host and cvo_fast_select
+int fast_select_entry(cvo_ctx* ctx, const char* who, int rows, int cols, const uint8_t* gray, const cvo_fast_schedule_t* schedule, int* pixel, int* n,
+                      int* threshold_used) {
   std::string msg;
   int rc = fast_validate_plane(rows, cols, gray, &msg);
   if (rc == CVO_OK) rc = fast_validate_schedule(schedule, &msg);
@@ -171,11 +151,11 @@ int cvo_fast_select(cvo_ctx* ctx, int rows, int cols, const uint8_t* gray, const
     rc = CVO_E_INVALID;
     msg = "pixel and n are required";
   }
-  if (rc != CVO_OK) return fail(ctx, rc, "cvo_fast_select: " + msg);
-  return frontend_call(ctx, "cvo_fast_select", [&] {
+  if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
+  return frontend_call(ctx, who, [&] {
     std::vector<int> pix;
     StereoStatsAcc st;
-    if (stereo_on_host(ctx, rows, cols)) {
+    if (!ctx || stereo_on_host(ctx, rows, cols)) {
       fast_select_cpu(GrayView{gray, 1}, cols, rows, *schedule, pix, st);
     } else {
       st.on_device = 1;
@@ -189,9 +169,23 @@ int cvo_fast_select(cvo_ctx* ctx, int rows, int cols, const uint8_t* gray, const
     st.candidates = st.kept = pix.size();
     copy_kept(pix, pixel, n);
     if (threshold_used) *threshold_used = st.threshold_used;
-    ctx->stereo_last = st;
+    if (ctx) ctx->stereo_last = st;
     return CVO_OK;
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int cvo_fast_select_host(int rows, int cols, const uint8_t* gray, const cvo_fast_schedule_t* schedule, int* pixel, int* n, int* threshold_used) {
+  return fast_select_entry(nullptr, "cvo_fast_select_host", rows, cols, gray, schedule, pixel, n, threshold_used);
+}
+
+int cvo_fast_select(cvo_ctx* ctx, int rows, int cols, const uint8_t* gray, const cvo_fast_schedule_t* schedule, int* pixel, int* n,
+                    int* threshold_used) {
+  if (!ctx) return CVO_E_INVALID;
+  return fast_select_entry(ctx, "cvo_fast_select", rows, cols, gray, schedule, pixel, n, threshold_used);
 }
 
 }  // extern "C"

@@ -1,7 +1,18 @@
-// cvo_frontend.hip -- what the front ends (cvo_voxel.hip, cvo_rgbd.hip, cvo_fast.hip, cvo_stereo.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip) share on the host: the
-// growable scratch regions (type and layout: cvo_internal.h), the launches of an ordered compaction (cvo_k_compact.h) and
-// the read-back of its total, the frame of an entry point and the copy-out of the kept indices.
+// cvo_frontend.hip -- what the front ends (cvo_voxel.hip, cvo_rgbd.hip, cvo_fast.hip, cvo_stereo.hip, cvo_lidar.hip, cvo_nlm.hip,
+// cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip) share on the host: the growable scratch regions (type and layout:
+// cvo_internal.h), the launches of an ordered compaction (cvo_k_compact.h) and the read-back of its total, the route rule,
+// the frame of an entry point and the copy-out of the kept indices.
 // A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.  Shared declarations: cvo_internal.h.
+//
+// The entry frame, once for every front end.  A pair cvo_X_host / cvo_X is two one-line extern "C" functions over ONE
+// X_entry(ctx /* nullptr: the twin */, who, ...), and an upload entry point has the same three steps:
+//   validate  X_entry checks the arguments, before any lock, and refuses through fail(ctx, code, who + ": " + text): with a
+//             context the text is what cvo_last_error returns, the twin returns the bare code;
+//   lock      frontend_call(ctx, who, body) takes the context's upload_mutex ONCE around the body.  Whatever the body calls
+//             (the routes, dfilter_run, upload_one_locked, stereo_upload_locked ...) has the contract "the caller holds
+//             upload_mutex" and never enters an extern "C" function: the mutex is not recursive;
+//   commit    the body chooses the route (!ctx || route_on_host(...) is the CPU twin) and, as its last statement and only with
+//             a context, stores ctx->X_last = stats: a call that fails or is refused leaves the previous call's stats.
 
 // Room for `need` bytes: a region that is too small is given back once upload_stream has drained and allocated anew.
 int DeviceScratch::reserve(cvo_ctx* ctx, size_t need, const char* what) {
@@ -45,6 +56,10 @@ int compact_total(cvo_ctx* ctx, const VoxelCtl* ctl, int n, const char* who, con
   if (h->n_kept > (unsigned)n) return fail(ctx, CVO_E_HIP, std::string(who) + ": the device kept more " + what + " than it was given");
   return CVO_OK;
 }
+
+// The route rule of every front end.  The context's X_HOST switch forces the CPU twin (> 0) or the kernels (0); left alone
+// (< 0), a call smaller than the front end's measured crossover (its X_HOST_BELOW, in its own section) takes the twin.
+bool route_on_host(int host_switch, long long size, long long below) { return host_switch > 0 || (host_switch < 0 && size < below); }
 
 // The frame of a front end's entry point once its arguments are checked: body() under the context's upload_mutex; an
 // exception (the allocation of a host buffer) becomes CVO_E_NOMEM with its text.  The _host entry points have no context:

@@ -12,7 +12,7 @@
 //   cvo_queue.hip   the batch queue                                    cvo_eval.hip    inner products, single evaluations
 //   cvo_export.hip  association / ELL exports                          cvo_debug.hip   test and profiling hooks
 //   cvo_irls.hip    multi-frame align (the least-squares solve of CvoBatchIRLS)
-//   cvo_frontend.hip  what the front ends below share: scratch regions, the ordered-compaction launcher, the entry frame
+//   cvo_frontend.hip  what the front ends below share: scratch regions, the ordered-compaction launcher, the route rule, the entry frame
 //   cvo_voxel.hip   voxel-grid downsampling: selection on the device or the host, upload of the survivors
 //   cvo_rgbd.hip    RGB-D front end: depth + colour frame to candidate points and to a resident cloud
 //   cvo_fast.hip    the CV_FAST point selection: FAST-9/16 scores, the reference's threshold schedule
@@ -21,6 +21,7 @@
 //   cvo_nlm.hip     non-local-means denoising of an 8-bit image: RawImage's first statement
 //   cvo_sgm.hip     the stereo matcher: left + right gray planes to the left disparity (semi-global matching over census)
 //   cvo_dfilter.hip the disparity post-filter: libelas's speckle, gap and adaptive-mean passes on the matcher's or a caller's map
+//   cvo_stereo_pair.hip  the entry points that chain matcher, filter and stereo front end under one lock
 #include "cvo_internal.h"
 
 #include "cvo_ctx.hip"
@@ -35,6 +36,7 @@
 #include "cvo_nlm.hip"
 #include "cvo_sgm.hip"
 #include "cvo_dfilter.hip"
+#include "cvo_stereo_pair.hip"
 #include "cvo_sched.hip"
 #include "cvo_queue.hip"
 #include "cvo_eval.hip"

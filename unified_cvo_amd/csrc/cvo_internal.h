@@ -1,5 +1,5 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
 // pair, graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -161,6 +161,8 @@ struct NlmStatsAcc {
 // what cvo_debug_sgm_stats reports of the context's last cvo_stereo_disparity (cvo_sgm.hip), and where cvo_debug_sgm_readback
 // finds the census planes and S of a call that ran on the device
 struct SgmStatsAcc {
+  SgmStatsAcc() = default;
+  explicit SgmStatsAcc(const SgmConst& k) : rows(k.rows), cols(k.cols), D(k.D), paths(k.paths) {}
   int on_device = 0, rows = 0, cols = 0, D = 0, paths = 0, tile_w = 0, tile_h = 0;
   int lines[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // lines launched per direction
   size_t o_census_left = 0, o_census_right = 0, o_S = 0, o_disparity = 0;
@@ -169,6 +171,8 @@ struct SgmStatsAcc {
 // what cvo_debug_dfilter_stats reports of the context's last disparity filter (cvo_dfilter.hip), and where it finds the maps
 // after each stage of a call that ran on the device (a stage that did not run: its input's)
 struct DFilterStatsAcc {
+  DFilterStatsAcc() = default;
+  explicit DFilterStatsAcc(const DFilterConst& k) : rows(k.rows), cols(k.cols) {}
   int on_device = 0, rows = 0, cols = 0, tile_w = 0, tile_h = 0;
   unsigned long long segments = 0, removed = 0, filled = 0;  // speckle: segments of valid pixels, valid pixels removed; gap: pixels filled
   size_t o_speckle = 0, o_gap = 0, o_tmp = 0;

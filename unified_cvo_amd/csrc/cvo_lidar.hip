@@ -12,7 +12,7 @@ namespace {
 // (profiles/lidar/crossover.txt)
 constexpr int LIDAR_HOST_BELOW = 12000;
 
-bool lidar_on_host(const cvo_ctx* ctx, int n) { return ctx->opt.lidar_host > 0 || (ctx->opt.lidar_host < 0 && n < LIDAR_HOST_BELOW); }
+bool lidar_on_host(const cvo_ctx* ctx, int n) { return route_on_host(ctx->opt.lidar_host, n, LIDAR_HOST_BELOW); }
 
 // ---- glibc's TYPE_3 random(): r[i] += r[i - 3] over 31 words, the result without its lowest bit ----
 unsigned lidar_rand_next(cvo_lidar_rand_t* s) {
@@ -484,11 +484,31 @@ void lidar_copy_out(const std::vector<int>& index, const std::vector<unsigned ch
   if (n) *n = (int)index.size();
 }
 
+// the refusals every entry point shares (a twin, ctx == nullptr, stores no text)
 int lidar_check(cvo_ctx* ctx, const char* who, const cvo_lidar_scan_t* scan, const cvo_lidar_config_t* cfg, const cvo_lidar_rand_t* rand) {
   std::string msg;
   const int rc = lidar_validate(scan, cfg, rand, &msg);
-  if (rc != CVO_OK && ctx) return fail(ctx, rc, std::string(who) + ": " + msg);
-  return rc;
+  return rc != CVO_OK ? fail(ctx, rc, std::string(who) + ": " + msg) : rc;
+}
+
+// the body of cvo_lidar_select_host and cvo_lidar_select; *rand moves on only when the call succeeds
+int lidar_select_entry(cvo_ctx* ctx, const char* who, const cvo_lidar_scan_t* scan, const cvo_lidar_config_t* cfg, cvo_lidar_rand_t* rand, int* index,
+                       unsigned char* is_edge, int* n) {
+  const int rc = lidar_check(ctx, who, scan, cfg, rand);
+  if (rc != CVO_OK) return rc;
+  if (!index || !n) return fail(ctx, CVO_E_INVALID, std::string(who) + ": index and n are required");
+  return frontend_call(ctx, who, [&] {
+    std::vector<int> idx;
+    std::vector<unsigned char> edge;
+    LidarStatsAcc st;
+    cvo_lidar_rand_t r = *rand;
+    const int rc = lidar_select_any(ctx, *scan, *cfg, &r, idx, edge, st);
+    if (rc != CVO_OK) return rc;
+    *rand = r;
+    lidar_copy_out(idx, edge, index, is_edge, n);
+    if (ctx) ctx->lidar_last = st;
+    return CVO_OK;
+  });
 }
 
 }  // namespace
@@ -532,40 +552,13 @@ unsigned int cvo_lidar_rand_next(cvo_lidar_rand_t* state) {
 }
 
 int cvo_lidar_select_host(const cvo_lidar_scan_t* scan, const cvo_lidar_config_t* cfg, cvo_lidar_rand_t* rand, int* index, unsigned char* is_edge, int* n) {
-  const int rc = lidar_check(nullptr, "", scan, cfg, rand);
-  if (rc != CVO_OK) return rc;
-  if (!index || !n) return CVO_E_INVALID;
-  return frontend_call(nullptr, "", [&] {
-    std::vector<int> idx;
-    std::vector<unsigned char> edge;
-    LidarStatsAcc st;
-    cvo_lidar_rand_t r = *rand;
-    const int rc = lidar_select_any(nullptr, *scan, *cfg, &r, idx, edge, st);
-    if (rc != CVO_OK) return rc;
-    *rand = r;
-    lidar_copy_out(idx, edge, index, is_edge, n);
-    return CVO_OK;
-  });
+  return lidar_select_entry(nullptr, "cvo_lidar_select_host", scan, cfg, rand, index, is_edge, n);
 }
 
 int cvo_lidar_select(cvo_ctx* ctx, const cvo_lidar_scan_t* scan, const cvo_lidar_config_t* cfg, cvo_lidar_rand_t* rand, int* index, unsigned char* is_edge,
                      int* n) {
   if (!ctx) return CVO_E_INVALID;
-  const int rc = lidar_check(ctx, "cvo_lidar_select", scan, cfg, rand);
-  if (rc != CVO_OK) return rc;
-  if (!index || !n) return fail(ctx, CVO_E_INVALID, "cvo_lidar_select: index and n are required");
-  return frontend_call(ctx, "cvo_lidar_select", [&] {
-    std::vector<int> idx;
-    std::vector<unsigned char> edge;
-    LidarStatsAcc st;
-    cvo_lidar_rand_t r = *rand;
-    const int rc = lidar_select_any(ctx, *scan, *cfg, &r, idx, edge, st);
-    if (rc != CVO_OK) return rc;
-    *rand = r;
-    lidar_copy_out(idx, edge, index, is_edge, n);
-    ctx->lidar_last = st;
-    return CVO_OK;
-  });
+  return lidar_select_entry(ctx, "cvo_lidar_select", scan, cfg, rand, index, is_edge, n);
 }
 
 int cvo_cloud_upload_lidar(cvo_ctx* ctx, const cvo_lidar_scan_t* scan, const cvo_lidar_config_t* cfg, cvo_lidar_rand_t* rand, cvo_cloud** out, int* index,

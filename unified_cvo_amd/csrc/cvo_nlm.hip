@@ -9,7 +9,7 @@ namespace {
 // pixels; below, the CPU twin is the default route (profiles/nlm/crossover.txt)
 constexpr int NLM_HOST_BELOW = 256;
 
-bool nlm_on_host(const cvo_ctx* ctx, long long np) { return ctx->opt.nlm_host > 0 || (ctx->opt.nlm_host < 0 && np < NLM_HOST_BELOW); }
+bool nlm_on_host(const cvo_ctx* ctx, long long np) { return route_on_host(ctx->opt.nlm_host, np, NLM_HOST_BELOW); }
 
 struct NlmTable {
   int th = 0, sh = 0, mult = 0, shift = 0, n_table = 0, n_nonzero = 0;

@@ -394,9 +394,7 @@ int rgbd_points_device(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, int method, std:
   return rgbd_fetch(ctx, d.pix, kept, pix);
 }
 
-bool rgbd_on_host(const cvo_ctx* ctx, const cvo_rgbd_frame_t& f) {
-  return ctx->opt.rgbd_host > 0 || (ctx->opt.rgbd_host < 0 && (long long)f.cols * f.rows < RGBD_HOST_BELOW);
-}
+bool rgbd_on_host(const cvo_ctx* ctx, const cvo_rgbd_frame_t& f) { return route_on_host(ctx->opt.rgbd_host, (long long)f.cols * f.rows, RGBD_HOST_BELOW); }
 
 // The drivers' per-frame recipe for either frame type: both candidate sets - edges, then FULL - through the voxel grid
 // (leaf / divisor for the edges); pixel indices of the survivors, edge first, n_edge of them edges, and - xyz != nullptr, host
@@ -473,30 +471,9 @@ int rgbd_recipe_pixels(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t& f,
       });
 }
 
-}  // namespace
-
-extern "C" {
-
-int cvo_rgbd_points_host(const cvo_rgbd_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat, float* label, float* geotype) {
-  std::string msg;
-  int rc = rgbd_validate(frame, &msg);
-  if (rc == CVO_OK) rc = rgbd_method(method, &msg);
-  if (rc == CVO_OK && method == CVO_SELECT_DSO_EDGES) rc = rgbd_threshold_range(frame->cols, frame->rows, &msg);
-  if (rc != CVO_OK) return rc;
-  if (!pixel || !n) return CVO_E_INVALID;
-  return frontend_call(nullptr, "", [&] {
-    std::vector<int> pix;
-    RgbdStatsAcc st;
-    rgbd_candidates_cpu(*frame, method, pix, st);
-    rgbd_point_rows(*frame, method, pix, xyz, feat, label, geotype);
-    copy_kept(pix, pixel, n);
-    return CVO_OK;
-  });
-}
-
-int cvo_rgbd_points(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat, float* label,
-                    float* geotype) {
-  if (!ctx) return CVO_E_INVALID;
+// the body of cvo_rgbd_points_host and cvo_rgbd_points
+int rgbd_points_entry(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat,
+                      float* label, float* geotype) {
   std::string msg;
   int rc = rgbd_validate(frame, &msg);
   if (rc == CVO_OK) rc = rgbd_method(method, &msg);
@@ -505,11 +482,11 @@ int cvo_rgbd_points(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, int method, int
     rc = CVO_E_INVALID;
     msg = "pixel and n are required";
   }
-  if (rc != CVO_OK) return fail(ctx, rc, "cvo_rgbd_points: " + msg);
-  return frontend_call(ctx, "cvo_rgbd_points", [&] {
+  if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
+  return frontend_call(ctx, who, [&] {
     std::vector<int> pix;
     RgbdStatsAcc st;
-    if (rgbd_on_host(ctx, *frame)) {
+    if (!ctx || rgbd_on_host(ctx, *frame)) {
       rgbd_candidates_cpu(*frame, method, pix, st);
     } else {
       st.on_device = 1;
@@ -518,9 +495,23 @@ int cvo_rgbd_points(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, int method, int
     }
     rgbd_point_rows(*frame, method, pix, xyz, feat, label, geotype);
     copy_kept(pix, pixel, n);
-    ctx->rgbd_last = st;
+    if (ctx) ctx->rgbd_last = st;
     return CVO_OK;
   });
+}
+
+}  // namespace
+
+extern "C" {
+
+int cvo_rgbd_points_host(const cvo_rgbd_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat, float* label, float* geotype) {
+  return rgbd_points_entry(nullptr, "cvo_rgbd_points_host", frame, method, pixel, n, xyz, feat, label, geotype);
+}
+
+int cvo_rgbd_points(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat, float* label,
+                    float* geotype) {
+  if (!ctx) return CVO_E_INVALID;
+  return rgbd_points_entry(ctx, "cvo_rgbd_points", frame, method, pixel, n, xyz, feat, label, geotype);
 }
 
 int cvo_cloud_upload_rgbd(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, float leaf, float edge_divisor, cvo_cloud** out, int* pixel,

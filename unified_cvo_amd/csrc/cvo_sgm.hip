@@ -1,19 +1,27 @@
-// cvo_sgm.hip -- the stereo matcher: cvo_stereo_disparity(_host) (left + right gray planes to the float left disparity the
-// stereo front end reads, invalid = -10), cvo_cloud_upload_stereo_pair (the matcher, then cvo_cloud_upload_stereo as it is),
-// cvo_debug_sgm_stats and cvo_debug_sgm_readback.  Semi-global matching over a 9 x 7 census cost - the project's OWN matcher,
-// not upstream's libelas (StaticStereo::disparity) and not any other SGM implementation; tests/np_sgm.py states what is
-// computed.  The CPU twin (sgm_cpu) walks the same lines (sgm_line) with the same arithmetic (cvo_sgm_math.h) as the kernels
-// of cvo_k_sgm.h, one after the other.  A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.
+// cvo_sgm.hip -- the stereo matcher (left + right gray planes to the float left disparity the stereo front end reads, invalid
+// = -10): its refusals, its two routes, cvo_debug_sgm_stats and cvo_debug_sgm_readback; its entry points, cvo_stereo_disparity
+// (_host), are in cvo_stereo_pair.hip with the chains that run it.  Semi-global matching over a 9 x 7 census cost - the
+// project's OWN matcher, not upstream's libelas (StaticStereo::disparity) and not any other SGM implementation; tests/np_sgm.py
+// states what is computed.  The CPU twin (sgm_cpu) walks the same lines (sgm_line) with the same arithmetic (cvo_sgm_math.h)
+// as the kernels of cvo_k_sgm.h, one after the other.  A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.
 namespace {
 
 // pixels; below, the CPU twin is the default route (profiles/sgm/crossover.txt)
 constexpr int SGM_HOST_BELOW = 128;
 constexpr long long SGM_MAX_PIXELS = 1ll << 24, SGM_MAX_WORKSPACE = 1ll << 31;
 
-bool sgm_on_host(const cvo_ctx* ctx, long long np) { return ctx->opt.sgm_host > 0 || (ctx->opt.sgm_host < 0 && np < SGM_HOST_BELOW); }
+bool sgm_on_host(const cvo_ctx* ctx, long long np) { return route_on_host(ctx->opt.sgm_host, np, SGM_HOST_BELOW); }
 
-int sgm_validate(int rows, int cols, const void* left, const void* right, const cvo_sgm_config_t* cfg, const void* out, std::string* msg) {
-  if (!left || !right || !cfg || !out) return *msg = "a required pointer is missing", CVO_E_INVALID;
+// The matcher's refusals in two parts (a chain that makes the map itself has no pointer to it): the planes and the map ...
+int sgm_validate_pointers(std::initializer_list<const void*> required, std::string* msg) {
+  for (const void* p : required)
+    if (!p) return *msg = "a required pointer is missing", CVO_E_INVALID;
+  return CVO_OK;
+}
+
+// ... and the configuration with the sizes it admits
+int sgm_validate_config(int rows, int cols, const cvo_sgm_config_t* cfg, std::string* msg) {
+  if (!cfg) return *msg = "a required pointer is missing", CVO_E_INVALID;
   if (rows < 1 || cols < 1) return *msg = "rows and cols start at 1", CVO_E_INVALID;
   if (cfg->max_disparity != 64 && cfg->max_disparity != 128 && cfg->max_disparity != 256)
     return *msg = "max_disparity must be 64, 128 or 256, got " + std::to_string(cfg->max_disparity), CVO_E_INVALID;
@@ -209,63 +217,6 @@ int sgm_device(cvo_ctx* ctx, const SgmConst& k, const unsigned char* left, const
   return CVO_OK;
 }
 
-// the body of both entry points: ctx == nullptr is the twin without a context
-int sgm_disparity(cvo_ctx* ctx, const char* who, int rows, int cols, const uint8_t* left, const uint8_t* right, const cvo_sgm_config_t* cfg,
-                  float* disparity) {
-  std::string msg;
-  const int rc = sgm_validate(rows, cols, left, right, cfg, disparity, &msg);
-  if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
-  return frontend_call(ctx, who, [&] {
-    const SgmConst k = sgm_const(rows, cols, *cfg);
-    SgmStatsAcc stats;
-    stats.rows = rows;
-    stats.cols = cols;
-    stats.D = k.D;
-    stats.paths = k.paths;
-    if (!ctx || sgm_on_host(ctx, (long long)rows * cols)) {
-      std::vector<float> out((size_t)rows * cols);
-      sgm_cpu(k, left, right, out.data());
-      std::memcpy(disparity, out.data(), sizeof(float) * out.size());
-    } else {
-      stats.on_device = 1;
-      const int rc = sgm_device(ctx, k, left, right, disparity, stats);
-      if (rc != CVO_OK) return rc;
-    }
-    if (ctx) ctx->sgm_last = stats;
-    return CVO_OK;
-  });
-}
-
-// cvo_cloud_upload_stereo_pair and its _filtered form (cvo_dfilter.hip): match(rows, cols, left, disparity) makes the map
-template <class Match>
-int upload_stereo_pair(cvo_ctx* ctx, const char* who, const cvo_stereo_frame_t* frame, const uint8_t* right_gray, const cvo_sgm_config_t* cfg, int method,
-                       cvo_cloud** out, int* pixel, int* n, Match match) {
-  if (!frame || !out) return fail(ctx, CVO_E_INVALID, std::string(who) + ": frame and out are required");
-  std::string msg;
-  float placeholder = 0.f;  // (the matcher's refusals come first; they do not look at the map)
-  int rc = sgm_validate(frame->rows, frame->cols, frame->image, right_gray, cfg, &placeholder, &msg);
-  if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
-  try {
-    const size_t np = (size_t)frame->rows * frame->cols;
-    std::vector<float> disparity(np);
-    cvo_stereo_frame_t f = *frame;
-    f.disparity = disparity.data();
-    if ((rc = stereo_check(ctx, who, &f, &method, &msg)) != CVO_OK) return rc;
-    // the left plane: the frame's gray plane, or the gray the front end itself takes of the image
-    std::vector<uint8_t> gray;
-    const uint8_t* left = f.gray ? f.gray : f.image;
-    if (!f.gray && f.channels != 1) {
-      gray.resize(np);
-      for (size_t p = 0; p < np; p++) gray[p] = (uint8_t)rgbd_gray(f.image, f.channels, p);
-      left = gray.data();
-    }
-    if ((rc = match(f.rows, f.cols, left, disparity.data())) != CVO_OK) return rc;
-    return cvo_cloud_upload_stereo(ctx, &f, method, out, pixel, n);
-  } catch (const std::exception& e) {
-    return fail(ctx, CVO_E_NOMEM, std::string(who) + ": " + e.what());
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -278,23 +229,6 @@ void cvo_sgm_config_default(cvo_sgm_config_t* cfg) {
   cfg->uniqueness = 5;
   cfg->lr_max_diff = 1;
   cfg->paths = 8;
-}
-
-int cvo_stereo_disparity_host(int rows, int cols, const uint8_t* left, const uint8_t* right, const cvo_sgm_config_t* cfg, float* disparity) {
-  return sgm_disparity(nullptr, "cvo_stereo_disparity_host", rows, cols, left, right, cfg, disparity);
-}
-
-int cvo_stereo_disparity(cvo_ctx* ctx, int rows, int cols, const uint8_t* left, const uint8_t* right, const cvo_sgm_config_t* cfg,
-                         float* disparity) {
-  if (!ctx) return CVO_E_INVALID;
-  return sgm_disparity(ctx, "cvo_stereo_disparity", rows, cols, left, right, cfg, disparity);
-}
-
-int cvo_cloud_upload_stereo_pair(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, const uint8_t* right_gray, const cvo_sgm_config_t* cfg, int method,
-                                 cvo_cloud** out, int* pixel, int* n) {
-  if (!ctx) return CVO_E_INVALID;
-  return upload_stereo_pair(ctx, "cvo_cloud_upload_stereo_pair", frame, right_gray, cfg, method, out, pixel, n,
-                            [&](int rows, int cols, const uint8_t* left, float* disparity) { return cvo_stereo_disparity(ctx, rows, cols, left, right_gray, cfg, disparity); });
 }
 
 int cvo_debug_sgm_stats(cvo_ctx* ctx, int* on_device, int* max_disparity, int* paths, int* lines, int* rows, int* cols, int* tile_w, int* tile_h) {

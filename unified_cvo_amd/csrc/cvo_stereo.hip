@@ -1,6 +1,7 @@
 // cvo_stereo.hip -- stereo front end: cvo_stereo_points (CvoPointCloud(ImageStereo, Calibration, CV_FAST / DSO_EDGES / FULL)
 // from a GIVEN disparity map: libelas is not part of this library), cvo_stereo_points_host (the same on one CPU thread, no
-// context), cvo_cloud_upload_stereo (the pairwise KITTI driver's cloud: those rows through the ordinary upload),
+// context), cvo_cloud_upload_stereo (the pairwise KITTI driver's cloud: those rows through the ordinary upload; its locked
+// body, stereo_upload_locked, is also the last stage of the pair chain of cvo_stereo_pair.hip),
 // cvo_cloud_upload_stereo_recipe (the multi-frame KITTI driver's per-frame block, main_multi_frame_irls_kitti.cpp:235-292),
 // cvo_debug_stereo_stats.  The candidates come from cvo_fast.hip (CV_FAST) and the RGB-D section (DSO_EDGES, FULL), features,
 // labels, recipe rows and the voxel passes are the RGB-D section's; what is new here is the keep predicate and the
@@ -8,14 +9,15 @@
 // come back.  A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.
 namespace {
 
-int stereo_validate(const cvo_stereo_frame_t* f, std::string* msg) {
+// map_given false: the pair chain (cvo_stereo_pair.hip), which makes the disparity itself
+int stereo_validate(const cvo_stereo_frame_t* f, bool map_given, std::string* msg) {
   if (!f) {
     *msg = "frame is NULL";
     return CVO_E_INVALID;
   }
   auto usable = [](float v) { return std::isfinite(v) && v != 0.f; };
   return frame_validate(f->rows, f->cols, f->channels, f->image, f->num_classes, f->semantic, msg, [&]() -> std::string {
-    if (!f->disparity) return "disparity is NULL";
+    if (map_given && !f->disparity) return "disparity is NULL";
     if (!usable(f->fx) || !usable(f->fy)) return "fx and fy must be finite and not 0, got " + std::to_string(f->fx) + ", " + std::to_string(f->fy);
     if (!usable(f->baseline)) return "baseline must be finite and not 0, got " + std::to_string(f->baseline);
     return "";
@@ -148,9 +150,9 @@ int stereo_points_device(cvo_ctx* ctx, const cvo_stereo_frame_t& f, int method, 
   return CVO_OK;
 }
 
-// the constructor's points by the context's route
+// the constructor's points by the context's route (ctx == nullptr: the twin)
 int stereo_points_any(cvo_ctx* ctx, const cvo_stereo_frame_t& f, int method, std::vector<int>& pix, std::vector<float>& xyz, StereoStatsAcc& st) {
-  if (stereo_on_host(ctx, f.rows, f.cols)) {
+  if (!ctx || stereo_on_host(ctx, f.rows, f.cols)) {
     stereo_points_cpu(f, method, pix, xyz, st);
     return CVO_OK;
   }
@@ -187,45 +189,23 @@ int stereo_recipe_pixels(cvo_ctx* ctx, const char* who, const cvo_stereo_frame_t
   return CVO_OK;
 }
 
-// the refusals every entry point shares (method nullptr: the recipe, which runs DSO_EDGES and FULL)
-int stereo_check(cvo_ctx* ctx, const char* who, const cvo_stereo_frame_t* frame, const int* method, std::string* msg) {
+// the refusals every entry point shares (method nullptr: the recipe, which runs DSO_EDGES and FULL; a twin stores no text)
+int stereo_check(cvo_ctx* ctx, const char* who, const cvo_stereo_frame_t* frame, const int* method, bool map_given = true) {
   const bool dso = !method || *method == CVO_SELECT_DSO_EDGES;
-  int rc = stereo_validate(frame, msg);
-  if (rc == CVO_OK && method) rc = stereo_method(*method, msg);
-  if (rc == CVO_OK && dso) rc = rgbd_threshold_range(frame->cols, frame->rows, msg);
-  if (rc != CVO_OK && ctx) return fail(ctx, rc, std::string(who) + ": " + *msg);
-  return rc;
+  std::string msg;
+  int rc = stereo_validate(frame, map_given, &msg);
+  if (rc == CVO_OK && method) rc = stereo_method(*method, &msg);
+  if (rc == CVO_OK && dso) rc = rgbd_threshold_range(frame->cols, frame->rows, &msg);
+  return rc != CVO_OK ? fail(ctx, rc, std::string(who) + ": " + msg) : rc;
 }
 
-}  // namespace
-
-extern "C" {
-
-int cvo_stereo_points_host(const cvo_stereo_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat, float* label, float* geotype) {
-  std::string msg;
-  const int rc = stereo_check(nullptr, "", frame, &method, &msg);
+// the body of cvo_stereo_points_host and cvo_stereo_points
+int stereo_points_entry(cvo_ctx* ctx, const char* who, const cvo_stereo_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat,
+                        float* label, float* geotype) {
+  const int rc = stereo_check(ctx, who, frame, &method);
   if (rc != CVO_OK) return rc;
-  if (!pixel || !n) return CVO_E_INVALID;
-  return frontend_call(nullptr, "", [&] {
-    std::vector<int> pix;
-    std::vector<float> p3;
-    StereoStatsAcc st;
-    stereo_points_cpu(*frame, method, pix, p3, st);
-    rgbd_point_rows(stereo_view(*frame), method, pix, nullptr, feat, label, geotype);
-    if (xyz && !p3.empty()) std::memcpy(xyz, p3.data(), sizeof(float) * p3.size());
-    copy_kept(pix, pixel, n);
-    return CVO_OK;
-  });
-}
-
-int cvo_stereo_points(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat, float* label,
-                      float* geotype) {
-  if (!ctx) return CVO_E_INVALID;
-  std::string msg;
-  const int rc = stereo_check(ctx, "cvo_stereo_points", frame, &method, &msg);
-  if (rc != CVO_OK) return rc;
-  if (!pixel || !n) return fail(ctx, CVO_E_INVALID, "cvo_stereo_points: pixel and n are required");
-  return frontend_call(ctx, "cvo_stereo_points", [&] {
+  if (!pixel || !n) return fail(ctx, CVO_E_INVALID, std::string(who) + ": pixel and n are required");
+  return frontend_call(ctx, who, [&] {
     std::vector<int> pix;
     std::vector<float> p3;
     StereoStatsAcc st;
@@ -234,47 +214,64 @@ int cvo_stereo_points(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, int method,
     rgbd_point_rows(stereo_view(*frame), method, pix, nullptr, feat, label, geotype);
     if (xyz && !p3.empty()) std::memcpy(xyz, p3.data(), sizeof(float) * p3.size());
     copy_kept(pix, pixel, n);
-    ctx->stereo_last = st;
+    if (ctx) ctx->stereo_last = st;
     return CVO_OK;
   });
 }
 
+// cvo_cloud_upload_stereo of a checked frame - and the last stage of the pair chain (cvo_stereo_pair.hip) -: the caller holds
+// upload_mutex
+int stereo_upload_locked(cvo_ctx* ctx, const cvo_stereo_frame_t& frame, int method, cvo_cloud** out, int* pixel, int* n) {
+  std::vector<int> pix;
+  std::vector<float> p3;
+  StereoStatsAcc st;
+  int rc = stereo_points_any(ctx, frame, method, pix, p3, st);
+  if (rc != CVO_OK) return rc;
+  // the rows as cvo_cloud_upload takes them: F = channels + 2 features zero-padded to FD, labels padded / cut to NC
+  const size_t np = pix.size(), F = (size_t)frame.channels + 2, C = (size_t)frame.num_classes;
+  std::vector<float> ft(F * np), lb(C * np), geo(2 * np), feat((size_t)FD * np, 0.f), label(C ? (size_t)NC * np : 0, 0.f);
+  rgbd_point_rows(stereo_view(frame), method, pix, nullptr, ft.data(), C ? lb.data() : nullptr, geo.data());
+  for (size_t i = 0; i < np; i++) {
+    std::memcpy(&feat[(size_t)FD * i], &ft[F * i], sizeof(float) * std::min(F, (size_t)FD));
+    if (C) std::memcpy(&label[(size_t)NC * i], &lb[C * i], sizeof(float) * std::min(C, (size_t)NC));
+  }
+  const HostCloud h{(int)np, (const char*)p3.data(), 12, (const char*)feat.data(), sizeof(float) * FD, C ? (const char*)label.data() : nullptr,
+                    sizeof(float) * NC, (const char*)geo.data(), 8};
+  if ((rc = upload_one_locked(ctx, h, out)) != CVO_OK) return rc;
+  copy_kept(pix, pixel, n);
+  ctx->stereo_last = st;
+  return CVO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cvo_stereo_points_host(const cvo_stereo_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat, float* label, float* geotype) {
+  return stereo_points_entry(nullptr, "cvo_stereo_points_host", frame, method, pixel, n, xyz, feat, label, geotype);
+}
+
+int cvo_stereo_points(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat, float* label,
+                      float* geotype) {
+  if (!ctx) return CVO_E_INVALID;
+  return stereo_points_entry(ctx, "cvo_stereo_points", frame, method, pixel, n, xyz, feat, label, geotype);
+}
+
 int cvo_cloud_upload_stereo(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, int method, cvo_cloud** out, int* pixel, int* n) {
   if (!ctx) return CVO_E_INVALID;
-  std::string msg;
-  const int rc = stereo_check(ctx, "cvo_cloud_upload_stereo", frame, &method, &msg);
+  const int rc = stereo_check(ctx, "cvo_cloud_upload_stereo", frame, &method);
   if (rc != CVO_OK) return rc;
   if (!out) return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_stereo: out is NULL");
-  return frontend_call(ctx, "cvo_cloud_upload_stereo", [&] {
-    std::vector<int> pix;
-    std::vector<float> p3;
-    StereoStatsAcc st;
-    int rc = stereo_points_any(ctx, *frame, method, pix, p3, st);
-    if (rc != CVO_OK) return rc;
-    // the rows as cvo_cloud_upload takes them: F = channels + 2 features zero-padded to FD, labels padded / cut to NC
-    const size_t np = pix.size(), F = (size_t)frame->channels + 2, C = (size_t)frame->num_classes;
-    std::vector<float> ft(F * np), lb(C * np), geo(2 * np), feat((size_t)FD * np, 0.f), label(C ? (size_t)NC * np : 0, 0.f);
-    rgbd_point_rows(stereo_view(*frame), method, pix, nullptr, ft.data(), C ? lb.data() : nullptr, geo.data());
-    for (size_t i = 0; i < np; i++) {
-      std::memcpy(&feat[(size_t)FD * i], &ft[F * i], sizeof(float) * std::min(F, (size_t)FD));
-      if (C) std::memcpy(&label[(size_t)NC * i], &lb[C * i], sizeof(float) * std::min(C, (size_t)NC));
-    }
-    const HostCloud h{(int)np, (const char*)p3.data(), 12, (const char*)feat.data(), sizeof(float) * FD, C ? (const char*)label.data() : nullptr,
-                      sizeof(float) * NC, (const char*)geo.data(), 8};
-    if ((rc = upload_one_locked(ctx, h, out)) != CVO_OK) return rc;
-    copy_kept(pix, pixel, n);
-    ctx->stereo_last = st;
-    return CVO_OK;
-  });
+  return frontend_call(ctx, "cvo_cloud_upload_stereo", [&] { return stereo_upload_locked(ctx, *frame, method, out, pixel, n); });
 }
 
 int cvo_cloud_upload_stereo_recipe(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, float leaf, float edge_divisor, cvo_cloud** out, int* pixel,
                                    unsigned char* is_edge, int* n) {
   if (!ctx) return CVO_E_INVALID;
-  std::string msg;
-  const int rc = stereo_check(ctx, "cvo_cloud_upload_stereo_recipe", frame, nullptr, &msg);
+  const int rc = stereo_check(ctx, "cvo_cloud_upload_stereo_recipe", frame, nullptr);
   if (rc != CVO_OK) return rc;
   if (!out) return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_stereo_recipe: out is NULL");
+  std::string msg;
   if (voxel_validate(0, nullptr, leaf, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_stereo_recipe: leaf: " + msg);
   if (!std::isfinite(edge_divisor) || !(edge_divisor > 0.f))
     return fail(ctx, CVO_E_INVALID, "cvo_cloud_upload_stereo_recipe: edge_divisor must be finite and > 0, got " + std::to_string(edge_divisor));

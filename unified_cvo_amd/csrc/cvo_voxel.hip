@@ -116,20 +116,34 @@ int voxel_run_device(cvo_ctx* ctx, int n, const float* xyz, const float* d_xyz_g
 // default route of small frames.  VOXEL_HOST=0 / 1 forces one route for every size.
 constexpr int VOX_HOST_BELOW = 4096;
 
-// Argument checks + the route the context's switches choose.  The caller holds upload_mutex.
+// Size checks + the route the context's switches choose (ctx == nullptr: the twin).  The caller holds upload_mutex.
 int voxel_select(cvo_ctx* ctx, const char* who, int n, const float* xyz, float s, std::vector<int>& kept) {
   if (n > VOX_MAX_POINTS) return fail(ctx, CVO_E_UNSUPPORTED, std::string(who) + ": more than 2^24 points");
   std::string msg;
   if (voxel_validate(0, nullptr, s, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": " + msg);
   kept.clear();
-  if (n == 0 || ctx->opt.voxel_host > 0 || (ctx->opt.voxel_host < 0 && n < VOX_HOST_BELOW)) {
+  if (!ctx || n == 0 || route_on_host(ctx->opt.voxel_host, n, VOX_HOST_BELOW)) {
     if (voxel_validate(n, xyz, s, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": " + msg);
     voxel_select_cpu(n, xyz, s, kept);
-    ctx->vox_capacity = 0;  // (no table: cvo_debug_voxel_stats reads zeros)
-    ctx->vox_last = VoxelCtl{};
+    if (ctx) {
+      ctx->vox_capacity = 0;  // (no table: cvo_debug_voxel_stats reads zeros)
+      ctx->vox_last = VoxelCtl{};
+    }
     return CVO_OK;
   }
   return voxel_run_device(ctx, n, xyz, nullptr, s, &kept, nullptr);
+}
+
+// the body of cvo_voxel_select_host and cvo_voxel_select: n and the pointers, then voxel_select's refusals
+int voxel_entry(cvo_ctx* ctx, const char* who, int n, const float* xyz, float voxel_size, int* kept, int* n_kept) {
+  if (n < 0 || (n > 0 && (!xyz || !kept)) || !n_kept) return fail(ctx, CVO_E_INVALID, std::string(who) + ": bad argument");
+  return frontend_call(ctx, who, [&] {
+    std::vector<int> k;
+    const int rc = voxel_select(ctx, who, n, xyz, voxel_size, k);
+    if (rc != CVO_OK) return rc;
+    copy_kept(k, kept, n_kept);
+    return CVO_OK;
+  });
 }
 
 }  // namespace
@@ -137,27 +151,12 @@ int voxel_select(cvo_ctx* ctx, const char* who, int n, const float* xyz, float s
 extern "C" {
 
 int cvo_voxel_select_host(int n, const float* xyz, float voxel_size, int* kept, int* n_kept) {
-  if (n < 0 || (n > 0 && (!xyz || !kept)) || !n_kept) return CVO_E_INVALID;
-  if (n > VOX_MAX_POINTS) return CVO_E_UNSUPPORTED;
-  return frontend_call(nullptr, "", [&] {
-    const int rc = voxel_validate(n, xyz, voxel_size, nullptr);
-    if (rc != CVO_OK) return rc;
-    std::vector<int> k;
-    voxel_select_cpu(n, xyz, voxel_size, k);
-    copy_kept(k, kept, n_kept);
-    return CVO_OK;
-  });
+  return voxel_entry(nullptr, "cvo_voxel_select_host", n, xyz, voxel_size, kept, n_kept);
 }
 
 int cvo_voxel_select(cvo_ctx* ctx, int n, const float* xyz, float voxel_size, int* kept, int* n_kept) {
-  if (!ctx || n < 0 || (n > 0 && (!xyz || !kept)) || !n_kept) return fail(ctx, CVO_E_INVALID, "cvo_voxel_select: bad argument");
-  return frontend_call(ctx, "cvo_voxel_select", [&] {
-    std::vector<int> k;
-    const int rc = voxel_select(ctx, "cvo_voxel_select", n, xyz, voxel_size, k);
-    if (rc != CVO_OK) return rc;
-    copy_kept(k, kept, n_kept);
-    return CVO_OK;
-  });
+  if (!ctx) return CVO_E_INVALID;
+  return voxel_entry(ctx, "cvo_voxel_select", n, xyz, voxel_size, kept, n_kept);
 }
 
 // Coordinates go to the device alone (12 bytes per point); the survivors' rows are gathered on the host straight into the
