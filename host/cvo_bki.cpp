@@ -1,0 +1,109 @@
+// semantic_bki::SemanticBKIOctoMap and cvo::CvoPointCloud(const SemanticBKIOctoMap*, num_classes) over cvo_map_* (include/cvo_hip.h),
+// and CvoGPU::map_open.
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "cvo/CvoGPU.hpp"
+#include "mapping/bkioctomap.h"
+
+namespace cvo {
+
+cvo_map* CvoGPU::map_open(const cvo_map_config_t& cfg, long long initial_voxels) const {
+  std::lock_guard<std::mutex> lk(call_mutex);
+  cvo_map* m = nullptr;
+  const int rc = cvo_map_open(ctx, &cfg, initial_voxels, &m);
+  if (rc != CVO_OK) throw std::invalid_argument(std::string("cvo_map_open: ") + cvo_last_error(ctx));
+  return m;
+}
+
+std::string CvoGPU::last_error() const { return cvo_last_error(ctx); }
+
+CvoPointCloud::CvoPointCloud(const semantic_bki::SemanticBKIOctoMap* map, const int num_classes) {
+  if (!map || num_classes != map->num_classes()) throw std::invalid_argument("CvoPointCloud(map, num_classes): the map has another number of classes");
+  num_classes_ = num_classes;
+  feature_dimensions_ = 5;
+  if (!map->handle()) return;  // (nothing inserted yet)
+  long long n = 0, occupied = 0;  // (the size is one counting pass over the table; the voxels are collected and sorted once, below)
+  if (cvo_map_size(map->handle(), nullptr, &occupied) != CVO_OK) throw std::runtime_error("cvo_map_size failed");
+  std::vector<float> xyz(3 * (size_t)occupied), feat(5 * (size_t)occupied), label((size_t)num_classes * occupied);
+  const int rc = map->on_host() ? cvo_map_cloud_host(map->handle(), occupied, xyz.data(), feat.data(), label.data(), &n)
+                                : cvo_map_cloud(map->handle(), occupied, xyz.data(), feat.data(), label.data(), &n, nullptr);
+  if (rc != CVO_OK) throw std::runtime_error("cvo_map_cloud failed (" + std::to_string(rc) + ")");
+  num_points_ = (int)n;
+  positions_.resize((size_t)n);
+  features_.resize((int)n, 5);
+  labels_.resize((int)n, num_classes);
+  geometric_types_.assign(2 * (size_t)n, 0.f);
+  for (long long i = 0; i < n; i++) {
+    positions_[(size_t)i] = Vec3f{{xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]}};
+    for (int c = 0; c < 5; c++) features_((int)i, c) = feat[5 * i + c];
+    for (int c = 0; c < num_classes; c++) labels_((int)i, c) = label[(size_t)num_classes * i + c];
+  }
+}
+
+}  // namespace cvo
+
+namespace semantic_bki {
+
+static cvo_map_config_t make_config(float resolution, unsigned short block_depth, int num_class, float sf2, float ell, float prior, float var_thresh,
+                                    float free_thresh, float occupied_thresh) {
+  cvo_map_config_t c;
+  cvo_map_config_default(&c);
+  c.resolution = resolution;
+  c.block_depth = block_depth;
+  c.num_classes = num_class - 1;
+  c.sf2 = sf2;
+  c.ell = ell;
+  c.prior = prior;
+  c.var_thresh = var_thresh;
+  c.free_thresh = free_thresh;
+  c.occupied_thresh = occupied_thresh;
+  if (block_depth != 1) throw std::invalid_argument("SemanticBKIOctoMap: only block_depth 1 is built");
+  if (num_class < 1 || num_class > 20) throw std::invalid_argument("SemanticBKIOctoMap: num_class lies in 1 .. 20");
+  return c;
+}
+
+SemanticBKIOctoMap::SemanticBKIOctoMap(float resolution, unsigned short block_depth, int num_class, float sf2, float ell, float prior, float var_thresh,
+                                       float free_thresh, float occupied_thresh)
+    : cfg_(make_config(resolution, block_depth, num_class, sf2, ell, prior, var_thresh, free_thresh, occupied_thresh)) {}
+
+SemanticBKIOctoMap::SemanticBKIOctoMap(const cvo::CvoGPU& gpu, float resolution, unsigned short block_depth, int num_class, float sf2, float ell,
+                                       float prior, float var_thresh, float free_thresh, float occupied_thresh)
+    : gpu_(&gpu), cfg_(make_config(resolution, block_depth, num_class, sf2, ell, prior, var_thresh, free_thresh, occupied_thresh)) {}
+
+SemanticBKIOctoMap::~SemanticBKIOctoMap() {
+  if (map_) cvo_map_close(map_);
+}
+
+void SemanticBKIOctoMap::insert_pointcloud_csm(const CVOPointCloud* cloud, const point3f& origin, float ds_resolution, float free_res, float max_range) {
+  if (!cloud) throw std::invalid_argument("insert_pointcloud_csm: no cloud");
+  if (!map_) {
+    cfg_.ds_resolution = ds_resolution;
+    cfg_.free_resolution = free_res;
+    cfg_.max_range = max_range;
+    if (gpu_) {
+      map_ = gpu_->map_open(cfg_);
+    } else if (cvo_map_open_host(&cfg_, &map_) != CVO_OK) {
+      throw std::invalid_argument("insert_pointcloud_csm: the library refused the map's configuration");
+    }
+  } else if (free_res != cfg_.free_resolution || max_range != cfg_.max_range) {
+    throw std::invalid_argument("insert_pointcloud_csm: free_res and max_range are fixed by the map's first insert");
+  }
+  const int n = cloud->num_points(), C = cfg_.num_classes;
+  if (C > 0 && cloud->num_classes() != C) throw std::invalid_argument("insert_pointcloud_csm: the cloud's label rows do not have the map's classes");
+  std::vector<float> xyz(3 * (size_t)n), feat, label((size_t)C * n);
+  if (cloud->feature_dimensions() == 5) feat.resize(5 * (size_t)n);
+  for (int i = 0; i < n; i++) {
+    for (int a = 0; a < 3; a++) xyz[3 * (size_t)i + a] = cloud->positions()[(size_t)i][a];
+    if (!feat.empty())
+      for (int c = 0; c < 5; c++) feat[5 * (size_t)i + c] = cloud->features()(i, c);
+    for (int c = 0; c < C; c++) label[(size_t)C * i + c] = cloud->labels()(i, c);
+  }
+  const float* f = feat.empty() ? nullptr : feat.data();
+  const float* l = C > 0 ? label.data() : nullptr;
+  const int rc = gpu_ ? cvo_map_insert(map_, n, xyz.data(), f, l, origin.data()) : cvo_map_insert_host(map_, n, xyz.data(), f, l, origin.data());
+  if (rc != CVO_OK) throw std::invalid_argument("insert_pointcloud_csm: " + (gpu_ ? gpu_->last_error() : "the library refused the cloud (" + std::to_string(rc) + ")"));
+}
+
+}  // namespace semantic_bki

@@ -200,6 +200,11 @@ class CvoGPU {
   void compute_association_gpu(const CvoPointCloud& source_points, const CvoPointCloud& target_points,
                                const Mat4f& T_target_frame_to_source_frame, const Mat3f& non_isotropic_kernel,
                                Association& association) const;
+  // New: a semantic voxel map on this object's context (cvo_map_open, include/cvo_hip.h; mapping/bkioctomap.h wraps it in upstream's
+  // names).  The caller closes it with cvo_map_close before this object goes.  Refusals throw std::invalid_argument.  last_error:
+  // cvo_last_error of the context.  Defined in host/cvo_bki.cpp.
+  cvo_map* map_open(const cvo_map_config_t& cfg, long long initial_voxels = 0) const;
+  std::string last_error() const;
 
  private:
   CvoParams params;

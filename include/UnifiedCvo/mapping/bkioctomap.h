@@ -1,0 +1,68 @@
+// The semantic voxel map behind upstream's names (mapping/bkioctomap.h, mapping/point3f.h), written afresh over the C-ABI of
+// include/cvo_hip.h (cvo_map_*): what the body of upstream's driver main_local_mapping.cpp uses -
+//   semantic_bki::SemanticBKIOctoMap map(resolution, block_depth, num_class + 1, sf2, ell, prior, var_thresh, free_thresh, occupied_thresh);
+//   map.insert_pointcloud_csm(&transformed_pc, origin, ds_resolution, free_resolution, max_range);
+//   cvo::CvoPointCloud cloud_out(&map, num_class);
+// block_depth 1 only (std::invalid_argument otherwise); tests/np_bki.py states what is computed.  Defined in host/cvo_bki.cpp.
+#pragma once
+#include <ostream>
+
+#include "cvo_hip.h"
+#include "utils/CvoPointCloud.hpp"
+
+namespace cvo {
+class CvoGPU;
+}
+
+namespace semantic_bki {
+
+// the subset of upstream's point3f the driver uses
+class point3f {
+ public:
+  point3f() : v_{0.f, 0.f, 0.f} {}
+  point3f(float x, float y, float z) : v_{x, y, z} {}
+  float& x() { return v_[0]; }
+  float& y() { return v_[1]; }
+  float& z() { return v_[2]; }
+  const float& x() const { return v_[0]; }
+  const float& y() const { return v_[1]; }
+  const float& z() const { return v_[2]; }
+  const float* data() const { return v_; }
+
+ private:
+  float v_[3];
+};
+inline std::ostream& operator<<(std::ostream& out, const point3f& p) { return out << "(" << p.x() << " " << p.y() << " " << p.z() << ")"; }
+
+typedef cvo::CvoPointCloud CVOPointCloud;
+
+class SemanticBKIOctoMap {
+ public:
+  // num_class counts the free class, as upstream: a cloud's label rows have num_class - 1 entries (num_class 1: clouds without labels).
+  // The map is the CPU twin's (one thread) ...
+  SemanticBKIOctoMap(float resolution, unsigned short block_depth, int num_class, float sf2, float ell, float prior, float var_thresh,
+                     float free_thresh, float occupied_thresh);
+  // ... or, new, lives on gpu's context (the switch BKI_HOST decides its side at the first insert)
+  SemanticBKIOctoMap(const cvo::CvoGPU& gpu, float resolution, unsigned short block_depth, int num_class, float sf2, float ell, float prior,
+                     float var_thresh, float free_thresh, float occupied_thresh);
+  ~SemanticBKIOctoMap();
+  SemanticBKIOctoMap(const SemanticBKIOctoMap&) = delete;
+  SemanticBKIOctoMap& operator=(const SemanticBKIOctoMap&) = delete;
+
+  // The cloud's points are in the map frame.  free_res and max_range belong to the map here: the first insert fixes them, a
+  // later insert with other values throws std::invalid_argument, as does anything the library refuses.  ds_resolution is
+  // accepted and unused, as upstream.
+  void insert_pointcloud_csm(const CVOPointCloud* cloud, const point3f& origin, float ds_resolution, float free_res, float max_range);
+
+  float get_resolution() const { return cfg_.resolution; }
+  int num_classes() const { return cfg_.num_classes; }  // of a label row
+  cvo_map* handle() const { return map_; }              // nullptr before the first insert
+  bool on_host() const { return gpu_ == nullptr; }
+
+ private:
+  const cvo::CvoGPU* gpu_ = nullptr;
+  cvo_map_config_t cfg_;
+  cvo_map* map_ = nullptr;
+};
+
+}  // namespace semantic_bki

@@ -22,6 +22,9 @@ class ImageRGBD;
 class ImageStereo;
 }  // namespace cvo
 struct cvo_lidar_rand_t;
+namespace semantic_bki {
+class SemanticBKIOctoMap;
+}
 namespace cvo {
 
 class CvoPointCloud {
@@ -69,6 +72,11 @@ class CvoPointCloud {
                 std::vector<int>* index = nullptr, cvo_lidar_rand_t* rand = nullptr);
   CvoPointCloud(const float* xyzi, int n, const std::vector<int>& semantic, int num_classes, int target_num_points, int beam_num,
                 PointSelectionMethod pt_selection_method = LOAM, std::vector<int>* index = nullptr, cvo_lidar_rand_t* rand = nullptr);
+
+  // upstream bkioctomap.cpp:22-78 (mapping/bkioctomap.h): the OCCUPIED voxels of a semantic voxel map - centre, fs / sum(ms[1:]),
+  // ms[1..] / sum(ms) -, here in ascending key order (cvo_map_cloud, include/cvo_hip.h); F = 5.  num_classes must be the map's;
+  // std::invalid_argument otherwise.  Defined in host/cvo_bki.cpp.
+  CvoPointCloud(const semantic_bki::SemanticBKIOctoMap* map, const int num_classes);
 
   static CvoPointCloud from_xyz(const float* xyz, int n);                                // type (1,0), F = 0
   static CvoPointCloud from_xyzrgb(const float* xyz, const unsigned char* rgb, int n);   // type (0,1), F = 5

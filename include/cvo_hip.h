@@ -497,6 +497,52 @@ int cvo_stereo_disparity_filtered(cvo_ctx* ctx, int rows, int cols, const uint8_
 int cvo_cloud_upload_stereo_pair_filtered(cvo_ctx* ctx, const cvo_stereo_frame_t* frame, const uint8_t* right_gray,
                                           const cvo_sgm_config_t* sgm_cfg, const cvo_dfilter_config_t* dfilter_cfg, int method,
                                           cvo_cloud** out, int* pixel, int* n);
+/* ---- semantic voxel map: posed clouds fused into a voxel map, its occupied voxels read out as a cloud.  It is upstream's
+ * bki_mapping_lib as its driver main_local_mapping.cpp uses it - semantic_bki::SemanticBKIOctoMap::insert_pointcloud_csm under the
+ * counting sensor model with free-space beam samples, block_depth 1, and CvoPointCloud(const SemanticBKIOctoMap*, num_classes).
+ * The statement is tests/np_bki.py; the CPU twin and the kernels of cvo_k_bki.h equal it bit for bit (shared arithmetic:
+ * cvo_bki_math.h).  Its choices where upstream's text pins nothing - feature rows summed in ascending hit index, the cloud in
+ * ascending key order - and its departures are listed there and in DESIGN.md section 4; parity with upstream's binary is
+ * unpinned.  num_classes = 0 is an extension: every hit is class 1 of a two-class map and the cloud has no label rows.
+ * A map of a context lives on ONE side, taken at its first insert and kept: switch BKI_HOST=1 / 0 the CPU twin (one thread) /
+ * the device; unset, a map whose first insert has fewer than 2129 training points takes the twin (measured: profiles/bki/bki_probe.txt).  Inserts and read-outs of a device map run on the
+ * context's upload stream, like a voxel selection; the table grows by itself (k_bki_rehash) before an insert could take it
+ * past half full.  Close every map before its context is destroyed.
+ * Refusals leave the map as it was.  CVO_E_INVALID: resolution or free_resolution not finite or <= 0, a threshold outside
+ * [0, 1], prior negative or not finite, num_classes outside 0 .. 19 (cvo_map_open); a coordinate or origin that is not finite,
+ * a hit, beam sample or origin whose block index leaves [1, 2^20 - 2] on an axis, label rows missing on a map with classes
+ * (insert; cvo_last_error names the hit).  CVO_E_UNSUPPORTED: block_depth != 1; 2^24 training points or more in one insert
+ * (hits kept, their beam samples, the origin); a hit with 65536 beam samples or more; a table beyond 2^30 slots. */
+typedef struct cvo_map cvo_map;
+typedef struct cvo_map_config_t {
+  float resolution;      /* voxel edge, > 0 */
+  int block_depth;       /* 1 */
+  int num_classes;       /* C: classes of a label row, 0 .. 19; the map has C + 1, class 0 = free space */
+  float sf2, ell;        /* accepted, change nothing (as upstream's counting sensor model) */
+  float prior;           /* ms of a new voxel, >= 0 */
+  float var_thresh;      /* accepted, changes nothing */
+  float free_thresh, occupied_thresh; /* in [0, 1] */
+  float ds_resolution;   /* accepted, changes nothing */
+  float free_resolution; /* distance between beam samples, > 0 */
+  float max_range;       /* > 0: hits farther from the origin are dropped; <= 0: off */
+} cvo_map_config_t;
+void cvo_map_config_default(cvo_map_config_t* cfg);   /* main_local_mapping.cpp: 0.05, 1, 0, 1, 1, 0, 1, 0.65, 0.9, -1, 1, -1 */
+int cvo_map_open(cvo_ctx* ctx, const cvo_map_config_t* cfg, long long initial_voxels, cvo_map** out);
+void cvo_map_close(cvo_map* map);
+/* n hits already in the map frame: xyz n x 3, feat n x 5 or NULL (zeros), label n x num_classes (NULL only with 0 classes) */
+int cvo_map_insert(cvo_map* map, int n, const float* xyz, const float* feat, const float* label, const float origin[3]);
+/* the rows moved by a 3x4 row-major pose as cvo_cloud_transformed moves them, the pose's translation as origin */
+int cvo_map_insert_posed(cvo_map* map, int n, const float* xyz, const float* feat, const float* label, const float pose12[12]);
+int cvo_map_size(cvo_map* map, long long* voxels, long long* occupied);   /* either pointer may be NULL; host maps too */
+/* The OCCUPIED voxels in ascending key order: *n rows; xyz / feat / label (n x 3 / 5 / num_classes, each optional) are written
+ * when capacity >= *n (CVO_E_INVALID otherwise, *n set).  resident != NULL: the cloud cvo_cloud_upload makes of exactly those
+ * rows (label rows of fewer than 19 classes followed by zeros), to align a new frame against. */
+int cvo_map_cloud(cvo_map* map, long long capacity, float* xyz, float* feat, float* label, long long* n, cvo_cloud** resident);
+/* the CPU twin on a map without a context */
+int cvo_map_open_host(const cvo_map_config_t* cfg, cvo_map** out);
+void cvo_map_close_host(cvo_map* map);
+int cvo_map_insert_host(cvo_map* map, int n, const float* xyz, const float* feat, const float* label, const float origin[3]);
+int cvo_map_cloud_host(cvo_map* map, long long capacity, float* xyz, float* feat, float* label, long long* n);
 int cvo_cloud_size(const cvo_cloud* c);
 void cvo_cloud_free(cvo_cloud* c);
 

@@ -140,6 +140,12 @@ int cvo_debug_sgm_readback(cvo_ctx* ctx, unsigned long long* census_left, unsign
 int cvo_debug_dfilter_stats(cvo_ctx* ctx, int* on_device, int* rows, int* cols, int* tile_w, int* tile_h,
                             unsigned long long* counts /* 3 */, float* after_speckle, float* after_gap, float* mean_tmp);
 
+/* The last insert of a map (either kind): on_device; counts[8] = training points, block memberships, the longest run of hits in
+ * one voxel, the table's capacity (slots of a device map; voxels of a host map), growths of the table so far, the longest probe
+ * of that insert, voxels stored, classes of the map.  keys / ms / fs (capacity x 1 / classes / 5, each optional): the raw
+ * table, ~0 the key of a free slot, so that a test can name the first voxel that differs from the statement. */
+int cvo_debug_map_stats(cvo_map* map, int* on_device, unsigned long long* counts /* 8 */, unsigned long long* keys, float* ms, float* fs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -251,6 +251,12 @@ class cvo_dfilter_config_t(C.Structure):
     _fields_ = [("speckle_sim_threshold", C.c_float), ("speckle_size", C.c_int), ("ipol_gap_width", C.c_int), ("adaptive_mean", C.c_int)]
 
 
+class cvo_map_config_t(C.Structure):
+    _fields_ = [("resolution", C.c_float), ("block_depth", C.c_int), ("num_classes", C.c_int), ("sf2", C.c_float), ("ell", C.c_float),
+                ("prior", C.c_float), ("var_thresh", C.c_float), ("free_thresh", C.c_float), ("occupied_thresh", C.c_float),
+                ("ds_resolution", C.c_float), ("free_resolution", C.c_float), ("max_range", C.c_float)]
+
+
 CVO_DEPTH_U16, CVO_DEPTH_F32 = 0, 1
 CVO_SELECT_CV_FAST, CVO_SELECT_DSO_EDGES, CVO_SELECT_FULL = 0, 2, 8
 CVO_FAST_RGBD, CVO_FAST_STEREO, CVO_FAST_STEREO_SEMANTIC = (9, 15000, 12000, 13), (4, 24000, 15000, 50), (4, 28000, 15000, 50)
@@ -281,6 +287,8 @@ EXPORTED = [
     "cvo_debug_sgm_readback",
     "cvo_dfilter_config_default", "cvo_disparity_filter_host", "cvo_disparity_filter", "cvo_stereo_disparity_filtered",
     "cvo_cloud_upload_stereo_pair_filtered", "cvo_debug_dfilter_stats",
+    "cvo_map_config_default", "cvo_map_open", "cvo_map_close", "cvo_map_insert", "cvo_map_insert_posed", "cvo_map_size", "cvo_map_cloud",
+    "cvo_map_open_host", "cvo_map_close_host", "cvo_map_insert_host", "cvo_map_cloud_host", "cvo_debug_map_stats",
 ]
 
 _libs = {}
@@ -423,6 +431,22 @@ def lib(path=None):
     L.cvo_stereo_disparity_filtered.argtypes = [vp, ip, ip, bp, bp, sc, dc, fp]
     L.cvo_cloud_upload_stereo_pair_filtered.argtypes = [vp, C.POINTER(cvo_stereo_frame_t), bp, sc, dc, ip, C.POINTER(vp), ipp, ipp]
     L.cvo_debug_dfilter_stats.argtypes = [vp] + [ipp] * 5 + [C.POINTER(C.c_ulonglong), fp, fp, fp]
+    mc, ll, llp = C.POINTER(cvo_map_config_t), C.c_longlong, C.POINTER(C.c_longlong)
+    L.cvo_map_config_default.argtypes = [mc]
+    L.cvo_map_config_default.restype = None
+    L.cvo_map_open.argtypes = [vp, mc, ll, C.POINTER(vp)]
+    L.cvo_map_open_host.argtypes = [mc, C.POINTER(vp)]
+    L.cvo_map_close.argtypes = [vp]
+    L.cvo_map_close.restype = None
+    L.cvo_map_close_host.argtypes = [vp]
+    L.cvo_map_close_host.restype = None
+    L.cvo_map_insert.argtypes = [vp, ip, fp, fp, fp, fp]
+    L.cvo_map_insert_host.argtypes = [vp, ip, fp, fp, fp, fp]
+    L.cvo_map_insert_posed.argtypes = [vp, ip, fp, fp, fp, fp]
+    L.cvo_map_size.argtypes = [vp, llp, llp]
+    L.cvo_map_cloud.argtypes = [vp, ll, fp, fp, fp, llp, C.POINTER(vp)]
+    L.cvo_map_cloud_host.argtypes = [vp, ll, fp, fp, fp, llp]
+    L.cvo_debug_map_stats.argtypes = [vp, ipp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), fp, fp]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

@@ -584,6 +584,159 @@ class DeviceCloudAoS(DeviceCloud):
         self.handle = h
 
 
+class MapConfig:
+    """cvo_map_config_t: the semantic voxel map's configuration; the defaults are those of upstream's driver
+    main_local_mapping.cpp.  sf2, ell, var_thresh and ds_resolution are accepted and change nothing, as upstream."""
+
+    FIELDS = ("resolution", "block_depth", "num_classes", "sf2", "ell", "prior", "var_thresh", "free_thresh", "occupied_thresh",
+              "ds_resolution", "free_resolution", "max_range")
+
+    def __init__(self, resolution=0.05, block_depth=1, num_classes=0, sf2=1.0, ell=1.0, prior=0.0, var_thresh=1.0, free_thresh=0.65,
+                 occupied_thresh=0.9, ds_resolution=-1.0, free_resolution=1.0, max_range=-1.0):
+        self.resolution, self.block_depth, self.num_classes = float(resolution), int(block_depth), int(num_classes)
+        self.sf2, self.ell, self.prior, self.var_thresh = float(sf2), float(ell), float(prior), float(var_thresh)
+        self.free_thresh, self.occupied_thresh = float(free_thresh), float(occupied_thresh)
+        self.ds_resolution, self.free_resolution, self.max_range = float(ds_resolution), float(free_resolution), float(max_range)
+
+    def c_struct(self):
+        return _capi.cvo_map_config_t(*[getattr(self, f) for f in self.FIELDS])
+
+
+def _map_rows(pc_or_rows, num_classes):
+    """(xyz, feat or None, label or None) float32 rows of a CvoPointCloud or of a tuple (xyz[, feat[, label]])."""
+    if isinstance(pc_or_rows, CvoPointCloud):
+        pc = pc_or_rows
+        rows = (pc.positions_, pc.features_ if pc.feature_dimensions_ == 5 else None, pc.labels_ if pc.num_classes_ else None)
+    else:
+        rows = tuple(pc_or_rows) if isinstance(pc_or_rows, (tuple, list)) else (pc_or_rows,)
+        rows = rows + (None,) * (3 - len(rows))
+    xyz = np.ascontiguousarray(rows[0], np.float32).reshape(-1, 3)
+    feat = None if rows[1] is None else np.ascontiguousarray(rows[1], np.float32).reshape(-1, 5)
+    label = None if rows[2] is None or num_classes == 0 else np.ascontiguousarray(rows[2], np.float32).reshape(xyz.shape[0], -1)
+    if feat is not None and feat.shape[0] != xyz.shape[0]:
+        raise ValueError("feature rows and points differ in number")
+    if label is not None and label.shape[1] != num_classes:
+        raise ValueError(f"label rows have {label.shape[1]} classes, the map {num_classes}")
+    return xyz, feat, label
+
+
+class SemanticMap:
+    """cvo_map: a semantic voxel map (upstream's SemanticBKIOctoMap under its counting sensor model, block_depth 1;
+    tests/np_bki.py states it).  CvoGPU.map_open makes one on a context; SemanticMap(None, config) is the CPU twin's."""
+
+    def __init__(self, gpu, config=None, initial_voxels=0):
+        self.gpu, self.config = gpu, config or MapConfig()
+        self.L = gpu.L if gpu is not None else _capi.lib()
+        cfg, h = self.config.c_struct(), C.c_void_p()
+        if gpu is not None:
+            gpu._check(self.L.cvo_map_open(gpu.ctx, C.byref(cfg), int(initial_voxels), C.byref(h)))
+            gpu._maps.append(weakref.ref(self))
+        else:
+            rc = self.L.cvo_map_open_host(C.byref(cfg), C.byref(h))
+            if rc != 0:
+                _raise(rc, "cvo_map_open_host refused the configuration")
+        self.handle = h
+
+    def _check(self, rc, text):
+        if self.gpu is not None:
+            return self.gpu._check(rc)
+        if rc != 0:
+            _raise(rc, text)
+        return rc
+
+    def insert(self, pc_or_rows, origin=None, pose=None):
+        """cvo_map_insert(_host): the hits, already in the map frame, seen from `origin`; or cvo_map_insert_posed: the rows
+        moved by `pose` (3x4 or 4x4), its translation the origin."""
+        xyz, feat, label = _map_rows(pc_or_rows, self.config.num_classes)
+        if (origin is None) == (pose is None):
+            raise ValueError("give the origin or the pose")
+        if pose is not None:
+            if self.gpu is None:
+                raise ValueError("a host map takes rows in the map frame")
+            T = np.ascontiguousarray(np.asarray(pose, np.float32)[:3, :4])
+            return self._check(self.L.cvo_map_insert_posed(self.handle, xyz.shape[0], _fptr(xyz), _fptr(feat), _fptr(label), _fptr(T)), "")
+        o = np.ascontiguousarray(origin, np.float32).reshape(3)
+        call = self.L.cvo_map_insert if self.gpu is not None else self.L.cvo_map_insert_host
+        return self._check(call(self.handle, xyz.shape[0], _fptr(xyz), _fptr(feat), _fptr(label), _fptr(o)), "cvo_map_insert_host refused the hits")
+
+    def size(self):
+        """cvo_map_size -> (voxels stored, of them OCCUPIED)."""
+        v, o = C.c_longlong(), C.c_longlong()
+        self._check(self.L.cvo_map_size(self.handle, C.byref(v), C.byref(o)), "cvo_map_size failed")
+        return v.value, o.value
+
+    def cloud(self, resident=False):
+        """cvo_map_cloud(_host): the OCCUPIED voxels in ascending key order -> (xyz (n, 3), feat (n, 5), label (n, C)); with
+        resident=True also the DeviceCloud cvo_cloud_upload makes of those rows, as a fourth element."""
+        cap, C_ = self.size()[1], self.config.num_classes  # (one counting pass; the voxels are collected and sorted once, below)
+        xyz, feat, label = np.zeros((cap, 3), np.float32), np.zeros((cap, 5), np.float32), np.zeros((cap, C_), np.float32)
+        n = C.c_longlong()
+        lab = _fptr(label) if C_ else None
+        if self.gpu is None:
+            if resident:
+                raise ValueError("a host map has no resident cloud")
+            self._check(self.L.cvo_map_cloud_host(self.handle, cap, _fptr(xyz), _fptr(feat), lab, C.byref(n)), "cvo_map_cloud_host failed")
+            return xyz[:n.value], feat[:n.value], label[:n.value]
+        h = C.c_void_p()
+        self._check(self.L.cvo_map_cloud(self.handle, cap, _fptr(xyz), _fptr(feat), lab, C.byref(n), C.byref(h) if resident else None), "")
+        out = (xyz[:n.value], feat[:n.value], label[:n.value])
+        if not resident:
+            return out
+        dc = DeviceCloud.__new__(DeviceCloud)
+        dc.gpu, dc.n, dc._keep, dc.handle = self.gpu, int(n.value), None, h
+        return out + (dc,)
+
+    def debug_stats(self, readback=False):
+        """cvo_debug_map_stats of the last insert -> dict(on_device, training, members, longest_run, capacity, growths,
+        longest_probe, voxels, classes); readback=True adds the stored voxels sorted by key: keys (v,), ms (v, classes), fs (v, 5)."""
+        on, counts = C.c_int(), (C.c_ulonglong * 8)()
+        self._check(self.L.cvo_debug_map_stats(self.handle, C.byref(on), counts, None, None, None), "cvo_debug_map_stats failed")
+        names = ("training", "members", "longest_run", "capacity", "growths", "longest_probe", "voxels", "classes")
+        out = dict(on_device=on.value, **{k: int(v) for k, v in zip(names, counts)})
+        if readback:
+            cap, nc = max(out["capacity"], 1), out["classes"]
+            keys, ms, fs = np.full(cap, np.uint64(2**64 - 1), np.uint64), np.zeros((cap, nc), np.float32), np.zeros((cap, 5), np.float32)
+            self._check(self.L.cvo_debug_map_stats(self.handle, None, None, keys.ctypes.data_as(C.POINTER(C.c_ulonglong)), _fptr(ms), _fptr(fs)),
+                        "cvo_debug_map_stats failed")
+            live = np.flatnonzero(keys != np.uint64(2**64 - 1))
+            live = live[np.argsort(keys[live], kind="stable")]
+            out.update(keys=keys[live], ms=ms[live], fs=fs[live])
+        return out
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if self.gpu is None:
+                self.L.cvo_map_close_host(self.handle)
+            elif self.gpu.ctx:
+                self.L.cvo_map_close(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def map_open_host(config=None):
+    """cvo_map_open_host: a semantic voxel map of the CPU twin (one thread, no context)."""
+    return SemanticMap(None, config)
+
+
+def map_insert_host(smap, pc_or_rows, origin):
+    """cvo_map_insert_host on a map of map_open_host."""
+    return smap.insert(pc_or_rows, origin=origin)
+
+
+def map_cloud_host(smap):
+    """cvo_map_cloud_host on a map of map_open_host."""
+    return smap.cloud()
+
+
+def map_close_host(smap):
+    smap.close()
+
+
 # numpy view of pcl::PointSegmentedDistribution<5, 19> (PointSegmentedDistribution.hpp:17-99): byte offsets as laid out
 # by PCL_ADD_POINT4D / PCL_ADD_RGB and the member order, verified with a layout-identical struct (SURVEY.md 8(a) T1)
 CVO_POINT_DTYPE = np.dtype({
@@ -720,12 +873,17 @@ class CvoGPU:
             raise CvoError(f"cvo_ctx_create(device={device}) failed with {rc}: is a HIP GPU visible?")
         self.ctx = ctx
         self._queues = []  # weak references to the live BatchQueue objects (closed before the context goes)
+        self._maps = []    # ... and to the live SemanticMap objects
 
     def close(self):
         for w in list(getattr(self, "_queues", [])):
             q = w()
             if q is not None:
                 q.close()
+        for w in list(getattr(self, "_maps", [])):
+            m = w()
+            if m is not None:
+                m.close()
         if getattr(self, "ctx", None):
             self.L.cvo_ctx_destroy(self.ctx)
             self.ctx = None
@@ -756,6 +914,10 @@ class CvoGPU:
 
     def upload(self, pc):
         return DeviceCloud(self, pc)
+
+    def map_open(self, config=None, initial_voxels=0):
+        """cvo_map_open: a semantic voxel map on this context (MapConfig; initial_voxels sizes the first table)."""
+        return SemanticMap(self, config, initial_voxels)
 
     def _voxel_size(self, voxel_size):
         return float(self.params.multiframe_downsample_voxel_size if voxel_size is None else voxel_size)

@@ -1,0 +1,646 @@
+// cvo_bki.hip -- the semantic voxel map: cvo_map_open / _insert / _insert_posed / _size / _cloud / _close, their _host twins
+// on a map without a context, and cvo_debug_map_stats.  It is semantic_bki::SemanticBKIOctoMap::insert_pointcloud_csm at
+// block_depth 1 with the read-out of CvoPointCloud(const SemanticBKIOctoMap*, num_classes); tests/np_bki.py states what is
+// computed, the CPU twin (BkiHostMap) and the kernels of cvo_k_bki.h share cvo_bki_math.h.  A map lives on ONE side: a map
+// of a context takes its side at its first insert (switch BKI_HOST; unset: by that insert's training points) and keeps it,
+// its table does not migrate.  A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.
+#include <unordered_map>
+
+namespace {
+
+// training points of a map's FIRST insert below which the map lives on the host: the smallest frame whose ten inserts and
+// read-out took the device less time than the twin (profiles/bki/bki_probe.txt)
+constexpr long long BKI_HOST_BELOW = 2129;
+
+struct BkiStats {
+  int on_device = 0;
+  unsigned long long training = 0, members = 0, longest_run = 0, longest_probe = 0;
+};
+
+// ---- CPU twin: one thread ----
+struct BkiHostMap {
+  std::unordered_map<unsigned long long, unsigned> index;
+  std::vector<unsigned long long> keys;
+  std::vector<float> ms, fs;
+};
+
+struct BkiMember {
+  unsigned long long key;
+  int cls;  // 0: a beam sample or the origin
+  int hit;
+};
+
+}  // namespace
+
+struct cvo_map {
+  cvo_ctx* ctx = nullptr;  // nullptr: a host-only map
+  cvo_map_config_t cfg{};
+  BkiConst k{};
+  int side = -1;  // -1: no insert yet; 0: the device; 1: the host
+  bool broken = false;
+  BkiHostMap host;
+  // the device side: one allocation behind the table; the hits of an insert and its work arrays
+  BkiTable t{};
+  char* slab = nullptr;
+  unsigned long long slots = 0, voxels = 0, initial_slots = 0;
+  long long occupied = -1;  // -1: not counted since the last insert
+  int growths = 0;
+  DeviceScratch in_scratch, work_scratch;
+  BkiStats last{};
+};
+
+namespace {
+
+int bki_validate_config(const cvo_map_config_t* c, std::string* msg) {
+  if (!c) return *msg = "a required pointer is missing", CVO_E_INVALID;
+  if (!std::isfinite(c->resolution) || !(c->resolution > 0.f)) return *msg = "resolution must be finite and > 0", CVO_E_INVALID;
+  if (!std::isfinite(c->free_resolution) || !(c->free_resolution > 0.f)) return *msg = "free_resolution must be finite and > 0", CVO_E_INVALID;
+  if (!(c->free_thresh >= 0.f && c->free_thresh <= 1.f) || !(c->occupied_thresh >= 0.f && c->occupied_thresh <= 1.f))
+    return *msg = "free_thresh and occupied_thresh lie in [0, 1]", CVO_E_INVALID;
+  if (!std::isfinite(c->prior) || c->prior < 0.f) return *msg = "prior must be finite and >= 0", CVO_E_INVALID;
+  if (!std::isfinite(c->max_range)) return *msg = "max_range must be finite (<= 0: off)", CVO_E_INVALID;
+  if (c->num_classes < 0 || c->num_classes > BKI_MAX_CLASSES) return *msg = "num_classes lies in 0 .. 19", CVO_E_INVALID;
+  if (c->block_depth != 1) return *msg = "only block_depth 1 is built", CVO_E_UNSUPPORTED;
+  return CVO_OK;
+}
+
+BkiConst bki_const(const cvo_map_config_t& c) {
+  BkiConst k;
+  k.size = c.resolution;
+  k.half = c.resolution / 2.0f;
+  k.prior = c.prior;
+  k.free_thresh = c.free_thresh;
+  k.occupied_thresh = c.occupied_thresh;
+  k.free_resolution = c.free_resolution;
+  k.max_range = c.max_range;
+  k.C = c.num_classes;
+  k.nclass = std::max(c.num_classes, 1) + 1;
+  return k;
+}
+
+// what every insert checks before either route: the pointers, the size, every coordinate finite
+int bki_validate_insert(const cvo_map* m, int n, const float* xyz, const float* label, const float* origin, std::string* msg) {
+  if (!m || !origin || n < 0 || (n > 0 && !xyz)) return *msg = "a required pointer is missing", CVO_E_INVALID;
+  if (n > 0 && m->k.C > 0 && !label) return *msg = "a map with classes needs label rows", CVO_E_INVALID;
+  if (m->broken) return *msg = "an earlier insert failed on the device half way: the map cannot be used", CVO_E_HIP;
+  for (int a = 0; a < 3; a++)
+    if (!std::isfinite(origin[a])) return *msg = "the origin is not finite", CVO_E_INVALID;
+  for (size_t i = 0; i < 3 * (size_t)n; i++)
+    if (!std::isfinite(xyz[i])) return *msg = "hit " + std::to_string(i / 3) + " has a coordinate that is not finite", CVO_E_INVALID;
+  if ((long long)n >= BKI_MAX_TRAINING) return *msg = "more than 2^24 training points in one insert", CVO_E_UNSUPPORTED;
+  return CVO_OK;
+}
+
+std::string bki_bad_text(unsigned status, unsigned index, int n) {
+  const std::string who = (int)index >= n ? std::string("the origin") : "hit " + std::to_string(index);
+  if (status & BKI_BAD_RANGE) return who + " or one of its beam samples leaves the map's 2^20 blocks per axis";
+  if (status & BKI_BAD_TOO_MANY) return who + " needs 65536 beam samples or more";
+  return who + " belongs to more than 8 blocks";
+}
+
+// The training points of one insert - hits max_range keeps, their beam samples, the origin -, counted without any block
+// arithmetic; stops as soon as `limit` is reached (a ray of BKI_MAX_RAY samples or more counts as `limit`).
+unsigned long long bki_training_count(const BkiConst& k, int n, const float* xyz, const float* origin, unsigned long long limit) {
+  unsigned long long training = 1;
+  for (int i = 0; i < n && training < limit; i++) {
+    const float* p = xyz + 3 * (size_t)i;
+    if (!bki_in_range(k, p, origin)) continue;
+    unsigned too_many = 0;
+    bki_hit_points(k, p, origin, &too_many, [&](float, float, float, bool) { return ++training < limit; });
+    if (too_many) return limit;
+  }
+  return training;
+}
+
+// The memberships of one insert in upstream's order, or the refusal.  `training` counts the points.
+int bki_members_cpu(const BkiConst& k, int n, const float* xyz, const float* label, const float* origin, std::vector<BkiMember>* out,
+                    unsigned long long* training, std::string* msg) {
+  unsigned bad = 0;
+  *training = 0;
+  auto point = [&](int i, int cls) {
+    return [&, i, cls](float x, float y, float z, bool hit) {
+      const int c = hit ? cls : 0;
+      const int m = bki_members(k, x, y, z, [&](unsigned long long key) { if (out) out->push_back(BkiMember{key, c, hit ? i : -1}); });
+      if (m < 0) return bad |= BKI_BAD_RANGE, false;
+      (*training)++;
+      return true;
+    };
+  };
+  for (int i = 0; i < n && !bad; i++) {
+    const float* p = xyz + 3 * (size_t)i;
+    if (!bki_in_range(k, p, origin)) continue;
+    unsigned too_many = 0;
+    bki_hit_points(k, p, origin, &too_many, point(i, k.C > 0 ? bki_class(label + (size_t)i * k.C, k.C) : 1));
+    if (too_many) bad |= BKI_BAD_TOO_MANY;
+    if (bad) return *msg = bki_bad_text(bad, (unsigned)i, n), bad & BKI_BAD_RANGE ? CVO_E_INVALID : CVO_E_UNSUPPORTED;
+  }
+  point(n, 0)(origin[0], origin[1], origin[2], false);
+  if (bad) return *msg = bki_bad_text(bad, (unsigned)n, n), CVO_E_INVALID;
+  if (*training >= (unsigned long long)BKI_MAX_TRAINING) return *msg = "more than 2^24 training points in one insert", CVO_E_UNSUPPORTED;
+  return CVO_OK;
+}
+
+int bki_insert_cpu(cvo_map* m, int n, const float* xyz, const float* feat, const float* label, const float* origin, BkiStats* stats, std::string* msg) {
+  const BkiConst& k = m->k;
+  std::vector<BkiMember> mem;
+  unsigned long long training = 0;
+  // (the caps come first, as in the statement, and before any membership is stored)
+  if (bki_training_count(k, n, xyz, origin, (unsigned long long)BKI_MAX_TRAINING) >= (unsigned long long)BKI_MAX_TRAINING)
+    return *msg = "2^24 training points or more in one insert, or a hit with 65536 beam samples or more", CVO_E_UNSUPPORTED;
+  const int rc = bki_members_cpu(k, n, xyz, label, origin, &mem, &training, msg);
+  if (rc != CVO_OK) return rc;
+  // per block touched: integer class counts, the float sum of its hits' feature rows in ascending hit index, from 0
+  std::unordered_map<unsigned long long, unsigned> touched;
+  std::vector<unsigned long long> tkeys;
+  std::vector<unsigned> counts;
+  std::vector<float> fbar;
+  for (const BkiMember& e : mem) {
+    auto it = touched.find(e.key);
+    if (it == touched.end()) {
+      it = touched.emplace(e.key, (unsigned)tkeys.size()).first;
+      tkeys.push_back(e.key);
+      counts.resize(counts.size() + (size_t)k.nclass, 0u);
+      fbar.resize(fbar.size() + BKI_FEAT, 0.f);
+    }
+    const size_t b = it->second;
+    counts[b * (size_t)k.nclass + (size_t)e.cls]++;
+    if (e.hit >= 0 && feat)
+      for (int f = 0; f < BKI_FEAT; f++) fbar[b * BKI_FEAT + f] += feat[(size_t)e.hit * BKI_FEAT + f];
+  }
+  BkiHostMap& h = m->host;
+  unsigned long long longest = 0;
+  for (size_t b = 0; b < tkeys.size(); b++) {
+    auto it = h.index.find(tkeys[b]);
+    if (it == h.index.end()) {
+      it = h.index.emplace(tkeys[b], (unsigned)h.keys.size()).first;
+      h.keys.push_back(tkeys[b]);
+      h.ms.resize(h.ms.size() + (size_t)k.nclass, k.prior);
+      h.fs.resize(h.fs.size() + BKI_FEAT, 0.f);
+    }
+    const size_t v = it->second;
+    unsigned long long hits = 0;
+    for (int c = 0; c < k.nclass; c++) {
+      h.ms[v * (size_t)k.nclass + c] += (float)counts[b * (size_t)k.nclass + c];
+      if (c) hits += counts[b * (size_t)k.nclass + c];
+    }
+    for (int f = 0; f < BKI_FEAT; f++) h.fs[v * BKI_FEAT + f] += fbar[b * BKI_FEAT + f];
+    longest = std::max(longest, hits);
+  }
+  stats->training = training;
+  stats->members = mem.size();
+  stats->longest_run = longest;
+  return CVO_OK;
+}
+
+// the occupied voxels of the host map in ascending key order
+std::vector<std::pair<unsigned long long, unsigned>> bki_occupied_cpu(const cvo_map* m) {
+  std::vector<std::pair<unsigned long long, unsigned>> occ;
+  for (size_t v = 0; v < m->host.keys.size(); v++)
+    if (bki_state(m->k, &m->host.ms[v * (size_t)m->k.nclass]) == BKI_OCCUPIED) occ.emplace_back(m->host.keys[v], (unsigned)v);
+  std::sort(occ.begin(), occ.end());
+  return occ;
+}
+
+// ---- device route ----
+unsigned bki_blocks(unsigned long long n) { return (unsigned)((n + BKI_THREADS - 1) / BKI_THREADS); }
+unsigned bki_stride_blocks(unsigned long long n) { return std::max(1u, std::min(bki_blocks(n), (unsigned)BKI_GRID_MAX)); }
+
+// a fresh table of `slots` slots: keys empty, ms = prior, fs and the counters zero
+int bki_table_alloc(cvo_map* m, unsigned long long slots, BkiTable* t, char** slab) {
+  cvo_ctx* ctx = m->ctx;
+  const BkiConst& k = m->k;
+  ScratchLayout lay;
+  const int ncnt = k.nclass + 1;
+  const size_t o_keys = lay.take(8 * slots), o_ms = lay.take(4 * slots * (size_t)k.nclass), o_fs = lay.take(4 * slots * BKI_FEAT),
+               o_cnt = lay.take(4 * slots * (size_t)ncnt), o_seg = lay.take(4 * slots);
+  char* p = nullptr;
+  const hipError_t e = hipMalloc(&p, lay.off);
+  if (e != hipSuccess) return fail(ctx, CVO_E_NOMEM, std::string("voxel map table hipMalloc: ") + hipGetErrorString(e));
+  *slab = p;
+  *t = BkiTable{(unsigned long long*)(p + o_keys), (float*)(p + o_ms), (float*)(p + o_fs), (unsigned*)(p + o_cnt), (unsigned*)(p + o_seg),
+                (unsigned)(slots - 1), k.nclass, ncnt};
+  hipStream_t st = ctx->upload_stream;
+  hipError_t r = hipMemsetAsync(t->keys, 0xFF, 8 * slots, st);
+  if (r == hipSuccess) r = hipMemsetAsync(t->fs, 0, 4 * slots * BKI_FEAT, st);
+  if (r == hipSuccess) r = hipMemsetAsync(t->cnt, 0, 4 * slots * (size_t)ncnt, st);
+  if (r == hipSuccess) {
+    hipLaunchKernelGGL(k_bki_fill, dim3(bki_stride_blocks(slots * (size_t)k.nclass)), dim3(BKI_THREADS), 0, st, t->ms, (size_t)slots * k.nclass, k.prior);
+    r = hipGetLastError();
+  }
+  if (r != hipSuccess) {
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(p);
+    *slab = nullptr;
+    return fail(ctx, CVO_E_HIP, std::string("voxel map table: ") + hipGetErrorString(r));
+  }
+  return CVO_OK;
+}
+
+// The table doubles - a fresh one, k_bki_rehash of the old one into it - until `need` voxels fill at most half of it.  The
+// old table goes only once its contents stand in the new one: an error leaves the map as it was.
+int bki_table_grow(cvo_map* m, unsigned long long need) {
+  cvo_ctx* ctx = m->ctx;
+  while (2 * need > m->slots) {
+    const unsigned long long slots = m->slots ? 2 * m->slots : m->initial_slots;
+    if (slots > BKI_MAX_SLOTS) return fail(ctx, CVO_E_UNSUPPORTED, "the voxel map would need more than 2^30 slots");
+    BkiTable t{};
+    char* slab = nullptr;
+    int rc = bki_table_alloc(m, slots, &t, &slab);
+    if (rc != CVO_OK) return rc;
+    hipError_t e = hipSuccess;
+    if (m->slab) {
+      hipLaunchKernelGGL(k_bki_rehash, dim3(bki_stride_blocks(m->slots)), dim3(BKI_THREADS), 0, ctx->upload_stream, m->t, t);
+      e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->upload_stream);
+    if (e != hipSuccess) {
+      (void)hipFree(slab);
+      return fail(ctx, CVO_E_HIP, std::string("voxel map rehash: ") + hipGetErrorString(e));
+    }
+    if (m->slab) {
+      (void)hipFree(m->slab);
+      m->growths++;
+    }
+    m->slab = slab;
+    m->t = t;
+    m->slots = slots;
+  }
+  return CVO_OK;
+}
+
+int bki_insert_device(cvo_map* m, int n, const float* xyz, const float* feat, const float* label, const float* origin, BkiStats* stats) {
+  cvo_ctx* ctx = m->ctx;
+  hipStream_t st = ctx->upload_stream;
+  const BkiConst& k = m->k;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ScratchLayout lay;
+  const size_t nn = (size_t)n;
+  const size_t o_ctl = lay.take(sizeof(BkiCtl)), o_xyz = lay.take(12 * nn), o_feat = lay.take(feat ? 4 * BKI_FEAT * nn : 0),
+               o_label = lay.take(k.C > 0 ? 4 * (size_t)k.C * nn : 0), o_mc = lay.take(4 * (nn + 1)), o_hslot = lay.take(4 * BKI_HIT_SLOTS * nn);
+  int rc;
+  if ((rc = m->in_scratch.reserve(ctx, lay.off, "voxel map insert scratch")) != CVO_OK) return rc;
+  char* base = m->in_scratch.p;
+  BkiInsertArgs a{};
+  a.k = k;
+  a.n = n;
+  a.xyz = (const float*)(base + o_xyz);
+  a.feat = feat ? (const float*)(base + o_feat) : nullptr;
+  a.label = k.C > 0 ? (const float*)(base + o_label) : nullptr;
+  for (int q = 0; q < 3; q++) a.origin[q] = origin[q];
+  a.mc = (unsigned*)(base + o_mc);
+  a.hslot = (unsigned*)(base + o_hslot);
+  a.ctl = (BkiCtl*)(base + o_ctl);
+  BkiCtl h{};
+  h.bad_index = ~0u;
+  HIP_TRY(ctx, hipMemcpyAsync(a.ctl, &h, sizeof h, hipMemcpyHostToDevice, st));
+  if (n) HIP_TRY(ctx, hipMemcpyAsync((void*)a.xyz, xyz, 12 * nn, hipMemcpyHostToDevice, st));
+  if (n && feat) HIP_TRY(ctx, hipMemcpyAsync((void*)a.feat, feat, 4 * BKI_FEAT * nn, hipMemcpyHostToDevice, st));
+  if (n && k.C > 0) HIP_TRY(ctx, hipMemcpyAsync((void*)a.label, label, 4 * (size_t)k.C * nn, hipMemcpyHostToDevice, st));
+  const dim3 per_hit(bki_blocks(nn + 1)), block(BKI_THREADS);
+  hipLaunchKernelGGL(k_bki_count, per_hit, block, 0, st, a);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(&h, a.ctl, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  // (the caps come first, as in the statement: k_bki_count goes on counting behind a bad block index)
+  if (h.status & BKI_BAD_TOO_MANY)  // (bad_index is the first bad hit of any kind: named only when this is the one kind)
+    return fail(ctx, CVO_E_UNSUPPORTED, "cvo_map_insert: " + (h.status == BKI_BAD_TOO_MANY ? bki_bad_text(h.status, h.bad_index, n) : std::string("a hit needs 65536 beam samples or more")));
+  if (h.training >= (unsigned long long)BKI_MAX_TRAINING) return fail(ctx, CVO_E_UNSUPPORTED, "cvo_map_insert: 2^24 training points or more in one insert");
+  if (h.status) return fail(ctx, h.status & BKI_BAD_RANGE ? CVO_E_INVALID : CVO_E_UNSUPPORTED, "cvo_map_insert: " + bki_bad_text(h.status, h.bad_index, n));
+  // the work arrays, and room in the table for every membership to be a new voxel
+  ScratchLayout work;
+  const size_t o_rec = work.take(4 * h.members), o_seg = work.take(4 * h.hit_members), o_seg2 = work.take(4 * h.hit_members),
+               o_long = work.take(8 * (h.hit_members / (BKI_SHORT_RUN + 1) + 1));
+  if ((rc = m->work_scratch.reserve(ctx, work.off, "voxel map work scratch")) != CVO_OK) return rc;
+  if ((rc = bki_table_grow(m, m->voxels + h.members)) != CVO_OK) return rc;
+  char* w = m->work_scratch.p;
+  a.t = m->t;
+  a.rec = (unsigned*)(w + o_rec);
+  a.seg = (unsigned*)(w + o_seg);
+  a.seg2 = (unsigned*)(w + o_seg2);
+  a.longlist = (unsigned*)(w + o_long);
+  m->broken = true;  // (until the table's counters are back at zero)
+  m->occupied = -1;
+  hipLaunchKernelGGL(k_bki_emit, per_hit, block, 0, st, a);
+  hipLaunchKernelGGL(k_bki_alloc, dim3(bki_stride_blocks(h.members)), block, 0, st, a);
+  if (n) hipLaunchKernelGGL(k_bki_scatter, dim3(bki_blocks(nn * BKI_HIT_SLOTS)), block, 0, st, a);
+  hipLaunchKernelGGL(k_bki_update, dim3(bki_stride_blocks(h.members)), block, 0, st, a);
+  if (feat && h.hit_members > (unsigned long long)BKI_SHORT_RUN)
+    hipLaunchKernelGGL(k_bki_long, dim3((unsigned)std::min<unsigned long long>(h.hit_members / (BKI_SHORT_RUN + 1), BKI_GRID_MAX)), dim3(BKI_WAVE), 0, st, a);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(&h, a.ctl, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  m->broken = false;
+  m->voxels += h.fresh;
+  stats->training = h.training;
+  stats->members = h.members;
+  stats->longest_run = h.longest_run;
+  stats->longest_probe = h.longest_probe;
+  return CVO_OK;
+}
+
+// Collects and sorts the occupied voxels of a device map; *okey / *oslot point at the sorted arrays in work_scratch, *rows at
+// room for the rows behind them.  count_only: one pass over the table that writes nothing but the number.
+int bki_collect_device(cvo_map* m, bool count_only, unsigned* n_occ, const unsigned long long** okey, const unsigned** oslot, char** rows) {
+  cvo_ctx* ctx = m->ctx;
+  hipStream_t st = ctx->upload_stream;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t V = count_only ? 0 : (size_t)m->voxels, nbmax = bki_blocks(V);
+  ScratchLayout lay;
+  const size_t o_ctl = lay.take(sizeof(BkiCtl)), o_k0 = lay.take(8 * V), o_k1 = lay.take(8 * V), o_s0 = lay.take(4 * V), o_s1 = lay.take(4 * V),
+               o_hist = lay.take(4 * 256 * nbmax), o_rows = lay.take(4 * V * (size_t)(3 + BKI_FEAT + BKI_MAX_CLASSES));
+  int rc;
+  if ((rc = m->work_scratch.reserve(ctx, lay.off, "voxel map work scratch")) != CVO_OK) return rc;
+  char* w = m->work_scratch.p;
+  BkiCtl* ctl = (BkiCtl*)(w + o_ctl);
+  unsigned long long* key[2] = {(unsigned long long*)(w + o_k0), (unsigned long long*)(w + o_k1)};
+  unsigned* slot[2] = {(unsigned*)(w + o_s0), (unsigned*)(w + o_s1)};
+  unsigned* hist = (unsigned*)(w + o_hist);
+  *rows = w + o_rows;
+  *okey = key[0];
+  *oslot = slot[0];
+  *n_occ = 0;
+  if (!m->voxels) return m->occupied = 0, CVO_OK;
+  BkiCtl h{};
+  HIP_TRY(ctx, hipMemsetAsync(ctl, 0, sizeof *ctl, st));
+  hipLaunchKernelGGL(k_bki_occupied, dim3(bki_stride_blocks(m->slots)), dim3(BKI_THREADS), 0, st, m->k, m->t, count_only ? nullptr : key[0],
+                     count_only ? nullptr : slot[0], ctl);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(&h, ctl, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if (h.n_occ > m->voxels) return fail(ctx, CVO_E_HIP, "cvo_map_cloud: the device found more occupied voxels than the map holds");
+  const unsigned n = h.n_occ, nb = bki_blocks(n);
+  for (int pass = 0; pass < 8 && n > 1 && !count_only; pass++) {  // (eight passes: the result is back in key[0] / slot[0])
+    const int from = pass & 1, to = from ^ 1;
+    hipLaunchKernelGGL(k_bki_radix_hist, dim3(nb), dim3(BKI_THREADS), 0, st, n, (const unsigned long long*)key[from], 8 * pass, hist);
+    hipLaunchKernelGGL(k_bki_radix_scan, dim3(1), dim3(256), 0, st, nb, hist);
+    hipLaunchKernelGGL(k_bki_radix_scatter, dim3(nb), dim3(BKI_THREADS), 0, st, n, (const unsigned long long*)key[from], (const unsigned*)slot[from],
+                       8 * pass, (const unsigned*)hist, key[to], slot[to]);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  *n_occ = n;
+  m->occupied = n;
+  return CVO_OK;
+}
+
+// the rows of the cloud read out, on the host: xyz n x 3, feat n x 5, label n x C
+struct BkiRows {
+  long long n = 0;
+  std::vector<float> xyz, feat, label;
+};
+
+int bki_rows(cvo_map* m, bool want_rows, BkiRows* out) {
+  const BkiConst& k = m->k;
+  if (m->side != 0) {
+    const auto occ = bki_occupied_cpu(m);
+    out->n = (long long)occ.size();
+    m->occupied = out->n;
+    if (!want_rows) return CVO_OK;
+    out->xyz.resize(3 * occ.size());
+    out->feat.resize(BKI_FEAT * occ.size());
+    out->label.resize((size_t)k.C * occ.size());
+    for (size_t i = 0; i < occ.size(); i++) {
+      const size_t v = occ[i].second;
+      bki_row(k, occ[i].first, &m->host.ms[v * (size_t)k.nclass], &m->host.fs[v * BKI_FEAT], &out->xyz[3 * i], &out->feat[BKI_FEAT * i],
+              k.C > 0 ? &out->label[(size_t)k.C * i] : nullptr);
+    }
+    return CVO_OK;
+  }
+  cvo_ctx* ctx = m->ctx;
+  unsigned n = 0;
+  const unsigned long long* okey;
+  const unsigned* oslot;
+  char* rows;
+  const int rc = bki_collect_device(m, !want_rows, &n, &okey, &oslot, &rows);
+  if (rc != CVO_OK) return rc;
+  out->n = n;
+  if (!want_rows || !n) return CVO_OK;
+  float* d_xyz = (float*)rows;
+  float* d_feat = d_xyz + 3 * (size_t)n;
+  float* d_label = d_feat + BKI_FEAT * (size_t)n;
+  hipStream_t st = ctx->upload_stream;
+  hipLaunchKernelGGL(k_bki_rows, dim3(bki_blocks(n)), dim3(BKI_THREADS), 0, st, k, m->t, n, okey, oslot, d_xyz, d_feat, d_label);
+  HIP_TRY(ctx, hipGetLastError());
+  out->xyz.resize(3 * (size_t)n);
+  out->feat.resize(BKI_FEAT * (size_t)n);
+  out->label.resize((size_t)k.C * n);
+  HIP_TRY(ctx, hipMemcpyAsync(out->xyz.data(), d_xyz, 12 * (size_t)n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(out->feat.data(), d_feat, 4 * BKI_FEAT * (size_t)n, hipMemcpyDeviceToHost, st));
+  if (k.C > 0) HIP_TRY(ctx, hipMemcpyAsync(out->label.data(), d_label, 4 * (size_t)k.C * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return CVO_OK;
+}
+
+// the side of a context's map, taken at its first insert
+int bki_choose_side(const cvo_map* m, int n, const float* xyz, const float* origin) {
+  const int sw = m->ctx->opt.bki_host;
+  if (sw >= 0) return sw > 0 ? 1 : 0;
+  // (the count stops at the crossover: a large frame costs this no more than a small one)
+  return route_on_host(-1, (long long)bki_training_count(m->k, n, xyz, origin, (unsigned long long)BKI_HOST_BELOW), BKI_HOST_BELOW) ? 1 : 0;
+}
+
+int bki_insert_entry(cvo_map* m, bool host_call, const char* who, int n, const float* xyz, const float* feat, const float* label, const float* origin) {
+  if (!m || host_call != (m->ctx == nullptr)) return CVO_E_INVALID;
+  cvo_ctx* ctx = m->ctx;
+  std::string msg;
+  const int rc = bki_validate_insert(m, n, xyz, label, origin, &msg);
+  if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
+  return frontend_call(ctx, who, [&] {
+    BkiStats stats;
+    int r;
+    const int side = m->side >= 0 ? m->side : (ctx ? bki_choose_side(m, n, xyz, origin) : 1);
+    if (side == 1) {
+      std::string text;
+      r = bki_insert_cpu(m, n, xyz, feat, label, origin, &stats, &text);
+      if (r != CVO_OK) return fail(ctx, r, std::string(who) + ": " + text);
+      m->occupied = -1;
+    } else {
+      stats.on_device = 1;
+      if ((r = bki_insert_device(m, n, xyz, feat, label, origin, &stats)) != CVO_OK) return r;
+    }
+    m->side = side;
+    m->last = stats;
+    return (int)CVO_OK;
+  });
+}
+
+int bki_open(cvo_ctx* ctx, const char* who, const cvo_map_config_t* cfg, long long initial_voxels, cvo_map** out) {
+  std::string msg;
+  if (!out) return fail(ctx, CVO_E_INVALID, std::string(who) + ": a required pointer is missing");
+  const int rc = bki_validate_config(cfg, &msg);
+  if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
+  if (initial_voxels < 0 || (unsigned long long)initial_voxels > BKI_MAX_SLOTS / 2) return fail(ctx, CVO_E_INVALID, std::string(who) + ": initial_voxels lies in 0 .. 2^29");
+  cvo_map* m = new cvo_map();
+  m->ctx = ctx;
+  m->cfg = *cfg;
+  m->k = bki_const(*cfg);
+  unsigned long long slots = 32;  // (twice the voxels, a power of two)
+  while (slots < 2 * (unsigned long long)initial_voxels) slots *= 2;
+  m->initial_slots = slots;
+  if (!ctx) m->side = 1;
+  *out = m;
+  return CVO_OK;
+}
+
+int bki_cloud_entry(cvo_map* m, bool host_call, const char* who, long long capacity, float* xyz, float* feat, float* label, long long* n, cvo_cloud** resident) {
+  if (!m || host_call != (m->ctx == nullptr)) return CVO_E_INVALID;
+  cvo_ctx* ctx = m->ctx;
+  if (!n || capacity < 0) return fail(ctx, CVO_E_INVALID, std::string(who) + ": a required pointer is missing");
+  if (m->broken) return fail(ctx, CVO_E_HIP, std::string(who) + ": an earlier insert failed on the device half way: the map cannot be used");
+  if (resident) *resident = nullptr;
+  return frontend_call(ctx, who, [&] {
+    BkiRows rows;
+    const bool want = xyz || feat || label || resident;
+    int rc = bki_rows(m, want, &rows);
+    if (rc != CVO_OK) return rc;
+    *n = rows.n;
+    if (!want) return (int)CVO_OK;
+    if ((xyz || feat || label) && capacity < rows.n) return fail(ctx, CVO_E_INVALID, std::string(who) + ": the cloud has more rows than `capacity`");
+    if (xyz && rows.n) std::memcpy(xyz, rows.xyz.data(), 4 * rows.xyz.size());
+    if (feat && rows.n) std::memcpy(feat, rows.feat.data(), 4 * rows.feat.size());
+    if (label && rows.n && m->k.C > 0) std::memcpy(label, rows.label.data(), 4 * rows.label.size());
+    if (resident) {
+      // what cvo_cloud_upload makes of the rows; a label row of fewer than NC classes is followed by zeros
+      std::vector<float> wide;
+      const int C = m->k.C;
+      if (C > 0 && C < NC) {
+        wide.assign((size_t)NC * rows.n, 0.f);
+        for (long long i = 0; i < rows.n; i++) std::memcpy(&wide[(size_t)NC * i], &rows.label[(size_t)C * i], 4 * (size_t)C);
+      }
+      const float* lab = C == 0 ? nullptr : (C < NC ? wide.data() : rows.label.data());
+      const HostCloud h{(int)rows.n, (const char*)rows.xyz.data(), 12, (const char*)rows.feat.data(), sizeof(float) * FD, (const char*)lab,
+                        sizeof(float) * NC, nullptr, 8};
+      if ((rc = upload_one_locked(ctx, h, resident)) != CVO_OK) return rc;
+    }
+    return (int)CVO_OK;
+  });
+}
+
+}  // namespace
+
+extern "C" {
+
+void cvo_map_config_default(cvo_map_config_t* cfg) {
+  if (!cfg) return;
+  cfg->resolution = 0.05f;
+  cfg->block_depth = 1;
+  cfg->num_classes = 0;
+  cfg->sf2 = 1.f;
+  cfg->ell = 1.f;
+  cfg->prior = 0.f;
+  cfg->var_thresh = 1.f;
+  cfg->free_thresh = 0.65f;
+  cfg->occupied_thresh = 0.9f;
+  cfg->ds_resolution = -1.f;
+  cfg->free_resolution = 1.f;
+  cfg->max_range = -1.f;
+}
+
+int cvo_map_open(cvo_ctx* ctx, const cvo_map_config_t* cfg, long long initial_voxels, cvo_map** out) {
+  if (!ctx) return CVO_E_INVALID;
+  return bki_open(ctx, "cvo_map_open", cfg, initial_voxels, out);
+}
+
+int cvo_map_open_host(const cvo_map_config_t* cfg, cvo_map** out) { return bki_open(nullptr, "cvo_map_open_host", cfg, 0, out); }
+
+void cvo_map_close(cvo_map* m) {
+  if (!m) return;
+  if (m->ctx) {
+    std::lock_guard<std::mutex> lk(m->ctx->upload_mutex);
+    (void)hipSetDevice(m->ctx->device);
+    (void)hipStreamSynchronize(m->ctx->upload_stream);
+    if (m->slab) (void)hipFree(m->slab);
+    m->in_scratch.release();
+    m->work_scratch.release();
+  }
+  delete m;
+}
+
+void cvo_map_close_host(cvo_map* m) {
+  if (m && !m->ctx) delete m;
+}
+
+int cvo_map_insert(cvo_map* m, int n, const float* xyz, const float* feat, const float* label, const float origin[3]) {
+  return bki_insert_entry(m, false, "cvo_map_insert", n, xyz, feat, label, origin);
+}
+
+int cvo_map_insert_host(cvo_map* m, int n, const float* xyz, const float* feat, const float* label, const float origin[3]) {
+  return bki_insert_entry(m, true, "cvo_map_insert_host", n, xyz, feat, label, origin);
+}
+
+int cvo_map_insert_posed(cvo_map* m, int n, const float* xyz, const float* feat, const float* label, const float pose12[12]) {
+  if (!m || !m->ctx) return CVO_E_INVALID;
+  if (!pose12 || n < 0 || (n > 0 && !xyz)) return fail(m->ctx, CVO_E_INVALID, "cvo_map_insert_posed: a required pointer is missing");
+  // the rows under the pose as cvo_cloud_transformed moves them (transform_point_pose_vec), the translation as origin
+  std::vector<float> moved;
+  try {
+    moved.resize(3 * (size_t)n);
+  } catch (const std::exception& e) {
+    return fail(m->ctx, CVO_E_NOMEM, std::string("cvo_map_insert_posed: ") + e.what());
+  }
+  const float* T = pose12;
+  for (int i = 0; i < n; i++) {
+    const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
+    for (int r = 0; r < 3; r++) moved[3 * (size_t)i + r] = std::fmaf(T[4 * r], x, T[4 * r + 1] * y) + std::fmaf(T[4 * r + 2], z, T[4 * r + 3]);
+  }
+  const float origin[3] = {T[3], T[7], T[11]};
+  return bki_insert_entry(m, false, "cvo_map_insert_posed", n, moved.data(), feat, label, origin);
+}
+
+int cvo_map_size(cvo_map* m, long long* voxels, long long* occupied) {
+  if (!m) return CVO_E_INVALID;
+  cvo_ctx* ctx = m->ctx;
+  if (m->broken) return fail(ctx, CVO_E_HIP, "cvo_map_size: an earlier insert failed on the device half way: the map cannot be used");
+  return frontend_call(ctx, "cvo_map_size", [&] {
+    if (occupied && m->occupied < 0) {
+      BkiRows rows;
+      const int rc = bki_rows(m, false, &rows);
+      if (rc != CVO_OK) return rc;
+    }
+    if (voxels) *voxels = m->side == 0 ? (long long)m->voxels : (long long)m->host.keys.size();
+    if (occupied) *occupied = m->occupied;
+    return (int)CVO_OK;
+  });
+}
+
+int cvo_map_cloud(cvo_map* m, long long capacity, float* xyz, float* feat, float* label, long long* n, cvo_cloud** resident) {
+  return bki_cloud_entry(m, false, "cvo_map_cloud", capacity, xyz, feat, label, n, resident);
+}
+
+int cvo_map_cloud_host(cvo_map* m, long long capacity, float* xyz, float* feat, float* label, long long* n) {
+  return bki_cloud_entry(m, true, "cvo_map_cloud_host", capacity, xyz, feat, label, n, nullptr);
+}
+
+int cvo_debug_map_stats(cvo_map* m, int* on_device, unsigned long long* counts, unsigned long long* keys, float* ms, float* fs) {
+  if (!m) return CVO_E_INVALID;
+  cvo_ctx* ctx = m->ctx;
+  return frontend_call(ctx, "cvo_debug_map_stats", [&] {
+    const bool dev = m->side == 0;
+    const unsigned long long capacity = dev ? m->slots : m->host.keys.size();
+    if (on_device) *on_device = m->last.on_device;
+    if (counts) {
+      counts[0] = m->last.training;
+      counts[1] = m->last.members;
+      counts[2] = m->last.longest_run;
+      counts[3] = capacity;
+      counts[4] = (unsigned long long)m->growths;
+      counts[5] = m->last.longest_probe;
+      counts[6] = dev ? m->voxels : m->host.keys.size();
+      counts[7] = (unsigned long long)m->k.nclass;
+    }
+    if (!keys && !ms && !fs) return (int)CVO_OK;
+    if (!dev) {
+      if (keys && capacity) std::memcpy(keys, m->host.keys.data(), 8 * capacity);
+      if (ms && capacity) std::memcpy(ms, m->host.ms.data(), 4 * m->host.ms.size());
+      if (fs && capacity) std::memcpy(fs, m->host.fs.data(), 4 * m->host.fs.size());
+      return (int)CVO_OK;
+    }
+    hipStream_t st = ctx->upload_stream;
+    if (keys) HIP_TRY(ctx, hipMemcpyAsync(keys, m->t.keys, 8 * capacity, hipMemcpyDeviceToHost, st));
+    if (ms) HIP_TRY(ctx, hipMemcpyAsync(ms, m->t.ms, 4 * capacity * (size_t)m->k.nclass, hipMemcpyDeviceToHost, st));
+    if (fs) HIP_TRY(ctx, hipMemcpyAsync(fs, m->t.fs, 4 * capacity * BKI_FEAT, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return (int)CVO_OK;
+  });
+}
+
+}  // extern "C"

@@ -1,0 +1,154 @@
+// cvo_bki_math.h -- the arithmetic of the semantic voxel map (semantic_bki::SemanticBKIOctoMap under its counting sensor
+// model, block_depth = 1) that the CPU twin (cvo_bki.hip) and the kernels (cvo_k_bki.h) share, so that the two cannot drift:
+// the block index of a coordinate, the closed float box of a block, the beam samples of a hit, the class of a label row, the
+// state of a voxel and the rows of the cloud read out.  tests/np_bki.py states the same in numpy.  Everything here is plain
+// float / double arithmetic without fused multiply-adds (the build compiles with -ffp-contract=off).
+#pragma once
+
+namespace cvo_dev {
+
+constexpr int BKI_KOFF = 524288;                // block index 524288 is the block centred on 0
+constexpr double BKI_K0_LO = 1.0;               // k0 in [1, 2^20 - 2]: k0 - 1 .. k0 + 1 fit the key's 20-bit fields
+constexpr double BKI_K0_HI = 1048575.0;         // (exclusive bound of the double before it is truncated)
+constexpr int BKI_MAX_CLASSES = 19;             // C of the configuration: 0 .. 19 (a cloud's label row)
+constexpr int BKI_FEAT = 5;
+// training points of ONE insert (hits that max_range keeps, their beam samples, the origin): below 2^24 every class count of
+// an insert is an exact float and a beam's running sum d always grows
+constexpr long long BKI_MAX_TRAINING = 1ll << 24;
+constexpr int BKI_MAX_RAY = 65536;              // ... and l / free_resolution of one hit stays below this (a lane walks a beam alone)
+enum : int { BKI_FREE = 0, BKI_OCCUPIED = 1, BKI_UNKNOWN = 2 };
+enum : unsigned { BKI_BAD_RANGE = 1, BKI_BAD_TOO_MANY = 2, BKI_BAD_INTERNAL = 4 };
+
+struct BkiConst {
+  float size, half;  // Block::size = resolution at block_depth 1; half = size / 2.0f
+  float prior, free_thresh, occupied_thresh, free_resolution, max_range;
+  int C;       // classes of a label row; 0: clouds without labels (the extension: every hit is class 1)
+  int nclass;  // classes of the map: max(C, 1) + 1, class 0 = free space
+};
+
+// k0 = int64(p / (double)size + 524288.5); false: outside [1, 2^20 - 2] (p is finite)
+__host__ __device__ inline bool bki_k0(float p, float size, long long* k0) {
+  const double q = (double)p / (double)size + 524288.5;
+  if (!(q >= BKI_K0_LO && q < BKI_K0_HI)) return false;
+  *k0 = (long long)q;
+  return true;
+}
+
+// upstream's closed box of block k on one axis: c - h <= p <= c + h in float, c = float(k - 524288) * size
+__host__ __device__ inline float bki_centre(long long k, float size) { return (float)(k - BKI_KOFF) * size; }
+__host__ __device__ inline bool bki_holds(long long k, float p, float size, float half) {
+  const float c = bki_centre(k, size);
+  return c - half <= p && p <= c + half;
+}
+
+// the blocks of k0 - 1, k0, k0 + 1 that hold p on one axis, ascending; returns how many (0: p lies in a rounding gap)
+__host__ __device__ inline int bki_axis(float p, long long k0, float size, float half, unsigned ks[3]) {
+  int n = 0;
+  for (long long k = k0 - 1; k <= k0 + 1; k++)
+    if (bki_holds(k, p, size, half)) ks[n++] = (unsigned)k;
+  return n;
+}
+
+__host__ __device__ inline unsigned long long bki_key(unsigned kx, unsigned ky, unsigned kz) {
+  return ((unsigned long long)kx << 40) | ((unsigned long long)ky << 20) | (unsigned long long)kz;
+}
+
+// f(key) for every block that holds (x, y, z), x-major then y then z, each axis ascending.  Returns the number of blocks, or
+// -1 when a k0 leaves its range (nothing is visited then).
+template <class F>
+__host__ __device__ inline int bki_members(const BkiConst& k, float x, float y, float z, F&& f) {
+  long long k0x, k0y, k0z;
+  if (!bki_k0(x, k.size, &k0x) || !bki_k0(y, k.size, &k0y) || !bki_k0(z, k.size, &k0z)) return -1;
+  unsigned ax[3], ay[3], az[3];
+  const int nx = bki_axis(x, k0x, k.size, k.half, ax), ny = bki_axis(y, k0y, k.size, k.half, ay), nz = bki_axis(z, k0z, k.size, k.half, az);
+  for (int a = 0; a < nx; a++)
+    for (int b = 0; b < ny; b++)
+      for (int c = 0; c < nz; c++) f(bki_key(ax[a], ay[b], az[c]));
+  return nx * ny * nz;
+}
+
+// float sum of squares of the float differences, left to right
+__host__ __device__ inline float bki_dist2(const float p[3], const float o[3]) {
+  const float dx = p[0] - o[0], dy = p[1] - o[1], dz = p[2] - o[2];
+  return dx * dx + dy * dy + dz * dz;
+}
+
+// max_range > 0 drops a hit when sqrt((double)s) > max_range, s = bki_dist2.  Decided without a square root: for a float s
+// and a float R the double R * R is exact (48 bits), and a float s that differs from it differs by more than the 2^-52
+// relative width within which the rounded double root could still equal R - so the rounded root exceeds R exactly when s
+// exceeds R * R.
+__host__ __device__ inline bool bki_in_range(const BkiConst& k, const float p[3], const float o[3]) {
+  if (!(k.max_range > 0.f)) return true;
+  return !((double)bki_dist2(p, o) > (double)k.max_range * (double)k.max_range);
+}
+
+// The training points of one kept hit, in upstream's order: f(x, y, z, true) for the hit, then f(x, y, z, false) for each
+// of its beam samples - d the running float sum fr, fr + fr, ... while d < l, then one more at l - fr when l > fr; each
+// sample origin + n * d with a separate multiply and add.  f returns false to stop.  Returns false when the ray would need
+// BKI_MAX_RAY samples or more (nothing is visited then), or when f stopped.  l = 0 (hit == origin): no samples, the
+// NaN direction is never used.
+template <class F>
+__host__ __device__ inline bool bki_hit_points(const BkiConst& k, const float p[3], const float o[3], unsigned* too_many, F&& f) {
+  const float fr = k.free_resolution;
+  const float l = sqrtf(bki_dist2(p, o));  // (the double root rounded to float is the same number)
+  if (!(l / fr < (float)BKI_MAX_RAY)) return *too_many = 1, false;
+  if (!f(p[0], p[1], p[2], true)) return false;
+  const float nx = (p[0] - o[0]) / l, ny = (p[1] - o[1]) / l, nz = (p[2] - o[2]) / l;
+  for (float d = fr; d < l; d += fr)
+    if (!f(o[0] + nx * d, o[1] + ny * d, o[2] + nz * d, false)) return false;
+  if (l > fr) {
+    const float d = l - fr;
+    if (!f(o[0] + nx * d, o[1] + ny * d, o[2] + nz * d, false)) return false;
+  }
+  return true;
+}
+
+// class of a hit: 1 + the first maximum of its label row (C = 0: 1)
+__host__ __device__ inline int bki_class(const float* label, int C) {
+  int best = 0;
+  for (int c = 1; c < C; c++)
+    if (label[c] > label[best]) best = c;
+  return 1 + best;
+}
+
+// sequential float sum of ms[from .. nclass)
+__host__ __device__ inline float bki_sum(const float* ms, int from, int nclass) {
+  float s = 0.f;
+  for (int c = from; c < nclass; c++) s += ms[c];
+  return s;
+}
+
+// the state, a function of ms alone: probs = ms / sum(ms); first maximum class 0 -> FREE; else p = 1 - probs[0]:
+// OCCUPIED above occupied_thresh, FREE below free_thresh, UNKNOWN between
+__host__ __device__ inline int bki_state(const BkiConst& k, const float* ms) {
+  const float sum = bki_sum(ms, 0, k.nclass);
+  const float p0 = ms[0] / sum;
+  float best = p0;
+  bool free_wins = true;
+  for (int c = 1; c < k.nclass; c++) {
+    const float pc = ms[c] / sum;
+    if (pc > best) best = pc, free_wins = false;
+  }
+  if (free_wins) return BKI_FREE;
+  const float p = 1.f - p0;
+  return p > k.occupied_thresh ? BKI_OCCUPIED : (p < k.free_thresh ? BKI_FREE : BKI_UNKNOWN);
+}
+
+// the row of an occupied voxel in the cloud read out: its centre, fs / sum(ms[1:]), ms[1 .. C] / sum(ms)
+__host__ __device__ inline void bki_row(const BkiConst& k, unsigned long long key, const float* ms, const float* fs, float* xyz, float* feat, float* label) {
+  if (xyz) {
+    xyz[0] = bki_centre((long long)(key >> 40), k.size);
+    xyz[1] = bki_centre((long long)((key >> 20) & 0xFFFFFull), k.size);
+    xyz[2] = bki_centre((long long)(key & 0xFFFFFull), k.size);
+  }
+  if (feat) {
+    const float occ = bki_sum(ms, 1, k.nclass);
+    for (int c = 0; c < BKI_FEAT; c++) feat[c] = fs[c] / occ;
+  }
+  if (label) {
+    const float sum = bki_sum(ms, 0, k.nclass);
+    for (int c = 1; c <= k.C; c++) label[c - 1] = ms[c] / sum;
+  }
+}
+
+}  // namespace cvo_dev

@@ -1,5 +1,5 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip, cvo_bki.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
 // pair, graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -72,3 +72,4 @@
 #include "cvo_k_nlm.h"
 #include "cvo_k_sgm.h"
 #include "cvo_k_dfilter.h"
+#include "cvo_k_bki.h"

@@ -48,6 +48,7 @@ struct CtxOptions {
   int nlm_host = -1;          // cvo_nlm_denoise / cvo_nlm_denoise_lab: as rgbd_host (cvo_nlm.hip)
   int sgm_host = -1;          // cvo_stereo_disparity / cvo_cloud_upload_stereo_pair's matcher: as rgbd_host (cvo_sgm.hip)
   int dfilter_host = -1;      // cvo_disparity_filter / the filter of the _filtered entry points: as rgbd_host (cvo_dfilter.hip)
+  int bki_host = -1;          // the side a cvo_map takes at its first insert: 1 = the CPU twin, 0 = the kernels, -1 = by size (cvo_bki.hip)
   int fast_tile = 1;          // k_fast_score reads the ring from an LDS tile with a 3-pixel halo; 0: through the cache
   int voxel_prepass = 1;      // k_voxel_insert resolves a block's duplicates in LDS first
   // ---- diagnostics ----
@@ -103,6 +104,7 @@ constexpr OptionSpec kOptions[] = {
     opt_int("NLM_HOST", &CtxOptions::nlm_host, -1, 1),
     opt_int("SGM_HOST", &CtxOptions::sgm_host, -1, 1),
     opt_int("DFILTER_HOST", &CtxOptions::dfilter_host, -1, 1),
+    opt_int("BKI_HOST", &CtxOptions::bki_host, -1, 1),
     opt_int("FAST_TILE", &CtxOptions::fast_tile, 0, 1),
     {"VERBOSE", OptKind::Level, nullptr, &CtxOptions::verbose, nullptr, 0, 0},
     opt_flag("KERNEL_CLOCK", &CtxOptions::kernel_clock),
