@@ -56,6 +56,21 @@ int cvo_debug_last_candidates(cvo_ctx* ctx, unsigned long long* out);
  * inputs, so that the device code itself can be pinned against numpy / scipy.  ops and layouts: k_scalar_math in
  * unified_cvo_amd/csrc/cvo_kernels.h.  in / out: host arrays of 16 doubles per item (op 7: one item of 2 + n / n). */
 int cvo_debug_scalar_math(cvo_ctx* ctx, int op, int n, const double* in, double* out);
+/* Runs ONE shared device primitive of the front ends' kernels (unified_cvo_amd/csrc/cvo_k_prims.h, cvo_k_compact.h,
+ * cvo_k_sort.h) on caller-supplied host arrays, which are copied up, worked on in place and copied back: k64 (n64 64-bit
+ * words), a (na 32-bit words), b (nb 32-bit words).  Arrays too small for the op's n and m are refused.
+ *   op 0  scan           a[n] block counts -> their exclusive offsets, b[0] = the total (k_compact_scan; n <= 16384)
+ *   op 1  radix sort     k64[2 n], a[2 n]: n (key, value) pairs in the first halves -> sorted by key, stable, in the first
+ *                        halves; the second halves and b[256 * ceil(n / 256)] are the sort's scratch
+ *   op 2  wave_alloc     ceil(n / 256) blocks of 256 lanes: a[i] = want of lane i -> the first of its places; b[0]: the counter
+ *   op 3  table_insert   k64[n + m]: n keys, behind them the table of m = 2^k >= 2 n slots (cleared here, returned);
+ *                        a[i] = slot of key i; b[1 + i] = 2 * slots visited + fresh; b[0] += fresh lanes (wave_count_add)
+ *   op 4  uf_unite       n cells, m edges a[2 e], a[2 e + 1]; b[n]: the parents (every cell its own, set here); a second
+ *                        launch leaves k64[c] = uf_find(c)
+ *   op 5  block ranks    blocks of 1024: a[i] != 0 flags element i, b[block] = block offset; k64[i] = inclusive rank << 32 |
+ *                        exclusive rank (~0u where the flag is not set) */
+int cvo_debug_prim(cvo_ctx* ctx, int op, int n, int m, unsigned long long* k64, size_t n64, unsigned* a, size_t na, unsigned* b,
+                   size_t nb);
 /* CVO_VERIFY_LISTS=1 (environment, read when a call starts): rows k_verify re-derived with the literal scan during the
  * last align call, summed over pairs and iterations (0 when the check was off). */
 int cvo_debug_verified_rows(cvo_ctx* ctx, unsigned long long* rows);

@@ -1,7 +1,8 @@
 """The ordered compactions of the four front ends (voxel grid, RGB-D, FAST, stereo) above 1024 blocks.
 
-All of them scan their per-block counts with k_voxel_scan (cvo_k_voxel.h): ONE block of 1024 threads, thread t takes
-per = ceil(nb / 1024) consecutive counts.  Every entry point accepts 2^24 points or pixels (nb = 16384, per = 16); the
+All of them scan their per-block counts with compact_scan_counts (cvo_k_compact.h) - RGB-D, FAST and stereo in
+k_compact_scan, the voxel grid in its own k_voxel_scan, which sums the insert's statistics in the same launch -: ONE block
+of 1024 threads, thread t takes per = ceil(nb / 1024) consecutive counts.  Every entry point accepts 2^24 points or pixels (nb = 16384, per = 16); the
 other modules stop at 977 blocks (per = 1).  Here: per = 2, 3 and 16 - threads left without counts, a last working thread
 with ONE count, the write-back loop -, k_voxel_insert striding over more than 512 blocks into a table above 2^21 slots,
 FULL's column-major enumeration above 2^20 pixels, and the extreme voxel indices +-(2^20 - 1).  The device routes are
@@ -30,7 +31,7 @@ in 18.4 s; that host's CPU is faster than the one above, and the test that meets
   test_upload_rgbd_of_a_large_frame            0.90 s
   test_stereo_points_of_a_large_frame          [FULL] 0.44 s, [CV_FAST] 0.52 s
 
-What discriminates: with k_voxel_scan's per cut to max(1, nb / 1024) on a scratch build - the remainder blocks keep their
+What discriminates: with the scan's per cut to max(1, nb / 1024) on a scratch build - the remainder blocks keep their
 counts as offsets - the voxel cases at 2^20 + 1 and 2^21 + 1025, FAST at 1040 x 1024 and 1031 x 1040, every RGB-D test
 and stereo FULL fail, and every test of test_gpu_voxel / rgbd / fast / stereo.py passes.  Voxel at 2^24 (a multiple of
 1024 blocks) and FAST / CV_FAST at 1025 x 2048 do not see that mutation: the frame's last row is its last two blocks,

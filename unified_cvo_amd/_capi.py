@@ -269,7 +269,7 @@ EXPORTED = [
     "cvo_function_angle", "cvo_association", "cvo_association_non_isotropic", "cvo_cloud_transformed", "cvo_edge_kernel_matrix", "cvo_debug_last_ell", "cvo_debug_time_scan", "cvo_debug_time_kernels",
     "cvo_debug_kernel_clock",
     "cvo_debug_last_candidates", "cvo_debug_list_builds", "cvo_debug_row_classes", "cvo_debug_speculation", "cvo_debug_scan_stats", "cvo_debug_last_geometry", "cvo_version",
-    "cvo_align_association", "cvo_debug_scalar_math", "cvo_debug_verified_rows", "cvo_debug_device_memory", "cvo_cloud_upload_many",
+    "cvo_align_association", "cvo_debug_scalar_math", "cvo_debug_prim", "cvo_debug_verified_rows", "cvo_debug_device_memory", "cvo_cloud_upload_many",
     "cvo_ctx_set_option", "cvo_ctx_advice", "cvo_debug_cloud_order",
     "cvo_process_hint_hw_queues", "cvo_shutdown",
     "cvo_batch_open", "cvo_batch_submit", "cvo_batch_poll", "cvo_batch_pending", "cvo_batch_stats", "cvo_batch_close",
@@ -364,6 +364,7 @@ def lib(path=None):
     L.cvo_align_association.argtypes = [vp, ip, C.POINTER(C.c_int), C.POINTER(C.c_int), fp, C.c_size_t,
                                         C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.cvo_debug_scalar_math.argtypes = [vp, ip, ip, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.cvo_debug_prim.argtypes = [vp, ip, ip, ip, C.POINTER(C.c_ulonglong), C.c_size_t, C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]
     L.cvo_debug_verified_rows.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.cvo_debug_device_memory.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.cvo_debug_cloud_order.argtypes = [vp, C.POINTER(C.c_int)]

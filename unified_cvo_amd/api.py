@@ -1627,6 +1627,15 @@ class CvoGPU:
         self._check(self.L.cvo_debug_scalar_math(self.ctx, op, n, a.ctypes.data_as(dp), out.ctypes.data_as(dp)))
         return out
 
+    def debug_prim(self, op, n, m, k64, a, b):
+        """Runs one shared device primitive (cvo_debug_prim of include/cvo_hip_debug.h, which lists the ops and the layouts) on
+        copies of the arrays k64 (uint64), a and b (uint32); returns the three as the device left them."""
+        k64, a, b = np.array(k64, np.uint64).reshape(-1), np.array(a, np.uint32).reshape(-1), np.array(b, np.uint32).reshape(-1)
+        ptr = lambda x, t: x.ctypes.data_as(C.POINTER(t)) if x.size else None
+        self._check(self.L.cvo_debug_prim(self.ctx, op, n, m, ptr(k64, C.c_ulonglong), k64.size, ptr(a, C.c_uint), a.size,
+                                          ptr(b, C.c_uint), b.size))
+        return k64, a, b
+
     def debug_device_memory(self):
         """(free, total) bytes of this context's device."""
         f, t = C.c_size_t(), C.c_size_t()

@@ -368,14 +368,8 @@ int bki_collect_device(cvo_map* m, bool count_only, unsigned* n_occ, const unsig
   HIP_TRY(ctx, hipMemcpyAsync(&h, ctl, sizeof h, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if (h.n_occ > m->voxels) return fail(ctx, CVO_E_HIP, "cvo_map_cloud: the device found more occupied voxels than the map holds");
-  const unsigned n = h.n_occ, nb = bki_blocks(n);
-  for (int pass = 0; pass < 8 && n > 1 && !count_only; pass++) {  // (eight passes: the result is back in key[0] / slot[0])
-    const int from = pass & 1, to = from ^ 1;
-    hipLaunchKernelGGL(k_bki_radix_hist, dim3(nb), dim3(BKI_THREADS), 0, st, n, (const unsigned long long*)key[from], 8 * pass, hist);
-    hipLaunchKernelGGL(k_bki_radix_scan, dim3(1), dim3(256), 0, st, nb, hist);
-    hipLaunchKernelGGL(k_bki_radix_scatter, dim3(nb), dim3(BKI_THREADS), 0, st, n, (const unsigned long long*)key[from], (const unsigned*)slot[from],
-                       8 * pass, (const unsigned*)hist, key[to], slot[to]);
-  }
+  const unsigned n = h.n_occ;
+  if (!count_only) sort_pairs_u64(ctx, n, key, slot, hist);
   HIP_TRY(ctx, hipGetLastError());
   *n_occ = n;
   m->occupied = n;

@@ -34,6 +34,67 @@ int cvo_debug_scalar_math(cvo_ctx* ctx, int op, int n, const double* in, double*
   return rc;
 }
 
+// Every size the kernels index with is checked here: nothing the caller passes can make them leave the three arrays.
+int cvo_debug_prim(cvo_ctx* ctx, int op, int n, int m, unsigned long long* k64, size_t n64, unsigned* a, size_t na, unsigned* b, size_t nb) {
+  const char* who = "cvo_debug_prim";
+  if (!ctx || n < 0 || m < 0 || n > (1 << 20) || m > (1 << 20) || (n64 && !k64) || (na && !a) || (nb && !b))
+    return fail(ctx, CVO_E_INVALID, std::string(who) + ": bad argument");
+  const size_t N = (size_t)n, M = (size_t)m;
+  bool ok = false;
+  int threads = 256, lanes = n;
+  switch (op) {
+    case PRIM_SCAN: ok = n <= COMPACT_MAX_ELEMENTS / COMPACT_THREADS && na >= N && nb >= 1; break;
+    case PRIM_SORT: ok = n64 >= 2 * N && na >= 2 * N && nb >= 256 * ((N + SORT_THREADS - 1) / SORT_THREADS); break;
+    case PRIM_WAVE_ALLOC: ok = na >= N && nb >= 1; break;
+    case PRIM_INSERT: ok = m >= 2 && (m & (m - 1)) == 0 && 2 * N <= M && n64 >= N + M && na >= N && nb >= N + 1; break;
+    case PRIM_UNION:
+      ok = na >= 2 * M && nb >= N && n64 >= N;
+      for (size_t e = 0; ok && e < 2 * M; e++) ok = a[e] < (unsigned)n;
+      for (size_t c = 0; ok && c < N; c++) b[c] = (unsigned)c;  // every cell its own root
+      lanes = m;
+      break;
+    case PRIM_RANK:
+      ok = na >= N && nb >= (N + COMPACT_THREADS - 1) / COMPACT_THREADS && n64 >= N;
+      threads = COMPACT_THREADS;
+      break;
+    default: break;
+  }
+  if (!ok) return fail(ctx, CVO_E_INVALID, std::string(who) + ": op " + std::to_string(op) + " with arrays too small for n, m, or a bad n, m");
+  if (op == PRIM_INSERT) std::fill(k64 + N, k64 + N + M, TABLE_EMPTY);
+  std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = ctx->upload_stream;
+  void* host[3] = {k64, a, b};
+  const size_t bytes[3] = {8 * n64, 4 * na, 4 * nb}, off[3] = {0, 8 * n64, 8 * n64 + align_up(4 * na, 8)};
+  char* d = nullptr;
+  HIP_TRY(ctx, hipMalloc(&d, off[2] + bytes[2] + 8));
+  unsigned long long* d64 = (unsigned long long*)d;
+  unsigned *da = (unsigned*)(d + off[1]), *db = (unsigned*)(d + off[2]);
+  hipError_t e = hipSuccess;
+  for (int q = 0; q < 3 && e == hipSuccess; q++)
+    if (bytes[q]) e = hipMemcpyAsync(d + off[q], host[q], bytes[q], hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    const dim3 grid((unsigned)std::max(1, (lanes + threads - 1) / threads));
+    if (op == PRIM_SCAN) {
+      hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(COMPACT_THREADS), 0, st, n, da, db);
+    } else if (op == PRIM_SORT) {
+      unsigned long long* const key[2] = {d64, d64 + N};
+      unsigned* const val[2] = {da, da + N};
+      sort_pairs_u64(ctx, (unsigned)n, key, val, db);
+    } else {
+      hipLaunchKernelGGL(k_prim, grid, dim3(threads), 0, st, op, n, m, d64, da, db);
+      if (op == PRIM_UNION) hipLaunchKernelGGL(k_prim, dim3((unsigned)std::max(1, (n + 255) / 256)), dim3(256), 0, st, (int)PRIM_FIND, n, m, d64, da, db);
+    }
+    e = hipGetLastError();
+  }
+  for (int q = 0; q < 3 && e == hipSuccess; q++)
+    if (bytes[q]) e = hipMemcpyAsync(host[q], d + off[q], bytes[q], hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d);
+  if (e != hipSuccess) return fail(ctx, CVO_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  return CVO_OK;
+}
+
 int cvo_debug_cloud_order(const cvo_cloud* c, int* out) {
   if (!c || !out) return CVO_E_INVALID;
   for (int r = 0; r < c->n; r++) out[r] = c->h_order[r];

@@ -39,7 +39,7 @@ int fast_validate_plane(int rows, int cols, const unsigned char* gray, std::stri
     *msg = "gray is NULL";
     return CVO_E_INVALID;
   }
-  if ((long long)rows * cols > VOX_MAX_POINTS) {
+  if ((long long)rows * cols > COMPACT_MAX_ELEMENTS) {
     *msg = "more than 2^24 pixels";
     return CVO_E_UNSUPPORTED;
   }
@@ -126,7 +126,7 @@ int fast_device_select(cvo_ctx* ctx, RgbdDevice& d, const cvo_fast_schedule_t& s
   *list = d.out;
   *n = count[t];
   if (*n == 0) return CVO_OK;
-  return compact(ctx, np, FastAbove{d.score, t, d.out}, d.blocks, d.ctl);  // (no synchronisation: the selection stays on the device)
+  return compact(ctx, np, FastAbove{d.score, t, d.out}, d.blocks, scan_into(ctx, d.ctl));  // (no synchronisation: the selection stays on the device)
 }
 
 // a gray plane as the frame the RGB-D staging lays out: one channel, no depth, no classes

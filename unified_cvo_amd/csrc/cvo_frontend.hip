@@ -1,7 +1,7 @@
 // cvo_frontend.hip -- what the front ends (cvo_voxel.hip, cvo_rgbd.hip, cvo_fast.hip, cvo_stereo.hip, cvo_lidar.hip, cvo_nlm.hip,
 // cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip) share on the host: the growable scratch regions (type and layout:
-// cvo_internal.h), the launches of an ordered compaction (cvo_k_compact.h) and the read-back of its total, the route rule,
-// the frame of an entry point and the copy-out of the kept indices.
+// cvo_internal.h), the launches of an ordered compaction (cvo_k_compact.h) and of the radix sort (cvo_k_sort.h), the read-back of
+// a compaction's total, the route rule, the frame of an entry point and the copy-out of the kept indices.
 // A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.  Shared declarations: cvo_internal.h.
 //
 // The entry frame, once for every front end.  A pair cvo_X_host / cvo_X is two one-line extern "C" functions over ONE
@@ -30,31 +30,56 @@ int DeviceScratch::reserve(cvo_ctx* ctx, size_t need, const char* what) {
 
 namespace {
 
+// the scan of a compaction that leaves nothing but its total
+auto scan_into(cvo_ctx* ctx, unsigned* total) {
+  return [=](int nb, unsigned* blocks) {
+    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(COMPACT_THREADS), 0, ctx->upload_stream, nb, blocks, total);
+  };
+}
+
 // An ordered compaction of n elements whose per-block counts are already in `blocks` (k_rgbd_select makes them itself):
-// k_voxel_scan turns them into offsets and leaves the total in ctl->n_kept - summing n_stats block statistics of
-// k_voxel_insert on the way -, k_compact_write<P> writes the survivors.  On upload_stream, no synchronisation.
-template <class P>
-int compact_counted(cvo_ctx* ctx, int n, const P& pred, unsigned* blocks, VoxelCtl* ctl, int n_stats = 0, const VoxelBlockStats* stats = nullptr) {
+// scan(nb, blocks) enqueues the one-block scan that turns them into offsets and leaves the total for compact_total,
+// k_compact_write<P> writes the survivors.  On upload_stream, no synchronisation.
+template <class P, class Scan>
+int compact_counted(cvo_ctx* ctx, int n, const P& pred, unsigned* blocks, Scan scan) {
   const int nb = (n + COMPACT_THREADS - 1) / COMPACT_THREADS;
-  hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, ctx->upload_stream, nb, blocks, ctl, n_stats, stats);
+  scan(nb, blocks);
   hipLaunchKernelGGL(k_compact_write<P>, dim3(nb), dim3(COMPACT_THREADS), 0, ctx->upload_stream, n, pred, (const unsigned*)blocks);
   HIP_TRY(ctx, hipGetLastError());
   return CVO_OK;
 }
 
 // count -> scan -> write
-template <class P>
-int compact(cvo_ctx* ctx, int n, const P& pred, unsigned* blocks, VoxelCtl* ctl, int n_stats = 0, const VoxelBlockStats* stats = nullptr) {
+template <class P, class Scan>
+int compact(cvo_ctx* ctx, int n, const P& pred, unsigned* blocks, Scan scan) {
   hipLaunchKernelGGL(k_compact_count<P>, dim3((n + COMPACT_THREADS - 1) / COMPACT_THREADS), dim3(COMPACT_THREADS), 0, ctx->upload_stream, n, pred, blocks);
-  return compact_counted(ctx, n, pred, blocks, ctl, n_stats, stats);
+  return compact_counted(ctx, n, pred, blocks, scan);
 }
 
-// what a compaction left in ctl: one copy, one synchronisation.  A total above n is refused as `who`: the device kept more `what` than it was given.
-int compact_total(cvo_ctx* ctx, const VoxelCtl* ctl, int n, const char* who, const char* what, VoxelCtl* h) {
-  HIP_TRY(ctx, hipMemcpyAsync(h, ctl, sizeof *h, hipMemcpyDeviceToHost, ctx->upload_stream));
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
-  if (h->n_kept > (unsigned)n) return fail(ctx, CVO_E_HIP, std::string(who) + ": the device kept more " + what + " than it was given");
+// a total above n is refused as `who`: the device kept more `what` than it was given
+int compact_check(cvo_ctx* ctx, unsigned kept, int n, const char* who, const char* what) {
+  if (kept > (unsigned)n) return fail(ctx, CVO_E_HIP, std::string(who) + ": the device kept more " + what + " than it was given");
   return CVO_OK;
+}
+
+// the total a compaction left: one copy, one synchronisation
+int compact_total(cvo_ctx* ctx, const unsigned* total, int n, const char* who, const char* what, unsigned* h) {
+  HIP_TRY(ctx, hipMemcpyAsync(h, total, sizeof *h, hipMemcpyDeviceToHost, ctx->upload_stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
+  return compact_check(ctx, *h, n, who, what);
+}
+
+// the radix sort of cvo_k_sort.h, enqueued: n pairs in key[0] / val[0], sorted there again; key[1] / val[1]: as much room,
+// hist: 256 counters per block of SORT_THREADS pairs
+void sort_pairs_u64(cvo_ctx* ctx, unsigned n, unsigned long long* const key[2], unsigned* const val[2], unsigned* hist) {
+  const unsigned nb = (n + SORT_THREADS - 1) / SORT_THREADS;
+  for (int pass = 0; pass < 8 && n > 1; pass++) {
+    const int from = pass & 1, to = from ^ 1;  // (eight passes: the result is back in key[0] / val[0])
+    hipLaunchKernelGGL(k_sort_hist, dim3(nb), dim3(SORT_THREADS), 0, ctx->upload_stream, n, (const unsigned long long*)key[from], 8 * pass, hist);
+    hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(256), 0, ctx->upload_stream, nb, hist);
+    hipLaunchKernelGGL(k_sort_scatter, dim3(nb), dim3(SORT_THREADS), 0, ctx->upload_stream, n, (const unsigned long long*)key[from],
+                       (const unsigned*)val[from], 8 * pass, (const unsigned*)hist, key[to], val[to]);
+  }
 }
 
 // The route rule of every front end.  The context's X_HOST switch forces the CPU twin (> 0) or the kernels (0); left alone

@@ -7,7 +7,7 @@
 //   k_bki_count    a lane per hit (and one for the origin) walks the hit's beam and counts its training points and block
 //                  memberships, checks every block index; nothing is written to the table.  The host reads the totals,
 //                  refuses or grows the table (k_bki_fill, k_bki_rehash), then enqueues the rest:
-//   k_bki_emit     the same walk; every membership enters the table (returning compare-and-swap, as k_voxel_insert) and
+//   k_bki_emit     the same walk; every membership enters the table (table_insert, cvo_k_prims.h) and
 //                  bumps the slot's INTEGER counters: all memberships, and per class of a hit.  The lane whose bump found
 //                  the total at zero marks its record FIRST: it stands for the voxel in the passes below.  Hits also note
 //                  their (at most 8) slots.
@@ -21,13 +21,12 @@
 //                  h hits: microseconds at 3000, about a second at 10^5 (DESIGN.md section 3 names the cliff).
 // Which slot a voxel lands in, which record is FIRST and the order inside a segment depend on arrival; no output does.
 //
-// The read-out: k_bki_occupied collects (key, slot) of the OCCUPIED voxels, a radix sort over the 64-bit key (8 passes of
-// k_bki_radix_hist / _scan / _scatter, stable, 256 elements per block) puts them in ascending key order, k_bki_rows writes
-// the rows.  Part of the kernel set of cvo_kernels.h; compiled only as part of cvo_hip.hip.
+// The read-out: k_bki_occupied collects (key, slot) of the OCCUPIED voxels (wave_alloc), the radix sort of cvo_k_sort.h puts
+// them in ascending key order, k_bki_rows writes the rows.  Part of the kernel set of cvo_kernels.h; compiled only as part of
+// cvo_hip.hip.
 #pragma once
 #include "cvo_bki_math.h"
-#include "cvo_k_voxel.h"
-#include "cvo_wave.h"
+#include "cvo_k_prims.h"
 
 namespace cvo_dev {
 
@@ -40,7 +39,7 @@ constexpr unsigned BKI_FIRST = 1u << 31;  // flag of a record; a table has at mo
 constexpr unsigned long long BKI_MAX_SLOTS = 1ull << 30;
 
 struct BkiTable {
-  unsigned long long* keys;  // VOX_EMPTY: free
+  unsigned long long* keys;  // TABLE_EMPTY: free
   float* ms;                 // nclass per slot; `prior` in every free slot
   float* fs;                 // BKI_FEAT per slot
   unsigned* cnt;             // ncnt per slot: [memberships, segment fill, hits of class 1 .. nclass - 1] of the running insert
@@ -63,21 +62,11 @@ struct BkiInsertArgs {
   float origin[3];
   unsigned* mc;        // n + 1: memberships of hit i with its samples; [n]: the origin's
   unsigned* rec;       // a slot per membership, BKI_FIRST on one record of every voxel touched
-  unsigned* hslot;     // n x BKI_HIT_SLOTS: the slots of hit i, VOX_NONE behind them
+  unsigned* hslot;     // n x BKI_HIT_SLOTS: the slots of hit i, SLOT_NONE behind them
   unsigned *seg, *seg2;  // hit indices per voxel; seg2: the ranked copy of the long ones
   unsigned* longlist;  // (slot, hits) of the voxels left to k_bki_long
   BkiCtl* ctl;
 };
-
-// `want` consecutive places of a bump counter for every lane, one atomic per wave.  Every lane of the wave calls it.
-__device__ __forceinline__ unsigned bki_wave_alloc(unsigned want, unsigned* counter) {
-  const int lane = threadIdx.x & 63;
-  const int incl = wave_prefix_incl_i32((int)want, lane);
-  int base = 0;
-  if (lane == 63 && incl) base = (int)atomicAdd(counter, (unsigned)incl);
-  base = __builtin_amdgcn_readlane(base, 63);
-  return (unsigned)base + (unsigned)incl - want;
-}
 
 // the training points of lane i: hit i < n with its beam, or the origin (i == n).  f(x, y, z, is_hit) as bki_hit_points.
 template <class F>
@@ -121,35 +110,21 @@ __global__ __launch_bounds__(BKI_THREADS) void k_bki_count(BkiInsertArgs a) {
   }
 }
 
-// The decisions are taken on what the compare-and-swap RETURNS, never on a plain load of keys[] (another XCD's L2 may hold a
-// stale line of it).  The table is at most half full after the insert: an empty slot is always met.
-__device__ __forceinline__ unsigned bki_table_insert(const BkiTable& t, unsigned long long key, unsigned* fresh, unsigned* longest) {
-  unsigned g = (unsigned)vox_mix(key) & t.mask, len = 1;
-  for (;;) {
-    const unsigned long long old = atomicCAS(&t.keys[g], VOX_EMPTY, key);
-    if (old == VOX_EMPTY) (*fresh)++;
-    if (old == VOX_EMPTY || old == key) break;
-    g = (g + 1) & t.mask;
-    len++;
-  }
-  *longest = max(*longest, len);
-  return g;
-}
-
 __global__ __launch_bounds__(BKI_THREADS) void k_bki_emit(BkiInsertArgs a) {
   const int i = blockIdx.x * BKI_THREADS + (int)threadIdx.x;
   const unsigned want = i <= a.n ? a.mc[i] : 0u;
-  unsigned at = bki_wave_alloc(want, &a.ctl->rec_used);
-  unsigned fresh = 0, longest = 0;
+  unsigned at = wave_alloc(want, &a.ctl->rec_used);
+  unsigned fresh = 0, longest = 0, len;
   if (i < a.n)
-    for (int m = 0; m < BKI_HIT_SLOTS; m++) a.hslot[(size_t)i * BKI_HIT_SLOTS + m] = VOX_NONE;
+    for (int m = 0; m < BKI_HIT_SLOTS; m++) a.hslot[(size_t)i * BKI_HIT_SLOTS + m] = SLOT_NONE;
   if (want) {
     const int cls = (i < a.n && a.k.C > 0) ? bki_class(a.label + (size_t)i * a.k.C, a.k.C) : 1;
     unsigned bad = 0;
     int hm = 0;
     bki_lane_points(a, i, &bad, [&](float x, float y, float z, bool hit) {
       bki_members(a.k, x, y, z, [&](unsigned long long key) {
-        const unsigned g = bki_table_insert(a.t, key, &fresh, &longest);
+        const unsigned g = table_insert(a.t.keys, a.t.mask, (unsigned)key_mix(key), key, &fresh, &len);
+        longest = max(longest, len);
         unsigned* c = a.t.cnt + (size_t)g * a.t.ncnt;
         const unsigned first = atomicAdd(&c[0], 1u) == 0u ? BKI_FIRST : 0u;
         if (hit) {
@@ -184,7 +159,7 @@ __global__ __launch_bounds__(BKI_THREADS) void k_bki_alloc(BkiInsertArgs a) {
       g = a.rec[r] & ~BKI_FIRST;
       h = bki_slot_hits(a.t, g);
     }
-    const unsigned off = bki_wave_alloc(h, &a.ctl->seg_used);
+    const unsigned off = wave_alloc(h, &a.ctl->seg_used);
     if (h) a.t.segoff[g] = off;
   }
 }
@@ -193,7 +168,7 @@ __global__ __launch_bounds__(BKI_THREADS) void k_bki_scatter(BkiInsertArgs a) {
   const size_t e = (size_t)blockIdx.x * BKI_THREADS + threadIdx.x;
   if (e >= (size_t)a.n * BKI_HIT_SLOTS) return;
   const unsigned g = a.hslot[e];
-  if (g == VOX_NONE) return;
+  if (g == SLOT_NONE) return;
   const unsigned at = atomicAdd(&a.t.cnt[(size_t)g * a.t.ncnt + 1], 1u);
   a.seg[a.t.segoff[g] + at] = (unsigned)(e / BKI_HIT_SLOTS);
 }
@@ -283,9 +258,8 @@ __global__ __launch_bounds__(BKI_THREADS) void k_bki_fill(float* ms, size_t n, f
 __global__ __launch_bounds__(BKI_THREADS) void k_bki_rehash(BkiTable from, BkiTable to) {
   for (size_t s = (size_t)blockIdx.x * BKI_THREADS + threadIdx.x; s <= from.mask; s += (size_t)gridDim.x * BKI_THREADS) {
     const unsigned long long key = from.keys[s];
-    if (key == VOX_EMPTY) continue;
-    unsigned fresh = 0, longest = 0;
-    const unsigned g = bki_table_insert(to, key, &fresh, &longest);
+    if (key == TABLE_EMPTY) continue;
+    const unsigned g = table_insert(to.keys, to.mask, (unsigned)key_mix(key), key);
     for (int c = 0; c < from.nclass; c++) to.ms[(size_t)g * to.nclass + c] = from.ms[s * from.nclass + c];
     for (int c = 0; c < BKI_FEAT; c++) to.fs[(size_t)g * BKI_FEAT + c] = from.fs[s * BKI_FEAT + c];
   }
@@ -296,81 +270,15 @@ __global__ __launch_bounds__(BKI_THREADS) void k_bki_occupied(BkiConst k, BkiTab
   const unsigned slots = t.mask + 1u;
   for (unsigned base = blockIdx.x * BKI_THREADS; base < slots; base += gridDim.x * BKI_THREADS) {  // (uniform per block)
     const unsigned g = base + threadIdx.x;
-    unsigned long long key = VOX_EMPTY;
+    unsigned long long key = TABLE_EMPTY;
     if (g < slots) key = t.keys[g];
-    const bool occ = key != VOX_EMPTY && bki_state(k, t.ms + (size_t)g * t.nclass) == BKI_OCCUPIED;
-    const unsigned at = bki_wave_alloc(occ ? 1u : 0u, &ctl->n_occ);
+    const bool occ = key != TABLE_EMPTY && bki_state(k, t.ms + (size_t)g * t.nclass) == BKI_OCCUPIED;
+    const unsigned at = wave_alloc(occ ? 1u : 0u, &ctl->n_occ);
     if (occ && okey) {  // (okey == nullptr: counted only)
       okey[at] = key;
       oslot[at] = g;
     }
   }
-}
-
-// rank of this thread's element among the block's earlier live elements with the same 8-bit digit; leaves the digit counts of
-// the block's four waves in wcount
-__device__ __forceinline__ unsigned bki_radix_rank(unsigned digit, bool live, unsigned (*wcount)[256]) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  for (int t = threadIdx.x; t < (BKI_THREADS / 64) * 256; t += BKI_THREADS) (&wcount[0][0])[t] = 0;
-  __syncthreads();
-  unsigned long long same = __ballot(live);
-  for (int b = 0; b < 8; b++) {
-    const bool bit = (digit >> b) & 1u;
-    const unsigned long long bal = __ballot(bit);
-    same &= bit ? bal : ~bal;
-  }
-  const unsigned below = (unsigned)__popcll(same & ((1ull << lane) - 1ull));
-  if (live && below == 0) wcount[w][digit] = (unsigned)__popcll(same);
-  __syncthreads();
-  unsigned r = below;
-  for (int q = 0; q < w; q++) r += wcount[q][digit];
-  return r;
-}
-
-__global__ __launch_bounds__(BKI_THREADS) void k_bki_radix_hist(unsigned n, const unsigned long long* key, int shift, unsigned* hist) {
-  __shared__ unsigned wcount[BKI_THREADS / 64][256];
-  const unsigned e = blockIdx.x * BKI_THREADS + threadIdx.x;
-  const bool live = e < n;
-  const unsigned digit = live ? (unsigned)(key[e] >> shift) & 255u : 0u;
-  (void)bki_radix_rank(digit, live, wcount);
-  unsigned c = 0;
-  for (int q = 0; q < BKI_THREADS / 64; q++) c += wcount[q][threadIdx.x];
-  hist[(size_t)blockIdx.x * 256 + threadIdx.x] = c;
-}
-
-// hist[block][digit] -> where the block's elements of that digit start: digits ascending, blocks ascending inside a digit
-__global__ __launch_bounds__(256) void k_bki_radix_scan(unsigned nb, unsigned* hist) {
-  __shared__ unsigned part[256];
-  unsigned total = 0;
-  for (unsigned b = 0; b < nb; b++) total += hist[(size_t)b * 256 + threadIdx.x];
-  part[threadIdx.x] = total;
-  __syncthreads();
-  for (int d = 1; d < 256; d *= 2) {
-    const unsigned add = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-    __syncthreads();
-    part[threadIdx.x] += add;
-    __syncthreads();
-  }
-  unsigned run = part[threadIdx.x] - total;
-  for (unsigned b = 0; b < nb; b++) {
-    const unsigned c = hist[(size_t)b * 256 + threadIdx.x];
-    hist[(size_t)b * 256 + threadIdx.x] = run;
-    run += c;
-  }
-}
-
-__global__ __launch_bounds__(BKI_THREADS) void k_bki_radix_scatter(unsigned n, const unsigned long long* key, const unsigned* slot, int shift,
-                                                                   const unsigned* hist, unsigned long long* key_out, unsigned* slot_out) {
-  __shared__ unsigned wcount[BKI_THREADS / 64][256];
-  const unsigned e = blockIdx.x * BKI_THREADS + threadIdx.x;
-  const bool live = e < n;
-  const unsigned long long k = live ? key[e] : 0ull;
-  const unsigned digit = (unsigned)(k >> shift) & 255u;
-  const unsigned rank = bki_radix_rank(digit, live, wcount);
-  if (!live) return;
-  const unsigned at = hist[(size_t)blockIdx.x * 256 + digit] + rank;
-  key_out[at] = k;
-  slot_out[at] = slot[e];
 }
 
 __global__ __launch_bounds__(BKI_THREADS) void k_bki_rows(BkiConst k, BkiTable t, unsigned n, const unsigned long long* key, const unsigned* slot,

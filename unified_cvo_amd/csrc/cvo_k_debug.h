@@ -1,6 +1,8 @@
-// cvo_k_debug.h -- k_verify (CVO_VERIFY_LISTS), k_scalar_math (device scalar maths on caller inputs), k_hold.
+// cvo_k_debug.h -- k_verify (CVO_VERIFY_LISTS), k_scalar_math (device scalar maths on caller inputs), k_prim (the shared device
+// primitives on caller arrays), k_hold.
 // Part of the kernel set of cvo_kernels.h (which states the whole iteration); compiled only as part of cvo_hip.hip.
 #pragma once
+#include "cvo_k_compact.h"
 #include "cvo_pair_math.h"
 #include "cvo_update.h"
 
@@ -188,6 +190,33 @@ __global__ __launch_bounds__(64) void k_scalar_math(int op, int n, const double*
       for (int q = 0; q < 9; q++) o[q] = (double)Ri[q];
       for (int q = 0; q < 3; q++) o[9 + q] = (double)Ti[q];
     }
+  }
+}
+
+// k_prim (cvo_debug_prim; ops and array layouts: include/cvo_hip_debug.h): one primitive of cvo_k_prims.h / cvo_k_compact.h on
+// caller arrays, one element per lane; lanes behind the last element take part in the wave- and block-wide calls with nothing.
+// The scan and the sort are kernels of their own, which cvo_debug_prim launches as the front ends do.
+enum { PRIM_SCAN = 0, PRIM_SORT, PRIM_WAVE_ALLOC, PRIM_INSERT, PRIM_UNION, PRIM_RANK, PRIM_FIND /* (second launch of PRIM_UNION) */ };
+__global__ __launch_bounds__(COMPACT_THREADS) void k_prim(int op, int n, int m, unsigned long long* k64, unsigned* a, unsigned* b) {
+  const int i = blockIdx.x * blockDim.x + (int)threadIdx.x;
+  if (op == PRIM_WAVE_ALLOC) {
+    const unsigned at = wave_alloc(i < n ? a[i] : 0u, b);
+    if (i < n) a[i] = at;
+  } else if (op == PRIM_INSERT) {
+    unsigned fresh = 0, len = 0;
+    if (i < n) {
+      a[i] = table_insert(k64 + n, (unsigned)m - 1u, (unsigned)key_mix(k64[i]), k64[i], &fresh, &len);
+      b[1 + i] = 2u * len + fresh;
+    }
+    wave_count_add(fresh != 0, b);
+  } else if (op == PRIM_UNION) {
+    if (i < m) uf_unite((int*)b, (int)a[2 * i], (int)a[2 * i + 1]);
+  } else if (op == PRIM_FIND) {
+    if (i < n) k64[i] = (unsigned long long)uf_find((int*)b, i);
+  } else if (op == PRIM_RANK) {  // (blocks of COMPACT_THREADS)
+    const bool f = i < n && a[i] != 0;
+    const unsigned excl = compact_block_rank<false>(f, b), incl = compact_block_rank<true>(f, b);
+    if (i < n) k64[i] = ((unsigned long long)incl << 32) | excl;
   }
 }
 

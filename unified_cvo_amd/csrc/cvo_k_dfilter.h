@@ -5,8 +5,7 @@
 // Every kernel but k_dfilter_gap runs one thread per pixel in blocks of DFILTER_TILE_W x DFILTER_TILE_H pixels, a wave per tile
 // row, so the 64 lanes of a wave are 64 consecutive pixels of one image row.
 //
-// Speckle: connected components of the valid pixels (4-neighbours within `sim`) by union-find, the parent of a set always its
-// lowest linear index (lidar_find / lidar_unite of cvo_k_lidar.h).
+// Speckle: connected components of the valid pixels (4-neighbours within `sim`) by uf_find / uf_unite of cvo_k_prims.h.
 // k_dfilter_label   parent[p] = the first pixel of p's horizontal run inside its wave (a ballot, no atomics): the horizontal
 //                   links cost nothing and leave trees of depth 1; size[p] = 0.
 // k_dfilter_unite   the links k_dfilter_label could not see: to the left across a wave's first lane, and downwards - the
@@ -15,8 +14,7 @@
 // k_dfilter_roots   root[p] = find(p), -1 for an invalid pixel; a wave adds each run of equal roots to size[root] with ONE
 //                   atomic, so a segment that covers the image takes one add per wave, not one per pixel.
 // k_dfilter_mask    the map with segments below speckle_size, and every negative value, as -10; counts segments and removed pixels.
-// Labels are minimum indices and sizes integer sums: the result does not depend on the order the waves run in.  Every find
-// loop ends on the parents as they are (parent[x] <= x strictly decreases to a root); nothing waits for another block.
+// Labels are minimum indices and sizes integer sums: the result does not depend on the order the waves run in.
 //
 // k_dfilter_gap     one wave per line (a row, or a column by its strides): a forward pass in steps of 64 pixels leaves the
 //                   index of the last valid pixel before every pixel (a ballot per step, the carry between steps uniform),
@@ -31,8 +29,7 @@
 // (64 + 7) x 4 or 64 x (4 + 7) region.
 #pragma once
 #include "cvo_dfilter_math.h"
-#include "cvo_k_lidar.h"
-#include "cvo_wave.h"
+#include "cvo_k_prims.h"
 
 namespace cvo_dev {
 
@@ -63,11 +60,6 @@ __device__ __forceinline__ DFilterPixel dfilter_pixel(int rows, int cols, int ti
   q.in = q.x < cols && q.y < rows;
   q.p = q.in ? (size_t)q.y * (size_t)cols + (size_t)q.x : 0;
   return q;
-}
-
-__device__ __forceinline__ void dfilter_count(bool f, unsigned* to) {
-  const unsigned long long m = __ballot(f);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(to, (unsigned)__popcll(m));
 }
 
 struct DFilterSpeckleArgs {
@@ -105,17 +97,17 @@ __global__ __launch_bounds__(DFILTER_THREADS) void k_dfilter_unite(const DFilter
   const float left = __shfl_up(v, 1), down_left = __shfl_up(down, 1);
   if (!q.in || !dfilter_valid(v)) return;
   const int p = (int)q.p;
-  if (q.lx == 0 && q.x > 0 && dfilter_linked(v, a.src[q.p - 1], a.sim)) lidar_unite(a.parent, p, p - 1);
+  if (q.lx == 0 && q.x > 0 && dfilter_linked(v, a.src[q.p - 1], a.sim)) uf_unite(a.parent, p, p - 1);
   if (dfilter_linked(v, down, a.sim)) {
     const bool implied = q.lx > 0 && dfilter_linked(v, left, a.sim) && dfilter_linked(left, down_left, a.sim) && dfilter_linked(down_left, down, a.sim);
-    if (!implied) lidar_unite(a.parent, p, p + a.cols);
+    if (!implied) uf_unite(a.parent, p, p + a.cols);
   }
 }
 
 __global__ __launch_bounds__(DFILTER_THREADS) void k_dfilter_roots(const DFilterSpeckleArgs a) {
   const DFilterPixel q = dfilter_pixel(a.rows, a.cols, a.tiles_x);
   int r = -1;
-  if (q.in && dfilter_valid(a.src[q.p])) r = lidar_find(a.parent, (int)q.p);  // (the parents no longer change: a launch behind)
+  if (q.in && dfilter_valid(a.src[q.p])) r = uf_find(a.parent, (int)q.p);  // (the parents no longer change: a launch behind)
   if (q.in) a.root[q.p] = r;
   const int before = __shfl_up(r, 1);
   const bool head = q.lx == 0 || before != r;
@@ -131,8 +123,8 @@ __global__ __launch_bounds__(DFILTER_THREADS) void k_dfilter_mask(const DFilterS
   const int r = q.in ? a.root[q.p] : -1;
   const bool keep = r >= 0 && a.size[r] >= (unsigned)a.speckle_size;
   if (q.in) a.out[q.p] = keep ? a.src[q.p] : DFILTER_INVALID;
-  dfilter_count(r >= 0 && r == (int)q.p, &a.counters->segments);
-  dfilter_count(r >= 0 && !keep, &a.counters->removed);
+  wave_count_add(r >= 0 && r == (int)q.p, &a.counters->segments);
+  wave_count_add(r >= 0 && !keep, &a.counters->removed);
 }
 
 struct DFilterGapArgs {

@@ -2,9 +2,10 @@
 // n_scan x horizon_scan range image.  The decisions are the functions of cvo_lidar_math.h, which the CPU twin calls too.
 //
 //   LidarTransition    predicate of k_compact_count: the 4 -> 1 quadrant transitions, whose inclusive scan is the ring id
-//   k_lidar_project    ring id, column and range of every point; the LAST point in index order wins its cell (atomicMax)
+//   k_lidar_project    ring id (compact_block_rank<true>), column and range of every point; the LAST point in index order wins
+//                      its cell (atomicMax)
 //   k_lidar_cells      per cell: range, ground (a gather over the pair below and the pair above), the union-find's start
-//   k_lidar_union      4-connected components, columns wrapping: union by atomicMin, the root is the lowest row-major cell
+//   k_lidar_union      4-connected components, columns wrapping: uf_unite (cvo_k_prims.h), the root is the lowest row-major cell
 //   k_lidar_flatten    the root of every cell; size and row mask (seed excluded) of a component by atomics on its root
 //   k_lidar_valid      the validity rule per cell, the component counts
 //   LidarSegKeep       predicate of the ordered compaction that makes the segmented cloud, row-major
@@ -15,10 +16,9 @@
 //   LidarCand, LidarKept   predicates of the two ordered compactions of the thinning: a candidate's rank is its draw
 //
 // No output depends on the order waves arrive in: max, min, add and or commute; every position comes from an ordered
-// compaction; blocks of one launch exchange values only through what atomics return (k_lidar_union reads parents with atomic
-// loads).  Part of the kernel set of cvo_kernels.h; compiled only as part of cvo_hip.hip.
+// compaction; the union-find is uf_find / uf_unite (cvo_k_prims.h).  Part of the kernel set of cvo_kernels.h; compiled only as
+// part of cvo_hip.hip.
 #pragma once
-#include "cvo_device.h"
 #include "cvo_k_compact.h"
 #include "cvo_lidar_math.h"
 
@@ -49,17 +49,9 @@ struct LidarTransition {
 
 __global__ __launch_bounds__(COMPACT_THREADS) void k_lidar_project(int n, LidarTransition tr, LidarConst k, const unsigned* __restrict__ block_offset,
                                                                    int* cellwin) {
-  __shared__ unsigned wcnt[COMPACT_THREADS / 64];
   const int i = blockIdx.x * COMPACT_THREADS + (int)threadIdx.x;
-  const bool f = tr.flag(i, n);
-  const unsigned long long m = __ballot(f);
-  const unsigned lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  if (lane == 0) wcnt[wv] = (unsigned)__popcll(m);
-  __syncthreads();
-  if (i >= n) return;
-  unsigned ring = block_offset[blockIdx.x] + (unsigned)__popcll(m & ((2ull << lane) - 1ull));  // inclusive: the transition point opens its ring
-  for (unsigned v = 0; v < wv; v++) ring += wcnt[v];
-  if (ring >= (unsigned)k.R) return;
+  const unsigned ring = compact_block_rank<true>(tr.flag(i, n), block_offset);  // inclusive: the transition point opens its ring
+  if (i >= n || ring >= (unsigned)k.R) return;
   const float4 q = tr.p[i];
   const int col = lidar_column(q.x, q.z, k.ang_res_x, k.H);
   if (col < 0 || lidar_range(q.x, q.y, q.z) < k.min_range) return;
@@ -72,11 +64,6 @@ __device__ __forceinline__ bool lidar_cell_pair(const float4* __restrict__ p, co
   const float4 pa = p[a], pb = p[b];
   const float lo[3] = {pa.x, pa.y, pa.z}, up[3] = {pb.x, pb.y, pb.z};
   return lidar_ground_pair(lo, up, k);
-}
-
-__device__ __forceinline__ void lidar_count(bool f, unsigned* to) {
-  const unsigned long long m = __ballot(f);
-  if ((threadIdx.x & 63) == 0 && m) atomicAdd(to, (unsigned)__popcll(m));
 }
 
 __global__ __launch_bounds__(LIDAR_THREADS) void k_lidar_cells(LidarConst k, const float4* __restrict__ p, const int* __restrict__ cellwin,
@@ -98,33 +85,8 @@ __global__ __launch_bounds__(LIDAR_THREADS) void k_lidar_cells(LidarConst k, con
     state[c] = !full ? LIDAR_EMPTY : (ground ? LIDAR_GROUND : LIDAR_LIVE);
     parent[c] = full && !ground ? c : -1;
   }
-  lidar_count(full, &stats->projected);
-  lidar_count(ground, &stats->ground);
-}
-
-__device__ __forceinline__ int lidar_find(int* parent, int x) {
-  for (;;) {
-    const int q = __hip_atomic_load(&parent[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (q == x) return x;
-    x = q;
-  }
-}
-
-// parent[x] <= x always, so a root is the lowest cell of its tree and the final root the lowest cell of the component
-__device__ __forceinline__ void lidar_unite(int* parent, int a, int b) {
-  for (;;) {
-    a = lidar_find(parent, a);
-    b = lidar_find(parent, b);
-    if (a == b) return;
-    if (a < b) {
-      const int t = a;
-      a = b;
-      b = t;
-    }
-    const int old = atomicMin(&parent[a], b);
-    if (old == a) return;
-    a = old;
-  }
+  wave_count_add(full, &stats->projected);
+  wave_count_add(ground, &stats->ground);
 }
 
 __global__ __launch_bounds__(LIDAR_THREADS) void k_lidar_union(LidarConst k, const float* __restrict__ range, const unsigned char* __restrict__ state,
@@ -133,8 +95,8 @@ __global__ __launch_bounds__(LIDAR_THREADS) void k_lidar_union(LidarConst k, con
   if (c >= cells || state[c] != LIDAR_LIVE) return;
   const int row = c / k.H, col = c - row * k.H;
   const int right = row * k.H + (col + 1 == k.H ? 0 : col + 1), down = c + k.H;
-  if (right != c && state[right] == LIDAR_LIVE && lidar_connected(range[c], range[right], true, k)) lidar_unite(parent, c, right);
-  if (row + 1 < k.R && state[down] == LIDAR_LIVE && lidar_connected(range[c], range[down], false, k)) lidar_unite(parent, c, down);
+  if (right != c && state[right] == LIDAR_LIVE && lidar_connected(range[c], range[right], true, k)) uf_unite(parent, c, right);
+  if (row + 1 < k.R && state[down] == LIDAR_LIVE && lidar_connected(range[c], range[down], false, k)) uf_unite(parent, c, down);
 }
 
 __global__ __launch_bounds__(LIDAR_THREADS) void k_lidar_flatten(LidarConst k, const unsigned char* __restrict__ state, int* parent, int* __restrict__ root,
@@ -145,7 +107,7 @@ __global__ __launch_bounds__(LIDAR_THREADS) void k_lidar_flatten(LidarConst k, c
     root[c] = -1;
     return;
   }
-  const int r = lidar_find(parent, c);  // (the parents no longer change: k_lidar_union is a launch behind)
+  const int r = uf_find(parent, c);  // (the parents no longer change: k_lidar_union is a launch behind)
   root[c] = r;
   atomicAdd(&size[r], 1u);
   if (r != c) {
@@ -166,8 +128,8 @@ __global__ __launch_bounds__(LIDAR_THREADS) void k_lidar_valid(LidarConst k, con
     }
     valid[c] = ok ? 1 : 0;
   }
-  lidar_count(is_root && ok, &stats->valid);
-  lidar_count(is_root && !ok, &stats->invalid);
+  wave_count_add(is_root && ok, &stats->valid);
+  wave_count_add(is_root && !ok, &stats->invalid);
 }
 
 struct LidarSegKeep {

@@ -9,7 +9,7 @@
 //   k_rgbd_select       one lane per pot x pot cell, for EVERY potential the schedule can ask for (2 .. 7) in one launch:
 //                       the first pixel in row-major order with the largest g2 strictly above its threshold.  Cells are
 //                       enumerated in the reference's nesting (blocks of 4 pot, 2 pot, pot, each row-major), padded to whole
-//                       4 pot blocks, so an ORDERED compaction (k_voxel_scan over the block counts it writes itself,
+//                       4 pot blocks, so an ORDERED compaction (k_compact_scan over the block counts it writes itself,
 //                       k_compact_write<RgbdCellHit>) gives output_uv of select() (:270-426) for each potential.  No atomic
 //                       decides a position.
 //   RgbdKeep            predicate of the ordered compaction (cvo_k_compact.h) over a pixel list - FULL's column-major order

@@ -1,30 +1,27 @@
 // cvo_k_voxel.h -- voxel-grid downsampling of a raw frame (cvo::VoxelMap, VoxelMap_impl.hpp:126-170): one point per occupied
 // voxel, the one with the lowest original index, in ascending original index.
 //
-//   k_voxel_insert   one point per lane: voxel key, open-addressing insert into a table in HBM with a returning 64-bit
-//                    compare-and-swap, unsigned min of the point's index on the slot.  Optionally (PRE) the 1024 points of a
-//                    block first meet in an LDS table and only the block's lowest index of every voxel goes to HBM.
+//   k_voxel_insert   one point per lane: voxel key, open-addressing insert into a table in HBM (table_insert, cvo_k_prims.h),
+//                    unsigned min of the point's index on the slot.  Optionally (PRE) the 1024 points of a block first meet
+//                    in an LDS table and only the block's lowest index of every voxel goes to HBM.
 //   VoxelFirst       the predicate of the ordered compaction (cvo_k_compact.h): keep = "my index is my slot's minimum";
 //                    k_compact_count<VoxelFirst> counts per block of 1024 points, k_compact_write<VoxelFirst> writes the
 //                    kept indices in ascending order.
-//   k_voxel_scan     exclusive scan of the block counts of ANY compaction (one block).
+//   k_voxel_scan     compact_scan_counts of this selection's block counts and, in the same launch, the sum of k_voxel_insert's
+//                    block statistics (one block).
 //
 // Which slot a voxel lands in depends on the order the waves arrive in; no output does: min commutes and the compaction is
 // ordered by index.  Part of the kernel set of cvo_kernels.h; compiled only as part of cvo_hip.hip.
 #pragma once
 #include "cvo_device.h"
 #include "cvo_k_compact.h"
-#include "cvo_wave.h"
 
 namespace cvo_dev {
 
 constexpr int VOX_THREADS = COMPACT_THREADS;      // points per block of every kernel here
 constexpr int VOX_INSERT_BLOCKS = 512;            // most blocks k_voxel_insert is launched with (two per CU; it strides)
 constexpr int VOX_LDS_SLOTS = 2048;               // block-local table of the pre-pass: 2 slots per point, never full
-constexpr int VOX_MAX_POINTS = 1 << 24;           // (the scan holds VOX_MAX_POINTS / VOX_THREADS block counts in one block)
 constexpr int VOX_KMAX = 1 << 20;                 // |k| < 2^20 per axis: three 21-bit fields, a 63-bit key
-constexpr unsigned long long VOX_EMPTY = ~0ull;   // (no key has bit 63)
-constexpr unsigned VOX_NONE = ~0u;                // slot[] of a point that did not enter the table; first[] of an empty slot
 enum : unsigned { VOX_BAD_FINITE = 1, VOX_BAD_X = 2, VOX_BAD_Y = 4, VOX_BAD_Z = 8 };
 
 // what a selection leaves for the host: one 48-byte copy
@@ -56,25 +53,14 @@ __host__ __device__ inline unsigned vox_key(float x, float y, float z, float s, 
   return 0;
 }
 
-// home slot: the finaliser of splitmix64 (neighbouring voxels differ in a few low bits of one field)
-__host__ __device__ inline unsigned long long vox_mix(unsigned long long k) {
-  k ^= k >> 30;
-  k *= 0xbf58476d1ce4e5b9ull;
-  k ^= k >> 27;
-  k *= 0x94d049bb133111ebull;
-  k ^= k >> 31;
-  return k;
-}
-
-// The decisions are taken on what the compare-and-swap RETURNS, never on a plain load of keys[]: another XCD's L2 may hold
-// a stale line of it while this kernel runs.  first[] / slot[] are read back by the NEXT kernel only.
+// SLOT_NONE: slot[] of a point that did not enter the table, first[] of an empty slot.  Both are read back by the NEXT kernel only.
 template <bool PRE>
 __global__ __launch_bounds__(VOX_THREADS) void k_voxel_insert(int n, const float* __restrict__ xyz, float s, unsigned mask,
                                                               unsigned long long* keys, unsigned* first, unsigned* __restrict__ slot,
                                                               VoxelCtl* ctl, VoxelBlockStats* __restrict__ block_stats) {
   __shared__ unsigned long long lkeys[PRE ? VOX_LDS_SLOTS : 1];
   __shared__ unsigned lfirst[PRE ? VOX_LDS_SLOTS : 1];
-  unsigned probes = 0, longest = 0, fresh = 0, entered = 0, bad = 0;
+  unsigned probes = 0, longest = 0, fresh = 0, entered = 0, bad = 0, len;
   for (int base = blockIdx.x * VOX_THREADS; base < n; base += gridDim.x * VOX_THREADS) {  // (uniform per block: the barriers below)
     const int i = base + (int)threadIdx.x;
     unsigned long long key = 0;
@@ -84,20 +70,16 @@ __global__ __launch_bounds__(VOX_THREADS) void k_voxel_insert(int n, const float
       bad |= b;
       live = b == 0;
     }
-    const unsigned long long h = vox_mix(key);
+    const unsigned long long h = key_mix(key);
     if (PRE) {
       for (int t = threadIdx.x; t < VOX_LDS_SLOTS; t += VOX_THREADS) {
-        lkeys[t] = VOX_EMPTY;
-        lfirst[t] = VOX_NONE;
+        lkeys[t] = TABLE_EMPTY;
+        lfirst[t] = SLOT_NONE;
       }
       __syncthreads();
       unsigned ls = (unsigned)(h >> 40) & (VOX_LDS_SLOTS - 1);
       if (live) {
-        for (;;) {
-          const unsigned long long old = atomicCAS(&lkeys[ls], VOX_EMPTY, key);
-          if (old == VOX_EMPTY || old == key) break;
-          ls = (ls + 1) & (VOX_LDS_SLOTS - 1);
-        }
+        ls = table_insert(lkeys, VOX_LDS_SLOTS - 1, ls, key);
         atomicMin(&lfirst[ls], (unsigned)i);
       }
       __syncthreads();
@@ -105,21 +87,14 @@ __global__ __launch_bounds__(VOX_THREADS) void k_voxel_insert(int n, const float
       __syncthreads();                           // (the next trip clears the table)
     }
     if (live) {
-      unsigned g = (unsigned)h & mask, len = 1;
-      for (;;) {
-        const unsigned long long old = atomicCAS(&keys[g], VOX_EMPTY, key);
-        if (old == VOX_EMPTY) fresh++;
-        if (old == VOX_EMPTY || old == key) break;
-        g = (g + 1) & mask;  // (capacity >= 2 n: an empty slot is always met)
-        len++;
-      }
+      const unsigned g = table_insert(keys, mask, (unsigned)h, key, &fresh, &len);  // (capacity >= 2 n)
       atomicMin(&first[g], (unsigned)i);
       slot[i] = g;
       probes += len;
       longest = max(longest, len);
       entered++;
     } else if (i < n) {
-      slot[i] = VOX_NONE;
+      slot[i] = SLOT_NONE;
     }
   }
   if (bad) atomicOr(&ctl->status, bad);
@@ -166,11 +141,9 @@ struct VoxelFirst {
   __device__ void write(unsigned at, const Item& i) const { kept[at] = i; }
 };
 
-// block_count[0 .. nb) -> its exclusive prefix sums, in place; the total -> ctl->n_kept.  One block; nb <= VOX_MAX_POINTS / VOX_THREADS.
-// Also sums the n_stats <= VOX_INSERT_BLOCKS block statistics of k_voxel_insert into ctl.
+// the total -> ctl->n_kept; also sums the n_stats <= VOX_INSERT_BLOCKS block statistics of k_voxel_insert into ctl.  One block.
 __global__ __launch_bounds__(VOX_THREADS) void k_voxel_scan(int nb, unsigned* block_count, VoxelCtl* ctl, int n_stats,
                                                             const VoxelBlockStats* __restrict__ block_stats) {
-  __shared__ unsigned part[VOX_THREADS];
   __shared__ unsigned long long tot[3];
   __shared__ unsigned longest;
   if (threadIdx.x < 3) tot[threadIdx.x] = 0;
@@ -183,25 +156,9 @@ __global__ __launch_bounds__(VOX_THREADS) void k_voxel_scan(int nb, unsigned* bl
     atomicAdd(&tot[2], b.entered);
     atomicMax(&longest, b.longest);
   }
-  const int per = (nb + VOX_THREADS - 1) / VOX_THREADS, lo = min((int)threadIdx.x * per, nb), hi = min(lo + per, nb);
-  unsigned sum = 0;
-  for (int b = lo; b < hi; b++) sum += block_count[b];
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  for (int d = 1; d < VOX_THREADS; d *= 2) {  // (inclusive, Hillis-Steele)
-    const unsigned add = (int)threadIdx.x >= d ? part[threadIdx.x - d] : 0u;
-    __syncthreads();
-    part[threadIdx.x] += add;
-    __syncthreads();
-  }
-  unsigned run = part[threadIdx.x] - sum;
-  for (int b = lo; b < hi; b++) {
-    const unsigned c = block_count[b];
-    block_count[b] = run;
-    run += c;
-  }
+  const unsigned total = compact_scan_counts(nb, block_count);
   if (threadIdx.x == VOX_THREADS - 1) {  // (the barriers of the scan lie between the LDS atomics above and these reads)
-    ctl->n_kept = part[VOX_THREADS - 1];
+    ctl->n_kept = total;
     ctl->probes = tot[0];
     ctl->occupied = tot[1];
     ctl->entered = tot[2];

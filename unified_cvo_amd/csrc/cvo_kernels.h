@@ -63,7 +63,9 @@
 #include "cvo_k_debug.h"
 #include "cvo_k_cloud.h"
 #include "cvo_k_irls.h"
+#include "cvo_k_prims.h"
 #include "cvo_k_compact.h"
+#include "cvo_k_sort.h"
 #include "cvo_k_voxel.h"
 #include "cvo_k_rgbd.h"
 #include "cvo_k_fast.h"

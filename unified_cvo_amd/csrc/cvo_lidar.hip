@@ -298,7 +298,7 @@ void lidar_lego_cpu(const cvo_lidar_scan_t& s, const LidarConst& k, cvo_lidar_ra
 struct LidarDevice {
   float4* pts;
   unsigned* blocks;
-  VoxelCtl* ctl;  // [4]: transitions, segmented points, draws, thinned points
+  unsigned* ctl;  // [4] totals: transitions, segmented points, draws, thinned points
   char* zero;     // stats, size, mask, cand, kept: cleared together
   size_t zero_bytes;
   LidarStats* stats;
@@ -311,7 +311,7 @@ struct LidarDevice {
 int lidar_device_layout(cvo_ctx* ctx, int n, const LidarConst& k, LidarDevice& d) {
   const size_t cells = (size_t)k.R * k.H, nb = (std::max((size_t)n, cells) + COMPACT_THREADS - 1) / COMPACT_THREADS;
   ScratchLayout l;
-  const size_t o_pts = l.take(sizeof(float4) * (size_t)n), o_blocks = l.take(sizeof(unsigned) * nb), o_ctl = l.take(sizeof(VoxelCtl) * 4);
+  const size_t o_pts = l.take(sizeof(float4) * (size_t)n), o_blocks = l.take(sizeof(unsigned) * nb), o_ctl = l.take(sizeof(unsigned) * 4);
   const size_t o_zero = l.off, o_stats = l.take(sizeof(LidarStats)), o_size = l.take(4 * cells), o_mask = l.take(16 * cells), o_cand = l.take(cells),
                o_kept = l.take(cells), zero_end = l.off;
   const size_t o_state = l.take(cells), o_valid = l.take(cells), o_occ = l.take(cells), o_quarter = l.take(cells);
@@ -325,7 +325,7 @@ int lidar_device_layout(cvo_ctx* ctx, int n, const LidarConst& k, LidarDevice& d
   char* b = ctx->lidar_scratch.p;
   d.pts = (float4*)(b + o_pts);
   d.blocks = (unsigned*)(b + o_blocks);
-  d.ctl = (VoxelCtl*)(b + o_ctl);
+  d.ctl = (unsigned*)(b + o_ctl);
   d.zero = b + o_zero;
   d.zero_bytes = zero_end - o_zero;
   d.stats = (LidarStats*)(b + o_stats);
@@ -370,7 +370,7 @@ int lidar_lego_device(cvo_ctx* ctx, const cvo_lidar_scan_t& s, const LidarConst&
   const LidarTransition tr{d.pts};
   const int nbp = (n + COMPACT_THREADS - 1) / COMPACT_THREADS;
   hipLaunchKernelGGL(k_compact_count<LidarTransition>, dim3(nbp), dim3(COMPACT_THREADS), 0, q, n, tr, d.blocks);
-  hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, q, nbp, d.blocks, d.ctl + 0, 0, (const VoxelBlockStats*)nullptr);
+  hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(COMPACT_THREADS), 0, q, nbp, d.blocks, d.ctl + 0);
   hipLaunchKernelGGL(k_lidar_project, dim3(nbp), dim3(COMPACT_THREADS), 0, q, n, tr, k, (const unsigned*)d.blocks, d.cellwin);
   hipLaunchKernelGGL(k_lidar_cells, dim3(cell_blocks), dim3(LIDAR_THREADS), 0, q, k, (const float4*)d.pts, (const int*)d.cellwin, d.range, d.state, d.parent,
                      d.stats);
@@ -379,15 +379,15 @@ int lidar_lego_device(cvo_ctx* ctx, const cvo_lidar_scan_t& s, const LidarConst&
   hipLaunchKernelGGL(k_lidar_valid, dim3(cell_blocks), dim3(LIDAR_THREADS), 0, q, k, (const int*)d.root, (const unsigned*)d.size, (const unsigned*)d.mask,
                      d.valid, d.stats);
   HIP_TRY(ctx, hipGetLastError());
-  if ((rc = compact(ctx, cells, LidarSegKeep{k.H, d.valid, d.range, d.cellwin, d.seg_cell, d.seg_col, d.seg_pt, d.seg_range}, d.blocks, d.ctl + 1)) != CVO_OK)
-    return rc;
+  const LidarSegKeep seg_keep{k.H, d.valid, d.range, d.cellwin, d.seg_cell, d.seg_col, d.seg_pt, d.seg_range};
+  if ((rc = compact(ctx, cells, seg_keep, d.blocks, scan_into(ctx, d.ctl + 1))) != CVO_OK) return rc;
   between();
-  VoxelCtl seg{};
+  unsigned seg = 0;
   if ((rc = compact_total(ctx, d.ctl + 1, cells, who, "range-image cells", &seg)) != CVO_OK) return rc;
-  const int S = (int)seg.n_kept;
+  const int S = (int)seg;
   std::vector<int> before((size_t)k.R + 1, 0), n_edge((size_t)k.R * LIDAR_SIXTHS, 0), edge_pt((size_t)k.R * LIDAR_SIXTHS * LIDAR_EDGE_CAP), out_k, out_pt;
   std::vector<unsigned char> quarter((size_t)S);
-  VoxelCtl ctl[4] = {};
+  unsigned ctl[4] = {};
   LidarStats hs{};
   cvo_lidar_rand_t ahead = *rand;
   if (S > 0) {
@@ -400,8 +400,8 @@ int lidar_lego_device(cvo_ctx* ctx, const cvo_lidar_scan_t& s, const LidarConst&
     hipLaunchKernelGGL(k_lidar_pick, dim3(k.R), dim3(LIDAR_PICK_THREADS), 0, q, S, k.edge_thr, (const int*)d.before, (const float*)d.curv,
                        (const unsigned char*)d.occluded, (const int*)d.seg_col, (const int*)d.seg_pt, d.edge_pt, d.n_edge, d.cand);
     HIP_TRY(ctx, hipGetLastError());
-    if ((rc = compact(ctx, S, LidarCand{d.cand, d.quarter, d.kept}, d.blocks, d.ctl + 2)) != CVO_OK) return rc;
-    if ((rc = compact(ctx, S, LidarKept{d.kept, d.seg_pt, d.out_k, d.out_pt}, d.blocks, d.ctl + 3)) != CVO_OK) return rc;
+    if ((rc = compact(ctx, S, LidarCand{d.cand, d.quarter, d.kept}, d.blocks, scan_into(ctx, d.ctl + 2))) != CVO_OK) return rc;
+    if ((rc = compact(ctx, S, LidarKept{d.kept, d.seg_pt, d.out_k, d.out_pt}, d.blocks, scan_into(ctx, d.ctl + 3))) != CVO_OK) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(before.data(), d.before, sizeof(int) * before.size(), hipMemcpyDeviceToHost, q));
     HIP_TRY(ctx, hipMemcpyAsync(n_edge.data(), d.n_edge, sizeof(int) * n_edge.size(), hipMemcpyDeviceToHost, q));
     HIP_TRY(ctx, hipMemcpyAsync(edge_pt.data(), d.edge_pt, sizeof(int) * edge_pt.size(), hipMemcpyDeviceToHost, q));
@@ -409,7 +409,7 @@ int lidar_lego_device(cvo_ctx* ctx, const cvo_lidar_scan_t& s, const LidarConst&
   }
   HIP_TRY(ctx, hipMemcpyAsync(&hs, d.stats, sizeof hs, hipMemcpyDeviceToHost, q));
   HIP_TRY(ctx, hipStreamSynchronize(q));
-  const unsigned draws = ctl[2].n_kept, thinned = ctl[3].n_kept;
+  const unsigned draws = ctl[2], thinned = ctl[3];
   if (draws > (unsigned)S || thinned > draws) return fail(ctx, CVO_E_HIP, std::string(who) + ": the device kept more candidates than it was given");
   out_k.resize(thinned);
   out_pt.resize(thinned);

@@ -25,7 +25,7 @@ int frame_validate(int rows, int cols, int channels, const unsigned char* image,
   const std::string wrong = calibration();
   if (!wrong.empty()) return bad(wrong);
   if (num_classes < 0 || (num_classes > 0 && !semantic)) return bad("num_classes > 0 needs the semantic image");
-  if ((long long)rows * cols > VOX_MAX_POINTS) {
+  if ((long long)rows * cols > COMPACT_MAX_ELEMENTS) {
     *msg = "more than 2^24 pixels";
     return CVO_E_UNSUPPORTED;
   }
@@ -241,7 +241,7 @@ struct RgbdDevice {
   float *g2 = nullptr, *ths = nullptr, *sm = nullptr, *xyz = nullptr;
   int *hit = nullptr, *sel = nullptr, *pix = nullptr, *out = nullptr;
   unsigned* blocks = nullptr;
-  VoxelCtl* ctl = nullptr;
+  unsigned* ctl = nullptr;  // the total of the last compaction
   unsigned char* score = nullptr;  // FAST score bytes and the frame's 257-bin histogram (cvo_fast.hip), when asked for
   unsigned* fast_hist = nullptr;
   int img_channels = 1;
@@ -273,7 +273,7 @@ int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select,
   for (int k = 0; k < RGBD_POTS; k++) cap = std::max(cap, (size_t)rgbd_cells(RGBD_POT_MIN + k, w, h));
   cap += np;
   ScratchLayout l;
-  const size_t o_ctl = l.take(sizeof(VoxelCtl)), o_img = l.take(need_select ? img_bytes : 0), o_depth = l.take(depth_bytes),
+  const size_t o_ctl = l.take(sizeof(unsigned)), o_img = l.take(need_select ? img_bytes : 0), o_depth = l.take(depth_bytes),
                o_excl = l.take(f.num_classes > 0 ? np : 0), o_g2 = l.take(need_select ? sizeof(float) * np : 0), o_ths = l.take(2 * sizeof(float) * n_ths),
                o_hit = l.take(sizeof(int) * (size_t)d.n_cells), o_sel = l.take(sizeof(int) * (size_t)d.n_cells), o_blocks = l.take(sizeof(unsigned) * nb),
                o_pix = l.take(sizeof(int) * cap), o_out = l.take(sizeof(int) * cap), o_xyz = l.take(sizeof(float) * 3 * cap),
@@ -281,7 +281,7 @@ int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select,
   const int rc = ctx->rgbd_scratch.reserve(ctx, l.off, "RGB-D scratch");
   if (rc != CVO_OK) return rc;
   char* b = ctx->rgbd_scratch.p;
-  d.ctl = (VoxelCtl*)(b + o_ctl);
+  d.ctl = (unsigned*)(b + o_ctl);
   d.img = (unsigned char*)(b + o_img);
   d.depth = b + o_depth;
   d.excl = f.num_classes > 0 ? (unsigned char*)(b + o_excl) : nullptr;
@@ -322,14 +322,14 @@ int rgbd_device_select(cvo_ctx* ctx, RgbdDevice& d, RgbdStatsAcc& stats, const i
   }
   hipLaunchKernelGGL(k_rgbd_select, dim3(d.nb_cells), dim3(RGBD_THREADS), 0, st, w, h, d.cells, (const float*)d.g2, (const float*)d.sm, d.hit,
                      d.blocks);
-  const int rc = compact_counted(ctx, d.n_cells, RgbdCellHit{d.hit, d.sel}, d.blocks, d.ctl);
+  const int rc = compact_counted(ctx, d.n_cells, RgbdCellHit{d.hit, d.sel}, d.blocks, scan_into(ctx, d.ctl));
   if (rc != CVO_OK) return rc;
   d.sel_offset.assign((size_t)d.nb_cells + 1, 0u);
-  VoxelCtl c{};
+  unsigned c = 0;
   HIP_TRY(ctx, hipMemcpyAsync(d.sel_offset.data(), d.blocks, sizeof(unsigned) * (size_t)d.nb_cells, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipMemcpyAsync(&c, d.ctl, sizeof c, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
-  d.sel_offset[d.nb_cells] = c.n_kept;
+  d.sel_offset[d.nb_cells] = c;
   auto first = [&](int pot) { return d.sel_offset[(size_t)d.cells.start[pot - RGBD_POT_MIN] / RGBD_THREADS]; };
   auto count = [&](int pot) { return (int)(d.sel_offset[(size_t)d.cells.start[pot - RGBD_POT_MIN + 1] / RGBD_THREADS] - first(pot)); };
   const int pot = rgbd_schedule(count, stats);
@@ -347,11 +347,11 @@ int frame_device_backproject(cvo_ctx* ctx, const char* who, RgbdDevice& d, P pre
   if (n == 0) return CVO_OK;
   pred.pix_out = d.pix + at;
   pred.xyz = d.xyz + 3 * (size_t)at;
-  int rc = compact(ctx, n, pred, d.blocks, d.ctl);
+  int rc = compact(ctx, n, pred, d.blocks, scan_into(ctx, d.ctl));
   if (rc != CVO_OK) return rc;
-  VoxelCtl c{};
+  unsigned c = 0;
   if ((rc = compact_total(ctx, d.ctl, n, who, "pixels", &c)) != CVO_OK) return rc;
-  *n_out = (int)c.n_kept;
+  *n_out = (int)c;
   return CVO_OK;
 }
 

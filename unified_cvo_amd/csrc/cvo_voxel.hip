@@ -36,13 +36,13 @@ void voxel_select_cpu(int n, const float* xyz, float s, std::vector<int>& kept) 
   kept.clear();
   size_t cap = 64;
   while (cap < 2 * (size_t)n) cap *= 2;
-  std::vector<unsigned long long> keys(cap, VOX_EMPTY);
+  std::vector<unsigned long long> keys(cap, TABLE_EMPTY);
   for (int i = 0; i < n; i++) {
     unsigned long long key = 0;
     (void)vox_key(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], s, &key);
-    size_t g = (size_t)vox_mix(key) & (cap - 1);
-    while (keys[g] != VOX_EMPTY && keys[g] != key) g = (g + 1) & (cap - 1);
-    if (keys[g] == VOX_EMPTY) {
+    size_t g = (size_t)key_mix(key) & (cap - 1);
+    while (keys[g] != TABLE_EMPTY && keys[g] != key) g = (g + 1) & (cap - 1);
+    if (keys[g] == TABLE_EMPTY) {
       keys[g] = key;
       kept.push_back(i);
     }
@@ -82,11 +82,15 @@ int voxel_run_device(cvo_ctx* ctx, int n, const float* xyz, const float* d_xyz_g
     hipLaunchKernelGGL(k_voxel_insert<true>, dim3(grid), dim3(VOX_THREADS), 0, st, n, d_xyz, s, mask, keys, first, slot, ctl, stats);
   else
     hipLaunchKernelGGL(k_voxel_insert<false>, dim3(grid), dim3(VOX_THREADS), 0, st, n, d_xyz, s, mask, keys, first, slot, ctl, stats);
-  if ((rc = compact(ctx, n, VoxelFirst{mask, first, slot, d_kept}, (unsigned*)(b + o_blocks), ctl, grid, stats)) != CVO_OK) return rc;
+  auto scan = [&](int nbs, unsigned* count) {  // (the selection's own: the block statistics are summed in the same launch)
+    hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, st, nbs, count, ctl, grid, (const VoxelBlockStats*)stats);
+  };
+  if ((rc = compact(ctx, n, VoxelFirst{mask, first, slot, d_kept}, (unsigned*)(b + o_blocks), scan)) != CVO_OK) return rc;
   VoxelCtl h{};
-  // (the "kept more than it was given" refusal now comes before the one of h.status; at most n points are ever kept, so the
-  // two cannot meet)
-  if ((rc = compact_total(ctx, ctl, n, "voxel selection", "points", &h)) != CVO_OK) return rc;
+  // (at most n points are ever kept: the "kept more than it was given" refusal and the one of h.status cannot meet)
+  HIP_TRY(ctx, hipMemcpyAsync(&h, ctl, sizeof h, hipMemcpyDeviceToHost, st));  // (the whole control word: one copy, one synchronisation)
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if ((rc = compact_check(ctx, h.n_kept, n, "voxel selection", "points")) != CVO_OK) return rc;
   if (h.status) {
     std::string msg;
     std::vector<float> back;
@@ -118,7 +122,7 @@ constexpr int VOX_HOST_BELOW = 4096;
 
 // Size checks + the route the context's switches choose (ctx == nullptr: the twin).  The caller holds upload_mutex.
 int voxel_select(cvo_ctx* ctx, const char* who, int n, const float* xyz, float s, std::vector<int>& kept) {
-  if (n > VOX_MAX_POINTS) return fail(ctx, CVO_E_UNSUPPORTED, std::string(who) + ": more than 2^24 points");
+  if (n > COMPACT_MAX_ELEMENTS) return fail(ctx, CVO_E_UNSUPPORTED, std::string(who) + ": more than 2^24 points");
   std::string msg;
   if (voxel_validate(0, nullptr, s, &msg) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": " + msg);
   kept.clear();
