@@ -209,16 +209,20 @@ unsigned bki_stride_blocks(unsigned long long n) { return std::max(1u, std::min(
 int bki_table_alloc(cvo_map* m, unsigned long long slots, BkiTable* t, char** slab) {
   cvo_ctx* ctx = m->ctx;
   const BkiConst& k = m->k;
-  ScratchLayout lay;
   const int ncnt = k.nclass + 1;
-  const size_t o_keys = lay.take(8 * slots), o_ms = lay.take(4 * slots * (size_t)k.nclass), o_fs = lay.take(4 * slots * BKI_FEAT),
-               o_cnt = lay.take(4 * slots * (size_t)ncnt), o_seg = lay.take(4 * slots);
+  *t = BkiTable{nullptr, nullptr, nullptr, nullptr, nullptr, (unsigned)(slots - 1), k.nclass, ncnt};
+  auto list = [&](ScratchLayout& l) {
+    l.take(t->keys, slots);
+    l.take(t->ms, slots * (size_t)k.nclass);
+    l.take(t->fs, slots * BKI_FEAT);
+    l.take(t->cnt, slots * (size_t)ncnt);
+    l.take(t->segoff, slots);
+  };
   char* p = nullptr;
-  const hipError_t e = hipMalloc(&p, lay.off);
+  const hipError_t e = hipMalloc(&p, ScratchLayout().walk(list));
   if (e != hipSuccess) return fail(ctx, CVO_E_NOMEM, std::string("voxel map table hipMalloc: ") + hipGetErrorString(e));
   *slab = p;
-  *t = BkiTable{(unsigned long long*)(p + o_keys), (float*)(p + o_ms), (float*)(p + o_fs), (unsigned*)(p + o_cnt), (unsigned*)(p + o_seg),
-                (unsigned)(slots - 1), k.nclass, ncnt};
+  ScratchLayout(p).walk(list);
   hipStream_t st = ctx->upload_stream;
   hipError_t r = hipMemsetAsync(t->keys, 0xFF, 8 * slots, st);
   if (r == hipSuccess) r = hipMemsetAsync(t->fs, 0, 4 * slots * BKI_FEAT, st);
@@ -273,23 +277,20 @@ int bki_insert_device(cvo_map* m, int n, const float* xyz, const float* feat, co
   hipStream_t st = ctx->upload_stream;
   const BkiConst& k = m->k;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ScratchLayout lay;
   const size_t nn = (size_t)n;
-  const size_t o_ctl = lay.take(sizeof(BkiCtl)), o_xyz = lay.take(12 * nn), o_feat = lay.take(feat ? 4 * BKI_FEAT * nn : 0),
-               o_label = lay.take(k.C > 0 ? 4 * (size_t)k.C * nn : 0), o_mc = lay.take(4 * (nn + 1)), o_hslot = lay.take(4 * BKI_HIT_SLOTS * nn);
-  int rc;
-  if ((rc = m->in_scratch.reserve(ctx, lay.off, "voxel map insert scratch")) != CVO_OK) return rc;
-  char* base = m->in_scratch.p;
   BkiInsertArgs a{};
   a.k = k;
   a.n = n;
-  a.xyz = (const float*)(base + o_xyz);
-  a.feat = feat ? (const float*)(base + o_feat) : nullptr;
-  a.label = k.C > 0 ? (const float*)(base + o_label) : nullptr;
   for (int q = 0; q < 3; q++) a.origin[q] = origin[q];
-  a.mc = (unsigned*)(base + o_mc);
-  a.hslot = (unsigned*)(base + o_hslot);
-  a.ctl = (BkiCtl*)(base + o_ctl);
+  int rc = m->in_scratch.lay_out(ctx, "voxel map insert scratch", [&](ScratchLayout& l) {
+    l.take(a.ctl, 1);
+    l.take(a.xyz, 3 * nn);
+    if (feat) l.take(a.feat, BKI_FEAT * nn);
+    if (k.C > 0) l.take(a.label, (size_t)k.C * nn);
+    l.take(a.mc, nn + 1);
+    l.take(a.hslot, BKI_HIT_SLOTS * nn);
+  });
+  if (rc != CVO_OK) return rc;
   BkiCtl h{};
   h.bad_index = ~0u;
   HIP_TRY(ctx, hipMemcpyAsync(a.ctl, &h, sizeof h, hipMemcpyHostToDevice, st));
@@ -307,17 +308,15 @@ int bki_insert_device(cvo_map* m, int n, const float* xyz, const float* feat, co
   if (h.training >= (unsigned long long)BKI_MAX_TRAINING) return fail(ctx, CVO_E_UNSUPPORTED, "cvo_map_insert: 2^24 training points or more in one insert");
   if (h.status) return fail(ctx, h.status & BKI_BAD_RANGE ? CVO_E_INVALID : CVO_E_UNSUPPORTED, "cvo_map_insert: " + bki_bad_text(h.status, h.bad_index, n));
   // the work arrays, and room in the table for every membership to be a new voxel
-  ScratchLayout work;
-  const size_t o_rec = work.take(4 * h.members), o_seg = work.take(4 * h.hit_members), o_seg2 = work.take(4 * h.hit_members),
-               o_long = work.take(8 * (h.hit_members / (BKI_SHORT_RUN + 1) + 1));
-  if ((rc = m->work_scratch.reserve(ctx, work.off, "voxel map work scratch")) != CVO_OK) return rc;
+  rc = m->work_scratch.lay_out(ctx, "voxel map work scratch", [&](ScratchLayout& l) {
+    l.take(a.rec, h.members);
+    l.take(a.seg, h.hit_members);
+    l.take(a.seg2, h.hit_members);
+    l.take(a.longlist, 2 * (h.hit_members / (BKI_SHORT_RUN + 1) + 1));  // ((slot, hits) per voxel)
+  });
+  if (rc != CVO_OK) return rc;
   if ((rc = bki_table_grow(m, m->voxels + h.members)) != CVO_OK) return rc;
-  char* w = m->work_scratch.p;
   a.t = m->t;
-  a.rec = (unsigned*)(w + o_rec);
-  a.seg = (unsigned*)(w + o_seg);
-  a.seg2 = (unsigned*)(w + o_seg2);
-  a.longlist = (unsigned*)(w + o_long);
   m->broken = true;  // (until the table's counters are back at zero)
   m->occupied = -1;
   hipLaunchKernelGGL(k_bki_emit, per_hit, block, 0, st, a);
@@ -340,22 +339,24 @@ int bki_insert_device(cvo_map* m, int n, const float* xyz, const float* feat, co
 
 // Collects and sorts the occupied voxels of a device map; *okey / *oslot point at the sorted arrays in work_scratch, *rows at
 // room for the rows behind them.  count_only: one pass over the table that writes nothing but the number.
-int bki_collect_device(cvo_map* m, bool count_only, unsigned* n_occ, const unsigned long long** okey, const unsigned** oslot, char** rows) {
+int bki_collect_device(cvo_map* m, bool count_only, unsigned* n_occ, const unsigned long long** okey, const unsigned** oslot, float** rows) {
   cvo_ctx* ctx = m->ctx;
   hipStream_t st = ctx->upload_stream;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t V = count_only ? 0 : (size_t)m->voxels, nbmax = bki_blocks(V);
-  ScratchLayout lay;
-  const size_t o_ctl = lay.take(sizeof(BkiCtl)), o_k0 = lay.take(8 * V), o_k1 = lay.take(8 * V), o_s0 = lay.take(4 * V), o_s1 = lay.take(4 * V),
-               o_hist = lay.take(4 * 256 * nbmax), o_rows = lay.take(4 * V * (size_t)(3 + BKI_FEAT + BKI_MAX_CLASSES));
-  int rc;
-  if ((rc = m->work_scratch.reserve(ctx, lay.off, "voxel map work scratch")) != CVO_OK) return rc;
-  char* w = m->work_scratch.p;
-  BkiCtl* ctl = (BkiCtl*)(w + o_ctl);
-  unsigned long long* key[2] = {(unsigned long long*)(w + o_k0), (unsigned long long*)(w + o_k1)};
-  unsigned* slot[2] = {(unsigned*)(w + o_s0), (unsigned*)(w + o_s1)};
-  unsigned* hist = (unsigned*)(w + o_hist);
-  *rows = w + o_rows;
+  BkiCtl* ctl = nullptr;
+  unsigned long long* key[2] = {nullptr, nullptr};
+  unsigned *slot[2] = {nullptr, nullptr}, *hist = nullptr;
+  const int rc = m->work_scratch.lay_out(ctx, "voxel map work scratch", [&](ScratchLayout& l) {
+    l.take(ctl, 1);
+    l.take(key[0], V);
+    l.take(key[1], V);
+    l.take(slot[0], V);
+    l.take(slot[1], V);
+    l.take(hist, 256 * nbmax);
+    l.take(*rows, V * (size_t)(3 + BKI_FEAT + BKI_MAX_CLASSES));
+  });
+  if (rc != CVO_OK) return rc;
   *okey = key[0];
   *oslot = slot[0];
   *n_occ = 0;
@@ -403,12 +404,11 @@ int bki_rows(cvo_map* m, bool want_rows, BkiRows* out) {
   unsigned n = 0;
   const unsigned long long* okey;
   const unsigned* oslot;
-  char* rows;
-  const int rc = bki_collect_device(m, !want_rows, &n, &okey, &oslot, &rows);
+  float* d_xyz;
+  const int rc = bki_collect_device(m, !want_rows, &n, &okey, &oslot, &d_xyz);
   if (rc != CVO_OK) return rc;
   out->n = n;
   if (!want_rows || !n) return CVO_OK;
-  float* d_xyz = (float*)rows;
   float* d_feat = d_xyz + 3 * (size_t)n;
   float* d_label = d_feat + BKI_FEAT * (size_t)n;
   hipStream_t st = ctx->upload_stream;

@@ -33,53 +33,48 @@ Dims make_dims(int N, int M) {
 // returns the slot's size.  Sizing a slot is the same walk from base 0 into a descriptor nobody uses (plan_batch).  N:
 // the call's largest source cloud, d: make_dims of the call's largest clouds; every region ends on a multiple of 256 bytes.
 size_t place_regions(PairDesc& D, uintptr_t base, int N, const Dims& d, int Kmax, int trace_capacity, bool long_lists) {
-  size_t off = 0;
-  auto at = [&](auto*& ptr, size_t offset) { ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + offset); };
-  auto take = [&](auto*& ptr, size_t count) {  // `count` elements of the pointer's own type
-    at(ptr, off);
-    off = align_up(off + sizeof(*ptr) * count, 256);
-  };
+  ScratchLayout l((const void*)base);
   const size_t n = (size_t)N, words = (n + 63) / 64, nba = (size_t)d.nblk_assoc;
   // the row arrays of the per-iteration kernels first, at the fixed offsets of cvo_device.h (row_off_*)
-  at(D.cand_cnt, row_off_cand_cnt(d.Npad));
-  at(D.ip, row_off_ip(d.Npad));
-  at(D.nnz_row, row_off_nnz(d.Npad));
-  at(D.xp4, row_off_xp4(d.Npad));
-  at(D.cand_j, row_off_cand_j(d.Npad));  // ASSOC_CAP16 x u16 == ASSOC_CAP32 x i32 == 128 bytes per row
-  off = row_off_ell(d.Npad);
-  take(D.ell, (size_t)d.Npad * Kmax);
-  take(D.ell_j, (size_t)d.Npad * Kmax);
-  take(D.ycull, (size_t)d.Mpad);
-  take(D.xcull, n + XCULL_PAD);
-  take(D.gbox, 2 * (size_t)d.NGpad);
-  take(D.cellbox, 2 * (size_t)(d.NGpad / 16));
-  take(D.sbox, 2 * (size_t)d.nchunks);
-  take(D.masks, (n + 8) * d.nchunks);
-  take(D.rowbits, (size_t)(N + 4) * d.rbw_max);
-  take(D.row_cnt, n);
-  take(D.tile_count, 1);
-  take(D.ovf_rows, n);
-  take(D.ovf_bits, words + 4);
-  take(D.gate, 1);
-  take(D.gate_flow, 1);
-  take(D.dense_off, n);
-  take(D.dense_rel, n);
-  take(D.ovf_wsum, words + 4);
-  take(D.word_base, words + 5);
-  take(D.done, 1);
-  take(D.rowperm, n);
-  take(D.iorig, n);
-  take(D.long_stamp, n);
-  if (long_lists) take(D.long_j, n * LONG_CAP);
-  take(D.rowres, n);
+  l.at(D.cand_cnt, row_off_cand_cnt(d.Npad));
+  l.at(D.ip, row_off_ip(d.Npad));
+  l.at(D.nnz_row, row_off_nnz(d.Npad));
+  l.at(D.xp4, row_off_xp4(d.Npad));
+  l.at(D.cand_j, row_off_cand_j(d.Npad));  // ASSOC_CAP16 x u16 == ASSOC_CAP32 x i32 == 128 bytes per row
+  l.off = row_off_ell(d.Npad);
+  l.take(D.ell, (size_t)d.Npad * Kmax);
+  l.take(D.ell_j, (size_t)d.Npad * Kmax);
+  l.take(D.ycull, (size_t)d.Mpad);
+  l.take(D.xcull, n + XCULL_PAD);
+  l.take(D.gbox, 2 * (size_t)d.NGpad);
+  l.take(D.cellbox, 2 * (size_t)(d.NGpad / 16));
+  l.take(D.sbox, 2 * (size_t)d.nchunks);
+  l.take(D.masks, (n + 8) * d.nchunks);
+  l.take(D.rowbits, (size_t)(N + 4) * d.rbw_max);
+  l.take(D.row_cnt, n);
+  l.take(D.tile_count, 1);
+  l.take(D.ovf_rows, n);
+  l.take(D.ovf_bits, words + 4);
+  l.take(D.gate, 1);
+  l.take(D.gate_flow, 1);
+  l.take(D.dense_off, n);
+  l.take(D.dense_rel, n);
+  l.take(D.ovf_wsum, words + 4);
+  l.take(D.word_base, words + 5);
+  l.take(D.done, 1);
+  l.take(D.rowperm, n);
+  l.take(D.iorig, n);
+  l.take(D.long_stamp, n);
+  if (long_lists) l.take(D.long_j, n * LONG_CAP);
+  l.take(D.rowres, n);
   // (rows x the pair's own coefficient split, coeff_split(): one slice above 4096 points, at most 32768 / rows below)
-  take(D.rowcoef, 4 * (size_t)std::max(N, 32768));
-  take(D.flow_part, FLOW_GRANULES * nba);
-  take(D.cnt_part, 4 * nba);
-  take(D.coef_part, COEF_GRANULES * nba * COEFF_SPLIT_MAX);  // (the coefficient phase uses the association's row blocks)
-  take(D.shadow, SHADOW_WORDS);
-  if (trace_capacity > 0) take(D.trace, (size_t)trace_capacity);
-  return off;
+  l.take(D.rowcoef, 4 * (size_t)std::max(N, 32768));
+  l.take(D.flow_part, FLOW_GRANULES * nba);
+  l.take(D.cnt_part, 4 * nba);
+  l.take(D.coef_part, COEF_GRANULES * nba * COEFF_SPLIT_MAX);  // (the coefficient phase uses the association's row blocks)
+  l.take(D.shadow, SHADOW_WORDS);
+  if (trace_capacity > 0) l.take(D.trace, (size_t)trace_capacity);
+  return l.off;
 }
 
 void free_control_block(cvo_ctx* c) {

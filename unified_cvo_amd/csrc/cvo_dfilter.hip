@@ -131,13 +131,24 @@ void dfilter_cpu(const DFilterConst& k, float* d, DFilterStatsAcc& stats) {
 int dfilter_device(cvo_ctx* ctx, const DFilterConst& k, const float* in, const float* d_in, float* out, DFilterStatsAcc& stats) {
   hipStream_t st = ctx->upload_stream;
   const size_t np = (size_t)k.rows * k.cols, map = 4 * np;
-  ScratchLayout lay;
-  const size_t o_in = lay.take(map), o_parent = lay.take(map), o_root = lay.take(map), o_size = lay.take(map), o_prev = lay.take(map);
-  const size_t o_speckle = lay.take(map), o_gap_rows = lay.take(map), o_gap = lay.take(map), o_tmp = lay.take(map);
-  const size_t o_out = lay.take(map + sizeof(DFilterCounters));  // the counters behind the map: one download
-  int rc;
-  if ((rc = ctx->dfilter_scratch.reserve(ctx, lay.off, "disparity filter scratch")) != CVO_OK) return rc;
-  char* base = ctx->dfilter_scratch.p;
+  float *d_map = nullptr, *d_speckle = nullptr, *d_gap_rows = nullptr, *d_gap = nullptr, *d_tmp = nullptr, *d_out = nullptr;
+  DFilterSpeckleArgs a;
+  DFilterGapArgs g;
+  const int rc = ctx->dfilter_scratch.lay_out(ctx, "disparity filter scratch", [&](ScratchLayout& l) {
+    l.take(d_map, np);
+    l.take(a.parent, np);
+    l.take(a.root, np);
+    l.take(a.size, np);
+    l.take(g.prev, np);
+    l.take(d_speckle, np);
+    l.take(d_gap_rows, np);
+    l.take(d_gap, np);
+    l.take(d_tmp, np);
+    l.take_as<char>(d_out, map + sizeof(DFilterCounters));  // the counters behind the map: one download
+  });
+  if (rc != CVO_OK) return rc;
+  // (the read-back keeps offsets, not pointers: a later refused call may move the region while this call's record stands)
+  auto offset_of = [&](const float* p) { return (size_t)((const char*)p - ctx->dfilter_scratch.p); };
   // pinned staging: [the map going up][the result and its counters coming down]
   const size_t down = align_up(map, 256), staging = down + map + sizeof(DFilterCounters);
   if (staging > ctx->dfilter_staging_bytes) {
@@ -150,26 +161,22 @@ int dfilter_device(cvo_ctx* ctx, const DFilterConst& k, const float* in, const f
     ctx->dfilter_staging_bytes = staging;
   }
   char* host = ctx->dfilter_staging;
-  DFilterCounters* counters = (DFilterCounters*)(base + o_out + map);
+  DFilterCounters* counters = (DFilterCounters*)(d_out + np);
   HIP_TRY(ctx, hipMemsetAsync(counters, 0, sizeof *counters, st));
   if (!d_in) {
     std::memcpy(host, in, map);
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_in, host, map, hipMemcpyHostToDevice, st));
-    d_in = (const float*)(base + o_in);
+    HIP_TRY(ctx, hipMemcpyAsync(d_map, host, map, hipMemcpyHostToDevice, st));
+    d_in = d_map;
   }
   const int tiles_x = (k.cols + DFILTER_TILE_W - 1) / DFILTER_TILE_W;
   const dim3 grid((unsigned)tiles_x * (unsigned)((k.rows + DFILTER_TILE_H - 1) / DFILTER_TILE_H)), block(DFILTER_THREADS);  // (at most 2^24 pixels)
   const bool speckle = k.speckle_size > 1, gap = k.gap_width >= 1, mean = k.mean != 0;
   // the last stage that runs writes the result; a stage that does not run passes its input on
   const float* cur = d_in;
-  const size_t o_speckle_out = gap || mean ? o_speckle : o_out, o_gap_out = mean ? o_gap : o_out;
+  float *const speckle_out = gap || mean ? d_speckle : d_out, *const gap_out = mean ? d_gap : d_out;
   if (speckle) {
-    DFilterSpeckleArgs a;
     a.src = cur;
-    a.out = (float*)(base + o_speckle_out);
-    a.parent = (int*)(base + o_parent);
-    a.root = (int*)(base + o_root);
-    a.size = (unsigned*)(base + o_size);
+    a.out = speckle_out;
     a.counters = counters;
     a.rows = k.rows;
     a.cols = k.cols;
@@ -182,13 +189,11 @@ int dfilter_device(cvo_ctx* ctx, const DFilterConst& k, const float* in, const f
     hipLaunchKernelGGL(k_dfilter_mask, grid, block, 0, st, a);
     cur = a.out;
   }
-  stats.o_speckle = speckle ? o_speckle_out : 0;
+  stats.o_speckle = speckle ? offset_of(speckle_out) : 0;
   stats.speckle_resident = speckle;
   if (gap) {
-    DFilterGapArgs g;
     g.in = cur;
-    g.out = (float*)(base + o_gap_rows);
-    g.prev = (int*)(base + o_prev);
+    g.out = d_gap_rows;
     g.filled = &counters->filled_rows;
     g.n_lines = k.rows;
     g.len = k.cols;
@@ -197,7 +202,7 @@ int dfilter_device(cvo_ctx* ctx, const DFilterConst& k, const float* in, const f
     g.width = k.gap_width;
     hipLaunchKernelGGL(k_dfilter_gap, dim3((unsigned)g.n_lines), dim3(64), 0, st, g);
     g.in = g.out;
-    g.out = (float*)(base + o_gap_out);
+    g.out = gap_out;
     g.filled = &counters->filled_cols;
     g.n_lines = k.cols;
     g.len = k.rows;
@@ -206,27 +211,27 @@ int dfilter_device(cvo_ctx* ctx, const DFilterConst& k, const float* in, const f
     hipLaunchKernelGGL(k_dfilter_gap, dim3((unsigned)g.n_lines), dim3(64), 0, st, g);
     cur = g.out;
   }
-  stats.o_gap = gap ? o_gap_out : stats.o_speckle;
+  stats.o_gap = gap ? offset_of(gap_out) : stats.o_speckle;
   stats.gap_resident = speckle || gap;
   if (mean) {
     DFilterMeanArgs m;
     m.in = cur;
     m.tmp = nullptr;
-    m.out = (float*)(base + o_tmp);
+    m.out = d_tmp;
     m.rows = k.rows;
     m.cols = k.cols;
     m.tiles_x = tiles_x;
     hipLaunchKernelGGL(k_dfilter_mean_h, grid, block, 0, st, m);
     m.tmp = m.out;
-    m.out = (float*)(base + o_out);
+    m.out = d_out;
     hipLaunchKernelGGL(k_dfilter_mean_v, grid, block, 0, st, m);
     cur = m.out;
   }
-  stats.o_tmp = o_tmp;
+  stats.o_tmp = offset_of(d_tmp);
   stats.tmp_resident = mean;
-  if (cur != (const float*)(base + o_out)) HIP_TRY(ctx, hipMemcpyAsync(base + o_out, cur, map, hipMemcpyDeviceToDevice, st));  // (every stage off)
+  if (cur != d_out) HIP_TRY(ctx, hipMemcpyAsync(d_out, cur, map, hipMemcpyDeviceToDevice, st));  // (every stage off)
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(host + down, base + o_out, map + sizeof(DFilterCounters), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(host + down, d_out, map + sizeof(DFilterCounters), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   std::memcpy(out, host + down, map);  // (nothing is written unless the call succeeds)
   DFilterCounters c;

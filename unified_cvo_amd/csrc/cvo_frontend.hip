@@ -1,6 +1,6 @@
 // cvo_frontend.hip -- what the front ends (cvo_voxel.hip, cvo_rgbd.hip, cvo_fast.hip, cvo_stereo.hip, cvo_lidar.hip, cvo_nlm.hip,
-// cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip) share on the host: the growable scratch regions (type and layout:
-// cvo_internal.h), the launches of an ordered compaction (cvo_k_compact.h) and of the radix sort (cvo_k_sort.h), the read-back of
+// cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip) share on the host: the growable scratch regions (a front end writes ONE list of its buffers, DeviceScratch::lay_out
+// sizes and binds it: cvo_internal.h), the launches of an ordered compaction (cvo_k_compact.h) and of the radix sort (cvo_k_sort.h), the read-back of
 // a compaction's total, the route rule, the frame of an entry point and the copy-out of the kept indices.
 // A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.  Shared declarations: cvo_internal.h.
 //

@@ -1,6 +1,6 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip, cvo_bki.hip, cvo_debug.hip) share: the context, a resident cloud, the workspace layout of a
-// pair, graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip, cvo_bki.hip, cvo_debug.hip) share: the context, a resident cloud, the typed walk that lays
+// out EVERY device region (ScratchLayout: a pair's workspace, the front ends' scratch, the map's table, a cloud's slabs), graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -30,12 +30,9 @@ using namespace cvo_dev;
 
 #define CVO_VERSION_STRING "unified_cvo_amd 0.1 (gfx950)"
 
-struct cvo_cloud {
-  cvo_ctx* ctx = nullptr;  // identity check only: never dereferenced after upload (the context may be gone)
-  int device = 0;
-  int n = 0;
-  char* slab = nullptr;     // the one device allocation behind the pointers below
-  size_t slab_bytes = 0;
+// The arrays of a cloud's slab (upload_host_cloud's list): a cloud's own, and the same list over the staging buffer the slab
+// is uploaded from.  An array the caller did not supply stays null.
+struct CloudArrays {
   float4* x4 = nullptr;
   float4* xs4 = nullptr;    // x4 permuted into the spatial order
   float4* feat = nullptr;   // 2 float4 per point      } in SPATIAL order (position r = point order[r]): the kernels
@@ -43,14 +40,26 @@ struct cvo_cloud {
   float2* geo = nullptr;    //                         } gather per candidate
   int* lid = nullptr;       // class id per point, spatial order: only when EVERY label row is an exact one-hot (a single
                             // 1.0f, the rest 0.0f) - the semantic kernel then needs 4 bytes per candidate, not 80
+  int* order = nullptr;        // spatial (k-d) order: sorted position -> original index
+  int* inv = nullptr;          // its inverse: original index -> sorted position
+  // a cloud ordered on the device: the caller's rows in ORIGINAL order and the scratch of k_kd_order, null otherwise
+  float *raw_feat = nullptr, *raw_label = nullptr, *raw_geo = nullptr;
+  int* raw_lid = nullptr;
+  unsigned short *seg_of_pos = nullptr, *seg_lo = nullptr;
+};
+
+struct cvo_cloud : CloudArrays {
+  cvo_ctx* ctx = nullptr;  // identity check only: never dereferenced after upload (the context may be gone)
+  int device = 0;
+  int n = 0;
+  char* slab = nullptr;     // the one device allocation behind the arrays
+  size_t slab_bytes = 0;
   // Attributes the caller did not supply are zeros (what the reference leaves in the default-constructed CvoPoint).
   // They are not uploaded: a zeroed slab is allocated the first time a call needs them (colour / semantic /
   // geometric-type kernels on a cloud without those arrays), see ensure_attributes.
   mutable char* zero_slab = nullptr;
   // bounding spheres of the 64-point tiles of xs4 (k_tile_spheres), made the first time k_overlap reads this cloud
   mutable float4* tile4 = nullptr;
-  int* order = nullptr;        // spatial (k-d) order: sorted position -> original index
-  int* inv = nullptr;          // its inverse: original index -> sorted position
   std::vector<int> h_order;  // host copy (the ELL is stored by sorted row; exports map it back)
   float cx = 0, cy = 0, cz = 0;  // centroid (used only as the cull centre)
   float rmax = 0;                // largest |p| (bounds the motion of any point under a pose change)
@@ -179,14 +188,30 @@ struct DFilterStatsAcc {
   bool speckle_resident = false, gap_resident = false, tmp_resident = false;
 };
 
-// offsets of a call's buffers in one device allocation, 256-byte aligned; `off` ends as the bytes to allocate
+// THE walk over the buffers of one allocation (a pair's workspace slot, a front end's scratch region, the map's table, a
+// cloud's slab and its staging copy): a layout is ONE list of take(pointer, count) lines, and this is the only code that
+// turns "offset, align, cast" into a pointer.  Every buffer begins on a multiple of 256 bytes from `base`; `off` ends as the
+// bytes to allocate, so sizing a region is the same list walked from base 0 into pointers nobody reads.
 struct ScratchLayout {
+  uintptr_t base;
   size_t off = 0;
-  size_t take(size_t bytes) {
-    const size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
+  explicit ScratchLayout(const void* at = nullptr) : base((uintptr_t)at) {}
+  // one walk of a list(ScratchLayout&) from `base`: its pointers bound there; returns the bytes its buffers need
+  template <class List>
+  size_t walk(List&& list) { return list(*this), off; }
+  // a fixed position (row_off_*), or - offset == off - where the next buffer will begin
+  template <class T>
+  void at(T*& ptr, size_t offset) const { ptr = reinterpret_cast<T*>(base + offset); }
+  // `count` elements of type E behind a pointer of another type: the void* fields, and a byte count that is no multiple
+  // of the pointer's element
+  template <class E, class T>
+  void take_as(T*& ptr, size_t count) {
+    at(ptr, off);
+    off = align_up(off + sizeof(E) * count, 256);
   }
+  // `count` elements of the pointer's own type
+  template <class T>
+  void take(T*& ptr, size_t count) { take_as<T>(ptr, count); }
 };
 
 // a growable device region of a front end, laid out anew by every call and used on upload_stream under upload_mutex
@@ -194,6 +219,15 @@ struct DeviceScratch {
   char* p = nullptr;
   size_t bytes = 0;
   int reserve(cvo_ctx* ctx, size_t need, const char* what);  // cvo_frontend.hip; what: "voxel scratch", "RGB-D scratch"
+  // Room for the buffers of `list(ScratchLayout&)`, then the list's pointers bound to them: the list sizes the region from
+  // base 0 and is walked again from where the region is AFTER reserve, so no pointer outlives a reallocation.
+  template <class List>
+  int lay_out(cvo_ctx* ctx, const char* what, List list) {
+    const int rc = reserve(ctx, ScratchLayout().walk(list), what);
+    if (rc != CVO_OK) return rc;
+    ScratchLayout(p).walk(list);
+    return CVO_OK;
+  }
   void release() {
     if (p) (void)hipFree(p);
     p = nullptr;

@@ -299,8 +299,7 @@ struct LidarDevice {
   float4* pts;
   unsigned* blocks;
   unsigned* ctl;  // [4] totals: transitions, segmented points, draws, thinned points
-  char* zero;     // stats, size, mask, cand, kept: cleared together
-  size_t zero_bytes;
+  char *zero, *zero_end;  // stats, size, mask, cand, kept: cleared together
   LidarStats* stats;
   unsigned *size, *mask;
   unsigned char *cand, *kept, *state, *valid, *occluded, *quarter;
@@ -310,48 +309,36 @@ struct LidarDevice {
 
 int lidar_device_layout(cvo_ctx* ctx, int n, const LidarConst& k, LidarDevice& d) {
   const size_t cells = (size_t)k.R * k.H, nb = (std::max((size_t)n, cells) + COMPACT_THREADS - 1) / COMPACT_THREADS;
-  ScratchLayout l;
-  const size_t o_pts = l.take(sizeof(float4) * (size_t)n), o_blocks = l.take(sizeof(unsigned) * nb), o_ctl = l.take(sizeof(unsigned) * 4);
-  const size_t o_zero = l.off, o_stats = l.take(sizeof(LidarStats)), o_size = l.take(4 * cells), o_mask = l.take(16 * cells), o_cand = l.take(cells),
-               o_kept = l.take(cells), zero_end = l.off;
-  const size_t o_state = l.take(cells), o_valid = l.take(cells), o_occ = l.take(cells), o_quarter = l.take(cells);
-  const size_t o_cellwin = l.take(4 * cells), o_parent = l.take(4 * cells), o_root = l.take(4 * cells), o_seg_cell = l.take(4 * cells),
-               o_seg_col = l.take(4 * cells), o_seg_pt = l.take(4 * cells), o_before = l.take(4 * ((size_t)k.R + 1)),
-               o_edge_pt = l.take(4 * (size_t)k.R * LIDAR_SIXTHS * LIDAR_EDGE_CAP), o_n_edge = l.take(4 * (size_t)k.R * LIDAR_SIXTHS),
-               o_out_k = l.take(4 * cells), o_out_pt = l.take(4 * cells), o_range = l.take(4 * cells), o_seg_range = l.take(4 * cells),
-               o_curv = l.take(4 * cells);
-  const int rc = ctx->lidar_scratch.reserve(ctx, l.off, "LiDAR scratch");
-  if (rc != CVO_OK) return rc;
-  char* b = ctx->lidar_scratch.p;
-  d.pts = (float4*)(b + o_pts);
-  d.blocks = (unsigned*)(b + o_blocks);
-  d.ctl = (unsigned*)(b + o_ctl);
-  d.zero = b + o_zero;
-  d.zero_bytes = zero_end - o_zero;
-  d.stats = (LidarStats*)(b + o_stats);
-  d.size = (unsigned*)(b + o_size);
-  d.mask = (unsigned*)(b + o_mask);
-  d.cand = (unsigned char*)(b + o_cand);
-  d.kept = (unsigned char*)(b + o_kept);
-  d.state = (unsigned char*)(b + o_state);
-  d.valid = (unsigned char*)(b + o_valid);
-  d.occluded = (unsigned char*)(b + o_occ);
-  d.quarter = (unsigned char*)(b + o_quarter);
-  d.cellwin = (int*)(b + o_cellwin);
-  d.parent = (int*)(b + o_parent);
-  d.root = (int*)(b + o_root);
-  d.seg_cell = (int*)(b + o_seg_cell);
-  d.seg_col = (int*)(b + o_seg_col);
-  d.seg_pt = (int*)(b + o_seg_pt);
-  d.before = (int*)(b + o_before);
-  d.edge_pt = (int*)(b + o_edge_pt);
-  d.n_edge = (int*)(b + o_n_edge);
-  d.out_k = (int*)(b + o_out_k);
-  d.out_pt = (int*)(b + o_out_pt);
-  d.range = (float*)(b + o_range);
-  d.seg_range = (float*)(b + o_seg_range);
-  d.curv = (float*)(b + o_curv);
-  return CVO_OK;
+  return ctx->lidar_scratch.lay_out(ctx, "LiDAR scratch", [&](ScratchLayout& l) {
+    l.take(d.pts, (size_t)n);
+    l.take(d.blocks, nb);
+    l.take(d.ctl, 4);
+    l.at(d.zero, l.off);
+    l.take(d.stats, 1);
+    l.take(d.size, cells);
+    l.take(d.mask, 4 * cells);  // (four words of row bits per cell)
+    l.take(d.cand, cells);
+    l.take(d.kept, cells);
+    l.at(d.zero_end, l.off);
+    l.take(d.state, cells);
+    l.take(d.valid, cells);
+    l.take(d.occluded, cells);
+    l.take(d.quarter, cells);
+    l.take(d.cellwin, cells);
+    l.take(d.parent, cells);
+    l.take(d.root, cells);
+    l.take(d.seg_cell, cells);
+    l.take(d.seg_col, cells);
+    l.take(d.seg_pt, cells);
+    l.take(d.before, (size_t)k.R + 1);
+    l.take(d.edge_pt, (size_t)k.R * LIDAR_SIXTHS * LIDAR_EDGE_CAP);
+    l.take(d.n_edge, (size_t)k.R * LIDAR_SIXTHS);
+    l.take(d.out_k, cells);
+    l.take(d.out_pt, cells);
+    l.take(d.range, cells);
+    l.take(d.seg_range, cells);
+    l.take(d.curv, cells);
+  });
 }
 
 // `between`: host work that needs no device result (edge_detection), run while the range-image kernels do
@@ -365,7 +352,7 @@ int lidar_lego_device(cvo_ctx* ctx, const cvo_lidar_scan_t& s, const LidarConst&
   int rc = lidar_device_layout(ctx, n, k, d);
   if (rc != CVO_OK) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(d.pts, s.xyzi, sizeof(float4) * (size_t)n, hipMemcpyHostToDevice, q));
-  HIP_TRY(ctx, hipMemsetAsync(d.zero, 0, d.zero_bytes, q));
+  HIP_TRY(ctx, hipMemsetAsync(d.zero, 0, (size_t)(d.zero_end - d.zero), q));
   HIP_TRY(ctx, hipMemsetAsync(d.cellwin, 0xff, sizeof(int) * (size_t)cells, q));
   const LidarTransition tr{d.pts};
   const int nbp = (n + COMPACT_THREADS - 1) / COMPACT_THREADS;

@@ -150,25 +150,26 @@ int nlm_device(cvo_ctx* ctx, int rows, int cols, int stride, const unsigned char
                NlmStatsAcc& stats) {
   hipStream_t st = ctx->upload_stream;
   const size_t bytes = (size_t)rows * cols * stride;
-  ScratchLayout lay;
-  const size_t o_src = lay.take(bytes), o_dst = lay.take(bytes);
-  size_t o_w[2] = {0, 0};
-  for (int i = 0; i < n_pass; i++) o_w[i] = lay.take(sizeof(int) * (size_t)pass[i].table->n_nonzero);
-  int rc;
-  if ((rc = ctx->nlm_scratch.reserve(ctx, lay.off, "denoising scratch")) != CVO_OK) return rc;
-  char* base = ctx->nlm_scratch.p;
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_src, src, bytes, hipMemcpyHostToDevice, st));
+  unsigned char *d_src = nullptr, *d_dst = nullptr;
+  int* d_w[2] = {nullptr, nullptr};
+  const int rc = ctx->nlm_scratch.lay_out(ctx, "denoising scratch", [&](ScratchLayout& l) {
+    l.take(d_src, bytes);
+    l.take(d_dst, bytes);
+    for (int i = 0; i < n_pass; i++) l.take(d_w[i], (size_t)pass[i].table->n_nonzero);
+  });
+  if (rc != CVO_OK) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync(d_src, src, bytes, hipMemcpyHostToDevice, st));
   for (int i = 0; i < n_pass; i++) {
     const NlmTable& t = *pass[i].table;
-    HIP_TRY(ctx, hipMemcpyAsync(base + o_w[i], t.weight.data(), sizeof(int) * (size_t)t.n_nonzero, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_w[i], t.weight.data(), sizeof(int) * (size_t)t.n_nonzero, hipMemcpyHostToDevice, st));
     NlmArgs a;
-    a.src = (const unsigned char*)(base + o_src) + pass[i].first;
-    a.dst = (unsigned char*)(base + o_dst) + pass[i].first;
+    a.src = d_src + pass[i].first;
+    a.dst = d_dst + pass[i].first;
     a.src_stride = a.dst_stride = stride;
     a.rows = rows;
     a.cols = cols;
     a.sh = t.sh;
-    a.weight = (const int*)(base + o_w[i]);
+    a.weight = d_w[i];
     a.n_nonzero = t.n_nonzero;
     a.n_lds = std::min(t.n_nonzero, NLM_TABLE_LDS);
     a.shift = t.shift;
@@ -188,7 +189,7 @@ int nlm_device(cvo_ctx* ctx, int rows, int cols, int stride, const unsigned char
     stats.table_in_lds = stats.table_in_lds && a.n_lds == t.n_nonzero;
   }
   std::vector<unsigned char> out(bytes);  // (dst may be src, and nothing is written unless the call succeeds)
-  HIP_TRY(ctx, hipMemcpyAsync(out.data(), base + o_dst, bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(out.data(), d_dst, bytes, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   std::memcpy(dst, out.data(), bytes);
   return CVO_OK;

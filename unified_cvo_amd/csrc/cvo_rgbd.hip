@@ -272,30 +272,24 @@ int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select,
   size_t cap = 0;  // candidates of both sets: every pixel (FULL) + the largest selection
   for (int k = 0; k < RGBD_POTS; k++) cap = std::max(cap, (size_t)rgbd_cells(RGBD_POT_MIN + k, w, h));
   cap += np;
-  ScratchLayout l;
-  const size_t o_ctl = l.take(sizeof(unsigned)), o_img = l.take(need_select ? img_bytes : 0), o_depth = l.take(depth_bytes),
-               o_excl = l.take(f.num_classes > 0 ? np : 0), o_g2 = l.take(need_select ? sizeof(float) * np : 0), o_ths = l.take(2 * sizeof(float) * n_ths),
-               o_hit = l.take(sizeof(int) * (size_t)d.n_cells), o_sel = l.take(sizeof(int) * (size_t)d.n_cells), o_blocks = l.take(sizeof(unsigned) * nb),
-               o_pix = l.take(sizeof(int) * cap), o_out = l.take(sizeof(int) * cap), o_xyz = l.take(sizeof(float) * 3 * cap),
-               o_score = l.take(need_fast ? np : 0), o_fhist = l.take(need_fast ? sizeof(unsigned) * FAST_BINS : 0);
-  const int rc = ctx->rgbd_scratch.reserve(ctx, l.off, "RGB-D scratch");
+  const int rc = ctx->rgbd_scratch.lay_out(ctx, "RGB-D scratch", [&](ScratchLayout& l) {
+    l.take(d.ctl, 1);
+    l.take(d.img, need_select ? img_bytes : 0);
+    l.take_as<char>(d.depth, depth_bytes);
+    if (f.num_classes > 0) l.take(d.excl, np);
+    l.take(d.g2, need_select ? np : 0);
+    l.take(d.ths, 2 * n_ths);  // (thresholds, then their smoothed copy)
+    d.sm = d.ths + n_ths;
+    l.take(d.hit, (size_t)d.n_cells);
+    l.take(d.sel, (size_t)d.n_cells);
+    l.take(d.blocks, nb);
+    l.take(d.pix, cap);
+    l.take(d.out, cap);
+    l.take(d.xyz, 3 * cap);
+    l.take(d.score, need_fast ? np : 0);
+    l.take(d.fast_hist, need_fast ? (size_t)FAST_BINS : 0);
+  });
   if (rc != CVO_OK) return rc;
-  char* b = ctx->rgbd_scratch.p;
-  d.ctl = (unsigned*)(b + o_ctl);
-  d.img = (unsigned char*)(b + o_img);
-  d.depth = b + o_depth;
-  d.excl = f.num_classes > 0 ? (unsigned char*)(b + o_excl) : nullptr;
-  d.g2 = (float*)(b + o_g2);
-  d.ths = (float*)(b + o_ths);
-  d.sm = d.ths + n_ths;
-  d.hit = (int*)(b + o_hit);
-  d.sel = (int*)(b + o_sel);
-  d.blocks = (unsigned*)(b + o_blocks);
-  d.pix = (int*)(b + o_pix);
-  d.out = (int*)(b + o_out);
-  d.xyz = (float*)(b + o_xyz);
-  d.score = (unsigned char*)(b + o_score);
-  d.fast_hist = (unsigned*)(b + o_fhist);
   hipStream_t st = ctx->upload_stream;
   if (need_select) HIP_TRY(ctx, hipMemcpyAsync(d.img, g.p, img_bytes, hipMemcpyHostToDevice, st));
   if (depth_bytes) HIP_TRY(ctx, hipMemcpyAsync(d.depth, f.depth, depth_bytes, hipMemcpyHostToDevice, st));

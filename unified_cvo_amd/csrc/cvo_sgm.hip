@@ -162,35 +162,38 @@ void sgm_launch_select(hipStream_t st, const SgmSelectArgs& a) {
 int sgm_device(cvo_ctx* ctx, const SgmConst& k, const unsigned char* left, const unsigned char* right, float* out, SgmStatsAcc& stats) {
   hipStream_t st = ctx->upload_stream;
   const size_t np = (size_t)k.rows * k.cols;
-  ScratchLayout lay;
-  const size_t o_left = lay.take(np), o_right = lay.take(np), o_cl = lay.take(8 * np), o_cr = lay.take(8 * np);
-  const size_t o_S = lay.take(2 * np * (size_t)k.D), o_disp = lay.take(4 * np);
-  int rc;
-  if ((rc = ctx->sgm_scratch.reserve(ctx, lay.off, "stereo matcher scratch")) != CVO_OK) return rc;
-  char* base = ctx->sgm_scratch.p;
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_left, left, np, hipMemcpyHostToDevice, st));
-  HIP_TRY(ctx, hipMemcpyAsync(base + o_right, right, np, hipMemcpyHostToDevice, st));
   SgmCensusArgs c;
-  c.left = (const unsigned char*)(base + o_left);
-  c.right = (const unsigned char*)(base + o_right);
-  c.census_left = (unsigned long long*)(base + o_cl);
-  c.census_right = (unsigned long long*)(base + o_cr);
+  SgmPathArgs a;
+  float* d_disp = nullptr;
+  const int rc = ctx->sgm_scratch.lay_out(ctx, "stereo matcher scratch", [&](ScratchLayout& l) {  // (stats.o_*: where the read-back finds them)
+    l.take(c.left, np);
+    l.take(c.right, np);
+    stats.o_census_left = l.off;
+    l.take(c.census_left, np);
+    stats.o_census_right = l.off;
+    l.take(c.census_right, np);
+    stats.o_S = l.off;
+    l.take(a.S, np * (size_t)k.D);
+    stats.o_disparity = l.off;
+    l.take(d_disp, np);
+  });
+  if (rc != CVO_OK) return rc;
+  HIP_TRY(ctx, hipMemcpyAsync((void*)c.left, left, np, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync((void*)c.right, right, np, hipMemcpyHostToDevice, st));
   c.rows = k.rows;
   c.cols = k.cols;
   c.tiles_x = (k.cols + SGM_TILE_W - 1) / SGM_TILE_W;
   const unsigned tiles = (unsigned)c.tiles_x * (unsigned)((k.rows + SGM_TILE_H - 1) / SGM_TILE_H);  // (at most 2^24 pixels: under 2^24 tiles)
   hipLaunchKernelGGL(k_sgm_census, dim3(tiles, 2), dim3(SGM_CENSUS_THREADS), 0, st, c);
-  SgmPathArgs a;
   a.census_left = c.census_left;
   a.census_right = c.census_right;
-  a.S = (unsigned short*)(base + o_S);
   a.rows = k.rows;
   a.cols = k.cols;
   a.p1 = k.p1;
   a.p2 = k.p2;
   a.n_lines = 0;
   a.accumulate = 0;
-  const SgmSelectArgs s{a.S, (float*)(base + o_disp), k.rows, k.cols, k.uniqueness, k.lr_max_diff};
+  const SgmSelectArgs s{a.S, d_disp, k.rows, k.cols, k.uniqueness, k.lr_max_diff};
   if (k.D == 64) {
     sgm_launch_paths<64>(st, a, k.paths, stats.lines);
     sgm_launch_select<64>(st, s);
@@ -204,14 +207,10 @@ int sgm_device(cvo_ctx* ctx, const SgmConst& k, const unsigned char* left, const
   HIP_TRY(ctx, hipGetLastError());
   if (out) {
     std::vector<float> host(np);  // (nothing is written unless the call succeeds)
-    HIP_TRY(ctx, hipMemcpyAsync(host.data(), base + o_disp, 4 * np, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), d_disp, 4 * np, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     std::memcpy(out, host.data(), 4 * np);
   }
-  stats.o_disparity = o_disp;
-  stats.o_census_left = o_cl;
-  stats.o_census_right = o_cr;
-  stats.o_S = o_S;
   stats.tile_w = SGM_TILE_W;
   stats.tile_h = SGM_TILE_H;
   return CVO_OK;

@@ -8,9 +8,14 @@ int ensure_attributes(cvo_ctx* ctx, const cvo_cloud* c, bool need_feat, bool nee
   if ((!need_feat || c->feat) && (!need_label || c->label) && (!need_geo || c->geo)) return CVO_OK;
   cvo_cloud* m = const_cast<cvo_cloud*>(c);
   const size_t nn = (size_t)std::max(c->n, 1);
-  const size_t o_feat = 0, o_label = align_up(sizeof(float4) * 2 * nn, 256), o_geo = o_label + align_up(sizeof(float4) * 5 * nn, 256);
-  const size_t bytes = o_geo + align_up(sizeof(float2) * nn, 256);
+  CloudArrays z;
+  auto list = [&](ScratchLayout& l) {
+    l.take(z.feat, 2 * nn);
+    l.take(z.label, 5 * nn);
+    l.take(z.geo, nn);
+  };
   if (!m->zero_slab) {
+    const size_t bytes = ScratchLayout().walk(list);
     HIP_TRY(ctx, hipSetDevice(c->device));
     hipError_t e = hipMalloc(&m->zero_slab, bytes);
     if (e != hipSuccess) return fail(ctx, CVO_E_NOMEM, std::string("cloud hipMalloc: ") + hipGetErrorString(e));
@@ -22,9 +27,10 @@ int ensure_attributes(cvo_ctx* ctx, const cvo_cloud* c, bool need_feat, bool nee
     }
     if (created) *created = true;
   }
-  if (!m->feat) m->feat = (float4*)(m->zero_slab + o_feat);
-  if (!m->label) m->label = (float4*)(m->zero_slab + o_label);
-  if (!m->geo) m->geo = (float2*)(m->zero_slab + o_geo);
+  ScratchLayout(m->zero_slab).walk(list);
+  if (!m->feat) m->feat = z.feat;
+  if (!m->label) m->label = z.label;
+  if (!m->geo) m->geo = z.geo;
   return CVO_OK;
 }
 
@@ -162,30 +168,39 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
     if (!onehot) lid_host.clear();
   }
   const bool has_lid = !lid_host.empty();
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
-  // (device ordering: the caller's arrays go up in ORIGINAL order - x4 stays, the raw attribute arrays are scratch - and
-  // the kernel writes the spatially ordered ones; host ordering: everything is staged in its final form)
-  const size_t o_x4 = take(sizeof(float4) * nn);
-  const size_t o_rawf = device_order && h.feat ? take(sizeof(float) * FD * nn) : 0, o_rawl = device_order && h.label ? take(sizeof(float) * NC * nn) : 0,
-               o_rawg = device_order && h.geo ? take(sizeof(float) * 2 * nn) : 0,
-               o_rawlid = device_order && has_lid ? take(sizeof(int) * nn) : 0;
-  const size_t up_bytes_device = off;
-  const size_t o_xs4 = take(sizeof(float4) * nn), o_order = take(sizeof(int) * nn), o_inv = take(sizeof(int) * nn);
-  const size_t o_feat = h.feat ? take(sizeof(float4) * 2 * nn) : 0, o_label = h.label ? take(sizeof(float4) * 5 * nn) : 0,
-               o_geo = h.geo ? take(sizeof(float2) * nn) : 0, o_lid = has_lid ? take(sizeof(int) * nn) : 0;
   int NP = KD_THREADS;
   while (NP < n) NP *= 2;
-  const size_t o_segpos = device_order ? take(sizeof(unsigned short) * (size_t)NP) : 0,
-               o_seglo = device_order ? take(sizeof(unsigned short) * 2 * KD_MAX_SEGS) : 0;
-  const size_t up_bytes = device_order ? up_bytes_device : off;
+  // (device ordering: the caller's arrays go up in ORIGINAL order - x4 stays, the raw attribute arrays are scratch - and
+  // the kernel writes the spatially ordered ones; host ordering: everything is staged in its final form)
+  // THE list of the slab's arrays, walked over two bases: the staging buffer (into s) and the slab (into the cloud itself
+  // and, for k_kd_order, into the job: `a` is whatever names these arrays)
+  size_t up_bytes = 0;  // the prefix of the slab that is staged and uploaded
+  auto list = [&](auto& a) {
+    return [&](ScratchLayout& l) {
+      l.take(a.x4, nn);
+      if (device_order && h.feat) l.take(a.raw_feat, FD * nn);
+      if (device_order && h.label) l.take(a.raw_label, NC * nn);
+      if (device_order && h.geo) l.take(a.raw_geo, 2 * nn);
+      if (device_order && has_lid) l.take(a.raw_lid, nn);
+      if (device_order) up_bytes = l.off;
+      l.take(a.xs4, nn);
+      l.take(a.order, nn);
+      l.take(a.inv, nn);
+      if (h.feat) l.take(a.feat, 2 * nn);
+      if (h.label) l.take(a.label, 5 * nn);
+      if (h.geo) l.take(a.geo, nn);
+      if (has_lid) l.take(a.lid, nn);
+      if (device_order) l.take(a.seg_of_pos, (size_t)NP);
+      if (device_order) l.take(a.seg_lo, 2 * KD_MAX_SEGS);
+      if (!device_order) up_bytes = l.off;
+    };
+  };
+  CloudArrays s;
+  const size_t slab_bytes = ScratchLayout().walk(list(s));
   std::vector<char>& stage = sc->stage;
   stage.assign(up_bytes, 0);  // (pageable: kept alive by the caller until the stream has been synchronised)
-  float* x4 = reinterpret_cast<float*>(&stage[o_x4]);
+  ScratchLayout(stage.data()).walk(list(s));
+  float* x4 = reinterpret_cast<float*>(s.x4);
   double sx = 0, sy = 0, sz = 0, r2max = 0;
   for (int i = 0; i < n; i++) {
     const float* p = reinterpret_cast<const float*>(h.xyz + h.row(i) * h.xyz_stride);
@@ -207,63 +222,38 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
   }
   if (!std::isfinite(c->cx) || !std::isfinite(c->cy) || !std::isfinite(c->cz)) c->cx = c->cy = c->cz = 0.f;
   if (device_order) {
-    if (h.feat) {
-      float* f = reinterpret_cast<float*>(&stage[o_rawf]);
-      for (int i = 0; i < n; i++) std::memcpy(&f[FD * (size_t)i], h.feat + h.row(i) * h.feat_stride, sizeof(float) * FD);
-    }
-    if (h.label) {
-      float* l = reinterpret_cast<float*>(&stage[o_rawl]);
-      for (int i = 0; i < n; i++) std::memcpy(&l[NC * (size_t)i], h.label + h.row(i) * h.label_stride, sizeof(float) * NC);
-    }
-    if (h.geo) {
-      float* g = reinterpret_cast<float*>(&stage[o_rawg]);
-      for (int i = 0; i < n; i++) std::memcpy(&g[2 * (size_t)i], h.geo + h.row(i) * h.geo_stride, sizeof(float) * 2);
-    }
-    if (has_lid) std::memcpy(&stage[o_rawlid], lid_host.data(), sizeof(int) * (size_t)n);
+    if (h.feat)
+      for (int i = 0; i < n; i++) std::memcpy(&s.raw_feat[FD * (size_t)i], h.feat + h.row(i) * h.feat_stride, sizeof(float) * FD);
+    if (h.label)
+      for (int i = 0; i < n; i++) std::memcpy(&s.raw_label[NC * (size_t)i], h.label + h.row(i) * h.label_stride, sizeof(float) * NC);
+    if (h.geo)
+      for (int i = 0; i < n; i++) std::memcpy(&s.raw_geo[2 * (size_t)i], h.geo + h.row(i) * h.geo_stride, sizeof(float) * 2);
+    if (has_lid) std::memcpy(s.raw_lid, lid_host.data(), sizeof(int) * (size_t)n);
   } else {
     std::vector<int> order;
     spatial_order(x4, n, order, ctx->opt.no_sort, ctx->opt.order == CloudOrder::Virtual);
     // colour, class distributions and geometric types are kept in SPATIAL order only (position r holds the attributes of
     // point order[r]): the kernels index them by sorted position, like the coordinates they gather per candidate
-    if (h.feat) {
-      float* f8 = reinterpret_cast<float*>(&stage[o_feat]);
-      for (int r = 0; r < n; r++) std::memcpy(&f8[FD_PAD * (size_t)r], h.feat + h.row(order[r]) * h.feat_stride, sizeof(float) * FD);
-    }
-    if (h.label) {
-      float* l20 = reinterpret_cast<float*>(&stage[o_label]);
-      for (int r = 0; r < n; r++) std::memcpy(&l20[NC_PAD * (size_t)r], h.label + h.row(order[r]) * h.label_stride, sizeof(float) * NC);
-    }
-    if (h.geo) {
-      float* g2 = reinterpret_cast<float*>(&stage[o_geo]);
-      for (int r = 0; r < n; r++) std::memcpy(&g2[2 * (size_t)r], h.geo + h.row(order[r]) * h.geo_stride, sizeof(float) * 2);
-    }
-    if (has_lid) {
-      int* li = reinterpret_cast<int*>(&stage[o_lid]);
-      for (int r = 0; r < n; r++) li[r] = lid_host[(size_t)order[r]];
-    }
-    float* xs = reinterpret_cast<float*>(&stage[o_xs4]);
-    for (int r = 0; r < n; r++) std::memcpy(&xs[4 * (size_t)r], &x4[4 * (size_t)order[r]], 16);
-    if (n > 0) std::memcpy(&stage[o_order], order.data(), sizeof(int) * (size_t)n);
-    {
-      int* inv = reinterpret_cast<int*>(&stage[o_inv]);
-      for (int r = 0; r < n; r++) inv[order[r]] = r;
-    }
+    if (h.feat)
+      for (int r = 0; r < n; r++) std::memcpy(&s.feat[FD_PAD / 4 * (size_t)r], h.feat + h.row(order[r]) * h.feat_stride, sizeof(float) * FD);
+    if (h.label)
+      for (int r = 0; r < n; r++) std::memcpy(&s.label[NC_PAD / 4 * (size_t)r], h.label + h.row(order[r]) * h.label_stride, sizeof(float) * NC);
+    if (h.geo)
+      for (int r = 0; r < n; r++) std::memcpy(&s.geo[r], h.geo + h.row(order[r]) * h.geo_stride, sizeof(float) * 2);
+    if (has_lid)
+      for (int r = 0; r < n; r++) s.lid[r] = lid_host[(size_t)order[r]];
+    for (int r = 0; r < n; r++) s.xs4[r] = s.x4[order[r]];
+    if (n > 0) std::memcpy(s.order, order.data(), sizeof(int) * (size_t)n);
+    for (int r = 0; r < n; r++) s.inv[order[r]] = r;
     c->h_order = std::move(order);
   }
-  hipError_t e = hipMalloc(&c->slab, off);
-  c->slab_bytes = off;
+  hipError_t e = hipMalloc(&c->slab, slab_bytes);
+  c->slab_bytes = slab_bytes;
   if (e != hipSuccess) {
     cvo_cloud_free(c);
     return fail(ctx, CVO_E_NOMEM, std::string("cloud hipMalloc: ") + hipGetErrorString(e));
   }
-  c->x4 = (float4*)(c->slab + o_x4);
-  c->xs4 = (float4*)(c->slab + o_xs4);
-  c->order = (int*)(c->slab + o_order);
-  c->inv = (int*)(c->slab + o_inv);
-  c->feat = h.feat ? (float4*)(c->slab + o_feat) : nullptr;
-  c->label = h.label ? (float4*)(c->slab + o_label) : nullptr;
-  c->geo = h.geo ? (float2*)(c->slab + o_geo) : nullptr;
-  c->lid = has_lid ? (int*)(c->slab + o_lid) : nullptr;
+  ScratchLayout(c->slab).walk(list(*c));
   if (n > 0) {
     e = hipMemcpyAsync(c->slab, stage.data(), up_bytes, hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) {
@@ -274,23 +264,9 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
   sc->c = c;
   sc->job = KdJob{};
   if (device_order) {
-    KdJob& J = sc->job;
-    J.n = n;
-    J.NP = NP;
-    J.x4 = c->x4;
-    J.seg_of_pos = (unsigned short*)(c->slab + o_segpos);
-    J.seg_lo = (unsigned short*)(c->slab + o_seglo);
-    J.order = c->order;
-    J.inv = c->inv;
-    J.xs4 = c->xs4;
-    J.raw_feat = h.feat ? (const float*)(c->slab + o_rawf) : nullptr;
-    J.feat = c->feat;
-    J.raw_label = h.label ? (const float*)(c->slab + o_rawl) : nullptr;
-    J.label = c->label;
-    J.raw_geo = h.geo ? (const float*)(c->slab + o_rawg) : nullptr;
-    J.geo = c->geo;
-    J.raw_lid = has_lid ? (const int*)(c->slab + o_rawlid) : nullptr;
-    J.lid = c->lid;
+    ScratchLayout(c->slab).walk(list(sc->job));
+    sc->job.n = n;
+    sc->job.NP = NP;
     c->h_order.assign((size_t)n, 0);
   }
   return CVO_OK;
@@ -499,18 +475,19 @@ int cvo_cloud_transformed(cvo_ctx* ctx, const cvo_cloud* in, const float pose12[
   }
   // same slab layout: features, labels, geometric types and the spatial order are copied, coordinates rewritten
   // (attributes the input was uploaded without - NULL or pointing into its zero slab - stay absent in the copy)
-  auto rebase = [&](const void* p) -> char* {
-    const char* q = (const char*)p;
-    return (q && q >= in->slab && q < in->slab + in->slab_bytes) ? c->slab + (q - in->slab) : nullptr;
+  const ScratchLayout l(c->slab);
+  auto rebase = [&](auto*& to, const auto* from) {
+    const char* q = (const char*)from;
+    if (q && q >= in->slab && q < in->slab + in->slab_bytes) l.at(to, (size_t)(q - in->slab));
   };
-  c->x4 = (float4*)rebase(in->x4);
-  c->xs4 = (float4*)rebase(in->xs4);
-  c->feat = (float4*)rebase(in->feat);
-  c->label = (float4*)rebase(in->label);
-  c->geo = (float2*)rebase(in->geo);
-  c->lid = (int*)rebase(in->lid);
-  c->order = (int*)rebase(in->order);
-  c->inv = (int*)rebase(in->inv);
+  rebase(c->x4, in->x4);
+  rebase(c->xs4, in->xs4);
+  rebase(c->feat, in->feat);
+  rebase(c->label, in->label);
+  rebase(c->geo, in->geo);
+  rebase(c->lid, in->lid);
+  rebase(c->order, in->order);
+  rebase(c->inv, in->inv);
   Pose12 P;
   for (int q = 0; q < 12; q++) P.T[q] = pose12[q];
   if (in->n > 0) {

@@ -58,25 +58,30 @@ int voxel_run_device(cvo_ctx* ctx, int n, const float* xyz, const float* d_xyz_g
   size_t cap = 1024;
   while (cap < 2 * (size_t)n) cap *= 2;
   const int nb = (n + VOX_THREADS - 1) / VOX_THREADS;
-  ScratchLayout l;
-  const size_t o_ctl = l.take(sizeof(VoxelCtl)), o_stats = l.take(sizeof(VoxelBlockStats) * VOX_INSERT_BLOCKS), o_keys = l.take(sizeof(unsigned long long) * cap), o_first = l.take(sizeof(unsigned) * cap),
-               o_xyz = l.take(d_xyz_given ? 0 : sizeof(float) * 3 * (size_t)n), o_slot = l.take(sizeof(unsigned) * (size_t)n),
-               o_blocks = l.take(sizeof(unsigned) * (size_t)nb), o_kept = l.take(sizeof(int) * (size_t)n);
-  int rc = ctx->vox_scratch.reserve(ctx, l.off, "voxel scratch");
+  VoxelCtl* ctl = nullptr;
+  VoxelBlockStats* stats = nullptr;
+  unsigned long long* keys = nullptr;
+  unsigned *first = nullptr, *slot = nullptr, *blocks = nullptr;
+  const char* table_end = nullptr;  // keys and first[] are adjacent: one fill
+  int* d_kept = nullptr;
+  const float* d_xyz = d_xyz_given;
+  int rc = ctx->vox_scratch.lay_out(ctx, "voxel scratch", [&](ScratchLayout& l) {
+    l.take(ctl, 1);
+    l.take(stats, VOX_INSERT_BLOCKS);
+    l.take(keys, cap);
+    l.take(first, cap);
+    l.at(table_end, l.off);
+    if (!d_xyz_given) l.take(d_xyz, 3 * (size_t)n);
+    l.take(slot, (size_t)n);
+    l.take(blocks, (size_t)nb);
+    l.take(d_kept, (size_t)n);
+  });
   if (rc != CVO_OK) return rc;
-  char* b = ctx->vox_scratch.p;
-  VoxelCtl* ctl = (VoxelCtl*)(b + o_ctl);
-  unsigned long long* keys = (unsigned long long*)(b + o_keys);
-  unsigned* first = (unsigned*)(b + o_first);
-  const float* d_xyz = d_xyz_given ? d_xyz_given : (const float*)(b + o_xyz);
-  unsigned* slot = (unsigned*)(b + o_slot);
-  int* d_kept = (int*)(b + o_kept);
-  VoxelBlockStats* stats = (VoxelBlockStats*)(b + o_stats);
   hipStream_t st = ctx->upload_stream;
   const unsigned mask = (unsigned)(cap - 1);
   HIP_TRY(ctx, hipMemsetAsync(ctl, 0, sizeof(VoxelCtl), st));
-  HIP_TRY(ctx, hipMemsetAsync(keys, 0xFF, o_xyz - o_keys, st));  // keys and first[] are adjacent: one fill
-  if (!d_xyz_given) HIP_TRY(ctx, hipMemcpyAsync(b + o_xyz, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemsetAsync(keys, 0xFF, (size_t)(table_end - (const char*)keys), st));
+  if (!d_xyz_given) HIP_TRY(ctx, hipMemcpyAsync((void*)d_xyz, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, st));
   const int grid = std::min(nb, VOX_INSERT_BLOCKS);
   if (ctx->opt.voxel_prepass)
     hipLaunchKernelGGL(k_voxel_insert<true>, dim3(grid), dim3(VOX_THREADS), 0, st, n, d_xyz, s, mask, keys, first, slot, ctl, stats);
@@ -85,7 +90,7 @@ int voxel_run_device(cvo_ctx* ctx, int n, const float* xyz, const float* d_xyz_g
   auto scan = [&](int nbs, unsigned* count) {  // (the selection's own: the block statistics are summed in the same launch)
     hipLaunchKernelGGL(k_voxel_scan, dim3(1), dim3(VOX_THREADS), 0, st, nbs, count, ctl, grid, (const VoxelBlockStats*)stats);
   };
-  if ((rc = compact(ctx, n, VoxelFirst{mask, first, slot, d_kept}, (unsigned*)(b + o_blocks), scan)) != CVO_OK) return rc;
+  if ((rc = compact(ctx, n, VoxelFirst{mask, first, slot, d_kept}, blocks, scan)) != CVO_OK) return rc;
   VoxelCtl h{};
   // (at most n points are ever kept: the "kept more than it was given" refusal and the one of h.status cannot meet)
   HIP_TRY(ctx, hipMemcpyAsync(&h, ctl, sizeof h, hipMemcpyDeviceToHost, st));  // (the whole control word: one copy, one synchronisation)
