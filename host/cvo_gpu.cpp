@@ -363,6 +363,24 @@ std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::upload_clouds(const std::vector<
   return out;
 }
 
+std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::upload_device(const cvo_device_rows_t& rows) const {
+  std::lock_guard<std::mutex> lk(call_mutex);
+  std::unique_ptr<ResidentClouds> out(new ResidentClouds());
+  out->handles.assign(1, nullptr);
+  out->kept_.resize(1);
+  check(ctx, cvo_cloud_from_device(ctx, &rows, out->handles.data()), "cvo_cloud_from_device");
+  return out;
+}
+
+std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::upload_device_aos192(const CvoPoint* d_pts, int n) const {
+  std::lock_guard<std::mutex> lk(call_mutex);
+  std::unique_ptr<ResidentClouds> out(new ResidentClouds());
+  out->handles.assign(1, nullptr);
+  out->kept_.resize(1);
+  check(ctx, cvo_cloud_from_device_aos192(ctx, n, d_pts, out->handles.data()), "cvo_cloud_from_device_aos192");
+  return out;
+}
+
 CvoPointCloud CvoGPU::voxel_downsample(const CvoPointCloud& cloud, float voxel_size, std::vector<int>* kept) const {
   std::lock_guard<std::mutex> lk(call_mutex);
   const int n = cloud.num_points();

@@ -87,6 +87,11 @@ class CvoGPU {
   std::unique_ptr<ResidentClouds> upload_clouds(const std::vector<const CvoPointCloud*>& clouds, int host_threads = 0) const;
   std::vector<int> align_batch(const ResidentClouds& sources, const ResidentClouds& targets, const std::vector<Mat4f>& inits,
                                std::vector<Mat4f>& transforms, double* seconds = nullptr) const;
+  // New: a resident cloud from rows that are ALREADY in this object's device memory (cvo_cloud_from_device /
+  // _aos192, include/cvo_hip.h: strided arrays or 192-byte CvoPoint records, complete when the call is made) - what
+  // upload_clouds returns for one cloud, without a host copy.  Refusals (host pointers, strides, row indices) throw.
+  std::unique_ptr<ResidentClouds> upload_device(const cvo_device_rows_t& rows) const;
+  std::unique_ptr<ResidentClouds> upload_device_aos192(const CvoPoint* d_pts, int n) const;
   // New: voxel-grid downsampling on the device - what the drivers do with cvo::VoxelMap before align()
   // (main_multi_frame_irls_tum.cpp:290-335; utils/VoxelMap.hpp is the host class): of every occupied voxel of side
   // voxel_size the point with the LOWEST index is kept, in ascending index (cvo_voxel_select, include/cvo_hip.h).

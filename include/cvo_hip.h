@@ -191,6 +191,37 @@ int cvo_cloud_upload_aos192(cvo_ctx* ctx, int n, const void* cvo_points, cvo_clo
  * out: n_clouds handles (all NULL on error). */
 int cvo_cloud_upload_many(cvo_ctx* ctx, int n_clouds, const int* n, const float* const* xyz, const float* const* feat,
                           const float* const* label, const float* const* geotype, int threads, cvo_cloud** out);
+/* ---- clouds from rows that are already in device memory (no reference counterpart: upstream builds every cloud on the host) ----
+ * A caller whose points are in HBM - a network's class scores in a tensor, its own HIP pre-processing - hands them over
+ * without a host copy.  Point i of the cloud is record r = rows ? rows[i] : i of strided arrays: 3 floats at
+ * xyz + r * xyz_stride, 5 at feat, 19 at label, 2 at geotype (strides in bytes; feat / label / geotype may be NULL and then
+ * read as zeros, as in cvo_cloud_upload).
+ * Contract: every pointer is device memory of the context's device, complete when the call is made (the caller synchronises
+ * its producer stream).  The library enqueues on its upload stream and returns after it has synchronised that stream; the
+ * arrays are only read, the cloud owns a copy and may outlive them.  The cloud is interchangeable with the one
+ * cvo_cloud_upload makes of the same rows: same spatial order (cvo_debug_cloud_order), same one-hot detection, bit-identical
+ * results of every solver, score, association, export, cvo_cloud_transformed and multi-frame call.  Non-finite coordinates
+ * are no error here either: such a cloud is ordered on the host and refused by the solvers.
+ * CVO_E_INVALID, nothing allocated, *out NULL - decided on the host before any launch: n < 0; xyz NULL with n > 0;
+ * n_records < 1, or < n without rows; a stride below the row's size or no multiple of 4; a pointer that is not 4-byte
+ * aligned, that hipPointerGetAttributes does not report as device memory of this context's device (host, pinned and
+ * managed memory, other devices), or whose n_records rows do not fit the allocation behind it.  No pointer is read
+ * through before it is classified.  Found by the ingest kernel: a rows[] entry outside [0, n_records) - the read is
+ * clamped, nothing out of bounds is loaded, and cvo_last_error names the first bad position. */
+typedef struct {
+  int n;                 /* points of the cloud */
+  int n_records;         /* records the arrays hold (>= 1 when n > 0); without `rows` it must be >= n */
+  const void* xyz;     size_t xyz_stride;      /* 3 floats at xyz + r * stride */
+  const void* feat;    size_t feat_stride;     /* 5 floats, or NULL */
+  const void* label;   size_t label_stride;    /* 19 floats, or NULL */
+  const void* geotype; size_t geotype_stride;  /* 2 floats, or NULL */
+  const int* rows;       /* device, optional: point i is record rows[i]; duplicates allowed */
+} cvo_device_rows_t;
+int cvo_cloud_from_device(cvo_ctx* ctx, const cvo_device_rows_t* rows, cvo_cloud** out);
+/* n_clouds clouds with one ingest launch, one read-back and one ordering launch.  out: n_clouds handles (all NULL on error). */
+int cvo_cloud_from_device_many(cvo_ctx* ctx, int n_clouds, const cvo_device_rows_t* rows, cvo_cloud** out);
+/* The device twin of cvo_cloud_upload_aos192: n 192-byte CvoPoint records in device memory, same byte offsets. */
+int cvo_cloud_from_device_aos192(cvo_ctx* ctx, int n, const void* d_pts, cvo_cloud** out);
 /* ---- voxel-grid downsampling: replaces cvo::VoxelMap<PointT> as the drivers use it (VoxelMap.hpp, VoxelMap_impl.hpp:126-170) ----
  * Voxel of a point: k = (lrint(x / s), lrint(y / s), lrint(z / s)) with the correctly rounded float quotient and ties to
  * even.  Of every occupied voxel ONE point is kept, the one with the lowest index (upstream draws a member at random);

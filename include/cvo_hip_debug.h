@@ -86,6 +86,11 @@ int cvo_debug_cloud_order(const cvo_cloud* cloud, int* out);
 int cvo_debug_last_score_batch(const cvo_ctx* ctx, int* overlap_evals, int* chain_evals, int* launches);
 /* Free / total bytes of the context's device (hipMemGetInfo), for leak checks without a second HIP runtime in the process. */
 int cvo_debug_device_memory(cvo_ctx* ctx, size_t* free_bytes, size_t* total_bytes);
+/* Device arrays for the tests of cvo_cloud_from_device, without a second HIP runtime in the process.  *d == NULL: allocates
+ * `bytes` of device memory on the context's device into *d; then, host_src != NULL, copies `bytes` from host_src to *d
+ * (synchronously) - with *d given, that overwrites an earlier buffer of at least `bytes`.  _release frees one. */
+int cvo_debug_device_buffer(cvo_ctx* ctx, size_t bytes, const void* host_src, void** d);
+int cvo_debug_device_release(cvo_ctx* ctx, void* d);
 /* k_irls_normal on its own: the kernel matrix of the last evaluation on this context (cvo_edge_kernel_matrix) as edge
  * (frame1, frame2) - the UNtransformed clouds the evaluated ones were moved from - at the poses pose1 / pose2 (3x4
  * row-major doubles).  out[91] = cost, g[12], the upper triangle of the 12 x 12 H row by row (78). */

@@ -257,6 +257,24 @@ class cvo_map_config_t(C.Structure):
                 ("ds_resolution", C.c_float), ("free_resolution", C.c_float), ("max_range", C.c_float)]
 
 
+class cvo_device_rows_t(C.Structure):
+    """Rows of one cloud in device memory (cvo_cloud_from_device): byte strides, optional row indices."""
+
+    _fields_ = [
+        ("n", C.c_int),
+        ("n_records", C.c_int),
+        ("xyz", C.c_void_p),
+        ("xyz_stride", C.c_size_t),
+        ("feat", C.c_void_p),
+        ("feat_stride", C.c_size_t),
+        ("label", C.c_void_p),
+        ("label_stride", C.c_size_t),
+        ("geotype", C.c_void_p),
+        ("geotype_stride", C.c_size_t),
+        ("rows", C.c_void_p),
+    ]
+
+
 CVO_DEPTH_U16, CVO_DEPTH_F32 = 0, 1
 CVO_SELECT_CV_FAST, CVO_SELECT_DSO_EDGES, CVO_SELECT_FULL = 0, 2, 8
 CVO_FAST_RGBD, CVO_FAST_STEREO, CVO_FAST_STEREO_SEMANTIC = (9, 15000, 12000, 13), (4, 24000, 15000, 50), (4, 28000, 15000, 50)
@@ -289,6 +307,8 @@ EXPORTED = [
     "cvo_cloud_upload_stereo_pair_filtered", "cvo_debug_dfilter_stats",
     "cvo_map_config_default", "cvo_map_open", "cvo_map_close", "cvo_map_insert", "cvo_map_insert_posed", "cvo_map_size", "cvo_map_cloud",
     "cvo_map_open_host", "cvo_map_close_host", "cvo_map_insert_host", "cvo_map_cloud_host", "cvo_debug_map_stats",
+    "cvo_cloud_from_device", "cvo_cloud_from_device_many", "cvo_cloud_from_device_aos192",
+    "cvo_debug_device_buffer", "cvo_debug_device_release",
 ]
 
 _libs = {}
@@ -448,6 +468,12 @@ def lib(path=None):
     L.cvo_map_cloud.argtypes = [vp, ll, fp, fp, fp, llp, C.POINTER(vp)]
     L.cvo_map_cloud_host.argtypes = [vp, ll, fp, fp, fp, llp]
     L.cvo_debug_map_stats.argtypes = [vp, ipp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong), fp, fp]
+    dr = C.POINTER(cvo_device_rows_t)
+    L.cvo_cloud_from_device.argtypes = [vp, dr, C.POINTER(vp)]
+    L.cvo_cloud_from_device_many.argtypes = [vp, ip, dr, C.POINTER(vp)]
+    L.cvo_cloud_from_device_aos192.argtypes = [vp, ip, vp, C.POINTER(vp)]
+    L.cvo_debug_device_buffer.argtypes = [vp, C.c_size_t, vp, C.POINTER(vp)]
+    L.cvo_debug_device_release.argtypes = [vp, vp]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

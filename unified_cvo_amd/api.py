@@ -769,6 +769,49 @@ def cvo_points_from_pointcloud(pc):
     return rec
 
 
+def _device_array(name, a, width, dtype, device):
+    """(address or None, records or None, row stride in bytes) of one argument of CvoGPU.upload_device; width None: the 1-D
+    index array `rows` (then: address, n, 4)."""
+    if a is None:
+        return None, None, 0
+    if not hasattr(a, "data_ptr"):  # (address, records, stride in bytes) / (address, n)
+        t = tuple(a)
+        if len(t) != (2 if width is None else 3):
+            raise ValueError(f"{name}: give a tensor or (address, {'n' if width is None else 'records, stride in bytes'})")
+        return int(t[0]) or None, int(t[1]), (4 if width is None else int(t[2]))
+    if not str(a.dtype).endswith(dtype):
+        raise TypeError(f"{name}: dtype {a.dtype}, {dtype} is required")
+    dev = a.device
+    if getattr(dev, "type", "cuda") == "cpu":
+        raise ValueError(f"{name} is a host tensor")
+    if getattr(dev, "index", None) not in (None, device):
+        raise ValueError(f"{name} is on device {dev.index}, the context on {device}")
+    shape, stride = tuple(a.shape), tuple(a.stride())
+    if width is None:
+        if len(shape) != 1 or (shape[0] > 1 and stride[0] != 1):
+            raise ValueError(f"{name} must be a contiguous 1-D tensor")
+        return int(a.data_ptr()) or None, int(shape[0]), 4
+    if len(shape) != 2 or shape[1] != width:
+        raise ValueError(f"{name} is {shape}, (records, {width}) is required")
+    if stride[1] != 1:
+        raise ValueError(f"{name}: rows must be contiguous (inner stride {stride[1]})")
+    return int(a.data_ptr()) or None, int(shape[0]), (4 * int(stride[0]) if shape[0] > 1 else 4 * width)
+
+
+def _sync_producers(objs):
+    """Waits for the current stream of every tensor's device, where the tensor's module offers <module>.cuda.current_stream
+    (torch does): the library reads the arrays on its own stream."""
+    import sys
+    seen = set()
+    for o in objs:
+        mod = sys.modules.get(type(o).__module__.split(".")[0])
+        cur = getattr(getattr(mod, "cuda", None), "current_stream", None)
+        key = (id(mod), str(o.device))
+        if cur is not None and key not in seen:
+            seen.add(key)
+            cur(o.device).synchronize()
+
+
 def _mat_to_c(T):
     a = np.ascontiguousarray(np.asarray(T, np.float32).reshape(4, 4).T).reshape(16)
     return a
@@ -872,6 +915,7 @@ class CvoGPU:
         if rc != 0:
             raise CvoError(f"cvo_ctx_create(device={device}) failed with {rc}: is a HIP GPU visible?")
         self.ctx = ctx
+        self.device = int(device)
         self._queues = []  # weak references to the live BatchQueue objects (closed before the context goes)
         self._maps = []    # ... and to the live SemanticMap objects
 
@@ -1199,6 +1243,76 @@ class CvoGPU:
             d.gpu, d.n, d._keep, d.handle = self, int(n[i]), None, C.c_void_p(out[i])
             res.append(d)
         return res
+
+    def _device_rows(self, xyz, feat=None, label=None, geotype=None, rows=None, n_records=None):
+        """cvo_device_rows_t of one cloud (+ the objects to synchronise), refusing what the wrapper can see is wrong."""
+        dev = self.device
+        arrs = [_device_array("xyz", xyz, 3, "float32", dev), _device_array("feat", feat, FEATURE_DIMENSIONS, "float32", dev),
+                _device_array("label", label, NUM_CLASSES, "float32", dev), _device_array("geotype", geotype, 2, "float32", dev)]
+        idx = _device_array("rows", rows, None, "int32", dev)
+        if xyz is None:
+            raise ValueError("xyz is required")
+        have = arrs[0][1]
+        if n_records is None:
+            n_records = have
+        n_records = int(n_records)
+        for name, (_, k, _) in zip(("xyz", "feat", "label", "geotype"), arrs):
+            if k is not None and k < n_records:
+                raise ValueError(f"{name} holds {k} records, n_records is {n_records}")
+        n = have if rows is None else idx[1]
+        if rows is None and n_records < n:
+            raise ValueError(f"n_records ({n_records}) < n ({n}) without rows")
+        d = _capi.cvo_device_rows_t(n, n_records, arrs[0][0], arrs[0][2], arrs[1][0], arrs[1][2], arrs[2][0], arrs[2][2],
+                                    arrs[3][0], arrs[3][2], idx[0])
+        return d, [a for a in (xyz, feat, label, geotype, rows) if hasattr(a, "data_ptr")]
+
+    def upload_device(self, xyz, feat=None, label=None, geotype=None, rows=None, n_records=None):
+        """cvo_cloud_from_device: a resident cloud from rows that are already in this context's device memory - no host copy.
+        Every array is either an object with data_ptr() / stride() / shape / dtype / device (a torch tensor: (records, 3 | 5 |
+        19 | 2) float32, inner stride 1, any row stride - a column slice of a wider tensor is fine) or a tuple (device address,
+        records, row stride in bytes).  rows: optional int32 indices (a contiguous 1-D tensor, or (address, n)): point i is
+        record rows[i].  n_records: how many records the arrays hold (default: xyz's).  For tensors of a module that offers
+        <module>.cuda.current_stream, that stream is synchronised first; with raw addresses the caller has done so."""
+        d, objs = self._device_rows(xyz, feat, label, geotype, rows, n_records)
+        _sync_producers(objs)
+        h = C.c_void_p()
+        self._check(self.L.cvo_cloud_from_device(self.ctx, C.byref(d), C.byref(h)))
+        return self._adopt(h, d.n)
+
+    def upload_device_many(self, clouds):
+        """cvo_cloud_from_device_many: a list of clouds - each a dict of upload_device's arguments, or a tuple of them in order -
+        with one ingest launch, one read-back and one ordering launch."""
+        specs = [self._device_rows(**c) if isinstance(c, dict) else self._device_rows(*c) for c in clouds]
+        k = len(specs)
+        if k == 0:
+            return []
+        _sync_producers([o for _, objs in specs for o in objs])
+        arr = (_capi.cvo_device_rows_t * k)(*[d for d, _ in specs])
+        out = (C.c_void_p * k)()
+        self._check(self.L.cvo_cloud_from_device_many(self.ctx, k, arr, out))
+        return [self._adopt(C.c_void_p(out[i]), arr[i].n) for i in range(k)]
+
+    def upload_device_aos192(self, address, n):
+        """cvo_cloud_from_device_aos192: n 192-byte CvoPoint records (CVO_POINT_DTYPE) at a device address."""
+        h = C.c_void_p()
+        self._check(self.L.cvo_cloud_from_device_aos192(self.ctx, int(n), C.c_void_p(int(address)), C.byref(h)))
+        return self._adopt(h, int(n))
+
+    def _adopt(self, handle, n):
+        d = DeviceCloud.__new__(DeviceCloud)
+        d.gpu, d.n, d._keep, d.handle = self, int(n), None, handle
+        return d
+
+    def debug_device_buffer(self, data, into=None):
+        """cvo_debug_device_buffer: the bytes of a numpy array in device memory -> the device address; into: an address this
+        call returned before, overwritten instead (the array must not be larger than that buffer)."""
+        a = np.ascontiguousarray(data)
+        d = C.c_void_p(into)
+        self._check(self.L.cvo_debug_device_buffer(self.ctx, max(a.nbytes, 1), a.ctypes.data_as(C.c_void_p) if a.nbytes else None, C.byref(d)))
+        return d.value
+
+    def debug_device_release(self, address):
+        self._check(self.L.cvo_debug_device_release(self.ctx, C.c_void_p(address)))
 
     def upload_aos192(self, records):
         """pcl_PointCloud_to_gpu: uploads an array of 192-byte CvoPoint records (dtype CVO_POINT_DTYPE)."""

@@ -327,6 +327,7 @@ void cvo_ctx_destroy(cvo_ctx* c) {
   c->nlm_scratch.release();
   c->sgm_scratch.release();
   c->dfilter_scratch.release();
+  c->ingest_scratch.release();
   if (c->dfilter_staging) (void)hipHostFree(c->dfilter_staging);
   for (int g = 0; g < cvo_ctx::MAX_GROUPS; g++) {
     for (int i = 0; i < 2; i++)

@@ -109,6 +109,37 @@ int cvo_debug_device_memory(cvo_ctx* ctx, size_t* free_bytes, size_t* total_byte
   return CVO_OK;
 }
 
+int cvo_debug_device_buffer(cvo_ctx* ctx, size_t bytes, const void* host_src, void** d) {
+  if (!ctx || !d || bytes == 0) return fail(ctx, CVO_E_INVALID, "cvo_debug_device_buffer: bad argument");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const bool fresh = *d == nullptr;
+  if (fresh) {
+    const hipError_t e = hipMalloc(d, bytes);
+    if (e != hipSuccess) {
+      *d = nullptr;
+      return fail(ctx, CVO_E_NOMEM, std::string("cvo_debug_device_buffer hipMalloc: ") + hipGetErrorString(e));
+    }
+  }
+  if (host_src) {
+    const hipError_t e = hipMemcpy(*d, host_src, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+      if (fresh) {
+        (void)hipFree(*d);
+        *d = nullptr;
+      }
+      return fail(ctx, CVO_E_HIP, std::string("cvo_debug_device_buffer copy: ") + hipGetErrorString(e));
+    }
+  }
+  return CVO_OK;
+}
+
+int cvo_debug_device_release(cvo_ctx* ctx, void* d) {
+  if (!ctx) return CVO_E_INVALID;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (d) HIP_TRY(ctx, hipFree(d));
+  return CVO_OK;
+}
+
 int cvo_debug_last_score_batch(const cvo_ctx* ctx, int* overlap_evals, int* chain_evals, int* launches) {
   if (!ctx) return CVO_E_INVALID;
   if (overlap_evals) *overlap_evals = ctx->last_score_overlap;

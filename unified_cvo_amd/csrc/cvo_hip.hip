@@ -13,6 +13,7 @@
 //   cvo_export.hip  association / ELL exports                          cvo_debug.hip   test and profiling hooks
 //   cvo_irls.hip    multi-frame align (the least-squares solve of CvoBatchIRLS)
 //   cvo_frontend.hip  what the front ends below share: scratch regions, the ordered-compaction launcher, the route rule, the entry frame
+//   cvo_ingest.hip  resident clouds from rows that are already in device memory: checks, k_cloud_ingest, the route rule, k_cloud_gather
 //   cvo_voxel.hip   voxel-grid downsampling: selection on the device or the host, upload of the survivors
 //   cvo_rgbd.hip    RGB-D front end: depth + colour frame to candidate points and to a resident cloud
 //   cvo_fast.hip    the CV_FAST point selection: FAST-9/16 scores, the reference's threshold schedule
@@ -29,6 +30,7 @@
 #include "cvo_launch.hip"
 #include "cvo_upload.hip"
 #include "cvo_frontend.hip"
+#include "cvo_ingest.hip"
 #include "cvo_voxel.hip"
 #include "cvo_rgbd.hip"
 #include "cvo_fast.hip"

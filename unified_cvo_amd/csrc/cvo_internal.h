@@ -1,5 +1,5 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip, cvo_bki.hip, cvo_debug.hip) share: the context, a resident cloud, the typed walk that lays
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_ingest.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip, cvo_bki.hip, cvo_debug.hip) share: the context, a resident cloud, the typed walk that lays
 // out EVERY device region (ScratchLayout: a pair's workspace, the front ends' scratch, the map's table, a cloud's slabs), graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -214,6 +214,39 @@ struct ScratchLayout {
   void take(T*& ptr, size_t count) { take_as<T>(ptr, count); }
 };
 
+// THE list of a cloud slab's arrays, for both upload routes (upload_host_cloud in cvo_upload.hip, ingest_device_clouds in cvo_ingest.hip):
+// `a` is whatever names these arrays - a CloudArrays (the cloud itself, the staging buffer's view) or the KdJob of the
+// ordering kernel.  *up_bytes: the prefix a host upload stages and copies (the caller's rows when the device orders them,
+// everything otherwise).
+struct SlabShape {
+  size_t nn;  // max(n, 1)
+  int NP;     // k_kd_order's padded size
+  bool feat, label, geo, lid;
+  bool raw;   // the caller's rows in ORIGINAL order are part of the slab (a cloud ordered on the device; every device-built cloud)
+  bool kd;    // ... and k_kd_order's scratch
+};
+template <class A>
+inline auto cloud_slab_list(A& a, const SlabShape& s, size_t* up_bytes) {
+  return [&a, s, up_bytes](ScratchLayout& l) {
+    l.take(a.x4, s.nn);
+    if (s.raw && s.feat) l.take(a.raw_feat, FD * s.nn);
+    if (s.raw && s.label) l.take(a.raw_label, NC * s.nn);
+    if (s.raw && s.geo) l.take(a.raw_geo, 2 * s.nn);
+    if (s.raw && s.lid) l.take(a.raw_lid, s.nn);
+    if (s.raw) *up_bytes = l.off;
+    l.take(a.xs4, s.nn);
+    l.take(a.order, s.nn);
+    l.take(a.inv, s.nn);
+    if (s.feat) l.take(a.feat, 2 * s.nn);
+    if (s.label) l.take(a.label, 5 * s.nn);
+    if (s.geo) l.take(a.geo, s.nn);
+    if (s.lid) l.take(a.lid, s.nn);
+    if (s.kd) l.take(a.seg_of_pos, (size_t)s.NP);
+    if (s.kd) l.take(a.seg_lo, 2 * KD_MAX_SEGS);
+    if (!s.raw) *up_bytes = l.off;
+  };
+}
+
 // a growable device region of a front end, laid out anew by every call and used on upload_stream under upload_mutex
 struct DeviceScratch {
   char* p = nullptr;
@@ -327,6 +360,9 @@ struct cvo_ctx {
   char* dfilter_staging = nullptr;
   size_t dfilter_staging_bytes = 0;
   DFilterStatsAcc dfilter_last{};
+  // clouds from device rows (cvo_ingest.hip): one growable device region - the jobs of k_cloud_ingest / k_cloud_gather and a
+  // control block per cloud (flag words + per-block partials), read back with one copy
+  DeviceScratch ingest_scratch;
   double clock_ms_per_tick = 0.0;  // s_memrealtime, calibrated on first use (cvo_debug_kernel_clock)
 };
 

@@ -62,6 +62,7 @@
 #include "cvo_k_coeff_dense.h"
 #include "cvo_k_debug.h"
 #include "cvo_k_cloud.h"
+#include "cvo_k_ingest.h"
 #include "cvo_k_irls.h"
 #include "cvo_k_prims.h"
 #include "cvo_k_compact.h"

@@ -152,18 +152,8 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
     lid_host.resize((size_t)n);
     bool onehot = true;
     for (int i = 0; i < n && onehot; i++) {
-      const float* l = reinterpret_cast<const float*>(h.label + h.row(i) * h.label_stride);
-      int hot = -1, ones = 0;
-      for (int c = 0; c < NC; c++) {
-        if (l[c] == 1.0f) {
-          hot = c;
-          ones++;
-        } else if (!(l[c] == 0.0f)) {
-          ones = 2;  // (neither 0 nor 1: a soft distribution)
-        }
-      }
-      onehot = ones == 1;
-      lid_host[i] = hot;
+      lid_host[i] = label_onehot_class(reinterpret_cast<const float*>(h.label + h.row(i) * h.label_stride));  // (cvo_k_ingest.h)
+      onehot = lid_host[i] >= 0;
     }
     if (!onehot) lid_host.clear();
   }
@@ -172,29 +162,11 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
   while (NP < n) NP *= 2;
   // (device ordering: the caller's arrays go up in ORIGINAL order - x4 stays, the raw attribute arrays are scratch - and
   // the kernel writes the spatially ordered ones; host ordering: everything is staged in its final form)
-  // THE list of the slab's arrays, walked over two bases: the staging buffer (into s) and the slab (into the cloud itself
-  // and, for k_kd_order, into the job: `a` is whatever names these arrays)
+  // THE list of the slab's arrays (cloud_slab_list), walked over two bases: the staging buffer (into s) and the slab (into
+  // the cloud itself and, for k_kd_order, into the job)
   size_t up_bytes = 0;  // the prefix of the slab that is staged and uploaded
-  auto list = [&](auto& a) {
-    return [&](ScratchLayout& l) {
-      l.take(a.x4, nn);
-      if (device_order && h.feat) l.take(a.raw_feat, FD * nn);
-      if (device_order && h.label) l.take(a.raw_label, NC * nn);
-      if (device_order && h.geo) l.take(a.raw_geo, 2 * nn);
-      if (device_order && has_lid) l.take(a.raw_lid, nn);
-      if (device_order) up_bytes = l.off;
-      l.take(a.xs4, nn);
-      l.take(a.order, nn);
-      l.take(a.inv, nn);
-      if (h.feat) l.take(a.feat, 2 * nn);
-      if (h.label) l.take(a.label, 5 * nn);
-      if (h.geo) l.take(a.geo, nn);
-      if (has_lid) l.take(a.lid, nn);
-      if (device_order) l.take(a.seg_of_pos, (size_t)NP);
-      if (device_order) l.take(a.seg_lo, 2 * KD_MAX_SEGS);
-      if (!device_order) up_bytes = l.off;
-    };
-  };
+  const SlabShape shape{nn, NP, h.feat != nullptr, h.label != nullptr, h.geo != nullptr, has_lid, device_order, device_order};
+  auto list = [&](auto& a) { return cloud_slab_list(a, shape, &up_bytes); };
   CloudArrays s;
   const size_t slab_bytes = ScratchLayout().walk(list(s));
   std::vector<char>& stage = sc->stage;
