@@ -41,7 +41,7 @@ struct cvo_map {
   BkiHostMap host;
   // the device side: one allocation behind the table; the hits of an insert and its work arrays
   BkiTable t{};
-  char* slab = nullptr;
+  DeviceRegion slab;
   unsigned long long slots = 0, voxels = 0, initial_slots = 0;
   long long occupied = -1;  // -1: not counted since the last insert
   int growths = 0;
@@ -206,7 +206,7 @@ unsigned bki_blocks(unsigned long long n) { return (unsigned)((n + BKI_THREADS -
 unsigned bki_stride_blocks(unsigned long long n) { return std::max(1u, std::min(bki_blocks(n), (unsigned)BKI_GRID_MAX)); }
 
 // a fresh table of `slots` slots: keys empty, ms = prior, fs and the counters zero
-int bki_table_alloc(cvo_map* m, unsigned long long slots, BkiTable* t, char** slab) {
+int bki_table_alloc(cvo_map* m, unsigned long long slots, BkiTable* t, DeviceRegion* slab) {
   cvo_ctx* ctx = m->ctx;
   const BkiConst& k = m->k;
   const int ncnt = k.nclass + 1;
@@ -218,11 +218,7 @@ int bki_table_alloc(cvo_map* m, unsigned long long slots, BkiTable* t, char** sl
     l.take(t->cnt, slots * (size_t)ncnt);
     l.take(t->segoff, slots);
   };
-  char* p = nullptr;
-  const hipError_t e = hipMalloc(&p, ScratchLayout().walk(list));
-  if (e != hipSuccess) return fail(ctx, CVO_E_NOMEM, std::string("voxel map table hipMalloc: ") + hipGetErrorString(e));
-  *slab = p;
-  ScratchLayout(p).walk(list);
+  if (const int rc = slab->lay_out(ctx, "voxel map table", list, nullptr); rc != CVO_OK) return rc;
   hipStream_t st = ctx->upload_stream;
   hipError_t r = hipMemsetAsync(t->keys, 0xFF, 8 * slots, st);
   if (r == hipSuccess) r = hipMemsetAsync(t->fs, 0, 4 * slots * BKI_FEAT, st);
@@ -232,9 +228,8 @@ int bki_table_alloc(cvo_map* m, unsigned long long slots, BkiTable* t, char** sl
     r = hipGetLastError();
   }
   if (r != hipSuccess) {
-    (void)hipStreamSynchronize(st);
-    (void)hipFree(p);
-    *slab = nullptr;
+    (void)hipStreamSynchronize(st);  // (what was enqueued writes the table: it goes with the caller's owner only after this)
+    slab->release();
     return fail(ctx, CVO_E_HIP, std::string("voxel map table: ") + hipGetErrorString(r));
   }
   return CVO_OK;
@@ -248,24 +243,18 @@ int bki_table_grow(cvo_map* m, unsigned long long need) {
     const unsigned long long slots = m->slots ? 2 * m->slots : m->initial_slots;
     if (slots > BKI_MAX_SLOTS) return fail(ctx, CVO_E_UNSUPPORTED, "the voxel map would need more than 2^30 slots");
     BkiTable t{};
-    char* slab = nullptr;
+    DeviceRegion slab;
     int rc = bki_table_alloc(m, slots, &t, &slab);
     if (rc != CVO_OK) return rc;
     hipError_t e = hipSuccess;
-    if (m->slab) {
+    if (m->slab.p) {
       hipLaunchKernelGGL(k_bki_rehash, dim3(bki_stride_blocks(m->slots)), dim3(BKI_THREADS), 0, ctx->upload_stream, m->t, t);
       e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->upload_stream);
-    if (e != hipSuccess) {
-      (void)hipFree(slab);
-      return fail(ctx, CVO_E_HIP, std::string("voxel map rehash: ") + hipGetErrorString(e));
-    }
-    if (m->slab) {
-      (void)hipFree(m->slab);
-      m->growths++;
-    }
-    m->slab = slab;
+    if (e != hipSuccess) return fail(ctx, CVO_E_HIP, std::string("voxel map rehash: ") + hipGetErrorString(e));
+    if (m->slab.p) m->growths++;
+    m->slab = std::move(slab);  // (the old table goes here)
     m->t = t;
     m->slots = slots;
   }
@@ -538,15 +527,13 @@ int cvo_map_open_host(const cvo_map_config_t* cfg, cvo_map** out) { return bki_o
 
 void cvo_map_close(cvo_map* m) {
   if (!m) return;
+  std::unique_lock<std::mutex> lk;
   if (m->ctx) {
-    std::lock_guard<std::mutex> lk(m->ctx->upload_mutex);
+    lk = std::unique_lock<std::mutex>(m->ctx->upload_mutex);
     (void)hipSetDevice(m->ctx->device);
     (void)hipStreamSynchronize(m->ctx->upload_stream);
-    if (m->slab) (void)hipFree(m->slab);
-    m->in_scratch.release();
-    m->work_scratch.release();
   }
-  delete m;
+  delete m;  // (the table and both scratch regions go with it)
 }
 
 void cvo_map_close_host(cvo_map* m) {

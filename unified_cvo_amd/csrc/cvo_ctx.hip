@@ -77,33 +77,6 @@ size_t place_regions(PairDesc& D, uintptr_t base, int N, const Dims& d, int Kmax
   return l.off;
 }
 
-void free_control_block(cvo_ctx* c) {
-  if (c->d_ctl) (void)hipFree(c->d_ctl);
-  if (c->h_ctl) (void)hipHostFree(c->h_ctl);
-  for (int i = 0; i < 2; i++)
-    if (c->h_status[i]) (void)hipHostFree(c->h_status[i]);
-  c->d_ctl = c->h_ctl = nullptr;
-  c->d_params = nullptr;
-  c->d_descs = nullptr;
-  c->d_states = nullptr;
-  c->d_status = nullptr;
-  c->h_status[0] = c->h_status[1] = nullptr;
-  c->cap_pairs = 0;
-}
-
-void free_workspace(cvo_ctx* c) {
-  if (c->arena) (void)hipFree(c->arena);
-  if (c->d_sb) (void)hipFree(c->d_sb);
-  if (c->d_sb_table) (void)hipFree(c->d_sb_table);
-  if (c->h_sb) (void)hipHostFree(c->h_sb);
-  if (c->h_sb_res) (void)hipHostFree(c->h_sb_res);
-  c->d_sb = c->d_sb_table = c->h_sb = c->h_sb_res = nullptr;
-  c->sb_jobs_cap = c->sb_tiles_cap = 0;
-  free_control_block(c);
-  c->arena = nullptr;
-  c->arena_bytes = 0;
-}
-
 void drop_graphs(cvo_ctx* c) {
   auto drop = [](CachedGraph& cg) {
     if (cg.exec) (void)hipGraphExecDestroy(cg.exec);
@@ -115,35 +88,20 @@ void drop_graphs(cvo_ctx* c) {
 }
 
 int ensure_workspace(cvo_ctx* c, int n_pairs, size_t bytes_per_pair) {
+  // (no stream to drain: no call is in flight on this context, every call ends synchronised)
+  int rc = CVO_OK;
+  bool moved = false;
   if (n_pairs > c->cap_pairs) {
-    free_control_block(c);
-    // control block: [DevParams | status words: per sub-batch status[n_g], want[n_g] | PairDesc[n] | PairState[n]]
-    c->ctl_off_status = align_up(sizeof(DevParams), 256);
-    c->ctl_off_descs = align_up(c->ctl_off_status + sizeof(int) * 2 * (size_t)n_pairs, 256);
-    c->ctl_off_states = align_up(c->ctl_off_descs + sizeof(PairDesc) * (size_t)n_pairs, 256);
-    c->ctl_bytes = align_up(c->ctl_off_states + sizeof(PairState) * (size_t)n_pairs, 256);
-    HIP_TRY(c, hipMalloc(&c->d_ctl, c->ctl_bytes));
-    HIP_TRY(c, hipHostMalloc(&c->h_ctl, c->ctl_bytes, hipHostMallocDefault));
-    c->d_params = (DevParams*)c->d_ctl;
-    c->d_status = (int*)(c->d_ctl + c->ctl_off_status);
-    c->d_descs = (PairDesc*)(c->d_ctl + c->ctl_off_descs);
-    c->d_states = (PairState*)(c->d_ctl + c->ctl_off_states);
-    for (int i = 0; i < 2; i++)  // fine-grained: what the device writes there needs no cache maintenance to be seen
-      HIP_TRY(c, hipHostMalloc(&c->h_status[i], sizeof(int) * 2 * (size_t)n_pairs, hipHostMallocMapped | hipHostMallocCoherent));
-    c->cap_pairs = n_pairs;
-    drop_graphs(c);
+    const size_t n = (size_t)n_pairs;
+    c->cap_pairs = 0;
+    rc = c->d_ctl.lay_out(c, "control block", control_block_list(c->d_params, c->d_status, c->d_descs, c->d_states, n), nullptr, &moved);
+    if (rc == CVO_OK) rc = c->h_ctl.lay_out(c, "control block staging", control_block_list(c->s_params, c->s_status, c->s_descs, c->s_states, n), nullptr);
+    for (int i = 0; i < 2 && rc == CVO_OK; i++) rc = c->h_status[i].reserve(c, sizeof(int) * 2 * n, "status mirror", nullptr);
+    if (rc == CVO_OK) c->cap_pairs = n_pairs;
   }
-  const size_t need = bytes_per_pair * (size_t)n_pairs;
-  if (need > c->arena_bytes) {
-    if (c->arena) (void)hipFree(c->arena);
-    c->arena = nullptr;
-    c->arena_bytes = 0;
-    hipError_t e = hipMalloc(&c->arena, need);
-    if (e != hipSuccess) return fail(c, CVO_E_NOMEM, "workspace hipMalloc failed: " + std::string(hipGetErrorString(e)));
-    c->arena_bytes = need;
-    drop_graphs(c);
-  }
-  return CVO_OK;
+  if (rc == CVO_OK) rc = c->arena.reserve(c, bytes_per_pair * (size_t)n_pairs, "workspace", nullptr, &moved);
+  if (moved) drop_graphs(c);  // (they hold the pointers)
+  return rc;
 }
 
 int coeff_split(int n) {
@@ -319,16 +277,6 @@ void cvo_ctx_destroy(cvo_ctx* c) {
     if (c->gstream[g]) drained = (hipStreamSynchronize(c->gstream[g]) == hipSuccess) && drained;
   if (c->upload_stream) drained = (hipStreamSynchronize(c->upload_stream) == hipSuccess) && drained;
   drop_graphs(c);
-  free_workspace(c);
-  if (c->d_kd_jobs) (void)hipFree(c->d_kd_jobs);
-  c->vox_scratch.release();
-  c->rgbd_scratch.release();
-  c->lidar_scratch.release();
-  c->nlm_scratch.release();
-  c->sgm_scratch.release();
-  c->dfilter_scratch.release();
-  c->ingest_scratch.release();
-  if (c->dfilter_staging) (void)hipHostFree(c->dfilter_staging);
   for (int g = 0; g < cvo_ctx::MAX_GROUPS; g++) {
     for (int i = 0; i < 2; i++)
       if (c->ev_chk[i][g]) (void)hipEventDestroy(c->ev_chk[i][g]);
@@ -353,7 +301,7 @@ void cvo_ctx_destroy(cvo_ctx* c) {
       if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
     }
   }
-  delete c;
+  delete c;  // (every region the context owns goes with it)
 }
 
 void cvo_shutdown(void) {

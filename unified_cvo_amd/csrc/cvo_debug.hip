@@ -7,19 +7,14 @@ int cvo_debug_scalar_math(cvo_ctx* ctx, int op, int n, const double* in, double*
   if (!ctx || !in || !out || n <= 0 || op < 0 || op > 13) return fail(ctx, CVO_E_INVALID, "cvo_debug_scalar_math: bad argument");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t n_in = op == 7 ? (size_t)n + 2 : 16 * (size_t)n, n_out = op == 7 ? (size_t)n : 16 * (size_t)n;
-  double *d_in = nullptr, *d_out = nullptr;
-  PairState* d_st = nullptr;
-  int rc = CVO_OK;
-  auto cleanup = [&]() {
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (d_st) (void)hipFree(d_st);
-  };
-  if (hipMalloc(&d_in, sizeof(double) * n_in) != hipSuccess || hipMalloc(&d_out, sizeof(double) * n_out) != hipSuccess ||
-      hipMalloc(&d_st, sizeof(PairState)) != hipSuccess) {
-    cleanup();
-    return fail(ctx, CVO_E_NOMEM, "cvo_debug_scalar_math: hipMalloc failed");
-  }
+  DeviceRegion r_in, r_out, r_st;
+  const char* who = "cvo_debug_scalar_math";
+  int rc;
+  if ((rc = r_in.reserve(ctx, sizeof(double) * n_in, who, nullptr)) != CVO_OK || (rc = r_out.reserve(ctx, sizeof(double) * n_out, who, nullptr)) != CVO_OK ||
+      (rc = r_st.reserve(ctx, sizeof(PairState), who, nullptr)) != CVO_OK)
+    return rc;
+  double *d_in = r_in.as<double>(), *d_out = r_out.as<double>();
+  PairState* d_st = r_st.as<PairState>();
   hipError_t e = hipMemcpyAsync(d_in, in, sizeof(double) * n_in, hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(d_out, 0, sizeof(double) * n_out, ctx->stream);
   if (e == hipSuccess) e = hipMemsetAsync(d_st, 0, sizeof(PairState), ctx->stream);
@@ -29,9 +24,8 @@ int cvo_debug_scalar_math(cvo_ctx* ctx, int op, int n, const double* in, double*
   }
   if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(double) * n_out, hipMemcpyDeviceToHost, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  if (e != hipSuccess) rc = fail(ctx, CVO_E_HIP, std::string("cvo_debug_scalar_math: ") + hipGetErrorString(e));
-  cleanup();
-  return rc;
+  if (e != hipSuccess) return fail(ctx, CVO_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  return CVO_OK;
 }
 
 // Every size the kernels index with is checked here: nothing the caller passes can make them leave the three arrays.
@@ -64,15 +58,20 @@ int cvo_debug_prim(cvo_ctx* ctx, int op, int n, int m, unsigned long long* k64, 
   std::lock_guard<std::mutex> lk(ctx->upload_mutex);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->upload_stream;
-  void* host[3] = {k64, a, b};
-  const size_t bytes[3] = {8 * n64, 4 * na, 4 * nb}, off[3] = {0, 8 * n64, 8 * n64 + align_up(4 * na, 8)};
-  char* d = nullptr;
-  HIP_TRY(ctx, hipMalloc(&d, off[2] + bytes[2] + 8));
-  unsigned long long* d64 = (unsigned long long*)d;
-  unsigned *da = (unsigned*)(d + off[1]), *db = (unsigned*)(d + off[2]);
+  unsigned long long* d64 = nullptr;
+  unsigned *da = nullptr, *db = nullptr;
+  DeviceRegion d;  // (of this call)
+  const int rc = d.lay_out(ctx, who, [&](ScratchLayout& l) {
+    l.take(d64, n64);
+    l.take(da, na);
+    l.take(db, nb);
+  }, nullptr);
+  if (rc != CVO_OK) return rc;
+  void *host[3] = {k64, a, b}, *dev[3] = {d64, da, db};
+  const size_t bytes[3] = {8 * n64, 4 * na, 4 * nb};
   hipError_t e = hipSuccess;
   for (int q = 0; q < 3 && e == hipSuccess; q++)
-    if (bytes[q]) e = hipMemcpyAsync(d + off[q], host[q], bytes[q], hipMemcpyHostToDevice, st);
+    if (bytes[q]) e = hipMemcpyAsync(dev[q], host[q], bytes[q], hipMemcpyHostToDevice, st);
   if (e == hipSuccess) {
     const dim3 grid((unsigned)std::max(1, (lanes + threads - 1) / threads));
     if (op == PRIM_SCAN) {
@@ -88,9 +87,8 @@ int cvo_debug_prim(cvo_ctx* ctx, int op, int n, int m, unsigned long long* k64, 
     e = hipGetLastError();
   }
   for (int q = 0; q < 3 && e == hipSuccess; q++)
-    if (bytes[q]) e = hipMemcpyAsync(host[q], d + off[q], bytes[q], hipMemcpyDeviceToHost, st);
+    if (bytes[q]) e = hipMemcpyAsync(host[q], dev[q], bytes[q], hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(d);
   if (e != hipSuccess) return fail(ctx, CVO_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
   return CVO_OK;
 }

@@ -149,23 +149,18 @@ int dfilter_device(cvo_ctx* ctx, const DFilterConst& k, const float* in, const f
   if (rc != CVO_OK) return rc;
   // (the read-back keeps offsets, not pointers: a later refused call may move the region while this call's record stands)
   auto offset_of = [&](const float* p) { return (size_t)((const char*)p - ctx->dfilter_scratch.p); };
-  // pinned staging: [the map going up][the result and its counters coming down]
-  const size_t down = align_up(map, 256), staging = down + map + sizeof(DFilterCounters);
-  if (staging > ctx->dfilter_staging_bytes) {
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (ctx->dfilter_staging) (void)hipHostFree(ctx->dfilter_staging);
-    ctx->dfilter_staging = nullptr;
-    ctx->dfilter_staging_bytes = 0;
-    const hipError_t e = hipHostMalloc(&ctx->dfilter_staging, staging, hipHostMallocDefault);
-    if (e != hipSuccess) return ctx->dfilter_staging = nullptr, fail(ctx, CVO_E_NOMEM, std::string("disparity filter staging hipHostMalloc: ") + hipGetErrorString(e));
-    ctx->dfilter_staging_bytes = staging;
-  }
-  char* host = ctx->dfilter_staging;
+  // pinned staging: [the map going up | the result and its counters coming down]
+  char *h_up = nullptr, *h_down = nullptr;
+  const int rc_staging = ctx->dfilter_staging.lay_out(ctx, "disparity filter staging", [&](ScratchLayout& l) {
+    l.take(h_up, map);
+    l.take(h_down, map + sizeof(DFilterCounters));
+  });
+  if (rc_staging != CVO_OK) return rc_staging;
   DFilterCounters* counters = (DFilterCounters*)(d_out + np);
   HIP_TRY(ctx, hipMemsetAsync(counters, 0, sizeof *counters, st));
   if (!d_in) {
-    std::memcpy(host, in, map);
-    HIP_TRY(ctx, hipMemcpyAsync(d_map, host, map, hipMemcpyHostToDevice, st));
+    std::memcpy(h_up, in, map);
+    HIP_TRY(ctx, hipMemcpyAsync(d_map, h_up, map, hipMemcpyHostToDevice, st));
     d_in = d_map;
   }
   const int tiles_x = (k.cols + DFILTER_TILE_W - 1) / DFILTER_TILE_W;
@@ -231,11 +226,11 @@ int dfilter_device(cvo_ctx* ctx, const DFilterConst& k, const float* in, const f
   stats.tmp_resident = mean;
   if (cur != d_out) HIP_TRY(ctx, hipMemcpyAsync(d_out, cur, map, hipMemcpyDeviceToDevice, st));  // (every stage off)
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(host + down, d_out, map + sizeof(DFilterCounters), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipMemcpyAsync(h_down, d_out, map + sizeof(DFilterCounters), hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
-  std::memcpy(out, host + down, map);  // (nothing is written unless the call succeeds)
+  std::memcpy(out, h_down, map);  // (nothing is written unless the call succeeds)
   DFilterCounters c;
-  std::memcpy(&c, host + down + map, sizeof c);
+  std::memcpy(&c, h_down + map, sizeof c);
   stats.segments = c.segments;
   stats.removed = c.removed;
   stats.filled = (unsigned long long)c.filled_rows + c.filled_cols;

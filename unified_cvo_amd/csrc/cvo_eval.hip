@@ -96,15 +96,13 @@ void fill_overlap_job(const cvo_cloud* X, const cvo_cloud* Y, const float* Tm, f
 int ensure_tiles(cvo_ctx* ctx, const cvo_cloud* c, hipStream_t s) {
   if (c->tile4) return CVO_OK;
   const int nt = (c->n + 63) / 64;
-  float4* t = nullptr;
-  HIP_TRY(ctx, hipMalloc(&t, sizeof(float4) * 2 * (size_t)nt));
-  hipLaunchKernelGGL(k_tile_spheres, dim3((nt + 3) / 4), dim3(256), 0, s, c->n, c->xs4, t);
+  DeviceRegion t;
+  if (const int rc = t.reserve(ctx, sizeof(float4) * 2 * (size_t)nt, "tile spheres", nullptr); rc != CVO_OK) return rc;
+  hipLaunchKernelGGL(k_tile_spheres, dim3((nt + 3) / 4), dim3(256), 0, s, c->n, c->xs4, t.as<float4>());
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) {
-    (void)hipFree(t);
-    return fail(ctx, CVO_E_HIP, std::string("k_tile_spheres: ") + hipGetErrorString(e));
-  }
-  c->tile4 = t;
+  if (e != hipSuccess) return fail(ctx, CVO_E_HIP, std::string("k_tile_spheres: ") + hipGetErrorString(e));
+  c->tiles = std::move(t);
+  c->tile4 = c->tiles.as<float4>();
   return CVO_OK;
 }
 
@@ -132,7 +130,7 @@ int run_ip_chain(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_clou
   if (rc != CVO_OK) return rc;
   HIP_TRY(ctx, hipGraphLaunch(ctx->chain_graph.exec, g.stream));
   HIP_TRY(ctx, hipStreamSynchronize(g.stream));
-  const volatile double* res = reinterpret_cast<const volatile double*>(ctx->h_status[1]);
+  const volatile double* res = ctx->h_status[1].as<double>();
   for (int p = 0; p < n; p++) {
     out[p] = res[p];
     ctx->h_states[p].asum = res[p];
@@ -146,33 +144,46 @@ int run_ip_chain(cvo_ctx* ctx, const cvo_params_t* params, int n, const cvo_clou
 // One launch of k_overlap and one synchronisation per chunk of the evaluation list.
 constexpr int SB_CHUNK_JOBS = 1024;    // jobs per launch (pinned results, device table and its staging are sized by it)
 constexpr int SB_CHUNK_TILES = 65536;  // row tiles per launch (4M source rows), unless one job alone has more
-constexpr size_t SB_START_BYTES = (sizeof(int) * (SB_CHUNK_JOBS + 1) + 255) / 256 * 256;
-constexpr size_t SB_TABLE_BYTES = SB_START_BYTES + (sizeof(OverlapJob) * SB_CHUNK_JOBS + 255) / 256 * 256;
-constexpr size_t SB_GATE_BYTES = (sizeof(int) * 2 * SB_CHUNK_JOBS + 255) / 256 * 256;
 
 struct ScoreResult {  // what k_overlap posts for one evaluation: the sum and its void flag in one 16-byte slot
   double sum;
   int over;
 };
 
-// Device workspace [gate words | partials] and the pinned results (a small call's slots share one cache line).  Gate words
-// are zeroed here once; the kernel leaves them at zero.
-int score_ws_reserve(cvo_ctx* ctx, int tiles) {
-  if (ctx->d_sb && tiles <= ctx->sb_tiles_cap) return CVO_OK;
-  const int tiles_cap = std::max(tiles, ctx->sb_tiles_cap);
-  if (ctx->d_sb) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->d_sb);
+// The score workspace [gate words | partials]: the partials are its open tail, as many row tiles as the region has room for
+struct ScoreWs {
+  int* gate = nullptr;
+  double* part = nullptr;
+  auto list() {
+    return [this](ScratchLayout& l) {
+      l.take(gate, 2 * SB_CHUNK_JOBS);
+      l.at(part, l.off);
+    };
   }
-  ctx->d_sb = nullptr;
-  ctx->sb_tiles_cap = ctx->sb_jobs_cap = 0;
-  HIP_TRY(ctx, hipMalloc(&ctx->d_sb, SB_GATE_BYTES + sizeof(double) * (size_t)tiles_cap));
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_sb, 0, SB_GATE_BYTES, ctx->stream));
-  if (!ctx->h_sb_res)
-    HIP_TRY(ctx, hipHostMalloc(&ctx->h_sb_res, sizeof(ScoreResult) * SB_CHUNK_JOBS, hipHostMallocMapped | hipHostMallocCoherent));
-  ctx->sb_jobs_cap = SB_CHUNK_JOBS;
-  ctx->sb_tiles_cap = tiles_cap;
-  return CVO_OK;
+};
+// The job table [tile starts | jobs] of k_overlap_table, over the device table and over its pinned staging
+struct ScoreTable {
+  int* start = nullptr;
+  OverlapJob* jobs = nullptr;
+  auto list() {
+    return [this](ScratchLayout& l) {
+      l.take(start, SB_CHUNK_JOBS + 1);
+      l.take(jobs, SB_CHUNK_JOBS);
+    };
+  }
+};
+
+// Room for `tiles` row tiles in the device workspace, and the pinned results (a small call's slots share one cache line).
+// Gate words are zeroed once per region; the kernel leaves them at zero.  *tiles_cap: the tiles the region holds.
+int score_ws_reserve(cvo_ctx* ctx, int tiles, ScoreWs* ws, int* tiles_cap) {
+  const size_t gate_bytes = ScratchLayout().walk(ws->list());
+  bool moved = false;
+  int rc = ctx->d_sb.reserve(ctx, gate_bytes + sizeof(double) * (size_t)tiles, "score workspace", ctx->stream, &moved);
+  if (rc != CVO_OK) return rc;
+  ScratchLayout(ctx->d_sb.p).walk(ws->list());
+  *tiles_cap = (int)((ctx->d_sb.bytes - gate_bytes) / sizeof(double));
+  if (moved) HIP_TRY(ctx, hipMemsetAsync(ws->gate, 0, gate_bytes, ctx->stream));
+  return ctx->h_sb_res.reserve(ctx, sizeof(ScoreResult) * SB_CHUNK_JOBS, "score results", nullptr);
 }
 
 struct ScoreEval {
@@ -213,29 +224,31 @@ int score_overlap(cvo_ctx* ctx, const cvo_params_t* params, std::pmr::vector<Sco
   std::pmr::vector<int> order(ev.size(), ev.get_allocator());
   for (size_t i = 0; i < ev.size(); i++) order[i] = (int)i;
   if (!by_args) std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return ev[a].X->n > ev[b].X->n; });
-  if ((rc = score_ws_reserve(ctx, by_args ? (int)tiles_sum : std::max(SB_CHUNK_TILES, tiles_max))) != CVO_OK) return rc;
+  ScoreWs ws;
+  int tiles_cap = 0;
+  if ((rc = score_ws_reserve(ctx, by_args ? (int)tiles_sum : std::max(SB_CHUNK_TILES, tiles_max), &ws, &tiles_cap)) != CVO_OK) return rc;
   OverlapArgs A;
   std::memset(&A, 0, sizeof(A));
   A.P = P;
   OverlapJob* jobs = A.job;
-  int* h_start = nullptr;
+  ScoreTable dt, ht;
   if (!by_args) {
-    if (!ctx->d_sb_table) HIP_TRY(ctx, hipMalloc(&ctx->d_sb_table, SB_TABLE_BYTES));
-    if (!ctx->h_sb) HIP_TRY(ctx, hipHostMalloc(&ctx->h_sb, SB_TABLE_BYTES, hipHostMallocDefault));
-    h_start = reinterpret_cast<int*>(ctx->h_sb);
-    jobs = reinterpret_cast<OverlapJob*>(ctx->h_sb + SB_START_BYTES);
+    if ((rc = ctx->d_sb_table.lay_out(ctx, "score table", dt.list(), nullptr)) != CVO_OK) return rc;
+    if ((rc = ctx->h_sb.lay_out(ctx, "score table staging", ht.list(), nullptr)) != CVO_OK) return rc;
+    jobs = ht.jobs;
   }
-  const int* d_start = reinterpret_cast<const int*>(ctx->d_sb_table);
-  const OverlapJob* d_jobs = reinterpret_cast<const OverlapJob*>(ctx->d_sb_table + SB_START_BYTES);
-  int* d_gate = reinterpret_cast<int*>(ctx->d_sb);
-  double* d_part = reinterpret_cast<double*>(ctx->d_sb + SB_GATE_BYTES);
-  ScoreResult* h_res = reinterpret_cast<ScoreResult*>(ctx->h_sb_res);
+  int* const h_start = ht.start;
+  const int* d_start = dt.start;
+  const OverlapJob* d_jobs = dt.jobs;
+  int* d_gate = ws.gate;
+  double* d_part = ws.part;
+  ScoreResult* h_res = ctx->h_sb_res.as<ScoreResult>();
   for (size_t pos = 0; pos < order.size();) {
     int n = 0, tiles = 0;
     while (pos + n < order.size() && n < SB_CHUNK_JOBS) {
       const ScoreEval& e = ev[order[pos + n]];
       const int t = (e.X->n + 63) / 64;
-      if (n > 0 && tiles + t > ctx->sb_tiles_cap) break;
+      if (n > 0 && tiles + t > tiles_cap) break;
       OverlapJob& J = jobs[n];
       std::memset(&J, 0, sizeof(J));
       fill_overlap_job(e.X, e.Y, e.T, e.ell, params->nearest_neighbors_max, J);
@@ -258,8 +271,7 @@ int score_overlap(cvo_ctx* ctx, const cvo_params_t* params, std::pmr::vector<Sco
       }
     } else {
       h_start[n] = tiles;
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sb_table, ctx->h_sb, SB_START_BYTES + sizeof(OverlapJob) * (size_t)n, hipMemcpyHostToDevice,
-                                  stream));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_sb_table.p, ctx->h_sb.p, (size_t)((const char*)(jobs + n) - ctx->h_sb.p), hipMemcpyHostToDevice, stream));
       const dim3 grid(tiles);
       switch (feat) {
         case FEAT_GEO: hipLaunchKernelGGL((k_overlap_table<FEAT_GEO>), grid, block, 0, stream, d_jobs, d_start, n, P); break;

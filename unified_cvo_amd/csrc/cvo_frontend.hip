@@ -1,6 +1,6 @@
 // cvo_frontend.hip -- what the front ends (cvo_voxel.hip, cvo_rgbd.hip, cvo_fast.hip, cvo_stereo.hip, cvo_lidar.hip, cvo_nlm.hip,
 // cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip) share on the host: the growable scratch regions (a front end writes ONE list of its buffers, DeviceScratch::lay_out
-// sizes and binds it: cvo_internal.h), the launches of an ordered compaction (cvo_k_compact.h) and of the radix sort (cvo_k_sort.h), the read-back of
+// sizes and binds it, draining upload_stream before the region moves: cvo_internal.h), the launches of an ordered compaction (cvo_k_compact.h) and of the radix sort (cvo_k_sort.h), the read-back of
 // a compaction's total, the route rule, the frame of an entry point and the copy-out of the kept indices.
 // A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.  Shared declarations: cvo_internal.h.
 //
@@ -13,20 +13,6 @@
 //             upload_mutex" and never enters an extern "C" function: the mutex is not recursive;
 //   commit    the body chooses the route (!ctx || route_on_host(...) is the CPU twin) and, as its last statement and only with
 //             a context, stores ctx->X_last = stats: a call that fails or is refused leaves the previous call's stats.
-
-// Room for `need` bytes: a region that is too small is given back once upload_stream has drained and allocated anew.
-int DeviceScratch::reserve(cvo_ctx* ctx, size_t need, const char* what) {
-  if (need <= bytes) return CVO_OK;
-  HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
-  release();
-  const hipError_t e = hipMalloc(&p, need);
-  if (e != hipSuccess) {
-    p = nullptr;
-    return fail(ctx, CVO_E_NOMEM, std::string(what) + " hipMalloc: " + hipGetErrorString(e));
-  }
-  bytes = need;
-  return CVO_OK;
-}
 
 namespace {
 

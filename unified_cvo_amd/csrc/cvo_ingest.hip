@@ -91,10 +91,10 @@ int ingest_device_clouds(cvo_ctx* ctx, int n_clouds, const cvo_device_rows_t* ro
     shapes[q] = SlabShape{(size_t)std::max(d.n, 1), NP, has && d.feat, has && d.label, has && d.geotype, has && d.label && !ctx->opt.no_onehot,
                           has, has && d.n >= 8 && d.n <= KD_MAX_POINTS && switches_device};
     size_t unused = 0;
-    c->slab_bytes = ScratchLayout().walk(cloud_slab_list(*c, shapes[q], &unused));
-    const hipError_t e = hipMalloc(&c->slab, c->slab_bytes);
-    if (e != hipSuccess) return hip_fail("cloud hipMalloc", e);
-    ScratchLayout(c->slab).walk(cloud_slab_list(*c, shapes[q], &unused));
+    if (const int rc = c->slab.lay_out(ctx, "cloud", cloud_slab_list(*c, shapes[q], &unused), nullptr); rc != CVO_OK) {
+      release();
+      return rc;
+    }
     if (has) {
       n_jobs++;
       gx = std::max(gx, std::min((d.n + INGEST_THREADS - 1) / INGEST_THREADS, INGEST_MAX_BLOCKS));
@@ -190,7 +190,7 @@ int ingest_device_clouds(cvo_ctx* ctx, int n_clouds, const cvo_device_rows_t* ro
     s.kd = s.kd && f.finite != 0u;  // the route rule of upload_host_cloud
     KdJob job{};
     size_t unused = 0;  // the job's pointers: the same list over the same slab, minus the class ids of a cloud that is not one-hot
-    ScratchLayout(c->slab).walk(cloud_slab_list(job, shapes[q], &unused));
+    ScratchLayout(c->slab.p).walk(cloud_slab_list(job, shapes[q], &unused));
     if (!has_lid) job.raw_lid = job.lid = nullptr;
     job.n = n;
     job.NP = shapes[q].NP;

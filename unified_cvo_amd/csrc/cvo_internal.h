@@ -1,6 +1,7 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
 // cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_ingest.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip, cvo_bki.hip, cvo_debug.hip) share: the context, a resident cloud, the typed walk that lays
-// out EVERY device region (ScratchLayout: a pair's workspace, the front ends' scratch, the map's table, a cloud's slabs), graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
+// out EVERY device region (ScratchLayout: a pair's workspace, the front ends' scratch, the map's table, a cloud's slabs, the control block, the score blocks), the owner of
+// EVERY device and pinned allocation (Region: move-only, frees in its destructor, ONE grow rule - drain, free, allocate, tell the caller it moved), graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,7 @@
 #include <string>
 #include <thread>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "cvo_kernels.h"
@@ -46,23 +48,6 @@ struct CloudArrays {
   float *raw_feat = nullptr, *raw_label = nullptr, *raw_geo = nullptr;
   int* raw_lid = nullptr;
   unsigned short *seg_of_pos = nullptr, *seg_lo = nullptr;
-};
-
-struct cvo_cloud : CloudArrays {
-  cvo_ctx* ctx = nullptr;  // identity check only: never dereferenced after upload (the context may be gone)
-  int device = 0;
-  int n = 0;
-  char* slab = nullptr;     // the one device allocation behind the arrays
-  size_t slab_bytes = 0;
-  // Attributes the caller did not supply are zeros (what the reference leaves in the default-constructed CvoPoint).
-  // They are not uploaded: a zeroed slab is allocated the first time a call needs them (colour / semantic /
-  // geometric-type kernels on a cloud without those arrays), see ensure_attributes.
-  mutable char* zero_slab = nullptr;
-  // bounding spheres of the 64-point tiles of xs4 (k_tile_spheres), made the first time k_overlap reads this cloud
-  mutable float4* tile4 = nullptr;
-  std::vector<int> h_order;  // host copy (the ELL is stored by sorted row; exports map it back)
-  float cx = 0, cy = 0, cz = 0;  // centroid (used only as the cull centre)
-  float rmax = 0;                // largest |p| (bounds the motion of any point under a pose change)
 };
 
 namespace {
@@ -247,41 +232,96 @@ inline auto cloud_slab_list(A& a, const SlabShape& s, size_t* up_bytes) {
   };
 }
 
-// a growable device region of a front end, laid out anew by every call and used on upload_stream under upload_mutex
-struct DeviceScratch {
+// THE owner of an allocation: every device and pinned region of the library is a member or a local of this type, and nothing
+// else calls hipMalloc / hipHostMalloc / hipFree / hipHostFree (but cvo_debug_device_buffer / _release, which hand a raw
+// pointer to the caller by contract).  Move-only; the destructor frees.  Defined below cvo_ctx.
+enum class Mem { Device, Pinned, Mapped };  // hipMalloc | hipHostMallocDefault | hipHostMallocMapped + Coherent (what the device writes there needs no cache maintenance to be seen)
+template <Mem K>
+struct Region {
   char* p = nullptr;
   size_t bytes = 0;
-  int reserve(cvo_ctx* ctx, size_t need, const char* what);  // cvo_frontend.hip; what: "voxel scratch", "RGB-D scratch"
+  Region() = default;
+  Region(Region&& o) noexcept : p(std::exchange(o.p, nullptr)), bytes(std::exchange(o.bytes, 0)) {}
+  Region& operator=(Region&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = std::exchange(o.p, nullptr);
+      bytes = std::exchange(o.bytes, 0);
+    }
+    return *this;
+  }
+  ~Region() { release(); }
+  void release() {
+    if (p) (void)(K == Mem::Device ? hipFree(p) : hipHostFree(p));
+    p = nullptr;
+    bytes = 0;
+  }
+  template <class T>
+  T* as() const { return reinterpret_cast<T*>(p); }
+  // Room for `need` bytes, grow-only: a region that is too small is given back once `drain` - the stream that may still
+  // read it, nullptr: none - has been synchronised, and allocated anew.  A failed allocation leaves the owner empty and is
+  // CVO_E_NOMEM "<what> hipMalloc: ...".  *moved (optional) is set when the region is a new one: whatever holds a pointer
+  // into it, or relies on its contents, acts on that.
+  int reserve(cvo_ctx* ctx, size_t need, const char* what, hipStream_t drain, bool* moved = nullptr);
   // Room for the buffers of `list(ScratchLayout&)`, then the list's pointers bound to them: the list sizes the region from
   // base 0 and is walked again from where the region is AFTER reserve, so no pointer outlives a reallocation.
   template <class List>
-  int lay_out(cvo_ctx* ctx, const char* what, List list) {
-    const int rc = reserve(ctx, ScratchLayout().walk(list), what);
+  int lay_out(cvo_ctx* ctx, const char* what, List list, hipStream_t drain, bool* moved = nullptr) {
+    const int rc = reserve(ctx, ScratchLayout().walk(list), what, drain, moved);
     if (rc != CVO_OK) return rc;
     ScratchLayout(p).walk(list);
     return CVO_OK;
   }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
+  // ... of a front end: laid out anew by every call and used on upload_stream under upload_mutex
+  template <class List>
+  int lay_out(cvo_ctx* ctx, const char* what, List list);
 };
+using DeviceRegion = Region<Mem::Device>;
+using DeviceScratch = DeviceRegion;  // (the front ends' name for theirs)
+using PinnedRegion = Region<Mem::Pinned>;
+using MappedRegion = Region<Mem::Mapped>;
+
+struct cvo_cloud : CloudArrays {
+  cvo_ctx* ctx = nullptr;  // identity check only: never dereferenced after upload (the context may be gone)
+  int device = 0;
+  int n = 0;
+  DeviceRegion slab;  // the one device allocation behind the arrays
+  // Attributes the caller did not supply are zeros (what the reference leaves in the default-constructed CvoPoint).
+  // They are not uploaded: a zeroed slab is allocated the first time a call needs them (colour / semantic /
+  // geometric-type kernels on a cloud without those arrays), see ensure_attributes.
+  mutable DeviceRegion zero_slab;
+  // bounding spheres of the 64-point tiles of xs4 (k_tile_spheres), made the first time k_overlap reads this cloud
+  mutable DeviceRegion tiles;
+  mutable float4* tile4 = nullptr;  // (typed view of `tiles`)
+  std::vector<int> h_order;  // host copy (the ELL is stored by sorted row; exports map it back)
+  float cx = 0, cy = 0, cz = 0;  // centroid (used only as the cull centre)
+  float rmax = 0;                // largest |p| (bounds the motion of any point under a pose change)
+};
+
+// THE list of the control block [DevParams | status words: per sub-batch status[n_g], want[n_g] | PairDesc[n] | PairState[n]],
+// walked once over the device block and once over its pinned staging copy
+inline auto control_block_list(DevParams*& params, int*& status, PairDesc*& descs, PairState*& states, size_t n) {
+  return [&params, &status, &descs, &states, n](ScratchLayout& l) {
+    l.take(params, 1);
+    l.take(status, 2 * n);
+    l.take(descs, n);
+    l.take(states, n);
+  };
+}
+
 
 struct cvo_ctx {
   int device = 0;
   CtxOptions opt;                          // the switches (cvo_options.h)
   std::mutex upload_mutex;                 // cvo_cloud_upload / _aos192 share upload_stream and the error string
   std::mutex kd_mutex;                     // the ordering launches of concurrent uploads share upload_stream and d_kd_jobs
-  KdJob* d_kd_jobs = nullptr;              // job descriptors of the running k_kd_order launch
-  int kd_jobs_cap = 0;
+  DeviceRegion d_kd_jobs;                  // job descriptors of the running k_kd_order launch
   hipStream_t stream = nullptr;
   hipStream_t upload_stream = nullptr;  // cvo_cloud_upload copies here (never waits for, nor delays, the solver's streams)
   std::string err;
   std::string advice;  // performance-relevant observations about the process set-up (cvo_ctx_advice), "" = none
   // workspace
-  char* arena = nullptr;
-  size_t arena_bytes = 0;
+  DeviceRegion arena;
   PairDesc* d_descs = nullptr;
   PairState* d_states = nullptr;
   int* d_status = nullptr;
@@ -289,24 +329,25 @@ struct cvo_ctx {
   // descriptors, states, status words and the parameter block live in ONE device allocation with a pinned staging copy
   // of the same layout: a call uploads its control state with one copy (four copies cost every cvo_align ~10 us and
   // an inner product a third of its time)
-  char* d_ctl = nullptr;
-  char* h_ctl = nullptr;
-  size_t ctl_bytes = 0, ctl_off_status = 0, ctl_off_descs = 0, ctl_off_states = 0;
+  DeviceRegion d_ctl;
+  PinnedRegion h_ctl;
+  DevParams* s_params = nullptr;  // the staging copy's parts (control_block_list over h_ctl, as d_params .. d_states over d_ctl)
+  int* s_status = nullptr;
+  PairDesc* s_descs = nullptr;
+  PairState* s_states = nullptr;
   int cap_pairs = 0;
   std::vector<PairDesc> h_descs;
   std::vector<PairState> h_states;
   // scores (cvo_inner_product / cvo_function_angle and their batches, k_overlap): per-job gate words (zero between
   // launches) + row-tile partials and the pinned results, sized on first use and grown (see score_ws_reserve); the device
   // job table + tile starts of k_overlap_table and its pinned staging, made by the first call that launches it
-  char* d_sb = nullptr;
-  char* d_sb_table = nullptr;
-  char* h_sb = nullptr;      // staging of the job table (one copy per k_overlap_table launch)
-  char* h_sb_res = nullptr;  // results: a double and a void flag per job (mapped, written by the device)
-  int sb_jobs_cap = 0, sb_tiles_cap = 0;
+  DeviceRegion d_sb, d_sb_table;
+  PinnedRegion h_sb;      // staging of the job table (one copy per k_overlap_table launch)
+  MappedRegion h_sb_res;  // results: a double and a void flag per job (written by the device)
   int last_score_overlap = 0, last_score_chain = 0, last_score_launches = 0;  // cvo_debug_last_score_batch
-  int* h_status[2] = {nullptr, nullptr};  // pinned; [0]: the live host mirror of the status / want words the device writes
-                                          // (PairDesc::status_host / want_host), [1]: a double per pair, the sum a single
-                                          // evaluation leaves for the host (PairDesc::asum_host, read by score_batch)
+  MappedRegion h_status[2];  // [0]: the live host mirror of the status / want words the device writes
+                             // (PairDesc::status_host / want_host), [1]: a double per pair, the sum a single
+                             // evaluation leaves for the host (PairDesc::asum_host, read by score_batch)
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   // A batch is split into up to MAX_GROUPS sub-batches, each enqueued on its own stream: the pairs are
   // independent, so one group's latency-bound kernels (k_update: one wave per pair) and launch tails
@@ -357,8 +398,7 @@ struct cvo_ctx {
   DeviceScratch dfilter_scratch;
   // ... and its pinned host staging, kept between calls: the map on its way up, the result with its counters on its way down
   // (a pageable 1.9 MB copy either way, into fresh pages every call, cost the call tens of milliseconds: DESIGN.md section 3)
-  char* dfilter_staging = nullptr;
-  size_t dfilter_staging_bytes = 0;
+  PinnedRegion dfilter_staging;
   DFilterStatsAcc dfilter_last{};
   // clouds from device rows (cvo_ingest.hip): one growable device region - the jobs of k_cloud_ingest / k_cloud_gather and a
   // control block per cloud (flag words + per-block partials), read back with one copy
@@ -381,3 +421,24 @@ int fail(cvo_ctx* ctx, int code, const std::string& msg) {
   } while (0)
 
 }  // namespace
+
+template <Mem K>
+int Region<K>::reserve(cvo_ctx* ctx, size_t need, const char* what, hipStream_t drain, bool* moved) {
+  if (need <= bytes) return CVO_OK;
+  if (drain) HIP_TRY(ctx, hipStreamSynchronize(drain));
+  release();
+  void* q = nullptr;
+  const hipError_t e = K == Mem::Device ? hipMalloc(&q, need)
+                                        : hipHostMalloc(&q, need, K == Mem::Pinned ? hipHostMallocDefault : hipHostMallocMapped | hipHostMallocCoherent);
+  if (e != hipSuccess) return fail(ctx, CVO_E_NOMEM, std::string(what) + " hipMalloc: " + hipGetErrorString(e));
+  p = static_cast<char*>(q);
+  bytes = need;
+  if (moved) *moved = true;
+  return CVO_OK;
+}
+
+template <Mem K>
+template <class List>
+int Region<K>::lay_out(cvo_ctx* ctx, const char* what, List list) {
+  return lay_out(ctx, what, list, ctx->upload_stream);
+}

@@ -9,13 +9,6 @@
 // unit); not compiled on its own.  Shared declarations: cvo_internal.h.
 namespace {
 
-struct DevAlloc {  // a device allocation released with the scope
-  void* p = nullptr;
-  ~DevAlloc() {
-    if (p) (void)hipFree(p);
-  }
-};
-
 // Exp_SE3(delta, is_wu = false) (LieGroup.cpp:169-192): u = delta[0..2] (translation), w = delta[3..5] (rotation);
 // Exp_SO3 / LeftJacobian_SO3 (LieGroup.cpp:28-55) with TOLERANCE = 1e-6f.  X: 3x4 row-major.
 void irls_exp_se3(const double d[6], double X[12]) {
@@ -209,13 +202,13 @@ int cvo_multiframe_align(cvo_ctx* ctx, const cvo_params_t* params, int n_frames,
     ent_off[k + 1] = ent_off[k] + slots;
     max_blocks += irls_blocks((int)slots);
   }
-  DevAlloc d_ent, d_edges, d_poses, d_part, d_out;
-  auto dmalloc = [&](DevAlloc& a, size_t bytes) -> hipError_t { return hipMalloc(&a.p, std::max<size_t>(bytes, 256)); };
-  if (dmalloc(d_ent, sizeof(IrlsEntry) * ent_off[E]) != hipSuccess || dmalloc(d_edges, sizeof(IrlsEdge) * E) != hipSuccess ||
-      dmalloc(d_poses, sizeof(double) * 12 * F) != hipSuccess ||
-      dmalloc(d_part, sizeof(double) * IRLS_W * (size_t)max_blocks) != hipSuccess ||
-      dmalloc(d_out, sizeof(double) * IRLS_W * E) != hipSuccess)
-    return fail(ctx, CVO_E_NOMEM, "cvo_multiframe_align: device allocation failed");
+  DeviceRegion d_ent, d_edges, d_poses, d_part, d_out;  // (of this call: they go with the scope)
+  auto dmalloc = [&](DeviceRegion& a, size_t bytes) { return a.reserve(ctx, std::max<size_t>(bytes, 256), "cvo_multiframe_align", nullptr); };
+  if (int rc; (rc = dmalloc(d_ent, sizeof(IrlsEntry) * ent_off[E])) != CVO_OK || (rc = dmalloc(d_edges, sizeof(IrlsEdge) * E)) != CVO_OK ||
+      (rc = dmalloc(d_poses, sizeof(double) * 12 * F)) != CVO_OK ||
+      (rc = dmalloc(d_part, sizeof(double) * IRLS_W * (size_t)max_blocks)) != CVO_OK ||
+      (rc = dmalloc(d_out, sizeof(double) * IRLS_W * E)) != CVO_OK)
+    return rc;
   IrlsEntry* ent = (IrlsEntry*)d_ent.p;
   IrlsDevice dv;
   dv.edges = (IrlsEdge*)d_edges.p;
@@ -242,10 +235,8 @@ int cvo_multiframe_align(cvo_ctx* ctx, const cvo_params_t* params, int n_frames,
                          clouds[f]->x4, clouds[f]->xs4, tf[f]->x4, tf[f]->xs4);
       HIP_TRY(ctx, hipGetLastError());
       transformed_bounds(clouds[f], pz.T, tf[f]);
-      if (tf[f]->tile4) {  // tile spheres of the old coordinates
-        (void)hipFree(tf[f]->tile4);
-        tf[f]->tile4 = nullptr;
-      }
+      tf[f]->tiles.release();  // tile spheres of the old coordinates
+      tf[f]->tile4 = nullptr;
     }
     // BinaryStateGPU::update_inner_product on every edge (IRLS_State_GPU.cu:43-79): neighbour budget, evaluation,
     // the matrix gathered into the edge's entry list on the device, its nonzero counts to the host
@@ -490,15 +481,17 @@ int cvo_debug_irls_normal(cvo_ctx* ctx, const cvo_cloud* frame1, const cvo_cloud
     return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_normal: the clouds are not those of the last evaluation");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int K = ctx->last_params.K_max;
-  DevAlloc d_ent, d_edges, d_poses, d_part, d_out;
+  DeviceRegion d_ent, d_edges, d_poses, d_part, d_out;
   const size_t slots = (size_t)D.N * K;
   const int nb = irls_blocks((int)slots);
-  if (hipMalloc(&d_ent.p, sizeof(IrlsEntry) * slots) != hipSuccess || hipMalloc(&d_edges.p, sizeof(IrlsEdge)) != hipSuccess ||
-      hipMalloc(&d_poses.p, sizeof(double) * 24) != hipSuccess ||
-      hipMalloc(&d_part.p, sizeof(double) * IRLS_W * (size_t)std::max(nb, 1)) != hipSuccess ||
-      hipMalloc(&d_out.p, sizeof(double) * IRLS_W) != hipSuccess)
-    return fail(ctx, CVO_E_NOMEM, "cvo_debug_irls_normal: device allocation failed");
-  int rc = irls_gather(ctx, D.N, K, (IrlsEntry*)d_ent.p);
+  auto dmalloc = [&](DeviceRegion& a, size_t bytes) { return a.reserve(ctx, bytes, "cvo_debug_irls_normal", nullptr); };
+  int rc;
+  if ((rc = dmalloc(d_ent, sizeof(IrlsEntry) * slots)) != CVO_OK || (rc = dmalloc(d_edges, sizeof(IrlsEdge))) != CVO_OK ||
+      (rc = dmalloc(d_poses, sizeof(double) * 24)) != CVO_OK ||
+      (rc = dmalloc(d_part, sizeof(double) * IRLS_W * (size_t)std::max(nb, 1))) != CVO_OK ||
+      (rc = dmalloc(d_out, sizeof(double) * IRLS_W)) != CVO_OK)
+    return rc;
+  rc = irls_gather(ctx, D.N, K, (IrlsEntry*)d_ent.p);
   if (rc != CVO_OK) return rc;
   std::vector<IrlsEdge> tab;
   (void)irls_table_add(tab, 0, frame1, frame2, 0, 1, (const IrlsEntry*)d_ent.p, (int)slots);
@@ -552,9 +545,10 @@ int cvo_debug_irls_eval(cvo_ctx* ctx, int n_frames, const cvo_cloud* const* clou
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   // ---- the launch table, by the driver's builder ----
-  DevAlloc d_ent, d_edges, d_poses, d_part, d_out;
-  if (hipMalloc(&d_ent.p, std::max<size_t>(sizeof(IrlsEntry) * h_ent.size(), 256)) != hipSuccess)
-    return fail(ctx, CVO_E_NOMEM, "cvo_debug_irls_eval: device allocation failed");
+  DeviceRegion d_ent, d_edges, d_poses, d_part, d_out;
+  auto dmalloc = [&](DeviceRegion& a, size_t bytes) { return a.reserve(ctx, bytes, "cvo_debug_irls_eval", nullptr); };
+  int rc;
+  if ((rc = dmalloc(d_ent, std::max<size_t>(sizeof(IrlsEntry) * h_ent.size(), 256))) != CVO_OK) return rc;
   std::vector<IrlsEdge> tab;
   int nb = 0;
   for (int k = 0; k < n_edges; k++) {
@@ -562,11 +556,11 @@ int cvo_debug_irls_eval(cvo_ctx* ctx, int n_frames, const cvo_cloud* const* clou
     nb = irls_table_add(tab, nb, clouds[a], clouds[b], a, b, (const IrlsEntry*)d_ent.p + ((size_t)slot_off[k] - first),
                         slot_off[k + 1] - slot_off[k]);
   }
-  if (hipMalloc(&d_edges.p, sizeof(IrlsEdge) * tab.size()) != hipSuccess ||
-      hipMalloc(&d_poses.p, sizeof(double) * 12 * (size_t)n_frames) != hipSuccess ||
-      hipMalloc(&d_part.p, sizeof(double) * IRLS_W * (size_t)std::max(nb, 1)) != hipSuccess ||
-      hipMalloc(&d_out.p, sizeof(double) * IRLS_W * tab.size()) != hipSuccess)
-    return fail(ctx, CVO_E_NOMEM, "cvo_debug_irls_eval: device allocation failed");
+  if ((rc = dmalloc(d_edges, sizeof(IrlsEdge) * tab.size())) != CVO_OK ||
+      (rc = dmalloc(d_poses, sizeof(double) * 12 * (size_t)n_frames)) != CVO_OK ||
+      (rc = dmalloc(d_part, sizeof(double) * IRLS_W * (size_t)std::max(nb, 1))) != CVO_OK ||
+      (rc = dmalloc(d_out, sizeof(double) * IRLS_W * tab.size())) != CVO_OK)
+    return rc;
   if (!h_ent.empty())
     HIP_TRY(ctx, hipMemcpyAsync(d_ent.p, h_ent.data(), sizeof(IrlsEntry) * h_ent.size(), hipMemcpyHostToDevice, ctx->stream));
   HIP_TRY(ctx, hipMemcpyAsync(d_edges.p, tab.data(), sizeof(IrlsEdge) * tab.size(), hipMemcpyHostToDevice, ctx->stream));
@@ -578,7 +572,7 @@ int cvo_debug_irls_eval(cvo_ctx* ctx, int n_frames, const cvo_cloud* const* clou
   dv.n_edges = n_edges;
   dv.n_blocks = nb;
   std::vector<double> X(poses, poses + 12 * (size_t)n_frames), o;
-  const int rc = irls_eval(ctx, dv, X, normal != 0, o);
+  rc = irls_eval(ctx, dv, X, normal != 0, o);
   if (rc != CVO_OK) return rc;
   std::memcpy(out, o.data(), sizeof(double) * o.size());
   return CVO_OK;
@@ -594,10 +588,10 @@ int cvo_debug_irls_gather(cvo_ctx* ctx, int K, int* r, int* c, float* w) {
   if (N <= 0 || K <= 0 || (size_t)N * K > (size_t)INT32_MAX) return fail(ctx, CVO_E_INVALID, "cvo_debug_irls_gather: bad size");
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t slots = (size_t)N * K;
-  DevAlloc d_ent;
-  if (hipMalloc(&d_ent.p, sizeof(IrlsEntry) * slots) != hipSuccess)
-    return fail(ctx, CVO_E_NOMEM, "cvo_debug_irls_gather: device allocation failed");
-  const int rc = irls_gather(ctx, N, K, (IrlsEntry*)d_ent.p);
+  DeviceRegion d_ent;
+  int rc = d_ent.reserve(ctx, sizeof(IrlsEntry) * slots, "cvo_debug_irls_gather", nullptr);
+  if (rc != CVO_OK) return rc;
+  rc = irls_gather(ctx, N, K, (IrlsEntry*)d_ent.p);
   if (rc != CVO_OK) return rc;
   std::vector<IrlsEntry> h(slots);
   HIP_TRY(ctx, hipMemcpyAsync(h.data(), d_ent.p, sizeof(IrlsEntry) * slots, hipMemcpyDeviceToHost, ctx->stream));

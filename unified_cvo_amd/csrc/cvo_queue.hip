@@ -45,7 +45,7 @@ struct cvo_batch_queue {
   int launched[cvo_ctx::MAX_GROUPS] = {}, inspected[cvo_ctx::MAX_GROUPS] = {};
   ChunkPlan next[cvo_ctx::MAX_GROUPS];  // (kind and dense flag; queue_step gives it its length)
   int running[cvo_ctx::MAX_GROUPS] = {};  // occupied slots per group
-  char* pinned = nullptr;                 // [slots] x (PairState out | PairDesc stage | PairState stage)
+  PinnedRegion pinned;                    // [PairState out[slots] | PairState stage[slots] | PairDesc stage[slots]]
   PairState* h_out = nullptr;
   PairDesc* h_desc_stage = nullptr;
   PairState* h_state_stage = nullptr;
@@ -118,7 +118,7 @@ int queue_step(cvo_batch_queue* q, int g, bool block, bool* progressed) {
       }
     }
     // finished pairs: their state is read out behind everything enqueued so far; the slot goes to the next waiting pair
-    const volatile int* hs = ctx->h_status[0] + 2 * p0;  // [status[ng] | want[ng]]
+    const volatile int* hs = ctx->h_status[0].as<int>() + 2 * p0;  // [status[ng] | want[ng]]
     GroupWant want;
     for (int k = 0; k < ng; k++) {
       cvo_batch_queue::Slot& sl = q->slot[p0 + k];
@@ -204,20 +204,19 @@ int cvo_batch_open(cvo_ctx* ctx, const cvo_params_t* params, int slots, int max_
   // twice that for the lean ones, as cvo_align_batch.
   q->cfg = loop_cfg(ctx, q->S, q->dp, 16, 32);
   q->slot.assign((size_t)slots, cvo_batch_queue::Slot());
-  const size_t per = align_up(sizeof(PairState), 256) * 2 + align_up(sizeof(PairDesc), 256);
-  hipError_t e = hipHostMalloc(&q->pinned, per * (size_t)slots, hipHostMallocDefault);
-  if (e != hipSuccess) {
+  rc = q->pinned.lay_out(ctx, "cvo_batch_open", [q, slots](ScratchLayout& l) {
+    l.take(q->h_out, (size_t)slots);
+    l.take(q->h_state_stage, (size_t)slots);
+    l.take(q->h_desc_stage, (size_t)slots);
+  }, nullptr);
+  if (rc != CVO_OK) {
     delete q;
-    return fail(ctx, CVO_E_NOMEM, std::string("cvo_batch_open: hipHostMalloc: ") + hipGetErrorString(e));
+    return rc;
   }
-  q->h_out = (PairState*)q->pinned;
-  q->h_state_stage = (PairState*)(q->pinned + align_up(sizeof(PairState), 256) * (size_t)slots);
-  q->h_desc_stage = (PairDesc*)(q->pinned + align_up(sizeof(PairState), 256) * 2 * (size_t)slots);
   // the set-up copies went to group 0's stream: the other sub-batch streams start behind them
-  e = hipEventRecord(ctx->ev_fork, ctx->stream);
+  hipError_t e = hipEventRecord(ctx->ev_fork, ctx->stream);
   for (int g = 1; g < q->G && e == hipSuccess; g++) e = hipStreamWaitEvent(q->geom[g].stream, ctx->ev_fork, 0);
   if (e != hipSuccess) {
-    (void)hipHostFree(q->pinned);
     delete q;
     return fail(ctx, CVO_E_HIP, std::string("cvo_batch_open: ") + hipGetErrorString(e));
   }
@@ -328,8 +327,7 @@ static void queue_release(cvo_batch_queue* q) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   for (int g = 0; g < q->G; g++) (void)hipStreamSynchronize(q->geom[g].stream);
-  if (q->pinned) (void)hipHostFree(q->pinned);
-  q->pinned = nullptr;
+  q->pinned.release();
   q->h_out = nullptr;
   q->h_desc_stage = nullptr;
   q->h_state_stage = nullptr;

@@ -139,7 +139,7 @@ void fill_pair(cvo_ctx* ctx, const BatchSetup* S, const cvo_params_t* params, co
   const int Kmax = params->nearest_neighbors_max;
   PairDesc& D = ctx->h_descs[p];
   std::memset(&D, 0, sizeof(D));
-  place_regions(D, (uintptr_t)ctx->arena + S->slot_bytes * (size_t)p, S->N, S->d, Kmax, trace_cap, S->long_lists);
+  place_regions(D, (uintptr_t)ctx->arena.p + S->slot_bytes * (size_t)p, S->N, S->d, Kmax, trace_cap, S->long_lists);
   D.N = X->n;
   D.M = Y->n;
   D.call_serial = serial;
@@ -183,10 +183,10 @@ void fill_pair(cvo_ctx* ctx, const BatchSetup* S, const cvo_params_t* params, co
     const auto [p0, p1] = group_bounds(n_slots, S->G, group_of(n_slots, S->G, p));
     D.status_out = ctx->d_status + 2 * p0 + (p - p0);
     D.want_out = ctx->d_status + 2 * p0 + (p1 - p0) + (p - p0);
-    D.status_host = ctx->h_status[0] + 2 * p0 + (p - p0);
-    D.want_host = ctx->h_status[0] + 2 * p0 + (p1 - p0) + (p - p0);
+    D.status_host = ctx->h_status[0].as<int>() + 2 * p0 + (p - p0);
+    D.want_host = ctx->h_status[0].as<int>() + 2 * p0 + (p1 - p0) + (p - p0);
   }
-  D.asum_host = reinterpret_cast<double*>(ctx->h_status[1]) + p;  // (2 ints per pair = one double)
+  D.asum_host = ctx->h_status[1].as<double>() + p;  // (2 ints per pair = one double)
 
   PairState& st = ctx->h_states[p];
   std::memset(&st, 0, sizeof(st));
@@ -296,7 +296,7 @@ int plan_batch(cvo_ctx* ctx, const BatchCall& c, int N, int M, BatchSetup* S, De
   {
     size_t free_b = 0, total_b = 0;
     size_t need = S->slot_bytes * (size_t)n_pairs;
-    const bool tight = need > ctx->arena_bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + ctx->arena_bytes;
+    const bool tight = need > ctx->arena.bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + ctx->arena.bytes;
     if (tight && S->long_lists) {
       // the long lists of overflow rows (N x 2 KB per pair) are a speed feature: without them such rows are scanned
       // literally.  Give them up before giving up the call.
@@ -305,14 +305,14 @@ int plan_batch(cvo_ctx* ctx, const BatchCall& c, int N, int M, BatchSetup* S, De
       need = S->slot_bytes * (size_t)n_pairs;
       if (o.verbose) fprintf(stderr, "[cvo] workspace: long lists dropped to fit device memory\n");
     }
-    if (need > ctx->arena_bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + ctx->arena_bytes) {
+    if (need > ctx->arena.bytes && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need > free_b + ctx->arena.bytes) {
       char msg[320];
       snprintf(msg, sizeof msg,
                "workspace of %d pair(s) of %d x %d points needs %.1f GiB (candidate bitmap N*M/8 = %.1f GiB per pair, ELL "
                "%.1f GiB per pair; the long lists of overflow rows have already been dropped) but %.1f GiB of device memory are "
                "free: split the batch or the clouds",
                n_pairs, N, M, need / 1073741824.0, (double)N * S->d.Mpad / 8.0 / 1073741824.0,
-               (double)S->d.Npad * Kmax * 20.0 / 1073741824.0, (free_b + ctx->arena_bytes) / 1073741824.0);
+               (double)S->d.Npad * Kmax * 20.0 / 1073741824.0, (free_b + ctx->arena.bytes) / 1073741824.0);
       return fail(ctx, CVO_E_NOMEM, msg);
     }
   }
@@ -365,7 +365,7 @@ int plan_batch(cvo_ctx* ctx, const BatchCall& c, int N, int M, BatchSetup* S, De
 int commit_batch(cvo_ctx* ctx, const BatchCall& c, BatchSetup* S, const DevParams& dp) {
   const int n_pairs = c.n_pairs;
   if (const int rc = ensure_workspace(ctx, n_pairs, S->slot_bytes); rc != CVO_OK) return rc;
-  S->geom.arena.base = ctx->arena;
+  S->geom.arena.base = ctx->arena.p;
   ctx->h_descs.resize(n_pairs);
   ctx->h_states.resize(n_pairs);
   if (!c.qd) {
@@ -382,20 +382,19 @@ int commit_batch(cvo_ctx* ctx, const BatchCall& c, BatchSetup* S, const DevParam
   // the blocks of k_assoc beyond a smaller pair's N still write their (zero) partials, but the
   // partial arrays of pairs whose N is smaller than the batch maximum are fully covered by nblk.
   // one copy from the pinned staging block (no call is in flight on this context: every call ends synchronised)
-  std::memcpy(ctx->h_ctl, &dp, sizeof(DevParams));
-  std::memset(ctx->h_ctl + ctx->ctl_off_status, c.qd ? 1 : 0, sizeof(int) * 2 * (size_t)ctx->cap_pairs);  // (queue: any non-zero word = finished)
-  std::memcpy(ctx->h_ctl + ctx->ctl_off_descs, ctx->h_descs.data(), sizeof(PairDesc) * (size_t)n_pairs);
-  std::memcpy(ctx->h_ctl + ctx->ctl_off_states, ctx->h_states.data(), sizeof(PairState) * (size_t)n_pairs);
-  std::memset(ctx->h_status[0], c.qd ? 1 : 0, sizeof(int) * 2 * (size_t)ctx->cap_pairs);
+  *ctx->s_params = dp;
+  std::memset(ctx->s_status, c.qd ? 1 : 0, sizeof(int) * 2 * (size_t)ctx->cap_pairs);  // (queue: any non-zero word = finished)
+  std::copy_n(ctx->h_descs.data(), n_pairs, ctx->s_descs);
+  std::copy_n(ctx->h_states.data(), n_pairs, ctx->s_states);
+  std::memset(ctx->h_status[0].p, c.qd ? 1 : 0, sizeof(int) * 2 * (size_t)ctx->cap_pairs);
   {
     // (descriptors and states of at most n_pairs <= cap_pairs slots are used; the block is laid out for cap_pairs)
-    const size_t upto = ctx->ctl_off_states + sizeof(PairState) * (size_t)n_pairs;
+    const char *base = ctx->h_ctl.p, *descs_end = (const char*)(ctx->s_descs + n_pairs), *states_end = (const char*)(ctx->s_states + n_pairs);
     if ((size_t)n_pairs * 2 >= (size_t)ctx->cap_pairs) {
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ctl, ctx->h_ctl, upto, hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ctl.p, base, (size_t)(states_end - base), hipMemcpyHostToDevice, ctx->stream));
     } else {  // a small call on a context sized for a large batch: skip the unused descriptors in between
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ctl, ctx->h_ctl, ctx->ctl_off_descs + sizeof(PairDesc) * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
-      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ctl + ctx->ctl_off_states, ctx->h_ctl + ctx->ctl_off_states, sizeof(PairState) * (size_t)n_pairs,
-                                  hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_ctl.p, base, (size_t)(descs_end - base), hipMemcpyHostToDevice, ctx->stream));
+      HIP_TRY(ctx, hipMemcpyAsync(ctx->d_states, ctx->s_states, sizeof(PairState) * (size_t)n_pairs, hipMemcpyHostToDevice, ctx->stream));
     }
   }
   if (!c.qd) ctx->last_xorder = c.sources[0]->h_order;
@@ -586,7 +585,7 @@ int cvo_align_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const
         t_wait += ms_since(tw);
         all_done = true;
         for (int g = 0; g < G; g++) {
-          const volatile int* hs = ctx->h_status[0] + 2 * geom[g].p0;  // [status[n_g] | want[n_g]], live (may be newer than chunk ch - 1)
+          const volatile int* hs = ctx->h_status[0].as<int>() + 2 * geom[g].p0;  // [status[n_g] | want[n_g]], live (may be newer than chunk ch - 1)
           const int ng = geom[g].n_pairs;
           for (int q = 0; q < ng; q++) all_done = all_done && hs[q] != 0;
           GroupWant want;
@@ -609,7 +608,7 @@ int cvo_align_batch(cvo_ctx* ctx, const cvo_params_t* params, int n_pairs, const
       for (int g = 0; g < G; g++) HIP_TRY(ctx, hipStreamSynchronize(geom[g].stream));
       bool fin = true;
       for (int g = 0; g < G; g++)
-        for (int q = 0; q < geom[g].n_pairs; q++) fin = fin && ((volatile int*)ctx->h_status[0])[2 * geom[g].p0 + q] != 0;
+        for (int q = 0; q < geom[g].n_pairs; q++) fin = fin && ctx->h_status[0].as<volatile int>()[2 * geom[g].p0 + q] != 0;
       if (!fin && ch >= chunk_cap) return fail(ctx, CVO_E_HIP, "cvo_align_batch: optimiser loop did not terminate");
     }
   }

@@ -14,20 +14,17 @@ int ensure_attributes(cvo_ctx* ctx, const cvo_cloud* c, bool need_feat, bool nee
     l.take(z.label, 5 * nn);
     l.take(z.geo, nn);
   };
-  if (!m->zero_slab) {
-    const size_t bytes = ScratchLayout().walk(list);
+  if (!m->zero_slab.p) {
     HIP_TRY(ctx, hipSetDevice(c->device));
-    hipError_t e = hipMalloc(&m->zero_slab, bytes);
-    if (e != hipSuccess) return fail(ctx, CVO_E_NOMEM, std::string("cloud hipMalloc: ") + hipGetErrorString(e));
-    e = hipMemsetAsync(m->zero_slab, 0, bytes, ctx->stream);
-    if (e != hipSuccess) {  // never hand the kernels an allocated-but-not-zeroed "zero" slab on a later call
-      (void)hipFree(m->zero_slab);
-      m->zero_slab = nullptr;
+    if (const int rc = m->zero_slab.lay_out(ctx, "cloud", list, nullptr); rc != CVO_OK) return rc;
+    const hipError_t e = hipMemsetAsync(m->zero_slab.p, 0, m->zero_slab.bytes, ctx->stream);
+    if (e != hipSuccess) {
+      m->zero_slab.release();  // never hand the kernels an allocated-but-not-zeroed "zero" slab on a later call
       return fail(ctx, CVO_E_HIP, std::string("cloud hipMemsetAsync: ") + hipGetErrorString(e));
     }
     if (created) *created = true;
   }
-  ScratchLayout(m->zero_slab).walk(list);
+  ScratchLayout(m->zero_slab.p).walk(list);
   if (!m->feat) m->feat = z.feat;
   if (!m->label) m->label = z.label;
   if (!m->geo) m->geo = z.geo;
@@ -168,7 +165,7 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
   const SlabShape shape{nn, NP, h.feat != nullptr, h.label != nullptr, h.geo != nullptr, has_lid, device_order, device_order};
   auto list = [&](auto& a) { return cloud_slab_list(a, shape, &up_bytes); };
   CloudArrays s;
-  const size_t slab_bytes = ScratchLayout().walk(list(s));
+  ScratchLayout().walk(list(s));
   std::vector<char>& stage = sc->stage;
   stage.assign(up_bytes, 0);  // (pageable: kept alive by the caller until the stream has been synchronised)
   ScratchLayout(stage.data()).walk(list(s));
@@ -219,15 +216,12 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
     for (int r = 0; r < n; r++) s.inv[order[r]] = r;
     c->h_order = std::move(order);
   }
-  hipError_t e = hipMalloc(&c->slab, slab_bytes);
-  c->slab_bytes = slab_bytes;
-  if (e != hipSuccess) {
+  if (const int rc = c->slab.lay_out(ctx, "cloud", list(*c), nullptr); rc != CVO_OK) {
     cvo_cloud_free(c);
-    return fail(ctx, CVO_E_NOMEM, std::string("cloud hipMalloc: ") + hipGetErrorString(e));
+    return rc;
   }
-  ScratchLayout(c->slab).walk(list(*c));
   if (n > 0) {
-    e = hipMemcpyAsync(c->slab, stage.data(), up_bytes, hipMemcpyHostToDevice, stream);
+    const hipError_t e = hipMemcpyAsync(c->slab.p, stage.data(), up_bytes, hipMemcpyHostToDevice, stream);
     if (e != hipSuccess) {
       cvo_cloud_free(c);
       return fail(ctx, CVO_E_HIP, std::string("cloud upload: ") + hipGetErrorString(e));
@@ -236,7 +230,7 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
   sc->c = c;
   sc->job = KdJob{};
   if (device_order) {
-    ScratchLayout(c->slab).walk(list(sc->job));
+    ScratchLayout(c->slab.p).walk(list(sc->job));
     sc->job.n = n;
     sc->job.NP = NP;
     c->h_order.assign((size_t)n, 0);
@@ -256,33 +250,29 @@ static int finish_uploads(cvo_ctx* ctx, std::vector<StagedCloud>& clouds) {
       np_max = std::max(np_max, sc.job.NP);
     }
   hipError_t e = hipSuccess;
+  int rc = CVO_OK;
   std::lock_guard<std::mutex> lk(ctx->kd_mutex);
   if (!jobs.empty()) {
-    if ((int)jobs.size() > ctx->kd_jobs_cap) {
-      if (ctx->d_kd_jobs) (void)hipFree(ctx->d_kd_jobs);
-      ctx->d_kd_jobs = nullptr;
-      ctx->kd_jobs_cap = 0;
-      e = hipMalloc(&ctx->d_kd_jobs, sizeof(KdJob) * jobs.size());
-      if (e == hipSuccess) ctx->kd_jobs_cap = (int)jobs.size();
-    }
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(ctx->d_kd_jobs, jobs.data(), sizeof(KdJob) * jobs.size(), hipMemcpyHostToDevice, ctx->upload_stream);
-    if (e == hipSuccess) {
+    // (nothing to drain: the launch that read the table last was synchronised below, under this mutex)
+    rc = ctx->d_kd_jobs.reserve(ctx, sizeof(KdJob) * jobs.size(), "ordering job table", nullptr);
+    if (rc == CVO_OK)
+      e = hipMemcpyAsync(ctx->d_kd_jobs.p, jobs.data(), sizeof(KdJob) * jobs.size(), hipMemcpyHostToDevice, ctx->upload_stream);
+    if (rc == CVO_OK && e == hipSuccess) {
       hipLaunchKernelGGL(k_kd_order, dim3((unsigned)jobs.size()), dim3(KD_THREADS), sizeof(unsigned long long) * (size_t)np_max,
-                         ctx->upload_stream, (const KdJob*)ctx->d_kd_jobs);
+                         ctx->upload_stream, ctx->d_kd_jobs.as<const KdJob>());
       e = hipGetLastError();
     }
     for (auto& sc : clouds)
-      if (e == hipSuccess && sc.c && sc.job.n > 0)
+      if (rc == CVO_OK && e == hipSuccess && sc.c && sc.job.n > 0)
         e = hipMemcpyAsync(sc.c->h_order.data(), sc.c->order, sizeof(int) * (size_t)sc.job.n, hipMemcpyDeviceToHost, ctx->upload_stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->upload_stream);
-  if (e != hipSuccess) {
+  if (rc != CVO_OK || e != hipSuccess) {
     for (auto& sc : clouds) {
       if (sc.c) cvo_cloud_free(sc.c);
       sc.c = nullptr;
     }
-    return fail(ctx, CVO_E_HIP, std::string("cloud upload (ordering): ") + hipGetErrorString(e));
+    return rc != CVO_OK ? rc : fail(ctx, CVO_E_HIP, std::string("cloud upload (ordering): ") + hipGetErrorString(e));
   }
   return CVO_OK;
 }
@@ -439,18 +429,16 @@ int cvo_cloud_transformed(cvo_ctx* ctx, const cvo_cloud* in, const float pose12[
   c->device = ctx->device;
   c->n = in->n;
   c->h_order = in->h_order;
-  c->slab_bytes = in->slab_bytes;
-  hipError_t e = hipMalloc(&c->slab, std::max<size_t>(in->slab_bytes, 256));
-  if (e != hipSuccess) {
+  if (const int rc = c->slab.reserve(ctx, in->slab.bytes, "cloud", nullptr); rc != CVO_OK) {
     delete c;
-    return fail(ctx, CVO_E_NOMEM, std::string("cloud hipMalloc: ") + hipGetErrorString(e));
+    return rc;
   }
   // same slab layout: features, labels, geometric types and the spatial order are copied, coordinates rewritten
   // (attributes the input was uploaded without - NULL or pointing into its zero slab - stay absent in the copy)
-  const ScratchLayout l(c->slab);
+  const ScratchLayout l(c->slab.p);
   auto rebase = [&](auto*& to, const auto* from) {
     const char* q = (const char*)from;
-    if (q && q >= in->slab && q < in->slab + in->slab_bytes) l.at(to, (size_t)(q - in->slab));
+    if (q && q >= in->slab.p && q < in->slab.p + in->slab.bytes) l.at(to, (size_t)(q - in->slab.p));
   };
   rebase(c->x4, in->x4);
   rebase(c->xs4, in->xs4);
@@ -463,7 +451,7 @@ int cvo_cloud_transformed(cvo_ctx* ctx, const cvo_cloud* in, const float pose12[
   Pose12 P;
   for (int q = 0; q < 12; q++) P.T[q] = pose12[q];
   if (in->n > 0) {
-    e = hipMemcpyAsync(c->slab, in->slab, in->slab_bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    hipError_t e = hipMemcpyAsync(c->slab.p, in->slab.p, in->slab.bytes, hipMemcpyDeviceToDevice, ctx->stream);
     if (e == hipSuccess) {
       hipLaunchKernelGGL(k_transform_pose, dim3((in->n + 255) / 256), dim3(256), 0, ctx->stream, in->n, P, in->x4, in->xs4,
                          c->x4, c->xs4);
@@ -485,9 +473,6 @@ int cvo_cloud_size(const cvo_cloud* c) { return c ? c->n : 0; }
 void cvo_cloud_free(cvo_cloud* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  if (c->slab) (void)hipFree(c->slab);
-  if (c->zero_slab) (void)hipFree(c->zero_slab);
-  if (c->tile4) (void)hipFree(c->tile4);
   delete c;
 }
 
