@@ -21,7 +21,11 @@ Departures:
     the cloud.
 Extension: num_classes = 0 (upstream's driver is broken for clouds without labels): every hit is class 1 of a two-class map
 and the cloud read out has no labels.
-Unpinned: parity with upstream's binary, as everywhere here - the library needs PCL and Eigen.
+Pinned against upstream's own compiled bkiblock.cpp, bkioctree.cpp, bkioctree_node.cpp, point3f.cpp and rtree.h
+(oracle/bki_upstream_driver.cpp, tests/golden/bki_upstream.npz, test_bki_upstream.py): k0_of, the centre expression, holds /
+blocks_of, state_of, read_out and Map on frames without beam samples - bit for bit, no difference found.  Unpinned, because
+their translation unit needs PCL and Eigen: training_data's order and max_range comparison, beam, upstream's enumeration of
+blocks (get_blocks_in_bbox), the Eigen products of predict_csm and maxCoeff's choice among equal label maxima.
 
 Every operation below is a single float32 (or, where said, float64) numpy operation: no fused multiply-add.
 """
@@ -155,6 +159,17 @@ def state_of(cfg, ms):
     return OCCUPIED if p > cfg.occupied_thresh else (FREE if p < cfg.free_thresh else UNKNOWN)
 
 
+def read_out(ms, fs):
+    """(get_features, get_occupied_probs) of a voxel: fs over the float sum of ms[1:], ms[1:] over the float sum of ms"""
+    occ, tot = F32(0), F32(0)
+    for m in ms[1:]:
+        occ = F32(occ + m)
+    for m in ms:
+        tot = F32(tot + m)
+    with np.errstate(all="ignore"):
+        return fs / occ, ms[1:] / tot
+
+
 class Map:
     """voxels: key -> [ms (nclass,) float32, fs (5,) float32]."""
 
@@ -207,12 +222,8 @@ class Map:
                 continue
             xyz.append([F32((key >> 40) - KOFF) * cfg.resolution, F32(((key >> 20) & 0xFFFFF) - KOFF) * cfg.resolution,
                         F32((key & 0xFFFFF) - KOFF) * cfg.resolution])
-            occ, tot = F32(0), F32(0)
-            for m in ms[1:]:
-                occ = F32(occ + m)
-            for m in ms:
-                tot = F32(tot + m)
-            feat.append(fs / occ)
-            lab.append(ms[1:C + 1] / tot)
+            f, l = read_out(ms, fs)
+            feat.append(f)
+            lab.append(l[:C])
         n = len(xyz)
         return (np.array(xyz, F32).reshape(n, 3), np.array(feat, F32).reshape(n, 5), np.array(lab, F32).reshape(n, C))
