@@ -88,19 +88,23 @@ def edge_entries(mat, ind, x1, x2):
     return x1[r].astype(np.float64), x2[c].astype(np.float64), mat[r, s].astype(np.float64)
 
 
-def solve(X, free, edges_terms, max_iterations, eval_cost):
+def solve(X, free, edges_terms, max_iterations, eval_cost, normal=None):
     """One trust-region solve.  X: F x 12 poses (modified copy returned); free: F bools; edges_terms: list of
-    (f1, f2, P1, P2, w).  Returns (X, dict(steps, accepted, termination, cost_initial, cost_final, events))."""
+    (f1, f2, P1, P2, w).  Returns (X, dict(steps, accepted, termination, cost_initial, cost_final, events)).
+    normal (optional): stands in for edge_normal, (P1, P2, w, T1, T2) -> (cost, g[12], H 12x12) of one edge - the
+    synthetic records of tests/test_irls_solve_cpu.py."""
     X = X.copy()
     F = X.shape[0]
     fi = -np.ones(F, int)
     fi[free] = np.arange(int(np.sum(free)))
     m = 6 * int(np.sum(free))
 
+    one_edge = normal or edge_normal
+
     def normal(Y):
         H, g, cost = np.zeros((m, m)), np.zeros(m), 0.0
         for f1, f2, P1, P2, w in edges_terms:
-            c, ge, He = edge_normal(P1, P2, w, Y[f1], Y[f2])
+            c, ge, He = one_edge(P1, P2, w, Y[f1], Y[f2])
             cost += c
             idx = [6 * fi[f1] + q if fi[f1] >= 0 else -1 for q in range(6)] + \
                   [6 * fi[f2] + q if fi[f2] >= 0 else -1 for q in range(6)]

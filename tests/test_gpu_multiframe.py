@@ -243,8 +243,8 @@ def test_multiframe_driver_matches_python(tmp_path):
 # With the suite's usual parameters (sigma 0.1, 8 steps per solve) every step is accepted, every solve ends on the
 # iteration cap (termination 5) and ell never decays.  The draws below reach the other branches; each test asserts that
 # the RESTATEMENT's rows contain the branch it is there for, so a test that stops reaching its branch fails.
-# Terminations 4 (trust-region radius below its minimum) and 6 (five invalid steps in a row) are not asserted anywhere:
-# no finite input tried reached them.
+# Terminations 4 (trust-region radius below its minimum) and 6 (five invalid steps in a row), which no finite input tried
+# reached, are asserted on the solver itself with injected evaluations: tests/test_irls_solve_cpu.py.
 
 def _branch_params(sigma=0.1, steps=8, per_ell=3, max_iters=6, ell=(0.3, 0.1, 0.7), K0=96):
     P = cases.load_params("geometric_gpu")

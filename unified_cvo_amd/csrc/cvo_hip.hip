@@ -11,7 +11,8 @@
 //   cvo_launch.hip  every kernel launch of the solver                  cvo_sched.hip   setup, chunk graphs, cvo_align_batch
 //   cvo_queue.hip   the batch queue                                    cvo_eval.hip    inner products, single evaluations
 //   cvo_export.hip  association / ELL exports                          cvo_debug.hip   test and profiling hooks
-//   cvo_irls.hip    multi-frame align (the least-squares solve of CvoBatchIRLS)
+//   cvo_irls.hip    multi-frame align (the outer loop of CvoBatchIRLS and its device workspace; the trust-region solve itself is
+//                   cvo_irls_solve.h, plain C++ that host/cvo_irls_solve_check runs without a device)
 //   cvo_frontend.hip  what the front ends below share: scratch regions, the ordered-compaction launcher, the route rule, the entry frame
 //   cvo_ingest.hip  resident clouds from rows that are already in device memory: checks, k_cloud_ingest, the route rule, k_cloud_gather
 //   cvo_voxel.hip   voxel-grid downsampling: selection on the device or the host, upload of the survivors

@@ -4,6 +4,7 @@
 // (cost only, at a candidate pose), k_irls_finish (the ordered per-edge pass over the block partials).
 // Part of the kernel set of cvo_kernels.h; compiled only as part of cvo_hip.hip.
 #pragma once
+#include "cvo_irls_solve.h"
 #include "cvo_wave.h"
 
 namespace cvo_dev {
@@ -11,7 +12,7 @@ namespace cvo_dev {
 constexpr int IRLS_THREADS = 256;
 constexpr int IRLS_PER_THREAD = 16;
 constexpr int IRLS_BLOCK_ENTRIES = IRLS_THREADS * IRLS_PER_THREAD;  // entry slots one block walks
-constexpr int IRLS_W = 91;  // per edge: cost, g[12], the upper triangle of the 12 x 12 H row by row [78]
+using cvo_irls::IRLS_W;  // per edge: cost, g[12], the upper triangle of the 12 x 12 H row by row [78]: the host solver's record
 
 // One stored entry (r, c, w = A.mat) of an edge's kernel matrix: row r of frame 1, column c of frame 2 (ORIGINAL
 // indices).  c < 0: an empty slot (the row had fewer than K entries).
