@@ -75,9 +75,20 @@ int cvo_debug_prim(cvo_ctx* ctx, int op, int n, int m, unsigned long long* k64, 
  * last align call, summed over pairs and iterations (0 when the check was off). */
 int cvo_debug_verified_rows(cvo_ctx* ctx, unsigned long long* rows);
 /* The spatial (k-d) ordering of a resident cloud: out[r] = original index of the point at sorted position r (n entries).
- * Computed on the device at upload (k_kd_order) for clouds of 8 .. 16384 finite points, on the host otherwise and under
- * CVO_ORDER=host / virtual / CVO_NO_SORT; no result depends on it. */
+ * Computed on the device at upload for clouds of 8 .. 16384 finite points (k_kd_order) and, under CVO_ORDER=wide, of up to
+ * 2^24 (the multi-block ordering, cvo_k_kd_wide.h); on the host otherwise and under CVO_ORDER=host / virtual / CVO_NO_SORT.
+ * No result depends on it. */
 int cvo_debug_cloud_order(const cvo_cloud* cloud, int* out);
+/* What ordered this cloud: 0 = the host, 1 = k_kd_order, 2 = the multi-block ordering of CVO_ORDER=wide (a cloud made by
+ * cvo_cloud_transformed: what ordered its input). */
+int cvo_debug_cloud_order_route(const cvo_cloud* cloud);
+/* The route rule itself, which every upload path calls: the value above for a cloud of n points, all finite or not, under
+ * the text order_value of the ORDER switch (NULL: unset) and NO_SORT set or not.  No context, no device. */
+int cvo_debug_order_route_rule(int n, int finite, const char* order_value, int no_sort);
+/* The host's plan of the multi-block ordering of n points (0 .. 2^24): *W = the leaf capacity of a default context, *n_rows
+ * = the cuts of segments of more than W points, rows = (level, lo, hi, left) of the first `capacity` of them, level by
+ * level and by position inside a level.  No context, no device.  W may be NULL. */
+int cvo_debug_wide_plan(int n, int* W, int* rows /* level, lo, hi, left */, int capacity, int* n_rows);
 /* What the last score call did - cvo_inner_product / cvo_function_angle (one job) or their _batch forms: evaluations summed
  * by k_overlap (the exact function_angle's <X, X> / <Y, Y> once per distinct cloud and lengthscale), evaluations repeated
  * or run by the list chain (void jobs, chain-only calls), and launches (k_overlap chunks + chain sub-batches).  E.g.

@@ -289,6 +289,7 @@ EXPORTED = [
     "cvo_debug_last_candidates", "cvo_debug_list_builds", "cvo_debug_row_classes", "cvo_debug_speculation", "cvo_debug_scan_stats", "cvo_debug_last_geometry", "cvo_version",
     "cvo_align_association", "cvo_debug_scalar_math", "cvo_debug_prim", "cvo_debug_verified_rows", "cvo_debug_device_memory", "cvo_cloud_upload_many",
     "cvo_ctx_set_option", "cvo_ctx_advice", "cvo_debug_cloud_order",
+    "cvo_debug_cloud_order_route", "cvo_debug_order_route_rule", "cvo_debug_wide_plan",
     "cvo_process_hint_hw_queues", "cvo_shutdown",
     "cvo_batch_open", "cvo_batch_submit", "cvo_batch_poll", "cvo_batch_pending", "cvo_batch_stats", "cvo_batch_close",
     "cvo_inner_product_batch", "cvo_function_angle_batch", "cvo_debug_last_score_batch",
@@ -388,6 +389,9 @@ def lib(path=None):
     L.cvo_debug_verified_rows.argtypes = [vp, C.POINTER(C.c_ulonglong)]
     L.cvo_debug_device_memory.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.cvo_debug_cloud_order.argtypes = [vp, C.POINTER(C.c_int)]
+    L.cvo_debug_cloud_order_route.argtypes = [vp]
+    L.cvo_debug_order_route_rule.argtypes = [ip, ip, C.c_char_p, ip]
+    L.cvo_debug_wide_plan.argtypes = [ip, C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int)]
     dp = C.POINTER(C.c_double)
     L.cvo_multiframe_align.argtypes = [vp, C.POINTER(cvo_params_t), ip, C.POINTER(vp), dp, C.POINTER(C.c_int), ip,
                                        C.POINTER(C.c_int), C.POINTER(cvo_multiframe_info_t),

@@ -509,6 +509,26 @@ class LidarRand:
         return int(_capi.lib().cvo_lidar_rand_next(C.byref(self.c)))
 
 
+def debug_order_route_rule(n, finite=True, order=None, no_sort=False):
+    """cvo_debug_order_route_rule: who orders a cloud of n points (0 host, 1 k_kd_order, 2 the multi-block ordering) under the
+    text `order` of the ORDER switch (None: unset) - the function the upload paths call, no context needed."""
+    return int(_capi.lib().cvo_debug_order_route_rule(int(n), int(bool(finite)), None if order is None else str(order).encode(), int(bool(no_sort))))
+
+
+def debug_wide_plan(n):
+    """cvo_debug_wide_plan -> (W, rows): the leaf capacity of a default context and the (level, lo, hi, left) of every cut of
+    a segment of more than W points in the host's plan of the multi-block ordering of n points."""
+    W, k = C.c_int(), C.c_int()
+    ipp = C.POINTER(C.c_int)
+    rc = _capi.lib().cvo_debug_wide_plan(int(n), C.byref(W), None, 0, C.byref(k))
+    rows = np.zeros((max(k.value, 1), 4), np.int32)
+    if rc == 0:
+        rc = _capi.lib().cvo_debug_wide_plan(int(n), C.byref(W), rows.ctypes.data_as(ipp), k.value, C.byref(k))
+    if rc != 0:
+        _raise(rc, "cvo_debug_wide_plan refused its arguments")
+    return W.value, rows[:k.value]
+
+
 def debug_lidar_atan2(y, x):
     """cvo_debug_lidar_atan2: the library's own atan2 in degrees (cvo_lidar_math.h, what the twin and the kernels compile),
     evaluated on the host for arrays y, x of doubles."""
@@ -561,6 +581,11 @@ class DeviceCloud:
         out = np.zeros(max(self.n, 1), np.int32)
         self.gpu._check(self.gpu.L.cvo_debug_cloud_order(self.handle, out.ctypes.data_as(C.POINTER(C.c_int))))
         return out[:self.n]
+
+    def debug_order_route(self):
+        """cvo_debug_cloud_order_route: what ordered this cloud - 0 the host, 1 k_kd_order, 2 the multi-block ordering of
+        ORDER=wide."""
+        return int(self.gpu.L.cvo_debug_cloud_order_route(self.handle))
 
     def __del__(self):
         try:

@@ -254,6 +254,9 @@ int cvo_ctx_create(int device, cvo_ctx** out) {
   // k_kd_order keeps the keys of a whole cloud in LDS: up to 128 KB of dynamic shared memory
   ok = ok && hipFuncSetAttribute((const void*)k_kd_order, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  (int)(sizeof(unsigned long long) * KD_MAX_POINTS)) == hipSuccess;
+  // ... and k_kd_wide_leaves those of a leaf: as much with WIDE_LEAF at its maximum
+  ok = ok && hipFuncSetAttribute((const void*)k_kd_wide_leaves, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)(sizeof(unsigned long long) * KD_MAX_POINTS)) == hipSuccess;
   if (!ok) {
     cvo_ctx_destroy(c);
     return CVO_E_HIP;

@@ -99,6 +99,29 @@ int cvo_debug_cloud_order(const cvo_cloud* c, int* out) {
   return CVO_OK;
 }
 
+int cvo_debug_cloud_order_route(const cvo_cloud* c) { return c ? c->order_route : CVO_E_INVALID; }
+
+int cvo_debug_order_route_rule(int n, int finite, const char* order_value, int no_sort) {
+  CtxOptions o;
+  const OptionSpec* spec = std::find_if(std::begin(kOptions), std::end(kOptions), [](const OptionSpec& s) { return s.kind == OptKind::Order; });
+  parse_option(o, *spec, order_value);
+  return order_route(n, finite != 0, o.order, no_sort != 0);
+}
+
+int cvo_debug_wide_plan(int n, int* W, int* rows, int capacity, int* n_rows) {
+  if (n < 0 || n > KD_WIDE_MAX_POINTS || !n_rows || capacity < 0 || (capacity > 0 && !rows)) return CVO_E_INVALID;
+  const int leaf = CtxOptions().wide_leaf;
+  if (W) *W = leaf;
+  WidePlan P;
+  wide_plan(n, leaf, P);
+  *n_rows = (int)P.segs.size();
+  for (int k = 0; k < std::min(capacity, *n_rows); k++) {
+    const int row[4] = {P.seg_level[k], P.segs[k].lo, P.segs[k].hi, P.segs[k].left};
+    std::memcpy(rows + 4 * (size_t)k, row, sizeof row);
+  }
+  return CVO_OK;
+}
+
 int cvo_debug_device_memory(cvo_ctx* ctx, size_t* free_bytes, size_t* total_bytes) {
   if (!ctx || !free_bytes || !total_bytes) return fail(ctx, CVO_E_INVALID, "cvo_debug_device_memory: bad argument");
   HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -1,7 +1,7 @@
 // cvo_ingest.hip -- resident clouds from rows that are already in device memory: cvo_cloud_from_device / _many / _aos192.
 // The argument checks (every pointer is classified before anything reads through it), one k_cloud_ingest launch over all
-// clouds of a call, one read-back of the control blocks, then upload_host_cloud's route rule: k_kd_order through
-// finish_uploads, or the host's spatial_order on the coordinates alone + k_cloud_gather.
+// clouds of a call, one read-back of the control blocks, then upload_host_cloud's route rule: k_kd_order or the wide
+// ordering through finish_uploads, or the host's spatial_order on the coordinates alone + k_cloud_gather.
 // A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.  Shared declarations: cvo_internal.h; the
 // helpers shared with the host route (spatial_order, cloud_slab_list, finish_uploads): cvo_upload.hip.
 namespace {
@@ -76,7 +76,6 @@ int ingest_device_clouds(cvo_ctx* ctx, int n_clouds, const cvo_device_rows_t* ro
   // whether the label rows are one-hot (raw_lid / lid are reserved whenever labels are given and NO_ONEHOT is not set; the
   // cloud's lid pointer stays null when a row fails the rule).  ONE walk, no second allocation; the raw arrays stay in
   // the slab on both routes (k_cloud_gather reads them where the host route would have staged the final form).
-  const bool switches_device = !ctx->opt.no_sort && ctx->opt.order == CloudOrder::Device;
   int gx = 1, n_jobs = 0;
   for (int q = 0; q < n_clouds; q++) {
     const cvo_device_rows_t& d = rows[q];
@@ -89,7 +88,7 @@ int ingest_device_clouds(cvo_ctx* ctx, int n_clouds, const cvo_device_rows_t* ro
     while (NP < d.n) NP *= 2;
     const bool has = d.n > 0;
     shapes[q] = SlabShape{(size_t)std::max(d.n, 1), NP, has && d.feat, has && d.label, has && d.geotype, has && d.label && !ctx->opt.no_onehot,
-                          has, has && d.n >= 8 && d.n <= KD_MAX_POINTS && switches_device};
+                          has, order_route(d.n, true, ctx->opt.order, ctx->opt.no_sort) == ORDER_ROUTE_BLOCK};
     size_t unused = 0;
     if (const int rc = c->slab.lay_out(ctx, "cloud", cloud_slab_list(*c, shapes[q], &unused), nullptr); rc != CVO_OK) {
       release();
@@ -185,9 +184,7 @@ int ingest_device_clouds(cvo_ctx* ctx, int n_clouds, const cvo_device_rows_t* ro
     if (!std::isfinite(c->cx) || !std::isfinite(c->cy) || !std::isfinite(c->cz)) c->cx = c->cy = c->cz = 0.f;
     const bool has_lid = shapes[q].lid && f.onehot != 0u;
     if (!has_lid) c->lid = c->raw_lid = nullptr;  // (reserved, unused: the kernels take the one-hot path from a non-null lid)
-    SlabShape s = shapes[q];
-    s.lid = has_lid;
-    s.kd = s.kd && f.finite != 0u;  // the route rule of upload_host_cloud
+    c->order_route = order_route(n, f.finite != 0u, ctx->opt.order, ctx->opt.no_sort);  // the route rule of upload_host_cloud
     KdJob job{};
     size_t unused = 0;  // the job's pointers: the same list over the same slab, minus the class ids of a cloud that is not one-hot
     ScratchLayout(c->slab.p).walk(cloud_slab_list(job, shapes[q], &unused));
@@ -195,7 +192,8 @@ int ingest_device_clouds(cvo_ctx* ctx, int n_clouds, const cvo_device_rows_t* ro
     job.n = n;
     job.NP = shapes[q].NP;
     c->h_order.assign((size_t)n, 0);
-    if (s.kd) {
+    staged[q].wide = c->order_route == ORDER_ROUTE_WIDE;
+    if (c->order_route != ORDER_ROUTE_HOST) {
       staged[q].job = job;
     } else {
       staged[q].job = KdJob{};
@@ -228,7 +226,7 @@ int ingest_device_clouds(cvo_ctx* ctx, int n_clouds, const cvo_device_rows_t* ro
       return hip_fail("gather", e);
     }
   }
-  // ---- device ordering: one k_kd_order launch over the clouds that asked for it, the orders back, THE synchronisation
+  // ---- device ordering: one k_kd_order launch over the clouds that asked for it, the wide clouds' launches, the orders back, THE synchronisation
   return finish_uploads(ctx, staged);  // (on error every cloud released)
 }
 

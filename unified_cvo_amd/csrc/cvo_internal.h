@@ -294,6 +294,7 @@ struct cvo_cloud : CloudArrays {
   mutable DeviceRegion tiles;
   mutable float4* tile4 = nullptr;  // (typed view of `tiles`)
   std::vector<int> h_order;  // host copy (the ELL is stored by sorted row; exports map it back)
+  int order_route = 0;       // who made it (order_route, cvo_upload.hip): 0 the host, 1 k_kd_order, 2 the wide ordering
   float cx = 0, cy = 0, cz = 0;  // centroid (used only as the cull centre)
   float rmax = 0;                // largest |p| (bounds the motion of any point under a pose change)
 };
@@ -315,7 +316,8 @@ struct cvo_ctx {
   CtxOptions opt;                          // the switches (cvo_options.h)
   std::mutex upload_mutex;                 // cvo_cloud_upload / _aos192 share upload_stream and the error string
   std::mutex kd_mutex;                     // the ordering launches of concurrent uploads share upload_stream and d_kd_jobs
-  DeviceRegion d_kd_jobs;                  // job descriptors of the running k_kd_order launch
+  DeviceRegion d_kd_jobs;                  // job descriptors of the running k_kd_order launch and of the wide clouds' k_cloud_gather
+  DeviceRegion d_kd_wide;                  // scratch of the wide ordering (wide_region_list), grown on demand, under kd_mutex too
   hipStream_t stream = nullptr;
   hipStream_t upload_stream = nullptr;  // cvo_cloud_upload copies here (never waits for, nor delays, the solver's streams)
   std::string err;

@@ -19,7 +19,8 @@ namespace cvo_dev {
 // segment in coordinate order (a segment never leaves its range of positions: the segment number is the key's top),
 // the split positions follow from the segment sizes alone, a block-wide prefix sum renumbers the segments.  Segments
 // that are done (<= 4 points) keep their order (their key's coordinate field is the position).  12-14 levels for
-// 16k points; up to KD_MAX_POINTS points per cloud (128 KB of keys in LDS), larger clouds are ordered on the host.
+// 16k points; up to KD_MAX_POINTS points per cloud (128 KB of keys in LDS), larger clouds are ordered on the host or,
+// under ORDER=wide, by the kernels of cvo_k_kd_wide.h, which share the level loop (kd_order_levels) with this one.
 // Then the kernel writes order / inverse / the sorted coordinates and gathers the attribute arrays the caller
 // supplied into spatial order (colour 5 -> 8 floats, classes 19 -> 20, geometric type 2).
 // ------------------------------------------------------------------------------------------
@@ -52,7 +53,7 @@ __device__ __forceinline__ unsigned kd_ordered(float v) {
   return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
 }
 // split of a segment of nn points (spatial_order / kd_split in cvo_hip.hip): 0 = the segment is done
-__device__ __forceinline__ int kd_left(int nn) {
+__host__ __device__ inline int kd_left(int nn) {
   if (nn <= 4) return 0;
   const int unit = nn > 512 ? 512 : (nn > 64 ? 64 : 4);
   int left = ((nn / 2 + unit - 1) / unit) * unit;
@@ -60,11 +61,114 @@ __device__ __forceinline__ int kd_left(int nn) {
   return left > 0 ? left : 0;
 }
 
+// The level loop of the ordering, for one block and up to KD_MAX_POINTS points whose keys fit in LDS (k_kd_order: a whole
+// cloud from its root box; k_kd_wide_leaves, cvo_k_kd_wide.h: one segment of a larger cloud from the level the global
+// partitions reached): kd_key[NP] in LDS, ext the extents at the first level (halved here, level by level), seg_of_pos[NP]
+// and seg_lo[2][seg_stride] scratch in global memory, fetch(id) the coordinates of local point id.  On return
+// kd_key[p] & 0xffff is the local point at sorted position p.  Every thread of the block calls it.
+template <class Fetch>
+__device__ __forceinline__ void kd_order_levels(unsigned long long* kd_key, int n, int NP, float (&ext)[3], unsigned short* seg_of_pos,
+                                                unsigned short* seg_lo, int seg_stride, Fetch fetch) {
+  __shared__ int s_scan[KD_THREADS / 64];
+  __shared__ int s_total;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // ---- one segment: all points in their original order
+  const int per = NP / KD_THREADS;  // consecutive positions per thread in the renumbering pass (NP >= KD_THREADS)
+  for (int p = tid; p < NP; p += KD_THREADS) {
+    kd_key[p] = p < n ? (unsigned long long)p : ~0ull;
+    seg_of_pos[p] = p < n ? (unsigned short)0 : (unsigned short)0xffff;
+  }
+  if (tid == 0) {
+    seg_lo[0] = 0;
+    seg_lo[1] = (unsigned short)n;  // (n <= 16384 < 65536)
+  }
+  __syncthreads();
+  int cur = 0, nseg = 1;
+  for (int level = 0; level < 24; level++) {
+    int axis = 0;
+    if (ext[1] > ext[axis]) axis = 1;
+    if (ext[2] > ext[axis]) axis = 2;
+    const unsigned short* slo = seg_lo + cur * seg_stride;
+    // ---- keys of this level
+    for (int p = tid; p < n; p += KD_THREADS) {
+      const unsigned id = (unsigned)(kd_key[p] & 0xffffull);
+      const unsigned s = seg_of_pos[p];
+      const int l0 = slo[s], nn = (int)slo[s + 1] - l0;
+      unsigned coord = (unsigned)p;  // a finished segment keeps its order
+      if (kd_left(nn) > 0) {
+        const float4 x = fetch(id);
+        coord = kd_ordered(axis == 0 ? x.x : (axis == 1 ? x.y : x.z));
+      }
+      kd_key[p] = ((unsigned long long)s << 48) | ((unsigned long long)coord << 16) | id;
+    }
+    __syncthreads();
+    // ---- bitonic sort of the NP keys (pads are ~0: they stay at the end)
+    for (int k = 2; k <= NP; k <<= 1)
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int t = tid; t < NP / 2; t += KD_THREADS) {
+          const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+          const unsigned long long a = kd_key[i], b = kd_key[l];
+          const bool asc = (i & k) == 0;
+          if ((a > b) == asc) {
+            kd_key[i] = b;
+            kd_key[l] = a;
+          }
+        }
+        __syncthreads();
+      }
+    // ---- new segments: a position starts one if it is the first of its segment or the split position of it
+    const int p0 = tid * per;
+    int cnt = 0;
+    unsigned flags = 0;  // per <= 16 positions per thread
+    for (int q = 0; q < per; q++) {
+      const int p = p0 + q;
+      if (p < n) {
+        const unsigned s = seg_of_pos[p];
+        const int l0 = slo[s], nn = (int)slo[s + 1] - l0;
+        const int left = kd_left(nn);
+        if (p == l0 || (left > 0 && p == l0 + left)) {
+          flags |= 1u << q;
+          cnt++;
+        }
+      }
+    }
+    int incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int v = __shfl_up(incl, o);
+      if (lane >= o) incl += v;
+    }
+    if (lane == 63) s_scan[wave] = incl;
+    __syncthreads();
+    int base = incl - cnt;
+    for (int w = 0; w < wave; w++) base += s_scan[w];
+    if (tid == KD_THREADS - 1) s_total = base + cnt;
+    __syncthreads();
+    const int total = s_total;
+    unsigned short* nlo = seg_lo + (cur ^ 1) * seg_stride;
+    int id_run = base - 1;
+    for (int q = 0; q < per; q++) {
+      const int p = p0 + q;
+      if (p < n) {
+        if (flags & (1u << q)) {
+          id_run++;
+          nlo[id_run] = (unsigned short)p;
+        }
+        seg_of_pos[p] = (unsigned short)id_run;
+      }
+    }
+    if (tid == 0) nlo[total] = (unsigned short)n;
+    __syncthreads();  // (the scratch arrays live in global memory: the barrier's workgroup-scope fence publishes them)
+    if (total == nseg) break;  // nothing was split: the ordering is complete
+    nseg = total;
+    cur ^= 1;
+    ext[axis] *= 0.5f;
+  }
+}
+
 __global__ __launch_bounds__(KD_THREADS) void k_kd_order(const KdJob* __restrict__ jobs) {
   extern __shared__ unsigned long long kd_key[];  // [NP]
   __shared__ float s_red[KD_THREADS / 64][6];
-  __shared__ int s_scan[KD_THREADS / 64];
-  __shared__ int s_total;
   const KdJob J = jobs[blockIdx.x];
   const int n = J.n, NP = J.NP, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   // ---- root box
@@ -97,98 +201,7 @@ __global__ __launch_bounds__(KD_THREADS) void k_kd_order(const KdJob* __restrict
     }
     ext[c] = b - a;
   }
-  // ---- one segment: all points in their original order
-  const int per = NP / KD_THREADS;  // consecutive positions per thread in the renumbering pass (NP >= KD_THREADS)
-  for (int p = tid; p < NP; p += KD_THREADS) {
-    kd_key[p] = p < n ? (unsigned long long)p : ~0ull;
-    J.seg_of_pos[p] = p < n ? (unsigned short)0 : (unsigned short)0xffff;
-  }
-  if (tid == 0) {
-    J.seg_lo[0] = 0;
-    J.seg_lo[1] = (unsigned short)n;  // (n <= 16384 < 65536)
-  }
-  __syncthreads();
-  int cur = 0, nseg = 1;
-  for (int level = 0; level < 24; level++) {
-    int axis = 0;
-    if (ext[1] > ext[axis]) axis = 1;
-    if (ext[2] > ext[axis]) axis = 2;
-    const unsigned short* slo = J.seg_lo + cur * KD_MAX_SEGS;
-    // ---- keys of this level
-    for (int p = tid; p < n; p += KD_THREADS) {
-      const unsigned id = (unsigned)(kd_key[p] & 0xffffull);
-      const unsigned s = J.seg_of_pos[p];
-      const int l0 = slo[s], nn = (int)slo[s + 1] - l0;
-      unsigned coord = (unsigned)p;  // a finished segment keeps its order
-      if (kd_left(nn) > 0) {
-        const float4 x = J.x4[id];
-        coord = kd_ordered(axis == 0 ? x.x : (axis == 1 ? x.y : x.z));
-      }
-      kd_key[p] = ((unsigned long long)s << 48) | ((unsigned long long)coord << 16) | id;
-    }
-    __syncthreads();
-    // ---- bitonic sort of the NP keys (pads are ~0: they stay at the end)
-    for (int k = 2; k <= NP; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        for (int t = tid; t < NP / 2; t += KD_THREADS) {
-          const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-          const unsigned long long a = kd_key[i], b = kd_key[l];
-          const bool asc = (i & k) == 0;
-          if ((a > b) == asc) {
-            kd_key[i] = b;
-            kd_key[l] = a;
-          }
-        }
-        __syncthreads();
-      }
-    // ---- new segments: a position starts one if it is the first of its segment or the split position of it
-    const int p0 = tid * per;
-    int cnt = 0;
-    unsigned flags = 0;  // per <= 16 positions per thread
-    for (int q = 0; q < per; q++) {
-      const int p = p0 + q;
-      if (p < n) {
-        const unsigned s = J.seg_of_pos[p];
-        const int l0 = slo[s], nn = (int)slo[s + 1] - l0;
-        const int left = kd_left(nn);
-        if (p == l0 || (left > 0 && p == l0 + left)) {
-          flags |= 1u << q;
-          cnt++;
-        }
-      }
-    }
-    int incl = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int v = __shfl_up(incl, o);
-      if (lane >= o) incl += v;
-    }
-    if (lane == 63) s_scan[wave] = incl;
-    __syncthreads();
-    int base = incl - cnt;
-    for (int w = 0; w < wave; w++) base += s_scan[w];
-    if (tid == KD_THREADS - 1) s_total = base + cnt;
-    __syncthreads();
-    const int total = s_total;
-    unsigned short* nlo = J.seg_lo + (cur ^ 1) * KD_MAX_SEGS;
-    int id_run = base - 1;
-    for (int q = 0; q < per; q++) {
-      const int p = p0 + q;
-      if (p < n) {
-        if (flags & (1u << q)) {
-          id_run++;
-          nlo[id_run] = (unsigned short)p;
-        }
-        J.seg_of_pos[p] = (unsigned short)id_run;
-      }
-    }
-    if (tid == 0) nlo[total] = (unsigned short)n;
-    __syncthreads();  // (the scratch arrays live in global memory: the barrier's workgroup-scope fence publishes them)
-    if (total == nseg) break;  // nothing was split: the ordering is complete
-    nseg = total;
-    cur ^= 1;
-    ext[axis] *= 0.5f;
-  }
+  kd_order_levels(kd_key, n, NP, ext, J.seg_of_pos, J.seg_lo, KD_MAX_SEGS, [&](unsigned id) { return J.x4[id]; });
   // ---- outputs
   for (int p = tid; p < n; p += KD_THREADS) {
     const int id = (int)(kd_key[p] & 0xffffull);

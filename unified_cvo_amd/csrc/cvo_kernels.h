@@ -67,6 +67,7 @@
 #include "cvo_k_prims.h"
 #include "cvo_k_compact.h"
 #include "cvo_k_sort.h"
+#include "cvo_k_kd_wide.h"
 #include "cvo_k_voxel.h"
 #include "cvo_k_rgbd.h"
 #include "cvo_k_fast.h"

@@ -10,7 +10,7 @@ namespace {
 constexpr int MAX_STREAMS = 8;    // sub-batch streams of a context (cvo_ctx::MAX_GROUPS)
 constexpr float SKIN_MIN = 0.05f;  // lower clamp of the skin (DevParams::skin_min), a fraction of the cut-off radius
 
-enum class CloudOrder { Device, Host, Virtual };  // who computes the spatial ordering of an upload (CVO_ORDER)
+enum class CloudOrder { Device, Host, Virtual, Wide };  // who computes the spatial ordering of an upload (CVO_ORDER; the rule: order_route, cvo_upload.hip)
 
 struct CtxOptions {
   // ---- list reuse / graphs (scripts/skin_sweep.py, early_sweep.py, first_chunk_sweep.sh) ----
@@ -40,6 +40,7 @@ struct CtxOptions {
   // ---- A/B switches of the tests: every one of them leaves the results bit-identical ----
   bool no_sort = false, no_long_lists = false, no_onehot = false, ip_chain = false, keep_columns = false, no_speculate = false;
   CloudOrder order = CloudOrder::Device;
+  int wide_leaf = KD_WIDE_LEAF;  // ORDER=wide: the largest segment one block orders in LDS (cvo_k_kd_wide.h)
   int row_max = ASSOC_CAP16;  // DevParams::row_max_cap; ASSOC_CAP16 = off
   int voxel_host = -1;        // cvo_voxel_select / cvo_cloud_upload_voxel: 1 = the CPU twin, 0 = the kernels, -1 = by size (cvo_voxel.hip)
   int rgbd_host = -1;         // cvo_rgbd_points / cvo_cloud_upload_rgbd: 1 = the CPU twin, 0 = the kernels, -1 = by size (cvo_rgbd.hip)
@@ -59,7 +60,7 @@ struct CtxOptions {
 
 // How the text of a switch is read.  Flag: on unless unset or a number equal to 0 ("1", "" and "yes" are on).  Level: a flag
 // whose number, when it has one above 1, is kept.  Integer / Real: atoi / atof (text without a number is 0), then the clamp.
-// Order: "host" / "virtual", anything else is the device's ordering.
+// Order: "host" / "virtual" / "wide", anything else is the device's ordering.
 enum class OptKind { Flag, Level, Integer, Real, Order };
 
 struct OptionSpec {
@@ -90,6 +91,7 @@ constexpr OptionSpec kOptions[] = {
     opt_int("QUEUE_ADMIT", &CtxOptions::queue_admit, 1),
     opt_flag("NO_SORT", &CtxOptions::no_sort),
     {"ORDER", OptKind::Order, nullptr, nullptr, nullptr, 0, 0},
+    opt_int("WIDE_LEAF", &CtxOptions::wide_leaf, KD_THREADS, KD_MAX_POINTS),
     opt_flag("NO_LONG_LISTS", &CtxOptions::no_long_lists),
     opt_int("ROW_MAX", &CtxOptions::row_max, 1, ASSOC_CAP16),
     opt_flag("NO_ONEHOT", &CtxOptions::no_onehot),
@@ -124,7 +126,7 @@ inline void parse_option(CtxOptions& o, const OptionSpec& s, const char* text) {
     case OptKind::Level: o.*s.integer = on ? std::max(1, atoi(text)) : 0; break;
     case OptKind::Integer: o.*s.integer = text ? std::max((int)s.lo, std::min(atoi(text), (int)s.hi)) : def.*s.integer; break;
     case OptKind::Real: o.*s.real = text ? std::max((float)s.lo, std::min((float)atof(text), (float)s.hi)) : def.*s.real; break;
-    case OptKind::Order: o.order = !text ? def.order : (!std::strcmp(text, "host") ? CloudOrder::Host : (!std::strcmp(text, "virtual") ? CloudOrder::Virtual : CloudOrder::Device)); break;
+    case OptKind::Order: o.order = !text ? def.order : (!std::strcmp(text, "host") ? CloudOrder::Host : (!std::strcmp(text, "virtual") ? CloudOrder::Virtual : (!std::strcmp(text, "wide") ? CloudOrder::Wide : CloudOrder::Device))); break;
   }
 }
 

@@ -1,4 +1,4 @@
-// cvo_upload.hip -- resident clouds: host-side spatial ordering (the twin of k_kd_order), staging, one allocation + one copy per cloud, cvo_cloud_upload / _aos192 / _many, cvo_cloud_transformed, zero slabs for attributes a cloud was uploaded without.
+// cvo_upload.hip -- resident clouds: the route rule of the ordering, the host's plan and launches of the multi-block ordering (ORDER=wide), host-side spatial ordering (the twin of k_kd_order), staging, one allocation + one copy per cloud, cvo_cloud_upload / _aos192 / _many, cvo_cloud_transformed, zero slabs for attributes a cloud was uploaded without.
 // A SECTION of the one translation unit cvo_hip.hip (which includes the sections in dependency order and says why it is one
 // unit); not compiled on its own.  Shared declarations: cvo_internal.h.
 namespace {
@@ -29,6 +29,111 @@ int ensure_attributes(cvo_ctx* ctx, const cvo_cloud* c, bool need_feat, bool nee
   if (!m->label) m->label = z.label;
   if (!m->geo) m->geo = z.geo;
   return CVO_OK;
+}
+
+// THE route rule of an upload, host rows or device rows: who orders a cloud of n points (cvo_debug_cloud_order_route's values).
+// Fewer than 8 points, a non-finite coordinate and NO_SORT are the identity, which the host writes.
+enum { ORDER_ROUTE_HOST = 0, ORDER_ROUTE_BLOCK = 1, ORDER_ROUTE_WIDE = 2 };
+int order_route(int n, bool finite, CloudOrder order, bool no_sort) {
+  if (n < 8 || !finite || no_sort) return ORDER_ROUTE_HOST;
+  if (order != CloudOrder::Device && order != CloudOrder::Wide) return ORDER_ROUTE_HOST;
+  if (n <= KD_MAX_POINTS) return ORDER_ROUTE_BLOCK;
+  return order == CloudOrder::Wide && n <= KD_WIDE_MAX_POINTS ? ORDER_ROUTE_WIDE : ORDER_ROUTE_HOST;
+}
+
+// The plan of the multi-block ordering (cvo_k_kd_wide.h) of n points with leaves of at most `leaf`: kd_left cuts by count, so
+// every segment of every level is known before anything runs.  Level by level, by position inside a level: the cuts of the
+// segments of more than `leaf` points, tiles of up to KD_WIDE_TILE positions over them, and every segment of at most `leaf`
+// points as a leaf of the level at which it appeared.
+struct WidePlan {
+  std::vector<KdWideSeg> segs;
+  std::vector<int> seg_level;  // of segs[i]
+  std::vector<KdWideTile> tiles;
+  std::vector<int> tile0;      // the first tile of every level, and the total behind them
+  std::vector<KdWideLeaf> leaves;
+  int sop_total = 0, np_max = 0;
+  int levels() const { return (int)tile0.size() - 1; }
+};
+void wide_plan(int n, int leaf, WidePlan& P) {
+  P = WidePlan{};
+  std::vector<std::pair<int, int>> cur{{0, n}}, nxt;
+  for (int level = 0;; level++) {
+    P.tile0.push_back((int)P.tiles.size());
+    nxt.clear();
+    for (const auto& [lo, hi] : cur) {
+      if (hi - lo > leaf) {
+        const int left = kd_left(hi - lo);
+        P.segs.push_back(KdWideSeg{lo, hi, left, (int)P.tiles.size()});
+        for (int at = lo; at < hi; at += KD_WIDE_TILE) P.tiles.push_back(KdWideTile{at, std::min(KD_WIDE_TILE, hi - at), (int)P.segs.size() - 1});
+        P.seg_level.push_back(level);
+        nxt.emplace_back(lo, lo + left);
+        nxt.emplace_back(lo + left, hi);
+      } else {
+        int NP = KD_THREADS;
+        while (NP < hi - lo) NP *= 2;
+        P.leaves.push_back(KdWideLeaf{lo, hi - lo, NP, level, P.sop_total});
+        P.sop_total += NP;
+        P.np_max = std::max(P.np_max, NP);
+      }
+    }
+    if (nxt.empty()) break;
+    cur.swap(nxt);
+  }
+}
+
+// THE list of the wide ordering's scratch region for the clouds of one call: the plans' tables (the prefix the host stages
+// and uploads with one copy), every cloud's small tables, and the per-point buffers, which the clouds share - they run one
+// after another on the upload stream.
+struct WideShape {
+  size_t n_max = 0, sop_max = 0, leaves_max = 0;
+  int seg_stride = 0;
+};
+template <class A>
+inline void wide_tables_list(ScratchLayout& l, A& a, const WidePlan& P) {
+  l.take(a.segs, P.segs.size());
+  l.take(a.tiles, P.tiles.size());
+  l.take(a.leaves, P.leaves.size());
+}
+inline auto wide_region_list(std::vector<KdWide>& J, const std::vector<WidePlan>& P, const WideShape& s, size_t* up_bytes) {
+  return [&J, &P, s, up_bytes](ScratchLayout& l) {
+    for (size_t k = 0; k < J.size(); k++) wide_tables_list(l, J[k], P[k]);
+    *up_bytes = l.off;
+    for (size_t k = 0; k < J.size(); k++) {
+      l.take(J[k].box, 6 * KD_WIDE_BOX_BLOCKS + 3);
+      l.take(J[k].hist, 1024 * P[k].segs.size());
+      l.take(J[k].tile_cnt, P[k].tiles.size());
+      l.take(J[k].seg_piv, P[k].segs.size());
+    }
+    KdWide& a = J[0];
+    l.take(a.buf[0], s.n_max);
+    l.take(a.buf[1], s.n_max);
+    l.take(a.keys, s.n_max);
+    l.take(a.seg_of_pos, s.sop_max);
+    l.take(a.seg_lo, 2 * (size_t)s.seg_stride * s.leaves_max);
+    for (size_t k = 1; k < J.size(); k++) {
+      J[k].buf[0] = a.buf[0], J[k].buf[1] = a.buf[1], J[k].keys = a.keys;
+      J[k].seg_of_pos = a.seg_of_pos, J[k].seg_lo = a.seg_lo;
+    }
+  };
+}
+
+// The launches of one cloud's wide ordering, back to back on `stream`: nothing comes back, nothing waits.  J.order holds the
+// order when they have run.
+hipError_t enqueue_wide_order(const KdWide& J, const WidePlan& P, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(J.hist, 0, sizeof(unsigned) * 1024 * P.segs.size(), stream);
+  if (e != hipSuccess) return e;
+  const int gb = std::min((J.n + 4 * KD_WIDE_THREADS - 1) / (4 * KD_WIDE_THREADS), KD_WIDE_BOX_BLOCKS);
+  hipLaunchKernelGGL(k_kd_wide_box, dim3((unsigned)gb), dim3(KD_WIDE_THREADS), 0, stream, J);
+  hipLaunchKernelGGL(k_kd_wide_ext, dim3(1), dim3(64), 0, stream, J, gb);
+  for (int g = 0; g < P.levels(); g++) {
+    const int t0 = P.tile0[g];
+    const dim3 grid((unsigned)(P.tile0[g + 1] - t0));
+    for (int pass = 0; pass < 4; pass++) hipLaunchKernelGGL(k_kd_wide_hist, grid, dim3(KD_WIDE_THREADS), 0, stream, J, g, t0, pass);
+    hipLaunchKernelGGL(k_kd_wide_count, grid, dim3(KD_WIDE_THREADS), 0, stream, J, t0);
+    hipLaunchKernelGGL(k_kd_wide_scatter, grid, dim3(KD_WIDE_THREADS), 0, stream, J, g, t0);
+  }
+  hipLaunchKernelGGL(k_kd_wide_leaves, dim3((unsigned)P.leaves.size()), dim3(KD_THREADS), sizeof(unsigned long long) * (size_t)P.np_max, stream, J);
+  return hipGetLastError();
 }
 
 }  // namespace
@@ -123,6 +228,7 @@ struct HostCloud {
 struct StagedCloud {
   cvo_cloud* c = nullptr;
   KdJob job{};          // job.n == 0: ordered on the host, nothing left to do
+  bool wide = false;    // the job is the wide ordering's (cvo_k_kd_wide.h) and k_cloud_gather's, not k_kd_order's
   std::vector<char> stage;
 };
 
@@ -134,15 +240,17 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
   c->device = ctx->device;
   c->n = n;
   const size_t nn = (size_t)std::max(n, 1);
-  // Where the ordering runs: on the device for clouds k_kd_order holds in LDS (the host then only stages, allocates and
-  // copies: ~0.1 ms of CPU per 10k cloud instead of 1.2), on this thread otherwise (tiny, huge or non-finite clouds,
-  // CVO_NO_SORT, CVO_ORDER=host).
+  // Where the ordering runs (order_route): on the device for clouds k_kd_order holds in LDS (the host then only stages,
+  // allocates and copies: ~0.1 ms of CPU per 10k cloud instead of 1.2) and, under CVO_ORDER=wide, for larger ones; on this
+  // thread otherwise (tiny, huge or non-finite clouds, CVO_NO_SORT, CVO_ORDER=host).
   bool finite = true;
   for (int i = 0; i < n && finite; i++) {
     const float* p = reinterpret_cast<const float*>(h.xyz + h.row(i) * h.xyz_stride);
     finite = std::isfinite(p[0]) && std::isfinite(p[1]) && std::isfinite(p[2]);
   }
-  const bool device_order = n >= 8 && n <= KD_MAX_POINTS && finite && !ctx->opt.no_sort && ctx->opt.order == CloudOrder::Device;
+  const int route = order_route(n, finite, ctx->opt.order, ctx->opt.no_sort);
+  const bool device_order = route != ORDER_ROUTE_HOST;
+  c->order_route = route;
   // one-hot class rows?  (exactly: the fast path replaces arithmetic on the rows by two constants)
   std::vector<int> lid_host;
   if (h.label && n > 0 && !ctx->opt.no_onehot) {
@@ -162,7 +270,7 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
   // THE list of the slab's arrays (cloud_slab_list), walked over two bases: the staging buffer (into s) and the slab (into
   // the cloud itself and, for k_kd_order, into the job)
   size_t up_bytes = 0;  // the prefix of the slab that is staged and uploaded
-  const SlabShape shape{nn, NP, h.feat != nullptr, h.label != nullptr, h.geo != nullptr, has_lid, device_order, device_order};
+  const SlabShape shape{nn, NP, h.feat != nullptr, h.label != nullptr, h.geo != nullptr, has_lid, device_order, route == ORDER_ROUTE_BLOCK};
   auto list = [&](auto& a) { return cloud_slab_list(a, shape, &up_bytes); };
   CloudArrays s;
   ScratchLayout().walk(list(s));
@@ -229,6 +337,7 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
   }
   sc->c = c;
   sc->job = KdJob{};
+  sc->wide = route == ORDER_ROUTE_WIDE;
   if (device_order) {
     ScratchLayout(c->slab.p).walk(list(sc->job));
     sc->job.n = n;
@@ -239,28 +348,79 @@ static int upload_host_cloud(cvo_ctx* ctx, const HostCloud& h, hipStream_t strea
 }
 
 // Second half of an upload: the copies of `clouds` have been enqueued (and, for upload_many, completed) - order the
-// clouds that asked for it with ONE launch of k_kd_order (a block per cloud) on the context's upload stream, bring the
-// permutations back (exports map rows through them), synchronise.  On error every cloud of the list is released.
+// clouds that asked for it with ONE launch of k_kd_order (a block per cloud) on the context's upload stream and, one after
+// another, the clouds of the wide ordering (its launches, then k_cloud_gather over all of them), bring the permutations
+// back (exports map rows through them), synchronise - once.  On error every cloud of the list is released.
 static int finish_uploads(cvo_ctx* ctx, std::vector<StagedCloud>& clouds) {
-  std::vector<KdJob> jobs;
-  int np_max = 0;
+  std::vector<KdJob> jobs, wide_jobs;
+  int np_max = 0, ggx = 1;
   for (auto& sc : clouds)
-    if (sc.c && sc.job.n > 0) {
+    if (sc.c && sc.job.n > 0 && !sc.wide) {
       jobs.push_back(sc.job);
       np_max = std::max(np_max, sc.job.NP);
     }
+  for (auto& sc : clouds)
+    if (sc.c && sc.job.n > 0 && sc.wide) {
+      wide_jobs.push_back(sc.job);
+      ggx = std::max(ggx, (int)std::min<long long>((5ll * sc.job.n + GATHER_THREADS - 1) / GATHER_THREADS, 4 * INGEST_MAX_BLOCKS));
+    }
+  // the wide clouds' plans and the staging copy of their tables (read by the copy below: alive until the synchronisation)
+  std::vector<WidePlan> plans(wide_jobs.size());
+  std::vector<KdWide> wide(wide_jobs.size()), wide_host(wide_jobs.size());
+  std::vector<char> wide_stage;
+  WideShape ws;
+  ws.seg_stride = ctx->opt.wide_leaf / 2 + 2;
+  for (size_t k = 0; k < wide_jobs.size(); k++) {
+    wide_plan(wide_jobs[k].n, ctx->opt.wide_leaf, plans[k]);
+    ws.n_max = std::max(ws.n_max, (size_t)wide_jobs[k].n);
+    ws.sop_max = std::max(ws.sop_max, (size_t)plans[k].sop_total);
+    ws.leaves_max = std::max(ws.leaves_max, plans[k].leaves.size());
+  }
   hipError_t e = hipSuccess;
   int rc = CVO_OK;
   std::lock_guard<std::mutex> lk(ctx->kd_mutex);
-  if (!jobs.empty()) {
+  if (!jobs.empty() || !wide_jobs.empty()) {
     // (nothing to drain: the launch that read the table last was synchronised below, under this mutex)
-    rc = ctx->d_kd_jobs.reserve(ctx, sizeof(KdJob) * jobs.size(), "ordering job table", nullptr);
-    if (rc == CVO_OK)
-      e = hipMemcpyAsync(ctx->d_kd_jobs.p, jobs.data(), sizeof(KdJob) * jobs.size(), hipMemcpyHostToDevice, ctx->upload_stream);
-    if (rc == CVO_OK && e == hipSuccess) {
+    const std::vector<KdJob>* tables[2] = {&jobs, &wide_jobs};
+    KdJob* d_jobs[2] = {nullptr, nullptr};
+    rc = ctx->d_kd_jobs.lay_out(ctx, "ordering job table", [&](ScratchLayout& l) {
+      l.take(d_jobs[0], jobs.size());
+      l.take(d_jobs[1], wide_jobs.size());
+    }, nullptr);
+    for (int q = 0; q < 2; q++)
+      if (rc == CVO_OK && e == hipSuccess && !tables[q]->empty())
+        e = hipMemcpyAsync(d_jobs[q], tables[q]->data(), sizeof(KdJob) * tables[q]->size(), hipMemcpyHostToDevice, ctx->upload_stream);
+    if (rc == CVO_OK && e == hipSuccess && !jobs.empty()) {
       hipLaunchKernelGGL(k_kd_order, dim3((unsigned)jobs.size()), dim3(KD_THREADS), sizeof(unsigned long long) * (size_t)np_max,
-                         ctx->upload_stream, ctx->d_kd_jobs.as<const KdJob>());
+                         ctx->upload_stream, (const KdJob*)d_jobs[0]);
       e = hipGetLastError();
+    }
+    if (rc == CVO_OK && e == hipSuccess && !wide_jobs.empty()) {
+      size_t up_bytes = 0;
+      rc = ctx->d_kd_wide.lay_out(ctx, "wide ordering scratch", wide_region_list(wide, plans, ws, &up_bytes), nullptr);
+      if (rc == CVO_OK) {
+        wide_stage.assign(up_bytes, 0);
+        ScratchLayout host(wide_stage.data());
+        for (size_t k = 0; k < wide.size(); k++) {
+          wide_tables_list(host, wide_host[k], plans[k]);
+          std::memcpy(const_cast<KdWideSeg*>(wide_host[k].segs), plans[k].segs.data(), sizeof(KdWideSeg) * plans[k].segs.size());
+          std::memcpy(const_cast<KdWideTile*>(wide_host[k].tiles), plans[k].tiles.data(), sizeof(KdWideTile) * plans[k].tiles.size());
+          std::memcpy(const_cast<KdWideLeaf*>(wide_host[k].leaves), plans[k].leaves.data(), sizeof(KdWideLeaf) * plans[k].leaves.size());
+        }
+        e = hipMemcpyAsync(ctx->d_kd_wide.p, wide_stage.data(), up_bytes, hipMemcpyHostToDevice, ctx->upload_stream);
+      }
+      for (size_t k = 0; rc == CVO_OK && e == hipSuccess && k < wide.size(); k++) {
+        wide[k].n = wide_jobs[k].n;
+        wide[k].seg_stride = ws.seg_stride;
+        wide[k].x4 = wide_jobs[k].x4;
+        wide[k].order = wide_jobs[k].order;
+        e = enqueue_wide_order(wide[k], plans[k], ctx->upload_stream);
+      }
+      if (rc == CVO_OK && e == hipSuccess) {
+        hipLaunchKernelGGL(k_cloud_gather, dim3((unsigned)ggx, (unsigned)wide_jobs.size()), dim3(GATHER_THREADS), 0, ctx->upload_stream,
+                           (const KdJob*)d_jobs[1]);
+        e = hipGetLastError();
+      }
     }
     for (auto& sc : clouds)
       if (rc == CVO_OK && e == hipSuccess && sc.c && sc.job.n > 0)
@@ -268,6 +428,7 @@ static int finish_uploads(cvo_ctx* ctx, std::vector<StagedCloud>& clouds) {
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->upload_stream);
   if (rc != CVO_OK || e != hipSuccess) {
+    (void)hipStreamSynchronize(ctx->upload_stream);  // (launches that read this call's tables and clouds may be in flight)
     for (auto& sc : clouds) {
       if (sc.c) cvo_cloud_free(sc.c);
       sc.c = nullptr;
@@ -429,6 +590,7 @@ int cvo_cloud_transformed(cvo_ctx* ctx, const cvo_cloud* in, const float pose12[
   c->device = ctx->device;
   c->n = in->n;
   c->h_order = in->h_order;
+  c->order_route = in->order_route;
   if (const int rc = c->slab.reserve(ctx, in->slab.bytes, "cloud", nullptr); rc != CVO_OK) {
     delete c;
     return rc;
