@@ -381,6 +381,46 @@ std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::upload_device_aos192(const CvoPo
   return out;
 }
 
+std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::merge(const ResidentClouds& clouds, const std::vector<double>* poses, float voxel_size) const {
+  if (poses && poses->size() != 12 * (size_t)clouds.size()) throw std::invalid_argument("merge: 12 pose entries per cloud");
+  std::lock_guard<std::mutex> lk(call_mutex);
+  const float s = voxel_size < 0.f ? params.multiframe_downsample_voxel_size / 2 : voxel_size;
+  std::vector<const cvo_cloud*> h(clouds.handles.begin(), clouds.handles.end());
+  size_t total = 0;
+  for (const cvo_cloud* c : h) total += (size_t)cvo_cloud_size(c);
+  std::unique_ptr<ResidentClouds> out(new ResidentClouds());
+  out->handles.assign(1, nullptr);
+  out->kept_.resize(1);
+  std::vector<int>& k = out->kept_[0];
+  k.resize(std::max<size_t>(total, 1));
+  int nk = 0;
+  check(ctx, cvo_cloud_merge(ctx, (int)h.size(), h.data(), poses ? poses->data() : nullptr, s, out->handles.data(), k.data(), &nk),
+        "cvo_cloud_merge");
+  k.resize((size_t)nk);
+  return out;
+}
+
+CvoPointCloud CvoGPU::download(const ResidentClouds& clouds, int k) const {
+  if (k < 0 || k >= clouds.size()) throw std::invalid_argument("download: no such cloud");
+  std::lock_guard<std::mutex> lk(call_mutex);
+  const cvo_cloud* c = clouds.handles[(size_t)k];
+  const int n = cvo_cloud_size(c);
+  const size_t nn = (size_t)n;
+  std::vector<float> xyz(3 * nn + 1), feat(CVO_FEATURE_DIMENSIONS * nn + 1), label(CVO_NUM_CLASSES * nn + 1), geo(2 * nn + 1);
+  int present = 0;
+  check(ctx, cvo_cloud_download(ctx, c, xyz.data(), feat.data(), label.data(), geo.data(), &present), "cvo_cloud_download");
+  const int F = present & CVO_CLOUD_HAS_FEAT ? CVO_FEATURE_DIMENSIONS : 0, Cn = present & CVO_CLOUD_HAS_LABEL ? CVO_NUM_CLASSES : 0;
+  CvoPointCloud out(F, Cn);
+  out.reserve(n, F, Cn);
+  for (int i = 0; i < n; i++) {
+    const float* f = &feat[CVO_FEATURE_DIMENSIONS * (size_t)i];
+    const float* l = &label[CVO_NUM_CLASSES * (size_t)i];
+    out.add_point(i, Vec3f{{xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]}}, std::vector<float>(f, f + F),
+                  std::vector<float>(l, l + Cn), {geo[2 * (size_t)i], geo[2 * (size_t)i + 1]});
+  }
+  return out;
+}
+
 CvoPointCloud CvoGPU::voxel_downsample(const CvoPointCloud& cloud, float voxel_size, std::vector<int>* kept) const {
   std::lock_guard<std::mutex> lk(call_mutex);
   const int n = cloud.num_points();

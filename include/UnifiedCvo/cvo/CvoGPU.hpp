@@ -92,6 +92,16 @@ class CvoGPU {
   // upload_clouds returns for one cloud, without a host copy.  Refusals (host pointers, strides, row indices) throw.
   std::unique_ptr<ResidentClouds> upload_device(const cvo_device_rows_t& rows) const;
   std::unique_ptr<ResidentClouds> upload_device_aos192(const CvoPoint* d_pts, int n) const;
+  // New: what the multi-frame drivers do right after the solve (merge_transformed_pc + a VoxelMap of side leaf / 2,
+  // main_covisMap_test.cpp:183-215, 464-534) without a host copy of any frame (cvo_cloud_merge, include/cvo_hip.h): ONE
+  // resident cloud (size() == 1) of the rows of every cloud of `clouds`, in original order, cloud after cloud, each moved by
+  // its pose - poses: 12 doubles per cloud, 3x4 row-major, what the ResidentClouds align() leaves; nullptr: nothing is moved
+  // - and thinned to the lowest row of every voxel.  voxel_size == 0: the concatenation; < 0:
+  // params.multiframe_downsample_voxel_size / 2, the covis driver's value.  kept(0): the global rows of the result's points.
+  // download: cloud k's rows in original order, bit for bit what was uploaded (cvo_cloud_download); attributes the cloud
+  // does not hold are left out (F = 0 / no classes / types 0).  Refusals throw.
+  std::unique_ptr<ResidentClouds> merge(const ResidentClouds& clouds, const std::vector<double>* poses, float voxel_size = 0.f) const;
+  CvoPointCloud download(const ResidentClouds& clouds, int k) const;
   // New: voxel-grid downsampling on the device - what the drivers do with cvo::VoxelMap before align()
   // (main_multi_frame_irls_tum.cpp:290-335; utils/VoxelMap.hpp is the host class): of every occupied voxel of side
   // voxel_size the point with the LOWEST index is kept, in ascending index (cvo_voxel_select, include/cvo_hip.h).

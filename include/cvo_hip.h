@@ -736,6 +736,39 @@ int cvo_multiframe_align(cvo_ctx* ctx, const cvo_params_t* params, int n_frames,
                          double* poses, const int* hold_const, int n_edges, const int* edges,
                          cvo_multiframe_info_t* info, cvo_multiframe_trace_t* trace, int trace_capacity, int* n_trace);
 
+/* ---- posed resident clouds merged into one, and a resident cloud read back: what the multi-frame drivers do right after
+ * the solve (merge_transformed_pc + a VoxelMap of side leaf / 2, main_covisMap_test.cpp:183-215, 464-534), without a host
+ * copy of any frame ----
+ * cvo_cloud_merge: the rows of clouds[0], clouds[1] ... in their ORIGINAL order, concatenated; global row = the rows of the
+ * clouds before it + the point's index.  poses: 12 doubles per cloud (3x4 ROW-major, what cvo_multiframe_align leaves),
+ * each cast to float and applied as cvo_cloud_transformed applies it (transform_point_pose_vec); NULL: no row is moved at
+ * all (the stored bits: -0.0f and non-finite values survive).  voxel_size == 0: the concatenation; voxel_size > 0: of
+ * every occupied voxel of that side the row with the lowest global index, as cvo_voxel_select chooses over the moved rows.
+ * kept (optional, room for every row): the global indices of the result's points, ascending (0, 1 ... when voxel_size ==
+ * 0); *n_kept (optional): their number.  An attribute is present in the result iff some non-empty input holds it; inputs
+ * without it contribute zeros.
+ * The result is interchangeable with the cloud cvo_cloud_upload_voxel (voxel_size == 0: cvo_cloud_upload) makes of the
+ * same moved, concatenated rows on the host: same spatial order, same one-hot detection, bit-identical results of every
+ * later call.  Everything stays on the device - rows, moved coordinates, kept indices - except what the ordering route of
+ * the result brings down today (cvo_cloud_from_device's rule).  Runs on the upload stream, synchronised on return.  The
+ * inputs are only read; one handle may appear several times.
+ * Refused on the host, before any launch or allocation: CVO_E_INVALID - n_clouds < 1, a NULL handle, a cloud of another
+ * context, a voxel size that is negative or not finite; CVO_E_UNSUPPORTED - n_clouds > 4096, more than 2^24 rows in
+ * total.  Refused by the selection (CVO_E_INVALID), as by cvo_voxel_select: a non-finite moved coordinate or |k| >= 2^20
+ * when voxel_size > 0.  On any error *out is NULL and nothing is kept.  All inputs empty: an empty cloud.
+ * cvo_cloud_download: the cloud's rows in ORIGINAL order, bit for bit what was uploaded (for a cloud of
+ * cvo_cloud_transformed: the moved coordinates): xyz n x 3, feat n x 5, label n x 19, geotype n x 2 floats; any pointer
+ * may be NULL.  *present (optional): CVO_CLOUD_HAS_* bits of the attributes the cloud really holds (0 for an empty cloud);
+ * the others are written as zeros. */
+#define CVO_CLOUD_HAS_FEAT 1
+#define CVO_CLOUD_HAS_LABEL 2
+#define CVO_CLOUD_HAS_GEOTYPE 4
+int cvo_cloud_merge(cvo_ctx* ctx, int n_clouds, const cvo_cloud* const* clouds,
+                    const double* poses /* 12 per cloud, 3x4 row-major, or NULL */, float voxel_size, cvo_cloud** out,
+                    int* kept /* or NULL */, int* n_kept /* or NULL */);
+int cvo_cloud_download(cvo_ctx* ctx, const cvo_cloud* cloud, float* xyz, float* feat, float* label, float* geotype,
+                       int* present);
+
 const char* cvo_version(void);
 
 #ifdef __cplusplus

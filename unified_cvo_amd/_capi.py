@@ -310,6 +310,7 @@ EXPORTED = [
     "cvo_map_open_host", "cvo_map_close_host", "cvo_map_insert_host", "cvo_map_cloud_host", "cvo_debug_map_stats",
     "cvo_cloud_from_device", "cvo_cloud_from_device_many", "cvo_cloud_from_device_aos192",
     "cvo_debug_device_buffer", "cvo_debug_device_release",
+    "cvo_cloud_merge", "cvo_cloud_download",
 ]
 
 _libs = {}
@@ -478,6 +479,8 @@ def lib(path=None):
     L.cvo_cloud_from_device_aos192.argtypes = [vp, ip, vp, C.POINTER(vp)]
     L.cvo_debug_device_buffer.argtypes = [vp, C.c_size_t, vp, C.POINTER(vp)]
     L.cvo_debug_device_release.argtypes = [vp, vp]
+    L.cvo_cloud_merge.argtypes = [vp, ip, C.POINTER(vp), dp, C.c_float, C.POINTER(vp), ipp, ipp]
+    L.cvo_cloud_download.argtypes = [vp, vp, fp, fp, fp, fp, ipp]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

@@ -587,6 +587,21 @@ class DeviceCloud:
         ORDER=wide."""
         return int(self.gpu.L.cvo_debug_cloud_order_route(self.handle))
 
+    def download(self):
+        """cvo_cloud_download: the cloud's rows in ORIGINAL order as a CvoPointCloud, bit for bit what was uploaded.  An
+        attribute the cloud does not hold is left out (features / labels: no columns; geometric types: zeros); `.present`
+        of the result holds the CVO_CLOUD_HAS_* bits (1 features, 2 labels, 4 geometric types)."""
+        n = self.n
+        xyz, feat, label = np.zeros((n, 3), np.float32), np.zeros((n, FEATURE_DIMENSIONS), np.float32), np.zeros((n, NUM_CLASSES), np.float32)
+        geo = np.zeros((n, 2), np.float32)
+        present = C.c_int()
+        self.gpu._check(self.gpu.L.cvo_cloud_download(self.gpu.ctx, self.handle, _fptr(xyz), _fptr(feat), _fptr(label), _fptr(geo),
+                                                      C.byref(present)))
+        has = present.value
+        pc = CvoPointCloud.from_arrays(xyz, feat if has & 1 else None, label if has & 2 else None, geo)
+        pc.present = has
+        return pc
+
     def __del__(self):
         try:
             self.free()
@@ -1327,6 +1342,34 @@ class CvoGPU:
         d = DeviceCloud.__new__(DeviceCloud)
         d.gpu, d.n, d._keep, d.handle = self, int(n), None, handle
         return d
+
+    def merge_clouds(self, clouds, poses=None, voxel_size=0.0, return_kept=False):
+        """cvo_cloud_merge: ONE resident cloud of the rows of `clouds` (DeviceCloud, in original order, cloud after cloud),
+        each moved by its pose - poses: (len(clouds), 12) or (len(clouds), 3, 4) doubles, what multiframe_align_raw returns;
+        None: nothing is moved - and, voxel_size > 0, thinned to the lowest global row of every voxel of that side.  Nothing
+        comes down to the host.  The cloud upload_voxel (voxel_size 0: upload) makes of the same moved, concatenated rows.
+        return_kept: (cloud, global indices of its points) instead of the cloud."""
+        clouds = list(clouds)
+        k = len(clouds)
+        handles = (C.c_void_p * max(k, 1))(*[None if c is None else c.handle for c in clouds])
+        P = None
+        if poses is not None:
+            P = np.ascontiguousarray(np.asarray(poses, np.float64).reshape(-1))
+            if P.shape[0] != 12 * k:
+                raise ValueError("poses: 12 entries per cloud")
+        total = sum(c.n for c in clouds if c is not None)
+        kept = np.zeros(max(total, 1), np.int32) if return_kept else None
+        nk = C.c_int()
+        h = C.c_void_p()
+        self._check(self.L.cvo_cloud_merge(self.ctx, k, handles, None if P is None else P.ctypes.data_as(C.POINTER(C.c_double)),
+                                           float(voxel_size), C.byref(h),
+                                           None if kept is None else kept.ctypes.data_as(C.POINTER(C.c_int)), C.byref(nk)))
+        out = self._adopt(h, nk.value)
+        return (out, kept[:nk.value].copy()) if return_kept else out
+
+    def download(self, cloud):
+        """DeviceCloud.download of a resident cloud."""
+        return cloud.download()
 
     def debug_device_buffer(self, data, into=None):
         """cvo_debug_device_buffer: the bytes of a numpy array in device memory -> the device address; into: an address this

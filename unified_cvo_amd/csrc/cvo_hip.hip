@@ -16,6 +16,7 @@
 //   cvo_frontend.hip  what the front ends below share: scratch regions, the ordered-compaction launcher, the route rule, the entry frame
 //   cvo_ingest.hip  resident clouds from rows that are already in device memory: checks, k_cloud_ingest, the route rule, k_cloud_gather
 //   cvo_voxel.hip   voxel-grid downsampling: selection on the device or the host, upload of the survivors
+//   cvo_merge.hip   resident clouds merged under their poses into one (k_cloud_unpack, then the two sections above) and read back
 //   cvo_rgbd.hip    RGB-D front end: depth + colour frame to candidate points and to a resident cloud
 //   cvo_fast.hip    the CV_FAST point selection: FAST-9/16 scores, the reference's threshold schedule
 //   cvo_stereo.hip  stereo front end: left frame + disparity to candidate points and to a resident cloud
@@ -33,6 +34,7 @@
 #include "cvo_frontend.hip"
 #include "cvo_ingest.hip"
 #include "cvo_voxel.hip"
+#include "cvo_merge.hip"
 #include "cvo_rgbd.hip"
 #include "cvo_fast.hip"
 #include "cvo_stereo.hip"

@@ -1,5 +1,5 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_ingest.hip, cvo_voxel.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip, cvo_bki.hip, cvo_debug.hip) share: the context, a resident cloud, the typed walk that lays
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_ingest.hip, cvo_voxel.hip, cvo_merge.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip, cvo_bki.hip, cvo_debug.hip) share: the context, a resident cloud, the typed walk that lays
 // out EVERY device region (ScratchLayout: a pair's workspace, the front ends' scratch, the map's table, a cloud's slabs, the control block, the score blocks), the owner of
 // EVERY device and pinned allocation (Region: move-only, frees in its destructor, ONE grow rule - drain, free, allocate, tell the caller it moved), graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once
@@ -405,6 +405,9 @@ struct cvo_ctx {
   // clouds from device rows (cvo_ingest.hip): one growable device region - the jobs of k_cloud_ingest / k_cloud_gather and a
   // control block per cloud (flag words + per-block partials), read back with one copy
   DeviceScratch ingest_scratch;
+  // merged and downloaded clouds (cvo_merge.hip): one growable device region - the jobs of k_cloud_unpack and the rows it
+  // writes (coordinates packed, attributes in padded rows), read by the voxel selection, the ingest and the copies down
+  DeviceScratch merge_scratch;
   double clock_ms_per_tick = 0.0;  // s_memrealtime, calibrated on first use (cvo_debug_kernel_clock)
 };
 

@@ -63,6 +63,7 @@
 #include "cvo_k_debug.h"
 #include "cvo_k_cloud.h"
 #include "cvo_k_ingest.h"
+#include "cvo_k_merge.h"
 #include "cvo_k_irls.h"
 #include "cvo_k_prims.h"
 #include "cvo_k_compact.h"
