@@ -133,6 +133,16 @@ int cvo_debug_voxel_stats(cvo_ctx* ctx, unsigned long long* capacity, unsigned l
 int cvo_debug_rgbd_stats(cvo_ctx* ctx, int* n_tried, int* potentials /* 8 */, int* counts /* 8 */,
                          unsigned long long* edge_selected, unsigned long long* edge_points,
                          unsigned long long* surface_points, unsigned long long* with_depth, int* on_device);
+/* What the context's last selection on the device left in its region - a cvo_rgbd_points / cvo_stereo_points(DSO_EDGES) or a
+ * recipe that took the device route; CVO_E_INVALID after a call on the host route, a FULL-only call, any later call that
+ * lays the region out again, or no call -: the frame's shape; counts[6], the pixels selected at the potentials 2 .. 7,
+ * tried by the schedule or not; g2 (rows x cols); ths and sm, the block thresholds and their smoothed squares, each with
+ * all (cols / 32)(rows / 32) + 100 entries; selected: the six selections one after the other (counts[0] + .. + counts[5]
+ * pixel indices v cols + u), each in the order the compaction left it.  Any pointer may be NULL: a first call with the
+ * arrays NULL sizes them.  Tests use it to name the first stage that differs from the statement without
+ * running anything again; the production path launches, copies and waits for nothing on its behalf. */
+int cvo_debug_rgbd_readback(cvo_ctx* ctx, int* rows, int* cols, int* counts /* 6 */, float* g2, float* ths, float* sm,
+                            int* selected);
 /* The context's last cvo_fast_select / cvo_stereo_points / cvo_cloud_upload_stereo / _recipe: the thresholds (CV_FAST) or
  * potentials (DSO_EDGES) the selector's schedule evaluated - *n_tried of them, the first `capacity` written - and the pixels
  * at each; the FAST threshold whose keypoints stand (-1: no FAST selection ran); the 257 pixel counts per FAST score

@@ -63,6 +63,149 @@ def test_points_equal_the_statement(name, depth):
         rc.assert_points_equal(rgbd_points_host(f, method), rc.statement_points(f, method), (name, depth, method))
 
 
+def _bins(name, bx, by):
+    f, s = rc.edge_frame(name), rc.edge_statement(name)
+    return rc.block_bins(s["g2"], f.rows, f.cols, bx, by), s["ths"][bx + by * (f.cols // 32)]
+
+
+def test_the_edge_cases_reach_their_edges():
+    """Each case of rc.EDGE_CASES does, on the statement, what its name says."""
+    st = rc.edge_statement
+    # shapes: the first considered pixel; blocks; 1024 cells at potential 2; the residues of every potential's 4 pot blocks
+    assert not np_rgbd.considered(7, 9).any() and np_rgbd.considered(8, 10).sum() == 1
+    assert [len(st("shape_7x9")["selected"][p]) for p in rc.POTS] == [0] * 6
+    assert [len(st("shape_8x10")["selected"][p]) for p in (3, 2)] == [1, 1]
+    assert st("shape_8x10")["points"][DSO_EDGES]["schedule"] == ([3, 2], [1, 1])
+    assert {r * c for r, c in rc.STRUCTURE_SHAPES} >= {1023, 1024, 1025}
+    for (r, c), blocks in (((31, 31), 0), ((31, 33), 0), ((25, 41), 0), ((32, 32), 1), ((33, 33), 1), ((63, 63), 1), ((64, 64), 4), ((65, 65), 4)):
+        assert (r // 32) * (c // 32) == blocks and np.count_nonzero(st("shape_%dx%d" % (r, c))["ths"]) == blocks
+    cells2 = {s: -(-s[0] // 2) * -(-s[1] // 2) for s in ((64, 64), (64, 65), (65, 64))}
+    assert cells2 == {(64, 64): 1024, (64, 65): 1024 + 32, (65, 64): 1024 + 32}
+    for pot in rc.POTS:
+        for axis in (0, 1):
+            assert {s[axis] % (4 * pot) for s in rc.RESIDUE_SHAPES} >= {0, 1, 4 * pot - 1}, (pot, axis)
+    for name in rc.EDGE_CASES:
+        f = rc.edge_frame(name)
+        assert f.rows * f.cols <= 36 * 3205 and (name == "shape_36x3205" or max(f.rows, f.cols) <= 130), name
+    # the threshold index: the next block row's first entry, the zero slack, and its last entry
+    for (r, c), reach in (((63, 63), 2), ((33, 63), 1), ((64, 95), 4), ((95, 64), 5), ((36, 3205), 199)):
+        idx = np_rgbd.threshold_index(r, c)[np_rgbd.considered(r, c)]
+        assert idx.max() == reach and reach >= (r // 32) * (c // 32) and reach < len(st("shape_%dx%d" % (r, c))["sm"]), (r, c)
+    idx = np_rgbd.threshold_index(64, 95)[np_rgbd.considered(64, 95)]
+    assert np.any(idx == 2) and 95 // 32 == 2  # block column 2 of 2 in block row 0: the next block row's first entry
+    assert len(st("shape_36x3205")["sm"]) == 200 and np.all(st("shape_36x3205")["sm"][100:] == 0)
+    idx = np_rgbd.threshold_index(*rc.WIDE_REFUSED)[np_rgbd.considered(*rc.WIDE_REFUSED)]
+    assert idx.max() == 200
+    # histogram and quantile
+    bins, th = _bins("hist_flat", 1, 1)
+    assert bins[0] == 1024 and th == 7 and np.all(st("hist_flat")["sm"][:9] == 49)
+    bins, th = _bins("hist_cap", 1, 1)
+    g2 = st("hist_cap")["g2"][32:64, 32:64]
+    assert np.all(np.sqrt(g2).astype(np.int64) == 127) and bins[48] == 1024 and th == 55
+    bins, th = _bins("hist_47_48_49", 1, 1)
+    roots = np.sqrt(st("hist_47_48_49")["g2"][32:64, 32:64]).astype(np.int64)
+    assert [np.count_nonzero(roots == r) for r in (47, 48, 49)] == [256, 128, 640] and roots.min() == 47
+    assert bins[47] == 256 and bins[48] == 768 and th == 48 + 7
+    for name, extra, q in (("quantile_at", 0, 5), ("quantile_above", 1, 0)):
+        for (bx, by), count in (((1, 1), 1024), ((1, 0), 992), ((2, 2), 961)):
+            bins, th = _bins(name, bx, by)
+            t = int(np.float32(count) * np.float32(0.5) + np.float32(0.5))
+            assert bins.sum() == count and bins[0] == t + extra and bins[5] == count - t - extra and th == q + 7, (name, bx, by, bins[:6])
+    roots = np.minimum(np.sqrt(st("hist_wave_ramp")["g2"][32:64, 32:64]).astype(np.int64), 48)
+    assert all(len(np.unique(roots[2 * k:2 * k + 2])) >= 40 for k in range(16))
+    ths = st("smooth_3x3")["ths"][:9]
+    assert len(np.unique(ths)) == 9
+    sm = st("smooth_3x3")["sm"][:9].reshape(3, 3)
+    t = ths.reshape(3, 3).astype(np.float64)
+    square = lambda total, n: np.float32(total / n) * np.float32(total / n)  # noqa: E731
+    assert sm[0, 0] == square(t[:2, :2].sum(), 4) and sm[0, 1] == square(t[:2].sum(), 6) and sm[1, 1] == square(t.sum(), 9)
+    # selection rules: the tie ...
+    s = st("sel_tie")
+    g2, w = s["g2"].reshape(-1), 96
+    for pot in rc.POTS:
+        tied = 0
+        sel = set(s["selected"][pot].tolist())
+        for y, x in rc.TIE_POKES:
+            plus = [(y - 1) * w + x, y * w + x - 1, y * w + x + 1, (y + 1) * w + x]  # (row-major order)
+            assert all(g2[p] == 900 for p in plus)
+            cells = {}
+            for p in plus:
+                cells.setdefault((p // w // pot, p % w // pot), []).append(p)
+            for members in cells.values():
+                assert members[0] in sel and not sel & set(members[1:]), (pot, y, x)
+                tied += len(members) > 1
+        assert tied >= 10, pot
+    # ... the threshold itself ...
+    s = st("sel_threshold")
+    (ye, xe), (ya, xa) = rc.THRESHOLD_EQUAL, rc.THRESHOLD_ABOVE
+    assert s["g2"][ye, xe] == s["sm"][np_rgbd.threshold_index(64, 64)[ye, xe]] == 49 and s["g2"][ya, xa] == 49.25
+    for pot in rc.POTS:
+        assert ye * 64 + xe not in s["selected"][pot] and ya * 64 + xa in s["selected"][pot]
+    # ... the considered region ...
+    s = st("sel_border")
+    h, w = rc.BORDER_SHAPE
+    for targets in rc.border_targets():
+        assert [c for _, _, c in targets] == [False, True, True, False]
+        for y, x, is_considered in targets:
+            assert s["g2"][y, x] == 3600 and np_rgbd.considered(h, w)[y, x] == is_considered
+            for pot in rc.POTS:
+                assert (y * w + x in s["selected"][pot]) == is_considered, (y, x, pot)
+    # ... perfect squares in a histogrammed block, and gray levels on the rounding boundary
+    g2 = st("sel_squares")["g2"]
+    assert np.count_nonzero(g2[1:63, 1:63] == 25.0) > 0 and np.count_nonzero(g2[1:63, 1:63] == 169.0) > 0
+    reached, missed = rc.bgr_boundary_triples()
+    for trip, rem in ((reached, 0), (missed, (1 << 14) - 1)):
+        assert len(trip) > 100 and np.all((1868 * trip[:, 0] + 9617 * trip[:, 1] + 4899 * trip[:, 2] + 8192) % (1 << 14) == rem)
+    f = rc.edge_frame("bgr_rounding")
+    px = f.image.reshape(-1, 3).astype(np.int64)
+    rem = (1868 * px[:, 0] + 9617 * px[:, 1] + 4899 * px[:, 2] + 8192) % (1 << 14)
+    assert f.channels == 3 and np.all((rem == 0) | (rem == (1 << 14) - 1)) and 400 < np.count_nonzero(rem == 0) < 1200
+    # depth: every special value is met by both methods; a NaN coordinate comes from u == cx under an infinite depth
+    for name, values in (("depth_f32", rc.DEPTH_F32), ("depth_u16", rc.DEPTH_U16)):
+        f = rc.edge_frame(name)
+        uv = st(name)["selected"][st(name)["points"][DSO_EDGES]["schedule"][0][-1]]
+        for v in values:
+            same = f.depth == v
+            if f.depth.dtype == np.float32:
+                same = np.isnan(f.depth) if np.isnan(v) else same & (np.signbit(f.depth) == np.signbit(v))
+            assert same.any() and same.reshape(-1)[uv].any(), (name, v)
+    p = st("depth_f32")["points"][FULL]
+    nan = np.isnan(p["xyz"])
+    assert nan[:, 0].any() and np.all(p["pixel"][nan[:, 0]] % 48 == 12) and np.all(np.isinf(p["xyz"][nan[:, 0], 2])) and not nan[:, 2].any()
+    kept = rc.edge_frame("depth_f32").depth.reshape(-1)[p["pixel"]]
+    assert np.any(kept == np.float32(1e-45)) and np.any(kept == -1.5) and not np.any(kept == 0)
+
+
+def test_first_difference_names_the_stage_and_the_index():
+    want = rc.edge_statement("shape_33x33")
+    back = dict(g2=want["g2"].copy(), ths=want["ths"].copy(), sm=want["sm"].copy(), selected={p: v.copy() for p, v in want["selected"].items()})
+    assert rc.first_difference(back, want) is None
+    back["selected"][6] = back["selected"][6][:-1]
+    assert "potential 6: %d entries for %d" % (len(back["selected"][6]), len(want["selected"][6])) in rc.first_difference(back, want)
+    back["selected"][4][3] += 1
+    assert "potential 4: 1 entries differ, first at 3" in rc.first_difference(back, want)
+    back["sm"][100] = 1.0  # (the last slack entry of 1 + 100)
+    assert "stage sm: 1 entries differ, first at 100: 1.0 for 0.0" in rc.first_difference(back, want)
+    back["g2"][2, 5] += 0.25
+    assert "stage g2: 1 entries differ, first at %d" % (2 * 33 + 5) in rc.first_difference(back, want)
+
+
+@pytest.mark.parametrize("name", list(rc.EDGE_CASES))
+def test_twin_equals_the_statement_on_the_edge_cases(name):
+    f = rc.edge_frame(name)
+    for method in (DSO_EDGES, FULL):
+        rc.assert_points_equal(rgbd_points_host(f, method), rc.edge_statement(name)["points"][method], (name, method), name in rc.NAN_COORDINATES)
+
+
+def test_the_widest_accepted_image_and_the_first_refused_one():
+    f = rc.refused_frame()
+    assert (f.rows, f.cols) == rc.WIDE_REFUSED
+    with pytest.raises(np_rgbd.Unsupported):
+        np_rgbd.dso_select(np_rgbd.gray_plane(f.image))
+    assert _raw_call(f.c_struct(), DSO_EDGES) == _capi.CVO_E_UNSUPPORTED
+    rc.assert_points_equal(rgbd_points_host(f, FULL), rc.statement_points(f, FULL), "refused, FULL")
+
+
 def test_caller_gray_plane_overrides_the_formula():
     f = rc.own_gray(rc.frame("small"))
     got = rgbd_points_host(f, DSO_EDGES)

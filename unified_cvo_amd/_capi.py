@@ -296,6 +296,7 @@ EXPORTED = [
     "cvo_multiframe_align", "cvo_debug_irls_normal", "cvo_debug_irls_eval", "cvo_debug_irls_gather",
     "cvo_voxel_select", "cvo_voxel_select_host", "cvo_cloud_upload_voxel", "cvo_debug_voxel_stats",
     "cvo_rgbd_points", "cvo_rgbd_points_host", "cvo_cloud_upload_rgbd", "cvo_debug_rgbd_stats",
+    "cvo_debug_rgbd_readback",
     "cvo_fast_select", "cvo_fast_select_host", "cvo_stereo_points", "cvo_stereo_points_host", "cvo_cloud_upload_stereo",
     "cvo_cloud_upload_stereo_recipe", "cvo_debug_stereo_stats",
     "cvo_lidar_config_default", "cvo_lidar_config_derive", "cvo_lidar_rand_seed", "cvo_lidar_rand_next", "cvo_lidar_select", "cvo_lidar_select_host",
@@ -410,6 +411,7 @@ def lib(path=None):
     L.cvo_rgbd_points_host.argtypes = [fr, ip, ipp, ipp, fp, fp, fp, fp]
     L.cvo_cloud_upload_rgbd.argtypes = [vp, fr, C.c_float, C.c_float, C.POINTER(vp), ipp, C.POINTER(C.c_ubyte), ipp]
     L.cvo_debug_rgbd_stats.argtypes = [vp, ipp, ipp, ipp] + [C.POINTER(C.c_ulonglong)] * 4 + [ipp]
+    L.cvo_debug_rgbd_readback.argtypes = [vp, ipp, ipp, ipp, fp, fp, fp, ipp]
     sched, sf, up = C.POINTER(cvo_fast_schedule_t), C.POINTER(cvo_stereo_frame_t), C.POINTER(C.c_ubyte)
     L.cvo_fast_select.argtypes = [vp, ip, ip, up, sched, ipp, ipp, ipp]
     L.cvo_fast_select_host.argtypes = [ip, ip, up, sched, ipp, ipp, ipp]

@@ -1074,6 +1074,20 @@ class CvoGPU:
         out.update(potentials=list(pots[:nt.value]), counts=list(cnts[:nt.value]), on_device=bool(dev.value))
         return out
 
+    def debug_rgbd_readback(self):
+        """cvo_debug_rgbd_readback: the stages of the last selection that ran on the device (rgbd_points / stereo_points with
+        DSO_EDGES, upload_rgbd, upload_stereo_recipe) -> dict(g2 (rows, cols) float32; ths, sm: all (cols // 32)(rows // 32)
+        + 100 entries; selected: {potential: pixel indices in the compaction's order} for the potentials 2 .. 7)."""
+        rows, cols, counts = C.c_int(), C.c_int(), (C.c_int * 6)()
+        self._check(self.L.cvo_debug_rgbd_readback(self.ctx, C.byref(rows), C.byref(cols), counts, None, None, None, None))
+        h, w, counts = rows.value, cols.value, list(counts)
+        n_ths = (w // 32) * (h // 32) + 100
+        g2, ths, sm = np.zeros((h, w), np.float32), np.zeros(n_ths, np.float32), np.zeros(n_ths, np.float32)
+        sel = np.zeros(max(sum(counts), 1), np.int32)
+        self._check(self.L.cvo_debug_rgbd_readback(self.ctx, None, None, None, _fptr(g2), _fptr(ths), _fptr(sm), sel.ctypes.data_as(C.POINTER(C.c_int))))
+        at = np.concatenate([[0], np.cumsum(counts)])
+        return dict(g2=g2, ths=ths, sm=sm, selected={2 + k: sel[at[k]:at[k + 1]].copy() for k in range(6)})
+
     def fast_select(self, gray, schedule=FAST_STEREO):
         """cvo_fast_select: as fast_select_host, by the context's route (switch STEREO_HOST)."""
         rc, pixel, used = _fast_select(lambda *a: self.L.cvo_fast_select(self.ctx, *a), gray, schedule)

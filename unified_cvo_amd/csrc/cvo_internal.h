@@ -132,6 +132,18 @@ struct RgbdStatsAcc {
   int on_device = 0;
 };
 
+// where cvo_debug_rgbd_readback finds the stages of the context's last selection on the device (rgbd_device_select, cvo_rgbd.hip):
+// host-side facts only.  The stages stay in rgbd_scratch until the region is laid out again (rgbd_device_stage), which ends
+// `valid`, as does an RGB-D call on the host route.
+struct RgbdSelectionAcc {
+  bool valid = false;
+  int w = 0, h = 0;
+  RgbdCells cells{};
+  std::vector<unsigned> sel_offset;  // exclusive offsets of the selection's blocks, the total last
+  const float *g2 = nullptr, *ths = nullptr, *sm = nullptr;
+  const int* sel = nullptr;
+};
+
 // what cvo_debug_stereo_stats reports of the context's last stereo / FAST call (cvo_fast.hip, cvo_stereo.hip)
 struct StereoStatsAcc {
   std::vector<int> tried, count;  // the selector's schedule: FAST thresholds (CV_FAST) or potentials (DSO_EDGES) tried, pixels at each
@@ -383,6 +395,7 @@ struct cvo_ctx {
   DeviceScratch rgbd_scratch;
   std::vector<unsigned char> rgbd_excl;  // staging of the exclusion bytes of a semantic frame
   RgbdStatsAcc rgbd_last{};
+  RgbdSelectionAcc rgbd_sel{};
   StereoStatsAcc stereo_last{};  // (the stereo front end and cvo_fast_select share the RGB-D region)
   // LiDAR front end (cvo_lidar.hip): one growable device region - the scan, the range image's per-cell arrays, the
   // segmented cloud's arrays, the picks

@@ -1,6 +1,7 @@
 // cvo_rgbd.hip -- RGB-D front end: cvo_rgbd_points (CvoPointCloud(ImageRGBD, Calibration, FULL / DSO_EDGES)),
 // cvo_rgbd_points_host (the same on one CPU thread, no context), cvo_cloud_upload_rgbd (the multi-frame drivers' per-frame
-// recipe: both candidate sets, voxel selection, edge rows then surface rows, the ordinary upload), cvo_debug_rgbd_stats.
+// recipe: both candidate sets, voxel selection, edge rows then surface rows, the ordinary upload), cvo_debug_rgbd_stats,
+// cvo_debug_rgbd_readback (the stages of the last selection on the device, for the tests).
 // On the device (kernels of cvo_k_rgbd.h on upload_stream, under upload_mutex) only pixels, depth and an exclusion byte
 // go up and only pixel indices come back; the survivors' rows are built on the host, as the voxel path does.
 // A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.
@@ -254,6 +255,7 @@ struct RgbdDevice {
 // (need_fast: room for the FAST detector's score bytes and histogram as well; a frame without a depth image copies none)
 int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select, RgbdDevice& d, bool need_fast = false) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->rgbd_sel.valid = false;  // (the region is about to be laid out anew: the last selection's stages end here)
   const int w = f.cols, h = f.rows;
   const size_t np = (size_t)w * h;
   d.w = w;
@@ -330,6 +332,16 @@ int rgbd_device_select(cvo_ctx* ctx, RgbdDevice& d, RgbdStatsAcc& stats, const i
   *list = d.sel + first(pot);
   *n = count(pot);
   if (*n < 0 || *n > rgbd_cells(pot, w, h)) return fail(ctx, CVO_E_HIP, "RGB-D selection: the device selected more pixels than there are cells");
+  RgbdSelectionAcc& s = ctx->rgbd_sel;  // (for cvo_debug_rgbd_readback: nothing is launched or copied for it)
+  s.w = w;
+  s.h = h;
+  s.cells = d.cells;
+  s.sel_offset = d.sel_offset;
+  s.g2 = d.g2;
+  s.ths = d.ths;
+  s.sm = d.sm;
+  s.sel = d.sel;
+  s.valid = true;
   return CVO_OK;
 }
 
@@ -465,6 +477,12 @@ int rgbd_recipe_pixels(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t& f,
       });
 }
 
+// a successful RGB-D call's last statement: its stats stand, and one that took the host route leaves no stages to read back
+void rgbd_commit(cvo_ctx* ctx, const RgbdStatsAcc& st) {
+  ctx->rgbd_last = st;
+  if (!st.on_device) ctx->rgbd_sel.valid = false;
+}
+
 // the body of cvo_rgbd_points_host and cvo_rgbd_points
 int rgbd_points_entry(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t* frame, int method, int* pixel, int* n, float* xyz, float* feat,
                       float* label, float* geotype) {
@@ -489,7 +507,7 @@ int rgbd_points_entry(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t* fra
     }
     rgbd_point_rows(*frame, method, pix, xyz, feat, label, geotype);
     copy_kept(pix, pixel, n);
-    if (ctx) ctx->rgbd_last = st;
+    if (ctx) rgbd_commit(ctx, st);
     return CVO_OK;
   });
 }
@@ -539,7 +557,7 @@ int cvo_cloud_upload_rgbd(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, float lea
     const HostCloud h{(int)np, (const char*)xyz.data(), 12, (const char*)feat.data(), sizeof(float) * FD, nullptr, 0, (const char*)geo.data(), 8};
     if ((rc = upload_one_locked(ctx, h, out)) != CVO_OK) return rc;
     copy_kept(pix, pixel, n, is_edge, n_edge);
-    ctx->rgbd_last = st;
+    rgbd_commit(ctx, st);
     return CVO_OK;
   });
 }
@@ -559,6 +577,27 @@ int cvo_debug_rgbd_stats(cvo_ctx* ctx, int* n_tried, int* potentials, int* count
   if (surface_points) *surface_points = s.surface_points;
   if (with_depth) *with_depth = s.with_depth;
   if (on_device) *on_device = s.on_device;
+  return CVO_OK;
+}
+
+int cvo_debug_rgbd_readback(cvo_ctx* ctx, int* rows, int* cols, int* counts, float* g2, float* ths, float* sm, int* selected) {
+  if (!ctx) return CVO_E_INVALID;
+  std::lock_guard<std::mutex> lk(ctx->upload_mutex);
+  const RgbdSelectionAcc& s = ctx->rgbd_sel;
+  if (!s.valid || !ctx->rgbd_scratch.p)
+    return fail(ctx, CVO_E_INVALID, "cvo_debug_rgbd_readback: the context's last RGB-D call ran no selection on the device");
+  if (rows) *rows = s.h;
+  if (cols) *cols = s.w;
+  auto first = [&](int k) { return s.sel_offset[(size_t)s.cells.start[k] / RGBD_THREADS]; };
+  for (int k = 0; counts && k < RGBD_POTS; k++) counts[k] = (int)(first(k + 1) - first(k));
+  hipStream_t st = ctx->upload_stream;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t np = (size_t)s.w * s.h, n_ths = (size_t)(s.w / 32) * (s.h / 32) + RGBD_THS_SLACK, n_sel = first(RGBD_POTS);
+  if (g2) HIP_TRY(ctx, hipMemcpyAsync(g2, s.g2, sizeof(float) * np, hipMemcpyDeviceToHost, st));
+  if (ths) HIP_TRY(ctx, hipMemcpyAsync(ths, s.ths, sizeof(float) * n_ths, hipMemcpyDeviceToHost, st));
+  if (sm) HIP_TRY(ctx, hipMemcpyAsync(sm, s.sm, sizeof(float) * n_ths, hipMemcpyDeviceToHost, st));
+  if (selected && n_sel) HIP_TRY(ctx, hipMemcpyAsync(selected, s.sel, sizeof(int) * n_sel, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
   return CVO_OK;
 }
 
