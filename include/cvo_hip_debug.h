@@ -95,6 +95,12 @@ int cvo_debug_wide_plan(int n, int* W, int* rows /* level, lo, hi, left */, int 
  * (1, 0, 1) for an inner product no row voids, (3, 0, 1) for an exact function_angle of two distinct clouds.  A call that
  * returns before any device work (a single call with an empty cloud) leaves the previous values.  Any pointer may be NULL. */
 int cvo_debug_last_score_batch(const cvo_ctx* ctx, int* overlap_evals, int* chain_evals, int* launches);
+/* The tile records every cull of k_overlap trusts (k_tile_spheres): for each 64 consecutive sorted positions of a resident
+ * cloud, out[8 t .. 8 t + 7] = centre x, y, z, radius, box half extents x, y, z, 0; *n_tiles = ceil(n / 64).  `out` holds
+ * 8 floats per tile.  The records are made on the stream of the scores when no score has read the cloud yet, and kept: a
+ * score before the call equals the score after it.  CVO_E_INVALID for a null pointer, an empty cloud, a cloud of another
+ * context. */
+int cvo_debug_cloud_tiles(cvo_ctx* ctx, const cvo_cloud* cloud, float* out /* n_tiles x 8 */, int* n_tiles);
 /* Free / total bytes of the context's device (hipMemGetInfo), for leak checks without a second HIP runtime in the process. */
 int cvo_debug_device_memory(cvo_ctx* ctx, size_t* free_bytes, size_t* total_bytes);
 /* Device arrays for the tests of cvo_cloud_from_device, without a second HIP runtime in the process.  *d == NULL: allocates

@@ -292,7 +292,7 @@ EXPORTED = [
     "cvo_debug_cloud_order_route", "cvo_debug_order_route_rule", "cvo_debug_wide_plan",
     "cvo_process_hint_hw_queues", "cvo_shutdown",
     "cvo_batch_open", "cvo_batch_submit", "cvo_batch_poll", "cvo_batch_pending", "cvo_batch_stats", "cvo_batch_close",
-    "cvo_inner_product_batch", "cvo_function_angle_batch", "cvo_debug_last_score_batch",
+    "cvo_inner_product_batch", "cvo_function_angle_batch", "cvo_debug_last_score_batch", "cvo_debug_cloud_tiles",
     "cvo_multiframe_align", "cvo_debug_irls_normal", "cvo_debug_irls_eval", "cvo_debug_irls_gather",
     "cvo_voxel_select", "cvo_voxel_select_host", "cvo_cloud_upload_voxel", "cvo_debug_voxel_stats",
     "cvo_rgbd_points", "cvo_rgbd_points_host", "cvo_cloud_upload_rgbd", "cvo_debug_rgbd_stats",
@@ -392,6 +392,7 @@ def lib(path=None):
     L.cvo_debug_device_memory.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     L.cvo_debug_cloud_order.argtypes = [vp, C.POINTER(C.c_int)]
     L.cvo_debug_cloud_order_route.argtypes = [vp]
+    L.cvo_debug_cloud_tiles.argtypes = [vp, vp, fp, C.POINTER(C.c_int)]
     L.cvo_debug_order_route_rule.argtypes = [ip, ip, C.c_char_p, ip]
     L.cvo_debug_wide_plan.argtypes = [ip, C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int)]
     dp = C.POINTER(C.c_double)

@@ -587,6 +587,14 @@ class DeviceCloud:
         ORDER=wide."""
         return int(self.gpu.L.cvo_debug_cloud_order_route(self.handle))
 
+    def debug_tiles(self):
+        """cvo_debug_cloud_tiles: the records k_overlap culls by, float32[ceil(n / 64), 8] - centre x, y, z, radius, box half
+        extents x, y, z, 0 of every 64 consecutive sorted positions (debug_order() says which points those are)."""
+        out = np.zeros(((self.n + 63) // 64 or 1, 8), np.float32)
+        nt = C.c_int()
+        self.gpu._check(self.gpu.L.cvo_debug_cloud_tiles(self.gpu.ctx, self.handle, _fptr(out), C.byref(nt)))
+        return out[:nt.value]
+
     def download(self):
         """cvo_cloud_download: the cloud's rows in ORIGINAL order as a CvoPointCloud, bit for bit what was uploaded.  An
         attribute the cloud does not hold is left out (features / labels: no columns; geometric types: zeros); `.present`

@@ -169,6 +169,22 @@ int cvo_debug_last_score_batch(const cvo_ctx* ctx, int* overlap_evals, int* chai
   return CVO_OK;
 }
 
+int cvo_debug_cloud_tiles(cvo_ctx* ctx, const cvo_cloud* cloud, float* out, int* n_tiles) {
+  const char* who = "cvo_debug_cloud_tiles";
+  if (!ctx || !cloud || !out || !n_tiles) return fail(ctx, CVO_E_INVALID, std::string(who) + ": bad argument");
+  if (cloud->ctx != ctx) return fail(ctx, CVO_E_INVALID, std::string(who) + ": the cloud belongs to another context");
+  if (cloud->n <= 0) return fail(ctx, CVO_E_INVALID, std::string(who) + ": empty cloud");
+  if (ctx->queue_open) return fail(ctx, CVO_E_INVALID, "a batch queue is open on this context (cvo_batch_close it first)");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  // the records the scores read: made here, on their stream, when no score has read this cloud yet - and kept
+  if (const int rc = ensure_tiles(ctx, cloud, ctx->stream); rc != CVO_OK) return rc;
+  const int nt = (cloud->n + 63) / 64;
+  HIP_TRY(ctx, hipMemcpyAsync(out, cloud->tile4, sizeof(float4) * 2 * (size_t)nt, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  *n_tiles = nt;
+  return CVO_OK;
+}
+
 int cvo_debug_verified_rows(cvo_ctx* ctx, unsigned long long* rows) {
   if (!ctx || !rows || ctx->last_pairs < 1) return fail(ctx, CVO_E_INVALID, "cvo_debug_verified_rows: bad argument");
   unsigned long long t = 0;
