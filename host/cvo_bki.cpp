@@ -19,6 +19,21 @@ cvo_map* CvoGPU::map_open(const cvo_map_config_t& cfg, long long initial_voxels)
 
 std::string CvoGPU::last_error() const { return cvo_last_error(ctx); }
 
+void CvoGPU::map_insert_cloud(cvo_map* map, const ResidentClouds& clouds, int k, const float* pose12, const float* origin) const {
+  if (k < 0 || k >= clouds.size()) throw std::invalid_argument("map_insert_cloud: no such cloud");
+  std::lock_guard<std::mutex> lk(call_mutex);
+  if (cvo_map_insert_cloud(map, clouds.handles[(size_t)k], pose12, origin) != CVO_OK) throw std::invalid_argument(cvo_last_error(ctx));
+}
+
+std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::map_resident_cloud(cvo_map* map) const {
+  std::lock_guard<std::mutex> lk(call_mutex);
+  std::unique_ptr<ResidentClouds> out(new ResidentClouds());
+  out->handles.assign(1, nullptr);
+  out->kept_.resize(1);
+  if (cvo_map_cloud_resident(map, out->handles.data(), nullptr) != CVO_OK) throw std::invalid_argument(cvo_last_error(ctx));
+  return out;
+}
+
 CvoPointCloud::CvoPointCloud(const semantic_bki::SemanticBKIOctoMap* map, const int num_classes) {
   if (!map || num_classes != map->num_classes()) throw std::invalid_argument("CvoPointCloud(map, num_classes): the map has another number of classes");
   num_classes_ = num_classes;
@@ -76,8 +91,8 @@ SemanticBKIOctoMap::~SemanticBKIOctoMap() {
   if (map_) cvo_map_close(map_);
 }
 
-void SemanticBKIOctoMap::insert_pointcloud_csm(const CVOPointCloud* cloud, const point3f& origin, float ds_resolution, float free_res, float max_range) {
-  if (!cloud) throw std::invalid_argument("insert_pointcloud_csm: no cloud");
+// the first insert opens the map with its free_res and max_range; a later one must name the same
+void SemanticBKIOctoMap::open_or_check(float ds_resolution, float free_res, float max_range) {
   if (!map_) {
     cfg_.ds_resolution = ds_resolution;
     cfg_.free_resolution = free_res;
@@ -90,6 +105,32 @@ void SemanticBKIOctoMap::insert_pointcloud_csm(const CVOPointCloud* cloud, const
   } else if (free_res != cfg_.free_resolution || max_range != cfg_.max_range) {
     throw std::invalid_argument("insert_pointcloud_csm: free_res and max_range are fixed by the map's first insert");
   }
+}
+
+void SemanticBKIOctoMap::insert_pointcloud_csm(const cvo::CvoGPU::ResidentClouds& clouds, int k, const float pose12[12], float ds_resolution,
+                                               float free_res, float max_range) {
+  if (!gpu_) throw std::invalid_argument("insert_pointcloud_csm: a map of the CPU twin takes host clouds");
+  if (!pose12) throw std::invalid_argument("insert_pointcloud_csm: no pose");
+  open_or_check(ds_resolution, free_res, max_range);
+  try {
+    gpu_->map_insert_cloud(map_, clouds, k, pose12, nullptr);
+  } catch (const std::invalid_argument& e) {
+    throw std::invalid_argument(std::string("insert_pointcloud_csm: ") + e.what());
+  }
+}
+
+std::unique_ptr<cvo::CvoGPU::ResidentClouds> SemanticBKIOctoMap::resident_cloud() const {
+  if (!gpu_) throw std::invalid_argument("resident_cloud: a map of the CPU twin has no resident cloud");
+  if (!map_) {  // (nothing inserted yet: the upload of no rows)
+    const cvo::CvoPointCloud none(5, cfg_.num_classes);
+    return gpu_->upload_clouds({&none});
+  }
+  return gpu_->map_resident_cloud(map_);
+}
+
+void SemanticBKIOctoMap::insert_pointcloud_csm(const CVOPointCloud* cloud, const point3f& origin, float ds_resolution, float free_res, float max_range) {
+  if (!cloud) throw std::invalid_argument("insert_pointcloud_csm: no cloud");
+  open_or_check(ds_resolution, free_res, max_range);
   const int n = cloud->num_points(), C = cfg_.num_classes;
   if (C > 0 && cloud->num_classes() != C) throw std::invalid_argument("insert_pointcloud_csm: the cloud's label rows do not have the map's classes");
   std::vector<float> xyz(3 * (size_t)n), feat, label((size_t)C * n);

@@ -219,6 +219,12 @@ class CvoGPU {
   // names).  The caller closes it with cvo_map_close before this object goes.  Refusals throw std::invalid_argument.  last_error:
   // cvo_last_error of the context.  Defined in host/cvo_bki.cpp.
   cvo_map* map_open(const cvo_map_config_t& cfg, long long initial_voxels = 0) const;
+  // New: the map's two calls that keep every cloud on the device (cvo_map_insert_cloud / cvo_map_cloud_resident; SemanticBKIOctoMap's
+  // insert_pointcloud_csm(const ResidentClouds&, ...) and resident_cloud() are these): cloud k of `clouds` as the hits of one insert,
+  // moved by pose12 (nullptr: as stored) and seen from origin (nullptr: the pose's translation); the occupied voxels as one
+  // resident cloud.  Refusals throw std::invalid_argument.
+  void map_insert_cloud(cvo_map* map, const ResidentClouds& clouds, int k, const float* pose12, const float* origin) const;
+  std::unique_ptr<ResidentClouds> map_resident_cloud(cvo_map* map) const;
   std::string last_error() const;
 
  private:

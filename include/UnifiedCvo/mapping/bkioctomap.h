@@ -5,14 +5,12 @@
 //   cvo::CvoPointCloud cloud_out(&map, num_class);
 // block_depth 1 only (std::invalid_argument otherwise); tests/np_bki.py states what is computed.  Defined in host/cvo_bki.cpp.
 #pragma once
+#include <memory>
 #include <ostream>
 
+#include "cvo/CvoGPU.hpp"
 #include "cvo_hip.h"
 #include "utils/CvoPointCloud.hpp"
-
-namespace cvo {
-class CvoGPU;
-}
 
 namespace semantic_bki {
 
@@ -53,6 +51,14 @@ class SemanticBKIOctoMap {
   // later insert with other values throws std::invalid_argument, as does anything the library refuses.  ds_resolution is
   // accepted and unused, as upstream.
   void insert_pointcloud_csm(const CVOPointCloud* cloud, const point3f& origin, float ds_resolution, float free_res, float max_range);
+  // New: cloud k of `clouds`, resident on the map's context, as the hits of one insert without a host copy
+  // (cvo_map_insert_cloud): its rows in original order, moved by pose12 (3x4 row-major, what align() leaves) and seen from the
+  // pose's translation.  The first insert fixes free_res and max_range, as above.  A map of the CPU twin throws.
+  void insert_pointcloud_csm(const cvo::CvoGPU::ResidentClouds& clouds, int k, const float pose12[12], float ds_resolution, float free_res,
+                             float max_range);
+  // New: the occupied voxels as one resident cloud built on the device (cvo_map_cloud_resident), to align the next frame
+  // against; what CvoPointCloud(&map, num_classes) uploaded would be.  Before the first insert: an empty cloud.
+  std::unique_ptr<cvo::CvoGPU::ResidentClouds> resident_cloud() const;
 
   float get_resolution() const { return cfg_.resolution; }
   int num_classes() const { return cfg_.num_classes; }  // of a label row
@@ -63,6 +69,7 @@ class SemanticBKIOctoMap {
   const cvo::CvoGPU* gpu_ = nullptr;
   cvo_map_config_t cfg_;
   cvo_map* map_ = nullptr;
+  void open_or_check(float ds_resolution, float free_res, float max_range);
 };
 
 }  // namespace semantic_bki

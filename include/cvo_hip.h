@@ -569,6 +569,27 @@ int cvo_map_size(cvo_map* map, long long* voxels, long long* occupied);   /* eit
  * when capacity >= *n (CVO_E_INVALID otherwise, *n set).  resident != NULL: the cloud cvo_cloud_upload makes of exactly those
  * rows (label rows of fewer than 19 classes followed by zeros), to align a new frame against. */
 int cvo_map_cloud(cvo_map* map, long long capacity, float* xyz, float* feat, float* label, long long* n, cvo_cloud** resident);
+/* A resident cloud in, a resident cloud out: on a map of the device side no row of either passes through the host.
+ * The rows of a resident cloud, in ORIGINAL order, as the hits of one insert.
+ * pose12 (3x4 row-major float, or NULL): the rows moved as cvo_cloud_transformed moves them
+ *   (transform_point_pose_vec).  NULL: the stored bits, nothing is multiplied.
+ * origin (3 floats, or NULL): NULL means the pose's translation, as cvo_map_insert_posed.
+ *   pose12 == NULL && origin == NULL is refused.
+ * The map is afterwards bit for bit what cvo_map_insert_posed (a pose, no origin) or cvo_map_insert of the moved rows leaves
+ * when given the rows cvo_cloud_download returns: a hit's label row is the first num_classes of the cloud's 19 columns, a
+ * cloud that holds no features inserts as feat == NULL does, n == 0 inserts the origin alone.  The hits are staged on the
+ * device (k_bki_stage); the side rule is the map's: an undecided map with BKI_HOST unset takes the host side when the device
+ * counts fewer than 2129 training points, and a map of the host side has the staged rows copied down for the twin.
+ * Refusals leave the map as it was, cvo_last_error begins "cvo_map_insert_cloud:".  CVO_E_INVALID: a NULL handle, a map of
+ * cvo_map_open_host, a cloud of another context, both pointers NULL, a pose or origin that is not finite, a moved coordinate
+ * that is not finite (the text names the hit), label rows missing on a map with classes, a block index outside
+ * [1, 2^20 - 2]; CVO_E_UNSUPPORTED: as cvo_map_insert. */
+int cvo_map_insert_cloud(cvo_map* map, const cvo_cloud* cloud, const float pose12[12], const float origin[3]);
+/* The OCCUPIED voxels, ascending key order, as a resident cloud; no row comes down to the host.
+ * *n (optional): their number.  Interchangeable with the cloud cvo_map_cloud(..., &resident) returns: the same rows, order,
+ * one-hot detection, scores and solves; the rows go from k_bki_rows to cvo_cloud_from_device's ingest where they are, so its
+ * route rule orders them (ORDER=wide above 16 384 voxels).  A map of the host side uploads the twin's rows. */
+int cvo_map_cloud_resident(cvo_map* map, cvo_cloud** out, long long* n);
 /* the CPU twin on a map without a context */
 int cvo_map_open_host(const cvo_map_config_t* cfg, cvo_map** out);
 void cvo_map_close_host(cvo_map* map);

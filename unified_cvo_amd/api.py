@@ -707,6 +707,33 @@ class SemanticMap:
         call = self.L.cvo_map_insert if self.gpu is not None else self.L.cvo_map_insert_host
         return self._check(call(self.handle, xyz.shape[0], _fptr(xyz), _fptr(feat), _fptr(label), _fptr(o)), "cvo_map_insert_host refused the hits")
 
+    def insert_cloud(self, cloud, pose=None, origin=None):
+        """cvo_map_insert_cloud: the rows of a resident cloud (DeviceCloud), in original order, as the hits of one insert,
+        without a host copy - moved by `pose` (3x4 or 4x4, cast to float32 as insert casts; None: the stored rows), seen
+        from `origin` (None: the pose's translation).  The map insert(cloud.download() rows, pose= / origin=) leaves."""
+        if pose is None and origin is None:
+            raise ValueError("give the origin or the pose")
+        if self.gpu is None:
+            raise ValueError("a host map takes rows, not a resident cloud")
+        T = o = None
+        if pose is not None:
+            P = np.asarray(pose, np.float32)
+            if P.shape not in ((3, 4), (4, 4)):
+                raise ValueError(f"the pose is 3x4 or 4x4, got {P.shape}")
+            T = np.ascontiguousarray(P[:3, :4])
+        if origin is not None:
+            o = np.ascontiguousarray(origin, np.float32).reshape(3)
+        return self._check(self.L.cvo_map_insert_cloud(self.handle, cloud.handle, _fptr(T), _fptr(o)), "")
+
+    def resident_cloud(self):
+        """cvo_map_cloud_resident: the OCCUPIED voxels in ascending key order as a DeviceCloud, built on the device from the
+        rows where the read-out kernel leaves them; interchangeable with cloud(resident=True)[3]."""
+        if self.gpu is None:
+            raise ValueError("a host map has no resident cloud")
+        h, n = C.c_void_p(), C.c_longlong()
+        self._check(self.L.cvo_map_cloud_resident(self.handle, C.byref(h), C.byref(n)), "")
+        return self.gpu._adopt(h, n.value)
+
     def size(self):
         """cvo_map_size -> (voxels stored, of them OCCUPIED)."""
         v, o = C.c_longlong(), C.c_longlong()

@@ -1,5 +1,6 @@
 // cvo_bki.hip -- the semantic voxel map: cvo_map_open / _insert / _insert_posed / _size / _cloud / _close, their _host twins
-// on a map without a context, and cvo_debug_map_stats.  It is semantic_bki::SemanticBKIOctoMap::insert_pointcloud_csm at
+// on a map without a context, cvo_map_insert_cloud / cvo_map_cloud_resident (a resident cloud in, a resident cloud out: the
+// hits staged by k_bki_stage, the rows read out handed to cvo_ingest.hip where they are) and cvo_debug_map_stats.  It is semantic_bki::SemanticBKIOctoMap::insert_pointcloud_csm at
 // block_depth 1 with the read-out of CvoPointCloud(const SemanticBKIOctoMap*, num_classes); tests/np_bki.py states what is
 // computed, the CPU twin (BkiHostMap) and the kernels of cvo_k_bki.h share cvo_bki_math.h.  A map lives on ONE side: a map
 // of a context takes its side at its first insert (switch BKI_HOST; unset: by that insert's training points) and keeps it,
@@ -261,43 +262,52 @@ int bki_table_grow(cvo_map* m, unsigned long long need) {
   return CVO_OK;
 }
 
-int bki_insert_device(cvo_map* m, int n, const float* xyz, const float* feat, const float* label, const float* origin, BkiStats* stats) {
+// The insert scratch of n hits, the layout k_bki_count ... k_bki_long read (and k_bki_stage writes): `a` bound to it, its
+// control block enqueued in its start state.  has_feat: the hits carry feature rows.
+int bki_insert_scratch(cvo_map* m, int n, bool has_feat, const float* origin, BkiInsertArgs* a) {
   cvo_ctx* ctx = m->ctx;
-  hipStream_t st = ctx->upload_stream;
   const BkiConst& k = m->k;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
   const size_t nn = (size_t)n;
-  BkiInsertArgs a{};
-  a.k = k;
-  a.n = n;
-  for (int q = 0; q < 3; q++) a.origin[q] = origin[q];
-  int rc = m->in_scratch.lay_out(ctx, "voxel map insert scratch", [&](ScratchLayout& l) {
-    l.take(a.ctl, 1);
-    l.take(a.xyz, 3 * nn);
-    if (feat) l.take(a.feat, BKI_FEAT * nn);
-    if (k.C > 0) l.take(a.label, (size_t)k.C * nn);
-    l.take(a.mc, nn + 1);
-    l.take(a.hslot, BKI_HIT_SLOTS * nn);
+  *a = BkiInsertArgs{};
+  a->k = k;
+  a->n = n;
+  for (int q = 0; q < 3; q++) a->origin[q] = origin[q];
+  const int rc = m->in_scratch.lay_out(ctx, "voxel map insert scratch", [&](ScratchLayout& l) {
+    l.take(a->ctl, 1);
+    l.take(a->xyz, 3 * nn);
+    if (has_feat) l.take(a->feat, BKI_FEAT * nn);
+    if (k.C > 0) l.take(a->label, (size_t)k.C * nn);
+    l.take(a->mc, nn + 1);
+    l.take(a->hslot, BKI_HIT_SLOTS * nn);
   });
   if (rc != CVO_OK) return rc;
   BkiCtl h{};
-  h.bad_index = ~0u;
-  HIP_TRY(ctx, hipMemcpyAsync(a.ctl, &h, sizeof h, hipMemcpyHostToDevice, st));
-  if (n) HIP_TRY(ctx, hipMemcpyAsync((void*)a.xyz, xyz, 12 * nn, hipMemcpyHostToDevice, st));
-  if (n && feat) HIP_TRY(ctx, hipMemcpyAsync((void*)a.feat, feat, 4 * BKI_FEAT * nn, hipMemcpyHostToDevice, st));
-  if (n && k.C > 0) HIP_TRY(ctx, hipMemcpyAsync((void*)a.label, label, 4 * (size_t)k.C * nn, hipMemcpyHostToDevice, st));
-  const dim3 per_hit(bki_blocks(nn + 1)), block(BKI_THREADS);
-  hipLaunchKernelGGL(k_bki_count, per_hit, block, 0, st, a);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(&h, a.ctl, sizeof h, hipMemcpyDeviceToHost, st));
-  HIP_TRY(ctx, hipStreamSynchronize(st));
+  h.bad_index = h.nonfinite = ~0u;
+  HIP_TRY(ctx, hipMemcpyAsync(a->ctl, &h, sizeof h, hipMemcpyHostToDevice, ctx->upload_stream));
+  return CVO_OK;
+}
+
+// what k_bki_count found that refuses the insert, as `who`
+int bki_count_refusal(cvo_ctx* ctx, const std::string& who, const BkiCtl& h, int n) {
   // (the caps come first, as in the statement: k_bki_count goes on counting behind a bad block index)
   if (h.status & BKI_BAD_TOO_MANY)  // (bad_index is the first bad hit of any kind: named only when this is the one kind)
-    return fail(ctx, CVO_E_UNSUPPORTED, "cvo_map_insert: " + (h.status == BKI_BAD_TOO_MANY ? bki_bad_text(h.status, h.bad_index, n) : std::string("a hit needs 65536 beam samples or more")));
-  if (h.training >= (unsigned long long)BKI_MAX_TRAINING) return fail(ctx, CVO_E_UNSUPPORTED, "cvo_map_insert: 2^24 training points or more in one insert");
-  if (h.status) return fail(ctx, h.status & BKI_BAD_RANGE ? CVO_E_INVALID : CVO_E_UNSUPPORTED, "cvo_map_insert: " + bki_bad_text(h.status, h.bad_index, n));
+    return fail(ctx, CVO_E_UNSUPPORTED, who + ": " + (h.status == BKI_BAD_TOO_MANY ? bki_bad_text(h.status, h.bad_index, n) : std::string("a hit needs 65536 beam samples or more")));
+  if (h.training >= (unsigned long long)BKI_MAX_TRAINING) return fail(ctx, CVO_E_UNSUPPORTED, who + ": 2^24 training points or more in one insert");
+  if (h.status) return fail(ctx, h.status & BKI_BAD_RANGE ? CVO_E_INVALID : CVO_E_UNSUPPORTED, who + ": " + bki_bad_text(h.status, h.bad_index, n));
+  return CVO_OK;
+}
+
+// The rest of an insert whose hits are staged and counted (h: the control block k_bki_count left, nothing refused): the
+// table grows, k_bki_emit ... k_bki_long run.
+int bki_insert_counted(cvo_map* m, BkiInsertArgs& a, BkiCtl& h, BkiStats* stats) {
+  cvo_ctx* ctx = m->ctx;
+  hipStream_t st = ctx->upload_stream;
+  const int n = a.n;
+  const size_t nn = (size_t)n;
+  const float* feat = a.feat;
+  const dim3 per_hit(bki_blocks(nn + 1)), block(BKI_THREADS);
   // the work arrays, and room in the table for every membership to be a new voxel
-  rc = m->work_scratch.lay_out(ctx, "voxel map work scratch", [&](ScratchLayout& l) {
+  int rc = m->work_scratch.lay_out(ctx, "voxel map work scratch", [&](ScratchLayout& l) {
     l.take(a.rec, h.members);
     l.take(a.seg, h.hit_members);
     l.take(a.seg2, h.hit_members);
@@ -326,6 +336,27 @@ int bki_insert_device(cvo_map* m, int n, const float* xyz, const float* feat, co
   return CVO_OK;
 }
 
+int bki_insert_device(cvo_map* m, int n, const float* xyz, const float* feat, const float* label, const float* origin, BkiStats* stats) {
+  cvo_ctx* ctx = m->ctx;
+  hipStream_t st = ctx->upload_stream;
+  const BkiConst& k = m->k;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t nn = (size_t)n;
+  BkiInsertArgs a{};
+  int rc = bki_insert_scratch(m, n, feat != nullptr, origin, &a);
+  if (rc != CVO_OK) return rc;
+  BkiCtl h{};
+  if (n) HIP_TRY(ctx, hipMemcpyAsync((void*)a.xyz, xyz, 12 * nn, hipMemcpyHostToDevice, st));
+  if (n && feat) HIP_TRY(ctx, hipMemcpyAsync((void*)a.feat, feat, 4 * BKI_FEAT * nn, hipMemcpyHostToDevice, st));
+  if (n && k.C > 0) HIP_TRY(ctx, hipMemcpyAsync((void*)a.label, label, 4 * (size_t)k.C * nn, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_bki_count, dim3(bki_blocks(nn + 1)), dim3(BKI_THREADS), 0, st, a);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(&h, a.ctl, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if ((rc = bki_count_refusal(ctx, "cvo_map_insert", h, n)) != CVO_OK) return rc;
+  return bki_insert_counted(m, a, h, stats);
+}
+
 // Collects and sorts the occupied voxels of a device map; *okey / *oslot point at the sorted arrays in work_scratch, *rows at
 // room for the rows behind them.  count_only: one pass over the table that writes nothing but the number.
 int bki_collect_device(cvo_map* m, bool count_only, unsigned* n_occ, const unsigned long long** okey, const unsigned** oslot, float** rows) {
@@ -343,7 +374,7 @@ int bki_collect_device(cvo_map* m, bool count_only, unsigned* n_occ, const unsig
     l.take(slot[0], V);
     l.take(slot[1], V);
     l.take(hist, 256 * nbmax);
-    l.take(*rows, V * (size_t)(3 + BKI_FEAT + BKI_MAX_CLASSES));
+    l.take(*rows, V * (size_t)(3 + BKI_FEAT + NC_PAD));  // (label rows: packed, or at the resident cloud's padded stride)
   });
   if (rc != CVO_OK) return rc;
   *okey = key[0];
@@ -401,7 +432,7 @@ int bki_rows(cvo_map* m, bool want_rows, BkiRows* out) {
   float* d_feat = d_xyz + 3 * (size_t)n;
   float* d_label = d_feat + BKI_FEAT * (size_t)n;
   hipStream_t st = ctx->upload_stream;
-  hipLaunchKernelGGL(k_bki_rows, dim3(bki_blocks(n)), dim3(BKI_THREADS), 0, st, k, m->t, n, okey, oslot, d_xyz, d_feat, d_label);
+  hipLaunchKernelGGL(k_bki_rows, dim3(bki_blocks(n)), dim3(BKI_THREADS), 0, st, k, m->t, n, okey, oslot, d_xyz, d_feat, d_label, k.C, k.C);
   HIP_TRY(ctx, hipGetLastError());
   out->xyz.resize(3 * (size_t)n);
   out->feat.resize(BKI_FEAT * (size_t)n);
@@ -464,6 +495,19 @@ int bki_open(cvo_ctx* ctx, const char* who, const cvo_map_config_t* cfg, long lo
   return CVO_OK;
 }
 
+// what cvo_cloud_upload makes of the rows read out; a label row of fewer than NC classes is followed by zeros
+int bki_upload_rows(cvo_ctx* ctx, int C, const BkiRows& rows, cvo_cloud** resident) {
+  std::vector<float> wide;
+  if (C > 0 && C < NC) {
+    wide.assign((size_t)NC * rows.n, 0.f);
+    for (long long i = 0; i < rows.n; i++) std::memcpy(&wide[(size_t)NC * i], &rows.label[(size_t)C * i], 4 * (size_t)C);
+  }
+  const float* lab = C == 0 ? nullptr : (C < NC ? wide.data() : rows.label.data());
+  const HostCloud h{(int)rows.n, (const char*)rows.xyz.data(), 12, (const char*)rows.feat.data(), sizeof(float) * FD, (const char*)lab,
+                    sizeof(float) * NC, nullptr, 8};
+  return upload_one_locked(ctx, h, resident);
+}
+
 int bki_cloud_entry(cvo_map* m, bool host_call, const char* who, long long capacity, float* xyz, float* feat, float* label, long long* n, cvo_cloud** resident) {
   if (!m || host_call != (m->ctx == nullptr)) return CVO_E_INVALID;
   cvo_ctx* ctx = m->ctx;
@@ -481,21 +525,113 @@ int bki_cloud_entry(cvo_map* m, bool host_call, const char* who, long long capac
     if (xyz && rows.n) std::memcpy(xyz, rows.xyz.data(), 4 * rows.xyz.size());
     if (feat && rows.n) std::memcpy(feat, rows.feat.data(), 4 * rows.feat.size());
     if (label && rows.n && m->k.C > 0) std::memcpy(label, rows.label.data(), 4 * rows.label.size());
-    if (resident) {
-      // what cvo_cloud_upload makes of the rows; a label row of fewer than NC classes is followed by zeros
-      std::vector<float> wide;
-      const int C = m->k.C;
-      if (C > 0 && C < NC) {
-        wide.assign((size_t)NC * rows.n, 0.f);
-        for (long long i = 0; i < rows.n; i++) std::memcpy(&wide[(size_t)NC * i], &rows.label[(size_t)C * i], 4 * (size_t)C);
-      }
-      const float* lab = C == 0 ? nullptr : (C < NC ? wide.data() : rows.label.data());
-      const HostCloud h{(int)rows.n, (const char*)rows.xyz.data(), 12, (const char*)rows.feat.data(), sizeof(float) * FD, (const char*)lab,
-                        sizeof(float) * NC, nullptr, 8};
-      if ((rc = upload_one_locked(ctx, h, resident)) != CVO_OK) return rc;
-    }
+    if (resident && (rc = bki_upload_rows(ctx, m->k.C, rows, resident)) != CVO_OK) return rc;
     return (int)CVO_OK;
   });
+}
+
+// ---- a resident cloud in, a resident cloud out: no row passes through the host on a map of the device side ----
+
+// The hits of cvo_map_insert_cloud staged on the device, then the side rule and either side's insert.  The caller holds
+// upload_mutex; pose (or nullptr) and origin are finite.
+int bki_insert_cloud_locked(cvo_map* m, const cvo_cloud* c, const float* pose12, const float* origin) {
+  const std::string who = "cvo_map_insert_cloud";
+  cvo_ctx* ctx = m->ctx;
+  hipStream_t st = ctx->upload_stream;
+  const BkiConst& k = m->k;
+  const int n = c->n;
+  const size_t nn = (size_t)n;
+  // what the cloud really holds (an attribute pointed into the zero slab counts as missing: cvo_merge.hip)
+  const float4* c_feat = n ? held(c, c->feat) : nullptr;
+  const float4* c_label = n ? held(c, c->label) : nullptr;
+  if (n > 0 && k.C > 0 && !c_label) return fail(ctx, CVO_E_INVALID, who + ": a map with classes needs label rows");
+  if (m->broken) return fail(ctx, CVO_E_HIP, who + ": an earlier insert failed on the device half way: the map cannot be used");
+  if ((long long)n >= BKI_MAX_TRAINING) return fail(ctx, CVO_E_UNSUPPORTED, who + ": more than 2^24 training points in one insert");
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  BkiInsertArgs a{};
+  int rc = bki_insert_scratch(m, n, c_feat != nullptr, origin, &a);
+  if (rc != CVO_OK) return rc;
+  if (n) {
+    BkiStageArgs s{};
+    s.n = n;
+    s.C = k.C;
+    s.has_pose = pose12 ? 1 : 0;
+    for (int q = 0; pose12 && q < 12; q++) s.pose[q] = pose12[q];
+    s.x4 = c->x4;
+    s.inv = c->inv;
+    s.feat = reinterpret_cast<const float*>(c_feat);
+    s.label = reinterpret_cast<const float*>(c_label);
+    s.xyz = const_cast<float*>(a.xyz);
+    s.ofeat = const_cast<float*>(a.feat);
+    s.olabel = const_cast<float*>(a.label);
+    s.ctl = a.ctl;
+    const int grid = std::min((n + BKI_STAGE_THREADS - 1) / BKI_STAGE_THREADS, BKI_STAGE_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_bki_stage, dim3((unsigned)grid), dim3(BKI_STAGE_THREADS), 0, st, s);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  // The side: the map's; on a map without one the switch's; with the switch unset the training points k_bki_count finds
+  // in the staged hits decide (the count bki_choose_side makes on the host for rows that are there).
+  int side = m->side >= 0 ? m->side : (ctx->opt.bki_host >= 0 ? (ctx->opt.bki_host > 0 ? 1 : 0) : -1);
+  if (side != 1) {
+    hipLaunchKernelGGL(k_bki_count, dim3(bki_blocks(nn + 1)), dim3(BKI_THREADS), 0, st, a);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  BkiCtl h{};
+  HIP_TRY(ctx, hipMemcpyAsync(&h, a.ctl, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  // (bki_validate_insert's check, made where the moved rows are)
+  if (h.nonfinite != ~0u) return fail(ctx, CVO_E_INVALID, who + ": hit " + std::to_string(h.nonfinite) + " has a coordinate that is not finite");
+  if (side < 0) side = route_on_host(-1, (long long)h.training, BKI_HOST_BELOW) ? 1 : 0;
+  BkiStats stats;
+  if (side == 1) {  // the staged arrays are the three bki_insert_cpu takes
+    std::vector<float> hx(3 * nn), hf(c_feat ? BKI_FEAT * nn : 0), hl((size_t)k.C * nn);
+    if (n) HIP_TRY(ctx, hipMemcpyAsync(hx.data(), a.xyz, 12 * nn, hipMemcpyDeviceToHost, st));
+    if (n && c_feat) HIP_TRY(ctx, hipMemcpyAsync(hf.data(), a.feat, 4 * BKI_FEAT * nn, hipMemcpyDeviceToHost, st));
+    if (n && k.C > 0) HIP_TRY(ctx, hipMemcpyAsync(hl.data(), a.label, 4 * (size_t)k.C * nn, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::string text;
+    rc = bki_insert_cpu(m, n, hx.data(), c_feat ? hf.data() : nullptr, k.C > 0 ? hl.data() : nullptr, origin, &stats, &text);
+    if (rc != CVO_OK) return fail(ctx, rc, who + ": " + text);
+    m->occupied = -1;
+  } else {
+    stats.on_device = 1;
+    if ((rc = bki_count_refusal(ctx, who, h, n)) != CVO_OK) return rc;
+    if ((rc = bki_insert_counted(m, a, h, &stats)) != CVO_OK) return rc;
+  }
+  m->side = side;
+  m->last = stats;
+  return CVO_OK;
+}
+
+// The occupied voxels of a device map as ingest rows where k_bki_rows leaves them - label rows at the padded stride
+// k_cloud_ingest reads, zeros behind the map's classes - and cvo_cloud_from_device's body on them: its route rule orders the
+// cloud.  The caller holds upload_mutex.
+int bki_cloud_resident_device(cvo_map* m, const char* who, std::vector<StagedCloud>& staged, long long* n_out) {
+  cvo_ctx* ctx = m->ctx;
+  const BkiConst& k = m->k;
+  unsigned n = 0;
+  const unsigned long long* okey;
+  const unsigned* oslot;
+  float* d_xyz;
+  const int rc = bki_collect_device(m, false, &n, &okey, &oslot, &d_xyz);
+  if (rc != CVO_OK) return rc;
+  float* d_feat = d_xyz + 3 * (size_t)n;
+  float* d_label = d_feat + BKI_FEAT * (size_t)n;
+  if (n) {
+    hipLaunchKernelGGL(k_bki_rows, dim3(bki_blocks(n)), dim3(BKI_THREADS), 0, ctx->upload_stream, k, m->t, n, okey, oslot, d_xyz, d_feat, d_label,
+                       NC_PAD, NC_PAD);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  cvo_device_rows_t d{};
+  d.n = d.n_records = (int)n;
+  d.xyz = d_xyz;
+  d.xyz_stride = 12;
+  d.feat = d_feat;
+  d.feat_stride = sizeof(float) * BKI_FEAT;
+  d.label = k.C > 0 ? d_label : nullptr;
+  d.label_stride = sizeof(float) * NC_PAD;
+  *n_out = n;
+  return ingest_device_clouds(ctx, 1, &d, staged, who);  // (synchronises upload_stream; on error the cloud is released)
 }
 
 }  // namespace
@@ -589,6 +725,50 @@ int cvo_map_cloud(cvo_map* m, long long capacity, float* xyz, float* feat, float
 
 int cvo_map_cloud_host(cvo_map* m, long long capacity, float* xyz, float* feat, float* label, long long* n) {
   return bki_cloud_entry(m, true, "cvo_map_cloud_host", capacity, xyz, feat, label, n, nullptr);
+}
+
+int cvo_map_insert_cloud(cvo_map* m, const cvo_cloud* cloud, const float pose12[12], const float origin[3]) {
+  const std::string who = "cvo_map_insert_cloud";
+  if (!m || !m->ctx) return CVO_E_INVALID;  // (a host map has no context to hold a text, and no device to stage on)
+  cvo_ctx* ctx = m->ctx;
+  if (!cloud) return fail(ctx, CVO_E_INVALID, who + ": a required pointer is missing");
+  if (cloud->ctx != ctx) return fail(ctx, CVO_E_INVALID, who + ": the cloud belongs to another context");
+  if (!pose12 && !origin) return fail(ctx, CVO_E_INVALID, who + ": neither a pose nor an origin is given");
+  for (int q = 0; pose12 && q < 12; q++)
+    if (!std::isfinite(pose12[q])) return fail(ctx, CVO_E_INVALID, who + ": the pose is not finite");
+  const float o[3] = {origin ? origin[0] : pose12[3], origin ? origin[1] : pose12[7], origin ? origin[2] : pose12[11]};
+  for (int q = 0; q < 3; q++)
+    if (!std::isfinite(o[q])) return fail(ctx, CVO_E_INVALID, who + ": the origin is not finite");
+  return frontend_call(ctx, who.c_str(), [&] { return bki_insert_cloud_locked(m, cloud, pose12, o); });
+}
+
+int cvo_map_cloud_resident(cvo_map* m, cvo_cloud** out, long long* n) {
+  const char* who = "cvo_map_cloud_resident";
+  if (out) *out = nullptr;
+  if (n) *n = 0;
+  if (!m || !m->ctx) return CVO_E_INVALID;
+  cvo_ctx* ctx = m->ctx;
+  if (!out) return fail(ctx, CVO_E_INVALID, std::string(who) + ": a required pointer is missing");
+  if (m->broken) return fail(ctx, CVO_E_HIP, std::string(who) + ": an earlier insert failed on the device half way: the map cannot be used");
+  std::vector<StagedCloud> staged;
+  long long rows_n = 0;
+  const int rc = frontend_call(ctx, who, [&] {
+    if (m->side == 0) return bki_cloud_resident_device(m, who, staged, &rows_n);
+    // a map of the host side (or without an insert): the twin's rows, uploaded
+    BkiRows rows;
+    int r = bki_rows(m, true, &rows);
+    if (r != CVO_OK) return r;
+    staged.resize(1);
+    if ((r = bki_upload_rows(ctx, m->k.C, rows, &staged[0].c)) != CVO_OK) return staged[0].c = nullptr, r;
+    rows_n = rows.n;
+    return (int)CVO_OK;
+  });
+  for (auto& sc : staged) {
+    if (rc == CVO_OK) *out = sc.c;
+    else if (sc.c) cvo_cloud_free(sc.c);  // (an exception left it behind; an error return released it itself)
+  }
+  if (rc == CVO_OK && n) *n = rows_n;
+  return rc;
 }
 
 int cvo_debug_map_stats(cvo_map* m, int* on_device, unsigned long long* counts, unsigned long long* keys, float* ms, float* fs) {

@@ -25,7 +25,7 @@
 //   cvo_sgm.hip     the stereo matcher: left + right gray planes to the left disparity (semi-global matching over census)
 //   cvo_dfilter.hip the disparity post-filter: libelas's speckle, gap and adaptive-mean passes on the matcher's or a caller's map
 //   cvo_stereo_pair.hip  the entry points that chain matcher, filter and stereo front end under one lock
-//   cvo_bki.hip     the semantic voxel map: posed clouds fused into a persistent table, its occupied voxels read out as a cloud
+//   cvo_bki.hip     the semantic voxel map: posed clouds (host rows or resident) fused into a persistent table, its occupied voxels read out as a cloud
 #include "cvo_internal.h"
 
 #include "cvo_ctx.hip"

@@ -21,6 +21,9 @@
 //                  h hits: microseconds at 3000, about a second at 10^5 (DESIGN.md section 3 names the cliff).
 // Which slot a voxel lands in, which record is FIRST and the order inside a segment depend on arrival; no output does.
 //
+// An insert of a resident cloud (cvo_map_insert_cloud) has k_bki_stage (cvo_k_bki_stage.h) write the hits where the host
+// would have copied them; the six kernels above follow unchanged.
+//
 // The read-out: k_bki_occupied collects (key, slot) of the OCCUPIED voxels (wave_alloc), the radix sort of cvo_k_sort.h puts
 // them in ascending key order, k_bki_rows writes the rows.  Part of the kernel set of cvo_kernels.h; compiled only as part of
 // cvo_hip.hip.
@@ -51,7 +54,8 @@ struct BkiTable {
 struct BkiCtl {
   unsigned status, bad_index;  // OR of BKI_BAD_*; the lowest hit index with a bad point (n: the origin)
   unsigned long long training, members, hit_members;
-  unsigned rec_used, seg_used, n_long, fresh, longest_probe, longest_run, n_occ, pad;
+  unsigned rec_used, seg_used, n_long, fresh, longest_probe, longest_run, n_occ;
+  unsigned nonfinite;  // k_bki_stage (cvo_k_bki_stage.h): the lowest row whose moved coordinate is not finite, ~0u: none
 };
 
 struct BkiInsertArgs {
@@ -281,13 +285,16 @@ __global__ __launch_bounds__(BKI_THREADS) void k_bki_occupied(BkiConst k, BkiTab
   }
 }
 
+// label rows: label_stride floats apart, the C values followed by zeros up to label_width (the packed rows of cvo_map_cloud:
+// both C; the rows k_cloud_ingest reads at a stride of 80 bytes, cvo_map_cloud_resident: both NC_PAD)
 __global__ __launch_bounds__(BKI_THREADS) void k_bki_rows(BkiConst k, BkiTable t, unsigned n, const unsigned long long* key, const unsigned* slot,
-                                                          float* xyz, float* feat, float* label) {
+                                                          float* xyz, float* feat, float* label, int label_stride, int label_width) {
   const unsigned i = blockIdx.x * BKI_THREADS + threadIdx.x;
   if (i >= n) return;
   const unsigned g = slot[i];
-  bki_row(k, key[i], t.ms + (size_t)g * t.nclass, t.fs + (size_t)g * BKI_FEAT, xyz + 3 * (size_t)i, feat + (size_t)BKI_FEAT * i,
-          k.C > 0 ? label + (size_t)k.C * i : nullptr);
+  float* lab = k.C > 0 ? label + (size_t)label_stride * i : nullptr;
+  bki_row(k, key[i], t.ms + (size_t)g * t.nclass, t.fs + (size_t)g * BKI_FEAT, xyz + 3 * (size_t)i, feat + (size_t)BKI_FEAT * i, lab);
+  for (int c = k.C; lab && c < label_width; c++) lab[c] = 0.f;
 }
 
 }  // namespace cvo_dev

@@ -78,3 +78,4 @@
 #include "cvo_k_sgm.h"
 #include "cvo_k_dfilter.h"
 #include "cvo_k_bki.h"
+#include "cvo_k_bki_stage.h"
