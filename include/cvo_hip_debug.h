@@ -89,6 +89,15 @@ int cvo_debug_order_route_rule(int n, int finite, const char* order_value, int n
  * = the cuts of segments of more than W points, rows = (level, lo, hi, left) of the first `capacity` of them, level by
  * level and by position inside a level.  No context, no device.  W may be NULL. */
 int cvo_debug_wide_plan(int n, int* W, int* rows /* level, lo, hi, left */, int capacity, int* n_rows);
+/* ... with leaves of at most `leaf` points, what a context with CVO_WIDE_LEAF=leaf uploads: the cuts of segments of more than
+ * `leaf` points.  CVO_E_INVALID for a leaf outside 1024 .. 16384. */
+int cvo_debug_wide_plan_at(int n, int leaf, int* rows /* level, lo, hi, left */, int capacity, int* n_rows);
+/* The select of the multi-block ordering, as the device computed it when `cloud` was uploaded by a context with
+ * CVO_WIDE_RECORD=1: for every cut of the cloud's plan, in plan order (cvo_debug_wide_plan_at's rows), pivot = the kd_ordered
+ * key of the segment's left-th smallest coordinate along the level's axis, rem = how many of the keys equal to it go left.
+ * *n_segments = the cuts, of which the first `capacity` are written.  CVO_E_INVALID for a cloud that was not ordered by the
+ * multi-block ordering itself (route != 2, or made by cvo_cloud_transformed) or was ordered without the switch. */
+int cvo_debug_cloud_wide_pivots(const cvo_cloud* cloud, int capacity, unsigned* pivot, unsigned* rem, int* n_segments);
 /* What the last score call did - cvo_inner_product / cvo_function_angle (one job) or their _batch forms: evaluations summed
  * by k_overlap (the exact function_angle's <X, X> / <Y, Y> once per distinct cloud and lengthscale), evaluations repeated
  * or run by the list chain (void jobs, chain-only calls), and launches (k_overlap chunks + chain sub-batches).  E.g.

@@ -33,6 +33,50 @@ def bit_pattern_key(v):
     return np.where(b >> 31 != 0, ~b, b ^ np.uint32(0x80000000)).astype(np.uint32)
 
 
+def ordered_key(v):
+    """kd_ordered (cvo_k_cloud.h) in numpy, uint32: the bit-pattern key of v + 0.0 - the two zeros are ONE key, 0x80000000 -
+    so that `<` on keys is `<` on the floats and `==` on keys is `==` on the floats.  What the multi-block ordering's radix
+    select works on (cvo_k_kd_wide.h); the statement itself sorts by float_key."""
+    return bit_pattern_key(np.asarray(v, np.float32) + np.float32(0.0))
+
+
+def key_to_float(k):
+    """The inverse of ordered_key: the float32 whose key is k.  (0x7fffffff is no float's key - it would be -0.0's, which
+    shares +0.0's - and keys from 0xff800000 on / up to 0x007fffff are the infinities and NaNs.)"""
+    k = np.asarray(k, np.uint32)
+    return np.where(k >> 31 != 0, k ^ np.uint32(0x80000000), ~k).astype(np.uint32).view(np.float32)
+
+
+def wide_plan(n, leaf):
+    """The plan of the multi-block ordering (wide_plan, cvo_upload.hip) of n points from kd_left alone: (level, lo, hi, left)
+    of every cut of a segment of more than `leaf` points, level by level and by position inside a level."""
+    return _wide_plan(n, leaf)[0]
+
+
+def wide_plan_leaves(n, leaf):
+    """... and its leaves: (level, lo, points, NP) of every segment of at most `leaf` points, with the level at which it left
+    the global partitions and the power of two (>= 1024) its block sorts."""
+    return _wide_plan(n, leaf)[1]
+
+
+def _wide_plan(n, leaf):
+    cuts, leaves, level, cur = [], [], 0, [(0, n)]
+    while cur:
+        nxt = []
+        for lo, hi in cur:
+            if hi - lo > leaf:
+                left = kd_left(hi - lo)
+                cuts.append((level, lo, hi, left))
+                nxt += [(lo, lo + left), (lo + left, hi)]
+            else:
+                NP = 1024
+                while NP < hi - lo:
+                    NP *= 2
+                leaves.append((level, lo, hi - lo, NP))
+        cur, level = nxt, level + 1
+    return cuts, leaves
+
+
 def order(xyz, key=float_key, record=None):
     """int32 permutation: the original index of the point at every sorted position.  record (a list): receives one
     (level, axis, lo, hi, left, members) per split - `members` the original indices of the segment [lo, hi) BEFORE the

@@ -1,7 +1,8 @@
 """The host side of the multi-block ordering (ORDER=wide), without a GPU: the route rule every upload path calls
 (cvo_debug_order_route_rule) over its whole table, and the plan the host uploads with a wide job (cvo_debug_wide_plan)
 against the statement np_kd.order's own record of its splits and, at sizes up to the cap of 2^24 points, against a
-recursion over np_kd.kd_left alone.  Every comparison is exact."""
+recursion over np_kd.kd_left alone (np_kd.wide_plan); the same plan at other leaf capacities (cvo_debug_wide_plan_at).  Every
+comparison is exact."""
 import os
 import re
 
@@ -9,12 +10,14 @@ import numpy as np
 import pytest
 
 import cases
+import kd_wide_cases
 import np_kd
-from unified_cvo_amd import _capi, debug_order_route_rule, debug_wide_plan, synth
+from unified_cvo_amd import _capi, debug_order_route_rule, debug_wide_plan, debug_wide_plan_at, synth
 
 KD_MAX = 16384
 WIDE_MAX = 1 << 24
-HOOKS = ("cvo_debug_cloud_order_route", "cvo_debug_order_route_rule", "cvo_debug_wide_plan")
+HOOKS = ("cvo_debug_cloud_order_route", "cvo_debug_order_route_rule", "cvo_debug_wide_plan", "cvo_debug_wide_plan_at",
+         "cvo_debug_cloud_wide_pivots")
 
 
 def _today(n, finite, order, no_sort):
@@ -60,23 +63,10 @@ def test_plan_equals_the_statements_splits(n):
     assert rows.tolist() == sorted(rows.tolist(), key=lambda r: (r[0], r[1]))
 
 
-def _recursion(n, W):
-    out, level, cur = [], 0, [(0, n)]
-    while cur:
-        nxt = []
-        for lo, hi in cur:
-            if hi - lo > W:
-                left = np_kd.kd_left(hi - lo)
-                out.append((level, lo, hi, left))
-                nxt += [(lo, lo + left), (lo + left, hi)]
-        cur, level = nxt, level + 1
-    return out
-
-
 @pytest.mark.parametrize("n", [1 << 22, WIDE_MAX - 1, WIDE_MAX])
 def test_plan_up_to_the_cap(n):
     W, rows = debug_wide_plan(n)
-    want = _recursion(n, W)
+    want = np_kd.wide_plan(n, W)
     assert rows.tolist() == [list(r) for r in want]
     assert all(lo % 512 == 0 and (hi % 512 == 0 or hi == n) and 0 < left < hi - lo for _, lo, hi, left in want)
 
@@ -91,6 +81,26 @@ def test_plan_edges():
     # two global levels first at the size whose halves no longer both fit a leaf
     levels = lambda n: 1 + int(debug_wide_plan(n)[1][:, 0].max())
     assert levels(2 * W) == 1 and levels(2 * W + 1) == 2
+
+
+@pytest.mark.parametrize("leaf", [1024, 2048, 16384])
+def test_plan_at_a_given_leaf(leaf):
+    """The sizes test_gpu_kd_wide_edges.py runs: the crafted clouds', the scatter's, the WIDE_LEAF cases'."""
+    for n in (kd_wide_cases.N, kd_wide_cases.SCATTER_N) + kd_wide_cases.LEAF_SIZES:
+        rows = debug_wide_plan_at(n, leaf)
+        assert rows.tolist() == [list(r) for r in np_kd.wide_plan(n, leaf)], (n, leaf)
+        assert len(rows) > 0 and all(hi - lo > leaf for _, lo, hi, _ in rows.tolist())
+    assert len(debug_wide_plan_at(leaf, leaf)) == 0 and len(debug_wide_plan_at(leaf + 1, leaf)) == 1
+
+
+def test_plan_at_the_default_leaf_is_the_default_plan():
+    W, rows = debug_wide_plan(70001)
+    assert np.array_equal(debug_wide_plan_at(70001, W), rows)
+    for leaf in (0, 1023, KD_MAX + 1, -1):
+        with pytest.raises(Exception):
+            debug_wide_plan_at(70001, leaf)
+    with pytest.raises(Exception):
+        debug_wide_plan_at(WIDE_MAX + 1, 2048)
 
 
 def test_header_and_binding_list_hold_the_hooks():

@@ -7,7 +7,7 @@ from .params import CvoParams, read_cvo_params_yaml, parse_cvo_yaml_text  # noqa
 from .api import (CvoGPU, CvoPointCloud, DeviceCloud, DeviceCloudAoS, CvoError, AlignResult, CvoFrameGPU,  # noqa: F401
                   BinaryStateGPU, CVO_POINT_DTYPE, cvo_points_from_pointcloud, RGBDFrame, rgbd_points_host, StereoFrame, fast_select_host,
                   stereo_points_host, LidarScan, LidarConfig, LidarRand, lidar_select_host, debug_lidar_atan2,
-                  debug_order_route_rule, debug_wide_plan,
+                  debug_order_route_rule, debug_wide_plan, debug_wide_plan_at,
                   nlm_weights, nlm_denoise_host, nlm_denoise_lab_host,
                   SGMConfig, stereo_disparity_host, DFilterConfig, disparity_filter_host,
                   MapConfig, SemanticMap, map_open_host, map_insert_host, map_cloud_host, map_close_host)

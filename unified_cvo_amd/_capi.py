@@ -290,6 +290,7 @@ EXPORTED = [
     "cvo_align_association", "cvo_debug_scalar_math", "cvo_debug_prim", "cvo_debug_verified_rows", "cvo_debug_device_memory", "cvo_cloud_upload_many",
     "cvo_ctx_set_option", "cvo_ctx_advice", "cvo_debug_cloud_order",
     "cvo_debug_cloud_order_route", "cvo_debug_order_route_rule", "cvo_debug_wide_plan",
+    "cvo_debug_wide_plan_at", "cvo_debug_cloud_wide_pivots",
     "cvo_process_hint_hw_queues", "cvo_shutdown",
     "cvo_batch_open", "cvo_batch_submit", "cvo_batch_poll", "cvo_batch_pending", "cvo_batch_stats", "cvo_batch_close",
     "cvo_inner_product_batch", "cvo_function_angle_batch", "cvo_debug_last_score_batch", "cvo_debug_cloud_tiles",
@@ -396,6 +397,8 @@ def lib(path=None):
     L.cvo_debug_cloud_tiles.argtypes = [vp, vp, fp, C.POINTER(C.c_int)]
     L.cvo_debug_order_route_rule.argtypes = [ip, ip, C.c_char_p, ip]
     L.cvo_debug_wide_plan.argtypes = [ip, C.POINTER(C.c_int), C.POINTER(C.c_int), ip, C.POINTER(C.c_int)]
+    L.cvo_debug_wide_plan_at.argtypes = [ip, ip, C.POINTER(C.c_int), ip, C.POINTER(C.c_int)]
+    L.cvo_debug_cloud_wide_pivots.argtypes = [vp, ip, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_int)]
     dp = C.POINTER(C.c_double)
     L.cvo_multiframe_align.argtypes = [vp, C.POINTER(cvo_params_t), ip, C.POINTER(vp), dp, C.POINTER(C.c_int), ip,
                                        C.POINTER(C.c_int), C.POINTER(cvo_multiframe_info_t),

@@ -529,6 +529,20 @@ def debug_wide_plan(n):
     return W.value, rows[:k.value]
 
 
+def debug_wide_plan_at(n, leaf):
+    """cvo_debug_wide_plan_at -> rows: debug_wide_plan's rows with leaves of at most `leaf` points (1024 .. 16384), the plan of a
+    context with WIDE_LEAF=leaf."""
+    k = C.c_int()
+    ipp = C.POINTER(C.c_int)
+    rc = _capi.lib().cvo_debug_wide_plan_at(int(n), int(leaf), None, 0, C.byref(k))
+    rows = np.zeros((max(k.value, 1), 4), np.int32)
+    if rc == 0:
+        rc = _capi.lib().cvo_debug_wide_plan_at(int(n), int(leaf), rows.ctypes.data_as(ipp), k.value, C.byref(k))
+    if rc != 0:
+        _raise(rc, "cvo_debug_wide_plan_at refused its arguments")
+    return rows[:k.value]
+
+
 def debug_lidar_atan2(y, x):
     """cvo_debug_lidar_atan2: the library's own atan2 in degrees (cvo_lidar_math.h, what the twin and the kernels compile),
     evaluated on the host for arrays y, x of doubles."""
@@ -586,6 +600,17 @@ class DeviceCloud:
         """cvo_debug_cloud_order_route: what ordered this cloud - 0 the host, 1 k_kd_order, 2 the multi-block ordering of
         ORDER=wide."""
         return int(self.gpu.L.cvo_debug_cloud_order_route(self.handle))
+
+    def debug_wide_pivots(self):
+        """cvo_debug_cloud_wide_pivots -> (pivot, rem), uint32 each: the select's result for every cut of the cloud's plan, in
+        plan order, as the device computed it.  Needs a context with WIDE_RECORD=1 and a cloud ordered by the multi-block
+        ordering; raises otherwise."""
+        n = C.c_int()
+        up = C.POINTER(C.c_uint)
+        self.gpu._check(self.gpu.L.cvo_debug_cloud_wide_pivots(self.handle, 0, None, None, C.byref(n)))
+        pivot, rem = np.zeros(max(n.value, 1), np.uint32), np.zeros(max(n.value, 1), np.uint32)
+        self.gpu._check(self.gpu.L.cvo_debug_cloud_wide_pivots(self.handle, n.value, pivot.ctypes.data_as(up), rem.ctypes.data_as(up), C.byref(n)))
+        return pivot[:n.value], rem[:n.value]
 
     def debug_tiles(self):
         """cvo_debug_cloud_tiles: the records k_overlap culls by, float32[ceil(n / 64), 8] - centre x, y, z, radius, box half

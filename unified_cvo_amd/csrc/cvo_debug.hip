@@ -109,15 +109,32 @@ int cvo_debug_order_route_rule(int n, int finite, const char* order_value, int n
 }
 
 int cvo_debug_wide_plan(int n, int* W, int* rows, int capacity, int* n_rows) {
-  if (n < 0 || n > KD_WIDE_MAX_POINTS || !n_rows || capacity < 0 || (capacity > 0 && !rows)) return CVO_E_INVALID;
   const int leaf = CtxOptions().wide_leaf;
-  if (W) *W = leaf;
+  const int rc = cvo_debug_wide_plan_at(n, leaf, rows, capacity, n_rows);
+  if (rc == CVO_OK && W) *W = leaf;
+  return rc;
+}
+
+int cvo_debug_wide_plan_at(int n, int leaf, int* rows, int capacity, int* n_rows) {
+  if (n < 0 || n > KD_WIDE_MAX_POINTS || !n_rows || capacity < 0 || (capacity > 0 && !rows)) return CVO_E_INVALID;
+  if (leaf < KD_THREADS || leaf > KD_MAX_POINTS) return CVO_E_INVALID;
   WidePlan P;
   wide_plan(n, leaf, P);
   *n_rows = (int)P.segs.size();
   for (int k = 0; k < std::min(capacity, *n_rows); k++) {
     const int row[4] = {P.seg_level[k], P.segs[k].lo, P.segs[k].hi, P.segs[k].left};
     std::memcpy(rows + 4 * (size_t)k, row, sizeof row);
+  }
+  return CVO_OK;
+}
+
+int cvo_debug_cloud_wide_pivots(const cvo_cloud* c, int capacity, unsigned* pivot, unsigned* rem, int* n_segments) {
+  if (!c || !n_segments || capacity < 0 || (capacity > 0 && (!pivot || !rem))) return CVO_E_INVALID;
+  if (c->order_route != ORDER_ROUTE_WIDE || c->h_wide_piv.empty()) return CVO_E_INVALID;
+  *n_segments = (int)(c->h_wide_piv.size() / 2);
+  for (int k = 0; k < std::min(capacity, *n_segments); k++) {
+    pivot[k] = c->h_wide_piv[2 * (size_t)k];
+    rem[k] = c->h_wide_piv[2 * (size_t)k + 1];
   }
   return CVO_OK;
 }

@@ -307,6 +307,7 @@ struct cvo_cloud : CloudArrays {
   mutable float4* tile4 = nullptr;  // (typed view of `tiles`)
   std::vector<int> h_order;  // host copy (the ELL is stored by sorted row; exports map it back)
   int order_route = 0;       // who made it (order_route, cvo_upload.hip): 0 the host, 1 k_kd_order, 2 the wide ordering
+  std::vector<unsigned> h_wide_piv;  // WIDE_RECORD=1, route 2: (pivot key, rem) of every planned segment (KdWide::seg_piv), else empty
   float cx = 0, cy = 0, cz = 0;  // centroid (used only as the cull centre)
   float rmax = 0;                // largest |p| (bounds the motion of any point under a pose change)
 };

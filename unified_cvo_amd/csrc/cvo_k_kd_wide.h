@@ -283,7 +283,9 @@ __global__ __launch_bounds__(KD_THREADS) void k_kd_wide_leaves(KdWide J) {
   const int* src = J.buf[L.level & 1] + L.lo;
   kd_order_levels(kd_key, L.n, L.NP, ext, J.seg_of_pos + L.sop_off, J.seg_lo + (size_t)blockIdx.x * 2 * J.seg_stride, J.seg_stride,
                   [&](unsigned id) { return J.x4[min((unsigned)src[id], (unsigned)J.n - 1u)]; });
-  for (int p = threadIdx.x; p < L.n; p += KD_THREADS) J.order[L.lo + p] = src[kd_key[p] & 0xffffull];
+  // (clamped like the reads above: k_cloud_gather scatters through `order` unguarded, so whatever the buffers hold, every id
+  // that leaves these kernels is one of the cloud's)
+  for (int p = threadIdx.x; p < L.n; p += KD_THREADS) J.order[L.lo + p] = (int)min((unsigned)src[kd_key[p] & 0xffffull], (unsigned)J.n - 1u);
 }
 
 }  // namespace cvo_dev

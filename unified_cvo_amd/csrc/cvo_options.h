@@ -41,6 +41,7 @@ struct CtxOptions {
   bool no_sort = false, no_long_lists = false, no_onehot = false, ip_chain = false, keep_columns = false, no_speculate = false;
   CloudOrder order = CloudOrder::Device;
   int wide_leaf = KD_WIDE_LEAF;  // ORDER=wide: the largest segment one block orders in LDS (cvo_k_kd_wide.h)
+  int wide_record = 0;           // ORDER=wide, tests only: 1 = an upload keeps the select's pivots (cvo_debug_cloud_wide_pivots)
   int row_max = ASSOC_CAP16;  // DevParams::row_max_cap; ASSOC_CAP16 = off
   int voxel_host = -1;        // cvo_voxel_select / cvo_cloud_upload_voxel: 1 = the CPU twin, 0 = the kernels, -1 = by size (cvo_voxel.hip)
   int rgbd_host = -1;         // cvo_rgbd_points / cvo_cloud_upload_rgbd: 1 = the CPU twin, 0 = the kernels, -1 = by size (cvo_rgbd.hip)
@@ -92,6 +93,7 @@ constexpr OptionSpec kOptions[] = {
     opt_flag("NO_SORT", &CtxOptions::no_sort),
     {"ORDER", OptKind::Order, nullptr, nullptr, nullptr, 0, 0},
     opt_int("WIDE_LEAF", &CtxOptions::wide_leaf, KD_THREADS, KD_MAX_POINTS),
+    opt_int("WIDE_RECORD", &CtxOptions::wide_record, 0, 1),
     opt_flag("NO_LONG_LISTS", &CtxOptions::no_long_lists),
     opt_int("ROW_MAX", &CtxOptions::row_max, 1, ASSOC_CAP16),
     opt_flag("NO_ONEHOT", &CtxOptions::no_onehot),

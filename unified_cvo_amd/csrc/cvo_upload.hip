@@ -425,6 +425,19 @@ static int finish_uploads(cvo_ctx* ctx, std::vector<StagedCloud>& clouds) {
     for (auto& sc : clouds)
       if (rc == CVO_OK && e == hipSuccess && sc.c && sc.job.n > 0)
         e = hipMemcpyAsync(sc.c->h_order.data(), sc.c->order, sizeof(int) * (size_t)sc.job.n, hipMemcpyDeviceToHost, ctx->upload_stream);
+    // WIDE_RECORD=1 (tests): the select's pivots of every wide cloud come down next to its order
+    if (ctx->opt.wide_record && !wide_jobs.empty()) {
+      size_t k = 0;
+      for (auto& sc : clouds) {
+        if (!(sc.c && sc.job.n > 0 && sc.wide)) continue;
+        if (rc == CVO_OK && e == hipSuccess) {
+          static_assert(sizeof(uint2) == 2 * sizeof(unsigned), "seg_piv is two words a segment");
+          sc.c->h_wide_piv.assign(2 * plans[k].segs.size(), 0u);
+          e = hipMemcpyAsync(sc.c->h_wide_piv.data(), wide[k].seg_piv, sizeof(uint2) * plans[k].segs.size(), hipMemcpyDeviceToHost, ctx->upload_stream);
+        }
+        k++;
+      }
+    }
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->upload_stream);
   if (rc != CVO_OK || e != hipSuccess) {
