@@ -91,8 +91,9 @@ SemanticBKIOctoMap::~SemanticBKIOctoMap() {
   if (map_) cvo_map_close(map_);
 }
 
-// the first insert opens the map with its free_res and max_range; a later one must name the same
-void SemanticBKIOctoMap::open_or_check(float ds_resolution, float free_res, float max_range) {
+// the first insert opens the map with its free_res and max_range; a later one must name the same.  Every insert names its kernel.
+void SemanticBKIOctoMap::open_or_check(const char* who, int kernel, float ds_resolution, float free_res, float max_range) {
+  const std::string w(who);
   if (!map_) {
     cfg_.ds_resolution = ds_resolution;
     cfg_.free_resolution = free_res;
@@ -100,23 +101,36 @@ void SemanticBKIOctoMap::open_or_check(float ds_resolution, float free_res, floa
     if (gpu_) {
       map_ = gpu_->map_open(cfg_);
     } else if (cvo_map_open_host(&cfg_, &map_) != CVO_OK) {
-      throw std::invalid_argument("insert_pointcloud_csm: the library refused the map's configuration");
+      throw std::invalid_argument(w + ": the library refused the map's configuration");
     }
   } else if (free_res != cfg_.free_resolution || max_range != cfg_.max_range) {
-    throw std::invalid_argument("insert_pointcloud_csm: free_res and max_range are fixed by the map's first insert");
+    throw std::invalid_argument(w + ": free_res and max_range are fixed by the map's first insert");
+  }
+  if (cvo_map_set_kernel(map_, kernel) != CVO_OK)
+    throw std::invalid_argument(w + ": " + (gpu_ ? gpu_->last_error() : std::string("the sparse kernel needs sf2 and ell finite and > 0")));
+}
+
+void SemanticBKIOctoMap::insert_resident(const char* who, int kernel, const cvo::CvoGPU::ResidentClouds& clouds, int k, const float pose12[12],
+                                         float ds_resolution, float free_res, float max_range) {
+  const std::string w(who);
+  if (!gpu_) throw std::invalid_argument(w + ": a map of the CPU twin takes host clouds");
+  if (!pose12) throw std::invalid_argument(w + ": no pose");
+  open_or_check(who, kernel, ds_resolution, free_res, max_range);
+  try {
+    gpu_->map_insert_cloud(map_, clouds, k, pose12, nullptr);
+  } catch (const std::invalid_argument& e) {
+    throw std::invalid_argument(w + ": " + e.what());
   }
 }
 
 void SemanticBKIOctoMap::insert_pointcloud_csm(const cvo::CvoGPU::ResidentClouds& clouds, int k, const float pose12[12], float ds_resolution,
                                                float free_res, float max_range) {
-  if (!gpu_) throw std::invalid_argument("insert_pointcloud_csm: a map of the CPU twin takes host clouds");
-  if (!pose12) throw std::invalid_argument("insert_pointcloud_csm: no pose");
-  open_or_check(ds_resolution, free_res, max_range);
-  try {
-    gpu_->map_insert_cloud(map_, clouds, k, pose12, nullptr);
-  } catch (const std::invalid_argument& e) {
-    throw std::invalid_argument(std::string("insert_pointcloud_csm: ") + e.what());
-  }
+  insert_resident("insert_pointcloud_csm", CVO_MAP_KERNEL_CSM, clouds, k, pose12, ds_resolution, free_res, max_range);
+}
+
+void SemanticBKIOctoMap::insert_pointcloud(const cvo::CvoGPU::ResidentClouds& clouds, int k, const float pose12[12], float ds_resolution,
+                                           float free_res, float max_range) {
+  insert_resident("insert_pointcloud", CVO_MAP_KERNEL_SPARSE, clouds, k, pose12, ds_resolution, free_res, max_range);
 }
 
 std::unique_ptr<cvo::CvoGPU::ResidentClouds> SemanticBKIOctoMap::resident_cloud() const {
@@ -129,10 +143,20 @@ std::unique_ptr<cvo::CvoGPU::ResidentClouds> SemanticBKIOctoMap::resident_cloud(
 }
 
 void SemanticBKIOctoMap::insert_pointcloud_csm(const CVOPointCloud* cloud, const point3f& origin, float ds_resolution, float free_res, float max_range) {
-  if (!cloud) throw std::invalid_argument("insert_pointcloud_csm: no cloud");
-  open_or_check(ds_resolution, free_res, max_range);
+  insert_host("insert_pointcloud_csm", CVO_MAP_KERNEL_CSM, cloud, origin, ds_resolution, free_res, max_range);
+}
+
+void SemanticBKIOctoMap::insert_pointcloud(const CVOPointCloud* cloud, const point3f& origin, float ds_resolution, float free_res, float max_range) {
+  insert_host("insert_pointcloud", CVO_MAP_KERNEL_SPARSE, cloud, origin, ds_resolution, free_res, max_range);
+}
+
+void SemanticBKIOctoMap::insert_host(const char* who, int kernel, const CVOPointCloud* cloud, const point3f& origin, float ds_resolution, float free_res,
+                                     float max_range) {
+  const std::string w(who);
+  if (!cloud) throw std::invalid_argument(w + ": no cloud");
+  open_or_check(who, kernel, ds_resolution, free_res, max_range);
   const int n = cloud->num_points(), C = cfg_.num_classes;
-  if (C > 0 && cloud->num_classes() != C) throw std::invalid_argument("insert_pointcloud_csm: the cloud's label rows do not have the map's classes");
+  if (C > 0 && cloud->num_classes() != C) throw std::invalid_argument(w + ": the cloud's label rows do not have the map's classes");
   std::vector<float> xyz(3 * (size_t)n), feat, label((size_t)C * n);
   if (cloud->feature_dimensions() == 5) feat.resize(5 * (size_t)n);
   for (int i = 0; i < n; i++) {
@@ -144,7 +168,7 @@ void SemanticBKIOctoMap::insert_pointcloud_csm(const CVOPointCloud* cloud, const
   const float* f = feat.empty() ? nullptr : feat.data();
   const float* l = C > 0 ? label.data() : nullptr;
   const int rc = gpu_ ? cvo_map_insert(map_, n, xyz.data(), f, l, origin.data()) : cvo_map_insert_host(map_, n, xyz.data(), f, l, origin.data());
-  if (rc != CVO_OK) throw std::invalid_argument("insert_pointcloud_csm: " + (gpu_ ? gpu_->last_error() : "the library refused the cloud (" + std::to_string(rc) + ")"));
+  if (rc != CVO_OK) throw std::invalid_argument(w + ": " + (gpu_ ? gpu_->last_error() : "the library refused the cloud (" + std::to_string(rc) + ")"));
 }
 
 }  // namespace semantic_bki

@@ -3,7 +3,9 @@
 //   semantic_bki::SemanticBKIOctoMap map(resolution, block_depth, num_class + 1, sf2, ell, prior, var_thresh, free_thresh, occupied_thresh);
 //   map.insert_pointcloud_csm(&transformed_pc, origin, ds_resolution, free_resolution, max_range);
 //   cvo::CvoPointCloud cloud_out(&map, num_class);
-// block_depth 1 only (std::invalid_argument otherwise); tests/np_bki.py states what is computed.  Defined in host/cvo_bki.cpp.
+// block_depth 1 only (std::invalid_argument otherwise); tests/np_bki.py states what is computed.  insert_pointcloud, whose
+// declaration upstream's header keeps commented out, is the same insert under the sparse kernel (cvo_map_set_kernel,
+// tests/np_bki_sparse.py); a map takes inserts of either kind in any order.  Defined in host/cvo_bki.cpp.
 #pragma once
 #include <memory>
 #include <ostream>
@@ -56,6 +58,11 @@ class SemanticBKIOctoMap {
   // pose's translation.  The first insert fixes free_res and max_range, as above.  A map of the CPU twin throws.
   void insert_pointcloud_csm(const cvo::CvoGPU::ResidentClouds& clouds, int k, const float pose12[12], float ds_resolution, float free_res,
                              float max_range);
+  // The same two inserts under the sparse kernel (SemanticBKInference::predict with covSparse over a block and its face
+  // neighbours; sf2 and ell are the constructor's): upstream's commented-out insert_pointcloud.  sf2 or ell not finite and > 0 throws.
+  void insert_pointcloud(const CVOPointCloud* cloud, const point3f& origin, float ds_resolution, float free_res, float max_range);
+  void insert_pointcloud(const cvo::CvoGPU::ResidentClouds& clouds, int k, const float pose12[12], float ds_resolution, float free_res,
+                         float max_range);
   // New: the occupied voxels as one resident cloud built on the device (cvo_map_cloud_resident), to align the next frame
   // against; what CvoPointCloud(&map, num_classes) uploaded would be.  Before the first insert: an empty cloud.
   std::unique_ptr<cvo::CvoGPU::ResidentClouds> resident_cloud() const;
@@ -69,7 +76,10 @@ class SemanticBKIOctoMap {
   const cvo::CvoGPU* gpu_ = nullptr;
   cvo_map_config_t cfg_;
   cvo_map* map_ = nullptr;
-  void open_or_check(float ds_resolution, float free_res, float max_range);
+  void open_or_check(const char* who, int kernel, float ds_resolution, float free_res, float max_range);
+  void insert_host(const char* who, int kernel, const CVOPointCloud* cloud, const point3f& origin, float ds_resolution, float free_res, float max_range);
+  void insert_resident(const char* who, int kernel, const cvo::CvoGPU::ResidentClouds& clouds, int k, const float pose12[12], float ds_resolution,
+                       float free_res, float max_range);
 };
 
 }  // namespace semantic_bki

@@ -549,7 +549,7 @@ typedef struct cvo_map_config_t {
   float resolution;      /* voxel edge, > 0 */
   int block_depth;       /* 1 */
   int num_classes;       /* C: classes of a label row, 0 .. 19; the map has C + 1, class 0 = free space */
-  float sf2, ell;        /* accepted, change nothing (as upstream's counting sensor model) */
+  float sf2, ell;        /* the sparse kernel's scale and length (cvo_map_set_kernel); the counting kernel ignores them, as upstream's */
   float prior;           /* ms of a new voxel, >= 0 */
   float var_thresh;      /* accepted, changes nothing */
   float free_thresh, occupied_thresh; /* in [0, 1] */
@@ -590,6 +590,20 @@ int cvo_map_insert_cloud(cvo_map* map, const cvo_cloud* cloud, const float pose1
  * one-hot detection, scores and solves; the rows go from k_bki_rows to cvo_cloud_from_device's ingest where they are, so its
  * route rule orders them (ORDER=wide above 16 384 voxels).  A map of the host side uploads the twin's rows. */
 int cvo_map_cloud_resident(cvo_map* map, cvo_cloud** out, long long* n);
+/* The kernel of the inserts that follow, on a map of either side or of cvo_map_open_host, between any two inserts; it applies
+ * to cvo_map_insert, _insert_posed, _insert_cloud and _insert_host alike.  CVO_MAP_KERNEL_CSM, the default: the counting
+ * sensor model above.  CVO_MAP_KERNEL_SPARSE: SemanticBKInference::predict with covSparse over get_extended_block's seven
+ * blocks, at block_depth 1 - every training point, beam samples and origin included, votes into the voxels of its blocks and
+ * of their face neighbours with the weight ((2 + cos 2 pi d)(1 - d) / 3 + sin 2 pi d / (2 pi)) sf2 of its distance d (in
+ * units of ell) to the voxel's centre, 0 from d = 1 on; every touched block and every face neighbour of one is stored.
+ * The statement is tests/np_bki_sparse.py (its own sin / cos routine, sums in ascending training order, slot by slot); the
+ * twin and the kernels of cvo_k_bki_sparse.h equal it bit for bit, and the same insert gives the same bits on every run.
+ * The side rule is unchanged.  One more cap: 2^24 block memberships or more in one sparse insert are CVO_E_UNSUPPORTED,
+ * nothing written.  CVO_E_INVALID, the map and its kernel as they were, cvo_last_error begins "cvo_map_set_kernel:": a NULL
+ * handle, an unknown kernel, SPARSE on a map whose sf2 or ell is not finite and > 0. */
+#define CVO_MAP_KERNEL_CSM 0
+#define CVO_MAP_KERNEL_SPARSE 1
+int cvo_map_set_kernel(cvo_map* map, int kernel);
 /* the CPU twin on a map without a context */
 int cvo_map_open_host(const cvo_map_config_t* cfg, cvo_map** out);
 void cvo_map_close_host(cvo_map* map);

@@ -313,7 +313,7 @@ EXPORTED = [
     "cvo_cloud_from_device", "cvo_cloud_from_device_many", "cvo_cloud_from_device_aos192",
     "cvo_debug_device_buffer", "cvo_debug_device_release",
     "cvo_cloud_merge", "cvo_cloud_download",
-    "cvo_map_insert_cloud", "cvo_map_cloud_resident",
+    "cvo_map_insert_cloud", "cvo_map_cloud_resident", "cvo_map_set_kernel",
 ]
 
 _libs = {}
@@ -489,6 +489,7 @@ def lib(path=None):
     L.cvo_cloud_merge.argtypes = [vp, ip, C.POINTER(vp), dp, C.c_float, C.POINTER(vp), ipp, ipp]
     L.cvo_cloud_download.argtypes = [vp, vp, fp, fp, fp, fp, ipp]
     L.cvo_map_insert_cloud.argtypes = [vp, vp, fp, fp]
+    L.cvo_map_set_kernel.argtypes = [vp, C.c_int]
     L.cvo_map_cloud_resident.argtypes = [vp, C.POINTER(vp), llp]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares

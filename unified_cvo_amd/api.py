@@ -659,7 +659,8 @@ class DeviceCloudAoS(DeviceCloud):
 
 class MapConfig:
     """cvo_map_config_t: the semantic voxel map's configuration; the defaults are those of upstream's driver
-    main_local_mapping.cpp.  sf2, ell, var_thresh and ds_resolution are accepted and change nothing, as upstream."""
+    main_local_mapping.cpp.  sf2 and ell are the sparse kernel's (SemanticMap.set_kernel); the counting kernel ignores them, and
+    var_thresh and ds_resolution are accepted and change nothing, as upstream."""
 
     FIELDS = ("resolution", "block_depth", "num_classes", "sf2", "ell", "prior", "var_thresh", "free_thresh", "occupied_thresh",
               "ds_resolution", "free_resolution", "max_range")
@@ -694,8 +695,9 @@ def _map_rows(pc_or_rows, num_classes):
 
 
 class SemanticMap:
-    """cvo_map: a semantic voxel map (upstream's SemanticBKIOctoMap under its counting sensor model, block_depth 1;
-    tests/np_bki.py states it).  CvoGPU.map_open makes one on a context; SemanticMap(None, config) is the CPU twin's."""
+    """cvo_map: a semantic voxel map (upstream's SemanticBKIOctoMap, block_depth 1, under its counting sensor model -
+    tests/np_bki.py states it - or, after set_kernel("sparse"), its sparse kernel - tests/np_bki_sparse.py).
+    CvoGPU.map_open makes one on a context; SemanticMap(None, config) is the CPU twin's."""
 
     def __init__(self, gpu, config=None, initial_voxels=0):
         self.gpu, self.config = gpu, config or MapConfig()
@@ -731,6 +733,16 @@ class SemanticMap:
         o = np.ascontiguousarray(origin, np.float32).reshape(3)
         call = self.L.cvo_map_insert if self.gpu is not None else self.L.cvo_map_insert_host
         return self._check(call(self.handle, xyz.shape[0], _fptr(xyz), _fptr(feat), _fptr(label), _fptr(o)), "cvo_map_insert_host refused the hits")
+
+    KERNELS = {"csm": 0, "sparse": 1}  # CVO_MAP_KERNEL_*
+
+    def set_kernel(self, kernel):
+        """cvo_map_set_kernel: "csm", the counting sensor model (the default), or "sparse", covSparse over a block and its
+        face neighbours (tests/np_bki_sparse.py states it); applies to every insert that follows."""
+        code = self.KERNELS.get(kernel, kernel)
+        if not isinstance(code, int):
+            raise ValueError(f"the kernel is 'csm' or 'sparse', got {kernel!r}")
+        return self._check(self.L.cvo_map_set_kernel(self.handle, code), "cvo_map_set_kernel refused the kernel")
 
     def insert_cloud(self, cloud, pose=None, origin=None):
         """cvo_map_insert_cloud: the rows of a resident cloud (DeviceCloud), in original order, as the hits of one insert,

@@ -4,7 +4,9 @@
 // block_depth 1 with the read-out of CvoPointCloud(const SemanticBKIOctoMap*, num_classes); tests/np_bki.py states what is
 // computed, the CPU twin (BkiHostMap) and the kernels of cvo_k_bki.h share cvo_bki_math.h.  A map lives on ONE side: a map
 // of a context takes its side at its first insert (switch BKI_HOST; unset: by that insert's training points) and keeps it,
-// its table does not migrate.  A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.
+// its table does not migrate.  cvo_map_set_kernel chooses what an insert computes: the counting sensor model above or the sparse
+// kernel (predict / covSparse over a block and its face neighbours; tests/np_bki_sparse.py, the twin bki_insert_sparse_cpu, the
+// kernels of cvo_k_bki_sparse.h).  A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.
 #include <unordered_map>
 
 namespace {
@@ -12,6 +14,9 @@ namespace {
 // training points of a map's FIRST insert below which the map lives on the host: the smallest frame whose ten inserts and
 // read-out took the device less time than the twin (profiles/bki/bki_probe.txt)
 constexpr long long BKI_HOST_BELOW = 2129;
+// ... and the same for a map whose kernel is the sparse one at its first insert (profiles/bki_sparse/bki_sparse_probe.txt): the
+// twin's sparse insert costs several times its counting insert, the device's less than twice
+constexpr long long BKI_SPARSE_HOST_BELOW = 547;
 
 struct BkiStats {
   int on_device = 0;
@@ -38,6 +43,7 @@ struct cvo_map {
   cvo_map_config_t cfg{};
   BkiConst k{};
   int side = -1;  // -1: no insert yet; 0: the device; 1: the host
+  int kernel = CVO_MAP_KERNEL_CSM;  // cvo_map_set_kernel: what the next insert runs
   bool broken = false;
   BkiHostMap host;
   // the device side: one allocation behind the table; the hits of an insert and its work arrays
@@ -193,6 +199,98 @@ int bki_insert_cpu(cvo_map* m, int n, const float* xyz, const float* feat, const
   return CVO_OK;
 }
 
+// ---- the sparse kernel on one thread (tests/np_bki_sparse.py) ----
+struct BkiSparseRecord {
+  unsigned long long key;
+  float p[3];
+  int cls, hit;
+};
+
+int bki_insert_sparse_cpu(cvo_map* m, int n, const float* xyz, const float* feat, const float* label, const float* origin, BkiStats* stats,
+                          std::string* msg) {
+  const BkiConst& k = m->k;
+  const float sf2 = m->cfg.sf2, ell = m->cfg.ell;
+  if (bki_training_count(k, n, xyz, origin, (unsigned long long)BKI_MAX_TRAINING) >= (unsigned long long)BKI_MAX_TRAINING)
+    return *msg = "2^24 training points or more in one insert, or a hit with 65536 beam samples or more", CVO_E_UNSUPPORTED;
+  // a first walk counts and checks (bki_members_cpu without a list), the second stores the records in training order
+  unsigned long long training = 0;
+  const int rc = bki_members_cpu(k, n, xyz, label, origin, nullptr, &training, msg);
+  if (rc != CVO_OK) return rc;
+  std::vector<BkiSparseRecord> rec;
+  auto point = [&](int i, int cls) {
+    return [&, i, cls](float x, float y, float z, bool hit) {
+      bki_members(k, x, y, z, [&](unsigned long long key) { rec.push_back(BkiSparseRecord{key, {x, y, z}, hit ? cls : 0, hit ? i : -1}); });
+      return rec.size() < (size_t)BKI_SPARSE_MAX_RECORDS;
+    };
+  };
+  for (int i = 0; i < n && rec.size() < (size_t)BKI_SPARSE_MAX_RECORDS; i++) {
+    const float* p = xyz + 3 * (size_t)i;
+    if (!bki_in_range(k, p, origin)) continue;
+    unsigned too_many = 0;
+    bki_hit_points(k, p, origin, &too_many, point(i, k.C > 0 ? bki_class(label + (size_t)i * k.C, k.C) : 1));
+  }
+  if (rec.size() < (size_t)BKI_SPARSE_MAX_RECORDS) point(n, 0)(origin[0], origin[1], origin[2], false);
+  if (rec.size() >= (size_t)BKI_SPARSE_MAX_RECORDS) return *msg = "2^24 block memberships or more in one insert under the sparse kernel", CVO_E_UNSUPPORTED;
+  // a block's training list: its records in training order, contiguous after a stable sort by key
+  std::stable_sort(rec.begin(), rec.end(), [](const BkiSparseRecord& a, const BkiSparseRecord& b) { return a.key < b.key; });
+  std::unordered_map<unsigned long long, std::pair<size_t, size_t>> seg;
+  unsigned long long longest = 0;
+  for (size_t b = 0; b < rec.size();) {
+    size_t e = b + 1;
+    while (e < rec.size() && rec[e].key == rec[b].key) e++;
+    seg.emplace(rec[b].key, std::make_pair(b, e));
+    longest = std::max<unsigned long long>(longest, e - b);
+    b = e;
+  }
+  // the test voxels: every touched block and its face neighbours, each once, new ones stored with ms = prior
+  BkiHostMap& h = m->host;
+  std::vector<unsigned> tests;
+  std::unordered_map<unsigned long long, char> seen;
+  for (size_t b = 0; b < rec.size(); b = seg[rec[b].key].second)
+    for (int j = 0; j < BKI_SPARSE_SLOTS; j++) {
+      unsigned long long key;
+      if (!bki_sparse_slot(rec[b].key, j, &key) || !seen.emplace(key, 1).second) continue;
+      auto it = h.index.find(key);
+      if (it == h.index.end()) {
+        it = h.index.emplace(key, (unsigned)h.keys.size()).first;
+        h.keys.push_back(key);
+        h.ms.resize(h.ms.size() + (size_t)k.nclass, k.prior);
+        h.fs.resize(h.fs.size() + BKI_FEAT, 0.f);
+      }
+      tests.push_back(it->second);
+    }
+  for (const unsigned v : tests) {
+    const unsigned long long vkey = h.keys[v];
+    const float centre[3] = {bki_centre((long long)(vkey >> 40), k.size), bki_centre((long long)((vkey >> 20) & 0xFFFFFull), k.size),
+                             bki_centre((long long)(vkey & 0xFFFFFull), k.size)};
+    for (int j = 0; j < BKI_SPARSE_SLOTS; j++) {
+      unsigned long long key;
+      if (!bki_sparse_slot(vkey, j, &key)) continue;
+      const auto it = seg.find(key);
+      if (it == seg.end()) continue;
+      float ybar[BKI_MAX_CLASSES + 1] = {}, fbar[BKI_FEAT] = {};
+      for (size_t r = it->second.first; r < it->second.second; r++) {
+        const float w = bki_sparse_k(centre, rec[r].p, sf2, ell);
+        ybar[rec[r].cls] += w;
+        if (rec[r].hit >= 0 && feat)
+          for (int f = 0; f < BKI_FEAT; f++) fbar[f] += w * feat[(size_t)rec[r].hit * BKI_FEAT + f];
+      }
+      for (int c = 0; c < k.nclass; c++) h.ms[v * (size_t)k.nclass + c] += ybar[c];
+      for (int f = 0; f < BKI_FEAT; f++) h.fs[v * BKI_FEAT + f] += fbar[f];
+    }
+  }
+  stats->training = training;
+  stats->members = rec.size();
+  stats->longest_run = longest;
+  return CVO_OK;
+}
+
+int bki_insert_cpu_kernel(cvo_map* m, int n, const float* xyz, const float* feat, const float* label, const float* origin, BkiStats* stats,
+                          std::string* msg) {
+  return m->kernel == CVO_MAP_KERNEL_SPARSE ? bki_insert_sparse_cpu(m, n, xyz, feat, label, origin, stats, msg)
+                                            : bki_insert_cpu(m, n, xyz, feat, label, origin, stats, msg);
+}
+
 // the occupied voxels of the host map in ascending key order
 std::vector<std::pair<unsigned long long, unsigned>> bki_occupied_cpu(const cvo_map* m) {
   std::vector<std::pair<unsigned long long, unsigned>> occ;
@@ -336,6 +434,65 @@ int bki_insert_counted(cvo_map* m, BkiInsertArgs& a, BkiCtl& h, BkiStats* stats)
   return CVO_OK;
 }
 
+// The rest of an insert under the sparse kernel, as bki_insert_counted: the table grows by seven voxels per membership - a
+// block and its face neighbours -, the records are stored, sorted by block, summed per test voxel (cvo_k_bki_sparse.h).
+int bki_insert_counted_sparse(cvo_map* m, BkiInsertArgs& a, BkiCtl& h, BkiStats* stats, const char* who) {
+  cvo_ctx* ctx = m->ctx;
+  hipStream_t st = ctx->upload_stream;
+  if (h.members >= (unsigned long long)BKI_SPARSE_MAX_RECORDS)
+    return fail(ctx, CVO_E_UNSUPPORTED, std::string(who) + ": 2^24 block memberships or more in one insert under the sparse kernel");
+  const size_t nrec = (size_t)h.members, nn = (size_t)a.n;
+  const unsigned nb = (unsigned)((nrec + SORT_THREADS - 1) / SORT_THREADS);
+  BkiSparseArgs s{};
+  unsigned* hist = nullptr;
+  int rc = m->work_scratch.lay_out(ctx, "voxel map work scratch", [&](ScratchLayout& l) {
+    l.take(s.key[0], nrec);
+    l.take(s.key[1], nrec);
+    l.take(s.val[0], nrec);
+    l.take(s.val[1], nrec);
+    l.take(s.pt, 3 * nrec);
+    l.take(s.meta, nrec);
+    l.take(s.base, nn + 2);
+    l.take(hist, 256 * (size_t)nb);
+    l.take(s.tests, BKI_SPARSE_SLOTS * nrec);
+    l.take(s.longlist, BKI_SPARSE_SLOTS * nrec / (BKI_SHORT_RUN + 1) + 1);
+  });
+  if (rc != CVO_OK) return rc;
+  if ((rc = bki_table_grow(m, m->voxels + BKI_SPARSE_SLOTS * h.members)) != CVO_OK) return rc;
+  a.t = m->t;
+  s.a = a;
+  s.sf2 = m->cfg.sf2;
+  s.ell = m->cfg.ell;
+  s.n_rec = (unsigned)nrec;
+  m->broken = true;  // (until the table's counters are back at zero)
+  m->occupied = -1;
+  const dim3 block(BKI_THREADS);
+  if (nrec) {  // (no membership: the origin alone, in a rounding gap between two boxes)
+    hipLaunchKernelGGL(k_bkis_offsets, dim3(1), dim3(BKIS_SCAN_THREADS), 0, st, s);
+    hipLaunchKernelGGL(k_bkis_emit, dim3(bki_blocks(nn + 1)), block, 0, st, s);
+    sort_pairs_u64(ctx, s.n_rec, s.key, s.val, hist);
+    const unsigned tests_grid = bki_stride_blocks(BKI_SPARSE_SLOTS * nrec);
+    hipLaunchKernelGGL(k_bkis_heads, dim3(bki_blocks(nrec)), block, 0, st, s);
+    hipLaunchKernelGGL(k_bkis_update, dim3(tests_grid), block, 0, st, s);
+    hipLaunchKernelGGL(k_bkis_long, dim3((unsigned)std::min<size_t>(BKI_SPARSE_SLOTS * nrec / (BKI_SHORT_RUN + 1) + 1, BKI_GRID_MAX)), dim3(BKI_WAVE), 0, st, s);
+    hipLaunchKernelGGL(k_bkis_reset, dim3(tests_grid), block, 0, st, s);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipMemcpyAsync(&h, a.ctl, sizeof h, hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  m->broken = false;
+  m->voxels += h.fresh;
+  stats->training = h.training;
+  stats->members = h.members;
+  stats->longest_run = h.longest_run;
+  stats->longest_probe = h.longest_probe;
+  return CVO_OK;
+}
+
+int bki_insert_counted_kernel(cvo_map* m, BkiInsertArgs& a, BkiCtl& h, BkiStats* stats, const char* who) {
+  return m->kernel == CVO_MAP_KERNEL_SPARSE ? bki_insert_counted_sparse(m, a, h, stats, who) : bki_insert_counted(m, a, h, stats);
+}
+
 int bki_insert_device(cvo_map* m, int n, const float* xyz, const float* feat, const float* label, const float* origin, BkiStats* stats) {
   cvo_ctx* ctx = m->ctx;
   hipStream_t st = ctx->upload_stream;
@@ -354,7 +511,7 @@ int bki_insert_device(cvo_map* m, int n, const float* xyz, const float* feat, co
   HIP_TRY(ctx, hipMemcpyAsync(&h, a.ctl, sizeof h, hipMemcpyDeviceToHost, st));
   HIP_TRY(ctx, hipStreamSynchronize(st));
   if ((rc = bki_count_refusal(ctx, "cvo_map_insert", h, n)) != CVO_OK) return rc;
-  return bki_insert_counted(m, a, h, stats);
+  return bki_insert_counted_kernel(m, a, h, stats, "cvo_map_insert");
 }
 
 // Collects and sorts the occupied voxels of a device map; *okey / *oslot point at the sorted arrays in work_scratch, *rows at
@@ -444,12 +601,16 @@ int bki_rows(cvo_map* m, bool want_rows, BkiRows* out) {
   return CVO_OK;
 }
 
+// the crossover of an undecided map: by the kernel its first insert runs
+long long bki_host_below(const cvo_map* m) { return m->kernel == CVO_MAP_KERNEL_SPARSE ? BKI_SPARSE_HOST_BELOW : BKI_HOST_BELOW; }
+
 // the side of a context's map, taken at its first insert
 int bki_choose_side(const cvo_map* m, int n, const float* xyz, const float* origin) {
   const int sw = m->ctx->opt.bki_host;
   if (sw >= 0) return sw > 0 ? 1 : 0;
   // (the count stops at the crossover: a large frame costs this no more than a small one)
-  return route_on_host(-1, (long long)bki_training_count(m->k, n, xyz, origin, (unsigned long long)BKI_HOST_BELOW), BKI_HOST_BELOW) ? 1 : 0;
+  const long long below = bki_host_below(m);
+  return route_on_host(-1, (long long)bki_training_count(m->k, n, xyz, origin, (unsigned long long)below), below) ? 1 : 0;
 }
 
 int bki_insert_entry(cvo_map* m, bool host_call, const char* who, int n, const float* xyz, const float* feat, const float* label, const float* origin) {
@@ -464,7 +625,7 @@ int bki_insert_entry(cvo_map* m, bool host_call, const char* who, int n, const f
     const int side = m->side >= 0 ? m->side : (ctx ? bki_choose_side(m, n, xyz, origin) : 1);
     if (side == 1) {
       std::string text;
-      r = bki_insert_cpu(m, n, xyz, feat, label, origin, &stats, &text);
+      r = bki_insert_cpu_kernel(m, n, xyz, feat, label, origin, &stats, &text);
       if (r != CVO_OK) return fail(ctx, r, std::string(who) + ": " + text);
       m->occupied = -1;
     } else {
@@ -581,7 +742,7 @@ int bki_insert_cloud_locked(cvo_map* m, const cvo_cloud* c, const float* pose12,
   HIP_TRY(ctx, hipStreamSynchronize(st));
   // (bki_validate_insert's check, made where the moved rows are)
   if (h.nonfinite != ~0u) return fail(ctx, CVO_E_INVALID, who + ": hit " + std::to_string(h.nonfinite) + " has a coordinate that is not finite");
-  if (side < 0) side = route_on_host(-1, (long long)h.training, BKI_HOST_BELOW) ? 1 : 0;
+  if (side < 0) side = route_on_host(-1, (long long)h.training, bki_host_below(m)) ? 1 : 0;
   BkiStats stats;
   if (side == 1) {  // the staged arrays are the three bki_insert_cpu takes
     std::vector<float> hx(3 * nn), hf(c_feat ? BKI_FEAT * nn : 0), hl((size_t)k.C * nn);
@@ -590,13 +751,13 @@ int bki_insert_cloud_locked(cvo_map* m, const cvo_cloud* c, const float* pose12,
     if (n && k.C > 0) HIP_TRY(ctx, hipMemcpyAsync(hl.data(), a.label, 4 * (size_t)k.C * nn, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     std::string text;
-    rc = bki_insert_cpu(m, n, hx.data(), c_feat ? hf.data() : nullptr, k.C > 0 ? hl.data() : nullptr, origin, &stats, &text);
+    rc = bki_insert_cpu_kernel(m, n, hx.data(), c_feat ? hf.data() : nullptr, k.C > 0 ? hl.data() : nullptr, origin, &stats, &text);
     if (rc != CVO_OK) return fail(ctx, rc, who + ": " + text);
     m->occupied = -1;
   } else {
     stats.on_device = 1;
     if ((rc = bki_count_refusal(ctx, who, h, n)) != CVO_OK) return rc;
-    if ((rc = bki_insert_counted(m, a, h, &stats)) != CVO_OK) return rc;
+    if ((rc = bki_insert_counted_kernel(m, a, h, &stats, who.c_str())) != CVO_OK) return rc;
   }
   m->side = side;
   m->last = stats;
@@ -701,6 +862,18 @@ int cvo_map_insert_posed(cvo_map* m, int n, const float* xyz, const float* feat,
   }
   const float origin[3] = {T[3], T[7], T[11]};
   return bki_insert_entry(m, false, "cvo_map_insert_posed", n, moved.data(), feat, label, origin);
+}
+
+int cvo_map_set_kernel(cvo_map* m, int kernel) {
+  if (!m) return CVO_E_INVALID;
+  cvo_ctx* ctx = m->ctx;
+  if (kernel != CVO_MAP_KERNEL_CSM && kernel != CVO_MAP_KERNEL_SPARSE) return fail(ctx, CVO_E_INVALID, "cvo_map_set_kernel: an unknown kernel");
+  if (kernel == CVO_MAP_KERNEL_SPARSE && !(std::isfinite(m->cfg.sf2) && m->cfg.sf2 > 0.f && std::isfinite(m->cfg.ell) && m->cfg.ell > 0.f))
+    return fail(ctx, CVO_E_INVALID, "cvo_map_set_kernel: the sparse kernel needs sf2 and ell finite and > 0");
+  return frontend_call(ctx, "cvo_map_set_kernel", [&] {
+    m->kernel = kernel;
+    return (int)CVO_OK;
+  });
 }
 
 int cvo_map_size(cvo_map* m, long long* voxels, long long* occupied) {

@@ -1,7 +1,8 @@
 // cvo_bki_math.h -- the arithmetic of the semantic voxel map (semantic_bki::SemanticBKIOctoMap under its counting sensor
 // model, block_depth = 1) that the CPU twin (cvo_bki.hip) and the kernels (cvo_k_bki.h) share, so that the two cannot drift:
 // the block index of a coordinate, the closed float box of a block, the beam samples of a hit, the class of a label row, the
-// state of a voxel and the rows of the cloud read out.  tests/np_bki.py states the same in numpy.  Everything here is plain
+// state of a voxel and the rows of the cloud read out - and, for the sparse kernel, the weight with its own sin / cos routine
+// and the neighbour slots.  tests/np_bki.py and tests/np_bki_sparse.py state the same in numpy.  Everything here is plain
 // float / double arithmetic without fused multiply-adds (the build compiles with -ffp-contract=off).
 #pragma once
 
@@ -149,6 +150,54 @@ __host__ __device__ inline void bki_row(const BkiConst& k, unsigned long long ke
     const float sum = bki_sum(ms, 0, k.nclass);
     for (int c = 1; c <= k.C; c++) label[c - 1] = ms[c] / sum;
   }
+}
+
+// ---- the sparse kernel (SemanticBKInference::predict / covSparse, get_extended_block; tests/np_bki_sparse.py) ----
+
+// memberships (work records) of ONE insert under the sparse kernel: the device sorts that many (key, record) pairs
+constexpr long long BKI_SPARSE_MAX_RECORDS = 1ll << 24;
+constexpr int BKI_SPARSE_SLOTS = 7;         // a voxel's neighbour slots: self, +x, -x, +y, -y, +z, -z
+constexpr float BKI_SPARSE_PI = 3.1415926f;  // upstream's constant
+constexpr float BKI_SPARSE_FAR = 1.5f;      // from this distance on (in units of ell) the weight is 0 without being evaluated
+
+// the block in neighbour slot j of `key`, get_extended_block's order; false: the index leaves the key's 20-bit field
+__host__ __device__ inline bool bki_sparse_slot(unsigned long long key, int j, unsigned long long* out) {
+  if (j == 0) return *out = key, true;
+  const int shift = 40 - 20 * ((j - 1) / 2);
+  const long long k = (long long)((key >> shift) & 0xFFFFFull) + ((j & 1) ? 1 : -1);
+  if (k < 0 || k > 0xFFFFFll) return false;
+  *out = (key & ~(0xFFFFFull << shift)) | ((unsigned long long)k << shift);
+  return true;
+}
+
+// sin and cos of a in [0, 3 pi), the statement's routine operation for operation: the quarter turn q nearest to a, r = a - q pi/2
+// in three steps (the first two exact), a polynomial each in z = r * r on |r| <= pi/4 by Horner's rule with separate
+// multiplies and adds, the quadrant's signs and swap.  cos 0 = 1 and sin 0 = 0 exactly.
+__host__ __device__ inline void bki_sparse_sincos(float a, float* s, float* c) {
+  const int q = (int)(a * 0.63661977f + 0.5f);
+  const float fq = (float)q;
+  float r = a - fq * 1.5703125f;
+  r = r - fq * 4.837512969970703125e-4f;
+  r = r - fq * 7.54978995489188216e-8f;
+  const float z = r * r;
+  const float ps = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
+  const float pc = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z - 0.5f * z + 1.0f;
+  const float s0 = (q & 1) ? pc : ps, c0 = (q & 1) ? ps : pc;
+  *s = (q & 2) ? -s0 : s0;
+  *c = ((q + 1) & 2) ? -c0 : c0;
+}
+
+// covSparse of one (voxel centre, training point) pair: d = |centre / ell - p / ell|, the squares summed left to right,
+// k = ((2 + cos 2 pi d)(1 - d) / 3 + sin 2 pi d / (2 pi)) sf2, negative values 0
+__host__ __device__ inline float bki_sparse_k(const float centre[3], const float p[3], float sf2, float ell) {
+  const float dx = centre[0] / ell - p[0] / ell, dy = centre[1] / ell - p[1] / ell, dz = centre[2] / ell - p[2] / ell;
+  const float d = sqrtf(dx * dx + dy * dy + dz * dz);
+  if (d >= BKI_SPARSE_FAR) return 0.f;
+  const float a = d * 2.0f * BKI_SPARSE_PI;
+  float s, c;
+  bki_sparse_sincos(a, &s, &c);
+  const float k = ((2.0f + c) * (1.0f - d) / 3.0f + s / (2.0f * BKI_SPARSE_PI)) * sf2;
+  return k < 0.f ? 0.f : k;
 }
 
 }  // namespace cvo_dev

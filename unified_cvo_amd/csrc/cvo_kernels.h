@@ -79,3 +79,4 @@
 #include "cvo_k_dfilter.h"
 #include "cvo_k_bki.h"
 #include "cvo_k_bki_stage.h"
+#include "cvo_k_bki_sparse.h"
