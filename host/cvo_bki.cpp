@@ -34,6 +34,12 @@ std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::map_resident_cloud(cvo_map* map)
   return out;
 }
 
+void CvoGPU::map_query_cloud(cvo_map* map, const ResidentClouds& clouds, int k, const float* pose12, const cvo_map_query_out_t& out) const {
+  if (k < 0 || k >= clouds.size()) throw std::invalid_argument("map_query_cloud: no such cloud");
+  std::lock_guard<std::mutex> lk(call_mutex);
+  if (cvo_map_query_cloud(map, clouds.handles[(size_t)k], pose12, &out) != CVO_OK) throw std::invalid_argument(cvo_last_error(ctx));
+}
+
 CvoPointCloud::CvoPointCloud(const semantic_bki::SemanticBKIOctoMap* map, const int num_classes) {
   if (!map || num_classes != map->num_classes()) throw std::invalid_argument("CvoPointCloud(map, num_classes): the map has another number of classes");
   num_classes_ = num_classes;
@@ -140,6 +146,128 @@ std::unique_ptr<cvo::CvoGPU::ResidentClouds> SemanticBKIOctoMap::resident_cloud(
     return gpu_->upload_clouds({&none});
   }
   return gpu_->map_resident_cloud(map_);
+}
+
+// ---- the read side ----
+struct SemanticBKIOctoMap::Reader {
+  cvo_map* map = nullptr;
+  bool host = true, temporary = false;
+  explicit Reader(const SemanticBKIOctoMap& m) : map(m.map_), host(m.gpu_ == nullptr) {
+    if (map) return;
+    cvo_map_config_t c = m.cfg_;
+    if (!(c.free_resolution > 0.f)) c.free_resolution = 1.f;
+    if (cvo_map_open_host(&c, &map) != CVO_OK) throw std::invalid_argument("SemanticBKIOctoMap: the library refused the map's configuration");
+    host = temporary = true;
+  }
+  ~Reader() {
+    if (temporary) cvo_map_close_host(map);
+  }
+  Reader(const Reader&) = delete;
+  Reader& operator=(const Reader&) = delete;
+};
+
+static void refused(const char* who, const cvo::CvoGPU* gpu, bool host, int rc) {
+  throw std::invalid_argument(std::string(who) + ": " + (gpu && !host ? gpu->last_error() : "the library refused the call (" + std::to_string(rc) + ")"));
+}
+
+std::vector<SemanticOcTreeNode> SemanticBKIOctoMap::nodes_of(const char* who, int n, const float* xyz, const cvo::CvoGPU::ResidentClouds* clouds,
+                                                             int k, const float* pose12) const {
+  const Reader r(*this);
+  const size_t nn = (size_t)n, nc = (size_t)(cfg_.num_classes > 1 ? cfg_.num_classes : 1) + 1;
+  std::vector<std::uint8_t> found(nn), state(nn);
+  std::vector<std::int32_t> sem(nn);
+  std::vector<float> probs(nc * nn), vars(nc * nn), feat(5 * nn), centre(3 * nn);
+  const cvo_map_query_out_t out{found.data(), state.data(), sem.data(), probs.data(), vars.data(), feat.data(), centre.data()};
+  if (clouds) {
+    if (r.host) throw std::invalid_argument(std::string(who) + (gpu_ ? ": nothing is inserted yet" : ": a map of the CPU twin takes points, not a resident cloud"));
+    try {
+      gpu_->map_query_cloud(r.map, *clouds, k, pose12, out);
+    } catch (const std::invalid_argument& e) {
+      throw std::invalid_argument(std::string(who) + ": " + e.what());
+    }
+  } else {
+    const int rc = r.host ? cvo_map_query_host(r.map, n, xyz, &out) : cvo_map_query(r.map, n, xyz, &out);
+    if (rc != CVO_OK) refused(who, gpu_, r.host, rc);
+  }
+  std::vector<SemanticOcTreeNode> nodes(nn);
+  for (size_t i = 0; i < nn; i++) {
+    SemanticOcTreeNode& s = nodes[i];
+    s.state_ = (State)state[i];
+    s.semantics_ = sem[i];
+    s.found_ = found[i];
+    s.probs_.assign(probs.begin() + (long)(nc * i), probs.begin() + (long)(nc * (i + 1)));
+    s.vars_.assign(vars.begin() + (long)(nc * i), vars.begin() + (long)(nc * (i + 1)));
+    for (int c = 0; c < 5; c++) s.feat_[c] = feat[5 * i + c];
+    s.centre_ = point3f(centre[3 * i], centre[3 * i + 1], centre[3 * i + 2]);
+  }
+  return nodes;
+}
+
+SemanticOcTreeNode SemanticBKIOctoMap::search(point3f p) const { return nodes_of("search", 1, p.data(), nullptr, 0, nullptr)[0]; }
+
+SemanticOcTreeNode SemanticBKIOctoMap::search(float x, float y, float z) const { return search(point3f(x, y, z)); }
+
+static std::vector<float> packed(const std::vector<point3f>& pts) {
+  std::vector<float> xyz(3 * pts.size());
+  for (size_t i = 0; i < pts.size(); i++)
+    for (int a = 0; a < 3; a++) xyz[3 * i + a] = pts[i].data()[a];
+  return xyz;
+}
+
+std::vector<SemanticOcTreeNode> SemanticBKIOctoMap::search(const std::vector<point3f>& points) const {
+  const std::vector<float> xyz = packed(points);
+  return nodes_of("search", (int)points.size(), xyz.data(), nullptr, 0, nullptr);
+}
+
+std::vector<SemanticOcTreeNode> SemanticBKIOctoMap::search(const cvo::CvoGPU::ResidentClouds& clouds, int k, const float pose12[12]) const {
+  if (k < 0 || k >= clouds.size()) throw std::invalid_argument("search: no such cloud");
+  return nodes_of("search", clouds.num_points(k), nullptr, &clouds, k, pose12);
+}
+
+std::vector<RayHit> SemanticBKIOctoMap::raycast(const std::vector<point3f>& origins, const std::vector<point3f>& ends, unsigned stop_mask,
+                                                int max_steps) const {
+  if (origins.size() != ends.size()) throw std::invalid_argument("raycast: origins and ends differ in number");
+  const Reader r(*this);
+  const size_t n = ends.size();
+  const std::vector<float> o = packed(origins), e = packed(ends);
+  std::vector<std::uint8_t> status(n), state(n);
+  std::vector<std::uint64_t> key(n);
+  std::vector<std::int32_t> steps(n), sem(n);
+  std::vector<float> centre(3 * n), t(n);
+  const cvo_map_ray_out_t out{status.data(), key.data(), centre.data(), t.data(), steps.data(), state.data(), sem.data()};
+  const int rc = r.host ? cvo_map_raycast_host(r.map, (int)n, o.data(), e.data(), stop_mask, max_steps, &out)
+                        : cvo_map_raycast(r.map, (int)n, o.data(), e.data(), stop_mask, max_steps, &out);
+  if (rc != CVO_OK) refused("raycast", gpu_, r.host, rc);
+  std::vector<RayHit> hits(n);
+  for (size_t i = 0; i < n; i++) {
+    hits[i].status = status[i];
+    hits[i].steps = steps[i];
+    hits[i].semantics = sem[i];
+    hits[i].state = (State)state[i];
+    hits[i].key = key[i];
+    hits[i].centre = point3f(centre[3 * i], centre[3 * i + 1], centre[3 * i + 2]);
+    hits[i].t = t[i];
+  }
+  return hits;
+}
+
+MapView SemanticBKIOctoMap::render(const float pose12[12], float fx, float fy, float cx, float cy, int rows, int cols, float z_far,
+                                   unsigned stop_mask) const {
+  if (rows < 1 || cols < 1 || (long long)rows * cols > (1ll << 24)) throw std::invalid_argument("render: rows and cols are at least 1, at most 2^24 pixels");
+  const Reader r(*this);
+  MapView v;
+  v.rows = rows, v.cols = cols, v.num_classes = cfg_.num_classes;
+  const size_t px = (size_t)rows * cols;
+  v.depth.resize(px);
+  v.semantics.resize(px);
+  v.feat.resize(5 * px);
+  v.label.resize((size_t)cfg_.num_classes * px);
+  static_assert(sizeof(int) == sizeof(std::int32_t), "MapView::semantics holds the library's int32");
+  const cvo_map_render_out_t out{v.depth.data(), (std::int32_t*)v.semantics.data(), v.feat.data(), v.label.empty() ? nullptr : v.label.data()};
+  const int rc = r.host ? cvo_map_render_host(r.map, pose12, fx, fy, cx, cy, rows, cols, z_far, stop_mask, &out)
+                        : cvo_map_render(r.map, pose12, fx, fy, cx, cy, rows, cols, z_far, stop_mask, &out);
+  if (rc != CVO_OK) refused("render", gpu_, r.host, rc);
+  return v;
 }
 
 void SemanticBKIOctoMap::insert_pointcloud_csm(const CVOPointCloud* cloud, const point3f& origin, float ds_resolution, float free_res, float max_range) {

@@ -225,6 +225,9 @@ class CvoGPU {
   // resident cloud.  Refusals throw std::invalid_argument.
   void map_insert_cloud(cvo_map* map, const ResidentClouds& clouds, int k, const float* pose12, const float* origin) const;
   std::unique_ptr<ResidentClouds> map_resident_cloud(cvo_map* map) const;
+  // New: cvo_map_query_cloud for cloud k of `clouds` (SemanticBKIOctoMap::search(const ResidentClouds&, ...) is this): what is at
+  // its rows, moved by pose12 (nullptr: as stored), without a host copy.  Refusals throw std::invalid_argument.
+  void map_query_cloud(cvo_map* map, const ResidentClouds& clouds, int k, const float* pose12, const cvo_map_query_out_t& out) const;
   std::string last_error() const;
 
  private:

@@ -609,6 +609,106 @@ int cvo_map_open_host(const cvo_map_config_t* cfg, cvo_map** out);
 void cvo_map_close_host(cvo_map* map);
 int cvo_map_insert_host(cvo_map* map, int n, const float* xyz, const float* feat, const float* label, const float origin[3]);
 int cvo_map_cloud_host(cvo_map* map, long long capacity, float* xyz, float* feat, float* label, long long* n);
+/* ---- the read side of the map: what is at this point, what does this segment meet first, what does the map look like from
+ * this pose.  The statement is tests/np_bki_query.py; the CPU twin and the kernels of cvo_k_bki_query.h equal it bit for bit
+ * (shared arithmetic: cvo_bki_math.h).  A query only reads: the table (keys, ms, fs, counters) is bit for bit what it was.
+ * It runs where the map lives - a map of the device side on the context's upload stream, ordered behind every insert and
+ * synchronised on return; a map of the host side, and a map without an insert, which stays undecided, through the twin.
+ *
+ * cvo_map_query is upstream's SemanticBKIOctoMap::search(x, y, z) over n points (xyz n x 3, map frame) with the node's
+ * getters.  A point's voxel is the key of its k0 = int64(p / (double)resolution + 524288.5) per axis (block_to_hash_key) -
+ * ONE voxel, not the up to 8 closed boxes an inserted hit belongs to: a point on a face was stored in two voxels and is found
+ * in one.  Every output pointer may be NULL:
+ *   found      1: a stored voxel has this key; 0: none; 2: "outside" - a coordinate is not finite or a k0 leaves [1, 2^20 - 2]
+ *   state      0 FREE, 1 OCCUPIED, 2 UNKNOWN: get_state, for a stored voxel the read-out's rule on its ms
+ *   semantics  get_semantics: the first maximum of ms / sum in float (Semantics::update's max_element over get_probs)
+ *   probs      n x (max(num_classes, 1) + 1): get_probs, ms[c] / sum
+ *   vars       as probs: get_vars, ((ms[c] / sum) - (ms[c] / sum) * (ms[c] / sum)) / (sum + 1), each operation a float operation
+ *   feat       n x 5: get_features, fs / (sum of ms[1:])
+ *   centre     n x 3: float(k0 - 524288) * resolution per axis
+ * A point without a stored voxel is answered by upstream's default node Semantics(): found 0, state UNKNOWN, ms = prior in
+ * every class and fs = 0 pushed through the same float expressions (prior 0: NaN probabilities, as upstream's), semantics -1
+ * (upstream leaves the member uninitialised; -1 is this library's choice).  A point "outside" is answered the same way with
+ * found 2 and a NaN centre - a deliberate difference from the inserts, which refuse such a coordinate: a query is read-only,
+ * and one bad pixel must not fail a frame.
+ * Refused, CVO_E_INVALID, cvo_last_error begins with the function's name: a NULL map, n < 0, xyz NULL with n > 0 (n == 0 is
+ * accepted); a map of cvo_map_open_host given to cvo_map_query or a map of a context given to cvo_map_query_host.
+ * cvo_map_query_cloud: the rows of a resident cloud, in ORIGINAL order, moved as cvo_cloud_transformed moves them
+ * (transform_point_pose_vec; pose12 NULL: the stored bits); on a map of the device side no row passes through the host
+ * (k_bki_query reads x4[i] as k_bki_stage does).  The results equal cvo_map_query of cvo_cloud_download's coordinates moved
+ * on the host with the same float arithmetic, bit for bit.  Also refused: a NULL cloud, a cloud of another context, a map of
+ * cvo_map_open_host, a pose that is not finite. */
+typedef struct cvo_map_query_out_t {
+  uint8_t* found;
+  uint8_t* state;
+  int32_t* semantics;
+  float* probs;
+  float* vars;
+  float* feat;
+  float* centre;
+} cvo_map_query_out_t;
+int cvo_map_query(cvo_map* map, int n, const float* xyz, const cvo_map_query_out_t* out);
+int cvo_map_query_cloud(cvo_map* map, const cvo_cloud* cloud, const float pose12[12], const cvo_map_query_out_t* out);
+int cvo_map_query_host(cvo_map* map, int n, const float* xyz, const cvo_map_query_out_t* out);
+/* cvo_map_raycast: n_rays segments origin[i] -> end[i] (3 floats each, map frame).  This is the library's own walk over
+ * the map's voxels, written for this library; it is NOT upstream's RayCaster and is not compared with it.  RayCaster has no
+ * caller upstream, and its text stands against restating it: its diagonal branch takes three from the step count for two
+ * steps; a ray whose start block is not stored sees nothing at all; and with xy_error > 0 and xz_error == 0 (or xy_error < 0
+ * and yz_error == 0) none of its four branches applies, so the same voxel is returned until the count runs out.
+ * The walk visits every voxel the segment passes through, face by face.  k0[a], k1[a]: the k0 of origin and end per axis;
+ * N[a] = |k1[a] - k0[a]|, s[a] its sign.  The walk has exactly 1 + N[x] + N[y] + N[z] voxels.  The i-th crossing on axis a
+ * (i = 1 .. N[a]) lies at b = ((k0[a] - 524288) + s[a] (i - 0.5)) * (double)resolution, its parameter is
+ * t = (b - (double)o[a]) / ((double)e[a] - (double)o[a]), every operation one IEEE double operation.  Each step takes the
+ * axis whose next crossing has the smallest t, ties go to the lowest axis (a corner is two or three face steps).  At every
+ * voxel, the origin's included, the stored state is looked up - FREE is bit 1, OCCUPIED 2, UNKNOWN 4, no stored voxel 8 - and
+ * the walk stops at the first voxel whose bit is in stop_mask (0 is valid: the walk reaches the end).
+ * Per ray, every pointer optional:
+ *   status     0: reached the end's voxel without stopping; 1: stopped; 2: more than max_steps voxels, nothing walked;
+ *              3: an endpoint not finite or outside the key range, nothing walked
+ *   key        (kx << 40) | (ky << 20) | kz of the last voxel visited - the stopping voxel, on status 0 the end's; ~0 when
+ *              nothing was walked (centre then NaN, t 0, steps 0, state UNKNOWN, semantics -1)
+ *   centre     3 floats, t: the float cast of the entering crossing's double t (0 in the origin's voxel), steps: voxels visited
+ *   state, semantics   of that voxel, as cvo_map_query answers (not stored: UNKNOWN, -1)
+ * max_steps lies in 1 .. 2^20.  Refused, CVO_E_INVALID: a NULL map, n_rays < 0, origin or end NULL with n_rays > 0,
+ * max_steps outside its range, stop_mask above 15, the wrong kind of map for the entry point. */
+typedef struct cvo_map_ray_out_t {
+  uint8_t* status;
+  uint64_t* key;
+  float* centre;
+  float* t;
+  int32_t* steps;
+  uint8_t* state;
+  int32_t* semantics;
+} cvo_map_ray_out_t;
+#define CVO_MAP_STOP_FREE 1u
+#define CVO_MAP_STOP_OCCUPIED 2u
+#define CVO_MAP_STOP_UNKNOWN 4u
+#define CVO_MAP_STOP_ABSENT 8u
+int cvo_map_raycast(cvo_map* map, int n_rays, const float* origin, const float* end, unsigned stop_mask, int max_steps,
+                    const cvo_map_ray_out_t* out);
+int cvo_map_raycast_host(cvo_map* map, int n_rays, const float* origin, const float* end, unsigned stop_mask, int max_steps,
+                         const cvo_map_ray_out_t* out);
+/* cvo_map_render: one ray of cvo_map_raycast per pixel of a pinhole camera at pose12 (3x4 row-major, camera to map).  Pixel
+ * (u, v) - column, row - has the camera-frame end point (((u - cx) / fx) * z_far, ((v - cy) / fy) * z_far, z_far) in float,
+ * each operation rounded on its own, moved by the pose with transform_point_pose_vec; the origin is the pose's translation.
+ * The rays are made on the device.  Every plane is optional, rows x cols row-major:
+ *   depth      (float)(t * (double)z_far) of the stopping voxel's entering crossing: a z-depth; 0: no stop
+ *   semantics  of the stopping voxel; -1: no stop (or a stop at a voxel that is not stored, with bit 8 in the mask)
+ *   feat       x 5: get_features; zeros without a stop
+ *   label      x num_classes: get_occupied_probs, the layout cvo_rgbd_frame_t::semantic takes; zeros without a stop
+ * max_steps is 2^20: a ray that would need more voxels, or whose end leaves the key range, renders as no stop.
+ * Refused: CVO_E_INVALID - a NULL map or pose, rows or cols < 1, fx, fy or z_far not finite or <= 0, cx or cy not finite, a
+ * pose that is not finite, stop_mask above 15; CVO_E_UNSUPPORTED - more than 2^24 pixels. */
+typedef struct cvo_map_render_out_t {
+  float* depth;
+  int32_t* semantics;
+  float* feat;
+  float* label;
+} cvo_map_render_out_t;
+int cvo_map_render(cvo_map* map, const float pose12[12], float fx, float fy, float cx, float cy, int rows, int cols, float z_far,
+                   unsigned stop_mask, const cvo_map_render_out_t* out);
+int cvo_map_render_host(cvo_map* map, const float pose12[12], float fx, float fy, float cx, float cy, int rows, int cols, float z_far,
+                        unsigned stop_mask, const cvo_map_render_out_t* out);
 int cvo_cloud_size(const cvo_cloud* c);
 void cvo_cloud_free(cvo_cloud* c);
 

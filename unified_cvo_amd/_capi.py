@@ -257,6 +257,29 @@ class cvo_map_config_t(C.Structure):
                 ("ds_resolution", C.c_float), ("free_resolution", C.c_float), ("max_range", C.c_float)]
 
 
+class cvo_map_query_out_t(C.Structure):
+    """Output pointers of cvo_map_query / _query_cloud / _query_host; each may be NULL."""
+
+    _fields_ = [("found", C.c_void_p), ("state", C.c_void_p), ("semantics", C.c_void_p), ("probs", C.c_void_p), ("vars", C.c_void_p),
+                ("feat", C.c_void_p), ("centre", C.c_void_p)]
+
+
+class cvo_map_ray_out_t(C.Structure):
+    """Output pointers of cvo_map_raycast(_host); each may be NULL."""
+
+    _fields_ = [("status", C.c_void_p), ("key", C.c_void_p), ("centre", C.c_void_p), ("t", C.c_void_p), ("steps", C.c_void_p),
+                ("state", C.c_void_p), ("semantics", C.c_void_p)]
+
+
+class cvo_map_render_out_t(C.Structure):
+    """Output planes of cvo_map_render(_host); each may be NULL."""
+
+    _fields_ = [("depth", C.c_void_p), ("semantics", C.c_void_p), ("feat", C.c_void_p), ("label", C.c_void_p)]
+
+
+CVO_MAP_STOP_FREE, CVO_MAP_STOP_OCCUPIED, CVO_MAP_STOP_UNKNOWN, CVO_MAP_STOP_ABSENT = 1, 2, 4, 8
+
+
 class cvo_device_rows_t(C.Structure):
     """Rows of one cloud in device memory (cvo_cloud_from_device): byte strides, optional row indices."""
 
@@ -314,6 +337,8 @@ EXPORTED = [
     "cvo_debug_device_buffer", "cvo_debug_device_release",
     "cvo_cloud_merge", "cvo_cloud_download",
     "cvo_map_insert_cloud", "cvo_map_cloud_resident", "cvo_map_set_kernel",
+    "cvo_map_query", "cvo_map_query_cloud", "cvo_map_query_host", "cvo_map_raycast", "cvo_map_raycast_host",
+    "cvo_map_render", "cvo_map_render_host",
 ]
 
 _libs = {}
@@ -491,6 +516,14 @@ def lib(path=None):
     L.cvo_map_insert_cloud.argtypes = [vp, vp, fp, fp]
     L.cvo_map_set_kernel.argtypes = [vp, C.c_int]
     L.cvo_map_cloud_resident.argtypes = [vp, C.POINTER(vp), llp]
+    qo, ro, vo = C.POINTER(cvo_map_query_out_t), C.POINTER(cvo_map_ray_out_t), C.POINTER(cvo_map_render_out_t)
+    L.cvo_map_query.argtypes = [vp, ip, fp, qo]
+    L.cvo_map_query_host.argtypes = [vp, ip, fp, qo]
+    L.cvo_map_query_cloud.argtypes = [vp, vp, fp, qo]
+    L.cvo_map_raycast.argtypes = [vp, ip, fp, fp, C.c_uint, ip, ro]
+    L.cvo_map_raycast_host.argtypes = [vp, ip, fp, fp, C.c_uint, ip, ro]
+    L.cvo_map_render.argtypes = [vp, fp] + [C.c_float] * 4 + [ip, ip, C.c_float, C.c_uint, vo]
+    L.cvo_map_render_host.argtypes = [vp, fp] + [C.c_float] * 4 + [ip, ip, C.c_float, C.c_uint, vo]
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

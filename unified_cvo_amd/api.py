@@ -4,6 +4,7 @@ include/UnifiedCvo/cvo/CvoGPU.hpp:49-229, utils/CvoPointCloud.hpp:126-188), over
 This is the harness used by tests/ and bench.py; the C++ veneer with the same names lives in
 include/UnifiedCvo/.  All compute happens in libcvo_hip.so on the GPU.
 """
+import collections
 import ctypes as C
 import weakref
 import os
@@ -657,6 +658,12 @@ class DeviceCloudAoS(DeviceCloud):
         self.handle = h
 
 
+# what SemanticMap.query / raycast / render return: one numpy array per output of the C call
+MapQuery = collections.namedtuple("MapQuery", "found state semantics probs vars feat centre")
+MapRays = collections.namedtuple("MapRays", "status key centre t steps state semantics")
+MapView = collections.namedtuple("MapView", "depth semantics feat label")
+
+
 class MapConfig:
     """cvo_map_config_t: the semantic voxel map's configuration; the defaults are those of upstream's driver
     main_local_mapping.cpp.  sf2 and ell are the sparse kernel's (SemanticMap.set_kernel); the counting kernel ignores them, and
@@ -770,6 +777,114 @@ class SemanticMap:
         h, n = C.c_void_p(), C.c_longlong()
         self._check(self.L.cvo_map_cloud_resident(self.handle, C.byref(h), C.byref(n)), "")
         return self.gpu._adopt(h, n.value)
+
+    STOP_BITS = {"free": 1, "occupied": 2, "unknown": 4, "absent": 8}  # CVO_MAP_STOP_*
+
+    @classmethod
+    def stop_mask(cls, stop):
+        """The stop mask of raycast / render: an int 0 .. 15, or names out of "free", "occupied", "unknown", "absent"."""
+        if isinstance(stop, (int, np.integer)) and not isinstance(stop, bool):
+            mask = int(stop)
+        else:
+            names = (stop,) if isinstance(stop, str) else tuple(stop)
+            unknown = [s for s in names if s not in cls.STOP_BITS]
+            if unknown:
+                raise ValueError(f"a stop is one of {sorted(cls.STOP_BITS)}, got {unknown[0]!r}")
+            mask = 0
+            for s in names:
+                mask |= cls.STOP_BITS[s]
+        if not 0 <= mask <= 15:
+            raise ValueError(f"the stop mask lies in 0 .. 15, got {mask}")
+        return mask
+
+    def _classes(self):
+        return max(self.config.num_classes, 1) + 1
+
+    def query(self, points_or_cloud, pose=None):
+        """cvo_map_query(_host) / cvo_map_query_cloud: what is at these points - upstream's search(x, y, z) with the node's
+        getters, batched.  points (n, 3) in the map frame, or a resident cloud (DeviceCloud) whose rows, in original order, are
+        moved by `pose` (3x4 or 4x4; None: as stored) on the device.  -> MapQuery(found, state, semantics, probs, vars, feat,
+        centre); found: 0 no stored voxel (the default node answers), 1 stored, 2 outside the map's key range or not finite."""
+        is_cloud = isinstance(points_or_cloud, DeviceCloud)
+        T = None
+        if pose is not None:
+            if not is_cloud:
+                raise ValueError("a pose moves a resident cloud; points are given in the map frame")
+            P = np.asarray(pose, np.float32)
+            if P.shape not in ((3, 4), (4, 4)):
+                raise ValueError(f"the pose is 3x4 or 4x4, got {P.shape}")
+            T = np.ascontiguousarray(P[:3, :4])
+        if is_cloud:
+            if self.gpu is None:
+                raise ValueError("a host map takes points, not a resident cloud")
+            n, xyz = int(points_or_cloud.n), None
+        else:
+            xyz = np.asarray(points_or_cloud, np.float32)
+            if xyz.ndim != 2 or xyz.shape[1] != 3:
+                raise ValueError(f"the points are (n, 3), got {xyz.shape}")
+            xyz = np.ascontiguousarray(xyz)
+            n = xyz.shape[0]
+        nc = self._classes()
+        r = MapQuery(np.zeros(n, np.uint8), np.zeros(n, np.uint8), np.zeros(n, np.int32), np.zeros((n, nc), np.float32),
+                     np.zeros((n, nc), np.float32), np.zeros((n, 5), np.float32), np.zeros((n, 3), np.float32))
+        out = _capi.cvo_map_query_out_t(*[a.ctypes.data for a in r])
+        if is_cloud:
+            self._check(self.L.cvo_map_query_cloud(self.handle, points_or_cloud.handle, _fptr(T), C.byref(out)), "")
+        else:
+            call = self.L.cvo_map_query if self.gpu is not None else self.L.cvo_map_query_host
+            self._check(call(self.handle, n, _fptr(xyz), C.byref(out)), "cvo_map_query_host refused the points")
+        return r
+
+    def raycast(self, origin, end, stop=("occupied",), max_steps=1 << 20):
+        """cvo_map_raycast(_host): the library's own walk (not upstream's RayCaster) over the voxels each segment
+        origin[i] -> end[i] passes through, face by face, to the first voxel whose state is in `stop` (names or a mask; 0 walks
+        to the end).  origin may be one point for all rays.  -> MapRays(status, key, centre, t, steps, state, semantics);
+        status: 0 reached the end, 1 stopped, 2 more than max_steps voxels, 3 an endpoint outside the map."""
+        mask = self.stop_mask(stop)
+        e = np.asarray(end, np.float32)
+        if e.ndim != 2 or e.shape[1] != 3:
+            raise ValueError(f"the ends are (n, 3), got {e.shape}")
+        o = np.asarray(origin, np.float32)
+        if o.shape == (3,):
+            o = np.broadcast_to(o, e.shape)
+        if o.shape != e.shape:
+            raise ValueError(f"origins {o.shape} and ends {e.shape} differ in shape")
+        if not 1 <= int(max_steps) <= 1 << 20:
+            raise ValueError(f"max_steps lies in 1 .. 2^20, got {max_steps}")
+        o, e, n = np.ascontiguousarray(o), np.ascontiguousarray(e), e.shape[0]
+        r = MapRays(np.zeros(n, np.uint8), np.zeros(n, np.uint64), np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32),
+                    np.zeros(n, np.uint8), np.zeros(n, np.int32))
+        out = _capi.cvo_map_ray_out_t(*[a.ctypes.data for a in r])
+        call = self.L.cvo_map_raycast if self.gpu is not None else self.L.cvo_map_raycast_host
+        self._check(call(self.handle, n, _fptr(o), _fptr(e), mask, int(max_steps), C.byref(out)), "cvo_map_raycast_host refused the rays")
+        return r
+
+    def render(self, pose, fx, fy, cx, cy, rows, cols, z_far, stop=("occupied",), planes=("depth", "semantics", "feat", "label")):
+        """cvo_map_render(_host): the map seen by a pinhole camera at `pose` (3x4 or 4x4, camera to map), one ray of raycast
+        per pixel out to camera z = z_far, made on the device.  -> MapView(depth, semantics, feat, label): rows x cols z-depth (0:
+        no stop), class (-1: no stop), x 5 features, x num_classes class distribution (cvo_rgbd_frame_t::semantic's layout);
+        a plane not named in `planes` is None and is not computed."""
+        mask = self.stop_mask(stop)
+        P = np.asarray(pose, np.float32)
+        if P.shape not in ((3, 4), (4, 4)):
+            raise ValueError(f"the pose is 3x4 or 4x4, got {P.shape}")
+        rows, cols = int(rows), int(cols)
+        if rows < 1 or cols < 1:
+            raise ValueError("rows and cols are at least 1")
+        if rows * cols > 1 << 24:
+            raise ValueError("more than 2^24 pixels")
+        bad = [p for p in planes if p not in MapView._fields]
+        if bad:
+            raise ValueError(f"a plane is one of {MapView._fields}, got {bad[0]!r}")
+        T = np.ascontiguousarray(P[:3, :4])
+        shapes = dict(depth=((rows, cols), np.float32), semantics=((rows, cols), np.int32), feat=((rows, cols, 5), np.float32),
+                      label=((rows, cols, self.config.num_classes), np.float32))
+        r = MapView(*[np.zeros(*shapes[p]) if p in planes else None for p in MapView._fields])
+        out = _capi.cvo_map_render_out_t(*[None if a is None or a.size == 0 else a.ctypes.data for a in r])
+        call = self.L.cvo_map_render if self.gpu is not None else self.L.cvo_map_render_host
+        self._check(call(self.handle, _fptr(T), float(fx), float(fy), float(cx), float(cy), rows, cols, float(z_far), mask, C.byref(out)),
+                    "cvo_map_render_host refused the view")
+        return r
 
     def size(self):
         """cvo_map_size -> (voxels stored, of them OCCUPIED)."""

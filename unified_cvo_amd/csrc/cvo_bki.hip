@@ -795,6 +795,322 @@ int bki_cloud_resident_device(cvo_map* m, const char* who, std::vector<StagedClo
   return ingest_device_clouds(ctx, 1, &d, staged, who);  // (synchronises upload_stream; on error the cloud is released)
 }
 
+// ---- the read side: point queries, ray casts, a rendered view (tests/np_bki_query.py; the kernels: cvo_k_bki_query.h) ----
+
+// a voxel of the host map, or the default node (ms = prior, fs = 0) in `def`
+struct BkiHostNode {
+  bool stored = false;
+  const float *ms = nullptr, *fs = nullptr;
+  float def_ms[BKI_MAX_CLASSES + 1], def_fs[BKI_FEAT];
+};
+
+void bki_node_cpu(const cvo_map* m, bool inside, unsigned long long key, BkiHostNode* node) {
+  const BkiConst& k = m->k;
+  node->stored = false;
+  if (inside) {
+    const auto it = m->host.index.find(key);
+    if (it != m->host.index.end()) {
+      node->stored = true;
+      node->ms = &m->host.ms[(size_t)it->second * (size_t)k.nclass];
+      node->fs = &m->host.fs[(size_t)it->second * BKI_FEAT];
+      return;
+    }
+  }
+  for (int c = 0; c < k.nclass; c++) node->def_ms[c] = k.prior;
+  for (int c = 0; c < BKI_FEAT; c++) node->def_fs[c] = 0.f;
+  node->ms = node->def_ms;
+  node->fs = node->def_fs;
+}
+
+void bki_node_class_cpu(const cvo_map* m, const BkiHostNode& node, int* state, int* semantics) {
+  *state = BKI_UNKNOWN;
+  *semantics = -1;
+  if (!node.stored) return;
+  const float* ms = node.ms;
+  *state = bki_state(m->k, ms);
+  *semantics = bki_semantics([&](int c) { return ms[c]; }, bki_sum(ms, 0, m->k.nclass), m->k.nclass);
+}
+
+unsigned bki_look_cpu(const cvo_map* m, unsigned long long key) {
+  const auto it = m->host.index.find(key);
+  return it == m->host.index.end() ? (unsigned)BKI_BIT_ABSENT : bki_state_bit(m->k, &m->host.ms[(size_t)it->second * (size_t)m->k.nclass]);
+}
+
+void bki_centre3(float size, bool valid, unsigned long long key, float* out) {
+  out[0] = valid ? bki_centre((long long)(key >> 40), size) : bki_nan();
+  out[1] = valid ? bki_centre((long long)((key >> 20) & 0xFFFFFull), size) : bki_nan();
+  out[2] = valid ? bki_centre((long long)(key & 0xFFFFFull), size) : bki_nan();
+}
+
+void bki_query_cpu(const cvo_map* m, int n, const float* xyz, const cvo_map_query_out_t& o) {
+  const BkiConst& k = m->k;
+  BkiHostNode node;
+  for (size_t i = 0; i < (size_t)n; i++) {
+    unsigned long long key = 0;
+    const bool inside = bki_point_key(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], k.size, &key);
+    bki_node_cpu(m, inside, key, &node);
+    int state, sem;
+    bki_node_class_cpu(m, node, &state, &sem);
+    const float sum = bki_sum(node.ms, 0, k.nclass), occ = bki_sum(node.ms, 1, k.nclass);
+    if (o.found) o.found[i] = (uint8_t)(!inside ? BKI_Q_OUTSIDE : (node.stored ? BKI_Q_FOUND : BKI_Q_ABSENT));
+    if (o.state) o.state[i] = (uint8_t)state;
+    if (o.semantics) o.semantics[i] = sem;
+    for (int c = 0; o.probs && c < k.nclass; c++) o.probs[i * (size_t)k.nclass + c] = bki_prob(node.ms[c], sum);
+    for (int c = 0; o.vars && c < k.nclass; c++) o.vars[i * (size_t)k.nclass + c] = bki_var(node.ms[c], sum);
+    for (int c = 0; o.feat && c < BKI_FEAT; c++) o.feat[i * BKI_FEAT + c] = node.fs[c] / occ;
+    if (o.centre) bki_centre3(k.size, inside, key, o.centre + 3 * i);
+  }
+}
+
+void bki_raycast_cpu(const cvo_map* m, int n, const float* origin, const float* end, unsigned stop_mask, int max_steps, const cvo_map_ray_out_t& o) {
+  const BkiConst& k = m->k;
+  BkiHostNode node;
+  for (size_t i = 0; i < (size_t)n; i++) {
+    const BkiRay r = bki_ray_walk(k.size, origin + 3 * i, end + 3 * i, stop_mask, max_steps, [&](unsigned long long key) { return bki_look_cpu(m, key); });
+    const bool walked = r.key != BKI_NO_KEY;
+    bki_node_cpu(m, walked, r.key, &node);
+    int state, sem;
+    bki_node_class_cpu(m, node, &state, &sem);
+    if (o.status) o.status[i] = (uint8_t)r.status;
+    if (o.key) o.key[i] = r.key;
+    if (o.centre) bki_centre3(k.size, walked, r.key, o.centre + 3 * i);
+    if (o.t) o.t[i] = r.t;
+    if (o.steps) o.steps[i] = r.steps;
+    if (o.state) o.state[i] = (uint8_t)state;
+    if (o.semantics) o.semantics[i] = sem;
+  }
+}
+
+struct BkiCamera {
+  float pose[12], fx, fy, cx, cy, z_far;
+  int rows, cols;
+};
+
+void bki_render_cpu(const cvo_map* m, const BkiCamera& cam, unsigned stop_mask, const cvo_map_render_out_t& out) {
+  const BkiConst& k = m->k;
+  const float* T = cam.pose;
+  const float o[3] = {T[3], T[7], T[11]};
+  BkiHostNode node;
+  for (int v = 0; v < cam.rows; v++)
+    for (int u = 0; u < cam.cols; u++) {
+      const size_t px = (size_t)v * cam.cols + u;
+      float c[3], e[3];
+      bki_pixel_end(u, v, cam.fx, cam.fy, cam.cx, cam.cy, cam.z_far, c);
+      for (int r = 0; r < 3; r++) e[r] = std::fmaf(T[4 * r], c[0], T[4 * r + 1] * c[1]) + std::fmaf(T[4 * r + 2], c[2], T[4 * r + 3]);
+      const BkiRay ray = bki_ray_walk(k.size, o, e, stop_mask, BKI_RAY_MAX_STEPS, [&](unsigned long long key) { return bki_look_cpu(m, key); });
+      const bool stop = ray.status == BKI_RAY_STOPPED;
+      bki_node_cpu(m, stop, ray.key, &node);
+      int state, sem;
+      bki_node_class_cpu(m, node, &state, &sem);
+      if (out.depth) out.depth[px] = stop ? (float)(ray.td * (double)cam.z_far) : 0.f;
+      if (out.semantics) out.semantics[px] = sem;
+      const float sum = bki_sum(node.ms, 0, k.nclass), occ = bki_sum(node.ms, 1, k.nclass);
+      for (int q = 0; out.feat && q < BKI_FEAT; q++) out.feat[BKI_FEAT * px + q] = stop ? node.fs[q] / occ : 0.f;
+      for (int q = 1; out.label && q <= k.C; q++) out.label[(size_t)k.C * px + q - 1] = stop ? node.ms[q] / sum : 0.f;
+    }
+}
+
+// room for `count` elements behind *d when the caller wants that output
+template <class T>
+void bki_take_if(ScratchLayout& l, const void* wanted, T*& d, size_t count) {
+  d = nullptr;
+  if (wanted) l.take(d, count);
+}
+
+template <class T>
+hipError_t bki_copy_down(T* host, const T* dev, size_t count, hipStream_t st) {
+  return host && count ? hipMemcpyAsync(host, dev, sizeof(T) * count, hipMemcpyDeviceToHost, st) : hipSuccess;
+}
+
+// points from host rows (xyz) or from a resident cloud under a pose (cloud; pose12 or nullptr)
+int bki_query_device(cvo_map* m, int n, const float* xyz, const cvo_cloud* cloud, const float* pose12, const cvo_map_query_out_t& o) {
+  cvo_ctx* ctx = m->ctx;
+  hipStream_t st = ctx->upload_stream;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t nn = (size_t)n, nc = (size_t)m->k.nclass;
+  BkiQueryArgs a{};
+  float* d_xyz = nullptr;
+  const int rc = m->work_scratch.lay_out(ctx, "voxel map query scratch", [&](ScratchLayout& l) {
+    if (xyz) l.take(d_xyz, 3 * nn);
+    bki_take_if(l, o.found, a.found, nn);
+    bki_take_if(l, o.state, a.state, nn);
+    bki_take_if(l, o.semantics, a.semantics, nn);
+    bki_take_if(l, o.probs, a.probs, nc * nn);
+    bki_take_if(l, o.vars, a.vars, nc * nn);
+    bki_take_if(l, o.feat, a.feat, BKI_FEAT * nn);
+    bki_take_if(l, o.centre, a.centre, 3 * nn);
+  });
+  if (rc != CVO_OK) return rc;
+  a.k = m->k;
+  a.t = m->t;
+  a.n = n;
+  if (xyz) {
+    HIP_TRY(ctx, hipMemcpyAsync(d_xyz, xyz, 12 * nn, hipMemcpyHostToDevice, st));
+    a.xyz = d_xyz;
+  } else {
+    a.x4 = cloud->x4;
+    a.has_pose = pose12 ? 1 : 0;
+    for (int q = 0; pose12 && q < 12; q++) a.pose[q] = pose12[q];
+  }
+  const unsigned tiles = (unsigned)((nn + BKI_QUERY_THREADS - 1) / BKI_QUERY_THREADS);
+  hipLaunchKernelGGL(k_bki_query, dim3(std::min(tiles, (unsigned)BKI_GRID_MAX)), dim3(BKI_QUERY_THREADS), 0, st, a);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, bki_copy_down((unsigned char*)o.found, (const unsigned char*)a.found, nn, st));
+  HIP_TRY(ctx, bki_copy_down((unsigned char*)o.state, (const unsigned char*)a.state, nn, st));
+  HIP_TRY(ctx, bki_copy_down((int*)o.semantics, (const int*)a.semantics, nn, st));
+  HIP_TRY(ctx, bki_copy_down(o.probs, (const float*)a.probs, nc * nn, st));
+  HIP_TRY(ctx, bki_copy_down(o.vars, (const float*)a.vars, nc * nn, st));
+  HIP_TRY(ctx, bki_copy_down(o.feat, (const float*)a.feat, BKI_FEAT * nn, st));
+  HIP_TRY(ctx, bki_copy_down(o.centre, (const float*)a.centre, 3 * nn, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return CVO_OK;
+}
+
+int bki_raycast_device(cvo_map* m, int n, const float* origin, const float* end, unsigned stop_mask, int max_steps, const cvo_map_ray_out_t& o) {
+  cvo_ctx* ctx = m->ctx;
+  hipStream_t st = ctx->upload_stream;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t nn = (size_t)n;
+  BkiRaycastArgs a{};
+  float *d_o = nullptr, *d_e = nullptr;
+  const int rc = m->work_scratch.lay_out(ctx, "voxel map ray scratch", [&](ScratchLayout& l) {
+    l.take(d_o, 3 * nn);
+    l.take(d_e, 3 * nn);
+    bki_take_if(l, o.status, a.out.status, nn);
+    bki_take_if(l, o.key, a.out.key, nn);
+    bki_take_if(l, o.centre, a.out.centre, 3 * nn);
+    bki_take_if(l, o.t, a.out.t, nn);
+    bki_take_if(l, o.steps, a.out.steps, nn);
+    bki_take_if(l, o.state, a.out.state, nn);
+    bki_take_if(l, o.semantics, a.out.semantics, nn);
+  });
+  if (rc != CVO_OK) return rc;
+  a.k = m->k;
+  a.t = m->t;
+  a.n = n;
+  a.stop_mask = stop_mask;
+  a.max_steps = max_steps;
+  a.origin = d_o;
+  a.end = d_e;
+  HIP_TRY(ctx, hipMemcpyAsync(d_o, origin, 12 * nn, hipMemcpyHostToDevice, st));
+  HIP_TRY(ctx, hipMemcpyAsync(d_e, end, 12 * nn, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(k_bki_raycast, dim3(bki_blocks(nn)), dim3(BKI_THREADS), 0, st, a);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, bki_copy_down((unsigned char*)o.status, (const unsigned char*)a.out.status, nn, st));
+  HIP_TRY(ctx, bki_copy_down((unsigned long long*)o.key, (const unsigned long long*)a.out.key, nn, st));
+  HIP_TRY(ctx, bki_copy_down(o.centre, (const float*)a.out.centre, 3 * nn, st));
+  HIP_TRY(ctx, bki_copy_down(o.t, (const float*)a.out.t, nn, st));
+  HIP_TRY(ctx, bki_copy_down((int*)o.steps, (const int*)a.out.steps, nn, st));
+  HIP_TRY(ctx, bki_copy_down((unsigned char*)o.state, (const unsigned char*)a.out.state, nn, st));
+  HIP_TRY(ctx, bki_copy_down((int*)o.semantics, (const int*)a.out.semantics, nn, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return CVO_OK;
+}
+
+int bki_render_device(cvo_map* m, const BkiCamera& cam, unsigned stop_mask, const cvo_map_render_out_t& o) {
+  cvo_ctx* ctx = m->ctx;
+  hipStream_t st = ctx->upload_stream;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t px = (size_t)cam.rows * cam.cols, C = (size_t)m->k.C;
+  BkiRenderArgs a{};
+  const int rc = m->work_scratch.lay_out(ctx, "voxel map render scratch", [&](ScratchLayout& l) {
+    bki_take_if(l, o.depth, a.depth, px);
+    bki_take_if(l, o.semantics, a.semantics, px);
+    bki_take_if(l, o.feat, a.feat, BKI_FEAT * px);
+    bki_take_if(l, C ? o.label : nullptr, a.label, C * px);
+  });
+  if (rc != CVO_OK) return rc;
+  a.k = m->k;
+  a.t = m->t;
+  a.rows = cam.rows;
+  a.cols = cam.cols;
+  a.stop_mask = stop_mask;
+  for (int q = 0; q < 12; q++) a.pose[q] = cam.pose[q];
+  a.fx = cam.fx, a.fy = cam.fy, a.cx = cam.cx, a.cy = cam.cy, a.z_far = cam.z_far;
+  const unsigned long long tiles = (unsigned long long)((cam.cols + BKI_RENDER_TILE - 1) / BKI_RENDER_TILE) * ((cam.rows + BKI_RENDER_TILE - 1) / BKI_RENDER_TILE);
+  hipLaunchKernelGGL(k_bki_render, dim3((unsigned)((tiles + BKI_THREADS / BKI_WAVE - 1) / (BKI_THREADS / BKI_WAVE))), dim3(BKI_THREADS), 0, st, a);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, bki_copy_down(o.depth, (const float*)a.depth, px, st));
+  HIP_TRY(ctx, bki_copy_down((int*)o.semantics, (const int*)a.semantics, px, st));
+  HIP_TRY(ctx, bki_copy_down(o.feat, (const float*)a.feat, BKI_FEAT * px, st));
+  if (C) HIP_TRY(ctx, bki_copy_down(o.label, (const float*)a.label, C * px, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  return CVO_OK;
+}
+
+// what every read checks first: the handle, the kind of map the entry point is for, a map an insert left half way
+int bki_read_check(cvo_map* m, bool host_call, const std::string& who) {
+  if (!m) return CVO_E_INVALID;
+  if (host_call != (m->ctx == nullptr))
+    return fail(m->ctx, CVO_E_INVALID, who + (host_call ? ": the map belongs to a context" : ": the map is one of cvo_map_open_host"));
+  if (m->broken) return fail(m->ctx, CVO_E_HIP, who + ": an earlier insert failed on the device half way: the map cannot be used");
+  return CVO_OK;
+}
+
+int bki_query_entry(cvo_map* m, bool host_call, const char* who, int n, const float* xyz, const cvo_map_query_out_t* out) {
+  int rc = bki_read_check(m, host_call, who);
+  if (rc != CVO_OK) return rc;
+  cvo_ctx* ctx = m->ctx;
+  if (n < 0) return fail(ctx, CVO_E_INVALID, std::string(who) + ": n is negative");
+  if (n > 0 && !xyz) return fail(ctx, CVO_E_INVALID, std::string(who) + ": a required pointer is missing");
+  const cvo_map_query_out_t o = out ? *out : cvo_map_query_out_t{};
+  return frontend_call(ctx, who, [&] {
+    if (n == 0) return (int)CVO_OK;
+    if (m->side == 0) return bki_query_device(m, n, xyz, nullptr, nullptr, o);
+    bki_query_cpu(m, n, xyz, o);  // (a map of the host side; an undecided map holds nothing and stays undecided)
+    return (int)CVO_OK;
+  });
+}
+
+int bki_ray_check(cvo_ctx* ctx, const std::string& who, unsigned stop_mask) {
+  if (stop_mask > 15u) return fail(ctx, CVO_E_INVALID, who + ": stop_mask has bits beyond FREE 1, OCCUPIED 2, UNKNOWN 4, not stored 8");
+  return CVO_OK;
+}
+
+int bki_raycast_entry(cvo_map* m, bool host_call, const char* who, int n, const float* origin, const float* end, unsigned stop_mask, int max_steps,
+                      const cvo_map_ray_out_t* out) {
+  int rc = bki_read_check(m, host_call, who);
+  if (rc != CVO_OK) return rc;
+  cvo_ctx* ctx = m->ctx;
+  if (n < 0) return fail(ctx, CVO_E_INVALID, std::string(who) + ": n_rays is negative");
+  if (n > 0 && (!origin || !end)) return fail(ctx, CVO_E_INVALID, std::string(who) + ": a required pointer is missing");
+  if (max_steps < 1 || max_steps > BKI_RAY_MAX_STEPS) return fail(ctx, CVO_E_INVALID, std::string(who) + ": max_steps lies in 1 .. 2^20");
+  if ((rc = bki_ray_check(ctx, who, stop_mask)) != CVO_OK) return rc;
+  const cvo_map_ray_out_t o = out ? *out : cvo_map_ray_out_t{};
+  return frontend_call(ctx, who, [&] {
+    if (n == 0) return (int)CVO_OK;
+    if (m->side == 0) return bki_raycast_device(m, n, origin, end, stop_mask, max_steps, o);
+    bki_raycast_cpu(m, n, origin, end, stop_mask, max_steps, o);
+    return (int)CVO_OK;
+  });
+}
+
+int bki_render_entry(cvo_map* m, bool host_call, const char* who, const float* pose12, float fx, float fy, float cx, float cy, int rows, int cols,
+                     float z_far, unsigned stop_mask, const cvo_map_render_out_t* out) {
+  int rc = bki_read_check(m, host_call, who);
+  if (rc != CVO_OK) return rc;
+  cvo_ctx* ctx = m->ctx;
+  const std::string w = who;
+  if (!pose12) return fail(ctx, CVO_E_INVALID, w + ": a required pointer is missing");
+  if (rows < 1 || cols < 1) return fail(ctx, CVO_E_INVALID, w + ": rows and cols are at least 1");
+  for (const float f : {fx, fy, z_far})
+    if (!std::isfinite(f) || !(f > 0.f)) return fail(ctx, CVO_E_INVALID, w + ": fx, fy and z_far are finite and > 0");
+  if (!std::isfinite(cx) || !std::isfinite(cy)) return fail(ctx, CVO_E_INVALID, w + ": cx and cy are finite");
+  for (int q = 0; q < 12; q++)
+    if (!std::isfinite(pose12[q])) return fail(ctx, CVO_E_INVALID, w + ": the pose is not finite");
+  if ((rc = bki_ray_check(ctx, w, stop_mask)) != CVO_OK) return rc;
+  if ((long long)rows * cols > BKI_RENDER_MAX_PIXELS) return fail(ctx, CVO_E_UNSUPPORTED, w + ": more than 2^24 pixels");
+  BkiCamera cam{};
+  for (int q = 0; q < 12; q++) cam.pose[q] = pose12[q];
+  cam.fx = fx, cam.fy = fy, cam.cx = cx, cam.cy = cy, cam.z_far = z_far, cam.rows = rows, cam.cols = cols;
+  const cvo_map_render_out_t o = out ? *out : cvo_map_render_out_t{};
+  return frontend_call(ctx, who, [&] {
+    if (m->side == 0) return bki_render_device(m, cam, stop_mask, o);
+    bki_render_cpu(m, cam, stop_mask, o);
+    return (int)CVO_OK;
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -942,6 +1258,64 @@ int cvo_map_cloud_resident(cvo_map* m, cvo_cloud** out, long long* n) {
   }
   if (rc == CVO_OK && n) *n = rows_n;
   return rc;
+}
+
+int cvo_map_query(cvo_map* m, int n, const float* xyz, const cvo_map_query_out_t* out) {
+  return bki_query_entry(m, false, "cvo_map_query", n, xyz, out);
+}
+
+int cvo_map_query_host(cvo_map* m, int n, const float* xyz, const cvo_map_query_out_t* out) {
+  return bki_query_entry(m, true, "cvo_map_query_host", n, xyz, out);
+}
+
+int cvo_map_query_cloud(cvo_map* m, const cvo_cloud* cloud, const float pose12[12], const cvo_map_query_out_t* out) {
+  const std::string who = "cvo_map_query_cloud";
+  const int rc = bki_read_check(m, false, who);
+  if (rc != CVO_OK) return rc;
+  cvo_ctx* ctx = m->ctx;
+  if (!cloud) return fail(ctx, CVO_E_INVALID, who + ": a required pointer is missing");
+  if (cloud->ctx != ctx) return fail(ctx, CVO_E_INVALID, who + ": the cloud belongs to another context");
+  for (int q = 0; pose12 && q < 12; q++)
+    if (!std::isfinite(pose12[q])) return fail(ctx, CVO_E_INVALID, who + ": the pose is not finite");
+  const cvo_map_query_out_t o = out ? *out : cvo_map_query_out_t{};
+  return frontend_call(ctx, who.c_str(), [&] {
+    const int n = cloud->n;
+    if (n == 0) return (int)CVO_OK;
+    if (m->side == 0) return bki_query_device(m, n, nullptr, cloud, pose12, o);
+    // a map of the host side, or one without an insert: the coordinates come down and are moved as the kernel moves them
+    std::vector<float4> x4((size_t)n);
+    std::vector<float> xyz(3 * (size_t)n);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemcpyAsync(x4.data(), cloud->x4, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, ctx->upload_stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->upload_stream));
+    const float* T = pose12;
+    for (size_t i = 0; i < (size_t)n; i++) {
+      const float x = x4[i].x, y = x4[i].y, z = x4[i].z;
+      xyz[3 * i] = x, xyz[3 * i + 1] = y, xyz[3 * i + 2] = z;
+      for (int r = 0; T && r < 3; r++) xyz[3 * i + r] = std::fmaf(T[4 * r], x, T[4 * r + 1] * y) + std::fmaf(T[4 * r + 2], z, T[4 * r + 3]);
+    }
+    bki_query_cpu(m, n, xyz.data(), o);
+    return (int)CVO_OK;
+  });
+}
+
+int cvo_map_raycast(cvo_map* m, int n_rays, const float* origin, const float* end, unsigned stop_mask, int max_steps, const cvo_map_ray_out_t* out) {
+  return bki_raycast_entry(m, false, "cvo_map_raycast", n_rays, origin, end, stop_mask, max_steps, out);
+}
+
+int cvo_map_raycast_host(cvo_map* m, int n_rays, const float* origin, const float* end, unsigned stop_mask, int max_steps,
+                         const cvo_map_ray_out_t* out) {
+  return bki_raycast_entry(m, true, "cvo_map_raycast_host", n_rays, origin, end, stop_mask, max_steps, out);
+}
+
+int cvo_map_render(cvo_map* m, const float pose12[12], float fx, float fy, float cx, float cy, int rows, int cols, float z_far, unsigned stop_mask,
+                   const cvo_map_render_out_t* out) {
+  return bki_render_entry(m, false, "cvo_map_render", pose12, fx, fy, cx, cy, rows, cols, z_far, stop_mask, out);
+}
+
+int cvo_map_render_host(cvo_map* m, const float pose12[12], float fx, float fy, float cx, float cy, int rows, int cols, float z_far,
+                        unsigned stop_mask, const cvo_map_render_out_t* out) {
+  return bki_render_entry(m, true, "cvo_map_render_host", pose12, fx, fy, cx, cy, rows, cols, z_far, stop_mask, out);
 }
 
 int cvo_debug_map_stats(cvo_map* m, int* on_device, unsigned long long* counts, unsigned long long* keys, float* ms, float* fs) {

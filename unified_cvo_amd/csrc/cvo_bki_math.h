@@ -200,4 +200,118 @@ __host__ __device__ inline float bki_sparse_k(const float centre[3], const float
   return k < 0.f ? 0.f : k;
 }
 
+// ---- the read side (tests/np_bki_query.py): a voxel as upstream's node getters answer for it (SemanticBKIOctoMap::search,
+// Semantics::get_probs / get_vars / get_features), and the library's own ray walk ----
+
+enum : int { BKI_Q_ABSENT = 0, BKI_Q_FOUND = 1, BKI_Q_OUTSIDE = 2 };  // `found` of a point query
+enum : unsigned { BKI_BIT_FREE = 1, BKI_BIT_OCCUPIED = 2, BKI_BIT_UNKNOWN = 4, BKI_BIT_ABSENT = 8 };  // a voxel in a stop mask
+enum : int { BKI_RAY_END = 0, BKI_RAY_STOPPED = 1, BKI_RAY_TOO_LONG = 2, BKI_RAY_OUTSIDE = 3 };
+constexpr int BKI_RAY_MAX_STEPS = 1 << 20;      // voxels of one ray
+constexpr long long BKI_RENDER_MAX_PIXELS = 1ll << 24;
+constexpr unsigned long long BKI_NO_KEY = ~0ull;  // the key of a ray that walked nothing
+
+// the one NaN the read side writes (the centre of a point outside the key range, of a ray that walked nothing)
+__host__ __device__ inline float bki_nan() { return __builtin_bit_cast(float, 0x7fc00000u); }
+
+// the voxel of a point: the key of its k0 per axis (block_to_hash_key); false: not finite, or a k0 outside [1, 2^20 - 2]
+__host__ __device__ inline bool bki_point_key(float x, float y, float z, float size, unsigned long long* key) {
+  long long kx, ky, kz;
+  if (!bki_k0(x, size, &kx) || !bki_k0(y, size, &ky) || !bki_k0(z, size, &kz)) return false;  // (NaN and infinity fail both comparisons)
+  *key = bki_key((unsigned)kx, (unsigned)ky, (unsigned)kz);
+  return true;
+}
+
+// get_probs / get_vars of one class, sum = bki_sum(ms, 0, nclass): every operation on its own, in upstream's written order
+__host__ __device__ inline float bki_prob(float m, float sum) { return m / sum; }
+__host__ __device__ inline float bki_var(float m, float sum) {
+  const float p = m / sum;
+  return (p - p * p) / (sum + 1.f);
+}
+
+// max_element over get_probs: the first maximum (all NaN: 0).  ms(c): the voxel's ms, or the prior for the default node.
+template <class M>
+__host__ __device__ inline int bki_semantics(M&& ms, float sum, int nclass) {
+  int best = 0;
+  float pb = ms(0) / sum;
+  for (int c = 1; c < nclass; c++) {
+    const float pc = ms(c) / sum;
+    if (pc > pb) pb = pc, best = c;
+  }
+  return best;
+}
+
+// the stop-mask bit of a stored voxel
+__host__ __device__ inline unsigned bki_state_bit(const BkiConst& k, const float* ms) { return 1u << bki_state(k, ms); }
+
+// parameter of the i-th crossing (i = 1 .. N) on one axis of the segment o -> e, from block k0 in direction s: the boundary
+// b = ((k0 - 524288) + s (i - 0.5)) resolution and t = (b - o) / (e - o) in double, one rounding per operation (the sum
+// in front of the resolution is exact)
+__host__ __device__ inline double bki_ray_t(long long k0, int s, long long i, double res, float o, float e) {
+  const double b = ((double)(k0 - BKI_KOFF) + (double)s * ((double)i - 0.5)) * res;
+  return (b - (double)o) / ((double)e - (double)o);
+}
+
+struct BkiRay {
+  int status, steps;       // BKI_RAY_*; voxels visited
+  unsigned long long key;  // the last voxel visited (the stopping voxel; the end's on BKI_RAY_END), BKI_NO_KEY: nothing walked
+  float t;                 // the cast of the parameter at which the walk entered it; 0 in the origin's voxel
+  double td;               // ... the parameter itself (cvo_map_render's depth is (float)(td * (double)z_far))
+};
+
+// The library's own walk over the voxels the segment o -> e passes through, face by face (NOT upstream's RayCaster): exactly
+// 1 + N[x] + N[y] + N[z] voxels, N the distance of the two k0 per axis, known before the first step; each step crosses the
+// axis whose next crossing has the smallest t, ties to the lowest axis.  look(key) -> BKI_BIT_* of the voxel; the walk stops
+// at the first voxel, the origin's included, whose bit is in stop_mask.  Both counts bound the loop: it cannot run away.
+template <class Look>
+__host__ __device__ inline BkiRay bki_ray_walk(float size, const float o[3], const float e[3], unsigned stop_mask, int max_steps, Look&& look) {
+  BkiRay r{BKI_RAY_OUTSIDE, 0, BKI_NO_KEY, 0.f, 0.0};
+  long long k0x, k0y, k0z, k1x, k1y, k1z;
+  if (!bki_k0(o[0], size, &k0x) || !bki_k0(o[1], size, &k0y) || !bki_k0(o[2], size, &k0z)) return r;
+  if (!bki_k0(e[0], size, &k1x) || !bki_k0(e[1], size, &k1y) || !bki_k0(e[2], size, &k1z)) return r;
+  const long long dx = k1x - k0x, dy = k1y - k0y, dz = k1z - k0z;
+  const long long nx = dx < 0 ? -dx : dx, ny = dy < 0 ? -dy : dy, nz = dz < 0 ? -dz : dz;
+  const int sx = dx > 0 ? 1 : (dx < 0 ? -1 : 0), sy = dy > 0 ? 1 : (dy < 0 ? -1 : 0), sz = dz > 0 ? 1 : (dz < 0 ? -1 : 0);
+  const long long total = 1 + nx + ny + nz;
+  if (total > (long long)max_steps) return r.status = BKI_RAY_TOO_LONG, r;
+  const double res = (double)size;
+  long long ix = 1, iy = 1, iz = 1, kx = k0x, ky = k0y, kz = k0z;
+  double tx = nx ? bki_ray_t(k0x, sx, 1, res, o[0], e[0]) : 0.0;
+  double ty = ny ? bki_ray_t(k0y, sy, 1, res, o[1], e[1]) : 0.0;
+  double tz = nz ? bki_ray_t(k0z, sz, 1, res, o[2], e[2]) : 0.0;
+  double t = 0.0;
+  for (long long step = 1; step <= total; step++) {
+    r.key = bki_key((unsigned)kx, (unsigned)ky, (unsigned)kz);
+    r.steps = (int)step;
+    r.t = (float)t;
+    r.td = t;
+    if (look(r.key) & stop_mask) return r.status = BKI_RAY_STOPPED, r;
+    if (step == total) break;
+    // the axis with crossings left whose next one comes first; ties: the lowest axis
+    int a = -1;
+    double tb = 0.0;
+    if (ix <= nx) a = 0, tb = tx;
+    if (iy <= ny && (a < 0 || ty < tb)) a = 1, tb = ty;
+    if (iz <= nz && (a < 0 || tz < tb)) a = 2, tb = tz;
+    if (a == 0) {
+      kx += sx, t = tx, ix++;
+      if (ix <= nx) tx = bki_ray_t(k0x, sx, ix, res, o[0], e[0]);
+    } else if (a == 1) {
+      ky += sy, t = ty, iy++;
+      if (iy <= ny) ty = bki_ray_t(k0y, sy, iy, res, o[1], e[1]);
+    } else {
+      if (a < 0) break;  // (no axis has a crossing left: the count says this cannot be)
+      kz += sz, t = tz, iz++;
+      if (iz <= nz) tz = bki_ray_t(k0z, sz, iz, res, o[2], e[2]);
+    }
+  }
+  return r.status = BKI_RAY_END, r;
+}
+
+// the camera-frame end point of pixel (u, v): (((u - cx) / fx) z_far, ((v - cy) / fy) z_far, z_far), each operation on its own
+__host__ __device__ inline void bki_pixel_end(int u, int v, float fx, float fy, float cx, float cy, float z_far, float out[3]) {
+  out[0] = (((float)u - cx) / fx) * z_far;
+  out[1] = (((float)v - cy) / fy) * z_far;
+  out[2] = z_far;
+}
+
 }  // namespace cvo_dev

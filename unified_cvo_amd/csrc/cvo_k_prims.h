@@ -83,5 +83,18 @@ __device__ __forceinline__ unsigned table_insert(unsigned long long* keys, unsig
   if (visited) *visited = len;
   return g;
 }
+// The slot of `key`, or SLOT_NONE: table_insert's home slot and probing, read-only.  For a table no kernel is writing (the
+// launch runs behind every insert on the same stream), so plain loads see every key.  The first empty slot ends the probe -
+// the table is at most half full -, and the slot count ends it whatever the table holds.
+__device__ __forceinline__ unsigned table_find(const unsigned long long* keys, unsigned mask, unsigned h, unsigned long long key) {
+  unsigned g = h & mask;
+  for (unsigned seen = 0; seen <= mask; seen++) {
+    const unsigned long long at = keys[g];
+    if (at == key) return g;
+    if (at == TABLE_EMPTY) return SLOT_NONE;
+    g = (g + 1) & mask;
+  }
+  return SLOT_NONE;
+}
 
 }  // namespace cvo_dev

@@ -80,3 +80,4 @@
 #include "cvo_k_bki.h"
 #include "cvo_k_bki_stage.h"
 #include "cvo_k_bki_sparse.h"
+#include "cvo_k_bki_query.h"
