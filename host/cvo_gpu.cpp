@@ -674,4 +674,61 @@ void CvoGPU::compute_association_gpu(const CvoPointCloud& a, const CvoPointCloud
   as.target_inliers = as.pairs.col;
 }
 
+namespace {
+
+// cvo_depth_filter over handles: the refined keyframe's handle and the original indices of its points
+cvo_cloud* depth_filter_handles(cvo_ctx* ctx, const CvoParams& params, const cvo_cloud* kf, const std::vector<const cvo_cloud*>& frames,
+                                const std::vector<Mat4f>& T_t2s, const std::vector<Mat4f>& T_s2t, const Mat3f& kernel, int min_count,
+                                std::vector<int>& kept) {
+  const size_t k = frames.size();
+  if (T_t2s.size() != k || T_s2t.size() != k) throw std::invalid_argument("depth_filter: one T_t2s and one T_s2t per frame");
+  std::vector<float> T(16 * k + 1), Td(16 * k + 1);
+  for (size_t q = 0; q < k; q++) {
+    std::copy(T_t2s[q].data(), T_t2s[q].data() + 16, T.begin() + 16 * q);
+    std::copy(T_s2t[q].data(), T_s2t[q].data() + 16, Td.begin() + 16 * q);
+  }
+  cvo_params_t p;
+  static_assert(sizeof(cvo_params_t) == sizeof(CvoParams), "cvo_params_t must stay layout-identical to cvo::CvoParams");
+  std::memcpy(&p, &params, sizeof(p));
+  kept.assign((size_t)std::max(cvo_cloud_size(kf), 1), 0);
+  cvo_cloud* out = nullptr;
+  int nk = 0;
+  check(ctx, cvo_depth_filter(ctx, &p, kf, (int)k, frames.data(), T.data(), Td.data(), kernel.data(), min_count, &out, kept.data(), nullptr,
+                              &nk, nullptr),
+        "cvo_depth_filter");
+  kept.resize((size_t)nk);
+  return out;
+}
+
+}  // namespace
+
+std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::depth_filter(const ResidentClouds& kf, int kf_index, const ResidentClouds& frames,
+                                                             const std::vector<Mat4f>& T_t2s, const std::vector<Mat4f>& T_s2t,
+                                                             const Mat3f& kernel, int min_count) const {
+  if (kf_index < 0 || kf_index >= kf.size()) throw std::invalid_argument("depth_filter: no such keyframe");
+  std::lock_guard<std::mutex> lk(call_mutex);
+  std::unique_ptr<ResidentClouds> out(new ResidentClouds());
+  out->handles.assign(1, nullptr);
+  out->kept_.resize(1);
+  const std::vector<const cvo_cloud*> h(frames.handles.begin(), frames.handles.end());
+  out->handles[0] = depth_filter_handles(ctx, params, kf.handles[(size_t)kf_index], h, T_t2s, T_s2t, kernel, min_count, out->kept_[0]);
+  return out;
+}
+
+CvoPointCloud CvoGPU::depth_filter(const CvoPointCloud& kf, const std::vector<const CvoPointCloud*>& frames, const std::vector<Mat4f>& T_t2s,
+                                   const std::vector<Mat4f>& T_s2t, const Mat3f& kernel, int min_count) const {
+  std::vector<const CvoPointCloud*> all{&kf};
+  all.insert(all.end(), frames.begin(), frames.end());
+  const std::unique_ptr<ResidentClouds> up = upload_clouds(all);
+  std::unique_ptr<ResidentClouds> res(new ResidentClouds());
+  res->handles.assign(1, nullptr);
+  res->kept_.resize(1);
+  {
+    std::lock_guard<std::mutex> lk(call_mutex);
+    const std::vector<const cvo_cloud*> h(up->handles.begin() + 1, up->handles.end());
+    res->handles[0] = depth_filter_handles(ctx, params, up->handles[0], h, T_t2s, T_s2t, kernel, min_count, res->kept_[0]);
+  }
+  return download(*res, 0);
+}
+
 }  // namespace cvo

@@ -102,6 +102,17 @@ class CvoGPU {
   // does not hold are left out (F = 0 / no classes / types 0).  Refusals throw.
   std::unique_ptr<ResidentClouds> merge(const ResidentClouds& clouds, const std::vector<double>* poses, float voxel_size = 0.f) const;
   CvoPointCloud download(const ResidentClouds& clouds, int k) const;
+  // New: keyframe depth filtering, the last loops of main_depth_filtering.cpp (208-298), without a host copy of any
+  // association or frame (cvo_depth_filter, include/cvo_hip.h): cloud kf_index of `kf` refined from every cloud of `frames`
+  // - T_t2s[k] is the association's transform for frame k (the driver's T_t^-1 T_s), T_s2t[k] the one whose third row gives
+  // an associated point's depth in the keyframe's frame (the driver's T_s^-1 T_t), `kernel` the non-isotropic kernel - as ONE
+  // resident cloud (size() == 1): the rows with more than min_count observations, moved along their rays.  kept(0): their
+  // original indices.  The CvoPointCloud overload mirrors the driver's last loop: clouds in, kf_filtered out.  Refusals throw.
+  std::unique_ptr<ResidentClouds> depth_filter(const ResidentClouds& kf, int kf_index, const ResidentClouds& frames,
+                                               const std::vector<Mat4f>& T_t2s, const std::vector<Mat4f>& T_s2t, const Mat3f& kernel,
+                                               int min_count = 3) const;
+  CvoPointCloud depth_filter(const CvoPointCloud& kf, const std::vector<const CvoPointCloud*>& frames, const std::vector<Mat4f>& T_t2s,
+                             const std::vector<Mat4f>& T_s2t, const Mat3f& kernel, int min_count = 3) const;
   // New: voxel-grid downsampling on the device - what the drivers do with cvo::VoxelMap before align()
   // (main_multi_frame_irls_tum.cpp:290-335; utils/VoxelMap.hpp is the host class): of every occupied voxel of side
   // voxel_size the point with the LOWEST index is kept, in ascending index (cvo_voxel_select, include/cvo_hip.h).

@@ -904,6 +904,72 @@ int cvo_cloud_merge(cvo_ctx* ctx, int n_clouds, const cvo_cloud* const* clouds,
 int cvo_cloud_download(cvo_ctx* ctx, const cvo_cloud* cloud, float* xyz, float* feat, float* label, float* geotype,
                        int* present);
 
+/* ---- keyframe depth filtering: the last loops of main_depth_filtering.cpp (208-298), frames in, cloud out -------------
+ * A keyframe's depths refined from later frames with known poses.  Per frame the driver runs compute_association_gpu(kf,
+ * frame, T_t2s, non_isotropic_kernel) and collects, for every keyframe row, the depth of each associated point moved into
+ * the keyframe's frame (row 2 of T_s2t applied as CvoPointCloud::transform applies it) and its weight a_ij; rows with more
+ * than three observations get a weighted mean depth and are re-projected along their ray, the others are dropped.  Here the
+ * keyframe and the frames are resident clouds and nothing of it comes down: the association stays where its evaluation left
+ * it, the accumulators and the moved rows live in a region the filter owns, the result is built from device rows.
+ * tests/np_depthfilter.py is the statement (numpy float32); the kernels and the CPU twin equal it bit for bit.
+ *
+ *   state per keyframe row (original order): depth_sum (float), weight_sum (float), count (int), zero at open;
+ *   add:    for the row's entries j in ascending target index: zj = T_depth(2,0) x_j + T_depth(2,1) y_j + T_depth(2,2) z_j +
+ *           T_depth(2,3) (three rounded products added left to right, no fused multiply-add), depth_sum += zj * a,
+ *           weight_sum += a, count += 1.  Frames in call order: the order upstream's depths[idx1] / weights[idx1] fill in;
+ *   finish: rows with count > min_count (upstream: 3; the comparison is strict): wbar = weight_sum / float(count),
+ *           d = (depth_sum + z0 wbar) / (weight_sum + wbar), xyz' = (xyz / z0) * d per component; features, labels and
+ *           geometric types copied; rows in ascending original index.  A row whose d or xyz' is not finite (z0 == 0, a zero
+ *           weight sum) is dropped and counted in *n_nonfinite: upstream's text pins nothing there, this is the library's
+ *           choice.  Finish leaves the state as it is: more frames may follow it.
+ * Departures from the driver's text: both matrices come from the caller (the driver derives T_t2s = T_t^-1 T_s and T_s2t =
+ * T_s^-1 T_t with Eigen's 4x4 float inverse); nearest_neighbors_max truncates a row's entries per frame, as upstream's
+ * kernel does; geometric types are off in the association (inner_product_non_isotropic_impl forces that).
+ *
+ * cvo_depth_filter_open: the filter COPIES what it needs of the keyframe - its rows in original order (k_cloud_unpack) and a
+ * resident cloud built from them, interchangeable with the keyframe - so the caller's handle may be freed as soon as open
+ * returns and is never dereferenced again.  The context must outlive the filter (close it before cvo_ctx_destroy).
+ * cvo_depth_filter_add: T and kernel_colmajor are exactly cvo_association_non_isotropic's (source = the keyframe, target =
+ * the frame); T_depth is 16 floats, column-major like T.  The frame is only read and may be freed on return.  Uses the
+ * context's pair workspace and stream like cvo_association (refused while a batch queue is open).
+ * cvo_depth_filter_state: the accumulators in original row order (cvo_depth_filter_size rows); any pointer may be NULL.
+ * cvo_depth_filter_finish: *out = the refined keyframe as a resident cloud, the cloud cvo_cloud_upload makes of the
+ * statement's rows (same spatial order and ordering route, same one-hot detection, bit-identical results of every later
+ * call); kept / depth (optional, room for every row): original indices and refined depths of its points; *n_kept,
+ * *n_nonfinite (optional).  Runs on the upload stream, synchronised on return.
+ * cvo_depth_filter: open, add for every frame (T / T_depth: 16 floats per frame), finish, close in one call.
+ * An empty keyframe or frame is accepted: add is a no-op, finish yields an empty cloud.  Every call is validated before
+ * anything is written (CVO_E_INVALID: a NULL argument, a cloud of another context, a non-finite T_depth, min_count < 0;
+ * CVO_E_UNSUPPORTED: a keyframe of more than 2^24 rows); on an error *out is NULL and the state is unchanged.  One error is
+ * found on the device: an add whose kernel matrix names a row, slot or column out of range is refused with CVO_E_HIP, as the
+ * association export refuses such a matrix; the filter's state is then lost and every later call but close is refused.
+ * Not built: several frames' associations in one launch; a fused kernel that never materialises the association (the
+ * ordered truncation at nearest_neighbors_max stands in the way); deriving the two matrices from world poses.
+ *
+ * The CPU twin needs no context: pure arithmetic over an association the caller already has, rows = keyframe rows in
+ * original order, columns ascending (the CSR cvo_association_non_isotropic returns).  _accumulate_host adds one frame to the
+ * caller's accumulators (CVO_E_INVALID, nothing written: row_ptr not ascending from 0, a column outside [0, n_target));
+ * _finish_host writes the kept rows' moved coordinates (n_kept x 3), indices and depths; any output pointer may be NULL. */
+typedef struct cvo_depth_filter_s cvo_depth_filter_t;
+int cvo_depth_filter_open(cvo_ctx* ctx, const cvo_cloud* keyframe, cvo_depth_filter_t** out);
+int cvo_depth_filter_add(cvo_depth_filter_t* df, const cvo_params_t* params, const cvo_cloud* frame, const float T[16],
+                         const float T_depth[16], const float kernel_colmajor[9]);
+int cvo_depth_filter_size(const cvo_depth_filter_t* df);
+int cvo_depth_filter_state(cvo_depth_filter_t* df, float* depth_sum, float* weight_sum, int* count);
+int cvo_depth_filter_finish(cvo_depth_filter_t* df, int min_count, cvo_cloud** out, int* kept /* or NULL */,
+                            float* depth /* or NULL */, int* n_kept /* or NULL */, int* n_nonfinite /* or NULL */);
+void cvo_depth_filter_close(cvo_depth_filter_t* df);
+int cvo_depth_filter(cvo_ctx* ctx, const cvo_params_t* params, const cvo_cloud* keyframe, int n_frames,
+                     const cvo_cloud* const* frames, const float* T /* 16 per frame */, const float* T_depth /* 16 per frame */,
+                     const float kernel_colmajor[9], int min_count, cvo_cloud** out, int* kept, float* depth, int* n_kept,
+                     int* n_nonfinite);
+int cvo_depth_filter_accumulate_host(int n_rows, const int* row_ptr, const int* col, const float* val, int n_target,
+                                     const float* target_xyz, const float T_depth[16], float* depth_sum, float* weight_sum,
+                                     int* count);
+int cvo_depth_filter_finish_host(int n_rows, const float* xyz, const float* depth_sum, const float* weight_sum,
+                                 const int* count, int min_count, float* xyz_out, int* kept, float* depth, int* n_kept,
+                                 int* n_nonfinite);
+
 const char* cvo_version(void);
 
 #ifdef __cplusplus

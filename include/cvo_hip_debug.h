@@ -202,6 +202,16 @@ int cvo_debug_dfilter_stats(cvo_ctx* ctx, int* on_device, int* rows, int* cols, 
  * table, ~0 the key of a free slot, so that a test can name the first voxel that differs from the statement. */
 int cvo_debug_map_stats(cvo_map* map, int* on_device, unsigned long long* counts /* 8 */, unsigned long long* keys, float* ms, float* fs);
 
+/* How the rows of the matrix a filter's last add accumulated were stored (by position, read from pair 0's workspace): rows
+ * with no entry; rows the thread-per-row kernel wrote into the slot-major matrix; rows the wave-per-row kernels wrote
+ * slot-major (NNZ_DENSE_FLAG, dense_off < 0) and as row-major runs (dense_off >= 0); rows that hold exactly the neighbour
+ * budget K (cut there, or just full); the longest row; K; the rows k_assoc_dense evaluated with a whole block (wide rows:
+ * more than 256 and at most 1216 candidates, in a launch of the wide instantiation with a block per overflow row).
+ * CVO_E_INVALID unless the context's last evaluation is this filter's last add (its call serial).  Any pointer may be NULL.
+ * Tests use it to assert that the row classes they mean to cover are populated. */
+int cvo_debug_depth_filter_rows(cvo_depth_filter_t* df, int* n_empty, int* n_list, int* n_dense_slot, int* n_run, int* n_full,
+                                int* max_nnz, int* K, int* n_wide);
+
 #ifdef __cplusplus
 }
 #endif

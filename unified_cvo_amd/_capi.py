@@ -339,6 +339,9 @@ EXPORTED = [
     "cvo_map_insert_cloud", "cvo_map_cloud_resident", "cvo_map_set_kernel",
     "cvo_map_query", "cvo_map_query_cloud", "cvo_map_query_host", "cvo_map_raycast", "cvo_map_raycast_host",
     "cvo_map_render", "cvo_map_render_host",
+    "cvo_depth_filter_open", "cvo_depth_filter_add", "cvo_depth_filter_size", "cvo_depth_filter_state", "cvo_depth_filter_finish",
+    "cvo_depth_filter_close", "cvo_depth_filter", "cvo_depth_filter_accumulate_host", "cvo_depth_filter_finish_host",
+    "cvo_debug_depth_filter_rows",
 ]
 
 _libs = {}
@@ -524,6 +527,18 @@ def lib(path=None):
     L.cvo_map_raycast_host.argtypes = [vp, ip, fp, fp, C.c_uint, ip, ro]
     L.cvo_map_render.argtypes = [vp, fp] + [C.c_float] * 4 + [ip, ip, C.c_float, C.c_uint, vo]
     L.cvo_map_render_host.argtypes = [vp, fp] + [C.c_float] * 4 + [ip, ip, C.c_float, C.c_uint, vo]
+    pp = C.POINTER(cvo_params_t)
+    L.cvo_depth_filter_open.argtypes = [vp, vp, C.POINTER(vp)]
+    L.cvo_depth_filter_add.argtypes = [vp, pp, vp, fp, fp, fp]
+    L.cvo_depth_filter_size.argtypes = [vp]
+    L.cvo_depth_filter_state.argtypes = [vp, fp, fp, ipp]
+    L.cvo_depth_filter_finish.argtypes = [vp, ip, C.POINTER(vp), ipp, fp, ipp, ipp]
+    L.cvo_depth_filter_close.argtypes = [vp]
+    L.cvo_depth_filter_close.restype = None
+    L.cvo_depth_filter.argtypes = [vp, pp, vp, ip, C.POINTER(vp), fp, fp, fp, ip, C.POINTER(vp), ipp, fp, ipp, ipp]
+    L.cvo_depth_filter_accumulate_host.argtypes = [ip, ipp, ipp, fp, ip, fp, fp, fp, fp, ipp]
+    L.cvo_depth_filter_finish_host.argtypes = [ip, fp, fp, fp, ipp, ip, fp, ipp, fp, ipp, ipp]
+    L.cvo_debug_depth_filter_rows.argtypes = [vp] + [ipp] * 8
     for name in EXPORTED:
         getattr(L, name)  # AttributeError here = the library does not export what the header declares
     _libs[path] = L

@@ -1044,6 +1044,162 @@ def _mat_to_c(T):
     return a
 
 
+def _mats_to_c(Ts, k, name):
+    """k 4x4 matrices (row, col) -> 16 k floats, column-major each, as the C-ABI takes its transforms."""
+    a = np.asarray(Ts, np.float32)
+    if a.size != 16 * k or (k and a.shape[-2:] != (4, 4)):
+        raise ValueError(f"{name}: one 4x4 matrix per frame")
+    if k == 0:
+        return np.zeros(16, np.float32)  # (never read)
+    return np.ascontiguousarray(a.reshape(k, 4, 4).transpose(0, 2, 1)).reshape(16 * k)
+
+
+def _kernel_to_c(kernel):
+    a = np.asarray(kernel, np.float32)
+    if a.shape != (3, 3):
+        raise ValueError("kernel: a 3x3 matrix")
+    return np.ascontiguousarray(a.T).reshape(9)
+
+
+def _min_count(min_count):
+    if int(min_count) != min_count or min_count < 0:
+        raise ValueError("min_count: an integer >= 0")
+
+
+def _mat4(T, name):
+    a = np.asarray(T, np.float32)
+    if a.shape != (4, 4):
+        raise ValueError(f"{name}: a 4x4 matrix")
+    return _mat_to_c(a)
+
+
+class DepthFilter:
+    """cvo_depth_filter_t: a keyframe's depths refined from later frames on the device (the last loops of
+    main_depth_filtering.cpp; tests/np_depthfilter.py states the arithmetic).  CvoGPU.depth_filter_open makes one."""
+
+    def __init__(self, gpu, keyframe):
+        self.handle = None
+        self.gpu, self.n = gpu, keyframe.n
+        h = C.c_void_p()
+        gpu._check(gpu.L.cvo_depth_filter_open(gpu.ctx, keyframe.handle, C.byref(h)))
+        self.handle = h
+
+    def _open(self):
+        if not self.handle:
+            raise ValueError("the depth filter is closed")
+
+    def add(self, frame, T, kernel, T_depth):
+        """cvo_depth_filter_add: one resident frame.  T and kernel (3x3, row / col) are compute_association_gpu_non_isotropic's
+        with the keyframe as source; T_depth (4x4): its third row gives an associated point's depth in the keyframe's frame."""
+        self._open()
+        if not isinstance(frame, DeviceCloud):
+            raise ValueError("add: the frame is a DeviceCloud (CvoGPU.upload makes one)")
+        Tm, Td, kcm = _mat4(T, "T"), _mat4(T_depth, "T_depth"), _kernel_to_c(kernel)
+        p = self.gpu.params.to_ctypes()
+        self.gpu._check(self.gpu.L.cvo_depth_filter_add(self.handle, C.byref(p), frame.handle, _fptr(Tm), _fptr(Td), _fptr(kcm)))
+        return self
+
+    def state(self):
+        """cvo_depth_filter_state -> (depth_sum float32[n], weight_sum float32[n], count int32[n]), original row order."""
+        self._open()
+        n = self.n
+        ds, ws, cnt = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.int32)
+        self.gpu._check(self.gpu.L.cvo_depth_filter_state(self.handle, _fptr(ds), _fptr(ws), cnt.ctypes.data_as(C.POINTER(C.c_int))))
+        return ds[:n], ws[:n], cnt[:n]
+
+    def finish(self, min_count=3, return_kept=False):
+        """cvo_depth_filter_finish: the refined keyframe as a DeviceCloud (rows with more than min_count observations, moved
+        along their rays); return_kept: (cloud, kept original indices, refined depths, rows dropped as non-finite).  The state
+        stays: more frames may follow."""
+        self._open()
+        _min_count(min_count)
+        n = self.n
+        kept, depth = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32)
+        nk, nf, h = C.c_int(), C.c_int(), C.c_void_p()
+        self.gpu._check(self.gpu.L.cvo_depth_filter_finish(self.handle, int(min_count), C.byref(h), kept.ctypes.data_as(C.POINTER(C.c_int)),
+                                                           _fptr(depth), C.byref(nk), C.byref(nf)))
+        out = self.gpu._adopt(h, nk.value)
+        return (out, kept[:nk.value].copy(), depth[:nk.value].copy(), nf.value) if return_kept else out
+
+    def debug_rows(self):
+        """cvo_debug_depth_filter_rows: dict(empty, list, dense_slot, run, full, max_nnz, K, wide) - how the rows of the last
+        add's matrix were stored and how many k_assoc_dense gave a whole block; valid until the context evaluates something else."""
+        self._open()
+        v = [C.c_int() for _ in range(8)]
+        self.gpu._check(self.gpu.L.cvo_debug_depth_filter_rows(self.handle, *[C.byref(x) for x in v]))
+        return dict(zip(("empty", "list", "dense_slot", "run", "full", "max_nnz", "K", "wide"), (x.value for x in v)))
+
+    def close(self):
+        if self.handle:
+            self.gpu.L.cvo_depth_filter_close(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _raise_depth(rc, who):
+    if rc != 0:
+        raise CvoError(f"error {rc}: {who}")
+
+
+def depth_filter_accumulate_host(row_ptr, col, val, target_xyz, T_depth, state=None):
+    """cvo_depth_filter_accumulate_host: one frame's association (CSR over the keyframe's rows, columns ascending) folded into
+    `state` = (depth_sum, weight_sum, count) - None: zeros - which is returned, updated in place.  No context."""
+    rp = np.ascontiguousarray(row_ptr, np.int32).reshape(-1)
+    if rp.size < 1:
+        raise ValueError("row_ptr: n_rows + 1 entries")
+    n = rp.size - 1
+    c, v = np.ascontiguousarray(col, np.int32).reshape(-1), np.ascontiguousarray(val, np.float32).reshape(-1)
+    if c.size != v.size or c.size < int(rp[-1]):
+        raise ValueError("col / val: row_ptr[-1] entries each")
+    y = np.ascontiguousarray(target_xyz, np.float32)
+    if y.ndim != 2 or y.shape[1] != 3:
+        raise ValueError("target_xyz: (m, 3)")
+    Td = _mat4(T_depth, "T_depth")
+    if state is None:
+        state = (np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32))
+    ds, ws, cnt = state
+    for a, t in ((ds, np.float32), (ws, np.float32), (cnt, np.int32)):
+        if not (isinstance(a, np.ndarray) and a.dtype == t and a.shape == (n,) and a.flags.c_contiguous):
+            raise ValueError("state: (float32[n], float32[n], int32[n]), contiguous")
+    ipp = C.POINTER(C.c_int)
+    _raise_depth(_capi.lib().cvo_depth_filter_accumulate_host(n, rp.ctypes.data_as(ipp), c.ctypes.data_as(ipp), _fptr(v), y.shape[0], _fptr(y),
+                                                              _fptr(Td), _fptr(ds), _fptr(ws), cnt.ctypes.data_as(ipp)),
+                 "cvo_depth_filter_accumulate_host refused the association")
+    return state
+
+
+def depth_filter_finish_host(xyz, state, min_count=3):
+    """cvo_depth_filter_finish_host -> (moved xyz of the kept rows (k, 3), kept original indices, refined depths, rows dropped as
+    non-finite).  No context."""
+    x = np.ascontiguousarray(xyz, np.float32)
+    if x.ndim != 2 or x.shape[1] != 3:
+        raise ValueError("xyz: (n, 3)")
+    n = x.shape[0]
+    _min_count(min_count)
+    ds, ws, cnt = (np.ascontiguousarray(state[0], np.float32), np.ascontiguousarray(state[1], np.float32), np.ascontiguousarray(state[2], np.int32))
+    if ds.shape != (n,) or ws.shape != (n,) or cnt.shape != (n,):
+        raise ValueError("state: three arrays of n entries")
+    out, kept, depth = np.zeros((max(n, 1), 3), np.float32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float32)
+    nk, nf = C.c_int(), C.c_int()
+    ipp = C.POINTER(C.c_int)
+    _raise_depth(_capi.lib().cvo_depth_filter_finish_host(n, _fptr(x), _fptr(ds), _fptr(ws), cnt.ctypes.data_as(ipp), int(min_count), _fptr(out),
+                                                          kept.ctypes.data_as(ipp), _fptr(depth), C.byref(nk), C.byref(nf)),
+                 "cvo_depth_filter_finish_host refused its arguments")
+    k = nk.value
+    return out[:k].copy(), kept[:k].copy(), depth[:k].copy(), nf.value
+
+
 class AlignResult:
     def __init__(self, ret, transform, info, trace=None):
         self.ret = ret
@@ -1571,6 +1727,37 @@ class CvoGPU:
     def download(self, cloud):
         """DeviceCloud.download of a resident cloud."""
         return cloud.download()
+
+    # -- keyframe depth filtering (main_depth_filtering.cpp:208-298) ----
+    def depth_filter_open(self, keyframe):
+        """cvo_depth_filter_open: a DepthFilter over a resident keyframe (DeviceCloud).  The filter copies what it needs: the
+        keyframe may be freed afterwards."""
+        if not isinstance(keyframe, DeviceCloud):
+            raise ValueError("depth_filter_open: the keyframe is a DeviceCloud (CvoGPU.upload makes one)")
+        return DepthFilter(self, keyframe)
+
+    def depth_filter(self, keyframe, frames, Ts, T_depths, kernel, min_count=3, return_kept=False):
+        """cvo_depth_filter: open, add every frame (Ts[k]: the association's transform, T_depths[k]: the one whose third row
+        gives the depth in the keyframe's frame; 4x4 each), finish, close - one call.  The refined keyframe as a DeviceCloud;
+        return_kept: (cloud, kept original indices, refined depths, rows dropped as non-finite)."""
+        if not isinstance(keyframe, DeviceCloud):
+            raise ValueError("depth_filter: the keyframe is a DeviceCloud (CvoGPU.upload makes one)")
+        frames = list(frames)
+        k = len(frames)
+        if any(not isinstance(f, DeviceCloud) for f in frames):
+            raise ValueError("depth_filter: every frame is a DeviceCloud")
+        Tm, Td = _mats_to_c(Ts, k, "Ts"), _mats_to_c(T_depths, k, "T_depths")
+        kcm = _kernel_to_c(kernel)
+        _min_count(min_count)
+        handles = (C.c_void_p * max(k, 1))(*[f.handle for f in frames])
+        kept, depth = np.zeros(max(keyframe.n, 1), np.int32), np.zeros(max(keyframe.n, 1), np.float32)
+        nk, nf, h = C.c_int(), C.c_int(), C.c_void_p()
+        p = self.params.to_ctypes()
+        self._check(self.L.cvo_depth_filter(self.ctx, C.byref(p), keyframe.handle, k, handles, _fptr(Tm), _fptr(Td), _fptr(kcm),
+                                            int(min_count), C.byref(h), kept.ctypes.data_as(C.POINTER(C.c_int)), _fptr(depth),
+                                            C.byref(nk), C.byref(nf)))
+        out = self._adopt(h, nk.value)
+        return (out, kept[:nk.value].copy(), depth[:nk.value].copy(), nf.value) if return_kept else out
 
     def debug_device_buffer(self, data, into=None):
         """cvo_debug_device_buffer: the bytes of a numpy array in device memory -> the device address; into: an address this

@@ -26,6 +26,8 @@
 //   cvo_dfilter.hip the disparity post-filter: libelas's speckle, gap and adaptive-mean passes on the matcher's or a caller's map
 //   cvo_stereo_pair.hip  the entry points that chain matcher, filter and stereo front end under one lock
 //   cvo_bki.hip     the semantic voxel map: posed clouds (host rows or resident) fused into a persistent table, its occupied voxels read out as a cloud
+//   cvo_depth.hip   the keyframe depth filter: a resident keyframe refined from resident frames (the non-isotropic association where its
+//                   evaluation left it, k_depth_accumulate, k_depth_finish, the ordered compaction, the ingest of cvo_ingest.hip)
 #include "cvo_internal.h"
 
 #include "cvo_ctx.hip"
@@ -49,4 +51,5 @@
 #include "cvo_eval.hip"
 #include "cvo_export.hip"
 #include "cvo_irls.hip"
+#include "cvo_depth.hip"
 #include "cvo_debug.hip"

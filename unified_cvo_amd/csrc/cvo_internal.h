@@ -1,5 +1,5 @@
 // cvo_internal.h -- what the sections of the host side (cvo_ctx.hip, cvo_upload.hip, cvo_launch.hip, cvo_sched.hip,
-// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_ingest.hip, cvo_voxel.hip, cvo_merge.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip, cvo_bki.hip, cvo_debug.hip) share: the context, a resident cloud, the typed walk that lays
+// cvo_queue.hip, cvo_eval.hip, cvo_export.hip, cvo_frontend.hip, cvo_ingest.hip, cvo_voxel.hip, cvo_merge.hip, cvo_rgbd.hip, cvo_lidar.hip, cvo_nlm.hip, cvo_sgm.hip, cvo_dfilter.hip, cvo_stereo_pair.hip, cvo_bki.hip, cvo_depth.hip, cvo_debug.hip) share: the context, a resident cloud, the typed walk that lays
 // out EVERY device region (ScratchLayout: a pair's workspace, the front ends' scratch, the map's table, a cloud's slabs, the control block, the score blocks), the owner of
 // EVERY device and pinned allocation (Region: move-only, frees in its destructor, ONE grow rule - drain, free, allocate, tell the caller it moved), graph keys and the error helpers.  The context's switches: cvo_options.h.  Included once, by cvo_hip.hip.
 #pragma once

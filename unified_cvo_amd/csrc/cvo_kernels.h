@@ -81,3 +81,4 @@
 #include "cvo_k_bki_stage.h"
 #include "cvo_k_bki_sparse.h"
 #include "cvo_k_bki_query.h"
+#include "cvo_k_depth.h"
