@@ -206,6 +206,18 @@ def test_every_plane_null_in_turn(gpu):
     assert L.cvo_map_query(m.handle, len(pts), pts.ctypes.data_as(C.POINTER(C.c_float)), C.byref(q)) == 0
     assert np.array_equal(qc.raw(centre), qc.raw(qc.expected("room")["query"]["centre"]))
     m.close()
+    # the ray cast's table: no output at all, then each output alone
+    m, (o, e, mask, steps) = device_map(gpu, "wall"), qc.case("wall").rays[0]
+    o, e = np.ascontiguousarray(np.broadcast_to(np.asarray(o, F32), np.shape(e))), np.ascontiguousarray(e, F32)
+    fp, want = C.POINTER(C.c_float), m.raycast(o, e, stop=mask, max_steps=steps)
+    assert qc.first_difference(want, qc.expected("wall")["rays"][0], qc.RAY_FIELDS) is None
+    assert L.cvo_map_raycast(m.handle, len(e), o.ctypes.data_as(fp), e.ctypes.data_as(fp), mask, steps, None) == 0
+    for field in qc.RAY_FIELDS:
+        one, r = np.zeros_like(getattr(want, field)), _capi.cvo_map_ray_out_t()
+        setattr(r, field, one.ctypes.data)
+        assert L.cvo_map_raycast(m.handle, len(e), o.ctypes.data_as(fp), e.ctypes.data_as(fp), mask, steps, C.byref(r)) == 0
+        assert np.array_equal(qc.raw(one), qc.raw(getattr(want, field))), field
+    m.close()
 
 
 # ---- 5. refusals ----

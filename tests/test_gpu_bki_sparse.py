@@ -198,6 +198,7 @@ def test_side_rule_of_a_map_that_starts_sparse():
         cfg = sc.config(sf2=1.0, ell=1.0, num_classes=2)  # (free_resolution 100, no beam samples: n + 1 training points)
         xyz, feat, label, origin = frames[0]
         cloud = g.upload(CvoPointCloud.from_arrays(xyz, feat, res.wide(label)))
+        tables = {}
         for route in ("insert", "insert_cloud"):
             m = open_map(g, cfg, kernel)
             if route == "insert":
@@ -206,8 +207,13 @@ def test_side_rule_of_a_map_that_starts_sparse():
                 m.insert_cloud(cloud, origin=origin)
             stats = m.debug_stats(readback=True)
             assert stats["training"] == n + 1 and stats["on_device"] == on_device, (kernel, n, route)
+            tables[route] = stats
             m.insert((xyz, feat, label), origin=origin)  # the side is kept
             assert m.debug_stats()["on_device"] == on_device
             m.close()
+        if not on_device:  # the twin stores voxels as they come: the resident rows, copied down, leave the host rows' table bit for bit
+            for k in ("keys", "ms", "fs"):
+                assert len(tables["insert"][k]) > 0
+                assert np.array_equal(tables["insert"][k].view(np.uint8), tables["insert_cloud"][k].view(np.uint8)), (kernel, n, k)
         cloud.free()
     g.close()

@@ -1,10 +1,14 @@
 // cvo_bki_math.h -- the arithmetic of the semantic voxel map (semantic_bki::SemanticBKIOctoMap under its counting sensor
-// model, block_depth = 1) that the CPU twin (cvo_bki.hip) and the kernels (cvo_k_bki.h) share, so that the two cannot drift:
+// model, block_depth = 1) that the CPU twin (cvo_bki_twin.h) and the kernels (cvo_k_bki.h) share, so that the two cannot drift:
 // the block index of a coordinate, the closed float box of a block, the beam samples of a hit, the class of a label row, the
 // state of a voxel and the rows of the cloud read out - and, for the sparse kernel, the weight with its own sin / cos routine
 // and the neighbour slots.  tests/np_bki.py and tests/np_bki_sparse.py state the same in numpy.  Everything here is plain
-// float / double arithmetic without fused multiply-adds (the build compiles with -ffp-contract=off).
+// float / double arithmetic without fused multiply-adds (the build compiles with -ffp-contract=off).  A host compiler takes
+// this header too (for cvo_bki_twin.h; cvo_host_attrs.h).
 #pragma once
+#include <cmath>
+
+#include "cvo_host_attrs.h"
 
 namespace cvo_dev {
 
@@ -40,6 +44,16 @@ __host__ __device__ inline float bki_centre(long long k, float size) { return (f
 __host__ __device__ inline bool bki_holds(long long k, float p, float size, float half) {
   const float c = bki_centre(k, size);
   return c - half <= p && p <= c + half;
+}
+
+// the centre of block `key` on one axis, its 20-bit index unpacked (THE place that knows the key's layout backwards), and on all three
+__host__ __device__ inline float bki_key_centre1(unsigned long long key, int axis, float size) {
+  return bki_centre((long long)(axis == 0 ? key >> 40 : (axis == 1 ? (key >> 20) & 0xFFFFFull : key & 0xFFFFFull)), size);
+}
+__host__ __device__ inline void bki_key_centre(unsigned long long key, float size, float out[3]) {
+  out[0] = bki_key_centre1(key, 0, size);
+  out[1] = bki_key_centre1(key, 1, size);
+  out[2] = bki_key_centre1(key, 2, size);
 }
 
 // the blocks of k0 - 1, k0, k0 + 1 that hold p on one axis, ascending; returns how many (0: p lies in a rounding gap)
@@ -137,11 +151,7 @@ __host__ __device__ inline int bki_state(const BkiConst& k, const float* ms) {
 
 // the row of an occupied voxel in the cloud read out: its centre, fs / sum(ms[1:]), ms[1 .. C] / sum(ms)
 __host__ __device__ inline void bki_row(const BkiConst& k, unsigned long long key, const float* ms, const float* fs, float* xyz, float* feat, float* label) {
-  if (xyz) {
-    xyz[0] = bki_centre((long long)(key >> 40), k.size);
-    xyz[1] = bki_centre((long long)((key >> 20) & 0xFFFFFull), k.size);
-    xyz[2] = bki_centre((long long)(key & 0xFFFFFull), k.size);
-  }
+  if (xyz) bki_key_centre(key, k.size, xyz);
   if (feat) {
     const float occ = bki_sum(ms, 1, k.nclass);
     for (int c = 0; c < BKI_FEAT; c++) feat[c] = fs[c] / occ;
@@ -212,6 +222,12 @@ constexpr unsigned long long BKI_NO_KEY = ~0ull;  // the key of a ray that walke
 
 // the one NaN the read side writes (the centre of a point outside the key range, of a ray that walked nothing)
 __host__ __device__ inline float bki_nan() { return __builtin_bit_cast(float, 0x7fc00000u); }
+// ... and the centre a read answers with: the voxel's, or that NaN three times
+__host__ __device__ inline void bki_key_centre_or_nan(bool valid, unsigned long long key, float size, float out[3]) {
+  out[0] = valid ? bki_key_centre1(key, 0, size) : bki_nan();
+  out[1] = valid ? bki_key_centre1(key, 1, size) : bki_nan();
+  out[2] = valid ? bki_key_centre1(key, 2, size) : bki_nan();
+}
 
 // the voxel of a point: the key of its k0 per axis (block_to_hash_key); false: not finite, or a k0 outside [1, 2^20 - 2]
 __host__ __device__ inline bool bki_point_key(float x, float y, float z, float size, unsigned long long* key) {

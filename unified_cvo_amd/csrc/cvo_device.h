@@ -10,6 +10,7 @@
 
 #include "../../include/cvo_hip.h"
 #include "../../include/cvo_hip_debug.h"
+#include "cvo_pose_math.h"
 
 namespace cvo_dev {
 
@@ -466,11 +467,12 @@ __device__ __forceinline__ V3 transform_point(const float* Ri, const float* Ti, 
 // transform_point_pose_vec (CvoGPU_impl.cu:85-161): a 3x4 ROW-major pose times (x, y, z, 1).  Eigen evaluates the
 // fixed-size 4-term inner product as (c0 + c1) + (c2 + c3); with nvcc's fmad contraction that is assumed to lower to
 // fma(T0, x, T1*y) + fma(T2, z, T3) (the first product of each sum is fused; T3 * 1.0f folds).  The oracle mirrors
-// exactly this form; like everything else here it is unpinned against a real reference build.
+// exactly this form; like everything else here it is unpinned against a real reference build.  The expression itself is
+// pose_point (cvo_pose_math.h), which the host loops that must equal the kernels call too.
 __device__ __forceinline__ V3 transform_point_pose_vec(const float* T, float x, float y, float z) {
-  return {__builtin_fmaf(T[0], x, T[1] * y) + __builtin_fmaf(T[2], z, T[3]),
-          __builtin_fmaf(T[4], x, T[5] * y) + __builtin_fmaf(T[6], z, T[7]),
-          __builtin_fmaf(T[8], x, T[9] * y) + __builtin_fmaf(T[10], z, T[11])};
+  float m[3];
+  pose_point(T, x, y, z, m);
+  return {m[0], m[1], m[2]};
 }
 
 // ---- double-precision division and exp() of the row loops, restated so that their loop-invariant parts can be hoisted ----

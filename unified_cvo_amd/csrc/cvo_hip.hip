@@ -25,7 +25,9 @@
 //   cvo_sgm.hip     the stereo matcher: left + right gray planes to the left disparity (semi-global matching over census)
 //   cvo_dfilter.hip the disparity post-filter: libelas's speckle, gap and adaptive-mean passes on the matcher's or a caller's map
 //   cvo_stereo_pair.hip  the entry points that chain matcher, filter and stereo front end under one lock
-//   cvo_bki.hip     the semantic voxel map: posed clouds (host rows or resident) fused into a persistent table, its occupied voxels read out as a cloud
+//   cvo_bki.hip     the semantic voxel map: posed clouds (host rows or resident) fused into a persistent table, its occupied voxels read out as a cloud,
+//                   point queries, ray casts and rendered views of it (the handle, the side rule and the device side; the CPU twin is
+//                   cvo_bki_twin.h, plain C++ that a host compiler builds without a device)
 //   cvo_depth.hip   the keyframe depth filter: a resident keyframe refined from resident frames (the non-isotropic association where its
 //                   evaluation left it, k_depth_accumulate, k_depth_finish, the ordered compaction, the ingest of cvo_ingest.hip)
 #include "cvo_internal.h"

@@ -1,6 +1,6 @@
 // cvo_k_bki_query.h -- the read side of the semantic voxel map on the device: what is at this point (k_bki_query, upstream's
 // SemanticBKIOctoMap::search with the node's getters), what does this segment meet first (k_bki_raycast), what does the map
-// look like from this pose (k_bki_render).  The arithmetic is cvo_bki_math.h, shared with the CPU twin (cvo_bki.hip); the
+// look like from this pose (k_bki_render).  The arithmetic is cvo_bki_math.h, shared with the CPU twin (cvo_bki_twin.h); the
 // statement is tests/np_bki_query.py.  The three kernels only READ the table (table_find, cvo_k_prims.h): the host enqueues
 // them on the upload stream behind every insert, no counter, key, ms or fs is written.
 //
@@ -30,7 +30,7 @@
 // bound looks like and what neither a VALU nor a bandwidth bound would give; the longest ray (about 2000 voxels) is the critical
 // path, and 66 blocks of 256 lanes leave most CUs idle.  k_bki_query has one probe per point: 30 - 45 us of a 0.3 ms call, which
 // is the launch and the copies around it at the sizes a frame has.  Part of the kernel set of cvo_kernels.h; compiled only as part of
-// cvo_hip.hip.  Host side: cvo_bki.hip.
+// cvo_hip.hip.  Host side: cvo_bki.hip (the twin: cvo_bki_twin.h).
 #pragma once
 #include "cvo_k_bki.h"
 
@@ -139,9 +139,7 @@ __global__ __launch_bounds__(BKI_QUERY_THREADS) void k_bki_query(BkiQueryArgs a)
       s_slot[tid] = slot;
       s_sum[tid] = sum;
       s_occ[tid] = occ;
-      s_centre[3 * tid] = inside ? bki_centre((long long)(key >> 40), a.k.size) : bki_nan();
-      s_centre[3 * tid + 1] = inside ? bki_centre((long long)((key >> 20) & 0xFFFFFull), a.k.size) : bki_nan();
-      s_centre[3 * tid + 2] = inside ? bki_centre((long long)(key & 0xFFFFFull), a.k.size) : bki_nan();
+      bki_key_centre_or_nan(inside, key, a.k.size, s_centre + 3 * tid);
       if (a.found) a.found[row] = (unsigned char)(!inside ? BKI_Q_OUTSIDE : (slot != SLOT_NONE ? BKI_Q_FOUND : BKI_Q_ABSENT));
       if (a.state) a.state[row] = (unsigned char)state;
       if (a.semantics) a.semantics[row] = sem;
@@ -189,10 +187,10 @@ __global__ __launch_bounds__(BKI_THREADS) void k_bki_raycast(BkiRaycastArgs a) {
   const BkiRayOut& out = a.out;
   if (out.status) out.status[i] = (unsigned char)r.status;
   if (out.key) out.key[i] = r.key;
-  if (out.centre) {
-    out.centre[3 * (size_t)i] = walked ? bki_centre((long long)(r.key >> 40), a.k.size) : bki_nan();
-    out.centre[3 * (size_t)i + 1] = walked ? bki_centre((long long)((r.key >> 20) & 0xFFFFFull), a.k.size) : bki_nan();
-    out.centre[3 * (size_t)i + 2] = walked ? bki_centre((long long)(r.key & 0xFFFFFull), a.k.size) : bki_nan();
+  if (out.centre) {  // (bki_key_centre_or_nan, written out: through the one pointer the compiler schedules the kernel differently)
+    out.centre[3 * (size_t)i] = walked ? bki_key_centre1(r.key, 0, a.k.size) : bki_nan();
+    out.centre[3 * (size_t)i + 1] = walked ? bki_key_centre1(r.key, 1, a.k.size) : bki_nan();
+    out.centre[3 * (size_t)i + 2] = walked ? bki_key_centre1(r.key, 2, a.k.size) : bki_nan();
   }
   if (out.t) out.t[i] = r.t;
   if (out.steps) out.steps[i] = r.steps;

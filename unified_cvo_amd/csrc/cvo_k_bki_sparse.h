@@ -82,15 +82,6 @@ __global__ __launch_bounds__(BKI_THREADS) void k_bkis_emit(BkiSparseArgs s) {
   });
 }
 
-// the slot of `key` in a table no kernel is writing keys to, or SLOT_NONE
-__device__ __forceinline__ unsigned bkis_find(const BkiTable& t, unsigned long long key) {
-  for (unsigned g = (unsigned)key_mix(key) & t.mask;; g = (g + 1) & t.mask) {
-    const unsigned long long k = t.keys[g];
-    if (k == key) return g;
-    if (k == TABLE_EMPTY) return SLOT_NONE;
-  }
-}
-
 __global__ __launch_bounds__(BKI_THREADS) void k_bkis_heads(BkiSparseArgs s) {
   const BkiTable& t = s.a.t;
   const unsigned p = blockIdx.x * BKI_THREADS + threadIdx.x;
@@ -132,18 +123,12 @@ __global__ __launch_bounds__(BKI_THREADS) void k_bkis_heads(BkiSparseArgs s) {
 __device__ __forceinline__ bool bkis_segment(const BkiTable& t, unsigned long long vkey, unsigned g, int j, unsigned* from, unsigned* to) {
   unsigned long long key;
   if (!bki_sparse_slot(vkey, j, &key)) return false;
-  const unsigned gn = j ? bkis_find(t, key) : g;
+  const unsigned gn = j ? table_find(t.keys, t.mask, (unsigned)key_mix(key), key) : g;  // (no kernel is writing keys now)
   if (gn == SLOT_NONE) return false;
   *to = t.cnt[(size_t)gn * t.ncnt];
   if (!*to) return false;
   *from = t.segoff[gn];
   return *from < *to;
-}
-
-__device__ __forceinline__ void bkis_centre(const BkiConst& k, unsigned long long key, float c[3]) {
-  c[0] = bki_centre((long long)(key >> 40), k.size);
-  c[1] = bki_centre((long long)((key >> 20) & 0xFFFFFull), k.size);
-  c[2] = bki_centre((long long)(key & 0xFFFFFull), k.size);
 }
 
 constexpr int BKIS_ACC = BKI_MAX_CLASSES + 1 + BKI_FEAT;  // a voxel's columns: ybar of every class, fbar
@@ -170,7 +155,7 @@ __global__ __launch_bounds__(BKI_THREADS) void k_bkis_update(BkiSparseArgs s) {
       continue;
     }
     float centre[3];
-    bkis_centre(k, vkey, centre);
+    bki_key_centre(vkey, k.size, centre);
     float* ms = t.ms + (size_t)g * t.nclass;
     float* fs = t.fs + (size_t)g * BKI_FEAT;
     for (int j = 0; j < BKI_SPARSE_SLOTS; j++) {
@@ -204,7 +189,7 @@ __global__ __launch_bounds__(BKI_WAVE) void k_bkis_long(BkiSparseArgs s) {
     const unsigned g = s.longlist[q];
     const unsigned long long vkey = t.keys[g];
     float centre[3];
-    bkis_centre(s.a.k, vkey, centre);
+    bki_key_centre(vkey, s.a.k.size, centre);
     // lane c < nclass holds ms[c], lane nclass + f holds fs[f]
     const bool is_ms = lane < nclass, is_fs = lane >= nclass && lane < nclass + (unsigned)BKI_FEAT;
     float* out = is_ms ? t.ms + (size_t)g * nclass + lane : (is_fs ? t.fs + (size_t)g * BKI_FEAT + (lane - nclass) : nullptr);

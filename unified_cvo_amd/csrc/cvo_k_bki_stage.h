@@ -1,7 +1,7 @@
 // cvo_k_bki_stage.h -- k_bki_stage: the rows of ONE resident cloud, in ORIGINAL order, as the hits of one insert into the
 // semantic voxel map (cvo_map_insert_cloud).  It writes the insert scratch in exactly the layout k_bki_count ... k_bki_long
 // read (BkiInsertArgs, cvo_k_bki.h): xyz n x 3, feat n x 5, label n x C, all packed, so the six insert kernels run unchanged
-// behind it - and, on a map of the host side, the three arrays are what bki_insert_cpu takes once they are copied down.
+// behind it - and, on a map of the host side, the three arrays are what the twin's insert takes once they are copied down.
 //
 // The addressing is k_cloud_unpack's (cvo_k_merge.h) for one job: row i has its coordinates in x4[i] - under the pose
 // transform_point_pose_vec(pose, x4[i]), the function cvo_cloud_transformed and cvo_map_insert_posed's host loop share;
@@ -24,7 +24,7 @@
 // Traffic per point of a cloud with colour and 19 classes: 16 + 4 + 32 + 80 = 132 B read (20 + 4 C + 36 in general), 12 + 20
 // + 4 C <= 108 B written.  9 284 points are 1.2 MB + 1.0 MB, 16 686 are 2.2 MB + 1.8 MB: under a microsecond at HBM speed,
 // no arithmetic to speak of - the launch is bound by its latency.  Part of the kernel set of
-// cvo_kernels.h; compiled only as part of cvo_hip.hip.  Host side: cvo_bki.hip.
+// cvo_kernels.h; compiled only as part of cvo_hip.hip.  Host side: cvo_bki.hip (the twin: cvo_bki_twin.h).
 #pragma once
 #include "cvo_k_bki.h"
 
