@@ -381,6 +381,35 @@ std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::upload_device_aos192(const CvoPo
   return out;
 }
 
+std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::upload_rgbd_points_device(const cvo_rgbd_device_frame_t& frame,
+                                                                          CvoPointCloud::PointSelectionMethod method) const {
+  std::lock_guard<std::mutex> lk(call_mutex);
+  std::unique_ptr<ResidentClouds> out(new ResidentClouds());
+  out->handles.assign(1, nullptr);
+  out->kept_.resize(1);
+  std::vector<int>& pixel = out->kept_[0];
+  pixel.resize((size_t)std::max(frame.rows, 1) * (size_t)std::max(frame.cols, 1));
+  int n = 0;
+  check(ctx, cvo_cloud_from_rgbd_device(ctx, &frame, (int)method, out->handles.data(), &n, pixel.data()), "cvo_cloud_from_rgbd_device");
+  pixel.resize((size_t)n);
+  return out;
+}
+
+std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::upload_rgbd_device(const cvo_rgbd_device_frame_t& frame, float leaf, float edge_divisor) const {
+  std::lock_guard<std::mutex> lk(call_mutex);
+  std::unique_ptr<ResidentClouds> out(new ResidentClouds());
+  out->handles.assign(1, nullptr);
+  out->kept_.resize(1);
+  std::vector<int>& pixel = out->kept_[0];
+  pixel.resize(2 * (size_t)std::max(frame.rows, 1) * (size_t)std::max(frame.cols, 1));
+  int n = 0, n_edge = 0;
+  check(ctx, cvo_cloud_from_rgbd_device_recipe(ctx, &frame, leaf > 0.f ? leaf : params.multiframe_downsample_voxel_size, edge_divisor,
+                                               out->handles.data(), &n, &n_edge, pixel.data()),
+        "cvo_cloud_from_rgbd_device_recipe");
+  pixel.resize((size_t)n);
+  return out;
+}
+
 std::unique_ptr<CvoGPU::ResidentClouds> CvoGPU::merge(const ResidentClouds& clouds, const std::vector<double>* poses, float voxel_size) const {
   if (poses && poses->size() != 12 * (size_t)clouds.size()) throw std::invalid_argument("merge: 12 pose entries per cloud");
   std::lock_guard<std::mutex> lk(call_mutex);

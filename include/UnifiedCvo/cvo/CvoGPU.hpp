@@ -92,6 +92,14 @@ class CvoGPU {
   // upload_clouds returns for one cloud, without a host copy.  Refusals (host pointers, strides, row indices) throw.
   std::unique_ptr<ResidentClouds> upload_device(const cvo_device_rows_t& rows) const;
   std::unique_ptr<ResidentClouds> upload_device_aos192(const CvoPoint* d_pts, int n) const;
+  // New: a resident cloud from an RGB-D FRAME that is already in this object's device memory (cvo_cloud_from_rgbd_device /
+  // _recipe, include/cvo_hip.h: dense image / gray / depth planes, class scores with byte strides, complete when the call
+  // is made).  upload_rgbd_points_device: CvoPointCloud(ImageRGBD, Calibration, method) for DSO_EDGES / FULL as
+  // upload_clouds would hold it; upload_rgbd_device: the multi-frame drivers' recipe (leaf <= 0 takes
+  // params.multiframe_downsample_voxel_size) - edge points first.  kept(0): the pixel index v * cols + u of every point.
+  // No plane and no row crosses to the host.  Refusals (host pointers, strides, extents, other methods) throw.
+  std::unique_ptr<ResidentClouds> upload_rgbd_points_device(const cvo_rgbd_device_frame_t& frame, CvoPointCloud::PointSelectionMethod method) const;
+  std::unique_ptr<ResidentClouds> upload_rgbd_device(const cvo_rgbd_device_frame_t& frame, float leaf = 0.f, float edge_divisor = 4.f) const;
   // New: what the multi-frame drivers do right after the solve (merge_transformed_pc + a VoxelMap of side leaf / 2,
   // main_covisMap_test.cpp:183-215, 464-534) without a host copy of any frame (cvo_cloud_merge, include/cvo_hip.h): ONE
   // resident cloud (size() == 1) of the rows of every cloud of `clouds`, in original order, cloud after cloud, each moved by

@@ -289,6 +289,54 @@ int cvo_rgbd_points_host(const cvo_rgbd_frame_t* frame, int method, int* pixel, 
  * entries): pixel index and set of every point; *n their number.  leaf, edge_divisor: finite and > 0. */
 int cvo_cloud_upload_rgbd(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, float leaf, float edge_divisor, cvo_cloud** out,
                           int* pixel, unsigned char* is_edge, int* n);
+/* ---- RGB-D frames that are already in device memory: the counterpart of cvo_cloud_from_device for frames ----
+ * A network's class scores in a tensor, a rendered view, an image the caller's own HIP code produced: image, depth and scores
+ * go in where they are, a RESIDENT cloud comes out.  No plane and no row crosses to the host, no host thread touches a pixel.
+ * image / gray / depth are DENSE (no strides): rows x cols x channels bytes, rows x cols bytes, rows x cols uint16_t or float.
+ * The score of class c at pixel (v, u) is the float at semantic + v * row_stride + u * pixel_stride + c * class_stride (bytes):
+ * H x W x C is (4 C cols, 4 C, 4), C x H x W is (4 cols, 4, 4 rows cols), a column slice of a wider tensor has larger ones.
+ * Contract (cvo_cloud_from_device's): every pointer is device memory of the context's device, complete when the call is made
+ * (the caller synchronises its producer stream).  The library enqueues on its upload stream and returns after it has
+ * synchronised that stream; the planes are only read - in place, nothing is staged -, the cloud owns what it keeps and may
+ * outlive them.  With f the host copy of the frame (scores brought to H x W x C): cvo_cloud_from_rgbd_device's cloud is
+ * interchangeable with cvo_cloud_upload of cvo_rgbd_points(f, method)'s rows, features zero-padded to 5 and classes to 19 (no
+ * label array without classes); cvo_cloud_from_rgbd_device_recipe's with cvo_cloud_upload_rgbd(f, leaf, edge_divisor)'s - the
+ * same n, n_edge and pixel order, the same rows on cvo_cloud_download, the same cvo_debug_cloud_order and one-hot detection,
+ * bit-identical scores and solves.  cvo_debug_rgbd_stats reports what the host-frame device route reports for f.
+ * Device frames ALWAYS take the kernels: RGBD_HOST and its crossover do not apply to them.  ORDER / NO_SORT / NO_ONEHOT act
+ * through the ingest as for cvo_cloud_from_device.  pixel (HOST memory, optional): the pixel index of every point, room for
+ * rows x cols (recipe: 2 x rows x cols) ints; NULL saves the copy and a synchronisation.
+ * CVO_E_INVALID, nothing allocated, *out NULL, decided on the host before any launch: cvo_rgbd_points' refusals of shape,
+ * channels, a missing plane, fx / fy / scaling_factor (and cvo_cloud_upload_rgbd's of leaf / edge_divisor), with the same
+ * messages; a semantic stride that is 0 or no multiple of 4; a plane that is not aligned (float depth and scores 4 bytes,
+ * uint16_t depth 2), that hipPointerGetAttributes does not report as device memory of this context's device (host, pinned
+ * and managed memory, other devices), or whose extent does not fit the allocation behind it.  No pointer is read through
+ * before it is classified.  CVO_E_UNSUPPORTED: the other selection methods, more than 2^24 pixels, a shape whose literal
+ * threshold index leaves the reference's allocation, num_classes > 19 (a resident cloud holds 19 class columns). */
+typedef struct cvo_rgbd_device_frame_t {
+  int rows, cols, channels;          /* channels: 1 or 3 */
+  const void* image;                 /* device, rows x cols x channels bytes, dense (BGR for 3): what RawImage holds after denoising */
+  const void* gray;                  /* device, rows x cols bytes, dense, or NULL (then as in cvo_rgbd_frame_t) */
+  const void* depth; int depth_type; /* device, rows x cols, dense; CVO_DEPTH_U16 / CVO_DEPTH_F32 */
+  float fx, fy, cx, cy, scaling_factor;
+  int num_classes;                   /* 0 .. 19; 0 = no semantics */
+  const void* semantic;              /* device floats, strided as above; NULL without classes */
+  size_t semantic_row_stride, semantic_pixel_stride, semantic_class_stride;   /* bytes */
+} cvo_rgbd_device_frame_t;
+/* CvoPointCloud(ImageRGBD, Calibration, method), method DSO_EDGES or FULL, as a resident cloud; *n (optional): its points */
+int cvo_cloud_from_rgbd_device(cvo_ctx* ctx, const cvo_rgbd_device_frame_t* frame, int method, cvo_cloud** out, int* n, int* pixel);
+/* the drivers' recipe, cvo_cloud_upload_rgbd's cloud; *n_edge (optional): the first n_edge points are the edges */
+int cvo_cloud_from_rgbd_device_recipe(cvo_ctx* ctx, const cvo_rgbd_device_frame_t* frame, float leaf, float edge_divisor,
+                                      cvo_cloud** out, int* n, int* n_edge, int* pixel);
+/* CPU twin of the row and exclusion arithmetic, no context: `frame` holds HOST pointers with the same strides.  The rows of the
+ * n given pixels (v * cols + u, each inside the image) as the resident cloud holds them - recipe 0: the constructor's rows of
+ * `method` (features zero-padded to 5), recipe 1: the recipe's rows, is_edge[i] != 0 an edge row (required) - xyz n x 3,
+ * feat n x 5, label n x 19 (zero-padded; may be NULL), geotype n x 2; excluded (optional): 1 where the pixel's first-maximum
+ * class is 10.  Any output may be NULL.  CVO_E_INVALID: what cvo_cloud_from_rgbd_device refuses of the frame's fields, n < 0,
+ * a pixel outside the image; CVO_E_UNSUPPORTED: num_classes > 19, another method. */
+int cvo_rgbd_frame_rows_host(const cvo_rgbd_device_frame_t* frame, int recipe, int method, int n, const int* pixel,
+                             const unsigned char* is_edge, float* xyz, float* feat, float* label, float* geotype,
+                             unsigned char* excluded);
 /* ---- CV_FAST point selection: replaces select_points_from_image's CV_FAST branch (CvoPointCloud.cpp:273-312) ----
  * cv::FAST(gray, keypoints, t, nonmax = false), TYPE_9_16: a pixel with 3 <= x < cols - 3, 3 <= y < rows - 3 is a corner at t
  * iff 9 cyclically contiguous pixels of its radius-3 ring are all brighter than I_p + t or all darker than I_p - t (strict;

@@ -11,4 +11,5 @@ from .api import (CvoGPU, CvoPointCloud, DeviceCloud, DeviceCloudAoS, CvoError, 
                   nlm_weights, nlm_denoise_host, nlm_denoise_lab_host,
                   SGMConfig, stereo_disparity_host, DFilterConfig, disparity_filter_host,
                   MapConfig, SemanticMap, MapQuery, MapRays, MapView, map_open_host, map_insert_host, map_cloud_host, map_close_host,
-                  DepthFilter, depth_filter_accumulate_host, depth_filter_finish_host)
+                  DepthFilter, depth_filter_accumulate_host, depth_filter_finish_host,
+                  DeviceRGBDFrame, rgbd_frame_rows_host)

@@ -178,6 +178,31 @@ class cvo_rgbd_frame_t(C.Structure):
     ]
 
 
+class cvo_rgbd_device_frame_t(C.Structure):
+    """An RGB-D frame whose planes are in device memory (cvo_cloud_from_rgbd_device) - or, for cvo_rgbd_frame_rows_host, in host
+    memory: dense image / gray / depth, class scores with byte strides."""
+
+    _fields_ = [
+        ("rows", C.c_int),
+        ("cols", C.c_int),
+        ("channels", C.c_int),
+        ("image", C.c_void_p),
+        ("gray", C.c_void_p),
+        ("depth", C.c_void_p),
+        ("depth_type", C.c_int),
+        ("fx", C.c_float),
+        ("fy", C.c_float),
+        ("cx", C.c_float),
+        ("cy", C.c_float),
+        ("scaling_factor", C.c_float),
+        ("num_classes", C.c_int),
+        ("semantic", C.c_void_p),
+        ("semantic_row_stride", C.c_size_t),
+        ("semantic_pixel_stride", C.c_size_t),
+        ("semantic_class_stride", C.c_size_t),
+    ]
+
+
 class cvo_fast_schedule_t(C.Structure):
     _fields_ = [("thresh", C.c_int), ("num_want", C.c_int), ("num_min", C.c_int), ("break_thresh", C.c_int)]
 
@@ -342,6 +367,7 @@ EXPORTED = [
     "cvo_depth_filter_open", "cvo_depth_filter_add", "cvo_depth_filter_size", "cvo_depth_filter_state", "cvo_depth_filter_finish",
     "cvo_depth_filter_close", "cvo_depth_filter", "cvo_depth_filter_accumulate_host", "cvo_depth_filter_finish_host",
     "cvo_debug_depth_filter_rows",
+    "cvo_cloud_from_rgbd_device", "cvo_cloud_from_rgbd_device_recipe", "cvo_rgbd_frame_rows_host",
 ]
 
 _libs = {}
@@ -443,6 +469,10 @@ def lib(path=None):
     L.cvo_rgbd_points.argtypes = [vp, fr, ip, ipp, ipp, fp, fp, fp, fp]
     L.cvo_rgbd_points_host.argtypes = [fr, ip, ipp, ipp, fp, fp, fp, fp]
     L.cvo_cloud_upload_rgbd.argtypes = [vp, fr, C.c_float, C.c_float, C.POINTER(vp), ipp, C.POINTER(C.c_ubyte), ipp]
+    dfr = C.POINTER(cvo_rgbd_device_frame_t)
+    L.cvo_cloud_from_rgbd_device.argtypes = [vp, dfr, C.c_int, C.POINTER(vp), ipp, ipp]
+    L.cvo_cloud_from_rgbd_device_recipe.argtypes = [vp, dfr, C.c_float, C.c_float, C.POINTER(vp), ipp, ipp, ipp]
+    L.cvo_rgbd_frame_rows_host.argtypes = [dfr, C.c_int, C.c_int, C.c_int, ipp, C.POINTER(C.c_ubyte), fp, fp, fp, fp, C.POINTER(C.c_ubyte)]
     L.cvo_debug_rgbd_stats.argtypes = [vp, ipp, ipp, ipp] + [C.POINTER(C.c_ulonglong)] * 4 + [ipp]
     L.cvo_debug_rgbd_readback.argtypes = [vp, ipp, ipp, ipp, fp, fp, fp, ipp]
     sched, sf, up = C.POINTER(cvo_fast_schedule_t), C.POINTER(cvo_stereo_frame_t), C.POINTER(C.c_ubyte)

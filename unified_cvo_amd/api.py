@@ -1039,6 +1039,157 @@ def _sync_producers(objs):
             cur(o.device).synchronize()
 
 
+def _is_tensor(a):
+    return hasattr(a, "data_ptr")
+
+
+def _plane_checks(name, a, dtypes, device):
+    """dtype, device and density of a tensor handed over as a dense plane -> its dtype's name."""
+    kind = [d for d in dtypes if str(a.dtype).endswith(d)]
+    if not kind:
+        raise TypeError(f"{name}: dtype {a.dtype}, {' or '.join(dtypes)} is required")
+    dev = a.device
+    if getattr(dev, "type", "cuda") == "cpu":
+        raise ValueError(f"{name} is a host tensor")
+    if getattr(dev, "index", None) not in (None, device):
+        raise ValueError(f"{name} is on device {dev.index}, the context on {device}")
+    shape, stride, want = tuple(a.shape), tuple(a.stride()), 1
+    for k in range(len(shape) - 1, -1, -1):
+        if shape[k] > 1 and stride[k] != want:
+            raise ValueError(f"{name} must be dense: strides {stride} for shape {shape}; pass {name}.contiguous()")
+        want *= shape[k]
+    return kind[0]
+
+
+class DeviceRGBDFrame:
+    """One RGB-D frame whose planes are ALREADY in device memory (cvo_rgbd_device_frame_t): what RGBDFrame holds, never copied.
+    Every plane is either a torch-like object (data_ptr(), stride(), shape, dtype, device) or a tuple of a device address and
+    what a tensor would have said:
+
+        image     (rows, cols) or (rows, cols, 3) uint8, BGR, dense            | (address, rows, cols, channels)
+        depth     (rows, cols) uint16 (or int16 holding those bits) / float32  | (address, "u16" or "f32")
+        gray      None or (rows, cols) uint8, dense                            | (address,)
+        semantic  None or float32 scores, layout "hwc" (rows, cols, classes) or "chw" (classes, rows, cols), ANY strides that
+                  are multiples of 4 bytes - a permuted view, a column slice of a wider tensor -
+                                                                             | (address, classes, row, pixel, class stride in bytes)
+
+    image / gray / depth must be contiguous (`.contiguous()`); the semantic strides are taken from the tensor.  device: the
+    context's device index, checked against every tensor."""
+
+    def __init__(self, image, depth, fx, fy, cx, cy, scaling_factor, gray=None, semantic=None, layout="hwc", device=0):
+        if layout not in ("hwc", "chw"):
+            raise ValueError(f"layout {layout!r}: 'hwc' (rows, cols, classes) or 'chw' (classes, rows, cols)")
+        self.device = int(device)
+        self.tensors = [a for a in (image, depth, gray, semantic) if _is_tensor(a)]
+        if _is_tensor(image):
+            _plane_checks("image", image, ("uint8",), device)
+            shape = tuple(image.shape)
+            if len(shape) == 3 and shape[2] == 1:
+                shape = shape[:2]
+            if len(shape) not in (2, 3) or (len(shape) == 3 and shape[2] != 3):
+                raise ValueError(f"image is {tuple(image.shape)}, (rows, cols) or (rows, cols, 3) is required")
+            self.rows, self.cols, self.channels = int(shape[0]), int(shape[1]), (1 if len(shape) == 2 else 3)
+            self.image = int(image.data_ptr())
+        else:
+            t = tuple(image)
+            if len(t) != 4:
+                raise ValueError("image: give a tensor or (address, rows, cols, channels)")
+            self.image, self.rows, self.cols, self.channels = (int(v) for v in t)
+        if _is_tensor(depth):
+            kind = _plane_checks("depth", depth, ("uint16", "int16", "float32"), device)
+            if tuple(depth.shape) != (self.rows, self.cols):
+                raise ValueError(f"depth is {tuple(depth.shape)}, the image {self.rows} x {self.cols}")
+            self.depth, self.depth_type = int(depth.data_ptr()), (_capi.CVO_DEPTH_F32 if kind == "float32" else _capi.CVO_DEPTH_U16)
+        else:
+            t = tuple(depth)
+            if len(t) != 2 or t[1] not in ("u16", "f32"):
+                raise ValueError('depth: give a tensor or (address, "u16" | "f32")')
+            self.depth, self.depth_type = int(t[0]), (_capi.CVO_DEPTH_F32 if t[1] == "f32" else _capi.CVO_DEPTH_U16)
+        self.gray = None
+        if gray is not None:
+            if _is_tensor(gray):
+                _plane_checks("gray", gray, ("uint8",), device)
+                if tuple(gray.shape) != (self.rows, self.cols):
+                    raise ValueError(f"gray is {tuple(gray.shape)}, the image {self.rows} x {self.cols}")
+                self.gray = int(gray.data_ptr())
+            else:
+                self.gray = int(gray[0] if isinstance(gray, (tuple, list)) else gray)
+        self.num_classes, self.semantic, self.semantic_strides = 0, None, (0, 0, 0)
+        if semantic is not None:
+            if _is_tensor(semantic):
+                if not str(semantic.dtype).endswith("float32"):
+                    raise TypeError(f"semantic: dtype {semantic.dtype}, float32 is required")
+                dev = semantic.device
+                if getattr(dev, "type", "cuda") == "cpu":
+                    raise ValueError("semantic is a host tensor")
+                if getattr(dev, "index", None) not in (None, device):
+                    raise ValueError(f"semantic is on device {dev.index}, the context on {device}")
+                shape, stride = tuple(semantic.shape), tuple(4 * int(s) for s in semantic.stride())
+                if len(shape) != 3 or (shape[:2] if layout == "hwc" else shape[1:]) != (self.rows, self.cols):
+                    raise ValueError(f"semantic is {shape} with layout {layout!r}, the image {self.rows} x {self.cols}")
+                r, p, c = (0, 1, 2) if layout == "hwc" else (1, 2, 0)
+                self.num_classes, self.semantic = int(shape[c]), int(semantic.data_ptr())
+                self.semantic_strides = (stride[r], stride[p], stride[c])
+            else:
+                t = tuple(semantic)
+                if len(t) != 5:
+                    raise ValueError("semantic: give a tensor or (address, classes, row stride, pixel stride, class stride) in bytes")
+                self.semantic, self.num_classes = int(t[0]), int(t[1])
+                self.semantic_strides = tuple(int(v) for v in t[2:])
+        self.fx, self.fy, self.cx, self.cy, self.scaling_factor = (float(v) for v in (fx, fy, cx, cy, scaling_factor))
+
+    def c_struct(self):
+        """cvo_rgbd_device_frame_t over this frame's planes (which must stay allocated until the call returns)."""
+        return _capi.cvo_rgbd_device_frame_t(self.rows, self.cols, self.channels, self.image or None, self.gray, self.depth or None, self.depth_type,
+                                             self.fx, self.fy, self.cx, self.cy, self.scaling_factor, self.num_classes, self.semantic,
+                                             *self.semantic_strides)
+
+
+def rgbd_frame_rows_host(frame, pixel, method=None, recipe=False, is_edge=None, semantic=None, layout="hwc"):
+    """cvo_rgbd_frame_rows_host: the CPU twin of the rows CvoGPU.upload_rgbd_points_device / upload_rgbd_device build, no
+    context.  frame: an RGBDFrame (host arrays); semantic (optional, replaces frame.semantic): a float32 numpy array or view
+    with ANY strides, layout "hwc" or "chw".  pixel: indices v * cols + u.  recipe False: the constructor's rows of `method`
+    (DSO_EDGES / FULL); True: the recipe's rows, is_edge per pixel.  -> dict(xyz (n, 3), feat (n, 5), label (n, 19) or None
+    without classes, geotype (n, 2), excluded (n,) bool)."""
+    L = _capi.lib()
+    if layout not in ("hwc", "chw"):
+        raise ValueError(f"layout {layout!r}: 'hwc' or 'chw'")
+    sem = frame.semantic if semantic is None else semantic
+    nc, sem_ptr, strides = 0, None, (0, 0, 0)
+    if sem is not None:
+        if sem.dtype != np.float32 or sem.ndim != 3:
+            raise ValueError("semantic: a 3-D float32 array is required")
+        r, p, c = (0, 1, 2) if layout == "hwc" else (1, 2, 0)
+        if (sem.shape[r], sem.shape[p]) != (frame.rows, frame.cols):
+            raise ValueError(f"semantic is {sem.shape} with layout {layout!r}, the image {frame.rows} x {frame.cols}")
+        nc, sem_ptr, strides = sem.shape[c], sem.ctypes.data, (sem.strides[r], sem.strides[p], sem.strides[c])
+    pixel = np.ascontiguousarray(pixel, np.int32).reshape(-1)
+    n = pixel.shape[0]
+    if recipe:
+        if is_edge is None or np.asarray(is_edge).reshape(-1).shape[0] != n:
+            raise ValueError("recipe rows need is_edge, one flag per pixel")
+        edge = np.ascontiguousarray(np.asarray(is_edge).reshape(-1) != 0, np.uint8)
+    else:
+        if method is None:
+            raise ValueError("give the method (DSO_EDGES or FULL), or recipe=True")
+        edge = None
+    ptr = lambda a: None if a is None else a.ctypes.data
+    fs = _capi.cvo_rgbd_device_frame_t(frame.rows, frame.cols, frame.channels, ptr(frame.image), ptr(frame.gray), ptr(frame.depth),
+                                       _capi.CVO_DEPTH_U16 if frame.depth.dtype == np.uint16 else _capi.CVO_DEPTH_F32,
+                                       frame.fx, frame.fy, frame.cx, frame.cy, frame.scaling_factor, int(nc), sem_ptr, *[int(s) for s in strides])
+    m = max(n, 1)
+    xyz, feat, geo = np.zeros((m, 3), np.float32), np.zeros((m, FEATURE_DIMENSIONS), np.float32), np.zeros((m, 2), np.float32)
+    label, excl = (np.zeros((m, NUM_CLASSES), np.float32) if nc else None), np.zeros(m, np.uint8)
+    rc = L.cvo_rgbd_frame_rows_host(C.byref(fs), int(bool(recipe)), int(method if method is not None else DSO_EDGES), n,
+                                    pixel.ctypes.data_as(C.POINTER(C.c_int)), None if edge is None else edge.ctypes.data_as(C.POINTER(C.c_ubyte)),
+                                    _fptr(xyz), _fptr(feat), _fptr(label), _fptr(geo), excl.ctypes.data_as(C.POINTER(C.c_ubyte)))
+    if rc != 0:
+        e = CvoError(f"error {rc}: cvo_rgbd_frame_rows_host refused the frame, the method or a pixel")
+        e.code = rc
+        raise e
+    return dict(xyz=xyz[:n], feat=feat[:n], label=None if label is None else label[:n], geotype=geo[:n], excluded=excl[:n].astype(bool))
+
+
 def _mat_to_c(T):
     a = np.ascontiguousarray(np.asarray(T, np.float32).reshape(4, 4).T).reshape(16)
     return a
@@ -1405,6 +1556,44 @@ class CvoGPU:
         d = DeviceCloud.__new__(DeviceCloud)
         d.gpu, d.n, d._keep, d.handle = self, n.value, None, h
         d.pixel, d.is_edge = pixel[:n.value].copy(), is_edge[:n.value].astype(bool)
+        return d
+
+    def _device_frame(self, frame):
+        if not isinstance(frame, DeviceRGBDFrame):
+            raise ValueError("a DeviceRGBDFrame is required (RGBDFrame holds host arrays: rgbd_points / upload_rgbd)")
+        if frame.device != self.device:
+            raise ValueError(f"the frame was described for device {frame.device}, the context is on {self.device}")
+        _sync_producers(frame.tensors)
+        return frame.c_struct()
+
+    def upload_rgbd_points_device(self, frame, method, want_pixel=False):
+        """cvo_cloud_from_rgbd_device: CvoPointCloud(ImageRGBD, Calibration, method), method FULL / DSO_EDGES, of a
+        DeviceRGBDFrame as a resident cloud - the cloud upload(rgbd_points(f, method)) makes of the frame's host copy f, with no
+        plane and no row crossing to the host.  want_pixel: `.pixel`, the index v * cols + u of every point (a copy down and a
+        synchronisation more).  For tensors of a module that offers <module>.cuda.current_stream that stream is synchronised
+        first; with raw addresses the caller has done so."""
+        fs = self._device_frame(frame)
+        pixel = np.zeros(max(frame.rows * frame.cols, 1), np.int32) if want_pixel else None
+        n, h = C.c_int(), C.c_void_p()
+        self._check(self.L.cvo_cloud_from_rgbd_device(self.ctx, C.byref(fs), int(method), C.byref(h), C.byref(n),
+                                                      None if pixel is None else pixel.ctypes.data_as(C.POINTER(C.c_int))))
+        d = self._adopt(h, n.value)
+        if want_pixel:
+            d.pixel = pixel[:n.value].copy()
+        return d
+
+    def upload_rgbd_device(self, frame, leaf=None, edge_divisor=4, want_pixel=False):
+        """cvo_cloud_from_rgbd_device_recipe: upload_rgbd's cloud of a DeviceRGBDFrame; `.n_edge` edge points come first.
+        want_pixel: `.pixel` and `.is_edge` per point, as upload_rgbd sets them."""
+        fs = self._device_frame(frame)
+        pixel = np.zeros(max(2 * frame.rows * frame.cols, 1), np.int32) if want_pixel else None
+        n, ne, h = C.c_int(), C.c_int(), C.c_void_p()
+        self._check(self.L.cvo_cloud_from_rgbd_device_recipe(self.ctx, C.byref(fs), self._voxel_size(leaf), float(edge_divisor), C.byref(h),
+                                                             C.byref(n), C.byref(ne), None if pixel is None else pixel.ctypes.data_as(C.POINTER(C.c_int))))
+        d = self._adopt(h, n.value)
+        d.n_edge = ne.value
+        if want_pixel:
+            d.pixel, d.is_edge = pixel[:n.value].copy(), np.arange(n.value) < ne.value
         return d
 
     def debug_rgbd_stats(self):

@@ -6,12 +6,12 @@
 // helpers shared with the host route (spatial_order, cloud_slab_list, finish_uploads): cvo_upload.hip.
 namespace {
 
-// One array of a cvo_device_rows_t: its rows must lie in ONE allocation of the context's device.  *why: the refusal's text.
-bool device_rows_ok(cvo_ctx* ctx, const char* what, const void* p, size_t stride, size_t row_bytes, size_t n_rows, std::string* why) {
+// One array a caller hands over in device memory (an array of a cvo_device_rows_t, a plane of a cvo_rgbd_device_frame_t): `need`
+// bytes of `units` (rows, bytes) from p, aligned to `align` bytes, must lie in ONE allocation of the context's device.  The
+// pointer is classified here, before anything reads through it.  *why: the refusal's text.
+bool device_extent_ok(cvo_ctx* ctx, const char* what, const void* p, size_t align, size_t need, const std::string& units, std::string* why) {
   const std::string w(what);
-  if (((uintptr_t)p & 3u) != 0) return *why = w + " is not 4-byte aligned", false;
-  if (stride < row_bytes || (stride & 3u) != 0 || stride > 0xffffffffull)
-    return *why = w + ": a stride of " + std::to_string(stride) + " bytes (rows of " + std::to_string(row_bytes) + " bytes, multiples of 4)", false;
+  if (((uintptr_t)p & (align - 1)) != 0) return *why = w + " is not " + std::to_string(align) + "-byte aligned", false;
   hipPointerAttribute_t attr{};
   if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
     (void)hipGetLastError();  // (an unregistered host pointer: the error is this call's answer, not the process's state)
@@ -26,10 +26,18 @@ bool device_rows_ok(cvo_ctx* ctx, const char* what, const void* p, size_t stride
     (void)hipGetLastError();
     return *why = w + ": no allocation found behind the pointer", false;
   }
-  const size_t need = (n_rows - 1) * stride + row_bytes, room = (size_t)((const char*)base + size - (const char*)p);
-  if (need > room)
-    return *why = w + ": " + std::to_string(n_rows) + " rows need " + std::to_string(need) + " bytes, the allocation ends after " + std::to_string(room), false;
+  const size_t room = (size_t)((const char*)base + size - (const char*)p);
+  if (need > room) return *why = w + ": " + units + " need " + std::to_string(need) + " bytes, the allocation ends after " + std::to_string(room), false;
   return true;
+}
+
+// One array of a cvo_device_rows_t: n_rows rows of row_bytes, `stride` bytes apart
+bool device_rows_ok(cvo_ctx* ctx, const char* what, const void* p, size_t stride, size_t row_bytes, size_t n_rows, std::string* why) {
+  const std::string w(what);
+  if (((uintptr_t)p & 3u) != 0) return *why = w + " is not 4-byte aligned", false;
+  if (stride < row_bytes || (stride & 3u) != 0 || stride > 0xffffffffull)
+    return *why = w + ": a stride of " + std::to_string(stride) + " bytes (rows of " + std::to_string(row_bytes) + " bytes, multiples of 4)", false;
+  return device_extent_ok(ctx, what, p, 4, (n_rows - 1) * stride + row_bytes, std::to_string(n_rows) + " rows", why);
 }
 
 // everything the host can decide about one cvo_device_rows_t, before any launch

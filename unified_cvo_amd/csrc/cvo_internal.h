@@ -394,6 +394,7 @@ struct cvo_ctx {
   // RGB-D front end (cvo_rgbd.hip): one growable device region - image, depth, exclusion bytes, g2, thresholds, cell hits,
   // candidate pixels and their coordinates (the recipes use both regions at once)
   DeviceScratch rgbd_scratch;
+  DeviceScratch rgbd_rows;  // the rows k_rgbd_rows writes of a device frame's kept pixels, until the ingest has read them (sized by the points kept, not by the frame)
   std::vector<unsigned char> rgbd_excl;  // staging of the exclusion bytes of a semantic frame
   RgbdStatsAcc rgbd_last{};
   RgbdSelectionAcc rgbd_sel{};

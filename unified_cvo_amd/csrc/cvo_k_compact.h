@@ -10,7 +10,8 @@
 //   typename P::Item                         what keep() hands to write() of the same lane
 //   bool P::keep(int i, int n, Item*) const  false for i >= n
 //   void P::write(unsigned at, const Item&) const
-// The predicates: VoxelFirst (cvo_k_voxel.h), RgbdCellHit, RgbdKeep (cvo_k_rgbd.h), FastAbove (cvo_k_fast.h), StereoKeep
+// The predicates: VoxelFirst (cvo_k_voxel.h), RgbdCellHit, RgbdKeep (cvo_k_rgbd.h), RgbdKeepScores, RgbdHasDepth (count only;
+// cvo_k_rgbd_rows.h), FastAbove (cvo_k_fast.h), StereoKeep
 // (cvo_k_stereo.h), LidarTransition (count only; k_lidar_project ranks it inclusively), LidarSegKeep, LidarCand, LidarKept
 // (cvo_k_lidar.h).  A kernel that already knows its flag counts with compact_block_count itself (k_rgbd_select).
 // Part of the kernel set of cvo_kernels.h.

@@ -71,6 +71,7 @@
 #include "cvo_k_kd_wide.h"
 #include "cvo_k_voxel.h"
 #include "cvo_k_rgbd.h"
+#include "cvo_k_rgbd_rows.h"
 #include "cvo_k_fast.h"
 #include "cvo_k_stereo.h"
 #include "cvo_k_lidar.h"

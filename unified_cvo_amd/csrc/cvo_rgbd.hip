@@ -4,6 +4,9 @@
 // cvo_debug_rgbd_readback (the stages of the last selection on the device, for the tests).
 // On the device (kernels of cvo_k_rgbd.h on upload_stream, under upload_mutex) only pixels, depth and an exclusion byte
 // go up and only pixel indices come back; the survivors' rows are built on the host, as the voxel path does.
+// cvo_cloud_from_rgbd_device / _recipe: the same two clouds of a frame whose planes are ALREADY in device memory - the planes
+// read in place, the class rule in the keep predicate, the rows by k_rgbd_rows (cvo_k_rgbd_rows.h), the cloud by the ingest of
+// cvo_ingest.hip: no plane and no row crosses to the host.  cvo_rgbd_frame_rows_host: the CPU twin of that row arithmetic.
 // A SECTION of the one translation unit cvo_hip.hip; not compiled on its own.
 namespace {
 
@@ -64,30 +67,16 @@ int rgbd_threshold_range(int w, int h, std::string* msg) {
   return CVO_E_UNSUPPORTED;
 }
 
-// the plane the gradient is taken of: the caller's gray plane, a 1-channel image, or the BGR image (gray per access)
-struct GrayView {
-  const unsigned char* p;
-  int channels;
-};
+// the plane the gradient is taken of (GrayView, cvo_k_rgbd_rows.h): the caller's gray plane, a 1-channel image, or the BGR image
 GrayView gray_view(const cvo_rgbd_frame_t& f) { return f.gray ? GrayView{f.gray, 1} : GrayView{f.image, f.channels}; }
 
-// gradient_[j] of the interleaved (dx, dy) array (RawImage.cpp:55-82), computed where it is asked for
-float rgbd_gradient_at(const GrayView& g, int w, int h, size_t j) {
-  const size_t p = j >> 1;
-  const int x = (int)(p % w), y = (int)(p / w);
-  if (x < 1 || y < 1 || x > w - 2 || y > h - 2) return 0.f;
-  const size_t d = (j & 1) ? (size_t)w : 1;
-  return 0.5f * ((float)rgbd_gray(g.p, g.channels, p + d) - (float)rgbd_gray(g.p, g.channels, p - d));
+// a host frame's dense rows x cols x num_classes scores as the strided view the shared arithmetic reads
+RgbdScores rgbd_scores(const cvo_rgbd_frame_t& f) {
+  const size_t c = (size_t)std::max(f.num_classes, 0);
+  return RgbdScores{(const char*)f.semantic, sizeof(float) * c * (size_t)f.cols, sizeof(float) * c, sizeof(float), f.semantic ? f.num_classes : 0, f.cols};
 }
 
-bool rgbd_excluded(const cvo_rgbd_frame_t& f, size_t p) {  // first maximum is class 10 (CvoPointCloud.cpp:501-507)
-  if (f.num_classes <= 0) return false;
-  const float* row = f.semantic + p * (size_t)f.num_classes;
-  int best = 0;
-  for (int c = 1; c < f.num_classes; c++)
-    if (row[c] > row[best]) best = c;
-  return best == 10;
-}
+bool rgbd_excluded(const cvo_rgbd_frame_t& f, size_t p) { return rgbd_excluded(rgbd_scores(f), p); }
 
 // dso_select_pixels' schedule (CvoPixelSelector.cpp:430-453) over count(pot): returns the potential whose selection stands
 template <class Count>
@@ -185,52 +174,39 @@ void rgbd_candidates_cpu(const cvo_rgbd_frame_t& f, int method, std::vector<int>
 
 RgbdCalib rgbd_calib(const cvo_rgbd_frame_t& f) { return RgbdCalib{f.fx, f.fy, f.cx, f.cy, f.scaling_factor}; }
 
-void rgbd_xyz(const cvo_rgbd_frame_t& f, int p, float* xyz) {
-  float dep = 0.f;
-  (void)rgbd_depth(f.depth, f.depth_type, (size_t)p, &dep);
-  rgbd_backproject(rgbd_calib(f), p % f.cols, p / f.cols, dep, xyz);
+// a host frame as the shared row arithmetic (rgbd_xyz, rgbd_features, rgbd_recipe_row of cvo_k_rgbd_rows.h) reads it
+RgbdRowFrame rgbd_row_frame(const cvo_rgbd_frame_t& f, const GrayView& g) {
+  return RgbdRowFrame{f.cols, f.rows, f.channels, f.image, g, f.depth, f.depth_type, rgbd_calib(f), rgbd_scores(f)};
 }
 
-// the channels + 2 features of the image constructor (CvoPointCloud.cpp:527-545).  The reference reads the interleaved
-// gradient array at the PIXEL index (v w + u, v w + u + 1): reproduced.
-void rgbd_features(const cvo_rgbd_frame_t& f, const GrayView& g, int p, float* out) {
-  const int ch = f.channels;
-  for (int c = 0; c < ch; c++) out[c] = (float)((double)(float)f.image[(size_t)p * ch + c] / 255.0);
-  out[ch] = (float)((double)rgbd_gradient_at(g, f.cols, f.rows, (size_t)p) / 500.0 + 0.5);
-  out[ch + 1] = (float)((double)rgbd_gradient_at(g, f.cols, f.rows, (size_t)p + 1) / 500.0 + 0.5);
+void rgbd_xyz(const cvo_rgbd_frame_t& f, int p, float* xyz) { rgbd_xyz(rgbd_row_frame(f, gray_view(f)), p, xyz); }
+
+// the geometric type of the image constructor's points (CV_FAST: the stereo constructor's pure edges)
+RgbdRowKind rgbd_constructor_rows(int method) {
+  return RgbdRowKind{0, method == CVO_SELECT_FULL ? 0.5f : (method == CVO_SELECT_CV_FAST ? 1.f : 0.9f),
+                     method == CVO_SELECT_FULL ? 0.5f : (method == CVO_SELECT_CV_FAST ? 0.f : 0.1f)};
 }
 
 // the rows of the kept pixels that are asked for (a stereo frame comes as its stereo_view and has its xyz already)
 void rgbd_point_rows(const cvo_rgbd_frame_t& f, int method, const std::vector<int>& pix, float* xyz, float* feat, float* label, float* geotype) {
-  const GrayView g = gray_view(f);
+  const RgbdRowFrame rf = rgbd_row_frame(f, gray_view(f));
   const int F = f.channels + 2;
-  const float t0 = method == CVO_SELECT_FULL ? 0.5f : (method == CVO_SELECT_CV_FAST ? 1.f : 0.9f);  // (CV_FAST: the stereo constructor's pure edges)
-  const float t1 = method == CVO_SELECT_FULL ? 0.5f : (method == CVO_SELECT_CV_FAST ? 0.f : 0.1f);
+  const RgbdRowKind kind = rgbd_constructor_rows(method);
   for (size_t i = 0; i < pix.size(); i++) {
-    if (xyz) rgbd_xyz(f, pix[i], xyz + 3 * i);
-    if (feat) rgbd_features(f, g, pix[i], feat + F * i);
+    if (xyz) rgbd_xyz(rf, pix[i], xyz + 3 * i);
+    if (feat) rgbd_features(rf, pix[i], feat + F * i);
     if (label && f.num_classes > 0)
       std::memcpy(label + i * (size_t)f.num_classes, f.semantic + (size_t)pix[i] * f.num_classes, sizeof(float) * (size_t)f.num_classes);
     if (geotype) {
-      geotype[2 * i] = t0;
-      geotype[2 * i + 1] = t1;
+      geotype[2 * i] = kind.t0;
+      geotype[2 * i + 1] = kind.t1;
     }
   }
 }
 
-// a row of the drivers' recipe: the first three image-constructor features through export_to_pcd's bytes
-// (min(255, int(f * 255)), CvoPointCloud.cpp:1237-1239) and back through the (XYZRGB, GeometryType) constructor (:614-618)
+// a row of the drivers' recipe (rgbd_recipe_row of cvo_k_rgbd_rows.h) of a host frame
 void rgbd_recipe_row(const cvo_rgbd_frame_t& f, const GrayView& g, int p, bool edge, float* xyz, float* feat5, float* geo) {
-  float ft[5] = {};
-  rgbd_features(f, g, p, ft);
-  rgbd_xyz(f, p, xyz);
-  for (int c = 0; c < 3; c++) {
-    const int byte = std::min(255, (int)(ft[c] * 255));
-    feat5[c] = (float)((double)(float)byte / 255.0);
-  }
-  feat5[3] = feat5[4] = 0.f;
-  geo[0] = edge ? 1.f : 0.f;
-  geo[1] = edge ? 0.f : 1.f;
+  rgbd_recipe_row(rgbd_row_frame(f, g), p, edge, xyz, feat5, geo);
 }
 
 // ---- device route --------------------------------------------------------------------------------------------------------
@@ -252,8 +228,10 @@ struct RgbdDevice {
 };
 
 // lays the frame's buffers out in the context's RGB-D scratch region and copies image, depth and exclusion bytes up
-// (need_fast: room for the FAST detector's score bytes and histogram as well; a frame without a depth image copies none)
-int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select, RgbdDevice& d, bool need_fast = false) {
+// (need_fast: room for the FAST detector's score bytes and histogram as well; a frame without a depth image copies none).
+// planes_on_device: f.image / gray / depth are the CALLER'S device memory (a checked cvo_rgbd_device_frame_t): the kernels
+// read them where they are - nothing is copied, no room is taken for them, and there is no exclusion plane (RgbdKeepScores).
+int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select, RgbdDevice& d, bool need_fast = false, bool planes_on_device = false) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->rgbd_sel.valid = false;  // (the region is about to be laid out anew: the last selection's stages end here)
   const int w = f.cols, h = f.rows;
@@ -269,16 +247,17 @@ int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select,
   d.nb_cells = d.n_cells / RGBD_THREADS;
   const GrayView g = gray_view(f);
   d.img_channels = g.channels;
-  const size_t img_bytes = np * (size_t)g.channels, depth_bytes = f.depth ? np * (f.depth_type == CVO_DEPTH_U16 ? 2 : 4) : 0;
+  const size_t img_bytes = planes_on_device ? 0 : np * (size_t)g.channels;
+  const size_t depth_bytes = f.depth && !planes_on_device ? np * (f.depth_type == CVO_DEPTH_U16 ? 2 : 4) : 0;
   const size_t n_ths = (size_t)(w / 32) * (h / 32) + RGBD_THS_SLACK, nb = std::max((np + RGBD_THREADS - 1) / RGBD_THREADS, (size_t)d.nb_cells);
   size_t cap = 0;  // candidates of both sets: every pixel (FULL) + the largest selection
   for (int k = 0; k < RGBD_POTS; k++) cap = std::max(cap, (size_t)rgbd_cells(RGBD_POT_MIN + k, w, h));
   cap += np;
   const int rc = ctx->rgbd_scratch.lay_out(ctx, "RGB-D scratch", [&](ScratchLayout& l) {
-    l.take(d.ctl, 1);
+    l.take(d.ctl, 2);  // (the compaction's total; the pixels with a depth of a device frame with classes)
     l.take(d.img, need_select ? img_bytes : 0);
     l.take_as<char>(d.depth, depth_bytes);
-    if (f.num_classes > 0) l.take(d.excl, np);
+    if (f.num_classes > 0 && !planes_on_device) l.take(d.excl, np);
     l.take(d.g2, need_select ? np : 0);
     l.take(d.ths, 2 * n_ths);  // (thresholds, then their smoothed copy)
     d.sm = d.ths + n_ths;
@@ -292,6 +271,11 @@ int rgbd_device_stage(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, bool need_select,
     l.take(d.fast_hist, need_fast ? (size_t)FAST_BINS : 0);
   });
   if (rc != CVO_OK) return rc;
+  if (planes_on_device) {  // (only ever read: the kernels take them as pointers to const)
+    d.img = const_cast<unsigned char*>(g.p);
+    d.depth = const_cast<void*>(f.depth);
+    return CVO_OK;
+  }
   hipStream_t st = ctx->upload_stream;
   if (need_select) HIP_TRY(ctx, hipMemcpyAsync(d.img, g.p, img_bytes, hipMemcpyHostToDevice, st));
   if (depth_bytes) HIP_TRY(ctx, hipMemcpyAsync(d.depth, f.depth, depth_bytes, hipMemcpyHostToDevice, st));
@@ -361,6 +345,36 @@ int frame_device_backproject(cvo_ctx* ctx, const char* who, RgbdDevice& d, P pre
   return CVO_OK;
 }
 
+// A device frame's back-projection: the class scores' rule in keep() (RgbdKeepScores) where the frame has classes, RgbdKeep
+// as it is where it has none.  with_depth (optional): the pixels of the whole frame with a depth, counted by the ordered
+// compaction's count and scan (RgbdHasDepth) ahead of the pass and read back with its total: still one synchronisation.
+int rgbd_device_backproject_scores(cvo_ctx* ctx, const cvo_rgbd_frame_t& view, const RgbdScores& scores, RgbdDevice& d, const int* list, int n, int at,
+                                   int* n_out, unsigned long long* with_depth) {
+  const char* who = "RGB-D back-projection";
+  RgbdKeep keep{list, d.w, d.h, d.depth, view.depth_type, nullptr, rgbd_calib(view), d.pix + at, d.xyz + 3 * (size_t)at};
+  *n_out = 0;
+  if (n == 0) return CVO_OK;
+  hipStream_t st = ctx->upload_stream;
+  if (with_depth) {
+    const int np = d.w * d.h;
+    const RgbdHasDepth has{d.depth, view.depth_type};
+    hipLaunchKernelGGL(k_compact_count<RgbdHasDepth>, dim3((np + COMPACT_THREADS - 1) / COMPACT_THREADS), dim3(COMPACT_THREADS), 0, st, np, has, d.blocks);
+    scan_into(ctx, d.ctl + 1)((np + COMPACT_THREADS - 1) / COMPACT_THREADS, d.blocks);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  int rc = scores.classes > 0 ? compact(ctx, n, RgbdKeepScores{keep, scores}, d.blocks, scan_into(ctx, d.ctl))
+                              : compact(ctx, n, keep, d.blocks, scan_into(ctx, d.ctl));
+  if (rc != CVO_OK) return rc;
+  unsigned c[2] = {0u, 0u};
+  HIP_TRY(ctx, hipMemcpyAsync(c, d.ctl, sizeof(unsigned) * (with_depth ? 2 : 1), hipMemcpyDeviceToHost, st));
+  HIP_TRY(ctx, hipStreamSynchronize(st));
+  if ((rc = compact_check(ctx, c[0], n, who, "pixels")) != CVO_OK) return rc;
+  if (with_depth && (rc = compact_check(ctx, c[1], d.w * d.h, who, "pixels with a depth")) != CVO_OK) return rc;
+  *n_out = (int)c[0];
+  if (with_depth) *with_depth = c[1];
+  return CVO_OK;
+}
+
 int rgbd_device_backproject(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, RgbdDevice& d, const int* list, int n, int at, int* n_out) {
   return frame_device_backproject(ctx, "RGB-D back-projection", d, RgbdKeep{list, d.w, d.h, d.depth, f.depth_type, d.excl, rgbd_calib(f), nullptr, nullptr},
                                   n, at, n_out);
@@ -402,6 +416,32 @@ int rgbd_points_device(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, int method, std:
 
 bool rgbd_on_host(const cvo_ctx* ctx, const cvo_rgbd_frame_t& f) { return route_on_host(ctx->opt.rgbd_host, (long long)f.cols * f.rows, RGBD_HOST_BELOW); }
 
+// The device route of the recipe below, up to where the survivors' pixel indices are in d.out (*total of them, the first
+// *n_edge the edges): staging (planes_on_device: of a device frame, rgbd_device_stage), device_pass, the two voxel selections.
+template <class DevicePass>
+int recipe_pixels_device(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t& view, bool planes_on_device, float leaf, float s_edge, RgbdDevice& d,
+                         int* n_edge, int* total, DevicePass device_pass) {
+  *total = 0;
+  int rc = rgbd_device_stage(ctx, view, true, d, false, planes_on_device);
+  if (rc != CVO_OK) return rc;
+  int n_e = 0, n_s = 0;
+  if ((rc = device_pass(d, &n_e, &n_s)) != CVO_OK) return rc;
+  for (int pass = 0; pass < 2; pass++) {
+    const int n = pass == 0 ? n_e : n_s, at = pass == 0 ? 0 : n_e;
+    if (n == 0) continue;
+    const int* d_kept = nullptr;
+    rc = voxel_run_device(ctx, n, nullptr, d.xyz + 3 * (size_t)at, pass == 0 ? s_edge : leaf, nullptr, &d_kept);
+    if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + ctx->err);
+    const int nk = (int)ctx->vox_last.n_kept;
+    hipLaunchKernelGGL(k_rgbd_gather, dim3((nk + RGBD_THREADS - 1) / RGBD_THREADS), dim3(RGBD_THREADS), 0, ctx->upload_stream, nk, n, d_kept,
+                       (const int*)(d.pix + at), d.out + *total);
+    HIP_TRY(ctx, hipGetLastError());
+    *total += nk;
+    if (pass == 0) *n_edge = nk;
+  }
+  return CVO_OK;
+}
+
 // The drivers' per-frame recipe for either frame type: both candidate sets - edges, then FULL - through the voxel grid
 // (leaf / divisor for the edges); pixel indices of the survivors, edge first, n_edge of them edges, and - xyz != nullptr, host
 // route only - their coordinates.  `view`: the frame as rgbd_device_stage reads it.
@@ -432,24 +472,9 @@ int recipe_pixels(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t& view, b
     return CVO_OK;
   }
   RgbdDevice d;
-  int rc = rgbd_device_stage(ctx, view, true, d);
-  if (rc != CVO_OK) return rc;
-  int n_e = 0, n_s = 0;
-  if ((rc = device_pass(d, &n_e, &n_s)) != CVO_OK) return rc;
   int total = 0;
-  for (int pass = 0; pass < 2; pass++) {
-    const int n = pass == 0 ? n_e : n_s, at = pass == 0 ? 0 : n_e;
-    if (n == 0) continue;
-    const int* d_kept = nullptr;
-    rc = voxel_run_device(ctx, n, nullptr, d.xyz + 3 * (size_t)at, pass == 0 ? s_edge : leaf, nullptr, &d_kept);
-    if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + ctx->err);
-    const int nk = (int)ctx->vox_last.n_kept;
-    hipLaunchKernelGGL(k_rgbd_gather, dim3((nk + RGBD_THREADS - 1) / RGBD_THREADS), dim3(RGBD_THREADS), 0, ctx->upload_stream, nk, n, d_kept,
-                       (const int*)(d.pix + at), d.out + total);
-    HIP_TRY(ctx, hipGetLastError());
-    total += nk;
-    if (pass == 0) *n_edge = nk;
-  }
+  const int rc = recipe_pixels_device(ctx, who, view, false, leaf, s_edge, d, n_edge, &total, device_pass);
+  if (rc != CVO_OK) return rc;
   return rgbd_fetch(ctx, d.out, total, pix);
 }
 
@@ -512,6 +537,200 @@ int rgbd_points_entry(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t* fra
   });
 }
 
+// ---- frames whose planes are already in device memory (cvo_rgbd_device_frame_t) ---------------------------------------------
+// The planes are read IN PLACE: the selection, the back-projection and k_rgbd_rows take the caller's pointers, nothing is
+// copied into the scratch region (the call synchronises before it returns, so the planes need not outlive it).  RGBD_HOST does
+// not apply.  The same struct with HOST pointers is what the twin cvo_rgbd_frame_rows_host reads.
+
+// the frame as the selection and the stage read it: the planes' pointers; the class scores go their own way (RgbdScores)
+cvo_rgbd_frame_t rgbd_device_view(const cvo_rgbd_device_frame_t& f) {
+  cvo_rgbd_frame_t v{};
+  v.rows = f.rows;
+  v.cols = f.cols;
+  v.channels = f.channels;
+  v.image = (const uint8_t*)f.image;
+  v.gray = (const uint8_t*)f.gray;
+  v.depth = f.depth;
+  v.depth_type = f.depth_type;
+  v.fx = f.fx;
+  v.fy = f.fy;
+  v.cx = f.cx;
+  v.cy = f.cy;
+  v.scaling_factor = f.scaling_factor;
+  return v;
+}
+
+RgbdScores rgbd_device_scores(const cvo_rgbd_device_frame_t& f) {
+  if (f.num_classes <= 0) return RgbdScores{nullptr, 0, 0, 0, 0, f.cols};
+  return RgbdScores{(const char*)f.semantic, f.semantic_row_stride, f.semantic_pixel_stride, f.semantic_class_stride, f.num_classes, f.cols};
+}
+
+RgbdRowFrame rgbd_device_row_frame(const cvo_rgbd_device_frame_t& f) {
+  const cvo_rgbd_frame_t v = rgbd_device_view(f);
+  RgbdRowFrame rf = rgbd_row_frame(v, gray_view(v));
+  rf.scores = rgbd_device_scores(f);
+  return rf;
+}
+
+// what the host can say of a device frame's FIELDS without classifying a pointer: cvo_rgbd_points' refusals in its words, then
+// the class count and the strides
+int rgbd_device_fields(const cvo_rgbd_device_frame_t* f, std::string* msg) {
+  if (!f) {
+    *msg = "frame is NULL";
+    return CVO_E_INVALID;
+  }
+  cvo_rgbd_frame_t v = rgbd_device_view(*f);
+  v.num_classes = f->num_classes;
+  v.semantic = (const float*)f->semantic;
+  const int rc = rgbd_validate(&v, msg);
+  if (rc != CVO_OK) return rc;
+  if (f->num_classes > NC) {
+    *msg = "num_classes " + std::to_string(f->num_classes) + ": a resident cloud holds " + std::to_string(NC) + " class columns";
+    return CVO_E_UNSUPPORTED;
+  }
+  const size_t stride[3] = {f->semantic_row_stride, f->semantic_pixel_stride, f->semantic_class_stride};
+  const char* name[3] = {"semantic_row_stride", "semantic_pixel_stride", "semantic_class_stride"};
+  for (int k = 0; f->num_classes > 0 && k < 3; k++)
+    if (stride[k] == 0 || (stride[k] & 3u) != 0 || stride[k] > 0xffffffffull) {
+      *msg = std::string(name[k]) + ": a stride of " + std::to_string(stride[k]) + " bytes (strides are > 0 and multiples of 4)";
+      return CVO_E_INVALID;
+    }
+  return CVO_OK;
+}
+
+// every plane classified (device_extent_ok, cvo_ingest.hip) before anything reads through it; the caller holds upload_mutex
+int rgbd_device_planes(cvo_ctx* ctx, const cvo_rgbd_device_frame_t& f, std::string* why) {
+  const size_t np = (size_t)f.rows * f.cols, depth_size = f.depth_type == CVO_DEPTH_U16 ? 2 : 4;
+  const std::string shape = std::to_string(f.rows) + " x " + std::to_string(f.cols);
+  if (!device_extent_ok(ctx, "image", f.image, 1, np * (size_t)f.channels, shape + " x " + std::to_string(f.channels) + " bytes", why)) return CVO_E_INVALID;
+  if (f.gray && !device_extent_ok(ctx, "gray", f.gray, 1, np, shape + " bytes", why)) return CVO_E_INVALID;
+  if (!device_extent_ok(ctx, "depth", f.depth, depth_size, np * depth_size, shape + (depth_size == 2 ? " uint16 depths" : " float depths"), why)) return CVO_E_INVALID;
+  if (f.num_classes > 0) {
+    const size_t need = (size_t)(f.rows - 1) * f.semantic_row_stride + (size_t)(f.cols - 1) * f.semantic_pixel_stride +
+                        (size_t)(f.num_classes - 1) * f.semantic_class_stride + sizeof(float);
+    if (!device_extent_ok(ctx, "semantic", f.semantic, 4, need, shape + " x " + std::to_string(f.num_classes) + " strided scores", why)) return CVO_E_INVALID;
+  }
+  return CVO_OK;
+}
+
+// the rows of the pixels d_pix[0 .. n) (the first n_edge a recipe's edges) by k_rgbd_rows, where k_cloud_ingest reads them, and
+// the ingest; the pixel list comes down only when the caller asked for it, ahead of the ingest's synchronisation.  staged: the cloud.
+int rgbd_device_cloud(cvo_ctx* ctx, const char* who, const RgbdRowFrame& rf, const RgbdRowKind& kind, const int* d_pix, int n, int n_edge, int* pixel,
+                      std::vector<StagedCloud>& staged) {
+  hipStream_t st = ctx->upload_stream;
+  RgbdRowsOut o{};
+  const bool labels = rf.scores.classes > 0 && !kind.recipe;  // (a recipe's cloud carries none, as cvo_cloud_upload_rgbd's)
+  if (n > 0) {
+    const size_t nn = (size_t)n;
+    const int rc = ctx->rgbd_rows.lay_out(ctx, "RGB-D rows", [&](ScratchLayout& l) {
+      l.take(o.xyz, 3 * nn);
+      l.take(o.feat, FD * nn);
+      if (labels) l.take(o.label, NC * nn);
+      l.take(o.geo, 2 * nn);
+    });
+    if (rc != CVO_OK) return rc;
+    hipLaunchKernelGGL(k_rgbd_rows, dim3((unsigned)((n + RGBD_ROW_THREADS - 1) / RGBD_ROW_THREADS)), dim3(RGBD_ROW_THREADS), 0, st, n, n_edge, d_pix, rf, kind, o);
+    HIP_TRY(ctx, hipGetLastError());
+    if (pixel) HIP_TRY(ctx, hipMemcpyAsync(pixel, d_pix, sizeof(int) * nn, hipMemcpyDeviceToHost, st));
+  }
+  cvo_device_rows_t r{};
+  r.n = r.n_records = n;
+  r.xyz = o.xyz;
+  r.xyz_stride = 12;
+  r.feat = o.feat;
+  r.feat_stride = sizeof(float) * FD;
+  r.label = o.label;
+  r.label_stride = sizeof(float) * NC;
+  r.geotype = o.geo;
+  r.geotype_stride = 8;
+  const int rc = ingest_device_clouds(ctx, 1, &r, staged, who);  // (synchronises upload_stream; on error the cloud is released)
+  if (rc != CVO_OK || n == 0) (void)hipStreamSynchronize(st);     // (nothing of this call is in flight when it returns)
+  return rc;
+}
+
+// the arguments every device-frame entry point refuses before it takes the lock
+int rgbd_device_check(const cvo_rgbd_device_frame_t* frame, int method, bool select, std::string* msg) {
+  int rc = rgbd_device_fields(frame, msg);
+  if (rc == CVO_OK) rc = rgbd_method(method, msg);
+  if (rc == CVO_OK && select) rc = rgbd_threshold_range(frame->cols, frame->rows, msg);
+  return rc;
+}
+
+int rgbd_from_device_points(cvo_ctx* ctx, const char* who, const cvo_rgbd_device_frame_t& f, int method, int* pixel, int* n_out,
+                            std::vector<StagedCloud>& staged) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::string why;
+  if (rgbd_device_planes(ctx, f, &why) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": " + why);
+  const cvo_rgbd_frame_t view = rgbd_device_view(f);
+  const RgbdRowFrame rf = rgbd_device_row_frame(f);
+  RgbdStatsAcc st;
+  st.on_device = 1;
+  RgbdDevice d;
+  int rc = rgbd_device_stage(ctx, view, method == CVO_SELECT_DSO_EDGES, d, false, true);
+  if (rc != CVO_OK) return rc;
+  const int* list = nullptr;
+  int n = f.cols * f.rows, kept = 0;
+  if (method == CVO_SELECT_DSO_EDGES && (rc = rgbd_device_select(ctx, d, st, &list, &n)) != CVO_OK) return rc;
+  unsigned long long with_depth = 0;
+  const bool count = method == CVO_SELECT_FULL && f.num_classes > 0;
+  if ((rc = rgbd_device_backproject_scores(ctx, view, rf.scores, d, list, n, 0, &kept, count ? &with_depth : nullptr)) != CVO_OK) return rc;
+  if (method == CVO_SELECT_FULL) {
+    st.surface_points = (unsigned long long)kept;
+    st.with_depth = count ? with_depth : (unsigned long long)kept;
+  } else {
+    st.edge_points = (unsigned long long)kept;
+  }
+  if ((rc = rgbd_device_cloud(ctx, who, rf, rgbd_constructor_rows(method), d.pix, kept, 0, pixel, staged)) != CVO_OK) return rc;
+  if (n_out) *n_out = kept;
+  rgbd_commit(ctx, st);
+  return CVO_OK;
+}
+
+int rgbd_from_device_recipe(cvo_ctx* ctx, const char* who, const cvo_rgbd_device_frame_t& f, float leaf, float divisor, int* pixel, int* n_out,
+                            int* n_edge_out, std::vector<StagedCloud>& staged) {
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::string why;
+  if (rgbd_device_planes(ctx, f, &why) != CVO_OK) return fail(ctx, CVO_E_INVALID, std::string(who) + ": " + why);
+  const cvo_rgbd_frame_t view = rgbd_device_view(f);
+  const RgbdRowFrame rf = rgbd_device_row_frame(f);
+  RgbdStatsAcc st;
+  st.on_device = 1;
+  RgbdDevice d;
+  int n_edge = 0, total = 0;
+  int rc = recipe_pixels_device(ctx, who, view, true, leaf, leaf / divisor, d, &n_edge, &total, [&](RgbdDevice& dd, int* n_e, int* n_s) {
+    const int* list = nullptr;
+    int n_sel = 0, rc2;
+    unsigned long long with_depth = 0;
+    const bool count = f.num_classes > 0;
+    if ((rc2 = rgbd_device_select(ctx, dd, st, &list, &n_sel)) != CVO_OK) return rc2;
+    if ((rc2 = rgbd_device_backproject_scores(ctx, view, rf.scores, dd, list, n_sel, 0, n_e, nullptr)) != CVO_OK) return rc2;
+    if ((rc2 = rgbd_device_backproject_scores(ctx, view, rf.scores, dd, nullptr, f.cols * f.rows, *n_e, n_s, count ? &with_depth : nullptr)) != CVO_OK)
+      return rc2;
+    st.edge_points = (unsigned long long)*n_e;
+    st.surface_points = (unsigned long long)*n_s;
+    st.with_depth = count ? with_depth : (unsigned long long)*n_s;
+    return (int)CVO_OK;
+  });
+  if (rc != CVO_OK) return rc;
+  if ((rc = rgbd_device_cloud(ctx, who, rf, RgbdRowKind{1, 0.f, 0.f}, d.out, total, n_edge, pixel, staged)) != CVO_OK) return rc;
+  if (n_out) *n_out = total;
+  if (n_edge_out) *n_edge_out = n_edge;
+  rgbd_commit(ctx, st);
+  return CVO_OK;
+}
+
+// the frame of both entry points: *out NULL unless the call succeeds
+template <class Body>
+int rgbd_from_device_call(cvo_ctx* ctx, const char* who, cvo_cloud** out, Body body) {
+  std::vector<StagedCloud> staged;
+  const int rc = frontend_call(ctx, who, [&] { return body(staged); });
+  for (auto& sc : staged) {
+    if (rc == CVO_OK) *out = sc.c;
+    else if (sc.c) cvo_cloud_free(sc.c);  // (an exception left it behind; an error return released it itself)
+  }
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -560,6 +779,80 @@ int cvo_cloud_upload_rgbd(cvo_ctx* ctx, const cvo_rgbd_frame_t* frame, float lea
     rgbd_commit(ctx, st);
     return CVO_OK;
   });
+}
+
+int cvo_cloud_from_rgbd_device(cvo_ctx* ctx, const cvo_rgbd_device_frame_t* frame, int method, cvo_cloud** out, int* n, int* pixel) {
+  const char* who = "cvo_cloud_from_rgbd_device";
+  if (out) *out = nullptr;
+  if (n) *n = 0;
+  if (!ctx) return CVO_E_INVALID;
+  std::string msg;
+  int rc = rgbd_device_check(frame, method, method == CVO_SELECT_DSO_EDGES, &msg);
+  if (rc == CVO_OK && !out) {
+    rc = CVO_E_INVALID;
+    msg = "out is NULL";
+  }
+  if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
+  return rgbd_from_device_call(ctx, who, out, [&](std::vector<StagedCloud>& staged) { return rgbd_from_device_points(ctx, who, *frame, method, pixel, n, staged); });
+}
+
+int cvo_cloud_from_rgbd_device_recipe(cvo_ctx* ctx, const cvo_rgbd_device_frame_t* frame, float leaf, float edge_divisor, cvo_cloud** out, int* n,
+                                      int* n_edge, int* pixel) {
+  const char* who = "cvo_cloud_from_rgbd_device_recipe";
+  if (out) *out = nullptr;
+  if (n) *n = 0;
+  if (n_edge) *n_edge = 0;
+  if (!ctx) return CVO_E_INVALID;
+  std::string msg;
+  int rc = rgbd_device_check(frame, CVO_SELECT_DSO_EDGES, true, &msg);
+  if (rc == CVO_OK && !out) {
+    rc = CVO_E_INVALID;
+    msg = "out is NULL";
+  }
+  if (rc == CVO_OK && voxel_validate(0, nullptr, leaf, &msg) != CVO_OK) {
+    rc = CVO_E_INVALID;
+    msg = "leaf: " + msg;
+  }
+  if (rc == CVO_OK && (!std::isfinite(edge_divisor) || !(edge_divisor > 0.f))) {
+    rc = CVO_E_INVALID;
+    msg = "edge_divisor must be finite and > 0, got " + std::to_string(edge_divisor);
+  }
+  if (rc == CVO_OK && voxel_validate(0, nullptr, leaf / edge_divisor, &msg) != CVO_OK) {
+    rc = CVO_E_INVALID;
+    msg = "leaf / edge_divisor: " + msg;
+  }
+  if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
+  return rgbd_from_device_call(ctx, who, out, [&](std::vector<StagedCloud>& staged) {
+    return rgbd_from_device_recipe(ctx, who, *frame, leaf, edge_divisor, pixel, n, n_edge, staged);
+  });
+}
+
+int cvo_rgbd_frame_rows_host(const cvo_rgbd_device_frame_t* frame, int recipe, int method, int n, const int* pixel, const unsigned char* is_edge,
+                             float* xyz, float* feat, float* label, float* geotype, unsigned char* excluded) {
+  std::string msg;
+  int rc = rgbd_device_fields(frame, &msg);
+  if (rc == CVO_OK && !recipe) rc = rgbd_method(method, &msg);
+  if (rc != CVO_OK) return rc;
+  if (n < 0 || (n > 0 && !pixel) || (n > 0 && recipe && !is_edge)) return CVO_E_INVALID;
+  const int np = frame->rows * frame->cols;
+  for (int i = 0; i < n; i++)
+    if ((unsigned)pixel[i] >= (unsigned)np) return CVO_E_INVALID;
+  const RgbdRowFrame rf = rgbd_device_row_frame(*frame);
+  const RgbdRowKind kind = recipe ? RgbdRowKind{1, 0.f, 0.f} : rgbd_constructor_rows(method);
+  for (int i = 0; i < n; i++) {
+    const int p = pixel[i];
+    float row_xyz[3], row_feat[FD], row_geo[2];
+    rgbd_row5(rf, kind, p, recipe && is_edge[i] != 0, row_xyz, row_feat, row_geo);
+    if (xyz) std::memcpy(xyz + 3 * (size_t)i, row_xyz, sizeof row_xyz);
+    if (feat) std::memcpy(feat + (size_t)FD * i, row_feat, sizeof row_feat);
+    if (geotype) std::memcpy(geotype + 2 * (size_t)i, row_geo, sizeof row_geo);
+    if (label) {
+      const char* at = rf.scores.classes > 0 ? rgbd_scores_at(rf.scores, (size_t)p) : nullptr;
+      for (int c = 0; c < NC; c++) label[(size_t)NC * i + c] = c < rf.scores.classes ? rgbd_score(at, rf.scores, c) : 0.f;
+    }
+    if (excluded) excluded[i] = rgbd_excluded(rf.scores, (size_t)p) ? 1 : 0;
+  }
+  return CVO_OK;
 }
 
 int cvo_debug_rgbd_stats(cvo_ctx* ctx, int* n_tried, int* potentials, int* counts, unsigned long long* edge_selected,
