@@ -378,7 +378,7 @@ int bki_rows_device(cvo_map* m, bool want_rows, int label_stride, cvo_device_row
   d->n = d->n_records = (int)n;
   if (!want_rows) return CVO_OK;  // (counted only: no row is laid out, *d names none)
   float *feat = xyz + 3 * (size_t)n, *label = feat + BKI_FEAT * (size_t)n;
-  *d = cvo_device_rows_t{(int)n, (int)n, xyz, 12, feat, sizeof(float) * BKI_FEAT, m->k.C > 0 ? label : nullptr, sizeof(float) * label_stride, nullptr, 0, nullptr};
+  *d = device_rows((int)n, (int)n, xyz, feat, BKI_FEAT, m->k.C > 0 ? label : nullptr, (size_t)label_stride, nullptr);  // (no geotype: absent)
   if (!n) return CVO_OK;
   hipLaunchKernelGGL(k_bki_rows, dim3(bki_blocks(n)), dim3(BKI_THREADS), 0, ctx->upload_stream, m->k, m->dev.t, n, okey, oslot, xyz, feat, label,
                      label_stride, label_stride);
@@ -875,23 +875,17 @@ int cvo_map_cloud_resident(cvo_map* m, cvo_cloud** out, long long* n) {
   cvo_ctx* ctx = m->ctx;
   if (!out) return fail(ctx, CVO_E_INVALID, std::string(who) + ": a required pointer is missing");
   if (m->broken) return fail(ctx, CVO_E_HIP, std::string(who) + ": " + BKI_SAYS_BROKEN);
-  std::vector<StagedCloud> staged;
   long long rows_n = 0;
-  const int rc = frontend_call(ctx, who, [&] {
+  const int rc = handover_call(ctx, who, out, [&](std::vector<StagedCloud>& staged) {
     if (m->side == 0) return bki_cloud_resident_device(m, who, staged, &rows_n);
-    // a map of the host side (or without an insert): the twin's rows, uploaded
+    // a map of the host side (or without an insert): the twin's rows, uploaded (the upload writes its cloud only when it succeeds)
     BkiRows rows;
-    int r = bki_rows(m, true, &rows);
+    const int r = bki_rows(m, true, &rows);
     if (r != CVO_OK) return r;
-    staged.resize(1);
-    if ((r = bki_upload_rows(ctx, m->k.C, rows, &staged[0].c)) != CVO_OK) return staged[0].c = nullptr, r;
     rows_n = rows.n;
-    return (int)CVO_OK;
+    staged.resize(1);
+    return bki_upload_rows(ctx, m->k.C, rows, &staged[0].c);
   });
-  for (auto& sc : staged) {
-    if (rc == CVO_OK) *out = sc.c;
-    else if (sc.c) cvo_cloud_free(sc.c);  // (an exception left it behind; an error return released it itself)
-  }
   if (rc == CVO_OK && n) *n = rows_n;
   return rc;
 }

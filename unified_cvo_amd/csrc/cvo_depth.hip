@@ -45,11 +45,8 @@ auto depth_region_list(cvo_depth_filter_t& f) {
   return [&f](ScratchLayout& l) {
     const size_t nn = (size_t)std::max(f.n, 1);
     l.take(f.d_job, 1);
-    l.take(f.xyz, 3 * nn);
+    unpacked_rows_list(l, f.present, nn, f.xyz, f.feat, f.label, f.geo);
     l.take(f.xyz_out, 3 * nn);
-    if (f.present & HAS_FEAT) l.take(f.feat, FD_PAD / 4 * nn);
-    if (f.present & HAS_LABEL) l.take(f.label, NC_PAD / 4 * nn);
-    if (f.present & HAS_GEOTYPE) l.take(f.geo, nn);
     l.take(f.depth_sum, nn);
     l.take(f.weight_sum, nn);
     l.take(f.count, nn);
@@ -65,23 +62,11 @@ auto depth_region_list(cvo_depth_filter_t& f) {
 
 // the filter's rows as ingest rows: `xyz` is either copy of the coordinates
 cvo_device_rows_t depth_rows(const cvo_depth_filter_t& f, const float* xyz, int n, const int* rows) {
-  cvo_device_rows_t d{};
-  d.n = n;
-  d.n_records = f.n;
-  d.xyz = xyz;
-  d.xyz_stride = 12;
-  d.feat = f.feat;
-  d.feat_stride = sizeof(float) * FD_PAD;
-  d.label = f.label;
-  d.label_stride = sizeof(float) * NC_PAD;
-  d.geotype = f.geo;
-  d.geotype_stride = 8;
-  d.rows = rows;
-  return d;
+  return device_rows(n, f.n, xyz, f.feat, FD_PAD, f.label, NC_PAD, f.geo, rows);
 }
 
-// the body of cvo_depth_filter_open under upload_mutex
-int depth_open_locked(cvo_ctx* ctx, const cvo_cloud* keyframe, cvo_depth_filter_t& f) {
+// the body of cvo_depth_filter_open under upload_mutex; staged: the filter's resident keyframe (none of an empty one), or what to release
+int depth_open_locked(cvo_ctx* ctx, const cvo_cloud* keyframe, cvo_depth_filter_t& f, std::vector<StagedCloud>& staged) {
   const char* who = "cvo_depth_filter_open";
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   f.ctx = ctx;
@@ -91,24 +76,8 @@ int depth_open_locked(cvo_ctx* ctx, const cvo_cloud* keyframe, cvo_depth_filter_
   int rc = f.region.lay_out(ctx, "depth filter", depth_region_list(f), nullptr);
   if (rc != CVO_OK) return rc;
   const hipStream_t st = ctx->upload_stream;
-  UnpackJob j{};
-  j.n = f.n;
-  j.x4 = keyframe->x4;
-  j.inv = keyframe->inv;
-  j.feat = held(keyframe, keyframe->feat);
-  j.label = held(keyframe, keyframe->label);
-  j.geo = held(keyframe, keyframe->geo);
-  UnpackOut o{};
-  o.n_jobs = 1;
-  o.total = f.n;
-  o.xyz = f.xyz;
-  o.feat = f.feat;
-  o.label = f.label;
-  o.geo = f.geo;
-  HIP_TRY(ctx, hipMemcpyAsync(f.d_job, &j, sizeof j, hipMemcpyHostToDevice, st));  // (j lives until the synchronisation below)
-  const int grid = std::min((f.n + UNPACK_THREADS - 1) / UNPACK_THREADS, UNPACK_MAX_BLOCKS);
-  hipLaunchKernelGGL(k_cloud_unpack, dim3((unsigned)grid), dim3(UNPACK_THREADS), 0, st, (const UnpackJob*)f.d_job, o);
-  HIP_TRY(ctx, hipGetLastError());
+  std::vector<UnpackJob> jobs;  // (alive until the synchronisation below)
+  if ((rc = unpack_launch(ctx, 1, &keyframe, nullptr, jobs, f.d_job, UnpackOut{1, f.n, f.xyz, f.feat, f.label, f.geo})) != CVO_OK) return rc;
   const size_t nn = (size_t)f.n;
   HIP_TRY(ctx, hipMemsetAsync(f.depth_sum, 0, sizeof(float) * nn, st));
   HIP_TRY(ctx, hipMemsetAsync(f.weight_sum, 0, sizeof(float) * nn, st));
@@ -116,32 +85,9 @@ int depth_open_locked(cvo_ctx* ctx, const cvo_cloud* keyframe, cvo_depth_filter_
   HIP_TRY(ctx, hipMemsetAsync(f.bad, 0, sizeof(unsigned), st));
   // the filter's own resident keyframe, from the rows where they are
   const cvo_device_rows_t d = depth_rows(f, f.xyz, f.n, nullptr);
-  std::vector<StagedCloud> staged;
   rc = ingest_device_clouds(ctx, 1, &d, staged, who);  // (synchronises upload_stream; on error the cloud is released)
-  if (rc != CVO_OK) {
-    (void)hipStreamSynchronize(st);
-    return rc;
-  }
-  f.kf = staged[0].c;
-  return CVO_OK;
-}
-
-// kernel_inv (row-major) and the squared cull radius, as cvo_association_non_isotropic builds them (cvo_export.hip)
-void depth_kernel_extra(const cvo_params_t* params, const float kernel_colmajor[9], float extra[10]) {
-  float km[9];
-  for (int i = 0; i < 3; i++)
-    for (int j = 0; j < 3; j++) km[3 * i + j] = kernel_colmajor[3 * j + i];
-  inverse3_eigen(km, extra);
-  const double sigma2 = (double)params->sigma * params->sigma;
-  const double cmax = params->is_using_intensity ? (double)params->c_sigma * params->c_sigma : 1.0;
-  const double smax = params->is_using_semantics ? (double)params->s_sigma * params->s_sigma : 1.0;
-  const double d2m = -2.0 * std::log((double)params->sp_thres / (sigma2 * cmax * smax));
-  const double lam = min_eig_sym3(extra);
-  double cull = INFINITY;
-  if (params->is_using_geometry && std::isfinite(d2m) && std::isfinite(lam) && lam > 0.0)
-    cull = d2m > 0.0 ? d2m / lam * 1.01 + 1e-12 : 0.0;
-  extra[9] = (float)cull;
-  if (!(extra[9] == extra[9])) extra[9] = INFINITY;
+  if (rc != CVO_OK) (void)hipStreamSynchronize(st);
+  return rc;
 }
 
 // everything cvo_depth_filter_add can refuse, before anything is written
@@ -165,7 +111,7 @@ int depth_add(cvo_depth_filter_t* df, const cvo_params_t* params, const cvo_clou
   if (df->n == 0 || frame->n == 0) return CVO_OK;  // (as cvo_association_non_isotropic: no pair)
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   float extra[10];
-  depth_kernel_extra(params, kernel_colmajor, extra);
+  noniso_extra(params, kernel_colmajor, extra);
   BatchSetup S;
   int rc = run_single_eval(ctx, params, df->kf, frame, T, 1.0f, &S, extra);
   if (rc != CVO_OK) return rc;
@@ -223,12 +169,9 @@ int depth_finish_locked(cvo_depth_filter_t* df, int min_count, std::vector<Stage
 int depth_finish(cvo_depth_filter_t* df, int min_count, cvo_cloud** out, int* kept, float* depth, int* n_kept, int* n_nonfinite) {
   const char* who = "cvo_depth_filter_finish";
   cvo_ctx* ctx = df->ctx;
-  std::vector<StagedCloud> staged;
-  const int rc = frontend_call(ctx, who, [&] { return depth_finish_locked(df, min_count, staged, kept, depth, n_kept, n_nonfinite); });
-  for (auto& sc : staged) {
-    if (rc == CVO_OK) *out = sc.c;
-    else if (sc.c) cvo_cloud_free(sc.c);  // (an exception or a failed copy left it behind)
-  }
+  const int rc = handover_call(ctx, who, out, [&](std::vector<StagedCloud>& staged) {
+    return depth_finish_locked(df, min_count, staged, kept, depth, n_kept, n_nonfinite);
+  });
   if (rc != CVO_OK) {
     if (n_kept) *n_kept = 0;
     if (n_nonfinite) *n_nonfinite = 0;
@@ -239,15 +182,16 @@ int depth_finish(cvo_depth_filter_t* df, int min_count, cvo_cloud** out, int* ke
 int depth_open(cvo_ctx* ctx, const cvo_cloud* keyframe, cvo_depth_filter_t** out, const char* who) {
   if (keyframe->n > COMPACT_MAX_ELEMENTS) return fail(ctx, CVO_E_UNSUPPORTED, std::string(who) + ": more than 2^24 rows");
   cvo_depth_filter_t* f = nullptr;
-  const int rc = frontend_call(ctx, who, [&] {
+  cvo_cloud* kf = nullptr;  // (the hand-over frame's `out` is the filter's keyframe here)
+  const int rc = handover_call(ctx, who, &kf, [&](std::vector<StagedCloud>& staged) {
     f = new cvo_depth_filter_t();
-    return depth_open_locked(ctx, keyframe, *f);
+    return depth_open_locked(ctx, keyframe, *f, staged);
   });
   if (rc != CVO_OK) {
-    if (f && f->kf) cvo_cloud_free(f->kf);
     delete f;
     return rc;
   }
+  f->kf = kf;
   *out = f;
   return CVO_OK;
 }

@@ -169,15 +169,10 @@ static double min_eig_sym3(const float a[9]) {
   return std::min(S[0][0], std::min(S[1][1], S[2][2]));
 }
 
-int cvo_association_non_isotropic(cvo_ctx* ctx, const cvo_params_t* params, const cvo_cloud* source,
-                                  const cvo_cloud* target, const float T[16], const float kernel_colmajor[9],
-                                  int* row_ptr, int* col, float* val, size_t capacity, size_t* nnz_out) {
-  if (!ctx || !params || !row_ptr || !T || !kernel_colmajor)
-    return fail(ctx, CVO_E_INVALID, "cvo_association_non_isotropic: bad argument");
-  if (!source || !target) return fail(ctx, CVO_E_INVALID, "null cloud");
-  if (nnz_out) *nnz_out = 0;
-  if (source->n == 0 || target->n == 0) return CVO_OK;  // CvoGPU.cu:1975-1976
-  float km[9], extra[10];
+// What the non-isotropic evaluation takes besides the pair (cvo_association_non_isotropic, the depth filter's add): extra[0..9) =
+// kernel_inv, row-major, of the caller's column-major kernel; extra[9] = the squared cull radius of the scan.
+static void noniso_extra(const cvo_params_t* params, const float kernel_colmajor[9], float extra[10]) {
+  float km[9];
   for (int i = 0; i < 3; i++)
     for (int j = 0; j < 3; j++) km[3 * i + j] = kernel_colmajor[3 * j + i];
   inverse3_eigen(km, extra);
@@ -195,10 +190,37 @@ int cvo_association_non_isotropic(cvo_ctx* ctx, const cvo_params_t* params, cons
     cull = d2m > 0.0 ? d2m / lam * 1.01 + 1e-12 : 0.0;
   extra[9] = (float)cull;
   if (!(extra[9] == extra[9])) extra[9] = INFINITY;
+}
+
+int cvo_association_non_isotropic(cvo_ctx* ctx, const cvo_params_t* params, const cvo_cloud* source,
+                                  const cvo_cloud* target, const float T[16], const float kernel_colmajor[9],
+                                  int* row_ptr, int* col, float* val, size_t capacity, size_t* nnz_out) {
+  if (!ctx || !params || !row_ptr || !T || !kernel_colmajor)
+    return fail(ctx, CVO_E_INVALID, "cvo_association_non_isotropic: bad argument");
+  if (!source || !target) return fail(ctx, CVO_E_INVALID, "null cloud");
+  if (nnz_out) *nnz_out = 0;
+  if (source->n == 0 || target->n == 0) return CVO_OK;  // CvoGPU.cu:1975-1976
+  float extra[10];
+  noniso_extra(params, kernel_colmajor, extra);
   BatchSetup S;
   int rc = run_single_eval(ctx, params, source, target, T, 1.0f, &S, extra);
   if (rc != CVO_OK) return rc;
   return export_association(ctx, source->n, row_ptr, col, val, capacity, nnz_out);
+}
+
+// The slot-major ELL of pair 0 as fetch_ell brought it down (N sorted rows) into the caller's arrays that are given, by original
+// row, K slots a row, in the reference's cleared layout: mat = 0, ind = -1 beyond a row's entries.
+static void ell_to_original_rows(const cvo_ctx* ctx, int N, int K, const std::vector<unsigned>& nz, const std::vector<float>& a,
+                                 const std::vector<int>& jj, float* mat, int* ind, unsigned int* nonzeros) {
+  for (int r = 0; r < N; r++) {
+    const int i = ctx->last_xorder[r];  // sorted row r holds original row i
+    if (nonzeros) nonzeros[i] = nz[r];
+    for (int s = 0; s < K; s++) {
+      const bool ok = (unsigned)s < nz[r];
+      if (mat) mat[(size_t)i * K + s] = ok ? a[(size_t)s * N + r] : 0.f;
+      if (ind) ind[(size_t)i * K + s] = ok ? jj[(size_t)s * N + r] : -1;
+    }
+  }
 }
 
 int cvo_edge_kernel_matrix(cvo_ctx* ctx, const cvo_params_t* params, const cvo_cloud* frame1, const cvo_cloud* frame2,
@@ -223,18 +245,9 @@ int cvo_edge_kernel_matrix(cvo_ctx* ctx, const cvo_params_t* params, const cvo_c
   unsigned mx = 0;
   rc = fetch_ell(ctx, 0, nz, a, jj, &mx);
   if (rc != CVO_OK) return rc;
-  const int N = frame1->n, K = num_neighbors;
+  ell_to_original_rows(ctx, frame1->n, num_neighbors, nz, a, jj, mat, ind, nonzeros);
   unsigned long long sum = 0;
-  for (int r = 0; r < N; r++) {
-    const int i = ctx->last_xorder[r];  // sorted row r holds original row i
-    if (nonzeros) nonzeros[i] = nz[r];
-    sum += nz[r];
-    for (int s2 = 0; s2 < K; s2++) {  // the reference's cleared layout: mat = 0, ind = -1 beyond the row's entries
-      const bool ok = (unsigned)s2 < nz[r];
-      if (mat) mat[(size_t)i * K + s2] = ok ? a[(size_t)s2 * N + r] : 0.f;
-      if (ind) ind[(size_t)i * K + s2] = ok ? jj[(size_t)s2 * N + r] : -1;
-    }
-  }
+  for (unsigned v : nz) sum += v;
   if (nonzero_sum) *nonzero_sum = (unsigned int)sum;
   return CVO_OK;
 }
@@ -250,16 +263,7 @@ int cvo_debug_last_ell(cvo_ctx* ctx, int K, float* mat, int* ind, unsigned int* 
   unsigned mx = 0;
   int rc = fetch_ell(ctx, 0, nz, a, jj, &mx);
   if (rc != CVO_OK) return rc;
-  const int N = ctx->h_descs[0].N;
-  for (int r = 0; r < N; r++) {
-    const int i = ctx->last_xorder[r];  // sorted row r holds original row i
-    if (nonzeros) nonzeros[i] = nz[r];
-    for (int s = 0; s < K; s++) {
-      const bool ok = (unsigned)s < nz[r];
-      if (mat) mat[(size_t)i * K + s] = ok ? a[(size_t)s * N + r] : 0.f;
-      if (ind) ind[(size_t)i * K + s] = ok ? jj[(size_t)s * N + r] : -1;
-    }
-  }
+  ell_to_original_rows(ctx, ctx->h_descs[0].N, K, nz, a, jj, mat, ind, nonzeros);
   return CVO_OK;
 }
 

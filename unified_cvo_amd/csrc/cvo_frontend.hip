@@ -86,6 +86,22 @@ int frontend_call(cvo_ctx* ctx, const char* who, Body body) {
   }
 }
 
+// THE hand-over frame of every entry point that makes resident clouds of rows on the device (cvo_cloud_from_device*, cvo_cloud_merge,
+// cvo_depth_filter_finish, cvo_cloud_from_rgbd_device*, cvo_map_cloud_resident): body(staged) under frontend_call.  CVO_OK:
+// out[q] = staged[q].c for every staged cloud.  Anything else: no out[q] is written (the entry point has nulled them) and
+// whatever `staged` still holds is freed: an exception, or a failure after the ingest, left it behind; a failed ingest or upload
+// released it itself.
+template <class Body>
+int handover_call(cvo_ctx* ctx, const char* who, cvo_cloud** out, Body body) {
+  std::vector<StagedCloud> staged;
+  const int rc = frontend_call(ctx, who, [&] { return body(staged); });
+  for (size_t q = 0; q < staged.size(); q++) {
+    if (rc == CVO_OK) out[q] = staged[q].c;
+    else if (staged[q].c) cvo_cloud_free(staged[q].c);
+  }
+  return rc;
+}
+
 // the kept indices, their number and - n_edge >= 0 - the flag of the first n_edge of them, to the caller's arrays that are given
 void copy_kept(const std::vector<int>& kept, int* out, int* n, unsigned char* is_edge = nullptr, int n_edge = -1) {
   if (out && !kept.empty()) std::memcpy(out, kept.data(), sizeof(int) * kept.size());

@@ -40,6 +40,13 @@ bool device_rows_ok(cvo_ctx* ctx, const char* what, const void* p, size_t stride
   return device_extent_ok(ctx, what, p, 4, (n_rows - 1) * stride + row_bytes, std::to_string(n_rows) + " rows", why);
 }
 
+// THE row table of rows at the fixed strides (xyz 12 bytes, geotype 8): n rows of n_records, feature rows of feat_floats and
+// label rows of label_floats floats, through `rows` where it is given.  A null attribute pointer: absent (its stride is not read).
+cvo_device_rows_t device_rows(int n, int n_records, const float* xyz, const void* feat, size_t feat_floats, const void* label, size_t label_floats,
+                              const void* geotype, const int* rows = nullptr) {
+  return cvo_device_rows_t{n, n_records, xyz, 12, feat, sizeof(float) * feat_floats, label, sizeof(float) * label_floats, geotype, 8, rows};
+}
+
 // everything the host can decide about one cvo_device_rows_t, before any launch
 int check_device_rows(cvo_ctx* ctx, const cvo_device_rows_t& d, const char* who) {
   auto bad = [&](const std::string& why) { return fail(ctx, CVO_E_INVALID, std::string(who) + ": " + why); };
@@ -238,16 +245,10 @@ int ingest_device_clouds(cvo_ctx* ctx, int n_clouds, const cvo_device_rows_t* ro
   return finish_uploads(ctx, staged);  // (on error every cloud released)
 }
 
-// the entry frame: lock, run, hand the clouds over - or none of them
+// the entry frame: the clouds of one call through THE hand-over frame (cvo_frontend.hip) - all of them, or none
 int from_device_call(cvo_ctx* ctx, int n_clouds, const cvo_device_rows_t* rows, cvo_cloud** out, const char* who) {
   for (int q = 0; q < n_clouds; q++) out[q] = nullptr;
-  std::vector<StagedCloud> staged;
-  const int rc = frontend_call(ctx, who, [&] { return ingest_device_clouds(ctx, n_clouds, rows, staged, who); });
-  for (size_t q = 0; q < staged.size(); q++) {
-    if (rc == CVO_OK) out[q] = staged[q].c;
-    else if (staged[q].c) cvo_cloud_free(staged[q].c);  // (an exception left them behind; an error return released them itself)
-  }
-  return rc;
+  return handover_call(ctx, who, out, [&](std::vector<StagedCloud>& staged) { return ingest_device_clouds(ctx, n_clouds, rows, staged, who); });
 }
 
 }  // namespace

@@ -18,17 +18,24 @@ int cloud_present(const cvo_cloud* c) {
   return (held(c, c->feat) ? HAS_FEAT : 0) | (held(c, c->label) ? HAS_LABEL : 0) | (held(c, c->geo) ? HAS_GEOTYPE : 0);
 }
 
-// The rows of `clouds` in original order, cloud after cloud, each under its pose (poses: 12 doubles per cloud, cast to
-// float as multiframe_refresh casts them, or nullptr: not moved), in the context's merge region: one k_cloud_unpack launch
-// on upload_stream, not synchronised.  *d describes them as ingest rows: xyz packed, the attributes of `want` that some cloud
-// holds at strides 32 / 80 / 8, the others null.  `jobs` is the launch's table on the host: alive until the stream has been
-// synchronised.  The caller holds upload_mutex; the clouds are the context's and hold `total` <= 2^24 rows together.
-int unpack_clouds(cvo_ctx* ctx, int n_clouds, const cvo_cloud* const* clouds, const double* poses, int want, int total,
-                  std::vector<UnpackJob>& jobs, cvo_device_rows_t* d) {
-  *d = cvo_device_rows_t{};
+// THE list of unpacked rows (k_cloud_unpack's padded rows, original order): nn rows of the coordinates and of the attributes
+// `present` names, for a region's typed walk.  The arrays it does not name stay null.
+void unpacked_rows_list(ScratchLayout& l, int present, size_t nn, float*& xyz, float4*& feat, float4*& label, float2*& geo) {
+  l.take(xyz, 3 * nn);
+  if (present & HAS_FEAT) l.take(feat, FD_PAD / 4 * nn);
+  if (present & HAS_LABEL) l.take(label, NC_PAD / 4 * nn);
+  if (present & HAS_GEOTYPE) l.take(geo, nn);
+}
+
+// THE unpack: the rows of the non-empty clouds of `clouds` in original order, cloud after cloud, each under its pose (poses: 12
+// doubles per cloud, cast to float as multiframe_refresh casts them, or nullptr: not moved), into o's arrays (a null attribute
+// array: not wanted): the job table copied to d_jobs (room for a job per non-empty cloud), one k_cloud_unpack launch on
+// upload_stream, not synchronised.  `jobs` is the table on the host: alive until the stream has been synchronised.  The caller
+// holds upload_mutex; the clouds are the context's and hold o.total in 1 .. 2^24 rows together.
+int unpack_launch(cvo_ctx* ctx, int n_clouds, const cvo_cloud* const* clouds, const double* poses, std::vector<UnpackJob>& jobs, UnpackJob* d_jobs,
+                  UnpackOut o) {
   jobs.clear();
-  if (total == 0) return CVO_OK;
-  int any = 0, base = 0;
+  int base = 0;
   for (int q = 0; q < n_clouds; q++) {
     const cvo_cloud* c = clouds[q];
     if (c->n == 0) continue;  // (no job: the first rows of the table stay strictly ascending)
@@ -42,37 +49,39 @@ int unpack_clouds(cvo_ctx* ctx, int n_clouds, const cvo_cloud* const* clouds, co
     j.feat = held(c, c->feat);
     j.label = held(c, c->label);
     j.geo = held(c, c->geo);
-    any |= cloud_present(c);
     jobs.push_back(j);
     base += c->n;
   }
-  any &= want;
-  UnpackJob* d_jobs = nullptr;
-  UnpackOut o{};
   o.n_jobs = (int)jobs.size();
-  o.total = total;
-  const size_t nn = (size_t)total;
-  const int rc = ctx->merge_scratch.lay_out(ctx, "merge scratch", [&](ScratchLayout& l) {
-    l.take(d_jobs, jobs.size());
-    l.take(o.xyz, 3 * nn);
-    if (any & HAS_FEAT) l.take(o.feat, FD_PAD / 4 * nn);
-    if (any & HAS_LABEL) l.take(o.label, NC_PAD / 4 * nn);
-    if (any & HAS_GEOTYPE) l.take(o.geo, nn);
-  });
-  if (rc != CVO_OK) return rc;
   HIP_TRY(ctx, hipMemcpyAsync(d_jobs, jobs.data(), sizeof(UnpackJob) * jobs.size(), hipMemcpyHostToDevice, ctx->upload_stream));
-  const int grid = std::min((total + UNPACK_THREADS - 1) / UNPACK_THREADS, UNPACK_MAX_BLOCKS);
+  const int grid = std::min((o.total + UNPACK_THREADS - 1) / UNPACK_THREADS, UNPACK_MAX_BLOCKS);
   hipLaunchKernelGGL(k_cloud_unpack, dim3((unsigned)grid), dim3(UNPACK_THREADS), 0, ctx->upload_stream, (const UnpackJob*)d_jobs, o);
   HIP_TRY(ctx, hipGetLastError());
-  d->n = d->n_records = total;
-  d->xyz = o.xyz;
-  d->xyz_stride = 12;
-  d->feat = o.feat;
-  d->feat_stride = sizeof(float) * FD_PAD;
-  d->label = o.label;
-  d->label_stride = sizeof(float) * NC_PAD;
-  d->geotype = o.geo;
-  d->geotype_stride = 8;
+  return CVO_OK;
+}
+
+// The rows of `clouds` (`total` of them together) unpacked into the context's merge region.  *d describes them as ingest rows:
+// xyz packed, the attributes of `want` that some cloud holds at strides 32 / 80 / 8, the others null.  jobs: see unpack_launch.
+int unpack_clouds(cvo_ctx* ctx, int n_clouds, const cvo_cloud* const* clouds, const double* poses, int want, int total,
+                  std::vector<UnpackJob>& jobs, cvo_device_rows_t* d) {
+  *d = cvo_device_rows_t{};
+  jobs.clear();
+  if (total == 0) return CVO_OK;
+  int any = 0, n_jobs = 0;
+  for (int q = 0; q < n_clouds; q++) {
+    any |= cloud_present(clouds[q]);
+    n_jobs += clouds[q]->n > 0 ? 1 : 0;
+  }
+  UnpackJob* d_jobs = nullptr;
+  UnpackOut o{};
+  o.total = total;
+  int rc = ctx->merge_scratch.lay_out(ctx, "merge scratch", [&](ScratchLayout& l) {
+    l.take(d_jobs, (size_t)n_jobs);
+    unpacked_rows_list(l, any & want, (size_t)total, o.xyz, o.feat, o.label, o.geo);
+  });
+  if (rc != CVO_OK) return rc;
+  if ((rc = unpack_launch(ctx, n_clouds, clouds, poses, jobs, d_jobs, o)) != CVO_OK) return rc;
+  *d = device_rows(total, total, o.xyz, o.feat, FD_PAD, o.label, NC_PAD, o.geo);
   return CVO_OK;
 }
 
@@ -156,12 +165,9 @@ int cvo_cloud_merge(cvo_ctx* ctx, int n_clouds, const cvo_cloud* const* clouds, 
     total += clouds[q]->n;
   }
   if (total > COMPACT_MAX_ELEMENTS) return fail(ctx, CVO_E_UNSUPPORTED, std::string(who) + ": more than 2^24 rows in total");
-  std::vector<StagedCloud> staged;
-  const int rc = frontend_call(ctx, who, [&] { return merge_locked(ctx, n_clouds, clouds, poses, voxel_size, (int)total, staged, kept, n_kept); });
-  for (auto& sc : staged) {
-    if (rc == CVO_OK) *out = sc.c;
-    else if (sc.c) cvo_cloud_free(sc.c);  // (an exception left it behind; an error return released it itself)
-  }
+  const int rc = handover_call(ctx, who, out, [&](std::vector<StagedCloud>& staged) {
+    return merge_locked(ctx, n_clouds, clouds, poses, voxel_size, (int)total, staged, kept, n_kept);
+  });
   if (rc != CVO_OK && n_kept) *n_kept = 0;
   return rc;
 }

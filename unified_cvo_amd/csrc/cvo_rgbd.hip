@@ -397,20 +397,74 @@ unsigned long long rgbd_count_depth(const cvo_rgbd_frame_t& f) {
   return c;
 }
 
-int rgbd_points_device(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, int method, std::vector<int>& pix, RgbdStatsAcc& st) {
-  RgbdDevice d;
-  int rc = rgbd_device_stage(ctx, f, method == CVO_SELECT_DSO_EDGES, d);
+// ---- THE device candidate chain of both RGB-D routes, over a back-projection policy with two operations:
+//   run(d, list, n, at, n_out, full)   the candidates list[0 .. n) (nullptr: every pixel) into d.pix / d.xyz from `at`; full: the FULL pass
+//   with_depth(d, n_full)              the pixels of the frame with a depth, asked once the FULL pass has kept n_full
+
+// a host frame (staged by rgbd_device_stage): the exclusion plane the host made hides pixels from the pass, and then from its count
+struct RgbdHostFramePolicy {
+  cvo_ctx* ctx;
+  const cvo_rgbd_frame_t& f;
+  int run(RgbdDevice& d, const int* list, int n, int at, int* n_out, bool) { return rgbd_device_backproject(ctx, f, d, list, n, at, n_out); }
+  unsigned long long with_depth(const RgbdDevice& d, int n_full) const { return d.excl ? rgbd_count_depth(f) : (unsigned long long)n_full; }
+};
+
+// a device frame (read in place): the class scores' rule runs in keep(), and the FULL pass of a frame with classes counts the depths itself
+struct RgbdDeviceFramePolicy {
+  cvo_ctx* ctx;
+  const cvo_rgbd_frame_t& view;
+  const RgbdScores& scores;
+  unsigned long long counted = 0;
+  int run(RgbdDevice& d, const int* list, int n, int at, int* n_out, bool full) {
+    return rgbd_device_backproject_scores(ctx, view, scores, d, list, n, at, n_out, full && scores.classes > 0 ? &counted : nullptr);
+  }
+  unsigned long long with_depth(const RgbdDevice&, int n_full) const { return scores.classes > 0 ? counted : (unsigned long long)n_full; }
+};
+
+// the stats of a call that ran the chain: n_edge edge candidates and n_full FULL ones kept (-1: that pass did not run)
+template <class Policy>
+void rgbd_chain_stats(RgbdStatsAcc& st, const Policy& bp, const RgbdDevice& d, int n_edge, int n_full) {
+  st.on_device = 1;
+  if (n_edge >= 0) st.edge_points = (unsigned long long)n_edge;
+  if (n_full < 0) return;
+  st.surface_points = (unsigned long long)n_full;
+  st.with_depth = bp.with_depth(d, n_full);
+}
+
+// the points of a method: stage -> select (the DSO edges) -> back-project -> stats; *kept pixel indices are in d.pix
+template <class Policy>
+int rgbd_points_chain(cvo_ctx* ctx, const cvo_rgbd_frame_t& view, bool planes_on_device, int method, Policy bp, RgbdDevice& d, RgbdStatsAcc& st,
+                      int* kept) {
+  const bool full = method == CVO_SELECT_FULL;
+  int rc = rgbd_device_stage(ctx, view, method == CVO_SELECT_DSO_EDGES, d, false, planes_on_device);
   if (rc != CVO_OK) return rc;
   const int* list = nullptr;
-  int n = f.cols * f.rows, kept = 0;
+  int n = view.cols * view.rows;
   if (method == CVO_SELECT_DSO_EDGES && (rc = rgbd_device_select(ctx, d, st, &list, &n)) != CVO_OK) return rc;
-  if ((rc = rgbd_device_backproject(ctx, f, d, list, n, 0, &kept)) != CVO_OK) return rc;
-  if (method == CVO_SELECT_FULL) {
-    st.surface_points = (unsigned long long)kept;
-    st.with_depth = d.excl ? rgbd_count_depth(f) : (unsigned long long)kept;
-  } else {
-    st.edge_points = (unsigned long long)kept;
-  }
+  if ((rc = bp.run(d, list, n, 0, kept, full)) != CVO_OK) return rc;
+  rgbd_chain_stats(st, bp, d, full ? -1 : *kept, full ? *kept : -1);
+  return CVO_OK;
+}
+
+// the recipe's device_pass (recipe_pixels): the selection, then both back-projections - edges from 0, FULL from *n_e - and the stats
+template <class Policy>
+auto rgbd_device_pass(cvo_ctx* ctx, int n_pixels, Policy bp, RgbdStatsAcc& st) {
+  return [ctx, n_pixels, bp, &st](RgbdDevice& d, int* n_e, int* n_s) mutable {
+    const int* list = nullptr;
+    int n_sel = 0, rc;
+    if ((rc = rgbd_device_select(ctx, d, st, &list, &n_sel)) != CVO_OK) return rc;
+    if ((rc = bp.run(d, list, n_sel, 0, n_e, false)) != CVO_OK) return rc;
+    if ((rc = bp.run(d, nullptr, n_pixels, *n_e, n_s, true)) != CVO_OK) return rc;
+    rgbd_chain_stats(st, bp, d, *n_e, *n_s);
+    return (int)CVO_OK;
+  };
+}
+
+int rgbd_points_device(cvo_ctx* ctx, const cvo_rgbd_frame_t& f, int method, std::vector<int>& pix, RgbdStatsAcc& st) {
+  RgbdDevice d;
+  int kept = 0;
+  const int rc = rgbd_points_chain(ctx, f, false, method, RgbdHostFramePolicy{ctx, f}, d, st, &kept);
+  if (rc != CVO_OK) return rc;
   return rgbd_fetch(ctx, d.pix, kept, pix);
 }
 
@@ -481,25 +535,14 @@ int recipe_pixels(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t& view, b
 // the recipe of an RGB-D frame
 int rgbd_recipe_pixels(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t& f, float leaf, float divisor, std::vector<int>& pix, int* n_edge,
                        RgbdStatsAcc& st) {
-  st.on_device = rgbd_on_host(ctx, f) ? 0 : 1;
   return recipe_pixels(
-      ctx, who, f, !st.on_device, leaf, divisor, pix, nullptr, n_edge,
+      ctx, who, f, rgbd_on_host(ctx, f), leaf, divisor, pix, nullptr, n_edge,
       [&](int method, std::vector<int>& cand, std::vector<float>& cxyz) {
         rgbd_candidates_cpu(f, method, cand, st);
         cxyz.resize(3 * cand.size());
         for (size_t i = 0; i < cand.size(); i++) rgbd_xyz(f, cand[i], &cxyz[3 * i]);
       },
-      [&](RgbdDevice& d, int* n_e, int* n_s) {
-        const int* list = nullptr;
-        int n_sel = 0, rc;
-        if ((rc = rgbd_device_select(ctx, d, st, &list, &n_sel)) != CVO_OK) return rc;
-        if ((rc = rgbd_device_backproject(ctx, f, d, list, n_sel, 0, n_e)) != CVO_OK) return rc;
-        if ((rc = rgbd_device_backproject(ctx, f, d, nullptr, f.cols * f.rows, *n_e, n_s)) != CVO_OK) return rc;
-        st.edge_points = (unsigned long long)*n_e;
-        st.surface_points = (unsigned long long)*n_s;
-        st.with_depth = d.excl ? rgbd_count_depth(f) : (unsigned long long)*n_s;
-        return CVO_OK;
-      });
+      rgbd_device_pass(ctx, f.cols * f.rows, RgbdHostFramePolicy{ctx, f}, st));
 }
 
 // a successful RGB-D call's last statement: its stats stand, and one that took the host route leaves no stages to read back
@@ -526,7 +569,6 @@ int rgbd_points_entry(cvo_ctx* ctx, const char* who, const cvo_rgbd_frame_t* fra
     if (!ctx || rgbd_on_host(ctx, *frame)) {
       rgbd_candidates_cpu(*frame, method, pix, st);
     } else {
-      st.on_device = 1;
       const int rc = rgbd_points_device(ctx, *frame, method, pix, st);
       if (rc != CVO_OK) return rc;
     }
@@ -633,16 +675,7 @@ int rgbd_device_cloud(cvo_ctx* ctx, const char* who, const RgbdRowFrame& rf, con
     HIP_TRY(ctx, hipGetLastError());
     if (pixel) HIP_TRY(ctx, hipMemcpyAsync(pixel, d_pix, sizeof(int) * nn, hipMemcpyDeviceToHost, st));
   }
-  cvo_device_rows_t r{};
-  r.n = r.n_records = n;
-  r.xyz = o.xyz;
-  r.xyz_stride = 12;
-  r.feat = o.feat;
-  r.feat_stride = sizeof(float) * FD;
-  r.label = o.label;
-  r.label_stride = sizeof(float) * NC;
-  r.geotype = o.geo;
-  r.geotype_stride = 8;
+  const cvo_device_rows_t r = device_rows(n, n, o.xyz, o.feat, FD, o.label, NC, o.geo);
   const int rc = ingest_device_clouds(ctx, 1, &r, staged, who);  // (synchronises upload_stream; on error the cloud is released)
   if (rc != CVO_OK || n == 0) (void)hipStreamSynchronize(st);     // (nothing of this call is in flight when it returns)
   return rc;
@@ -664,22 +697,10 @@ int rgbd_from_device_points(cvo_ctx* ctx, const char* who, const cvo_rgbd_device
   const cvo_rgbd_frame_t view = rgbd_device_view(f);
   const RgbdRowFrame rf = rgbd_device_row_frame(f);
   RgbdStatsAcc st;
-  st.on_device = 1;
   RgbdDevice d;
-  int rc = rgbd_device_stage(ctx, view, method == CVO_SELECT_DSO_EDGES, d, false, true);
+  int kept = 0;
+  int rc = rgbd_points_chain(ctx, view, true, method, RgbdDeviceFramePolicy{ctx, view, rf.scores}, d, st, &kept);
   if (rc != CVO_OK) return rc;
-  const int* list = nullptr;
-  int n = f.cols * f.rows, kept = 0;
-  if (method == CVO_SELECT_DSO_EDGES && (rc = rgbd_device_select(ctx, d, st, &list, &n)) != CVO_OK) return rc;
-  unsigned long long with_depth = 0;
-  const bool count = method == CVO_SELECT_FULL && f.num_classes > 0;
-  if ((rc = rgbd_device_backproject_scores(ctx, view, rf.scores, d, list, n, 0, &kept, count ? &with_depth : nullptr)) != CVO_OK) return rc;
-  if (method == CVO_SELECT_FULL) {
-    st.surface_points = (unsigned long long)kept;
-    st.with_depth = count ? with_depth : (unsigned long long)kept;
-  } else {
-    st.edge_points = (unsigned long long)kept;
-  }
   if ((rc = rgbd_device_cloud(ctx, who, rf, rgbd_constructor_rows(method), d.pix, kept, 0, pixel, staged)) != CVO_OK) return rc;
   if (n_out) *n_out = kept;
   rgbd_commit(ctx, st);
@@ -694,41 +715,16 @@ int rgbd_from_device_recipe(cvo_ctx* ctx, const char* who, const cvo_rgbd_device
   const cvo_rgbd_frame_t view = rgbd_device_view(f);
   const RgbdRowFrame rf = rgbd_device_row_frame(f);
   RgbdStatsAcc st;
-  st.on_device = 1;
   RgbdDevice d;
   int n_edge = 0, total = 0;
-  int rc = recipe_pixels_device(ctx, who, view, true, leaf, leaf / divisor, d, &n_edge, &total, [&](RgbdDevice& dd, int* n_e, int* n_s) {
-    const int* list = nullptr;
-    int n_sel = 0, rc2;
-    unsigned long long with_depth = 0;
-    const bool count = f.num_classes > 0;
-    if ((rc2 = rgbd_device_select(ctx, dd, st, &list, &n_sel)) != CVO_OK) return rc2;
-    if ((rc2 = rgbd_device_backproject_scores(ctx, view, rf.scores, dd, list, n_sel, 0, n_e, nullptr)) != CVO_OK) return rc2;
-    if ((rc2 = rgbd_device_backproject_scores(ctx, view, rf.scores, dd, nullptr, f.cols * f.rows, *n_e, n_s, count ? &with_depth : nullptr)) != CVO_OK)
-      return rc2;
-    st.edge_points = (unsigned long long)*n_e;
-    st.surface_points = (unsigned long long)*n_s;
-    st.with_depth = count ? with_depth : (unsigned long long)*n_s;
-    return (int)CVO_OK;
-  });
+  int rc = recipe_pixels_device(ctx, who, view, true, leaf, leaf / divisor, d, &n_edge, &total,
+                                rgbd_device_pass(ctx, f.cols * f.rows, RgbdDeviceFramePolicy{ctx, view, rf.scores}, st));
   if (rc != CVO_OK) return rc;
   if ((rc = rgbd_device_cloud(ctx, who, rf, RgbdRowKind{1, 0.f, 0.f}, d.out, total, n_edge, pixel, staged)) != CVO_OK) return rc;
   if (n_out) *n_out = total;
   if (n_edge_out) *n_edge_out = n_edge;
   rgbd_commit(ctx, st);
   return CVO_OK;
-}
-
-// the frame of both entry points: *out NULL unless the call succeeds
-template <class Body>
-int rgbd_from_device_call(cvo_ctx* ctx, const char* who, cvo_cloud** out, Body body) {
-  std::vector<StagedCloud> staged;
-  const int rc = frontend_call(ctx, who, [&] { return body(staged); });
-  for (auto& sc : staged) {
-    if (rc == CVO_OK) *out = sc.c;
-    else if (sc.c) cvo_cloud_free(sc.c);  // (an exception left it behind; an error return released it itself)
-  }
-  return rc;
 }
 
 }  // namespace
@@ -793,7 +789,7 @@ int cvo_cloud_from_rgbd_device(cvo_ctx* ctx, const cvo_rgbd_device_frame_t* fram
     msg = "out is NULL";
   }
   if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
-  return rgbd_from_device_call(ctx, who, out, [&](std::vector<StagedCloud>& staged) { return rgbd_from_device_points(ctx, who, *frame, method, pixel, n, staged); });
+  return handover_call(ctx, who, out, [&](std::vector<StagedCloud>& staged) { return rgbd_from_device_points(ctx, who, *frame, method, pixel, n, staged); });
 }
 
 int cvo_cloud_from_rgbd_device_recipe(cvo_ctx* ctx, const cvo_rgbd_device_frame_t* frame, float leaf, float edge_divisor, cvo_cloud** out, int* n,
@@ -822,7 +818,7 @@ int cvo_cloud_from_rgbd_device_recipe(cvo_ctx* ctx, const cvo_rgbd_device_frame_
     msg = "leaf / edge_divisor: " + msg;
   }
   if (rc != CVO_OK) return fail(ctx, rc, std::string(who) + ": " + msg);
-  return rgbd_from_device_call(ctx, who, out, [&](std::vector<StagedCloud>& staged) {
+  return handover_call(ctx, who, out, [&](std::vector<StagedCloud>& staged) {
     return rgbd_from_device_recipe(ctx, who, *frame, leaf, edge_divisor, pixel, n, n_edge, staged);
   });
 }
